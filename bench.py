@@ -3,18 +3,26 @@
 variant x cell matrix resident in HBM.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+          [--full] [--dump-outputs DIR]
 
 A step = one EM iteration over the whole matrix: alpha/beta update, per-cell log-likelihood pass (with the
 reference's expected-log-pmf column), exact median/quartiles over all cells, exclusion flags, per-locus
 statistics pass, locus filter.  Cells are sharded across ranks (strong scaling: the matrix is fixed, BASELINE
 cfg4 = 1M cells x 200k loci at 1%); the two exchanges per iteration are all-reduces over RCCL.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (with the roofline of the dominant kernel,
+whose events are recorded inside the timed region).  --full adds what takes runs of its own: the timed loop four more
+times, a per-kernel breakdown, the posterior phase, the CPU baseline and the ranks' agreement check.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -57,7 +65,45 @@ def parse():
                     help="extra cellector_set_option pairs (ablations), e.g. --opt overlap=1")
     ap.add_argument("--no-expected", action="store_true",
                     help="skip the expected_log_likelihood diagnostic column (NOT the reference-equivalent step)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: repeats of the timed loop, per-kernel breakdown, "
+                         "posterior phase, CPU baseline, ranks' agreement check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, g, last, gather_cells, write):
+    """What a caller of the timed path receives after its last step, as DIR/<name>.npy (every rank takes part in the
+    gathers of the per-cell arrays, which come out in global cell order; the rank with `write` writes):
+      iteration_summary  the step's IterSummary: any_change, n_new_excluded, n_rescued, n_excluded, n_loci_filtered,
+                         median, iqr, threshold, n_near_threshold
+      cell_*             ll, expected_ll, loci_used, normalized (cellector_iter_cell_outputs), excluded (0/1)
+      locus_*            contrib_min / contrib_maj, cells / alt / ref tallies of the minority and the majority
+                         (cellector_iter_locus_outputs), mask (0/1, cellector_loci_mask)
+    Counts are exact in float64 (float32 for the 0/1 flags).  cfg4 writes ~50 MB."""
+    summary = np.array([float(getattr(last, f)) for f, _ in last._fields_], np.float64)
+    arrays = {"iteration_summary": summary}
+    for k, v in g.cell_outputs().items():
+        arrays["cell_" + k] = gather_cells(v.astype(np.float64))
+    arrays["cell_excluded"] = gather_cells(g.excluded().astype(np.float64)).astype(np.float32)
+    for k, v in g.locus_outputs().items():
+        arrays["locus_" + k] = v.astype(np.float64)
+    arrays["locus_mask"] = g.loci_mask().astype(np.float32)
+    if not write:
+        return
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def roofline(args, kernel, launch_ms, units, b_alg, achieved, traffic, traffic_src, layout_bytes, lds_lookup_bytes,
@@ -100,7 +146,6 @@ def roofline(args, kernel, launch_ms, units, b_alg, achieved, traffic, traffic_s
 
 def main():
     args = parse()
-    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -259,57 +304,82 @@ def main():
     allreduce(el, dist.ReduceOp.MAX)
     elapsed = float(el.item())
     ms_per_step = elapsed / args.steps * 1e3
-    # the same K-step loop four more times (reported beside the headline, which stays the FIRST loop's elapsed / K): a timed
-    # region of tens of milliseconds moves by percent with one queue hiccup, and min / median make that visible
-    repeats = [ms_per_step]
-    for _ in range(4):
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        e1 = torch.tensor([time.perf_counter() - t1], dtype=torch.float64, device=dev)
-        allreduce(e1, dist.ReduceOp.MAX)
-        repeats.append(float(e1.item()) / args.steps * 1e3)
-    # every rank ran the same exact selection on the same all-gathered keys and saw the same all-reduced counters: the
-    # iteration summaries must agree to the bit (checked, reported in the line)
-    ranks_agree = True
-    if world > 1:
-        mine = torch.tensor([last.threshold, last.median, last.iqr, float(last.n_excluded), float(last.any_change)],
-                            dtype=torch.float64, device=dev)
-        lo, hi = mine.clone(), mine.clone()
-        allreduce(lo, dist.ReduceOp.MIN)
-        allreduce(hi, dist.ReduceOp.MAX)
-        ranks_agree = bool(torch.equal(lo, hi))
-
     # ---- the dominant kernel's duration: HIP events on the launch stream, recorded inside the timed region
     dom_id = ffi.K_TILE_LL if args.engine == 2 else ffi.K_CELL_LL
     dom_total_ms, dom_n = g.kernel_time(dom_id)
-    # ---- the other groups of kernels (breakdown only): the same steps once more, untimed, with every event pair on
-    g.set_option("timing", 1)
-    g.reset_timing()
-    for _ in range(args.steps):
-        step()
-    fence()
-    g.set_option("timing", 0)
-    ll_ms, ll_n = g.kernel_time(ffi.K_CELL_LL)
-    lo_ms, lo_n = g.kernel_time(ffi.K_LOCUS_STATS)
-    se_ms, se_n = g.kernel_time(ffi.K_SELECT)
-    ti_ms, ti_n = g.kernel_time(ffi.K_TILE_LL)
-    ll_avg = ll_ms / max(ll_n, 1)
     n_loc = ce - cb
-    # ---- the posterior phase (phases are timed separately): calculate_posteriors = three log-likelihood passes
-    # with three alpha/beta sets over all loci + the per-cell finalize, on the device (no output copies) and as the host sees
-    # it (4 x 8 B per cell copied back); untimed for the headline figure
-    post_ms = {}
-    for name, fetch in (("device", False), ("with_output_copy", True)):
-        g.posteriors(fetch=fetch)
+
+    def gather_cells(a):
+        # the ranks' contiguous cell slices (each padded to `per`) in global cell order
+        if world == 1:
+            return a
+        t = torch.zeros(per, dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+        t[:len(a)] = torch.from_numpy(a)
+        parts = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(parts, t)
+        return torch.cat(parts)[:N].cpu().numpy()
+
+    if args.dump_outputs:  # (before --full runs more steps: they move the state on)
+        dump_outputs(args.dump_outputs, g, last, gather_cells, rank == 0)
+
+    if args.full:
+        # the same K-step loop four more times (reported beside the headline, which stays the FIRST loop's elapsed / K): a timed
+        # region of tens of milliseconds moves by percent with one queue hiccup, and min / median make that visible
+        repeats = [ms_per_step]
+        for _ in range(4):
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            e1 = torch.tensor([time.perf_counter() - t1], dtype=torch.float64, device=dev)
+            allreduce(e1, dist.ReduceOp.MAX)
+            repeats.append(float(e1.item()) / args.steps * 1e3)
+        # every rank ran the same exact selection on the same all-gathered keys and saw the same all-reduced counters: the
+        # iteration summaries must agree to the bit (checked, reported in the line)
+        ranks_agree = True
+        if world > 1:
+            mine = torch.tensor([last.threshold, last.median, last.iqr, float(last.n_excluded), float(last.any_change)],
+                                dtype=torch.float64, device=dev)
+            lo, hi = mine.clone(), mine.clone()
+            allreduce(lo, dist.ReduceOp.MIN)
+            allreduce(hi, dist.ReduceOp.MAX)
+            ranks_agree = bool(torch.equal(lo, hi))
+
+        # ---- the other groups of kernels (breakdown only): the same steps once more, untimed, with every event pair on
+        g.set_option("timing", 1)
+        g.reset_timing()
+        for _ in range(args.steps):
+            step()
         fence()
-        t1 = time.perf_counter()
-        for _ in range(3):
+        g.set_option("timing", 0)
+        ll_ms, ll_n = g.kernel_time(ffi.K_CELL_LL)
+        lo_ms, lo_n = g.kernel_time(ffi.K_LOCUS_STATS)
+        se_ms, se_n = g.kernel_time(ffi.K_SELECT)
+        ti_ms, ti_n = g.kernel_time(ffi.K_TILE_LL)
+        ll_avg = ll_ms / max(ll_n, 1)
+        # ---- the posterior phase (phases are timed separately): calculate_posteriors = three log-likelihood passes
+        # with three alpha/beta sets over all loci + the per-cell finalize, on the device (no output copies) and as the host sees
+        # it (4 x 8 B per cell copied back); untimed for the headline figure
+        post_ms = {}
+        for name, fetch in (("device", False), ("with_output_copy", True)):
             g.posteriors(fetch=fetch)
-        fence()
-        post_ms[name] = (time.perf_counter() - t1) / 3 * 1e3
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(3):
+                g.posteriors(fetch=fetch)
+            fence()
+            post_ms[name] = (time.perf_counter() - t1) / 3 * 1e3
+        full = {
+            "ms_per_step_repeats": {"n": len(repeats), "min": min(repeats), "median": sorted(repeats)[len(repeats) // 2],
+                                    "all": repeats, "note": "the K-step loop five times; ms_per_step is the first"},
+            "posterior_phase_ms": post_ms,
+            "kernels_ms_note": "breakdown from a second, untimed run of the same steps with every event pair recorded; "
+                               "roofline.launch_ms is from the timed region",
+            "kernels_ms": {"cell_pass": ll_avg, "tile_ll": ti_ms / max(ti_n, 1), "locus_pass": lo_ms / max(lo_n, 1),
+                           "select": se_ms / max(se_n, 1)},
+            "ll_pass_evals_per_s": nnz_local * world / (ll_avg * 1e-3) if ll_avg > 0 else None,
+        }
     info = g.engine_info()
     # Dominant kernel and the entries ONE launch of it processes on this rank:
     #   engine 2: k_tile_ll, the regular entries (1 <= alt+ref <= 4); engine 1: k_cell_ll, all entries.
@@ -362,8 +432,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            "ms_per_step_repeats": {"n": len(repeats), "min": min(repeats), "median": sorted(repeats)[len(repeats) // 2],
-                                    "all": repeats, "note": "the K-step loop five times; ms_per_step is the first"},
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -384,23 +452,21 @@ def main():
                                       + (f"; {comm_note}" if comm_note else "")},
             "em_iters_per_s": args.steps / elapsed,
             "dense_cells_x_loci_per_s": float(N) * float(L) / (elapsed / args.steps),
-            "posterior_phase_ms": post_ms,
-            "kernels_ms_note": "breakdown from a second, untimed run of the same steps with every event pair recorded; "
-                               "roofline.launch_ms is from the timed region",
-            "kernels_ms": {"cell_pass": ll_avg, "tile_ll": ti_ms / max(ti_n, 1), "locus_pass": lo_ms / max(lo_n, 1),
-                           "select": se_ms / max(se_n, 1)},
-            "ll_pass_evals_per_s": nnz_local * world / (ll_avg * 1e-3) if ll_avg > 0 else None,
             "roofline": roofline(args, dom_kernel, dom_ms, dom_units, b_pass, achieved, traffic, traffic_src, layout_bytes,
                                  lds_lookup_bytes, lds_stage_bytes, lds_peak_gbs, sq),
             "engine": {"engine": args.engine, "nnz_regular": int(info.nnz_regular),
                        "nnz_overflow": int(info.nnz_overflow), "tile_bytes": int(info.tile_bytes)},
             "setup_s": t_setup,
             "last_iteration": {"n_excluded": int(last.n_excluded), "threshold": last.threshold,
-                               "any_change": int(last.any_change), "ranks_agree": ranks_agree},
+                               "any_change": int(last.any_change)},
+            "full": args.full,
         }
+        if args.full:
+            out["last_iteration"]["ranks_agree"] = ranks_agree
+            out.update(full)
 
     # ---- CPU baseline: the oracle (port of the reference's single-threaded path) on a bounded cell sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import binding as ob
         avg_row = max(1.0, nnz_local / max(n_loc, 1))
         n_sample = int(max(1, min(n_loc, args.cpu_sample_entries / avg_row)))
@@ -430,7 +496,7 @@ def main():
             out["cpu_baseline_all_cores"] = {"value": float(len(ent)) / cpu_mt, "unit": "evals/s", "cores": nt, "kind": "port",
                                              "sample": f"same sample, per-cell loop on {nt} threads (OpenMP), {cpu_mt:.2f} s"}
         o.close()
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
 
     if rank == 0:

@@ -15,7 +15,9 @@ def _declared():
 
 
 def test_every_declared_symbol_is_exported_and_bound(hip_lib_path):
-    lib = ctypes.CDLL(hip_lib_path)
+    # through the package's loader, which loads torch's HIP runtime first: a bare dlopen here would bind the system's copy
+    # and leave two runtimes in the process, so that the GPU tests run after this one find no device
+    lib = ffi.load_library(hip_lib_path)
     names = _declared()
     assert len(names) >= 30
     for n in names:

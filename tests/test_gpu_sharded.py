@@ -385,7 +385,8 @@ def test_sharded_order_statistics_on_adversarial_keys(oracle_lib, hip_lib_path):
 
 
 def test_bench_contract_on_cfg1():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", "3", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -397,3 +398,51 @@ def test_bench_contract_on_cfg1():
     assert set(d["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"} and d["roofline"]["bound"] == "lds" and d["roofline"]["hbm_frac_layout"] > 0 and d["roofline"]["lds"]["frac"] > 0
     assert d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
     assert "workload" in d["config"] and "model" not in d["config"]
+    assert d["full"] is True and d["ms_per_step_repeats"]["n"] == 5 and set(d["kernels_ms"]) >= {"tile_ll", "locus_pass", "select"}
+    assert set(d["posterior_phase_ms"]) == {"device", "with_output_copy"} and d["last_iteration"]["ranks_agree"] is True
+
+
+def test_bench_plain_run_and_dump_outputs_on_cfg1(hip_lib_path, tmp_path):
+    """A plain run times exactly --steps steps and prints the headline without what --full adds; --dump-outputs writes what
+    the last timed step computed: the library's outputs after warmup + steps iterations on the same generated matrix."""
+    from cellector_amd import Cellector
+    steps, warmup, out_dir = 4, 2, tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["full"] is False and d["dtype"] == "f64"
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(d["config"]["nnz_used"] / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    for k in ("ms_per_step_repeats", "kernels_ms", "posterior_phase_ms", "cpu_baseline", "ll_pass_evals_per_s"):
+        assert k not in d, k
+    got = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64_000_000
+    # the same path in this process: bench.py's options and generator arguments for cfg1 (1000 cells x 2000 loci, 10 %)
+    N, L_total = 1000, 2000
+    with Cellector(0) as g:
+        for k, v in (("keep_coo", 0), ("engine", 2), ("compute_expected", 1), ("synth_continue_pct", 30)):
+            g.set_option(k, v)
+        g.set_shard(0, N)
+        g.set_option("norm_zero", 0)
+        g.ingest_synthetic(L_total, N, 0.10, seed=4, minority_fraction=0.05, doublet_fraction=0.0)
+        g.ingest_finish(4, 4)
+        for _ in range(warmup + steps):
+            s = g.em_iteration(5.0)
+        want = {"iteration_summary": np.array([float(getattr(s, f)) for f, _ in s._fields_])}
+        want.update({"cell_" + k: v for k, v in g.cell_outputs().items()})
+        want["cell_excluded"] = g.excluded()
+        want.update({"locus_" + k: v for k, v in g.locus_outputs().items()})
+        want["locus_mask"] = g.loci_mask()
+    assert set(got) == set(want)
+    assert d["last_iteration"]["n_excluded"] == int(want["iteration_summary"][3])
+    counts = [0, 1, 2, 3, 4, 8]  # the summary's integer fields; 5-7 are median, iqr, threshold
+    assert np.array_equal(got["iteration_summary"][counts], want["iteration_summary"][counts])
+    assert np.allclose(got["iteration_summary"], want["iteration_summary"], rtol=1e-12, atol=1e-12)
+    for k, w in want.items():
+        assert got[k].shape == w.shape, k
+        if w.dtype.kind in "ui" or k == "cell_loci_used":
+            assert np.array_equal(got[k], w.astype(np.float64)), k
+        else:
+            assert np.allclose(got[k], w, rtol=1e-12, atol=1e-12), k

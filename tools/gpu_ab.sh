@@ -8,7 +8,7 @@ for v in "$@"; do
   # "lib.so|bench args": run this variant against another build of the library
   unset CELLECTOR_HIP_LIB
   case "$v" in *"|"*) export CELLECTOR_HIP_LIB="$PWD/${v%%|*}"; v="${v#*|}";; esac
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline $v > $out/bench.json 2> $out/bench.err || { echo "variant $i failed"; tail -5 $out/bench.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline $v > $out/bench.json 2> $out/bench.err || { echo "variant $i failed"; tail -5 $out/bench.err; exit 1; }
   python3 - <<PY
 import json,glob,csv
 line=[l for l in open("$out/bench.json") if l.startswith("{")][-1]

@@ -7,7 +7,7 @@ for v in "$@"; do
   out=gpurun_out/$tag/v$i; mkdir -p $out
   envs=""; args=""
   for w in $v; do case "$w" in [A-Z_]*=*) envs="$envs $w";; *) args="$args $w";; esac; done
-  env $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline $args > $out/bench.json 2> $out/bench.err || { echo "variant $i failed"; tail -5 $out/bench.err; exit 1; }
+  env $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $args > $out/bench.json 2> $out/bench.err || { echo "variant $i failed"; tail -5 $out/bench.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads([l for l in open("$out/bench.json") if l.startswith("{")][-1])

@@ -8,8 +8,8 @@ mkdir -p $out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1; rc=$?
 echo pytest=$rc; tail -3 $out/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline "$@" > $out/trace.log 2>&1; echo trace=$?
-timeout -k 10 600 python3 bench.py --no-cpu-baseline "$@" > $out/bench.json 2> $out/bench.err; echo bench=$?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline "$@" > $out/trace.log 2>&1; echo trace=$?
+timeout -k 10 600 python3 bench.py --full --no-cpu-baseline "$@" > $out/bench.json 2> $out/bench.err; echo bench=$?
 python3 - <<PY
 import json,glob,csv
 d=json.load(open("$out/bench.json"))

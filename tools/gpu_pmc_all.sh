@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 tag=$1; ctr=$2; shift; shift
 out=gpurun_out/$tag; mkdir -p $out
-timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv -d $out/pmc -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" > $out/pmc.log 2>&1 || { echo pmc failed; tail -5 $out/pmc.log; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv -d $out/pmc -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > $out/pmc.log 2>&1 || { echo pmc failed; tail -5 $out/pmc.log; exit 1; }
 python3 - <<PY
 import csv,glob,collections
 f=glob.glob("$out/pmc/*/*_counter_collection.csv")[0]

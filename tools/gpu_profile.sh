@@ -20,15 +20,15 @@ PY
 rm -rf "$1"
 }
 for w in cfg4 cfg3; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$w -- python3 bench.py --no-cpu-baseline --workload $w > $out/trace_$w.log 2>&1 || { echo trace $w failed; tail -5 $out/trace_$w.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$w -- python3 bench.py --full --no-cpu-baseline --workload $w > $out/trace_$w.log 2>&1 || { echo trace $w failed; tail -5 $out/trace_$w.log; exit 1; }
   cp $out/trace_$w/*/*_kernel_stats.csv $out/kernel_stats_$w.csv && rm -rf $out/trace_$w
   echo trace $w ok
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $out/pmc_${c}_$w -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --workload $w > $out/pmc_${c}_$w.log 2>&1 || { echo pmc $c $w failed; tail -5 $out/pmc_${c}_$w.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $out/pmc_${c}_$w -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --workload $w > $out/pmc_${c}_$w.log 2>&1 || { echo pmc $c $w failed; tail -5 $out/pmc_${c}_$w.log; exit 1; }
     summarise $out/pmc_${c}_$w
     echo $c $w ok
   done
 done
-timeout -k 10 900 python3 bench.py > $out/bench_cfg4.json 2> $out/bench_cfg4.err || { echo bench failed; tail -5 $out/bench_cfg4.err; exit 1; }
-timeout -k 10 600 python3 bench.py --workload cfg3 > $out/bench_cfg3.json 2> $out/bench_cfg3.err || { echo bench cfg3 failed; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $out/bench_cfg4.json 2> $out/bench_cfg4.err || { echo bench failed; tail -5 $out/bench_cfg4.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full --workload cfg3 > $out/bench_cfg3.json 2> $out/bench_cfg3.err || { echo bench cfg3 failed; exit 1; }
 echo done

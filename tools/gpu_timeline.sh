@@ -13,7 +13,7 @@ f=$(ls $out/trace$R/*/*_kernel_trace.csv | head -1)
 python3 tools/timeline.py $f 40 > $out/timeline$R.txt
 rm -rf $out/trace$R
 done
-timeout -k 10 600 python3 bench.py --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$out/bench.json')); print('ms', d['ms_per_step'], d['kernels_ms'], 'frac', d['roofline']['frac'], 'launch', d['roofline']['launch_ms'])"
 timeout -k 10 600 python3 tools/shard_rehearsal.py > $out/rehearsal.json 2> $out/rehearsal.err || { tail -5 $out/rehearsal.err; exit 1; }

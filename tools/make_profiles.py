@@ -24,7 +24,7 @@ for w in ("cfg4", "cfg3"):
         rows.append((k, f, wr, 2 * f * 1024 + wr * 1024))
     rows.sort(key=lambda r: -r[3])
     with open(os.path.join(dst, f"{tag}_{w}_pmc.csv"), "w") as o:
-        o.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), same command (python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --workload {w}); per-launch means in KiB as reported.\n")
+        o.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), same command (python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --workload {w}); per-launch means in KiB as reported.\n")
         o.write("# gfx950 correction (MI355X_MICROARCH.md, HBM): hbm_bytes = 2*FETCH*1024 + WRITE*1024 (FETCH_SIZE counts 1/2 of streamed read bytes; calibrated on k_fill in r1_v1_cfg4_pmc.csv)\n")
         o.write("kernel,FETCH_SIZE_KiB,WRITE_SIZE_KiB,hbm_bytes_corrected\n")
         for k, f, wr, b in rows:
@@ -50,7 +50,7 @@ for w in ("cfg4", "cfg3"):
                   "bank_conflict_frac_of_lds_cycles": vals["SQ_LDS_BANK_CONFLICT"] / vals["SQ_LDS_IDX_ACTIVE"],
                   "wave_wait_frac": vals["SQ_WAIT_INST_ANY"] / vals["SQ_WAVE_CYCLES"]}
             with open(os.path.join(dst, f"{tag}_cfg4_sq_tile.csv"), "w") as o:
-                o.write("# rocprofv3 --pmc (one pass), python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --opt overlap=0 (the overflow "
+                o.write("# rocprofv3 --pmc (one pass), python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --opt overlap=0 (the overflow "
                         "kernels in front of the tile kernel: the tile kernel alone); per-launch means, summed over the chip (256 CUs)\n")
                 o.write("# k_tile_ll<true,4>, cfg4\ncounter,value\n")
                 for k in sorted(vals):
