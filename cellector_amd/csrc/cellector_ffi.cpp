@@ -121,6 +121,8 @@ static void free_matrix(cellector_ctx *c)
     // tables itself (em_finish leaves tables_prebuilt set; the new matrix' table buffers are fresh allocations)
     c->tables_prebuilt = false; c->prebuilt_expected = false; c->work_zeroed = false; c->ovf_locus_pending = false;
     c->cell_join_pending = false;
+    // nor does per-iteration state: the fused locus filter of an unfinished iteration, the kept exclusion-set counts
+    c->filter_fused = false; c->tally_valid = false;
 }
 
 // the side stream gets the lowest priority the device offers: its kernels should only fill slots the main stream's
@@ -426,6 +428,10 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         if (v < 0 || v > 2) return ctx_fail(c, CELLECTOR_EINVAL, "locus_mode must be 0 (automatic), 1 (stream) or 2 (minority-driven)");
         c->locus_mode = (int)v;
     }
+    else if (!strcmp(key, "tally_delta")) {
+        if (v != 0 && v != 1) return ctx_fail(c, CELLECTOR_EINVAL, "tally_delta must be 0 (recount every iteration) or 1");
+        c->tally_delta = v != 0;
+    }
     else if (!strcmp(key, "compact_bits")) {
         if (v != 0 && v != 32) return ctx_fail(c, CELLECTOR_EINVAL, "compact_bits must be 0 (automatic) or 32");
         c->c4_bits_opt = (int)v;
@@ -441,6 +447,9 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         }
         if (v == 2 && c->ref_arith) return ctx_fail(c, CELLECTOR_EINVAL, "ref_arith is an engine 1 option: clear it before switching to engine 2");
         c->engine = (int)v;
+        // engine 1 moves the exclusion set without engine 2's kept counts; the fused filter is engine 2's alone
+        c->tally_valid = false;
+        c->filter_fused = false;
     }
     else return ctx_fail(c, CELLECTOR_EINVAL, "unknown option '%s'", key);
     return CELLECTOR_OK;
@@ -454,6 +463,7 @@ cellector_status cellector_set_partition(cellector_ctx *c, const uint64_t *bound
     REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "set_partition must precede the ingest");
     if (!bounds || n_bounds == 0) {  // back to the canonical equal ranges
         c->comm.has_bounds = false;
+        c->tally_valid = false;
         return CELLECTOR_OK;
     }
     REQUIRE(c, n_bounds == c->comm.n + 1, "set_partition: one boundary more than there are ranks");
@@ -461,6 +471,7 @@ cellector_status cellector_set_partition(cellector_ctx *c, const uint64_t *bound
     for (int r = 0; r < c->comm.n; r++) REQUIRE(c, bounds[r] <= bounds[r + 1], "set_partition: boundaries must not decrease");
     for (int r = 0; r <= c->comm.n; r++) c->comm.bounds[r] = bounds[r];
     c->comm.has_bounds = true;
+    c->tally_valid = false;
     return CELLECTOR_OK;
 }
 
@@ -491,6 +502,7 @@ cellector_status cellector_set_shard(cellector_ctx *c, uint64_t b, uint64_t e)
     REQUIRE(c, b <= e, "empty or inverted shard range");
     c->cell_begin = b;
     c->cell_end = e;
+    c->tally_valid = false;  // (the ingest that must follow rebuilds the counts anyway)
     return CELLECTOR_OK;
 }
 
@@ -853,6 +865,7 @@ cellector_status cellector_em_begin(cellector_ctx *c)
     READY(c);
     REQUIRE(c, c->em_phase == 0, "em_begin: previous iteration not finished");
     SETDEV(c);
+    c->filter_fused = false;  // (set by this iteration's locus pass; one left by an iteration that failed before em_finish is stale)
     // engine 2 forms alpha/beta inside its first kernel (k_build_tables); an empty shard has no cell pass at all
     if (c->engine != 2 || c->prebuilt_expected != c->compute_expected) c->tables_prebuilt = false;
     if (c->engine != 2 || c->nloc == 0) CHK(launch_alpha_beta(c));
@@ -947,6 +960,8 @@ cellector_status cellector_em_finish(cellector_ctx *c, cellector_iter_summary *o
     }
     std::swap(c->flags, c->flags_new);   // excluded_cells <- new_excluded (main.rs:43)
     std::swap(c->mask, c->mask_next);    // loci_used for the next iteration; mask_next keeps this iteration's
+    // engine 2's locus pass left the counts of the new set in tally / cnt2: they are the current set's now
+    if (c->engine == 2 && c->tiled_ready) c->tally_valid = true;
     c->n_excluded_global = (uint64_t)cnt[LC_N_EXCLUDED];
     c->iteration++;
     c->have_iter = true;

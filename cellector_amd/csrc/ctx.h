@@ -30,7 +30,9 @@ enum { LC_N_NEW = 0, LC_N_RESCUED = 1, LC_N_EXCLUDED = 2, LC_N_NEAR = 3 /* cells
 enum { P1_CELLS_REF = 0, P1_CELLS_ALT = 1, P1_SUM_REF = 2, P1_SUM_ALT = 3, P1_ENTRIES = 4, P1_PLANES = 5 };
 
 // d_counters slots (u32)
-enum { DC_N_FILTERED = 0, DC_N_MIN = 4 /* members of this shard's new exclusion set (k_flag) */ };
+enum { DC_N_FILTERED = 0, DC_N_MIN = 4 /* members of this shard's new exclusion set (k_flag) */,
+       DC_N_ADD = 5 /* ... of them not in the old set (k_flag's change list, front) */,
+       DC_N_RES = 6 /* cells of the old set not in the new one (rescued; the change list's back end) */ };
 
 #define T_ROWS_PER_TILE 1024  // rows (cells) of a tile of the tiled layout (= T_BC in kernels_tiled.hip)
 #define CELLECTOR_TILE_WORK_STRIDE 64  // column counters per table set of the persistent tile kernel (= T_GROUPS_MAX)
@@ -70,7 +72,12 @@ struct cellector_ctx {
     bool ref_arith = false;  // option ref_arith (engine 1): evaluate stats.rs:41-53 with ln_gamma differences, the reference's own rounding
     int64_t parse_window_opt = 0;  // option parse_window: 0 = whole file below 1 GB, 256 MB windows above; else the window in bytes
     bool fuse_filter = true;   // option "fuse_filter": an unsharded ctx applies the -80 locus filter inside k_locus_finalize (A/B)
-    bool filter_fused = false;  // this iteration's locus pass did so (em_finish then launches no k_locus_filter)
+    bool filter_fused = false;  // this iteration's locus pass did so (em_finish then launches no k_locus_filter); cleared by
+                                // em_finish, free_matrix, em_begin and the engine option
+    bool tally_delta = true;    // option "tally_delta": engine 2 keeps the exclusion set's per-(locus, code) counts across
+                                // iterations and updates them from the set's change (0: recounts every iteration; A/B)
+    bool tally_valid = false;   // tally / cnt2 hold the counts of the current exclusion set (flags): set by em_finish, cleared by
+                                // the locus pass (until its flag swap), a reload and an engine switch
     bool bank_order = true;  // option "bank_order": the tile builder orders every row's entries against LDS bank conflicts (tile_bank_order)
     int tile_groups_opt = 0;  // option tile_groups: 0 = chosen per matrix (tiled_setup), else forced (multiple of 8)
     // option sharded_select: a ctx with a communicator exchanges digit histograms (1) or all-gathers NORM (0); -1 = by the
@@ -159,7 +166,7 @@ struct cellector_ctx {
     uint32_t *t2_plist = nullptr, *t2_slist = nullptr;  // the pairs (locus << 5 | pair) / table sectors (locus << 3 | sector) that occur, locus order (static)
     uint32_t t2_np = 0, t2_ns = 0;
     uint32_t *t2_pmask = nullptr;    // [L] bit c2: the pair occurs at the locus (static)
-    uint32_t *cnt2 = nullptr;        // [L][32] ... of the cells of the new exclusion set (k_t2_minority; cleared by k_locus_finalize)
+    uint32_t *cnt2 = nullptr;        // [L][32] ... of the cells of the exclusion set (k_t2_minority; kept across iterations, see tally_valid)
     double *tab2 = nullptr;          // [L][48] per pass: log-pmfs of the pairs that occur + expected terms, six 64-byte sectors per locus
     // tier-2 TILES (deep coverage; kernels_tiled.hip, geo_t2): the cell side of the totals 5..t2_tiles walks a second tile set with
     // its own chunk tables in LDS instead of evaluating those entries one by one (k_ovf_cell_wide keeps the other totals)
@@ -191,7 +198,9 @@ struct cellector_ctx {
     uint64_t n_masked_loci = 0;
     uint32_t *tile_work = nullptr;   // [3][T_GROUPS_MAX] column counters of the persistent tile kernel, one set per table set
     uint32_t *minlist = nullptr;     // [nloc] local ids of the cells of the new exclusion set (arbitrary order)
-    uint32_t *hist_min = nullptr;    // [lr_sub][L][16] regular entries of minority cells per (locus, code), partial planes
+    uint32_t *chg = nullptr;         // [nloc] the set's change (k_flag): newly excluded cells from the front, rescued ones from the back
+    uint32_t *tally = nullptr;       // [L][16] regular entries of the exclusion set's cells per (locus, code), u32 (kept across iterations)
+    uint32_t *hist_min = nullptr;    // [2 * lr_sub][L][16] u16 partial planes of this iteration's counts (k_minority_ranges)
     uint32_t *mroff = nullptr;       // [R+1][mroff_cap] the excluded cells' offset rows, transposed (per iteration)
     uint64_t *mbeg = nullptr;        // [mroff_cap] start of the excluded cells' rows in csr_ent
     uint64_t mroff_cap = 0;

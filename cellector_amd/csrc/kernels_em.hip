@@ -99,10 +99,11 @@ __global__ __launch_bounds__(FLAG_THREADS) void k_flag(uint64_t n, const double 
                                                        const uint8_t *__restrict__ old_flags, uint8_t *__restrict__ new_flags,
                                                        double *__restrict__ counters, uint32_t *__restrict__ minlist /*may be null*/,
                                                        uint32_t *__restrict__ n_min, uint32_t *__restrict__ flag_bits /*with minlist*/,
+                                                       uint32_t *__restrict__ chg /*with minlist*/, uint32_t *__restrict__ n_chg /*[2]*/,
                                                        double near_rel)
 {
     __shared__ uint32_t s_wave[FLAG_THREADS / 64];
-    __shared__ uint32_t s_base;
+    __shared__ uint32_t s_base, s_base_new, s_base_res;
     const double thr = *d_thr;  // computed on the device by k_threshold
     // a block takes a contiguous span of cells (a multiple of the block size), wave w of it the 64-cell pieces w, w+16, ...
     const uint64_t span = ((n + gridDim.x - 1) / gridDim.x + FLAG_THREADS - 1) / FLAG_THREADS * FLAG_THREADS;
@@ -139,14 +140,18 @@ __global__ __launch_bounds__(FLAG_THREADS) void k_flag(uint64_t n, const double 
     // The members of the new exclusion set as a list (engine 2's minority-driven locus tally): ONE atomic per block
     // reserves the block's slots, then a second walk over the span (L2-hot) fills them.  The list's order depends on
     // the block order only through the bases, and only order-independent integer tallies are derived from it.
+    // The set's change likewise (engine 2 updates the kept counts from it): the newly excluded cells from the front of
+    // chg, the rescued ones from its back end (together at most n cells: the two parts never meet).
     if (threadIdx.x == 0) {
         uint32_t tot = 0, t_new = 0, t_res = 0, t_near = 0;
         for (int w = 0; w < FLAG_THREADS / 64; w++) {
-            const uint32_t x = s_wave[w];
+            const uint32_t x = s_wave[w], xn = s_new[w], xr = s_res[w];
             s_wave[w] = tot;
+            s_new[w] = t_new;
+            s_res[w] = t_res;
             tot += x;
-            t_new += s_new[w];
-            t_res += s_res[w];
+            t_new += xn;
+            t_res += xr;
             t_near += s_near[w];
         }
         if (t_near) atomicAdd(&counters[LC_N_NEAR], (double)t_near);
@@ -154,18 +159,29 @@ __global__ __launch_bounds__(FLAG_THREADS) void k_flag(uint64_t n, const double 
         if (t_res) atomicAdd(&counters[LC_N_RESCUED], (double)t_res);
         if (tot) atomicAdd(&counters[LC_N_EXCLUDED], (double)tot);
         s_base = (tot && minlist) ? atomicAdd(n_min, tot) : 0u;
+        s_base_new = (t_new && minlist) ? atomicAdd(&n_chg[0], t_new) : 0u;
+        s_base_res = (t_res && minlist) ? atomicAdd(&n_chg[1], t_res) : 0u;
     }
     if (!minlist) return;
     __syncthreads();
-    uint32_t pos = s_base + s_wave[threadIdx.x >> 6];
+    const uint32_t wv = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+    uint32_t pos = s_base + s_wave[wv], pos_new = s_base_new + s_new[wv], pos_res = s_base_res + s_res[wv];
     const uint64_t end_round = beg + (end - beg + 63) / 64 * 64;  // whole waves take part in the ballot
     for (uint64_t i = beg + threadIdx.x; i < end_round; i += FLAG_THREADS) {
-        const bool nf = i < end && norm[i] < thr;
+        const bool in = i < end;
+        const bool nf = in && norm[i] < thr;
+        const bool of = in && old_flags[i] != 0;
         const unsigned long long m = __ballot(nf);
-        if (nf) minlist[pos + (uint32_t)__popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] = (uint32_t)i;
+        if (nf) minlist[pos + (uint32_t)__popcll(m & below)] = (uint32_t)i;
         pos += (uint32_t)__popcll(m);
+        const unsigned long long mn = __ballot(nf && !of), mr = __ballot(of && !nf);
+        if (nf && !of) chg[pos_new + (uint32_t)__popcll(mn & below)] = (uint32_t)i;
+        if (of && !nf) chg[n - 1 - (pos_res + (uint32_t)__popcll(mr & below))] = (uint32_t)i;
+        pos_new += (uint32_t)__popcll(mn);
+        pos_res += (uint32_t)__popcll(mr);
         // the exclusion set as a bitmask too (locus pass): the wave's 64 cells are two words (i is 64-aligned in lane 0)
-        if ((threadIdx.x & 31) == 0 && i < end) flag_bits[i >> 5] = (uint32_t)(m >> (threadIdx.x & 32));
+        if ((threadIdx.x & 31) == 0 && in) flag_bits[i >> 5] = (uint32_t)(m >> (threadIdx.x & 32));
     }
 }
 
@@ -431,9 +447,11 @@ cellector_status launch_cell_ll(cellector_ctx *c, const double2 *ab, double *nor
 cellector_status launch_flag(cellector_ctx *c, const double *d_thr)
 {
     if (c->nloc == 0) return CELLECTOR_OK;
+    static_assert(DC_N_RES == DC_N_ADD + 1, "k_flag's two change counters are adjacent");
     hipLaunchKernelGGL(k_flag, dim3(grid_for(c->nloc, FLAG_THREADS * 4, 256)), dim3(FLAG_THREADS), 0, c->stream, c->nloc,
                        c->x_norm + c->cell_begin, d_thr, c->flags, c->flags_new, c->x_locus + LB_PLANES * c->L,
-                       c->tiled_ready ? c->minlist : (uint32_t *)nullptr, c->d_counters + DC_N_MIN, c->flag_bits, c->near_rel);
+                       c->tiled_ready ? c->minlist : (uint32_t *)nullptr, c->d_counters + DC_N_MIN, c->flag_bits, c->chg,
+                       c->d_counters + DC_N_ADD, c->near_rel);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
 }

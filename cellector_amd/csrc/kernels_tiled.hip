@@ -985,22 +985,27 @@ __global__ __launch_bounds__(64) void k_t2_cell(uint64_t n_rows, const uint64_t 
   }
 }
 
-// locus side: the tier-2 entries of the cells of the new exclusion set, counted per (locus, pair).  16 lanes per excluded
-// cell walk its overflow row (~16 entries: one 128-byte line); ~10^6 scattered integer atomics per iteration at 10^6 cells.
-// k_locus_finalize reads the counters and clears them again.
-__global__ __launch_bounds__(256) void k_t2_minority(const uint32_t *__restrict__ n_min_p, const uint32_t *__restrict__ minlist,
+// locus side: the tier-2 entries of the cells of the exclusion set, counted per (locus, pair).  16 lanes per cell walk its
+// overflow row (~16 entries: one 128-byte line); scattered integer atomics.  The counters are kept across iterations like
+// the regular codes' (tally_plan): with valid counts only the CHANGED cells are walked, +1 for a newly excluded cell and -1
+// (u32 wrap-around: exact) for a rescued one — nothing at all once the set stops moving; else the counters were cleared
+// (tiled_locus_pass) and the whole new set is counted.  (A change larger than the new set is walked as a change too: its
+// atomics are bounded by the two sets, and clearing first would take a launch of its own every iteration.)
+__global__ __launch_bounds__(256) void k_t2_minority(const uint32_t *__restrict__ tc, int valid, uint64_t nloc,
+                                                     const uint32_t *__restrict__ minlist, const uint32_t *__restrict__ chg,
                                                      const uint64_t *__restrict__ ovf_ptr, const uint64_t *__restrict__ ovf_ent,
                                                      uint32_t *__restrict__ cnt2)
 {
-    const uint32_t n_min = *n_min_p;
+    const uint32_t n_a = valid ? tc[1] : tc[0], n = valid ? n_a + tc[2] : n_a;
     const uint32_t j = threadIdx.x % LF_LANES;
     const uint32_t ng = gridDim.x * (256 / LF_LANES);
-    for (uint32_t k = (blockIdx.x * 256 + threadIdx.x) / LF_LANES; k < n_min; k += ng) {
-        const uint32_t cell = minlist[k];
+    for (uint32_t k = (blockIdx.x * 256 + threadIdx.x) / LF_LANES; k < n; k += ng) {
+        const uint32_t cell = !valid ? minlist[k] : k < n_a ? chg[k] : chg[nloc - 1 - (k - n_a)];
+        const uint32_t inc = k < n_a ? 1u : ~0u;
         for (uint64_t i = ovf_ptr[cell] + j, end = ovf_ptr[cell + 1]; i < end; i += LF_LANES) {
             const uint64_t en = ovf_ent[i];
-            const uint32_t r = ENT_REF(en), n = ENT_ALT(en) + r;
-            if (t2_total(n)) atomicAdd(&cnt2[(uint64_t)ENT_IDX(en) * T2_CSTRIDE + t2_code(n, r)], 1u);
+            const uint32_t r = ENT_REF(en), t = ENT_ALT(en) + r;
+            if (t2_total(t)) atomicAdd(&cnt2[(uint64_t)ENT_IDX(en) * T2_CSTRIDE + t2_code(t, r)], inc);
         }
     }
 }
@@ -1268,6 +1273,62 @@ __device__ __forceinline__ bool locus_by_minority(int mode, uint32_t n_min, uint
     return mode == 2 || (mode == 0 && (uint64_t)n_min * LM_DEN <= nloc * LM_NUM);
 }
 
+// The regular-code counts of the exclusion set per (locus, code) are KEPT across iterations (ctx tally, u32 [L][16]) and
+// updated from the set's change: new = old + the entries of the newly excluded cells - those of the rescued ones (integers:
+// exact and order independent; u32 wrap-around is exact too, every final count being non-negative).  The set hardly moves
+// once the loop settles (every timed bench step: no change), so the count kernels then return at once.  Per iteration, on the
+// device (tc = d_counters + DC_N_MIN: new set, newly excluded, rescued):
+//   valid, no change            nothing is counted, k_locus_finalize reads the kept plane
+//   valid, change <= new set    the minority-driven form walks the CHANGED cells' rows: a subset of the partial planes per
+//                               sign (u16 counters: a subset never mixes the two signs), k_locus_finalize adds them with
+//                               their signs to the kept plane and stores it back
+//   otherwise                   a recount of the new set: the minority-driven form (its planes replace the kept plane) or the
+//                               streamed one (k_locus_stats2 overwrites it), chosen as before (locus_mode)
+// A subset takes at least TALLY_SUB_CELLS cells (one batch of k_minority_ranges): a small change is few planes to add.
+#define TALLY_SUB_CELLS 1024
+struct TallyPlan {
+    uint32_t n_a, n_r;  // cells counted with sign + (list positions 0 .. n_a-1) and - (n_a .. n_a+n_r-1)
+    uint32_t s_a, s_r;  // subsets (u16 partial planes) of either sign
+    bool delta;         // the list is the change (k_flag's chg), else the new set (minlist)
+    bool fresh;         // minority-driven recount: the planes replace the kept counts
+    bool stream;        // streamed recount (k_locus_stats2)
+};
+__device__ __forceinline__ uint32_t tally_subsets(uint32_t n, uint32_t n_sub)
+{
+    return min(n_sub, (n + TALLY_SUB_CELLS - 1) / TALLY_SUB_CELLS);
+}
+__device__ __forceinline__ TallyPlan tally_plan(int mode, int valid, const uint32_t *tc, uint64_t nloc, uint32_t n_sub)
+{
+    const uint32_t n_min = tc[0], n_add = tc[1], n_res = tc[2];
+    TallyPlan p = {0u, 0u, 0u, 0u, false, false, false};
+    if (valid) {
+        const uint64_t n_chg = (uint64_t)n_add + n_res, cap = (uint64_t)n_sub * 32767u;
+        if (n_chg == 0) return p;
+        // (the transposed offsets hold nloc * LM_NUM / LM_DEN cells whatever the locus_mode: tiled_locus_pass)
+        if (n_chg <= n_min && n_chg * LM_DEN <= nloc * LM_NUM && n_add <= cap && n_res <= cap) {
+            p.delta = true;
+            p.n_a = n_add; p.n_r = n_res;
+            p.s_a = tally_subsets(n_add, n_sub); p.s_r = tally_subsets(n_res, n_sub);
+            return p;
+        }
+    }
+    if (locus_by_minority(mode, n_min, nloc, n_sub)) {
+        p.fresh = true;
+        p.n_a = n_min;
+        p.s_a = tally_subsets(n_min, n_sub);
+    } else {
+        p.stream = true;
+    }
+    return p;
+}
+// the k-th cell of the plan's list
+__device__ __forceinline__ uint32_t tally_cell(const TallyPlan &p, const uint32_t *__restrict__ minlist,
+                                               const uint32_t *__restrict__ chg, uint64_t nloc, uint32_t k)
+{
+    if (!p.delta) return minlist[k];
+    return k < p.n_a ? chg[k] : chg[nloc - 1 - (k - p.n_a)];
+}
+
 struct __attribute__((packed, aligned(4))) ls_u3 { uint32_t x, y, z; };  // 12-byte load at a 4-byte aligned address
 #define LS_THREADS 1024
 template <bool BITS_IN_LDS, int EB>
@@ -1275,10 +1336,10 @@ __global__ __launch_bounds__(LS_THREADS) void k_locus_stats2(uint64_t L, uint32_
                                                              const uint64_t *__restrict__ c4_ptr,
                                                              const uint32_t *__restrict__ c4_ent,
                                                              const uint32_t *__restrict__ flag_bits,
-                                                             uint32_t *__restrict__ hist_min /*plane 0*/, int locus_mode,
-                                                             uint64_t nloc, const uint32_t *__restrict__ n_min, uint32_t n_sub)
+                                                             uint32_t *__restrict__ tally, int locus_mode, int valid,
+                                                             uint64_t nloc, const uint32_t *__restrict__ tc, uint32_t n_sub)
 {
-    if (locus_by_minority(locus_mode, *n_min, nloc, n_sub)) return;  // k_minority_ranges counts this iteration
+    if (!tally_plan(locus_mode, valid, tc, nloc, n_sub).stream) return;  // kept counts, or k_minority_ranges counts
     extern __shared__ uint32_t s_bits[];
     __shared__ uint32_t s_whist[LS_THREADS / 64][16];
     if (threadIdx.x < (LS_THREADS / 64) * 16) (&s_whist[0][0])[threadIdx.x] = 0;
@@ -1365,10 +1426,10 @@ __global__ __launch_bounds__(LS_THREADS) void k_locus_stats2(uint64_t L, uint32_
         }
 #undef LS_PROCESS
 #undef LS_LOAD
-        // the wave's bins are this locus' minority counts per code: plane 0 of hist_min (same wave wrote the bins: LDS
+        // the wave's bins are this locus' minority counts per code: the kept plane (same wave wrote the bins: LDS
         // operations of one wave complete in order); k_locus_finalize turns them into the pass' outputs
         if (lane < 16) {
-            hist_min[l * 16 + lane] = whist[lane];
+            tally[l * 16 + lane] = whist[lane];
             whist[lane] = 0;
         }
     }
@@ -1433,22 +1494,22 @@ __global__ __launch_bounds__(256) void k_range_offsets(uint64_t n_rows, uint32_t
 // row.  k_minority_ranges then reads its range's offsets as contiguous runs instead of one 64-byte line per (cell, range)
 // out of the big per-cell table (measured: those line fetches were a third of that kernel's traffic).
 #define LT_CELLS 64
-__global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, uint64_t nloc, uint32_t n_sub, uint32_t R, uint64_t mstride,
-                                                          const uint32_t *__restrict__ n_min_p,
-                                                          const uint32_t *__restrict__ minlist,
+__global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, int valid, uint64_t nloc, uint32_t n_sub, uint32_t R,
+                                                          uint64_t mstride, const uint32_t *__restrict__ tc,
+                                                          const uint32_t *__restrict__ minlist, const uint32_t *__restrict__ chg,
                                                           const uint64_t *__restrict__ csr_ptr,
                                                           const uint32_t *__restrict__ roff, uint32_t *__restrict__ mroff,
                                                           uint64_t *__restrict__ mbeg)
 {
-    const uint32_t n_min = *n_min_p;
-    if (!locus_by_minority(locus_mode, n_min, nloc, n_sub)) return;
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const uint32_t n_list = tp.n_a + tp.n_r;  // the plan's list (none: the streamed form, or no change)
     const uint32_t k0 = blockIdx.x * LT_CELLS;
-    if (k0 >= n_min) return;
+    if (k0 >= n_list) return;
     extern __shared__ uint32_t s_t[];  // [LT_CELLS][row], row odd: the column read below strides by it
     __shared__ uint32_t s_cell[LT_CELLS];
-    const uint32_t row = (R + 1) | 1u, nk = min((uint32_t)LT_CELLS, n_min - k0);
+    const uint32_t row = (R + 1) | 1u, nk = min((uint32_t)LT_CELLS, n_list - k0);
     if (threadIdx.x < nk) {
-        const uint32_t cell = minlist[k0 + threadIdx.x];
+        const uint32_t cell = tally_cell(tp, minlist, chg, nloc, k0 + threadIdx.x);
         s_cell[threadIdx.x] = cell;
         mbeg[k0 + threadIdx.x] = csr_ptr[cell];
     }
@@ -1468,25 +1529,31 @@ __global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, uint64
     }
 }
 
-__global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, uint64_t nloc, uint64_t L, uint32_t R,
+__global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, int valid, uint64_t nloc, uint64_t L, uint32_t R,
                                                                uint32_t n_sub, uint64_t mstride,
-                                                               const uint32_t *__restrict__ n_min_p,
+                                                               const uint32_t *__restrict__ tc,
                                                                const uint32_t *__restrict__ mroff,
                                                                const uint64_t *__restrict__ mbeg,
                                                                const uint16_t *__restrict__ c4r,
-                                                               uint32_t *__restrict__ hist_min /*[n_sub][L][16] u16*/)
+                                                               uint32_t *__restrict__ hist_min /*[2 n_sub][L][16] u16*/)
 {
-    const uint32_t n_min = *n_min_p;
-    if (!locus_by_minority(locus_mode, n_min, nloc, n_sub)) return;
+    // (grid: R x 2 n_sub workgroups; those beyond the plan's subsets return)
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const uint32_t sub = blockIdx.x / R;
+    if (sub >= tp.s_a + tp.s_r) return;
     // u16 counters, two per word, code-major: the bank of a counter follows the locus (spread out), not the code (most
-    // entries are single reads: codes 0 and 1).  A subset has at most 32767 cells (locus_by_minority): no carry.
+    // entries are single reads: codes 0 and 1).  A subset has at most 32767 cells (tally_plan): no carry.  Its cells
+    // are all of one sign (k_locus_finalize adds or subtracts the whole plane).
     __shared__ uint32_t s_hist[T_NCODE * LR_ROW / 2];
     __shared__ uint64_t s_beg[LR_THREADS];
     __shared__ uint32_t s_len[LR_THREADS];
     const uint32_t tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const uint32_t r = blockIdx.x % R, sub = blockIdx.x / R;
-    const uint32_t per = (n_min + n_sub - 1) / n_sub;
-    const uint32_t k0 = min(n_min, sub * per), k1 = min(n_min, k0 + per);
+    const uint32_t r = blockIdx.x % R;
+    const bool neg = sub >= tp.s_a;
+    const uint32_t lo = neg ? tp.n_a : 0u, n_sign = neg ? tp.n_r : tp.n_a, s_sign = neg ? tp.s_r : tp.s_a;
+    const uint32_t q = neg ? sub - tp.s_a : sub;
+    const uint32_t per = (n_sign + s_sign - 1) / s_sign;
+    const uint32_t k0 = lo + min(n_sign, q * per), k1 = lo + min(n_sign, q * per + per);
     const uint32_t l0 = r * LR_LOCI;
     for (uint32_t i = tid; i < T_NCODE * LR_ROW / 2; i += LR_THREADS) s_hist[i] = 0;
     const uint32_t grp = lane / LR_GROUP, gl = lane % LR_GROUP;
@@ -1566,9 +1633,9 @@ __global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, 
 // (alt+ref == 0 or > T_K; ~1 %, their log-pmfs evaluated from the locus' cumulative-log row) are walked 16 at a time; per-lane partial results
 // are added by a 4-step butterfly over the 16 lanes (fixed shape: deterministic).
 template <bool INLINE_OVF>  // the overflow entries' log-pmfs: evaluated here (deep coverage) or read from ovf_lp (k_ovf_values)
-__global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mode, uint64_t nloc, uint32_t n_sub,
-                                                        const uint32_t *__restrict__ n_min_p,
-                                                        const uint32_t *__restrict__ hist_min,
+__global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mode, int valid, uint64_t nloc, uint32_t n_sub,
+                                                        const uint32_t *__restrict__ tc,
+                                                        const uint32_t *__restrict__ hist_min, uint32_t *__restrict__ tally,
                                                         const uint32_t *__restrict__ flag_bits,
                                                         const uint32_t *__restrict__ hist_all,
                                                         const double *__restrict__ tab, uint32_t tab_stride,
@@ -1578,14 +1645,15 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
                                                         const double *__restrict__ ovf_lp /*null: evaluate here*/,
                                                         const double *__restrict__ otab, const double *__restrict__ lf,
                                                         const double2 *__restrict__ ab, double *__restrict__ out,
-                                                        uint32_t *__restrict__ cnt2 /*null: no tier 2*/,
+                                                        const uint32_t *__restrict__ cnt2 /*null: no tier 2*/,
                                                         const uint32_t *__restrict__ hist_all2, const uint32_t *__restrict__ pmask2,
                                                         const double *__restrict__ tab2,
                                                         uint8_t *__restrict__ mask_next /*null: the locus filter is a kernel of its own*/,
                                                         uint32_t *__restrict__ n_filtered)
 {
-    // the minority-driven form left n_sub planes of u16 counts, the streamed form one plane of u32 counts
-    const bool by_min = locus_by_minority(locus_mode, *n_min_p, nloc, n_sub);
+    // the kept u32 counts (filled by k_locus_stats2 if it recounted), plus / minus this iteration's u16 partial planes
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const uint32_t n_planes = tp.s_a + tp.s_r;
     const uint32_t j = threadIdx.x % LF_LANES;
     const uint64_t l_raw = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / LF_LANES;
     const bool in = l_raw < L;
@@ -1597,13 +1665,13 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
     uint32_t nmin = 0;
     uint64_t amin = 0, rmin = 0;
     if (j < T_NCODE) {
-        uint32_t cnt = 0;
-        if (by_min) {
+        uint32_t cnt = tp.fresh ? 0u : tally[l * 16 + j];
+        if (n_planes) {
             const uint16_t *h16 = reinterpret_cast<const uint16_t *>(hist_min);
-            for (uint32_t p = 0; p < n_sub; p++) cnt += h16[((uint64_t)p * L + l) * 16 + j];
-        } else {
-            cnt = hist_min[l * 16 + j];
+            for (uint32_t p = 0; p < tp.s_a; p++) cnt += h16[((uint64_t)p * L + l) * 16 + j];
+            for (uint32_t p = tp.s_a; p < n_planes; p++) cnt -= h16[((uint64_t)p * L + l) * 16 + j];
         }
+        if (in && (n_planes || tp.fresh)) tally[l * 16 + j] = cnt;  // the counts of the new set, kept for the next iteration
         const uint32_t h_all = hist_all[l * T_NCODE + j];
         // (element stride 2 when the table holds (log-pmf, expected) pairs)
         const double t_code = tab[(l / T_BLU) * TAB_ELEMS + (l % T_BLU) * T_LROW + j];
@@ -1616,7 +1684,7 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
         }
     }
     // tier 2 (the overflow entries with totals 5..8, counted per (locus, pair) by k_t2_minority): lane j takes the pairs j and
-    // j + 16; count x table value, like the regular codes.  The counters are cleared for the next iteration.
+    // j + 16; count x table value, like the regular codes.  The counters are kept for the next iteration.
     if (cnt2) {
         const uint32_t pm = pmask2[l];  // (the pairs that occur at this locus, static: 8 of the 30 on a 125k-cell shard)
 #pragma unroll
@@ -1625,7 +1693,6 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
             if (!((pm >> c2) & 1u)) continue;  // the pair does not occur at this locus: no counts, no table slot
             const uint32_t h_all = hist_all2[l * T2_CSTRIDE + c2];
             const uint32_t cnt = cnt2[l * T2_CSTRIDE + c2];
-            if (cnt && in) cnt2[l * T2_CSTRIDE + c2] = 0u;  // (the clamped lanes beyond L only read)
             const uint32_t n2 = 5u + (c2 >= 6u) + (c2 >= 13u) + (c2 >= 21u), r2 = c2 - t2_code(n2, 0u);
             const double t_code = tab2[l * T2_ROW + t2_pos(n2, r2)];
             amin += (uint64_t)cnt * (n2 - r2);
@@ -2248,7 +2315,7 @@ void tiled_free(cellector_ctx *c)
     dev_free(c->c4_ptr); dev_free(c->c4_ent); dev_free(c->ovc_ptr); dev_free(c->ovc_ent);
     dev_free(c->hist_all); dev_free(c->tab); dev_free(c->part); dev_free(c->ab3);
     dev_free(c->masked_cnt); dev_free(c->flag_bits); dev_free(c->ovf_tab); dev_free(c->ovf_etab);
-    dev_free(c->ovf_sum); dev_free(c->ovf_lp); dev_free(c->ovc_locus); dev_free(c->ovf_tier_row[0]); dev_free(c->ovf_tier_row[1]); dev_free(c->ovf_tier_ent[0]); dev_free(c->ovf_tier_ent[1]); dev_free(c->ovf_tier_val); dev_free(c->ovf_ell_ptr); dev_free(c->ovf_ell); dev_free(c->ovf_nmask); dev_free(c->tile_work); dev_free(c->minlist); dev_free(c->hist_min); dev_free(c->roff); dev_free(c->c4r); dev_free(c->mroff); dev_free(c->mbeg);
+    dev_free(c->ovf_sum); dev_free(c->ovf_lp); dev_free(c->ovc_locus); dev_free(c->ovf_tier_row[0]); dev_free(c->ovf_tier_row[1]); dev_free(c->ovf_tier_ent[0]); dev_free(c->ovf_tier_ent[1]); dev_free(c->ovf_tier_val); dev_free(c->ovf_ell_ptr); dev_free(c->ovf_ell); dev_free(c->ovf_nmask); dev_free(c->tile_work); dev_free(c->minlist); dev_free(c->chg); dev_free(c->tally); dev_free(c->hist_min); dev_free(c->roff); dev_free(c->c4r); dev_free(c->mroff); dev_free(c->mbeg);
     dev_free(c->t2_plist); dev_free(c->t2_slist); dev_free(c->t2_pmask); dev_free(c->hist_all2); dev_free(c->cnt2); dev_free(c->tab2); dev_free(c->ovx_ptr); dev_free(c->ovx_ent); dev_free(c->ovx_locus); dev_free(c->ovx_lp);
     dev_free(c->tile2_ptr); dev_free(c->tiles2); dev_free(c->thdr2); dev_free(c->tab2c); dev_free(c->part2); dev_free(c->tile_work2); dev_free(c->ovr_ptr); dev_free(c->ovr_ent);
     c->ovr_n = 0;
@@ -2652,6 +2719,8 @@ cellector_status tiled_build(cellector_ctx *c)
     CHK(dev_alloc(c, &c->flag_bits, (nloc + 31) / 32 + 1));
     CHK(dev_alloc(c, &c->tile_work, 3 * T_GROUPS_MAX));
     CHK(dev_alloc(c, &c->minlist, nloc));
+    CHK(dev_alloc(c, &c->chg, nloc));
+    CHK(dev_alloc(c, &c->tally, L * 16));
     {
         // subsets of the exclusion set: enough (range, subset) workgroups to fill the chip once
         int ncu = 256;
@@ -2670,7 +2739,7 @@ cellector_status tiled_build(cellector_ctx *c)
         // the transposed offsets of the excluded cells, sized for the largest exclusion set the automatic choice hands to the
         // minority-driven form (allocated here, not in the first iteration's locus pass: that cost the first iteration a
         // stream synchronisation and two allocations — and a run has few iterations)
-        if (nloc && c->locus_mode != 1) {
+        if (nloc && (c->locus_mode != 1 || c->tally_delta)) {
             c->mroff_cap = ((nloc * LM_NUM / LM_DEN + LT_CELLS) + 63) & ~63ull;
             CHK(dev_alloc(c, &c->mroff, (uint64_t)(R + 1) * c->mroff_cap));
             CHK(dev_alloc(c, &c->mbeg, c->mroff_cap));
@@ -2678,8 +2747,12 @@ cellector_status tiled_build(cellector_ctx *c)
     }
     HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (nloc ? nloc : 1) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->flag_bits, 0, ((nloc + 31) / 32 + 1) * 4, c->stream));
+    if (L) HIPCHK(c, hipMemsetAsync(c->tally, 0, L * 16 * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tiled_ready = true;
+    // before the first iteration the exclusion set is empty (cellector_ingest_finish): the zeroed counts (tally, cnt2) are its
+    // counts.  (A build after engine-1 iterations is followed by the engine option's invalidation.)
+    c->tally_valid = c->iteration == 0;
     return CELLECTOR_OK;
 }
 
@@ -2972,6 +3045,11 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     //  own on the side stream beside k_minority_ranges: both stream scattered lines, the pair took as long as one after
     //  the other)
     const uint32_t words = (uint32_t)((c->nloc + 31) / 32);
+    // kept counts (tally, cnt2) of the old exclusion set: this iteration updates them from the change (k_flag's chg) on the device
+    // (tally_plan); else the next kernels recount.  Until em_finish swaps the flags they belong to neither set.
+    const int valid = c->tally_delta && c->tally_valid ? 1 : 0;
+    c->tally_valid = false;
+    if (!valid && c->t2) HIPCHK(c, hipMemsetAsync(c->cnt2, 0, c->L * T2_CSTRIDE * sizeof(uint32_t), c->stream));
     // (k_flag wrote the exclusion bitmask flag_bits along with the flags)
     const size_t lds = (size_t)words * 4;
     int ncu = 256;
@@ -2981,9 +3059,10 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     if (grid > need) grid = (unsigned)(need ? need : 1);
 #define LAUNCH_LS(INLDS, EBV, GRID, LDSB)                                                                              \
     hipLaunchKernelGGL((k_locus_stats2<INLDS, EBV>), dim3(GRID), dim3(LS_THREADS), LDSB, c->stream, c->L, words, c->c4_ptr, \
-                       c->c4_ent, c->flag_bits, c->hist_min, c->locus_mode, c->nloc, c->d_counters + DC_N_MIN, c->lr_sub)
+                       c->c4_ent, c->flag_bits, c->tally, c->locus_mode, valid, c->nloc, c->d_counters + DC_N_MIN, c->lr_sub)
     // (a forced minority-driven form, locus_mode 2, still launches the streamed kernel: it returns at once unless the
-    //  exclusion set is too large for that form's 16-bit counters, the one case the device predicate overrides the option)
+    //  exclusion set is too large for that form's 16-bit counters, the one case the device predicate overrides the option;
+    //  likewise locus_mode 1 launches the minority-driven kernels while counts are kept: they walk the change)
     if (lds <= 128 * 1024) {
         if (c->c4_bits == 24) {
             // the whole 2^20-cell bitmask: a padding entry (cell = all ones) then reads inside the allocation
@@ -2999,13 +3078,11 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
         LAUNCH_LS(false, 32, grid * 2, 4);  // more than 2^20 cells per shard: 32-bit entries, bitmask read from L2
     }
 #undef LAUNCH_LS
-    if (c->nloc == 0)  // an empty shard: no kernel fills the planes
-        HIPCHK(c, hipMemsetAsync(c->hist_min, 0, (uint64_t)c->lr_sub * c->L * 16 * sizeof(uint32_t), c->stream));
-    if (c->locus_mode != 1 && c->nloc) {
+    // capacity of the transposed offsets: the largest exclusion set the automatic choice hands to this form, also the largest
+    // change tally_plan walks; the forced form (tests, ablations) may need all cells
+    const uint64_t want = c->locus_mode == 2 ? c->nloc : (c->locus_mode == 0 || c->tally_delta) ? c->nloc * LM_NUM / LM_DEN + LT_CELLS : 0;
+    if (want && c->nloc) {
         const uint32_t R = (uint32_t)((c->L + LR_LOCI - 1) / LR_LOCI);
-        // capacity of the transposed offsets: the largest exclusion set the automatic choice hands to this form; the
-        // forced form (tests, ablations) may need all cells
-        const uint64_t want = c->locus_mode == 2 ? c->nloc : c->nloc * LM_NUM / LM_DEN + LT_CELLS;
         if (c->mroff_cap < want) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
             dev_free(c->mroff); dev_free(c->mbeg);
@@ -3017,15 +3094,18 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
         if (lds_t > 64 * 1024)
             HIPCHK(c, hipFuncSetAttribute((const void *)k_minority_offsets, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
         hipLaunchKernelGGL(k_minority_offsets, dim3(gcap(want, LT_CELLS, 0x7fffffffu)), dim3(256), lds_t, c->stream, c->locus_mode,
-                           c->nloc, c->lr_sub, R, c->mroff_cap, c->d_counters + DC_N_MIN, c->minlist, c->csr_ptr, c->roff, c->mroff, c->mbeg);
-        hipLaunchKernelGGL(k_minority_ranges, dim3(R * c->lr_sub), dim3(LR_THREADS), 0, c->stream, c->locus_mode, c->nloc, c->L, R,
-                           c->lr_sub, c->mroff_cap, c->d_counters + DC_N_MIN, c->mroff, c->mbeg, c->c4r, c->hist_min);
+                           valid, c->nloc, c->lr_sub, R, c->mroff_cap, c->d_counters + DC_N_MIN, c->minlist, c->chg, c->csr_ptr, c->roff,
+                           c->mroff, c->mbeg);
+        // (R x lr_sub workgroups per sign: a change that both adds and rescues cells fills twice the planes of a recount)
+        hipLaunchKernelGGL(k_minority_ranges, dim3(R * c->lr_sub * 2), dim3(LR_THREADS), 0, c->stream, c->locus_mode, valid, c->nloc,
+                           c->L, R, c->lr_sub, c->mroff_cap, c->d_counters + DC_N_MIN, c->mroff, c->mbeg, c->c4r, c->hist_min);
     }
-    // the excluded cells' tier-2 entries per (locus, pair).  (On the side stream it does NOT run beside k_minority_ranges, whose
-    // sixteen 128-register waves per CU leave no room: it started when that kernel ended, two event gaps later.)
+    // the tier-2 entries per (locus, pair) of the changed cells, or of the whole new set.  (On the side stream it does NOT run
+    // beside k_minority_ranges, whose sixteen 128-register waves per CU leave no room: it started when that kernel ended, two
+    // event gaps later.)
     if (c->t2 && c->nloc)
         hipLaunchKernelGGL(k_t2_minority, dim3(gcap(c->nloc / LM_DEN + 1, 256 / LF_LANES, 8192)), dim3(256), 0, c->stream, c->d_counters + DC_N_MIN,
-                           c->minlist, c->ovf_ptr, c->ovf_ent, c->cnt2);
+                           valid, c->nloc, c->minlist, c->chg, c->ovf_ptr, c->ovf_ent, c->cnt2);
     if (c->ovf_locus_pending) {  // the overflow entries' log-pmfs of this iteration (side stream)
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join2, 0));
         c->ovf_locus_pending = false;
@@ -3036,7 +3116,8 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     const double *w_lp = c->t2 ? c->ovx_lp : c->ovf_lp;
 #define LAUNCH_LF(INL)                                                                                                             \
     hipLaunchKernelGGL(k_locus_finalize<INL>, dim3(gcap(c->L * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->L, c->locus_mode, \
-                       c->nloc, c->lr_sub, c->d_counters + DC_N_MIN, c->hist_min, c->flag_bits, c->hist_all, c->tab_em,            \
+                       valid, c->nloc, c->lr_sub, c->d_counters + DC_N_MIN, c->hist_min, c->tally, c->flag_bits, c->hist_all,       \
+                       c->tab_em,                                                                                                  \
                        (uint32_t)c->tab_em_stride, c->mask, w_ptr, w_ent, w_lp, c->ovf_tab, c->lf, c->ab, c->x_locus,              \
                        c->t2 ? c->cnt2 : (uint32_t *)nullptr, c->hist_all2, c->t2_pmask, c->tab2,                                    \
                        c->filter_fused ? c->mask_next : (uint8_t *)nullptr, c->d_counters)

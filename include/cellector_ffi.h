@@ -84,7 +84,10 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * else 32-bit; 32 forces the wide form — set before ingest),
  * "locus_mode" (engine 2, default 0: per iteration the device picks how the per-locus minority counts
  * of get_locus_log_likelihoods, main.rs:368-420, are formed — 2 = walk only the excluded cells' rows,
- * 1 = stream the whole compact CSC past the exclusion bitmask; bit-identical results),
+ * 1 = stream the whole compact CSC past the exclusion bitmask; bit-identical results; these are the forms of a recount),
+ * "tally_delta" (engine 2, default 1: those counts are kept from one iteration to the next and updated with the cells
+ * whose exclusion changed — nothing to count once the set stops moving; the device recounts the whole set when the change
+ * is larger than the new set, and after a reload or an engine switch; 0 = recount every iteration; bit-identical — A/B),
  * "overlap" (engine 2, default 1: the kernels of the few entries with alt+ref = 0 or > 4 run on a side
  * stream beside the table-lookup kernel; 2 = their locus-side part only after that kernel; 0 = everything
  * in one stream; same results to the bit),
