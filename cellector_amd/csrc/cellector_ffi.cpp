@@ -14,6 +14,7 @@
 
 #include "ctx.h"
 #include "multi.h"
+#include "ref_log.h"
 
 cellector_status ctx_fail(const cellector_ctx *c, cellector_status s, const char *fmt, ...)
 {
@@ -107,6 +108,10 @@ static void free_matrix(cellector_ctx *c)
     dev_free(c->ab); dev_free(c->ab6); dev_free(c->mask); dev_free(c->mask_next);
     dev_free(c->flags); dev_free(c->flags_new); dev_free(c->ll); dev_free(c->ell); dev_free(c->nloci);
     dev_free(c->post);
+    dev_free(c->res_cand); dev_free(c->res_key); dev_free(c->res_done); dev_free(c->res_ent);
+    c->res_n = 0;
+    c->res_nnz = 0;
+    c->res_last_mode = 0;
     tiled_free(c);
     if (c->own_pass1) dev_free(c->x_pass1);
     if (c->own_norm) dev_free(c->x_norm);
@@ -340,6 +345,7 @@ void cellector_destroy(cellector_ctx *c)
     free_matrix(c);
     dev_free(c->lf); dev_free(c->d_counters); dev_free(c->sel_hist); dev_free(c->sel_state); dev_free(c->sel_out);
     dev_free(c->sel_list); dev_free(c->seld_hist); dev_free(c->seld_state);
+    dev_free(c->res_cnt); dev_free(c->res_dev);
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
@@ -363,9 +369,41 @@ cellector_status cellector_set_stream(cellector_ctx *c, void *s)
     return CELLECTOR_OK;
 }
 
+// ref_log.h repeats the C library's log (glibc >= 2.28 as selected on a CPU with FMA).  A host whose log is another one (an
+// older glibc, the variant without FMA on a CPU or VM that hides it) would give other bits: checked once, on arguments where
+// that log is not correctly rounded (a correctly rounded or differently built log differs there) and a few ordinary ones.
+static bool ref_log_matches_host()
+{
+    static const int ok = [] {
+        const double xs[] = {0x1.1000000000001p+0, 0x1.9029699ac8b51p-1, 0x1.107d0786575abp+9, 0x1.9d92c3bf393efp+264,
+                             0x1.244a7d7500750p-319, 0x1.0cf011ed22e53p-1, 0x1.6e752447f96bdp+40, 0x1.5abd26f74c705p+17,
+                             0x1.0d67af17a1c3dp+14, 0x1.a16d6a77cb0b3p-16, 2.0, 0.5, 3.0, 1e6, 0.999999, 1.000001};
+        for (double x : xs) {
+            volatile double vx = x;  // (the host's log at run time, not a constant folded by the compiler)
+            const double a = std::log(vx), b = ref_log(x);
+            if (memcmp(&a, &b, sizeof a) != 0) return 0;
+        }
+        return 1;
+    }();
+    return ok != 0;
+}
+
 cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t v)
 {
     if (!c || !key) return CELLECTOR_EINVAL;
+    if (!strcmp(key, "resolve_ties")) {
+        if (v < 0 || v > 2) return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties must be 0 (off), 1 (the near-tie bands) or 2 (every cell)");
+        if (v && (c->multi || comm_active(c->comm)))
+            return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties works on a single-device ctx: a sharded run would need the candidates of every shard");
+        if (c->multi) return CELLECTOR_OK;  // (0 on a multi-device ctx: nothing to switch off)
+        if (v && c->state == cellector_ctx::ST_READY && c->nnz && !c->res_ent)
+            return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties keeps every cell's entries in file order at the ingest: set it before the ingest");
+        if (v && !ref_log_matches_host())
+            return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties: this host's C library log differs from the one ref_log.h repeats "
+                                                 "(glibc >= 2.28, FMA variant), so the reference's bits cannot be promised");
+        c->resolve_ties = (int)v;
+        return CELLECTOR_OK;
+    }
     if (c->multi) return multi_set_option(c, key, v);
     if (!strcmp(key, "compute_expected")) c->compute_expected = v != 0;
     else if (!strcmp(key, "ref_arith")) {
@@ -899,6 +937,12 @@ cellector_status cellector_em_threshold(cellector_ctx *c, double iqr_multiple)
         if (comm_active(c->comm)) CHK((cellector_status)comm_allgather_cells(c, c->x_norm, n));
         CHK(select_threshold(c, c->x_norm, n, iqr_multiple));
     }
+    c->res_last_mode = 0;
+    if (c->resolve_ties) {  // the cells next to the order statistics and the threshold with the reference's arithmetic
+        REQUIRE(c, !comm_active(c->comm), "resolve_ties works on a single-device ctx");
+        CHK(resolve_ties(c, iqr_multiple));
+        c->res_last_mode = c->resolve_ties;
+    }
     // (the counters k_flag adds to were reset by this iteration's k_alpha_beta)
     CHK(launch_flag(c, c->sel_out + 10));
     if (c->engine == 2) CHK(tiled_locus_pass(c));
@@ -987,6 +1031,31 @@ cellector_status cellector_em_iteration(cellector_ctx *c, double iqr_multiple, c
     CHK(cellector_em_begin(c));
     CHK(cellector_em_threshold(c, iqr_multiple));
     return cellector_em_finish(c, out);
+}
+
+cellector_status cellector_iter_resolution(const cellector_ctx *c, cellector_resolution_t *out)
+{
+    if (!c || !out) return CELLECTOR_EINVAL;
+    memset(out, 0, sizeof *out);
+    if (c->multi || !c->res_last_mode) return CELLECTOR_OK;  // (nothing was resolved in the last iteration)
+    REQUIRE(c, c->em_phase != 1, "iter_resolution between em_begin and em_threshold");
+    uint32_t cnt[4];
+    CHK(d2h(c, cnt, c->res_cnt, sizeof cnt));
+    out->n_evaluated = (uint64_t)cnt[0] + cnt[1];
+    out->n_flags_changed = cnt[2];
+    out->changed = cnt[3];
+    out->mode = (uint32_t)c->res_last_mode;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_iter_resolved_cells(const cellector_ctx *c, uint32_t *ids)
+{
+    if (!c || !ids) return CELLECTOR_EINVAL;
+    if (c->multi || !c->res_last_mode) return CELLECTOR_OK;
+    REQUIRE(c, c->em_phase != 1, "iter_resolved_cells between em_begin and em_threshold");
+    uint32_t cnt[2];
+    CHK(d2h(c, cnt, c->res_cnt, sizeof cnt));
+    return d2h(c, ids, c->res_cand, ((uint64_t)cnt[0] + cnt[1]) * sizeof(uint32_t));
 }
 
 cellector_status cellector_iter_cell_outputs(const cellector_ctx *c, double *ll, double *ell, double *nl, double *norm)

@@ -88,6 +88,18 @@ struct cellector_ctx {
     bool keep_coo = true;
     double near_rel = CELLECTOR_NEAR_TIE_REL;  // near-tie band of this matrix, relative to max(1, |threshold|) (cellector_ingest_finish)
     int synth_continue_pct = 30;  // option synth_continue_pct: the synthetic generator's n = 1 + Geometric(1 - pct/100)
+    // option resolve_ties (kernels_resolve.hip; single device): 0 off, 1 the cells next to an order statistic or the
+    // threshold get the reference's arithmetic, 2 every cell does (diagnostic).  Buffers made on first use.
+    int resolve_ties = 0;
+    int res_last_mode = 0;            // resolve_ties of the last iteration (cellector_iter_resolution)
+    uint64_t *res_ent = nullptr;      // [nnz] csr_ent's rows in file order (the ingest builds it when the option is set)
+    uint64_t res_nnz = 0;
+    uint32_t *res_cand = nullptr;     // [nloc] candidate cells
+    double *res_key = nullptr;        // [nloc] their device keys
+    uint8_t *res_done = nullptr;      // [nloc] evaluated in the order-statistic bands
+    uint64_t res_n = 0;               // cells the three were made for
+    uint32_t *res_cnt = nullptr;      // [4] band candidates, threshold-band candidates, changed flags, changed-summary bits
+    double *res_dev = nullptr;        // [4] the device keys' median, iqr, threshold
 
     // shard
     uint64_t cell_begin = 0, cell_end = UINT64_MAX;
@@ -319,6 +331,9 @@ cellector_status ffi_order_statistics(cellector_ctx *c, const double *keys, uint
                                       double *out3);  // (cellector_ffi.cpp; a shard's slice of cellector_order_statistics)
 // ... over the keys of all shards of a sharded run (this shard holds n_local of the n_total), exchanged as digit histograms
 cellector_status select_threshold_sharded(cellector_ctx *c, const double *keys, uint64_t n_local, uint64_t n_total, double iqr_multiple);
+// option resolve_ties (kernels_resolve.hip): after select_threshold, before launch_flag
+cellector_status resolve_ties(cellector_ctx *c, double iqr_multiple);
+cellector_status resolve_build_file_order(cellector_ctx *c);  // (ingest_build, option set)
 // ingest
 cellector_status ingest_stage_host_coo(cellector_ctx *c, uint64_t nnz, const uint32_t *locus0,
                                        const uint32_t *cell0, const uint32_t *alt, const uint32_t *ref);

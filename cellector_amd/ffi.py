@@ -50,6 +50,8 @@ SIGNATURES = {
     "cellector_em_threshold": (_i, [_vp, _d]),
     "cellector_em_finish": (_i, [_vp, _vp]),
     "cellector_em_iteration": (_i, [_vp, _d, _vp]),
+    "cellector_iter_resolution": (_i, [_vp, _vp]),
+    "cellector_iter_resolved_cells": (_i, [_vp, _vp]),
     "cellector_iter_cell_outputs": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_iter_locus_outputs": (_i, [_vp] + [_vp] * 8),
     "cellector_loci_mask": (_i, [_vp, _vp]),
@@ -78,6 +80,10 @@ class EngineInfo(C.Structure):
 class IterSummary(C.Structure):
     _fields_ = [("any_change", C.c_int32), ("n_new_excluded", _u64), ("n_rescued", _u64), ("n_excluded", _u64),
                 ("n_loci_filtered", _u64), ("median", _d), ("iqr", _d), ("threshold", _d), ("n_near_threshold", _u64)]
+
+
+class Resolution(C.Structure):
+    _fields_ = [("n_evaluated", _u64), ("n_flags_changed", _u64), ("changed", C.c_uint32), ("mode", C.c_uint32)]
 
 
 class CellectorError(RuntimeError):
@@ -288,6 +294,20 @@ class Cellector:
             if not s.any_change:
                 break
         return out
+
+    def resolution(self):
+        """What option resolve_ties did in the last iteration (cellector_iter_resolution): cells evaluated with the reference's
+        arithmetic, exclusion flags it changed, bits 1/2/4 = median/iqr/threshold changed, the option's value."""
+        r = Resolution()
+        self._ck(self._lib.cellector_iter_resolution(self.h, C.byref(r)))
+        return r
+
+    def resolved_cells(self):
+        """The local indices of the cells option resolve_ties evaluated in the last iteration (sorted)."""
+        ids = np.zeros(self.resolution().n_evaluated, np.uint32)
+        if ids.size:
+            self._ck(self._lib.cellector_iter_resolved_cells(self.h, _p(ids)))
+        return np.sort(ids)
 
     def cell_outputs(self):
         n = self.n_local

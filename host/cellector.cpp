@@ -171,6 +171,7 @@ struct Params {
     int device = -1;                                   // extension: ONE GPU to run on
     std::vector<int> devices;                          // extension: the GPUs to shard the cells over (default: GPU 0)
     bool devices_auto = false;                         // --devices auto: as many visible GPUs as the input can feed
+    bool resolve_near_ties = false;                    // extension: option resolve_ties (single GPU)
 };
 
 const char *USAGE =
@@ -193,7 +194,10 @@ const char *USAGE =
     "        --device <n>                                                   run on this one GPU (not in the reference)\n"
     "        --devices <a,b,...>                                            GPUs to shard the cells over, RCCL exchanges between them (not in\n"
     "                                                                       the reference; default: GPU 0; `auto`: one visible GPU per 4 GB of\n"
-    "                                                                       alt.mtx text; a GPU listed twice = two logical shards on it)\n";
+    "                                                                       alt.mtx text; a GPU listed twice = two logical shards on it)\n"
+    "        --resolve_near_ties <true|false>                               evaluate the cells next to the median, the quartiles and the\n"
+    "                                                                       threshold with the reference's own arithmetic, so that they get\n"
+    "                                                                       the reference's bits (not in the reference; default false; one GPU)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -217,7 +221,8 @@ Params load_params(int argc, char **argv)
                                                               {"-g", "ground_truth"}, {"-v", "vcf"}};
     static const char *known[] = {"output_directory", "ref", "alt", "barcodes", "min_alt", "min_ref", "ground_truth",
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
-                                  "expected_percent_minority", "min_loci_for_assignment", "device", "devices"};
+                                  "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
+                                  "resolve_near_ties"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -264,6 +269,13 @@ Params load_params(int argc, char **argv)
             for (const std::string &t : split(got["devices"], ',')) p.devices.push_back((int)parse_usize("devices", t));
     }
     if (got.count("device") && got.count("devices")) die(1, "error: The argument '--device <n>' cannot be used with '--devices <a,b,...>'");
+    if (got.count("resolve_near_ties")) {
+        const std::string &v = got["resolve_near_ties"];
+        if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --resolve_near_ties: expected true or false");
+        p.resolve_near_ties = v == "true";
+    }
+    if (p.resolve_near_ties && (p.devices_auto || p.devices.size() > 1))
+        die(1, "error: The argument '--resolve_near_ties true' works on one GPU and cannot be used with '--devices <a,b,...>'");
     return p;
 }
 
@@ -420,6 +432,7 @@ int main(int argc, char **argv)
     if (const char *e = getenv("CELLECTOR_ENGINE")) g.ck(cellector_set_option(g.c, "engine", atoi(e)), "engine");
     if (const char *e = getenv("CELLECTOR_BANK_ORDER")) g.ck(cellector_set_option(g.c, "bank_order", atoi(e)), "bank_order");
     g.ck(cellector_set_option(g.c, "keep_coo", params.vcf ? 1 : 0), "option");
+    if (params.resolve_near_ties) g.ck(cellector_set_option(g.c, "resolve_ties", 1), "resolve_near_ties");
     lap("barcodes + device init");
     g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     lap("load_mtx (text -> device)");
@@ -459,7 +472,7 @@ int main(int argc, char **argv)
                (unsigned long long)s.n_new_excluded, (unsigned long long)s.n_rescued, (unsigned long long)(iteration + 1));
         printf("median normalized log likelihood %s with interquartile range %s, threshold %s\n", fmt(s.median).c_str(),
                fmt(s.iqr).c_str(), fmt(s.threshold).c_str());
-        if (s.n_near_threshold)  // stderr only: stdout stays byte-compatible with main.rs:338-339
+        if (s.n_near_threshold && !params.resolve_near_ties)  // stderr only: stdout stays byte-compatible with main.rs:338-339
             fprintf(stderr, "warning: iteration %llu: %llu cell(s) within 1e-9 (relative) of the threshold %s; the device's "
                             "log-pmf arithmetic differs from the reference's by ~1e-11, so their anomaly flag may differ from "
                             "the reference's\n", (unsigned long long)(iteration + 1), (unsigned long long)s.n_near_threshold,

@@ -114,7 +114,18 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * "bank_order" (engine 2, default 1: the tile builder orders every row's entries and the rows of a slice against LDS bank
  * conflicts; 0 keeps file order, the layout whose per-cell sums do not depend on which cells share a shard),
  * "t2_tiles" (engine 2, deep coverage: the cell side of the totals 5..8 (8, the default of a matrix with more than 3 % of
- * its entries outside 1..4), or 5..6 (6), walks a second tile set with chunk tables in LDS; 0: evaluated entry by entry). */
+ * its entries outside 1..4), or 5..6 (6), walks a second tile set with chunk tables in LDS; 0: evaluated entry by entry),
+ * "resolve_ties" (engines 1 and 2, single-device ctx only, default 0 = off: 1 = inside cellector_em_threshold, the cells
+ * whose normalised LL lies within 2 * band * max(1, |v|) of one of the six order statistics v behind the median and the
+ * quartiles, and then of the threshold, are evaluated again with the reference's own arithmetic — its ln_gamma
+ * differences, the C library's log and the file order of the cell's entries — and their LL and normalised LL replaced:
+ * median, iqr, threshold and the exclusion flags are then the reference's bits (band: see n_near_threshold);
+ * 2 = every cell is evaluated so (diagnostic: checks the band argument).  Set it before the ingest: the ingest then keeps
+ * every cell's entries in file order as well (8 more bytes per entry), the order the reference adds a cell's terms in; set
+ * after an ingest without it, 1 and 2 are refused.  A multi-device ctx or one with a communicator of more than one rank
+ * refuses 1 and 2 with CELLECTOR_EINVAL, and so does a host whose C library log is not the one the device repeats
+ * (glibc >= 2.28, FMA variant: checked on a few arguments).  Off: no launches, no allocations.
+ * See cellector_iter_resolution). */
 cellector_status cellector_set_option(cellector_ctx *ctx, const char *key, int64_t value);
 
 /* ---- sharding (before ingest) --------------------------------------------------------------- */
@@ -205,7 +216,8 @@ typedef struct {
      * LL at vartrix-like depth (alpha + beta ~ 1e4: the band is its 1e-9 floor), 1e-8 at alpha + beta ~ 1e6 — so such
      * a cell could fall on the other side of main.rs:330-332's strict `<` in the reference.  Non-zero = the
      * bit-identical-assignment claim does not cover those cells of this iteration.  host/cellector prints one
-     * stderr warning.  (Option ref_arith, engine 1, evaluates the reference's own formula instead.) */
+     * stderr warning.  (Option ref_arith, engine 1, evaluates the reference's own formula instead; option
+     * resolve_ties resolves these cells: cellector_iter_resolution.) */
     uint64_t n_near_threshold;
 } cellector_iter_summary;
 
@@ -224,6 +236,17 @@ cellector_status cellector_em_finish(cellector_ctx *ctx, cellector_iter_summary 
 /* single shard: A, B, C back to back */
 cellector_status cellector_em_iteration(cellector_ctx *ctx, double iqr_multiple,
                                         cellector_iter_summary *out);
+
+/* What option resolve_ties did in the last iteration (all zero when it was off, and on a multi-device ctx). */
+typedef struct {
+    uint64_t n_evaluated;      /* cells evaluated with the reference's arithmetic                                     */
+    uint64_t n_flags_changed;  /* exclusion flags that differ from those the device keys and threshold alone give      */
+    uint32_t changed;          /* bits that changed: 1 median, 2 iqr, 4 threshold                                    */
+    uint32_t mode;             /* the option's value in that iteration (1 or 2; 0: nothing was resolved)              */
+} cellector_resolution_t;
+cellector_status cellector_iter_resolution(const cellector_ctx *ctx, cellector_resolution_t *out);
+/* ... and which cells it evaluated: n_evaluated local cell indices (order unspecified); nothing when it was off. */
+cellector_status cellector_iter_resolved_cells(const cellector_ctx *ctx, uint32_t *ids /*[n_evaluated]*/);
 
 /* outputs of the last iteration (host buffers; any pointer may be NULL) */
 cellector_status cellector_iter_cell_outputs(const cellector_ctx *ctx, double *ll, double *expected_ll,

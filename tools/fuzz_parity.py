@@ -2,11 +2,15 @@
 """Randomised parity sweep (needs an MI355X): whole runs of the HIP path against the CPU oracle on matrices of random shape,
 density, minority share and count distribution — the checks of tests/test_gpu_parity.py on inputs nobody picked by hand.
 
-  python tools/fuzz_parity.py [--cases 40] [--seed 1] [--max-cells 60000]
+  python tools/fuzz_parity.py [--cases 40] [--seed 1] [--max-cells 60000] [--resolve-ties]
 
 Every case: ingest (device generator, then counts widened at random so that all overflow tiers occur), both engines or
 engine 2 with a random option set (locus-pass form, overlap, two shards), EM loop until the oracle stops, posteriors,
-assignments.  Prints one line per case and a summary; exits non-zero on the first mismatch."""
+assignments.  Prints one line per case and a summary; exits non-zero on the first mismatch.
+
+--resolve-ties: every single-device case runs a second time with option resolve_ties (set before the ingest) and must then
+match the oracle exactly in every iteration — median, iqr, threshold bits, exclusion flags, change counts — including the
+cases the plain comparison reports as undecidable (cells on the threshold to 1e-9); the summary counts both."""
 import argparse
 import os
 import sys
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--cases", type=int, default=40)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-cells", type=int, default=60000)
+    ap.add_argument("--resolve-ties", action="store_true", help="also run every single-device case with option resolve_ties")
     args = ap.parse_args()
     from cellector_amd import Cellector, ffi, synth
     from oracle import binding as ob
@@ -34,6 +39,7 @@ def main():
     mods = dict(ffi=ffi, synth=synth, ob=ob, engine=2)
     rng = np.random.default_rng(args.seed)
     t_all = time.time()
+    n_resolved = n_resolved_undecidable = 0
     for case in range(args.cases):
         N = int(rng.choice([1, 3, 70, 700, 1100, 5000, 20000, args.max_cells]))
         L = int(rng.choice([50, 400, 1500, 4200, 9000]))  # (one or two loci: every cell ties with thousands of others)
@@ -89,10 +95,48 @@ def main():
                     ok = None  # cells sit on the threshold to 1e-9: the comparison cannot decide, not a mismatch
             g.close()
         o.close()
-        print(f"{desc}: {'ok' if ok else ('undecidable (near-ties)' if ok is None else 'MISMATCH')} ({time.time() - t0:.1f} s)", flush=True)
+        res = ""
+        if args.resolve_ties and not two_shards and ok is not False:
+            res_ok = run_resolved(Cellector, ob, engine, opts, L, N, lo, ce, al, re, min_alt, min_ref)
+            n_resolved += 1
+            n_resolved_undecidable += ok is None
+            res = "; resolve_ties: " + ("exact" if res_ok else "MISMATCH")
+            if not res_ok:
+                ok = False
+        print(f"{desc}: {'ok' if ok else ('undecidable (near-ties)' if ok is None else 'MISMATCH')}{res} ({time.time() - t0:.1f} s)",
+              flush=True)
         if ok is False:
             sys.exit(1)
     print(f"{args.cases} cases ok in {time.time() - t_all:.0f} s")
+    if args.resolve_ties:
+        print(f"resolve_ties: {n_resolved} cases exact, {n_resolved_undecidable} of them undecidable without the option")
+
+
+def run_resolved(Cellector, ob, engine, opts, L, N, lo, ce, al, re, min_alt, min_ref):
+    """one device, option resolve_ties: median / iqr / threshold bits, flags and change counts of every iteration are the oracle's"""
+    o = ob.Oracle.from_coo(L, N, lo, ce, al, re, min_alt, min_ref)
+    g = Cellector(0)
+    g.set_option("engine", engine)
+    for k, v in opts.items():
+        g.set_option(k, v)
+    g.set_option("resolve_ties", 1)
+    g.load_coo(L, N, lo, ce, al, re, min_alt, min_ref)
+    ok = True
+    if o.loci_used and N:
+        for _ in range(30):
+            sg, so = g.em_iteration(5.0), o.em_iteration(5.0)
+            if not ((sg.median, sg.iqr, sg.threshold) == (so.median, so.iqr, so.threshold)
+                    and np.array_equal(g.excluded(), o.excluded())
+                    and (sg.any_change, sg.n_new_excluded, sg.n_rescued) == (so.any_change, so.n_new_excluded, so.n_rescued)):
+                print(f"  resolve_ties mismatch: device {(sg.median, sg.iqr, sg.threshold)} oracle {(so.median, so.iqr, so.threshold)}",
+                      flush=True)
+                ok = False
+                break
+            if not so.any_change:
+                break
+    g.close()
+    o.close()
+    return ok
 
 
 def run_two_shards(Cellector, ffi, o, L, N, lo, ce, al, re, min_alt, min_ref, opts):
