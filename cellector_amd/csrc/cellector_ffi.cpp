@@ -100,34 +100,13 @@ void timer_collect(cellector_ctx *c)
     }
 }
 
-static void free_matrix(cellector_ctx *c)
+// A reload (and cellector_destroy) drops the matrix, engine 2's layouts and what the calls left for each other as a whole:
+// every device buffer of the three groups goes back, every other field of them returns to its default.
+static void drop_matrix(cellector_ctx *c)
 {
-    dev_free(c->coo_locus); dev_free(c->coo_cell); dev_free(c->coo_alt); dev_free(c->coo_ref);
-    dev_free(c->csr_ptr); dev_free(c->csr_ent); dev_free(c->csc_ptr); dev_free(c->csc_ent);
-    dev_free(c->locus_ids); dev_free(c->s_alt); dev_free(c->s_ref); dev_free(c->n_ent); dev_free(c->to_used);
-    dev_free(c->ab); dev_free(c->ab6); dev_free(c->mask); dev_free(c->mask_next);
-    dev_free(c->flags); dev_free(c->flags_new); dev_free(c->ll); dev_free(c->ell); dev_free(c->nloci);
-    dev_free(c->post);
-    dev_free(c->res_cand); dev_free(c->res_key); dev_free(c->res_done); dev_free(c->res_ent);
-    c->res_n = 0;
-    c->res_nnz = 0;
-    c->res_last_mode = 0;
-    tiled_free(c);
-    if (c->own_pass1) dev_free(c->x_pass1);
-    if (c->own_norm) dev_free(c->x_norm);
-    if (c->own_locus) dev_free(c->x_locus);
-    c->x_pass1 = c->x_norm = c->x_locus = nullptr;
-    c->own_pass1 = c->own_norm = c->own_locus = true;
-    c->n_pass1 = c->n_norm = c->n_locus = 0;
-    c->coo_n = 0; c->L = c->nnz = c->nloc = 0;
-    c->state = cellector_ctx::ST_EMPTY;
-    c->em_phase = 0; c->iteration = 0; c->have_iter = false; c->n_excluded_global = 0;
-    // nothing built ahead for the previous matrix survives a reload: the next em_begin must form alpha/beta and the
-    // tables itself (em_finish leaves tables_prebuilt set; the new matrix' table buffers are fresh allocations)
-    c->tables_prebuilt = false; c->prebuilt_expected = false; c->work_zeroed = false; c->ovf_locus_pending = false;
-    c->cell_join_pending = false;
-    // nor does per-iteration state: the fused locus filter of an unfinished iteration, the kept exclusion-set counts
-    c->filter_fused = false; c->tally_valid = false;
+    static_cast<CtxCarry &>(*c) = CtxCarry();
+    static_cast<CtxTiled &>(*c) = CtxTiled();
+    static_cast<CtxMatrix &>(*c) = CtxMatrix();
 }
 
 // the side stream gets the lowest priority the device offers: its kernels should only fill slots the main stream's
@@ -145,7 +124,7 @@ static bool create_side_stream(hipStream_t *out)
     } while (0)
 #define SETDEV(c) HIPCHK((c), hipSetDevice((c)->device))
 
-// ---- caching layer under dev_alloc / dev_free (see ctx.h) -------------------------------------------------------
+// ---- caching layer under dev_alloc / DevBuf (see ctx.h) ---------------------------------------------------------
 namespace {
 struct DevBlock { void *p; size_t bytes; int device; };
 std::mutex g_cache_mu;
@@ -268,13 +247,13 @@ cellector_status cellector_create(cellector_ctx **out, int device_id)
         f *= (double)i;
         lf[i] = std::log(f);
     }
-    bool ok = hipMalloc((void **)&c->lf, sizeof lf) == hipSuccess &&
+    bool ok = dev_alloc(c, &c->lf, LF_TABLE_N) == CELLECTOR_OK &&
               hipMemcpy(c->lf, lf, sizeof lf, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMalloc((void **)&c->d_counters, 8 * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc((void **)&c->sel_hist, CELLECTOR_SEL_HIST_WORDS * sizeof(uint32_t)) == hipSuccess &&
+              dev_alloc(c, &c->d_counters, 8) == CELLECTOR_OK &&
+              dev_alloc(c, &c->sel_hist, CELLECTOR_SEL_HIST_WORDS) == CELLECTOR_OK &&
               hipMemset(c->sel_hist, 0, CELLECTOR_SEL_HIST_WORDS * sizeof(uint32_t)) == hipSuccess &&  // k_sel_finish re-zeroes
-              hipMalloc((void **)&c->sel_state, 4 * SEL_T * sizeof(uint64_t)) == hipSuccess &&
-              hipMalloc((void **)&c->sel_out, 16 * sizeof(double)) == hipSuccess &&
+              dev_alloc(c, &c->sel_state, 4 * SEL_T) == CELLECTOR_OK &&
+              dev_alloc(c, &c->sel_out, 16) == CELLECTOR_OK &&
               hipHostMalloc((void **)&c->h_sel, 32 * sizeof(double)) == hipSuccess &&
               (memset(c->h_sel, 0, 32 * sizeof(double)), true) &&
               hipHostGetDevicePointer((void **)&c->h_sum_dev, c->h_sel, 0) == hipSuccess &&
@@ -342,10 +321,11 @@ void cellector_destroy(cellector_ctx *c)
     timer_collect(c);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     c->ev_pool.clear();
-    free_matrix(c);
-    dev_free(c->lf); dev_free(c->d_counters); dev_free(c->sel_hist); dev_free(c->sel_state); dev_free(c->sel_out);
-    dev_free(c->sel_list); dev_free(c->seld_hist); dev_free(c->seld_state);
-    dev_free(c->res_cnt); dev_free(c->res_dev);
+    // (the device buffers go before the streams)
+    drop_matrix(c);
+    c->lf.reset(); c->d_counters.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
+    c->sel_list.reset(); c->seld_hist.reset(); c->seld_state.reset();
+    c->res_cnt.reset(); c->res_dev.reset();
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
@@ -538,8 +518,8 @@ cellector_status cellector_set_shard(cellector_ctx *c, uint64_t b, uint64_t e)
         return ctx_fail(c, CELLECTOR_EINVAL, "a ctx with a communicator shards the cells itself (contiguous ranges by rank: cellector_set_partition)");
     REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "set_shard must precede ingest");
     REQUIRE(c, b <= e, "empty or inverted shard range");
-    c->cell_begin = b;
-    c->cell_end = e;
+    c->req_cell_begin = b;
+    c->req_cell_end = e;
     c->tally_valid = false;  // (the ingest that must follow rebuilds the counts anyway)
     return CELLECTOR_OK;
 }
@@ -550,12 +530,10 @@ static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint
     SETDEV(c);
     {
         // keep a caller-bound PASS1 buffer across the reset
-        double *bound = c->own_pass1 ? nullptr : c->x_pass1;
-        uint64_t nb = c->n_pass1;
-        uint64_t cb = c->cell_begin, ce = c->cell_end;
-        free_matrix(c);
-        c->cell_begin = cb; c->cell_end = ce;
-        if (bound) { c->x_pass1 = bound; c->n_pass1 = nb; c->own_pass1 = false; }
+        double *bound = c->x_pass1 != c->x_pass1_own.get() ? c->x_pass1 : nullptr;
+        const uint64_t nb = c->n_pass1;
+        drop_matrix(c);
+        if (bound) { c->x_pass1 = bound; c->n_pass1 = nb; }
     }
     REQUIRE(c, total_loci <= 0xffffffffull && total_cells <= 0xffffffffull, "dims exceed 32-bit indices");
     c->total_loci = total_loci;
@@ -568,6 +546,9 @@ static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint
             return ctx_fail(c, CELLECTOR_EINVAL, "the partition covers %llu cells, the matrix has %llu",
                             (unsigned long long)c->comm.bounds[c->comm.n], (unsigned long long)total_cells);
         comm_range(c->comm, total_cells, c->comm.rank, &c->cell_begin, &c->cell_end);
+    } else {
+        c->cell_begin = c->req_cell_begin;
+        c->cell_end = c->req_cell_end;
     }
     if (c->cell_end > total_cells) c->cell_end = total_cells;
     if (c->cell_begin > c->cell_end) c->cell_begin = c->cell_end;
@@ -576,8 +557,8 @@ static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint
     if (c->x_pass1) {
         REQUIRE(c, c->n_pass1 >= need, "bound PASS1 exchange buffer too small");
     } else {
-        CHK(dev_alloc(c, &c->x_pass1, need));
-        c->own_pass1 = true;
+        CHK(dev_alloc(c, &c->x_pass1_own, need));
+        c->x_pass1 = c->x_pass1_own;
     }
     c->n_pass1 = need;
     return CELLECTOR_OK;
@@ -644,11 +625,11 @@ cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path,
     return s;
 }
 // ... step 2: a shard takes over its routed entries (arrays on its own device, cell index local, file order) as its staged COO.
-cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, uint32_t *locus, uint32_t *cell,
-                                  uint16_t *alt, uint16_t *ref, uint64_t n, bool sorted)
+cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, DevBuf<uint32_t> locus,
+                                  DevBuf<uint32_t> cell, DevBuf<uint16_t> alt, DevBuf<uint16_t> ref, uint64_t n, bool sorted)
 {
     CHK(begin_ingest(c, total_loci, total_cells));
-    c->coo_locus = locus; c->coo_cell = cell; c->coo_alt = alt; c->coo_ref = ref;
+    c->coo_locus = std::move(locus); c->coo_cell = std::move(cell); c->coo_alt = std::move(alt); c->coo_ref = std::move(ref);
     c->coo_n = n;
     c->coo_sorted = sorted;
     CHK(ingest_pass1(c));
@@ -712,9 +693,9 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
     const uint64_t need_norm = comm_active(c->comm) ? comm_cells_per_rank(c->total_cells, c->comm.n) * (uint64_t)c->comm.n : c->total_cells;
     const uint64_t need_locus = (uint64_t)LB_PLANES * L + LC_COUNTERS;
     if (c->x_norm) REQUIRE(c, c->n_norm >= need_norm, "bound NORM exchange buffer too small");
-    else { CHK(dev_alloc(c, &c->x_norm, need_norm)); c->own_norm = true; }
+    else { CHK(dev_alloc(c, &c->x_norm_own, need_norm)); c->x_norm = c->x_norm_own; }
     if (c->x_locus) REQUIRE(c, c->n_locus >= need_locus, "bound LOCUS exchange buffer too small");
-    else { CHK(dev_alloc(c, &c->x_locus, need_locus)); c->own_locus = true; }
+    else { CHK(dev_alloc(c, &c->x_locus_own, need_locus)); c->x_locus = c->x_locus_own; }
     c->n_norm = need_norm;
     c->n_locus = need_locus;
     HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (need_norm ? need_norm : 1) * 8, c->stream));
@@ -739,7 +720,7 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
         CHK(tiled_build(c));
         // the packed by-locus CSC (8 B per entry: 16 GB at 2e9 entries) is only streamed by engine 1; engine 2 has built
         // its compact CSC and overflow CSC from it.  Engine 1 must therefore be chosen BEFORE the ingest.
-        dev_free(c->csc_ent);
+        c->csc_ent.reset();
     }
     if (timing) fprintf(stderr, "[timing]   tiled layouts           %8.3f s\n", lap_s(&t));
     dev_cache_trim(c->device);  // the ingest's big temporaries are done: hand this device's cached blocks back
@@ -870,13 +851,13 @@ cellector_status cellector_bind_exchange_buffer(cellector_ctx *c, cellector_xchg
     switch (which) {
     case CELLECTOR_XCHG_PASS1:
         REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "bind PASS1 before ingest");
-        if (c->own_pass1) dev_free(c->x_pass1);
-        c->x_pass1 = p; c->n_pass1 = n; c->own_pass1 = false;
+        c->x_pass1_own.reset();
+        c->x_pass1 = p; c->n_pass1 = n;
         break;
     case CELLECTOR_XCHG_NORM:
         REQUIRE(c, c->state != cellector_ctx::ST_READY || n >= c->total_cells, "NORM buffer too small");
-        if (c->own_norm) dev_free(c->x_norm);
-        c->x_norm = p; c->n_norm = n; c->own_norm = false;
+        c->x_norm_own.reset();
+        c->x_norm = p; c->n_norm = n;
         break;
     case CELLECTOR_XCHG_LOCUS:
         REQUIRE(c, c->state != cellector_ctx::ST_READY || n >= (uint64_t)LB_PLANES * c->L + LC_COUNTERS,
@@ -887,8 +868,8 @@ cellector_status cellector_bind_exchange_buffer(cellector_ctx *c, cellector_xchg
                                      hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        if (c->own_locus) dev_free(c->x_locus);
-        c->x_locus = p; c->n_locus = n; c->own_locus = false;
+        c->x_locus_own.reset();
+        c->x_locus = p; c->n_locus = n;
         break;
     default: return ctx_fail(c, CELLECTOR_EINVAL, "unknown exchange buffer");
     }
@@ -1193,13 +1174,12 @@ cellector_status cellector_final_allele_tallies(cellector_ctx *c, uint64_t *alt_
     REQUIRE(c, c->keep_coo, "final tallies need the staged COO (option keep_coo=1)");
     SETDEV(c);
     const uint64_t TL = c->total_loci;
-    uint64_t *d = nullptr;
+    DevBuf<uint64_t> d;
     CHK(dev_alloc(c, &d, 4 * TL));
-    cellector_status s = launch_final_tallies(c, d);
+    CHK(launch_final_tallies(c, d));
     std::vector<uint64_t> h(4 * TL);
-    if (s == CELLECTOR_OK) s = d2h(c, h.data(), d, 4 * TL * 8);
-    dev_free(d);
-    CHK(s);
+    CHK(d2h(c, h.data(), d, 4 * TL * 8));
+    d.reset();
     if (alt_min) memcpy(alt_min, h.data(), TL * 8);
     if (ref_min) memcpy(ref_min, h.data() + TL, TL * 8);
     if (alt_maj) memcpy(alt_maj, h.data() + 2 * TL, TL * 8);
@@ -1242,7 +1222,7 @@ cellector_status ffi_order_statistics(cellector_ctx *c, const double *keys, uint
 {
     REQUIRE(c, n_total > 0 && (keys || !n_local), "order statistics: no keys");
     SETDEV(c);
-    double *d_keys = nullptr;
+    DevBuf<double> d_keys;
     CHK(dev_alloc(c, &d_keys, n_local ? n_local : 1));
     cellector_status st = CELLECTOR_OK;
     if (n_local && hipMemcpyAsync(d_keys, keys, n_local * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
@@ -1252,7 +1232,6 @@ cellector_status ffi_order_statistics(cellector_ctx *c, const double *keys, uint
                                                        : select_threshold(c, d_keys, n_local, iqr_multiple);
     if (st == CELLECTOR_OK && out3) st = d2h(c, out3, c->sel_out + 8, 3 * sizeof(double));
     else (void)hipStreamSynchronize(c->stream);
-    dev_free(d_keys);
     return st;
 }
 

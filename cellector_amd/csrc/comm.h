@@ -6,6 +6,7 @@
 //   * a same-process group for logical shards that SHARE a device (RCCL refuses duplicate devices): host barrier +
 //     device-side sums in rank order.  Tests and one-GPU rehearsals of the sharded path use it.
 #pragma once
+// (included through ctx.h, which defines DevBuf first)
 #include <condition_variable>
 #include <cstdint>
 #include <mutex>
@@ -38,7 +39,7 @@ struct Comm {
     uint64_t bounds[CELLECTOR_MAX_SHARDS + 1] = {};
     void *nccl = nullptr;         // ncclComm_t of this shard (RCCL transport)
     LocalGroup *local = nullptr;  // same-process transport (shared by the group's shards; owned by the root ctx)
-    double *tmp = nullptr;        // local transport: scratch for the sums, sized on first use
+    DevBuf<double> tmp;           // local transport: scratch for the sums, sized on first use
     uint64_t tmp_n = 0;
 };
 

@@ -5,7 +5,6 @@
 
 #include <rccl/rccl.h>
 
-#include "comm.h"
 #include "ctx.h"
 
 int comm_status_ok() { return (int)CELLECTOR_OK; }
@@ -136,7 +135,7 @@ void comm_destroy(cellector_ctx *c)
         (void)g_rccl.CommDestroy((ncclComm_t)c->comm.nccl);
     }
     c->comm.nccl = nullptr;
-    dev_free(c->comm.tmp);
+    c->comm.tmp.reset();
     c->comm.tmp_n = 0;
     c->comm.local = nullptr;  // (owned by the root)
     c->comm.n = 1;
@@ -187,12 +186,11 @@ static int local_allreduce(cellector_ctx *c, T *buf, uint64_t count)
     LocalGroup *g = c->comm.local;
     const uint64_t need = (count * sizeof(T) + 7) / 8;  // (the scratch is kept in doubles)
     if (c->comm.tmp_n < need) {
-        dev_free(c->comm.tmp);
         c->comm.tmp_n = 0;
         if (dev_alloc(c, &c->comm.tmp, need) != CELLECTOR_OK) return (int)CELLECTOR_ENOMEM;
         c->comm.tmp_n = need;
     }
-    T *tmp = reinterpret_cast<T *>(c->comm.tmp);
+    T *tmp = reinterpret_cast<T *>(c->comm.tmp.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));  // this shard's contribution is complete
     g->bufs[c->comm.rank] = buf;
     BARRIER(c, g);

@@ -407,8 +407,8 @@ cellector_status launch_ab_from_host(cellector_ctx *c, const double *alpha, cons
                                      const uint8_t *mask)
 {
     const uint64_t L = c->L;
-    double *d_a = nullptr, *d_b = nullptr;
-    uint8_t *d_m = nullptr;
+    DevBuf<double> d_a, d_b;
+    DevBuf<uint8_t> d_m;
     CHK(dev_alloc(c, &d_a, L));
     CHK(dev_alloc(c, &d_b, L));
     HIPCHK(c, hipMemcpyAsync(d_a, alpha, L * 8, hipMemcpyHostToDevice, c->stream));
@@ -420,7 +420,6 @@ cellector_status launch_ab_from_host(cellector_ctx *c, const double *alpha, cons
     hipLaunchKernelGGL(k_ab_from_arrays, dim3(grid_for(L, 256)), dim3(256), 0, c->stream, L, d_a, d_b, d_m, c->ab);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dev_free(d_a); dev_free(d_b); dev_free(d_m);
     return CELLECTOR_OK;
 }
 

@@ -75,7 +75,7 @@ __global__ void k_scan_add(uint64_t *__restrict__ data, uint64_t n, const uint64
 static cellector_status scan_rec(cellector_ctx *c, uint64_t *data, uint64_t n)
 {
     const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    uint64_t *sums = nullptr;
+    DevBuf<uint64_t> sums;
     if (nb > 1) CHK(dev_alloc(c, &sums, nb));
     hipLaunchKernelGGL(k_scan_block, dim3((unsigned)nb), dim3(IB), 0, c->stream, data, n, sums);
     HIPCHK(c, hipGetLastError());
@@ -84,7 +84,6 @@ static cellector_status scan_rec(cellector_ctx *c, uint64_t *data, uint64_t n)
         hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(IB), 0, c->stream, data, n, sums);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dev_free(sums);
     }
     return CELLECTOR_OK;
 }
@@ -112,36 +111,36 @@ cellector_status dev_sort_pairs_u32_u64(cellector_ctx *c, uint32_t *keys_in, uin
     size_t tmp_bytes = 0;
     HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u,
                                         (unsigned)end_bit, c->stream));
-    char *tmp = nullptr;
+    DevBuf<char> tmp;
     CHK(dev_alloc(c, &tmp, tmp_bytes));
-    hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u,
+    hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u,
                                              (unsigned)end_bit, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(tmp);
+    tmp.reset();
     HIPCHK(c, e);
     return CELLECTOR_OK;
 }
 
 // The same sort with the caller's two buffer pairs as the sort's ping-pong storage (both get overwritten; on return *keys /
-// *vals point at the sorted data, *keys_alt / *vals_alt at the other buffers).  The form above must leave its input alone
+// *vals hold the sorted data, *keys_alt / *vals_alt the other buffers).  The form above must leave its input alone
 // and therefore asks for a second pair of buffers as temporary storage: 24 GB at 2e9 pairs — fresh VRAM whenever the caching
 // layer has no block of that size, 0.7-1.5 s of mapping in one run out of three of the 1M x 200k ingest.
-cellector_status dev_sort_pairs_u32_u64_inplace(cellector_ctx *c, uint32_t **keys, uint32_t **keys_alt, uint64_t **vals,
-                                                uint64_t **vals_alt, uint64_t n, int end_bit)
+cellector_status dev_sort_pairs_u32_u64_inplace(cellector_ctx *c, DevBuf<uint32_t> *keys, DevBuf<uint32_t> *keys_alt,
+                                                DevBuf<uint64_t> *vals, DevBuf<uint64_t> *vals_alt, uint64_t n, int end_bit)
 {
     if (n == 0) return CELLECTOR_OK;
-    rocprim::double_buffer<uint32_t> kb(*keys, *keys_alt);
-    rocprim::double_buffer<uint64_t> vb(*vals, *vals_alt);
+    rocprim::double_buffer<uint32_t> kb(keys->get(), keys_alt->get());
+    rocprim::double_buffer<uint64_t> vb(vals->get(), vals_alt->get());
     size_t tmp_bytes = 0;
     HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)n, 0u, (unsigned)end_bit, c->stream));
-    char *tmp = nullptr;
+    DevBuf<char> tmp;
     CHK(dev_alloc(c, &tmp, tmp_bytes));
-    hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)n, 0u, (unsigned)end_bit, c->stream);
+    hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, kb, vb, (size_t)n, 0u, (unsigned)end_bit, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(tmp);
+    tmp.reset();
     HIPCHK(c, e);
-    *keys = kb.current(); *keys_alt = kb.alternate();
-    *vals = vb.current(); *vals_alt = vb.alternate();
+    if (kb.current() != keys->get()) std::swap(*keys, *keys_alt);
+    if (vb.current() != vals->get()) std::swap(*vals, *vals_alt);
     return CELLECTOR_OK;
 }
 
@@ -353,8 +352,6 @@ __global__ __launch_bounds__(256) void k_coo_take_range(uint64_t n, const uint32
     o_alt[p] = alt[i];
     o_ref[p] = ref[i];
 }
-// src holds the staged COO of ALL cells (cell index global).  Writes the entries of cells [cb, ce) — cell index made local,
-// order kept — into four new arrays on src's device; `keep` is caller scratch of n + 1 words.
 // entries per (global) cell of a staged piece, on the host: what the nnz-balancing partition of a multi-device ingest is cut from
 __global__ __launch_bounds__(256) void k_cell_hist(uint64_t n, const uint32_t *__restrict__ cell, uint64_t total_cells, uint32_t *__restrict__ hist)
 {
@@ -363,7 +360,7 @@ __global__ __launch_bounds__(256) void k_cell_hist(uint64_t n, const uint32_t *_
 }
 cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell, uint64_t n, uint64_t total_cells, std::vector<uint32_t> *out)
 {
-    uint32_t *d_hist = nullptr;
+    DevBuf<uint32_t> d_hist;
     out->assign(total_cells, 0u);
     if (!total_cells) return CELLECTOR_OK;
     CHK(dev_alloc(c, &d_hist, total_cells));
@@ -373,27 +370,26 @@ cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell,
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out->data(), d_hist, total_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_hist);
     if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "cell histogram: %s", hipGetErrorString(e));
     return CELLECTOR_OK;
 }
 
-cellector_status ingest_split_coo(cellector_ctx *src, uint64_t cb, uint64_t ce, uint64_t *keep, uint32_t **o_locus, uint32_t **o_cell,
-                                  uint16_t **o_alt, uint16_t **o_ref, uint64_t *n_out)
+cellector_status ingest_split_coo(cellector_ctx *c, const uint32_t *locus, const uint32_t *cell, const uint16_t *alt, const uint16_t *ref,
+                                  uint64_t n, uint64_t cb, uint64_t ce, uint64_t *keep, DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell,
+                                  DevBuf<uint16_t> *o_alt, DevBuf<uint16_t> *o_ref, uint64_t *n_out)
 {
-    const uint64_t n = src->coo_n;
     const unsigned g = (unsigned)((n + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_coo_in_range, dim3(g), dim3(256), 0, src->stream, n, src->coo_cell, cb, ce, keep);
-    HIPCHK(src, hipGetLastError());
+    hipLaunchKernelGGL(k_coo_in_range, dim3(g), dim3(256), 0, c->stream, n, cell, cb, ce, keep);
+    HIPCHK(c, hipGetLastError());
     uint64_t kept = 0;
-    CHK(dev_exclusive_scan_u64(src, keep, n + 1, &kept));
-    CHK(dev_alloc(src, o_locus, kept)); CHK(dev_alloc(src, o_cell, kept));
-    CHK(dev_alloc(src, o_alt, kept)); CHK(dev_alloc(src, o_ref, kept));
+    CHK(dev_exclusive_scan_u64(c, keep, n + 1, &kept));
+    CHK(dev_alloc(c, o_locus, kept)); CHK(dev_alloc(c, o_cell, kept));
+    CHK(dev_alloc(c, o_alt, kept)); CHK(dev_alloc(c, o_ref, kept));
     if (n)
-        hipLaunchKernelGGL(k_coo_take_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, src->stream, n, src->coo_locus, src->coo_cell,
-                           src->coo_alt, src->coo_ref, cb, ce, keep, *o_locus, *o_cell, *o_alt, *o_ref);
-    HIPCHK(src, hipGetLastError());
-    HIPCHK(src, hipStreamSynchronize(src->stream));
+        hipLaunchKernelGGL(k_coo_take_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, locus, cell, alt, ref, cb, ce,
+                           keep, o_locus->get(), o_cell->get(), o_alt->get(), o_ref->get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_out = kept;
     return CELLECTOR_OK;
 }
@@ -446,9 +442,9 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
 
     // ---- unsorted input: stable sort of the staged COO by locus
     if (!c->coo_sorted && n) {
-        uint32_t *k_out = nullptr, *cell_o = nullptr;
-        uint16_t *alt_o = nullptr, *ref_o = nullptr;
-        uint64_t *perm = nullptr, *perm_o = nullptr;
+        DevBuf<uint32_t> k_out, cell_o;
+        DevBuf<uint16_t> alt_o, ref_o;
+        DevBuf<uint64_t> perm, perm_o;
         CHK(dev_alloc(c, &k_out, n)); CHK(dev_alloc(c, &perm, n)); CHK(dev_alloc(c, &perm_o, n));
         hipLaunchKernelGGL(k_iota_u64, dim3(g1(n)), dim3(IB), 0, c->stream, n, perm);
         int bits = 1;
@@ -459,21 +455,19 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
                            c->coo_ref, cell_o, alt_o, ref_o);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dev_free(c->coo_locus); dev_free(c->coo_cell); dev_free(c->coo_alt); dev_free(c->coo_ref);
-        dev_free(perm); dev_free(perm_o);
-        c->coo_locus = k_out; c->coo_cell = cell_o; c->coo_alt = alt_o; c->coo_ref = ref_o;
-        c->coo_sorted = true;
+        c->coo_locus = std::move(k_out); c->coo_cell = std::move(cell_o); c->coo_alt = std::move(alt_o); c->coo_ref = std::move(ref_o);
+        c->coo_sorted = true;  // (perm, perm_o go with this block)
     }
 
     lap("filter + compaction");
     // ---- counts and pointers
-    uint64_t *loc_cnt = nullptr, *col_cnt = nullptr;
+    DevBuf<uint64_t> loc_cnt;
     CHK(dev_alloc(c, &c->csr_ptr, nloc + 1));
     CHK(dev_alloc(c, &loc_cnt, TL + 1));
     CHK(dev_alloc(c, &c->csc_ptr, L + 1));
     HIPCHK(c, hipMemsetAsync(loc_cnt, 0, (TL + 1) * 8, c->stream));
     if (n)
-        hipLaunchKernelGGL(k_count, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo_locus, (unsigned long long *)loc_cnt);
+        hipLaunchKernelGGL(k_count, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo_locus, (unsigned long long *)loc_cnt.get());
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_gather_used_counts, dim3(g1(L + 1)), dim3(IB), 0, c->stream, L, c->locus_ids, loc_cnt,
                        c->csc_ptr);
@@ -485,8 +479,8 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
 
     lap("counts + scans");
     // ---- CSC = filtered file order; CSR = stable sort of the same entries by cell
-    uint32_t *key = nullptr, *key_o = nullptr;
-    uint64_t *val = nullptr;
+    DevBuf<uint32_t> key, key_o;
+    DevBuf<uint64_t> val;
     CHK(dev_alloc(c, &c->csc_ent, c->nnz)); CHK(dev_alloc(c, &c->csr_ent, c->nnz));
     CHK(dev_alloc(c, &key, c->nnz)); CHK(dev_alloc(c, &key_o, c->nnz)); CHK(dev_alloc(c, &val, c->nnz));
     lap("allocations");
@@ -504,11 +498,10 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     lap("sort by cell");
-    dev_free(key); dev_free(key_o); dev_free(val); dev_free(loc_cnt);
+    key.reset(); key_o.reset(); val.reset(); loc_cnt.reset();
     lap("frees");
-    (void)col_cnt;
     if (!c->keep_coo) {
-        dev_free(c->coo_locus); dev_free(c->coo_cell); dev_free(c->coo_alt); dev_free(c->coo_ref);
+        c->coo_locus.reset(); c->coo_cell.reset(); c->coo_alt.reset(); c->coo_ref.reset();
         c->coo_n = 0;
     }
     return CELLECTOR_OK;

@@ -435,9 +435,9 @@ bool host_tok_u64(const std::string &s, int idx, uint64_t *out)
 }
 
 struct DevText {
-    uint8_t *text = nullptr;
+    DevBuf<uint8_t> text;
     uint64_t n = 0, n_lines = 0;
-    uint64_t *seg_off = nullptr;  // newlines before each NL_SEG-byte segment (exclusive scan of k_nl_count)
+    DevBuf<uint64_t> seg_off;  // newlines before each NL_SEG-byte segment (exclusive scan of k_nl_count)
     uint64_t n_seg = 0;
 };
 
@@ -534,10 +534,11 @@ cellector_status split_lines(cellector_ctx *c, const FileBytes &fb, DevText *dt)
 
 // the windows' buffers, shared by the two files of a pair (pinning 3 x 257 MB takes ~0.05 s)
 struct PwBuffers {
-    uint8_t *pin[PW_NB] = {}, *dev[PW_NB] = {};
+    uint8_t *pin[PW_NB] = {};
+    DevBuf<uint8_t> dev[PW_NB];
     hipEvent_t ev_up[PW_NB] = {}, ev_free[PW_NB] = {};
     hipStream_t up = nullptr;
-    uint64_t *seg = nullptr;
+    DevBuf<uint64_t> seg;
     uint64_t window = 0;
     int n = 0;
     cellector_status make(cellector_ctx *c, uint64_t win, int count)
@@ -562,27 +563,23 @@ struct PwBuffers {
             if (ev_up[b]) (void)hipEventDestroy(ev_up[b]);
             if (ev_free[b]) (void)hipEventDestroy(ev_free[b]);
             if (pin[b]) (void)hipHostFree(pin[b]);
-            dev_free(dev[b]);
+            dev[b].reset();
         }
-        dev_free(seg);
+        seg.reset();
         if (up) (void)hipStreamDestroy(up);
     }
 };
 
 template <typename T>
-cellector_status grow_tokens(cellector_ctx *c, T **arr, uint64_t used, uint64_t new_cap)
+cellector_status grow_tokens(cellector_ctx *c, DevBuf<T> *arr, uint64_t used, uint64_t new_cap)
 {
-    T *bigger = nullptr;
+    DevBuf<T> bigger;
     CHK(dev_alloc(c, &bigger, new_cap));
     hipError_t e = hipSuccess;
     if (used) e = hipMemcpyAsync(bigger, *arr, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        dev_free(bigger);
-        return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
-    }
-    dev_free(*arr);
-    *arr = bigger;
+    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+    *arr = std::move(bigger);
     return CELLECTOR_OK;
 }
 
@@ -590,14 +587,15 @@ cellector_status grow_tokens(cellector_ctx *c, T **arr, uint64_t used, uint64_t 
 // allocated here (capacity from the header's entry count, grown if the file holds more lines)
 template <bool ALT>
 cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t data_off, PwBuffers &B, uint64_t cap_hint,
-                                uint32_t **o0, uint32_t **o1, uint32_t **o2, uint64_t *n_lines, unsigned long long *bad,
-                                uint64_t w_begin = 0, uint64_t w_end = ~0ull)
+                                DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1, DevBuf<uint32_t> *o2, uint64_t *n_lines,
+                                unsigned long long *bad, uint64_t w_begin = 0, uint64_t w_end = ~0ull)
 {
     // [w_begin, w_end): the windows this call takes (a multi-device ingest gives every GPU a range of them).  Line indices
     // are then LOCAL: the number of newlines before the line inside the range; the line that starts right behind the range's
     // last newline — in the next range's bytes — is still this call's (look-ahead).  *n_lines = newlines in the range.
     const uint64_t window = B.window;
-    uint8_t *const *pin = B.pin, *const *dev = B.dev;
+    uint8_t *const *pin = B.pin;
+    const DevBuf<uint8_t> *dev = B.dev;
     hipEvent_t *ev_up = B.ev_up, *ev_free = B.ev_free;
     hipStream_t up = B.up;
     uint64_t *seg = B.seg;
@@ -770,8 +768,8 @@ void mtx_input_close(MtxInput *in) { delete in; }
 
 // a file small enough to sit on the device whole: one upload, one scan of its newlines, one tokeniser launch
 template <bool ALT>
-static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_t data_off, uint32_t **o0, uint32_t **o1,
-                                    uint32_t **o2, uint64_t *n_lines, unsigned long long *bad)
+static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_t data_off, DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1,
+                                    DevBuf<uint32_t> *o2, uint64_t *n_lines, unsigned long long *bad)
 {
     DevText t;
     cellector_status st = upload_text(c, fb, data_off, &t);
@@ -785,7 +783,6 @@ static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     }
-    dev_free(t.text); dev_free(t.seg_off);
     *n_lines = n;
     return st;
 }
@@ -811,10 +808,11 @@ struct MtxSplit {
     uint32_t bad_kind[CELLECTOR_MAX_SHARDS] = {}, unsorted[CELLECTOR_MAX_SHARDS] = {};
     uint32_t first_locus[CELLECTOR_MAX_SHARDS] = {}, last_locus[CELLECTOR_MAX_SHARDS] = {};
     uint64_t lines[CELLECTOR_MAX_SHARDS] = {};
-    uint32_t *r_dev[CELLECTOR_MAX_SHARDS] = {};
+    uint32_t *r_dev[CELLECTOR_MAX_SHARDS] = {};  // (each shard's ref counts, owned by the shard)
     int device[CELLECTOR_MAX_SHARDS] = {};
-    uint32_t *pl[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {}, *pc[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {};
-    uint16_t *pa[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {}, *pr[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {};
+    // [from][to]: the piece of shard `from`'s lines meant for shard `to`, on `from`'s device
+    DevBuf<uint32_t> pl[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS], pc[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS];
+    DevBuf<uint16_t> pa[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS], pr[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS];
     uint64_t cnt[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {};
     bool balance = false;                             // cut the cells so that every shard gets about the same number of entries
     std::vector<uint32_t> hist[CELLECTOR_MAX_SHARDS];  // ... from every parser's entries per cell
@@ -841,38 +839,28 @@ static cellector_status copy_between(cellector_ctx *c, void *dst, int dst_dev, c
     return CELLECTOR_OK;
 }
 
-cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *S, int rank, uint64_t parse_window, uint32_t **o_locus,
-                                        uint32_t **o_cell, uint16_t **o_alt, uint16_t **o_ref, uint64_t *o_n, bool *o_sorted)
+cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *S, int rank, uint64_t parse_window,
+                                        DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell, DevBuf<uint16_t> *o_alt,
+                                        DevBuf<uint16_t> *o_ref, uint64_t *o_n, bool *o_sorted)
 {
     const int n = S->n;
     const uint64_t TL = in->total_loci, TC = in->total_cells;
-    uint32_t *l1 = nullptr, *c1 = nullptr, *a = nullptr, *r = nullptr, *rk = nullptr, *flags = nullptr;
-    uint16_t *alt16 = nullptr, *ref16 = nullptr;
-    unsigned long long *bad = nullptr;
-    uint64_t *keep = nullptr;
-    auto cleanup = [&]() {
-        dev_free(l1); dev_free(c1); dev_free(a); dev_free(r); dev_free(rk); dev_free(flags); dev_free(bad); dev_free(keep);
-        dev_free(alt16); dev_free(ref16);
-        for (int d = 0; d < n; d++) {  // (the pieces this shard cut for the others, if it got that far)
-            dev_free(S->pl[rank][d]); dev_free(S->pc[rank][d]); dev_free(S->pa[rank][d]); dev_free(S->pr[rank][d]);
-            S->pl[rank][d] = S->pc[rank][d] = nullptr; S->pa[rank][d] = S->pr[rank][d] = nullptr;
-        }
-    };
+    DevBuf<uint32_t> l1, c1, a, r, rk, flags;
+    DevBuf<uint16_t> alt16, ref16;
+    DevBuf<unsigned long long> bad;
+    DevBuf<uint64_t> keep;
+    // (on a failure the pieces this shard cut for the others stay until the MtxSplit goes: a peer may still be reading them)
 #define SCHK(expr)                     \
     do {                               \
         cellector_status s__ = (expr); \
         if (s__ != CELLECTOR_OK) {     \
-            cleanup();                 \
             S->bar->fail();            \
             return s__;                \
         }                              \
     } while (0)
-#define SBARRIER()                                                                                       \
-    do {                                                                                                 \
-        if (!S->bar->barrier()) {                                                                        \
-            cleanup();                                                                                   \
-            return ctx_fail(c, CELLECTOR_ECOMM, "another shard of this ctx failed during the ingest");   \
-        }                                                                                                \
+#define SBARRIER()                                                                                                         \
+    do {                                                                                                                   \
+        if (!S->bar->barrier()) return ctx_fail(c, CELLECTOR_ECOMM, "another shard of this ctx failed during the ingest"); \
     } while (0)
     if (hipSetDevice(c->device) != hipSuccess) {  // (through the barrier group like every other failure: the peers must not wait)
         S->bar->fail();
@@ -917,8 +905,8 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
         SCHK((parse_windowed<true>(c, in->fa, in->off_a, B, hint ? hint : nb_a / (12 * (uint64_t)n) + 1024, &l1, &c1, &a, &ma, bad,
                                    std::min(nw_a, pa * rank), std::min(nw_a, pa * (rank + 1)))));
         lap("alt range (upload + tokens)");
-        SCHK((parse_windowed<false>(c, in->fr, in->off_r, B, hint ? hint : nb_r / (12 * (uint64_t)n) + 1024, (uint32_t **)nullptr,
-                                    (uint32_t **)nullptr, &r, &mr, bad + 1, std::min(nw_r, pr * rank), std::min(nw_r, pr * (rank + 1)))));
+        SCHK((parse_windowed<false>(c, in->fr, in->off_r, B, hint ? hint : nb_r / (12 * (uint64_t)n) + 1024, nullptr, nullptr, &r, &mr,
+                                    bad + 1, std::min(nw_r, pr * rank), std::min(nw_r, pr * (rank + 1)))));
         lap("ref range (upload + tokens)");
     }
     e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
@@ -939,7 +927,6 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
             if (S->bad_r[k] != ~0ull) first = std::min<unsigned long long>(first, rbase[k] + S->bad_r[k]);
         }
         if (first < nlines) {
-            cleanup();
             (void)S->bar->barrier();  // (every shard sees the same numbers and leaves here: nobody is left waiting)
             return ctx_fail(c, CELLECTOR_EPARSE, "cannot parse mtx entry %llu (line %llu of the data section)", first, first + 1);
         }
@@ -957,7 +944,7 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     }
     SBARRIER();  // (every shard has fetched what it needs out of the others' ref counts)
     lap("fetch ref counts");
-    dev_free(r);
+    r.reset();
     S->r_dev[rank] = nullptr;
     // ---- 3. zip + validation of this shard's lines, in place
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(count + 1)), dim3(PB), 0, c->stream, count, l1 + lo, c1 + lo, a + lo, rk + lo, TL, TC,
@@ -980,7 +967,6 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
         if (worst >= 0) {
             static const char *what[] = {"", "index 0 (indices are 1-based)", "locus index out of range", "cell index out of range",
                                          "count above 65535 not supported"};
-            cleanup();
             (void)S->bar->barrier();
             return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", S->bad_z[worst], what[S->bad_kind[worst] <= 4 ? S->bad_kind[worst] : 0]);
         }
@@ -1002,63 +988,51 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)));
     // ---- 4. one piece per destination shard (cells of its range, order kept, cell index local to it)
-    {
-        // (ingest_split_coo reads the staged COO of a ctx: lend it the arrays for the calls; this ctx has staged nothing yet)
-        c->coo_locus = l1 + lo; c->coo_cell = c1 + lo; c->coo_alt = alt16; c->coo_ref = ref16; c->coo_n = count;
-        cellector_status st = dev_alloc(c, &keep, count + 1);
-        if (S->balance && st == CELLECTOR_OK) {
-            // nnz-balanced ranges: every parser counts its entries per cell, all of them add the n histograms up (the same
-            // integers on every shard) and cut the cells where the running sum crosses k / n of the entries
-            st = ingest_cell_histogram(c, c->coo_cell, count, TC, &S->hist[rank]);
-            if (st != CELLECTOR_OK) { c->coo_locus = c->coo_cell = nullptr; c->coo_alt = c->coo_ref = nullptr; c->coo_n = 0; SCHK(st); }
-            if (!S->bar->barrier()) {
-                c->coo_locus = c->coo_cell = nullptr; c->coo_alt = c->coo_ref = nullptr; c->coo_n = 0;
-                cleanup();
-                return ctx_fail(c, CELLECTOR_ECOMM, "another shard of this ctx failed during the ingest");
-            }
-            std::vector<uint32_t> epc(TC, 0u);
-            for (int k = 0; k < n; k++)
-                for (uint64_t i = 0; i < TC; i++) epc[i] += S->hist[k][i];
-            comm_balanced_bounds(epc.data(), TC, n, c->comm.bounds);
-            c->comm.has_bounds = true;
-        }
-        for (int d = 0; d < n && st == CELLECTOR_OK; d++) {
-            uint64_t cb, ce;
-            comm_range(c->comm, TC, d, &cb, &ce);
-            st = ingest_split_coo(c, cb, ce, keep, &S->pl[rank][d], &S->pc[rank][d], &S->pa[rank][d], &S->pr[rank][d], &S->cnt[rank][d]);
-        }
-        c->coo_locus = c->coo_cell = nullptr; c->coo_alt = c->coo_ref = nullptr; c->coo_n = 0;
-        SCHK(st);
+    SCHK(dev_alloc(c, &keep, count + 1));
+    if (S->balance) {
+        // nnz-balanced ranges: every parser counts its entries per cell, all of them add the n histograms up (the same
+        // integers on every shard) and cut the cells where the running sum crosses k / n of the entries
+        SCHK(ingest_cell_histogram(c, c1 + lo, count, TC, &S->hist[rank]));
+        SBARRIER();
+        std::vector<uint32_t> epc(TC, 0u);
+        for (int k = 0; k < n; k++)
+            for (uint64_t i = 0; i < TC; i++) epc[i] += S->hist[k][i];
+        comm_balanced_bounds(epc.data(), TC, n, c->comm.bounds);
+        c->comm.has_bounds = true;
+    }
+    for (int d = 0; d < n; d++) {
+        uint64_t cb, ce;
+        comm_range(c->comm, TC, d, &cb, &ce);
+        SCHK(ingest_split_coo(c, l1 + lo, c1 + lo, alt16, ref16, count, cb, ce, keep, &S->pl[rank][d], &S->pc[rank][d], &S->pa[rank][d],
+                              &S->pr[rank][d], &S->cnt[rank][d]));
     }
     lap("zip + cut by owner");
     SBARRIER();
     // ---- 5. this shard's entries = the pieces meant for it, in rank order (= file order)
     uint64_t total = 0;
     for (int k = 0; k < n; k++) total += S->cnt[k][rank];
-    uint32_t *fl = nullptr, *fc = nullptr;
-    uint16_t *fa16 = nullptr, *fr16 = nullptr;
-    cellector_status st = dev_alloc(c, &fl, total);
-    if (st == CELLECTOR_OK) st = dev_alloc(c, &fc, total);
-    if (st == CELLECTOR_OK) st = dev_alloc(c, &fa16, total);
-    if (st == CELLECTOR_OK) st = dev_alloc(c, &fr16, total);
+    DevBuf<uint32_t> fl, fc;
+    DevBuf<uint16_t> fa16, fr16;
+    SCHK(dev_alloc(c, &fl, total));
+    SCHK(dev_alloc(c, &fc, total));
+    SCHK(dev_alloc(c, &fa16, total));
+    SCHK(dev_alloc(c, &fr16, total));
     uint64_t at = 0;
-    for (int k = 0; k < n && st == CELLECTOR_OK; k++) {
+    for (int k = 0; k < n; k++) {
         const uint64_t m = S->cnt[k][rank];
-        st = copy_between(c, fl + at, c->device, S->pl[k][rank], S->device[k], m * 4);
-        if (st == CELLECTOR_OK) st = copy_between(c, fc + at, c->device, S->pc[k][rank], S->device[k], m * 4);
-        if (st == CELLECTOR_OK) st = copy_between(c, fa16 + at, c->device, S->pa[k][rank], S->device[k], m * 2);
-        if (st == CELLECTOR_OK) st = copy_between(c, fr16 + at, c->device, S->pr[k][rank], S->device[k], m * 2);
+        SCHK(copy_between(c, fl + at, c->device, S->pl[k][rank], S->device[k], m * 4));
+        SCHK(copy_between(c, fc + at, c->device, S->pc[k][rank], S->device[k], m * 4));
+        SCHK(copy_between(c, fa16 + at, c->device, S->pa[k][rank], S->device[k], m * 2));
+        SCHK(copy_between(c, fr16 + at, c->device, S->pr[k][rank], S->device[k], m * 2));
         at += m;
     }
-    if (st != CELLECTOR_OK) { dev_free(fl); dev_free(fc); dev_free(fa16); dev_free(fr16); SCHK(st); }
-    if (!S->bar->barrier()) {  // (the pieces this shard made have been fetched by their destinations)
-        dev_free(fl); dev_free(fc); dev_free(fa16); dev_free(fr16);
-        cleanup();
-        return ctx_fail(c, CELLECTOR_ECOMM, "another shard of this ctx failed during the ingest");
+    SBARRIER();  // (the pieces this shard made have been fetched by their destinations)
+    for (int d = 0; d < n; d++) {
+        S->pl[rank][d].reset(); S->pc[rank][d].reset(); S->pa[rank][d].reset(); S->pr[rank][d].reset();
     }
-    cleanup();
+    l1.reset(); c1.reset(); a.reset(); rk.reset(); flags.reset(); bad.reset(); keep.reset(); alt16.reset(); ref16.reset();
     lap("gather own pieces");
-    *o_locus = fl; *o_cell = fc; *o_alt = fa16; *o_ref = fr16; *o_n = total;
+    *o_locus = std::move(fl); *o_cell = std::move(fc); *o_alt = std::move(fa16); *o_ref = std::move(fr16); *o_n = total;
 #undef SCHK
 #undef SBARRIER
     return CELLECTOR_OK;
@@ -1069,10 +1043,10 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
 // byte streams until they are zipped, so a second GPU takes the second file over its own PCIe link while the first one
 // tokenises the alt file; two files together also read faster from the page cache than one: 76 vs 43 GB/s measured).
 static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size_t off_r, uint64_t win, bool windowed, uint64_t nnz_hint,
-                                     uint32_t **r_out, uint64_t *n_r, unsigned long long *bad_host)
+                                     DevBuf<uint32_t> *r_out, uint64_t *n_r, unsigned long long *bad_host)
 {
     HIPCHK(h, hipSetDevice(h->device));
-    unsigned long long *bad = nullptr;
+    DevBuf<unsigned long long> bad;
     CHK(dev_alloc(h, &bad, 1));
     unsigned long long none = ~0ull;
     hipError_t e = hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, h->stream);
@@ -1083,9 +1057,9 @@ static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size
             PwBuffers B;
             st = B.make(h, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (fr.size - off_r + win - 1) / win)));
             if (st == CELLECTOR_OK)
-                st = parse_windowed<false>(h, fr, off_r, B, nnz_hint, (uint32_t **)nullptr, (uint32_t **)nullptr, r_out, n_r, bad);
+                st = parse_windowed<false>(h, fr, off_r, B, nnz_hint, nullptr, nullptr, r_out, n_r, bad);
         } else {
-            st = parse_whole<false>(h, fr, off_r, (uint32_t **)nullptr, (uint32_t **)nullptr, r_out, n_r, bad);
+            st = parse_whole<false>(h, fr, off_r, nullptr, nullptr, r_out, n_r, bad);
         }
     }
     if (st == CELLECTOR_OK) {
@@ -1093,7 +1067,6 @@ static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) st = ctx_fail(h, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     }
-    dev_free(bad);
     return st;
 }
 
@@ -1110,28 +1083,17 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
         fprintf(stderr, "[timing]     %-22s %8.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
         t_prev = now;
     };
-    uint32_t *l1 = nullptr, *c1 = nullptr, *a = nullptr, *r = nullptr, *flags = nullptr;
-    unsigned long long *bad = nullptr;  // [0] alt file, [1] ref file: smallest line that does not parse; [2] zip stage
-    uint64_t *keep = nullptr;
-    auto cleanup = [&]() {
-        dev_free(l1); dev_free(c1); dev_free(a); dev_free(r); dev_free(flags); dev_free(bad); dev_free(keep);
-    };
-#define PCHK(expr)                     \
-    do {                               \
-        cellector_status s__ = (expr); \
-        if (s__ != CELLECTOR_OK) {     \
-            cleanup();                 \
-            return s__;                \
-        }                              \
-    } while (0)
+    DevBuf<uint32_t> l1, c1, a, r, flags;
+    DevBuf<unsigned long long> bad;  // [0] alt file, [1] ref file: smallest line that does not parse; [2] zip stage
+    DevBuf<uint64_t> keep;
     HIPCHK(c, hipSetDevice(c->device));
-    PCHK(dev_alloc(c, &bad, 3)); PCHK(dev_alloc(c, &flags, 4));
+    CHK(dev_alloc(c, &bad, 3)); CHK(dev_alloc(c, &flags, 4));
     unsigned long long h_bad[3] = {~0ull, ~0ull, ~0ull};
     uint32_t h_flags[4] = {0, 0, 0, 0};
     hipError_t e = hipMemcpyAsync(bad, h_bad, sizeof h_bad, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(flags, h_flags, sizeof h_flags, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     // a multi-GB file goes through the device in windows (option parse_window forces a window size: tests); the token
     // arrays' capacity comes from the size line's entry count (a hint only: the reference never reads it)
     uint64_t n_a = 0, n_r = 0;
@@ -1147,7 +1109,7 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     const bool win_a = c->parse_window_opt > 0 || !fa.data || fa.size - off_a >= PW_MIN;
     const bool win_r = c->parse_window_opt > 0 || !fr.data || fr.size - off_r >= PW_MIN;
     if (helper) {  // the ref file on the helper's device, concurrently (its own ring of window buffers, its own stream)
-        uint32_t *r_h = nullptr;
+        DevBuf<uint32_t> r_h;
         unsigned long long bad_r = ~0ull;
         cellector_status st_r = CELLECTOR_OK;
         std::thread th([&] { st_r = parse_ref_on(helper, fr, off_r, win, win_r, in->nnz_hint, &r_h, &n_r, &bad_r); });
@@ -1169,8 +1131,8 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
             (hipMemcpyAsync(bad + 1, &bad_r, sizeof bad_r, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
              hipStreamSynchronize(c->stream) != hipSuccess))
             st_a = ctx_fail(c, CELLECTOR_EDEVICE, "parse: copy failed");
-        dev_free(r_h);
-        PCHK(st_a);
+        r_h.reset();
+        CHK(st_a);
         lap("alt + ref files (two devices)");
     } else {
         // While the host reads and the device tokenises (host-bound: ~1.5 s for 2 x 31 GB), a helper thread maps the VRAM the
@@ -1205,15 +1167,15 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
         PwBuffers B;  // one ring of window buffers for both files
         if (win_a || win_r) {
             const uint64_t longest = std::max(win_a ? fa.size - off_a : 0, win_r ? fr.size - off_r : 0);
-            PCHK(B.make(c, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (longest + win - 1) / win))));
+            CHK(B.make(c, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (longest + win - 1) / win))));
         }
-        if (win_a) PCHK((parse_windowed<true>(c, fa, off_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad)));
-        else PCHK((parse_whole<true>(c, fa, off_a, &l1, &c1, &a, &n_a, bad)));
+        if (win_a) CHK((parse_windowed<true>(c, fa, off_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad)));
+        else CHK((parse_whole<true>(c, fa, off_a, &l1, &c1, &a, &n_a, bad)));
         lap("alt file (upload + tokens)");
         if (win_r)
-            PCHK((parse_windowed<false>(c, fr, off_r, B, in->nnz_hint, (uint32_t **)nullptr, (uint32_t **)nullptr, &r, &n_r, bad + 1)));
+            CHK((parse_windowed<false>(c, fr, off_r, B, in->nnz_hint, nullptr, nullptr, &r, &n_r, bad + 1)));
         else
-            PCHK((parse_whole<false>(c, fr, off_r, (uint32_t **)nullptr, (uint32_t **)nullptr, &r, &n_r, bad + 1)));
+            CHK((parse_whole<false>(c, fr, off_r, nullptr, nullptr, &r, &n_r, bad + 1)));
         lap("ref file (upload + tokens)");
         if (premap.joinable()) premap.join();
         lap("wait for the pre-mapped blocks");
@@ -1221,16 +1183,14 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     const uint64_t n = std::min(n_a, n_r);  // izip!: stops at the shorter file
     e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     {   // (a line beyond the shorter file is never read by the reference: only failures among the first n count)
         const unsigned long long first = std::min(h_bad[0], h_bad[1]);
-        if (first < n) {
-            cleanup();
+        if (first < n)
             return ctx_fail(c, CELLECTOR_EPARSE, "cannot parse mtx entry %llu (line %llu of the data section)", first, first + 1);
-        }
     }
     const bool all_cells = c->cell_begin == 0 && c->cell_end >= c->total_cells;
-    if (!all_cells) PCHK(dev_alloc(c, &keep, n + 1));
+    if (!all_cells) CHK(dev_alloc(c, &keep, n + 1));
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(n + 1)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->total_loci, c->total_cells,
                        c->cell_begin, c->cell_end, keep, bad + 2, flags, flags + 1);
     // the validation result is read BEHIND k_pair_check on the ctx's stream (a caller-supplied non-blocking stream does
@@ -1238,9 +1198,8 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     if (h_bad[2] != ~0ull) {
-        cleanup();
         static const char *what[] = {"", "index 0 (indices are 1-based)", "locus index out of range", "cell index out of range",
                                      "count above 65535 not supported"};
         return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", h_bad[2], what[h_flags[0] <= 4 ? h_flags[0] : 0]);
@@ -1248,17 +1207,16 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     c->coo_sorted = h_flags[1] == 0;
     if (all_cells) {
         c->coo_n = n;
-        PCHK(dev_alloc(c, &c->coo_alt, n)); PCHK(dev_alloc(c, &c->coo_ref, n));
+        CHK(dev_alloc(c, &c->coo_alt, n)); CHK(dev_alloc(c, &c->coo_ref, n));
         if (n) hipLaunchKernelGGL(k_pair_take, dim3(pgrid(n)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->coo_alt, c->coo_ref);
-        c->coo_locus = l1;
-        c->coo_cell = c1;
-        l1 = c1 = nullptr;  // (owned by the ctx now)
+        c->coo_locus = std::move(l1);  // (the token arrays are the staged COO)
+        c->coo_cell = std::move(c1);
     } else {
         uint64_t kept = 0;
-        PCHK(dev_exclusive_scan_u64(c, keep, n + 1, &kept));
+        CHK(dev_exclusive_scan_u64(c, keep, n + 1, &kept));
         c->coo_n = kept;
-        PCHK(dev_alloc(c, &c->coo_locus, kept)); PCHK(dev_alloc(c, &c->coo_cell, kept));
-        PCHK(dev_alloc(c, &c->coo_alt, kept)); PCHK(dev_alloc(c, &c->coo_ref, kept));
+        CHK(dev_alloc(c, &c->coo_locus, kept)); CHK(dev_alloc(c, &c->coo_cell, kept));
+        CHK(dev_alloc(c, &c->coo_alt, kept)); CHK(dev_alloc(c, &c->coo_ref, kept));
         if (n)
             hipLaunchKernelGGL(k_pair_fill, dim3(pgrid(n)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->cell_begin, c->cell_end,
                                keep, c->coo_locus, c->coo_cell, c->coo_alt, c->coo_ref);
@@ -1266,8 +1224,6 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     lap("tokenise + zip + filter");
-    cleanup();
     if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
-#undef PCHK
     return CELLECTOR_OK;
 }

@@ -203,10 +203,10 @@ __global__ void k_res_scatter(uint64_t n, const uint32_t *__restrict__ locus, co
 // pointers) with every row in file order.  Called by ingest_build once to_used is final, before the entries are sorted by locus.
 cellector_status resolve_build_file_order(cellector_ctx *c)
 {
-    dev_free(c->res_ent);
+    c->res_ent.reset();
     const uint64_t n = c->coo_n;
-    uint64_t *pos = nullptr, *val = nullptr;
-    uint32_t *key = nullptr, *key_o = nullptr;
+    DevBuf<uint64_t> pos, val;
+    DevBuf<uint32_t> key, key_o;
     CHK(dev_alloc(c, &pos, n + 1));
     hipLaunchKernelGGL(k_res_used, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, c->stream, n, c->coo_locus, c->to_used, pos);
     HIPCHK(c, hipGetLastError());
@@ -220,7 +220,6 @@ cellector_status resolve_build_file_order(cellector_ctx *c)
     int bits = 1;
     while (bits < 32 && (1ull << bits) < c->nloc) bits++;
     CHK(dev_sort_pairs_u32_u64(c, key, key_o, val, c->res_ent, m, bits));  // (stable: file order inside a cell)
-    dev_free(pos); dev_free(key); dev_free(key_o); dev_free(val);
     c->res_nnz = m;
     return CELLECTOR_OK;
 }
@@ -239,7 +238,7 @@ cellector_status resolve_ties(cellector_ctx *c, double iqr_multiple)
         return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties needs every cell's entries in file order, kept by an ingest that ran with "
                                              "the option set: set it before the ingest");
     if (c->res_n != n) {
-        dev_free(c->res_cand); dev_free(c->res_key); dev_free(c->res_done);
+        c->res_cand.reset(); c->res_key.reset(); c->res_done.reset();
         CHK(dev_alloc(c, &c->res_cand, n)); CHK(dev_alloc(c, &c->res_key, n)); CHK(dev_alloc(c, &c->res_done, n));
         c->res_n = n;
     }

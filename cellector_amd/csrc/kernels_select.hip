@@ -496,10 +496,8 @@ cellector_status select_threshold(cellector_ctx *c, const double *keys, uint64_t
     const uint64_t ranks[SEL_T] = {k ? k - 1 : 0, k, clampr(q.hf1 - 1), clampr(q.hf1), clampr(q.hf3 - 1), clampr(q.hf3)};
     for (int t = 0; t < SEL_T; t++) r.r[t] = ranks[t];
     if (c->sel_list_cap < n) {
-        dev_free(c->sel_list);
-        c->sel_list = nullptr;
         c->sel_list_cap = 0;
-        CHK(dev_alloc(c, &c->sel_list, n));
+        CHK(dev_alloc(c, &c->sel_list, n));  // (the smaller list goes first)
         c->sel_list_cap = n;
     }
     uint32_t *hist0 = c->sel_hist, *hist1 = hist0 + SEL_NB0, *count = hist1 + SEL_T * SEL_NB1;

@@ -164,7 +164,7 @@ cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed,
     }
     p.nchunks = (uint32_t)((c->nloc + SY_CHUNK - 1) / SY_CHUNK);
     const uint64_t ntiles = c->total_loci * p.nchunks;
-    uint64_t *tiles = nullptr;
+    DevBuf<uint64_t> tiles;
     CHK(dev_alloc(c, &tiles, ntiles + 1));
     HIPCHK(c, hipMemsetAsync(tiles + ntiles, 0, 8, c->stream));
     const uint64_t max_grid = 1ull << 30;
@@ -186,7 +186,6 @@ cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed,
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dev_free(tiles);
     return CELLECTOR_OK;
 }
 
@@ -230,8 +229,9 @@ cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const c
     if (!c->coo_locus && c->coo_n) return ctx_fail(c, CELLECTOR_EINVAL, "write_staged_mtx: no staged matrix (option keep_coo=1)");
     const uint64_t n = c->coo_n, CH = 1ull << 25;  // 32M lines per chunk: at most 26 bytes each
     FILE *f[2] = {fopen(alt_path, "wb"), fopen(ref_path, "wb")};
-    uint64_t *off = nullptr;
-    uint8_t *dbuf = nullptr, *hbuf = nullptr;
+    DevBuf<uint64_t> off;
+    DevBuf<uint8_t> dbuf;
+    uint8_t *hbuf = nullptr;
     cellector_status st = CELLECTOR_OK;
     if (!f[0] || !f[1]) st = ctx_fail(c, CELLECTOR_EIO, "write_staged_mtx: cannot create %s", f[0] ? ref_path : alt_path);
     if (st == CELLECTOR_OK) st = dev_alloc(c, &off, CH + 1);
@@ -261,7 +261,6 @@ cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const c
     }
     for (int k = 0; k < 2; k++)
         if (f[k] && fclose(f[k]) != 0 && st == CELLECTOR_OK) st = ctx_fail(c, CELLECTOR_EIO, "write_staged_mtx: close failed");
-    dev_free(off); dev_free(dbuf);
     if (hbuf) (void)hipHostFree(hbuf);
     return st;
 }

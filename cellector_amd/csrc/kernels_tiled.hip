@@ -2309,23 +2309,6 @@ static inline unsigned gcap(uint64_t n, unsigned per_block, unsigned cap = 1u <<
     return (unsigned)g;
 }
 
-void tiled_free(cellector_ctx *c)
-{
-    dev_free(c->tile_ptr); dev_free(c->tiles); dev_free(c->thdr); dev_free(c->ovf_ptr); dev_free(c->ovf_ent);
-    dev_free(c->c4_ptr); dev_free(c->c4_ent); dev_free(c->ovc_ptr); dev_free(c->ovc_ent);
-    dev_free(c->hist_all); dev_free(c->tab); dev_free(c->part); dev_free(c->ab3);
-    dev_free(c->masked_cnt); dev_free(c->flag_bits); dev_free(c->ovf_tab); dev_free(c->ovf_etab);
-    dev_free(c->ovf_sum); dev_free(c->ovf_lp); dev_free(c->ovc_locus); dev_free(c->ovf_tier_row[0]); dev_free(c->ovf_tier_row[1]); dev_free(c->ovf_tier_ent[0]); dev_free(c->ovf_tier_ent[1]); dev_free(c->ovf_tier_val); dev_free(c->ovf_ell_ptr); dev_free(c->ovf_ell); dev_free(c->ovf_nmask); dev_free(c->tile_work); dev_free(c->minlist); dev_free(c->chg); dev_free(c->tally); dev_free(c->hist_min); dev_free(c->roff); dev_free(c->c4r); dev_free(c->mroff); dev_free(c->mbeg);
-    dev_free(c->t2_plist); dev_free(c->t2_slist); dev_free(c->t2_pmask); dev_free(c->hist_all2); dev_free(c->cnt2); dev_free(c->tab2); dev_free(c->ovx_ptr); dev_free(c->ovx_ent); dev_free(c->ovx_locus); dev_free(c->ovx_lp);
-    dev_free(c->tile2_ptr); dev_free(c->tiles2); dev_free(c->thdr2); dev_free(c->tab2c); dev_free(c->part2); dev_free(c->tile_work2); dev_free(c->ovr_ptr); dev_free(c->ovr_ent);
-    c->ovr_n = 0;
-    c->t2_tiles = 0;
-    c->ovx_n = 0; c->t2 = false;
-    c->mroff_cap = 0;
-    c->tiled_ready = false;
-    c->ovf_n = 0; c->n_masked_loci = 0;
-}
-
 // Chunk groups of a tile pass (see tiled_build): the count with the shortest modelled makespan of the persistent workgroups.
 static uint32_t tile_groups_for(const cellector_ctx *c, uint32_t nb, uint32_t nj)
 {
@@ -2485,12 +2468,10 @@ cellector_status tiled_build(cellector_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->tile_ptr + nt, 0, 8, c->stream));
     // every (cell, chunk) pair's first entry, once per row: the two builder passes searched each row per tile (two binary
     // searches of ~11 scattered probes per cell and tile: 1.4 TB through the L2 at 1M x 200k, 0.2 s)
-    uint32_t *toff = nullptr;
+    DevBuf<uint32_t> toff;  // (stays empty when there is no room for the table: the builder searches)
     if (nloc && dev_alloc(c, &toff, nloc * ((uint64_t)c->t_nj + 1)) == CELLECTOR_OK)
         hipLaunchKernelGGL(k_range_offsets, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->t_nj, (uint32_t)T_BLU, c->csr_ptr,
                            c->csr_ent, toff);
-    else
-        toff = nullptr;  // (no room for the table: the builder searches)
     // the compact by-cell entries (also the minority-driven locus pass' input): with the offsets table the builder reads these
     CHK(dev_alloc(c, &c->c4r, c->nnz));
     if (c->nnz)
@@ -2531,7 +2512,7 @@ cellector_status tiled_build(cellector_ctx *c)
     }
     if (toff) {
         HIPCHK(c, hipStreamSynchronize(c->stream));  // (the block goes back to the allocation cache: no kernel may still read it)
-        dev_free(toff);
+        toff.reset();
     }
     HIPCHK(c, hipGetLastError());
 
@@ -2618,25 +2599,22 @@ cellector_status tiled_build(cellector_ctx *c)
         hipLaunchKernelGGL(k_t2_hist, dim3(gcap(c->ovf_n, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->ovf_n, c->ovc_locus, c->ovc_ent,
                            c->hist_all2);
         {
-            uint64_t *np = nullptr, *ns = nullptr, tot_p = 0, tot_s = 0;
+            DevBuf<uint64_t> np, ns;
+            uint64_t tot_p = 0, tot_s = 0;
             CHK(dev_alloc(c, &np, L + 1));
             CHK(dev_alloc(c, &ns, L + 1));
             HIPCHK(c, hipMemsetAsync(np + L, 0, 8, c->stream));
             HIPCHK(c, hipMemsetAsync(ns + L, 0, 8, c->stream));
             hipLaunchKernelGGL(k_t2_lists<false>, dim3(gcap(L, 256)), dim3(256), 0, c->stream, L, c->hist_all2, np, ns, (uint32_t *)nullptr,
                                (uint32_t *)nullptr, (uint32_t *)nullptr);
-            cellector_status st = dev_exclusive_scan_u64(c, np, L + 1, &tot_p);
-            if (st == CELLECTOR_OK) st = dev_exclusive_scan_u64(c, ns, L + 1, &tot_s);
-            if (st == CELLECTOR_OK) st = dev_alloc(c, &c->t2_plist, tot_p);
-            if (st == CELLECTOR_OK) st = dev_alloc(c, &c->t2_slist, tot_s);
-            if (st == CELLECTOR_OK) st = dev_alloc(c, &c->t2_pmask, L);
-            if (st == CELLECTOR_OK) {
-                hipLaunchKernelGGL(k_t2_lists<true>, dim3(gcap(L, 256)), dim3(256), 0, c->stream, L, c->hist_all2, np, ns, c->t2_plist, c->t2_slist,
-                                   c->t2_pmask);
-                if (hipStreamSynchronize(c->stream) != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "tier-2 list build failed");
-            }
-            dev_free(np); dev_free(ns);
-            CHK(st);
+            CHK(dev_exclusive_scan_u64(c, np, L + 1, &tot_p));
+            CHK(dev_exclusive_scan_u64(c, ns, L + 1, &tot_s));
+            CHK(dev_alloc(c, &c->t2_plist, tot_p));
+            CHK(dev_alloc(c, &c->t2_slist, tot_s));
+            CHK(dev_alloc(c, &c->t2_pmask, L));
+            hipLaunchKernelGGL(k_t2_lists<true>, dim3(gcap(L, 256)), dim3(256), 0, c->stream, L, c->hist_all2, np, ns, c->t2_plist, c->t2_slist,
+                               c->t2_pmask);
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "tier-2 list build failed");
             c->t2_np = (uint32_t)tot_p; c->t2_ns = (uint32_t)tot_s;
         }
         CHK(dev_alloc(c, &c->ovx_ptr, L + 1));
@@ -2653,7 +2631,7 @@ cellector_status tiled_build(cellector_ctx *c)
             hipLaunchKernelGGL(k_ovf_locus_ids, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovx_ptr, c->ovx_locus);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dev_free(c->ovc_locus);  // (only the histogram needed it)
+        c->ovc_locus.reset();  // (only the histogram needed it)
     }
     {
         const uint64_t n_grp = (nloc + 63) / 64;
@@ -2673,7 +2651,7 @@ cellector_status tiled_build(cellector_ctx *c)
     // the tier lists of the entries the fast cell-side kernel leaves out
     c->ovf_n_tier[0] = c->ovf_n_tier[1] = 0;
     if (nloc && c->ovf_n) {
-        uint64_t *cnt0 = nullptr, *cnt1 = nullptr;
+        DevBuf<uint64_t> cnt0, cnt1;
         CHK(dev_alloc(c, &cnt0, nloc + 1));
         CHK(dev_alloc(c, &cnt1, nloc + 1));
         HIPCHK(c, hipMemsetAsync(cnt0 + nloc, 0, 8, c->stream));
@@ -2681,19 +2659,16 @@ cellector_status tiled_build(cellector_ctx *c)
         const unsigned g = gcap(nloc, 256, 0x7fffffffu);
         hipLaunchKernelGGL(k_ovf_tier_lists<false>, dim3(g), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, cnt0, cnt1,
                            (uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
-        cellector_status st = dev_exclusive_scan_u64(c, cnt0, nloc + 1, &c->ovf_n_tier[0]);
-        if (st == CELLECTOR_OK) st = dev_exclusive_scan_u64(c, cnt1, nloc + 1, &c->ovf_n_tier[1]);
-        for (int t = 0; t < 2 && st == CELLECTOR_OK; t++) {
-            st = dev_alloc(c, &c->ovf_tier_row[t], c->ovf_n_tier[t]);
-            if (st == CELLECTOR_OK) st = dev_alloc(c, &c->ovf_tier_ent[t], c->ovf_n_tier[t]);
+        CHK(dev_exclusive_scan_u64(c, cnt0, nloc + 1, &c->ovf_n_tier[0]));
+        CHK(dev_exclusive_scan_u64(c, cnt1, nloc + 1, &c->ovf_n_tier[1]));
+        for (int t = 0; t < 2; t++) {
+            CHK(dev_alloc(c, &c->ovf_tier_row[t], c->ovf_n_tier[t]));
+            CHK(dev_alloc(c, &c->ovf_tier_ent[t], c->ovf_n_tier[t]));
         }
-        if (st == CELLECTOR_OK) {
-            hipLaunchKernelGGL(k_ovf_tier_lists<true>, dim3(g), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, cnt0, cnt1,
-                               c->ovf_tier_row[0], c->ovf_tier_ent[0], c->ovf_tier_row[1], c->ovf_tier_ent[1]);
-            if (hipStreamSynchronize(c->stream) != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "tier list build failed");
-        }
-        dev_free(cnt0); dev_free(cnt1);
-        CHK(st);
+        hipLaunchKernelGGL(k_ovf_tier_lists<true>, dim3(g), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, cnt0, cnt1,
+                           c->ovf_tier_row[0], c->ovf_tier_ent[0], c->ovf_tier_row[1], c->ovf_tier_ent[1]);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "tier list build failed");
+        cnt0.reset(); cnt1.reset();
         CHK(dev_alloc(c, &c->ovf_tier_val, 2 * c->ovf_n_tier[1]));  // (log-pmf, expected term) of the tier-1 entries, per pass
     }
     // which totals the per-entry tables (k_ovf_tables, k_ovf_tables_e) must cover at every locus: those of the entries that
@@ -3085,7 +3060,7 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
         const uint32_t R = (uint32_t)((c->L + LR_LOCI - 1) / LR_LOCI);
         if (c->mroff_cap < want) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            dev_free(c->mroff); dev_free(c->mbeg);
+            c->mroff.reset(); c->mbeg.reset();
             c->mroff_cap = (want + 63) & ~63ull;
             CHK(dev_alloc(c, &c->mroff, (uint64_t)(R + 1) * c->mroff_cap));
             CHK(dev_alloc(c, &c->mbeg, c->mroff_cap));

@@ -269,13 +269,13 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
                 if (!S) { mtx_input_close(in); return ctx_fail(root, CELLECTOR_ENOMEM, "out of host memory"); }
                 const uint64_t window = s0->parse_window_opt > 0 ? (uint64_t)s0->parse_window_opt : 0;
                 st = run_all(root, [=](cellector_ctx *s, int rank) {
-                    uint32_t *pl = nullptr, *pc = nullptr;
-                    uint16_t *pa = nullptr, *pr = nullptr;
+                    DevBuf<uint32_t> pl, pc;
+                    DevBuf<uint16_t> pa, pr;
                     uint64_t cnt = 0;
                     bool sorted = false;
                     cellector_status r = ingest_stage_mtx_split(s, in, S, rank, window, &pl, &pc, &pa, &pr, &cnt, &sorted);
                     if (r != CELLECTOR_OK) return r;
-                    return ffi_adopt_staged(s, tl, tc, pl, pc, pa, pr, cnt, sorted);
+                    return ffi_adopt_staged(s, tl, tc, std::move(pl), std::move(pc), std::move(pa), std::move(pr), cnt, sorted);
                 });
                 if (st == CELLECTOR_ECOMM)  // (report the shard that failed, not one of those it released)
                     for (size_t r = 0; r < m->shards.size(); r++)
@@ -307,12 +307,13 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
     // detach the all-cells arrays from shard 0 (its own piece is cut from them like the others')
     cellector_ctx all;  // (a plain holder: no device state of its own is created or destroyed)
     all.device = s0->device; all.stream = s0->stream;
-    all.coo_locus = s0->coo_locus; all.coo_cell = s0->coo_cell; all.coo_alt = s0->coo_alt; all.coo_ref = s0->coo_ref;
+    all.coo_locus = std::move(s0->coo_locus); all.coo_cell = std::move(s0->coo_cell);
+    all.coo_alt = std::move(s0->coo_alt); all.coo_ref = std::move(s0->coo_ref);
     all.coo_n = s0->coo_n;
     const bool sorted = s0->coo_sorted;
     const uint64_t TL = s0->total_loci, TC = s0->total_cells;
-    s0->coo_locus = s0->coo_cell = nullptr; s0->coo_alt = s0->coo_ref = nullptr; s0->coo_n = 0;
-    uint64_t *keep = nullptr;
+    s0->coo_n = 0;
+    DevBuf<uint64_t> keep;
     st = dev_alloc(&all, &keep, all.coo_n + 1);
     const int n = (int)m->shards.size();
     if (st == CELLECTOR_OK && m->balance && !m->user_partition && n > 1) {  // the ranges: cut by entries per cell
@@ -327,15 +328,15 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
         cellector_ctx *s = m->shards[(size_t)r];
         uint64_t cb, ce;
         comm_range(s->comm, TC, r, &cb, &ce);
-        uint32_t *pl = nullptr, *pc = nullptr;
-        uint16_t *pa = nullptr, *pr = nullptr;
+        DevBuf<uint32_t> pl, pc;
+        DevBuf<uint16_t> pa, pr;
         uint64_t cnt = 0;
         (void)hipSetDevice(all.device);
-        st = ingest_split_coo(&all, cb, ce, keep, &pl, &pc, &pa, &pr, &cnt);
+        st = ingest_split_coo(&all, all.coo_locus, all.coo_cell, all.coo_alt, all.coo_ref, all.coo_n, cb, ce, keep, &pl, &pc, &pa, &pr, &cnt);
         if (st != CELLECTOR_OK) { root->err = all.err; break; }
         if (s->device != all.device) {  // move the piece to the shard's device
-            uint32_t *ql = nullptr, *qc = nullptr;
-            uint16_t *qa = nullptr, *qr = nullptr;
+            DevBuf<uint32_t> ql, qc;
+            DevBuf<uint16_t> qa, qr;
             (void)hipSetDevice(s->device);
             st = dev_alloc(s, &ql, cnt);
             if (st == CELLECTOR_OK) st = dev_alloc(s, &qc, cnt);
@@ -348,17 +349,17 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
                  dev_copy_sync(s->stream, qr, s->device, pr, all.device, cnt * 2) != hipSuccess))
                 st = ctx_fail(s, CELLECTOR_EDEVICE, "peer copy of the shard's entries failed: %s", hipGetErrorString(hipGetLastError()));
             (void)hipSetDevice(all.device);
-            dev_free(pl); dev_free(pc); dev_free(pa); dev_free(pr);
-            if (st != CELLECTOR_OK) { dev_free(ql); dev_free(qc); dev_free(qa); dev_free(qr); fail(s, st); break; }
-            pl = ql; pc = qc; pa = qa; pr = qr;
+            pl.reset(); pc.reset(); pa.reset(); pr.reset();
+            if (st != CELLECTOR_OK) { fail(s, st); break; }
+            pl = std::move(ql); pc = std::move(qc); pa = std::move(qa); pr = std::move(qr);
         }
         (void)hipSetDevice(s->device);
-        st = ffi_adopt_staged(s, TL, TC, pl, pc, pa, pr, cnt, sorted);
+        st = ffi_adopt_staged(s, TL, TC, std::move(pl), std::move(pc), std::move(pa), std::move(pr), cnt, sorted);
         if (st != CELLECTOR_OK) fail(s, st);
     }
     (void)hipSetDevice(all.device);
-    dev_free(keep);
-    dev_free(all.coo_locus); dev_free(all.coo_cell); dev_free(all.coo_alt); dev_free(all.coo_ref);
+    keep.reset();
+    all.coo_locus.reset(); all.coo_cell.reset(); all.coo_alt.reset(); all.coo_ref.reset();
     all.stream = nullptr;
     return st;
 }

@@ -371,19 +371,22 @@ def test_near_ties_are_reported(mods):
     g.close(); o.close()
 
 
-def test_context_reload_starts_clean(mods):
+@pytest.mark.parametrize("nb", [500, 1100])
+def test_context_reload_starts_clean(mods, nb):
     """A ctx that ran iterations on one matrix and is then loaded with another must not carry tables built ahead for the
-    old one (em_finish queues the next iteration's k_build_tables): the second run must equal a fresh ctx and the oracle."""
+    old one (em_finish queues the next iteration's k_build_tables), nor the old matrix' cell range (a second matrix with more
+    cells is owned whole): the second run must equal a fresh ctx and the oracle."""
     la, ca, aa, ra = mods["synth"].generate_coo(900, 700, 0.12, seed=5, minority_fraction=0.1)
-    lb, cb, ab_, rb = mods["synth"].generate_coo(1300, 500, 0.1, seed=6, minority_fraction=0.07)
+    lb, cb, ab_, rb = mods["synth"].generate_coo(1300, nb, 0.1, seed=6, minority_fraction=0.07)
     g = mods["Cellector"](0)
     g.load_coo(900, 700, la, ca, aa, ra)
     for _ in range(3):
         g.em_iteration(5.0)                      # leaves tables prebuilt for iteration 4 of matrix A
-    g.load_coo(1300, 500, lb, cb, ab_, rb)      # same ctx, new matrix
+    g.load_coo(1300, nb, lb, cb, ab_, rb)       # same ctx, new matrix
     f = mods["Cellector"](0)
-    f.load_coo(1300, 500, lb, cb, ab_, rb)
-    o = mods["ob"].Oracle.from_coo(1300, 500, lb, cb, ab_, rb)
+    f.load_coo(1300, nb, lb, cb, ab_, rb)
+    o = mods["ob"].Oracle.from_coo(1300, nb, lb, cb, ab_, rb)
+    assert (g.dims().cell_begin, g.dims().cell_end) == (0, nb)
     _check_matrix(g, o)
     for _ in range(30):
         sg, sf, so = g.em_iteration(5.0), f.em_iteration(5.0), o.em_iteration(5.0)

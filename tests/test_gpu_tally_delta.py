@@ -99,11 +99,10 @@ def test_invalidation_reload_shard_and_engine_switch(mods):
     """The kept counts belong to one matrix, one shard and engine 2's own iterations: a reload, a shard ctx and an engine
     switch 2 -> 1 -> 2 between iterations must give what a ctx that recounts every iteration gives."""
     synth = mods["synth"]
-    La, Na, Lb, Nb = 1300, 1700, 900, 1500
+    La, Na, Lb, Nb = 1300, 1700, 900, 2000
     coo_a = synth.generate_coo(La, Na, 0.03, seed=6, minority_fraction=0.2)
     coo_b = synth.generate_coo(Lb, Nb, 0.04, seed=5, minority_fraction=0.1)
-    # reload: a ctx that ran iterations on A, then B, against a fresh ctx on B.  (B has fewer cells than A: a reload keeps the
-    # cell range of the first ingest, so a larger second matrix would be a shard of its first cells — not what this checks.)
+    # reload: a ctx that ran iterations on A, then B (more cells than A), against a fresh ctx on B
     g = _ctx(mods, 1)
     g.load_coo(La, Na, *coo_a)
     for _ in range(2):
