@@ -459,6 +459,10 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         if (v < 0 || v > 64) return ctx_fail(c, CELLECTOR_EINVAL, "tile_groups must be 0 (automatic) or 1..64");
         c->tile_groups_opt = (int)v;
     }
+    else if (!strcmp(key, "tile_sb")) {
+        if (v != 0 && v != 2 && v != 4) return ctx_fail(c, CELLECTOR_EINVAL, "tile_sb must be 0 (automatic), 2 or 4");
+        c->tile_sb_opt = (int)v;
+    }
     else if (!strcmp(key, "locus_mode")) {
         if (v < 0 || v > 2) return ctx_fail(c, CELLECTOR_EINVAL, "locus_mode must be 0 (automatic), 1 (stream) or 2 (minority-driven)");
         c->locus_mode = (int)v;

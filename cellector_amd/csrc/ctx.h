@@ -116,6 +116,7 @@ struct CtxOptions {
                                 // iterations and updates them from the set's change (0: recounts every iteration; A/B)
     bool bank_order = true;  // option "bank_order": the tile builder orders every row's entries against LDS bank conflicts (tile_bank_order)
     int tile_groups_opt = 0;  // option tile_groups: 0 = chosen per matrix (tiled_setup), else forced (multiple of 8)
+    int tile_sb_opt = 0;  // option tile_sb: 0 = cell blocks per column of the tile kernel chosen per launch (run_tile_pass), 2 or 4 forced (tests)
     // option sharded_select: a ctx with a communicator exchanges digit histograms (1) or all-gathers NORM (0); -1 = by the
     // number of ranks (use_sharded_select)
     int sharded_select = -1;
@@ -270,6 +271,7 @@ struct CtxTiled {
     DevBuf<uint64_t> mbeg;           // [mroff_cap] start of the excluded cells' rows in csr_ent
     uint64_t mroff_cap = 0;
     uint32_t lr_sub = 1;             // subsets of the exclusion set = partial planes of hist_min
+    uint32_t lr_cap = 32767;         // cells of a subset: 65535 / (most entries of a cell at one locus), at most 32767 (u16 counters)
     DevBuf<uint16_t> c4r;            // [nnz] compact by-cell entries: locus inside its 4096-locus range | code << 12 (code 15: overflow entry)
     DevBuf<uint32_t> roff;           // [nloc][R+1] offsets of the locus ranges inside each by-cell CSR row
 };

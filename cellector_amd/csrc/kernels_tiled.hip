@@ -1265,11 +1265,13 @@ __device__ __forceinline__ void c4_write1(uint32_t *__restrict__ base, uint64_t 
 // Form of the locus pass, decided on the device from this shard's exclusion-set size (see k_minority_hist below)
 #define LM_NUM 1  // minority-driven when n_min / nloc <= LM_NUM / LM_DEN
 #define LM_DEN 8
-// (n_sub = partial planes of the minority-driven form: its 16-bit LDS counters hold a subset of at most 32767 cells — half
-// the range, so that even a file that lists every (locus, cell) pair twice cannot carry into the neighbouring counter)
-__device__ __forceinline__ bool locus_by_minority(int mode, uint32_t n_min, uint64_t nloc, uint32_t n_sub)
+// (n_sub = partial planes of the minority-driven form; sub_cap = cells of a subset, i.e. what its 16-bit LDS counters hold: a
+// cell adds to one counter as many times as it has entries at one locus — a file may list a (locus, cell) pair any number of
+// times, every line being an entry — so a subset takes at most 65535 / (the most entries a cell of this matrix has at one
+// locus) cells, and never more than 32767 (tiled_build: lr_cap).  A set too large for that is counted by the streamed form.)
+__device__ __forceinline__ bool locus_by_minority(int mode, uint32_t n_min, uint64_t nloc, uint32_t n_sub, uint32_t sub_cap)
 {
-    if ((uint64_t)n_min > (uint64_t)n_sub * 32767u) return false;
+    if ((uint64_t)n_min > (uint64_t)n_sub * sub_cap) return false;
     return mode == 2 || (mode == 0 && (uint64_t)n_min * LM_DEN <= nloc * LM_NUM);
 }
 
@@ -1284,7 +1286,9 @@ __device__ __forceinline__ bool locus_by_minority(int mode, uint32_t n_min, uint
 //                               their signs to the kept plane and stores it back
 //   otherwise                   a recount of the new set: the minority-driven form (its planes replace the kept plane) or the
 //                               streamed one (k_locus_stats2 overwrites it), chosen as before (locus_mode)
-// A subset takes at least TALLY_SUB_CELLS cells (one batch of k_minority_ranges): a small change is few planes to add.
+// A subset takes at least TALLY_SUB_CELLS cells (one batch of k_minority_ranges): a small change is few planes to add — or
+// sub_cap cells where that is less (a matrix that lists a pair 64 times or more), so that k_minority_ranges' share of
+// ceil(n / subsets) cells never exceeds sub_cap: with n <= n_sub * sub_cap (tally_plan) both arms of the min keep it.
 #define TALLY_SUB_CELLS 1024
 struct TallyPlan {
     uint32_t n_a, n_r;  // cells counted with sign + (list positions 0 .. n_a-1) and - (n_a .. n_a+n_r-1)
@@ -1293,29 +1297,30 @@ struct TallyPlan {
     bool fresh;         // minority-driven recount: the planes replace the kept counts
     bool stream;        // streamed recount (k_locus_stats2)
 };
-__device__ __forceinline__ uint32_t tally_subsets(uint32_t n, uint32_t n_sub)
+__device__ __forceinline__ uint32_t tally_subsets(uint32_t n, uint32_t n_sub, uint32_t sub_cap)
 {
-    return min(n_sub, (n + TALLY_SUB_CELLS - 1) / TALLY_SUB_CELLS);
+    const uint32_t per = max(1u, min((uint32_t)TALLY_SUB_CELLS, sub_cap));  // (sub_cap 0: only an empty list gets here)
+    return min(n_sub, (n + per - 1) / per);
 }
-__device__ __forceinline__ TallyPlan tally_plan(int mode, int valid, const uint32_t *tc, uint64_t nloc, uint32_t n_sub)
+__device__ __forceinline__ TallyPlan tally_plan(int mode, int valid, const uint32_t *tc, uint64_t nloc, uint32_t n_sub, uint32_t sub_cap)
 {
     const uint32_t n_min = tc[0], n_add = tc[1], n_res = tc[2];
     TallyPlan p = {0u, 0u, 0u, 0u, false, false, false};
     if (valid) {
-        const uint64_t n_chg = (uint64_t)n_add + n_res, cap = (uint64_t)n_sub * 32767u;
+        const uint64_t n_chg = (uint64_t)n_add + n_res, cap = (uint64_t)n_sub * sub_cap;
         if (n_chg == 0) return p;
         // (the transposed offsets hold nloc * LM_NUM / LM_DEN cells whatever the locus_mode: tiled_locus_pass)
         if (n_chg <= n_min && n_chg * LM_DEN <= nloc * LM_NUM && n_add <= cap && n_res <= cap) {
             p.delta = true;
             p.n_a = n_add; p.n_r = n_res;
-            p.s_a = tally_subsets(n_add, n_sub); p.s_r = tally_subsets(n_res, n_sub);
+            p.s_a = tally_subsets(n_add, n_sub, sub_cap); p.s_r = tally_subsets(n_res, n_sub, sub_cap);
             return p;
         }
     }
-    if (locus_by_minority(mode, n_min, nloc, n_sub)) {
+    if (locus_by_minority(mode, n_min, nloc, n_sub, sub_cap)) {
         p.fresh = true;
         p.n_a = n_min;
-        p.s_a = tally_subsets(n_min, n_sub);
+        p.s_a = tally_subsets(n_min, n_sub, sub_cap);
     } else {
         p.stream = true;
     }
@@ -1337,9 +1342,9 @@ __global__ __launch_bounds__(LS_THREADS) void k_locus_stats2(uint64_t L, uint32_
                                                              const uint32_t *__restrict__ c4_ent,
                                                              const uint32_t *__restrict__ flag_bits,
                                                              uint32_t *__restrict__ tally, int locus_mode, int valid,
-                                                             uint64_t nloc, const uint32_t *__restrict__ tc, uint32_t n_sub)
+                                                             uint64_t nloc, const uint32_t *__restrict__ tc, uint32_t n_sub, uint32_t sub_cap)
 {
-    if (!tally_plan(locus_mode, valid, tc, nloc, n_sub).stream) return;  // kept counts, or k_minority_ranges counts
+    if (!tally_plan(locus_mode, valid, tc, nloc, n_sub, sub_cap).stream) return;  // kept counts, or k_minority_ranges counts
     extern __shared__ uint32_t s_bits[];
     __shared__ uint32_t s_whist[LS_THREADS / 64][16];
     if (threadIdx.x < (LS_THREADS / 64) * 16) (&s_whist[0][0])[threadIdx.x] = 0;
@@ -1490,18 +1495,40 @@ __global__ __launch_bounds__(256) void k_range_offsets(uint64_t n_rows, uint32_t
     }
 }
 
+// The most entries any cell has at ONE locus (1 unless the file repeats a (locus, cell) pair): rows are sorted by locus, so
+// the entries of a pair are a run; the lane at a run's first entry measures it.  Wave per row; out: one u32, zeroed.
+__global__ __launch_bounds__(256) void k_max_pair_entries(uint64_t n_rows, const uint64_t *__restrict__ csr_ptr,
+                                                          const uint64_t *__restrict__ csr_ent, uint32_t *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
+    uint32_t best = 1;
+    for (uint64_t row = wave0; row < n_rows; row += nwaves) {
+        const uint64_t beg = csr_ptr[row], end = csr_ptr[row + 1];
+        for (uint64_t i = beg + 1 + lane; i < end; i += 64) {
+            const uint64_t l = ENT_IDX(csr_ent[i]);
+            if (ENT_IDX(csr_ent[i - 1]) != l) continue;               // not repeated (nearly always)
+            if (i - 1 > beg && ENT_IDX(csr_ent[i - 2]) == l) continue;  // inside a run: its second entry measures it
+            uint32_t run = 2;
+            for (uint64_t k = i + 1; k < end && ENT_IDX(csr_ent[k]) == l; k++) run++;
+            best = max(best, run);
+        }
+    }
+    if (best > 1) atomicMax(out, best);
+}
+
 // The excluded cells' offset rows, gathered and transposed: mroff[r][k] for the k-th cell of minlist, mbeg[k] = start of its
 // row.  k_minority_ranges then reads its range's offsets as contiguous runs instead of one 64-byte line per (cell, range)
 // out of the big per-cell table (measured: those line fetches were a third of that kernel's traffic).
 #define LT_CELLS 64
-__global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, int valid, uint64_t nloc, uint32_t n_sub, uint32_t R,
+__global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, int valid, uint64_t nloc, uint32_t n_sub, uint32_t sub_cap, uint32_t R,
                                                           uint64_t mstride, const uint32_t *__restrict__ tc,
                                                           const uint32_t *__restrict__ minlist, const uint32_t *__restrict__ chg,
                                                           const uint64_t *__restrict__ csr_ptr,
                                                           const uint32_t *__restrict__ roff, uint32_t *__restrict__ mroff,
                                                           uint64_t *__restrict__ mbeg)
 {
-    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub, sub_cap);
     const uint32_t n_list = tp.n_a + tp.n_r;  // the plan's list (none: the streamed form, or no change)
     const uint32_t k0 = blockIdx.x * LT_CELLS;
     if (k0 >= n_list) return;
@@ -1530,7 +1557,7 @@ __global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, int va
 }
 
 __global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, int valid, uint64_t nloc, uint64_t L, uint32_t R,
-                                                               uint32_t n_sub, uint64_t mstride,
+                                                               uint32_t n_sub, uint32_t sub_cap, uint64_t mstride,
                                                                const uint32_t *__restrict__ tc,
                                                                const uint32_t *__restrict__ mroff,
                                                                const uint64_t *__restrict__ mbeg,
@@ -1538,11 +1565,12 @@ __global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, 
                                                                uint32_t *__restrict__ hist_min /*[2 n_sub][L][16] u16*/)
 {
     // (grid: R x 2 n_sub workgroups; those beyond the plan's subsets return)
-    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub, sub_cap);
     const uint32_t sub = blockIdx.x / R;
     if (sub >= tp.s_a + tp.s_r) return;
     // u16 counters, two per word, code-major: the bank of a counter follows the locus (spread out), not the code (most
-    // entries are single reads: codes 0 and 1).  A subset has at most 32767 cells (tally_plan): no carry.  Its cells
+    // entries are single reads: codes 0 and 1).  A subset has at most sub_cap cells (tally_plan), each with at most 65535 / sub_cap
+    // entries at one locus: no carry.  Its cells
     // are all of one sign (k_locus_finalize adds or subtracts the whole plane).
     __shared__ uint32_t s_hist[T_NCODE * LR_ROW / 2];
     __shared__ uint64_t s_beg[LR_THREADS];
@@ -1633,7 +1661,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_minority_ranges(int locus_mode, 
 // (alt+ref == 0 or > T_K; ~1 %, their log-pmfs evaluated from the locus' cumulative-log row) are walked 16 at a time; per-lane partial results
 // are added by a 4-step butterfly over the 16 lanes (fixed shape: deterministic).
 template <bool INLINE_OVF>  // the overflow entries' log-pmfs: evaluated here (deep coverage) or read from ovf_lp (k_ovf_values)
-__global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mode, int valid, uint64_t nloc, uint32_t n_sub,
+__global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mode, int valid, uint64_t nloc, uint32_t n_sub, uint32_t sub_cap,
                                                         const uint32_t *__restrict__ tc,
                                                         const uint32_t *__restrict__ hist_min, uint32_t *__restrict__ tally,
                                                         const uint32_t *__restrict__ flag_bits,
@@ -1652,7 +1680,7 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
                                                         uint32_t *__restrict__ n_filtered)
 {
     // the kept u32 counts (filled by k_locus_stats2 if it recounted), plus / minus this iteration's u16 partial planes
-    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub);
+    const TallyPlan tp = tally_plan(locus_mode, valid, tc, nloc, n_sub, sub_cap);
     const uint32_t n_planes = tp.s_a + tp.s_r;
     const uint32_t j = threadIdx.x % LF_LANES;
     const uint64_t l_raw = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / LF_LANES;
@@ -2398,6 +2426,7 @@ static cellector_status t2_tiles_pass_g(cellector_ctx *c, const double2 *ab, int
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
     int sb = T_SB_MAX;
     while (sb > 2 && (uint64_t)((c->t_nb + sb - 1) / sb) * c->t2_groups * 10 < (uint64_t)ncu * 9) sb >>= 1;
+    if (c->tile_sb_opt) sb = c->tile_sb_opt;
     const uint32_t n_cols = (c->t_nb + sb - 1) / sb;
     uint32_t per_group = (uint32_t)ncu / c->t2_groups;
     if (per_group < 1) per_group = 1;
@@ -2709,10 +2738,21 @@ cellector_status tiled_build(cellector_ctx *c)
         c->lr_sub = sub;
         CHK(dev_alloc(c, &c->hist_min, (uint64_t)sub * L * 16));
         CHK(dev_alloc(c, &c->roff, nloc * (R + 1)));
-        if (nloc)
+        // what a subset may hold (locus_by_minority): its u16 counters take 65535 / (most entries of a cell at one locus)
+        DevBuf<uint32_t> pair_max;
+        CHK(dev_alloc(c, &pair_max, 1));
+        HIPCHK(c, hipMemsetAsync(pair_max, 0, sizeof(uint32_t), c->stream));
+        if (nloc) {
             hipLaunchKernelGGL(k_range_offsets, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, R, (uint32_t)LR_LOCI, c->csr_ptr, c->csr_ent,
                                c->roff);
+            hipLaunchKernelGGL(k_max_pair_entries, dim3(gcap(nloc, 4, 1u << 16)), dim3(256), 0, c->stream, nloc, c->csr_ptr, c->csr_ent,
+                               pair_max.get());
+        }
         HIPCHK(c, hipGetLastError());
+        uint32_t h_pair_max = 0;
+        HIPCHK(c, hipMemcpyAsync(&h_pair_max, pair_max, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->lr_cap = std::min<uint32_t>(32767u, 65535u / std::max<uint32_t>(1u, h_pair_max));
         // the transposed offsets of the excluded cells, sized for the largest exclusion set the automatic choice hands to the
         // minority-driven form (allocated here, not in the first iteration's locus pass: that cost the first iteration a
         // stream synchronisation and two allocations — and a run has few iterations)
@@ -2909,6 +2949,7 @@ static cellector_status run_tile_pass(cellector_ctx *c, int set, bool expected)
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
     int sb = T_SB_MAX;
     while (sb > 2 && (uint64_t)((c->t_nb + sb - 1) / sb) * c->t_groups * 10 < (uint64_t)ncu * 9) sb >>= 1;  // < 90 % of the CUs busy
+    if (c->tile_sb_opt) sb = c->tile_sb_opt;  // option tile_sb: the width forced (tests)
     const uint32_t n_cols = (c->t_nb + sb - 1) / sb;
     // persistent workgroups: one per CU, an equal number for every chunk group, never more than there are columns
     uint32_t per_group = (uint32_t)ncu / c->t_groups;
@@ -3036,7 +3077,7 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     if (grid > need) grid = (unsigned)(need ? need : 1);
 #define LAUNCH_LS(INLDS, EBV, GRID, LDSB)                                                                              \
     hipLaunchKernelGGL((k_locus_stats2<INLDS, EBV>), dim3(GRID), dim3(LS_THREADS), LDSB, c->stream, c->L, words, c->c4_ptr, \
-                       c->c4_ent, c->flag_bits, c->tally, c->locus_mode, valid, c->nloc, c->d_counters + DC_N_MIN, c->lr_sub)
+                       c->c4_ent, c->flag_bits, c->tally, c->locus_mode, valid, c->nloc, c->d_counters + DC_N_MIN, c->lr_sub, c->lr_cap)
     // (a forced minority-driven form, locus_mode 2, still launches the streamed kernel: it returns at once unless the
     //  exclusion set is too large for that form's 16-bit counters, the one case the device predicate overrides the option;
     //  likewise locus_mode 1 launches the minority-driven kernels while counts are kept: they walk the change)
@@ -3071,11 +3112,11 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
         if (lds_t > 64 * 1024)
             HIPCHK(c, hipFuncSetAttribute((const void *)k_minority_offsets, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
         hipLaunchKernelGGL(k_minority_offsets, dim3(gcap(want, LT_CELLS, 0x7fffffffu)), dim3(256), lds_t, c->stream, c->locus_mode,
-                           valid, c->nloc, c->lr_sub, R, c->mroff_cap, c->d_counters + DC_N_MIN, c->minlist, c->chg, c->csr_ptr, c->roff,
+                           valid, c->nloc, c->lr_sub, c->lr_cap, R, c->mroff_cap, c->d_counters + DC_N_MIN, c->minlist, c->chg, c->csr_ptr, c->roff,
                            c->mroff, c->mbeg);
         // (R x lr_sub workgroups per sign: a change that both adds and rescues cells fills twice the planes of a recount)
         hipLaunchKernelGGL(k_minority_ranges, dim3(R * c->lr_sub * 2), dim3(LR_THREADS), 0, c->stream, c->locus_mode, valid, c->nloc,
-                           c->L, R, c->lr_sub, c->mroff_cap, c->d_counters + DC_N_MIN, c->mroff, c->mbeg, c->c4r, c->hist_min);
+                           c->L, R, c->lr_sub, c->lr_cap, c->mroff_cap, c->d_counters + DC_N_MIN, c->mroff, c->mbeg, c->c4r, c->hist_min);
     }
     // the tier-2 entries per (locus, pair) of the changed cells, or of the whole new set.  (On the side stream it does NOT run
     // beside k_minority_ranges, whose sixteen 128-register waves per CU leave no room: it started when that kernel ended, two
@@ -3093,7 +3134,7 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     const double *w_lp = c->t2 ? c->ovx_lp : c->ovf_lp;
 #define LAUNCH_LF(INL)                                                                                                             \
     hipLaunchKernelGGL(k_locus_finalize<INL>, dim3(gcap(c->L * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->L, c->locus_mode, \
-                       valid, c->nloc, c->lr_sub, c->d_counters + DC_N_MIN, c->hist_min, c->tally, c->flag_bits, c->hist_all,       \
+                       valid, c->nloc, c->lr_sub, c->lr_cap, c->d_counters + DC_N_MIN, c->hist_min, c->tally, c->flag_bits, c->hist_all, \
                        c->tab_em,                                                                                                  \
                        (uint32_t)c->tab_em_stride, c->mask, w_ptr, w_ent, w_lp, c->ovf_tab, c->lf, c->ab, c->x_locus,              \
                        c->t2 ? c->cnt2 : (uint32_t *)nullptr, c->hist_all2, c->t2_pmask, c->tab2,                                    \
