@@ -1035,6 +1035,112 @@ cellector_status cellector_em_iteration(cellector_ctx *c, double iqr_multiple, c
     return cellector_em_finish(c, out);
 }
 
+// ---- placing the EM state ------------------------------------------------------------------------------
+// (exclusion set, loci mask) is the whole state of the loop; everything else a ctx carries from one call to the next is
+// derived from the two and is dropped or formed again here.
+static cellector_status state_call_check(cellector_ctx *c, const char *what)
+{
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    // a shard whose exchanges the host drives has no exchange point here to hang the tally reduction on
+    if (!comm_active(c->comm) && c->nloc != c->total_cells)
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: a cellector_set_shard ctx without a communicator cannot place EM state "
+                        "(attach a communicator, or use cellector_create_multi)", what);
+    return CELLECTOR_OK;
+}
+
+// what the calls left for each other and was derived from the state that is being replaced
+static void state_drop_carried(cellector_ctx *c)
+{
+    c->tally_valid = false;      // the next locus pass recounts tally / cnt2 (the path a reload takes)
+    c->tables_prebuilt = false;  // em_finish queued k_build_tables from the OLD tallies and mask: the next em_begin builds again
+    c->tab_event_valid = false;  // ... and forks the side stream from a fresh event, not from that kernel's
+    c->filter_fused = false;
+    c->work_zeroed = false;
+    c->res_last_mode = 0;
+    c->pa_last_mode = 0;
+    c->pa_labels_changed = c->pa_qual_changed = 0;
+    c->pa_ids.clear();
+}
+
+cellector_status cellector_set_excluded(cellector_ctx *c, const uint8_t *flags)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return multi_set_excluded(c, flags);
+    CHK(state_call_check(c, "set_excluded"));
+    REQUIRE(c, flags || c->nloc == 0, "set_excluded: null flags");
+    SETDEV(c);
+    const uint64_t n = c->nloc, L = c->L;
+    std::vector<uint8_t> f(n);
+    for (uint64_t i = 0; i < n; i++) f[i] = flags[i] ? 1 : 0;
+    state_drop_carried(c);  // (forces recounts and rebuilds only: harmless should the placement fail below)
+    CHK(launch_state_tallies(c, f.data()));  // allocates, then writes the flags and the tallies; synchronises
+    // the exchange the locus pass of an iteration is followed by: global tallies and the global member count on every rank
+    if (comm_active(c->comm)) CHK((cellector_status)comm_allreduce_sum(c, c->x_locus, (uint64_t)LB_PLANES * L + LC_COUNTERS));
+    double n_exc = 0.0;
+    CHK(d2h(c, &n_exc, c->x_locus + (uint64_t)LB_PLANES * L + LC_N_EXCLUDED, sizeof n_exc));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->n_excluded_global = (uint64_t)n_exc;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_set_loci_mask(cellector_ctx *c, const uint8_t *used)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return multi_set_loci_mask(c, used);
+    CHK(state_call_check(c, "set_loci_mask"));
+    REQUIRE(c, used || c->L == 0, "set_loci_mask: null mask");
+    SETDEV(c);
+    const uint64_t L = c->L;
+    std::vector<uint8_t> m(L);
+    uint64_t n_masked = 0;
+    for (uint64_t l = 0; l < L; l++) {
+        m[l] = used[l] ? 1 : 0;
+        n_masked += m[l] ? 0 : 1;
+    }
+    // engine 2's recount needs an all-ones "old" mask: allocated before the mask is written, so a failure leaves the ctx as it was
+    DevBuf<uint8_t> ones;
+    if (c->tiled_ready && L && c->nloc) CHK(dev_alloc(c, &ones, L));
+    state_drop_carried(c);
+    if (L) {
+        HIPCHK(c, hipMemcpyAsync(c->mask, m.data(), L, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->mask_next, m.data(), L, hipMemcpyHostToDevice, c->stream));
+    }
+    // engine 2 subtracts every cell's entries at masked loci from its used-locus count; engine 1 reads the mask itself
+    // (k_alpha_beta marks a masked locus' alpha, k_cell_ll skips it): nothing else to place
+    if (c->tiled_ready) CHK(tiled_masked_recount(c, ones.get()));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (m and the scratch may go)
+    c->n_masked_loci = n_masked;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_em_reset(cellector_ctx *c)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return multi_em_reset(c);
+    CHK(state_call_check(c, "em_reset"));
+    SETDEV(c);
+    const uint64_t L = c->L, n = c->nloc;
+    state_drop_carried(c);
+    HIPCHK(c, hipMemsetAsync(c->mask, 1, L ? L : 1, c->stream));  // load_data.rs:176-179: all loci used
+    HIPCHK(c, hipMemsetAsync(c->mask_next, 1, L ? L : 1, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->flags, 0, n ? n : 1, c->stream));   // main.rs:37: the empty set
+    HIPCHK(c, hipMemsetAsync(c->flags_new, 0, n ? n : 1, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ll, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ell, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->nloci, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (c->n_norm ? c->n_norm : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->x_locus, 0, ((uint64_t)LB_PLANES * L + LC_COUNTERS) * 8, c->stream));
+    if (c->tiled_ready) {
+        HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (n ? n : 1) * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->flag_bits, 0, ((n + 31) / 32 + 1) * 4, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->iteration = 0; c->have_iter = false; c->n_excluded_global = 0; c->n_masked_loci = 0;
+    c->last_median = c->last_iqr = c->last_thr = 0;
+    return CELLECTOR_OK;
+}
+
 cellector_status cellector_iter_resolution(const cellector_ctx *c, cellector_resolution_t *out)
 {
     if (!c || !out) return CELLECTOR_EINVAL;

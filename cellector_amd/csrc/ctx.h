@@ -405,6 +405,8 @@ cellector_status launch_ab_from_host(cellector_ctx *c, const double *alpha, cons
 cellector_status launch_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj,
                                    double lp_dbl, double *sdbl);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
+// placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
+cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);
 // order statistics: exact values at SEL_T 0-based ranks of n keys
 cellector_status select_threshold(cellector_ctx *c, const double *keys, uint64_t n, double iqr_multiple);
 cellector_status ffi_order_statistics(cellector_ctx *c, const double *keys, uint64_t n_local, uint64_t n_total, double iqr_multiple,
@@ -446,6 +448,8 @@ cellector_status tiled_build(cellector_ctx *c);
 cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em);
 cellector_status tiled_locus_pass(cellector_ctx *c);
 cellector_status tiled_masked_update(cellector_ctx *c);
+// masked_cnt from scratch under c->mask (cellector_set_loci_mask); ones: [L] device scratch, allocated before the mask was written
+cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones);
 cellector_status tiled_prebuild_tables(cellector_ctx *c);
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl);
 // device-side mtx text parse (kernels_parse.hip)

@@ -3174,6 +3174,22 @@ cellector_status tiled_masked_update(cellector_ctx *c)
     return CELLECTOR_OK;
 }
 
+// a caller's mask (cellector_set_loci_mask): the counts from scratch — zeroed, then one update from an all-ones "old" mask to c->mask
+cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones)
+{
+    HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (c->nloc ? c->nloc : 1) * 4, c->stream));
+    if (c->L == 0 || c->nloc == 0) return CELLECTOR_OK;
+    HIPCHK(c, hipMemsetAsync(ones, 1, c->L, c->stream));
+    if (c->c4_bits == 24)
+        hipLaunchKernelGGL(k_masked_update<24>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, ones, c->mask.get(),
+                           c->c4_ptr.get(), c->c4_ent.get(), c->ovc_ptr.get(), c->ovc_ent.get(), c->masked_cnt.get());
+    else
+        hipLaunchKernelGGL(k_masked_update<32>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, ones, c->mask.get(),
+                           c->c4_ptr.get(), c->c4_ent.get(), c->ovc_ptr.get(), c->ovc_ent.get(), c->masked_cnt.get());
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
+
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl)
 {
     c->tables_prebuilt = false;  // the posterior passes rebuild table set 0 and use its column counters

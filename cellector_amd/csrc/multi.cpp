@@ -475,6 +475,22 @@ cellector_status multi_em_iteration(cellector_ctx *root, double iqr_multiple, ce
     return st;
 }
 
+// ---- placing the EM state: the flags are global, every shard takes its slice and the shards reduce the tallies among
+// themselves (cellector_set_excluded on a ctx with a communicator); the mask is per-locus state, the same on every shard
+cellector_status multi_set_excluded(cellector_ctx *root, const uint8_t *flags)
+{
+    if (!flags) return ctx_fail(root, CELLECTOR_EINVAL, "set_excluded: null flags");
+    return per_cell(root, [=](cellector_ctx *s, uint64_t b) { return cellector_set_excluded(s, flags + b); });
+}
+cellector_status multi_set_loci_mask(cellector_ctx *root, const uint8_t *used)
+{
+    return run_all(root, [=](cellector_ctx *s, int) { return cellector_set_loci_mask(s, used); });
+}
+cellector_status multi_em_reset(cellector_ctx *root)
+{
+    return run_all(root, [=](cellector_ctx *s, int) { return cellector_em_reset(s); });
+}
+
 cellector_status multi_final_allele_tallies(cellector_ctx *root, uint64_t *alt_min, uint64_t *ref_min, uint64_t *alt_maj, uint64_t *ref_maj)
 {
     MultiCtx *m = root->multi;

@@ -23,6 +23,9 @@ cellector_status multi_cell_log_likelihoods(cellector_ctx *root, const double *a
 cellector_status multi_posteriors(cellector_ctx *root, double *posterior, double *doublet, double *ll_maj, double *ll_min);
 cellector_status multi_csr_rows(const cellector_ctx *root, uint64_t rb, uint64_t re, uint64_t *row_ptr, uint64_t *entries, uint64_t capacity);
 cellector_status multi_em_iteration(cellector_ctx *root, double iqr_multiple, cellector_iter_summary *out);
+cellector_status multi_set_excluded(cellector_ctx *root, const uint8_t *flags /*[total cells], global order*/);
+cellector_status multi_set_loci_mask(cellector_ctx *root, const uint8_t *used /*[L]*/);
+cellector_status multi_em_reset(cellector_ctx *root);
 cellector_status multi_final_allele_tallies(cellector_ctx *root, uint64_t *alt_min, uint64_t *ref_min, uint64_t *alt_maj, uint64_t *ref_maj);
 cellector_status multi_engine_info(const cellector_ctx *root, cellector_engine_info_t *o);
 cellector_status multi_reset_timing(cellector_ctx *root);

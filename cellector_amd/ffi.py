@@ -50,6 +50,9 @@ SIGNATURES = {
     "cellector_em_threshold": (_i, [_vp, _d]),
     "cellector_em_finish": (_i, [_vp, _vp]),
     "cellector_em_iteration": (_i, [_vp, _d, _vp]),
+    "cellector_set_excluded": (_i, [_vp, _vp]),
+    "cellector_set_loci_mask": (_i, [_vp, _vp]),
+    "cellector_em_reset": (_i, [_vp]),
     "cellector_iter_resolution": (_i, [_vp, _vp]),
     "cellector_iter_resolved_cells": (_i, [_vp, _vp]),
     "cellector_iter_cell_outputs": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -302,6 +305,27 @@ class Cellector:
             if not s.any_change:
                 break
         return out
+
+    # ---- placing the EM state (exclusion set, loci mask) without a reload
+    def set_excluded(self, flags):
+        """excluded_cells := {i : flags[i] != 0} (cellector_set_excluded): local cells, or all cells of a multi-device ctx.
+        The ctx is then the one whose last iteration produced this set: alpha_betas(), posteriors(), assign(),
+        final_allele_tallies() use it, the next em_iteration() counts new / rescued cells against it."""
+        f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+        if f.shape != (self.n_local,):
+            raise ValueError(f"set_excluded: {self.n_local} flags expected, got shape {f.shape}")
+        self._ck(self._lib.cellector_set_excluded(self.h, _p(f)))
+
+    def set_loci_mask(self, used):
+        """loci_used := used, 1 = used, as loci_mask() returns it (cellector_set_loci_mask)"""
+        m = np.ascontiguousarray(np.asarray(used) != 0, dtype=np.uint8)
+        if m.shape != (self.dims().loci_used,):
+            raise ValueError(f"set_loci_mask: {self.dims().loci_used} entries expected, got shape {m.shape}")
+        self._ck(self._lib.cellector_set_loci_mask(self.h, _p(m)))
+
+    def em_reset(self):
+        """back to the state the ingest left: empty exclusion set, all loci used, iteration 0 (cellector_em_reset)"""
+        self._ck(self._lib.cellector_em_reset(self.h))
 
     def resolution(self):
         """What option resolve_ties did in the last iteration (cellector_iter_resolution): cells evaluated with the reference's

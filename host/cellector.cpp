@@ -173,6 +173,7 @@ struct Params {
     bool devices_auto = false;                         // --devices auto: as many visible GPUs as the input can feed
     bool resolve_near_ties = false;                    // extension: option resolve_ties (single GPU)
     int resolve_assignments = 0;                       // extension: options resolve_ties + resolve_posteriors = 1 (true) / 2 (all)
+    std::optional<std::string> initial_minority;       // extension: barcodes of the initial exclusion set (main.rs:37 starts from none)
 };
 
 const char *USAGE =
@@ -203,7 +204,11 @@ const char *USAGE =
     "                                                                       next to a decision edge (all: of every cell) in the reference's\n"
     "                                                                       own arithmetic: cellector_assignments.tsv then has the reference's\n"
     "                                                                       labels and quals (all: its bytes) (not in the reference; default\n"
-    "                                                                       false; one GPU)\n";
+    "                                                                       false; one GPU)\n"
+    "        --initial_minority <file>                                      start the loop from these cells as the excluded (minority) set\n"
+    "                                                                       instead of the empty set: one barcode per line, first tab-separated\n"
+    "                                                                       column (a filtered cellector_assignments.tsv works), blank lines\n"
+    "                                                                       ignored (not in the reference)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -228,7 +233,7 @@ Params load_params(int argc, char **argv)
     static const char *known[] = {"output_directory", "ref", "alt", "barcodes", "min_alt", "min_ref", "ground_truth",
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
-                                  "resolve_near_ties", "resolve_assignments"};
+                                  "resolve_near_ties", "resolve_assignments", "initial_minority"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -286,6 +291,7 @@ Params load_params(int argc, char **argv)
             die(EXIT_PANIC, "invalid value '" + v + "' for --resolve_assignments: expected true, false or all");
         p.resolve_assignments = v == "true" ? 1 : (v == "all" ? 2 : 0);
     }
+    if (got.count("initial_minority")) p.initial_minority = got["initial_minority"];
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_assignments " + got["resolve_assignments"] +
                    "' works on one GPU and cannot be used with '--devices <a,b,...>'");
@@ -405,6 +411,22 @@ int main(int argc, char **argv)
         }
     }
 
+    // --initial_minority: the cells the loop starts from as excluded_cells (main.rs:37 has `HashSet::new()`)
+    std::vector<uint32_t> initial_minority;
+    if (params.initial_minority) {
+        Lines in(*params.initial_minority);
+        std::string line;
+        for (size_t line_no = 1; in.next(line); line_no++) {
+            const std::string bc = line.substr(0, line.find('\t'));
+            if (bc.empty()) continue;
+            const size_t cell = barcode_to_cell(bc);
+            if (cell == SIZE_MAX)
+                die(1, "error: --initial_minority " + *params.initial_minority + " line " + std::to_string(line_no) + ": barcode '" + bc +
+                           "' is not in the barcodes file " + params.barcodes);
+            initial_minority.push_back((uint32_t)cell);
+        }
+    }
+
     // CELLECTOR_TIMING=1: phase wall times on stderr (not part of the reference's output)
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
@@ -465,6 +487,18 @@ int main(int argc, char **argv)
     std::vector<uint32_t> entries_per_cell(N);
     g.ck(cellector_locus_ids(g.c, locus_ids.data()), "locus_ids");
     g.ck(cellector_entries_per_cell(g.c, entries_per_cell.data()), "entries_per_cell");
+
+    if (params.initial_minority) {  // excluded_cells before the first compute_new_excluded
+        std::vector<uint8_t> flags(N, 0);
+        for (const uint32_t cell : initial_minority) {
+            if (cell >= N)
+                die(1, "error: --initial_minority: barcode '" + std::string(barcodes[cell]) + "' is line " + std::to_string(cell + 1) +
+                           " of the barcodes file but the matrix has " + std::to_string(N) + " cells");
+            flags[cell] = 1;
+        }
+        g.ck(cellector_set_excluded(g.c, flags.data()), "initial_minority");
+        lap("initial exclusion set");
+    }
 
     // load_vcf_data (load_data.rs:37-63)
     std::vector<VcfLocus> vcf_data;

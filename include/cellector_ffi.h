@@ -250,6 +250,48 @@ cellector_status cellector_em_finish(cellector_ctx *ctx, cellector_iter_summary 
 cellector_status cellector_em_iteration(cellector_ctx *ctx, double iqr_multiple,
                                         cellector_iter_summary *out);
 
+/* ---- placing the EM state ---------------------------------------------------------------------
+ * The reference's loop state is (excluded_cells, loci_used): main.rs:37 starts it from `HashSet::new()` and
+ * load_data.rs:176-179 from all loci used; main.rs:43 and :444-447 are the only places that move it.  The three calls below
+ * put a ctx at a state of the caller's choosing without a reload: warm starts from a known partition (the reference's -g
+ * ground truth, a souporcell clustering, an earlier run's assignments), another interquartile_range_multiple on the resident
+ * matrix, checkpoint / restore.  Everything the ctx derives from the state (the per-locus minority tallies behind
+ * cellector_alpha_betas and the posterior phase, the kept counts of option tally_delta, the per-cell counts of entries at
+ * masked loci, tables built ahead) is formed again or dropped.
+ * All three need a loaded matrix and no iteration in flight (not between cellector_em_begin and cellector_em_finish), else
+ * CELLECTOR_EINVAL.  They work on a single-device ctx, on a multi-device ctx (global arrays, global cell order, like
+ * cellector_assign) and on a ctx with a communicator (this rank's local cells, like cellector_excluded; every rank makes
+ * the same call, the library reduces the tallies itself).  A cellector_set_shard ctx WITHOUT a communicator is refused with
+ * CELLECTOR_EINVAL: the host drives its exchanges and there is no exchange point for the tally reduction.
+ * cellector_iter_cell_outputs keeps returning the last iteration's per-cell values after set_excluded / set_loci_mask.
+ * cellector_iter_locus_outputs reads the exchange buffer and the mask the calls write, so after a placement it no longer
+ * shows the last iteration (and after cellector_em_reset it is refused until an iteration has finished):
+ *   - after set_excluded: the placed set's minority / majority counts and allele tallies, both contribution columns 0 (no
+ *     pass produced any); the minority cell count of a locus the CURRENT mask masks is 0;
+ *   - after set_loci_mask: the columns that are 0 at a masked locus (majority count, the four allele tallies) follow the
+ *     NEW mask, the contributions stay the last pass', and the minority cell count is NOT formed again: it stays 0 at a
+ *     locus the old mask masked and the new one uses, and keeps its value at a locus the new mask masks.
+ * So for a locus view of a placed state call set_loci_mask first, then set_excluded; the order matters to this one call
+ * only (nothing else reads that count before the next locus pass rewrites it).  Copy the locus outputs before a placement
+ * if the last iteration's are still wanted.
+ * Failure: the calls validate and allocate before they write.  If the tally exchange of a communicator fails afterwards
+ * (CELLECTOR_ECOMM), the ctx holds the new flags with unreduced tallies: call cellector_em_reset or place a set again. */
+/* excluded_cells := {i : flags[i] != 0} — replaces main.rs:37's `HashSet::new()` / main.rs:43's assignment.  Afterwards the
+ * ctx is the one whose last cellector_em_finish produced this set: cellector_excluded returns it, cellector_alpha_betas is
+ * init_alpha_betas(set) (main.rs:598-611), cellector_posteriors / _assign / _final_allele_tallies use it, and the next
+ * iteration is compute_new_excluded(excluded_cells = set) with n_new_excluded / n_rescued counted against it
+ * (main.rs:333-334).  The tallies are recounted on the device from the set's rows with integer atomics: exact for any set. */
+cellector_status cellector_set_excluded(cellector_ctx *ctx, const uint8_t *flags /*[local cells]*/);
+/* loci_used := used (1 = used, as cellector_loci_mask returns it; the same array on every rank) — replaces the all-true
+ * vector of load_data.rs:176-179 and the filter's writes (main.rs:444-447).  A masked locus leaves the per-cell sums
+ * (main.rs:556) and still counts in the tallies and alpha/beta, exactly like a locus the loop's own -80 filter masked.
+ * All-zero and all-one masks are legal (all-zero: every normalised LL is 0, main.rs:315-322). */
+cellector_status cellector_set_loci_mask(cellector_ctx *ctx, const uint8_t *used /*[L]*/);
+/* Back to the state cellector_ingest_finish left — empty exclusion set, all loci used, iteration 0, zeroed exchange and
+ * output buffers — i.e. main.rs:37 and load_data.rs:176-179 again, on the resident matrix.  No layout is rebuilt; options
+ * keep their values. */
+cellector_status cellector_em_reset(cellector_ctx *ctx);
+
 /* What option resolve_ties did in the last iteration (all zero when it was off, and on a multi-device ctx). */
 typedef struct {
     uint64_t n_evaluated;      /* cells evaluated with the reference's arithmetic                                     */

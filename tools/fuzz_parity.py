@@ -2,7 +2,7 @@
 """Randomised parity sweep (needs an MI355X): whole runs of the HIP path against the CPU oracle on matrices of random shape,
 density, minority share and count distribution — the checks of tests/test_gpu_parity.py on inputs nobody picked by hand.
 
-  python tools/fuzz_parity.py [--cases 40] [--seed 1] [--max-cells 60000] [--resolve-ties] [--resolve-posteriors]
+  python tools/fuzz_parity.py [--cases 40] [--seed 1] [--max-cells 60000] [--resolve-ties] [--resolve-posteriors] [--warm-start]
 
 Every case: ingest (device generator, then counts widened at random so that all overflow tiers occur), both engines or
 engine 2 with a random option set (locus-pass form, overlap, two shards), EM loop until the oracle stops, posteriors,
@@ -14,7 +14,11 @@ cases the plain comparison reports as undecidable (cells on the threshold to 1e-
 
 --resolve-posteriors: every single-device case runs again with resolve_ties and resolve_posteriors both on (mode 1, then mode 2):
 labels, anomaly flags and quals of cellector_assign must equal the oracle's and the evaluated cells' posterior, doublet
-posterior and LLs must be its bits, for 0.999 and a few random thresholds, some taken from a cell's own posterior."""
+posterior and LLs must be its bits, for 0.999 and a few random thresholds, some taken from a cell's own posterior.
+
+--warm-start: every case runs again from a random initial exclusion set of random size (0 ... N), placed with
+cellector_set_excluded (a single-device ctx, or one ctx over two logical shards for the two-shard cases) and in the oracle with
+Oracle.set_excluded: alpha/beta of the placed set exact, then every iteration as in the plain run, then posteriors."""
 import argparse
 import os
 import sys
@@ -35,6 +39,8 @@ def main():
     ap.add_argument("--resolve-ties", action="store_true", help="also run every single-device case with option resolve_ties")
     ap.add_argument("--resolve-posteriors", action="store_true",
                     help="also run every single-device case with resolve_ties and resolve_posteriors on (modes 1 and 2)")
+    ap.add_argument("--warm-start", action="store_true",
+                    help="also run every case from a random initial exclusion set (cellector_set_excluded)")
     args = ap.parse_args()
     from cellector_amd import Cellector, ffi, synth
     from oracle import binding as ob
@@ -47,6 +53,7 @@ def main():
     t_all = time.time()
     n_resolved = n_resolved_undecidable = 0
     n_assign = n_assign_evaluated = n_assign_cells = 0
+    n_warm = n_warm_undecidable = 0
     for case in range(args.cases):
         N = int(rng.choice([1, 3, 70, 700, 1100, 5000, 20000, args.max_cells]))
         L = int(rng.choice([50, 400, 1500, 4200, 9000]))  # (one or two loci: every cell ties with thousands of others)
@@ -119,6 +126,14 @@ def main():
             res += "; resolve_posteriors: " + ("exact" if a_ok else "MISMATCH")
             if not a_ok:
                 ok = False
+        if args.warm_start and ok is not False:
+            w_ok = run_warm_start(Cellector, ffi, synth, ob, T, engine, opts, two_shards, L, N, lo, ce, al, re, min_alt, min_ref,
+                                  np.random.default_rng(args.seed * 7919 + case))
+            n_warm += 1
+            n_warm_undecidable += w_ok is None
+            res += "; warm start: " + ("exact" if w_ok else ("undecidable (near-ties)" if w_ok is None else "MISMATCH"))
+            if w_ok is False:
+                ok = False
         print(f"{desc}: {'ok' if ok else ('undecidable (near-ties)' if ok is None else 'MISMATCH')}{res} ({time.time() - t0:.1f} s)",
               flush=True)
         if ok is False:
@@ -126,9 +141,44 @@ def main():
     print(f"{args.cases} cases ok in {time.time() - t_all:.0f} s")
     if args.resolve_ties:
         print(f"resolve_ties: {n_resolved} cases exact, {n_resolved_undecidable} of them undecidable without the option")
+    if args.warm_start:
+        print(f"warm start: {n_warm} cases, {n_warm - n_warm_undecidable} matched the oracle, {n_warm_undecidable} undecidable "
+              f"(near-ties), 0 mismatches")
     if args.resolve_posteriors:
         print(f"resolve_posteriors: {n_assign} cases exact (modes 1 and 2); mode 1 evaluated {n_assign_evaluated} of "
               f"{n_assign_cells} cells x thresholds")
+
+
+def run_warm_start(Cellector, ffi, synth, ob, T, engine, opts, two_shards, L, N, lo, ce, al, re, min_alt, min_ref, rng):
+    """the case again from a random initial exclusion set of random size.  True / None (near-ties: undecidable) / False"""
+    flags = np.zeros(N, np.uint8)
+    flags[rng.choice(N, int(rng.integers(0, N + 1)), replace=False)] = 1
+    o = ob.Oracle.from_coo(L, N, lo, ce, al, re, min_alt, min_ref)
+    g = Cellector(devices=[0, 0]) if two_shards else Cellector(0)
+    g.set_option("engine", engine)
+    for k, v in opts.items():
+        g.set_option(k, v)
+    g.load_coo(L, N, lo, ce, al, re, min_alt, min_ref)
+    g.set_excluded(flags)
+    o.set_excluded(flags)
+    ok = bool(np.array_equal(g.excluded(), flags))
+    (ag, bg), (ao, bo) = g.alpha_betas(), o.alpha_betas()
+    ok = ok and bool(np.array_equal(ag, ao) and np.array_equal(bg, bo))
+    if not ok:
+        print(f"  warm start: the placed state differs ({int(flags.sum())} of {N} cells)", flush=True)
+    elif o.loci_used and N:
+        try:
+            T._run_both(g, o)
+            T._check_posteriors(dict(ffi=ffi, synth=synth, ob=ob, engine=engine), g, o)
+        except AssertionError as e:
+            if "near-tie" not in str(e):
+                print(f"  warm start from {int(flags.sum())} of {N} cells: {str(e)[:300]}", flush=True)
+                ok = False
+            else:
+                ok = None
+    g.close()
+    o.close()
+    return ok
 
 
 def run_resolved_posteriors(Cellector, ob, engine, opts, L, N, lo, ce, al, re, min_alt, min_ref, rng):
