@@ -162,12 +162,20 @@ __global__ __launch_bounds__(PB) void k_parse_lines(const uint8_t *__restrict__ 
 
 // ---- zip, validate, shard filter ------------------------------------------------------------------------------
 enum { PE_NONE = 0, PE_INDEX0 = 1, PE_LOCUS = 2, PE_CELL = 3, PE_COUNT = 4 };
+#define PE_KIND_BITS 3  // k_pair_check reports (entry << PE_KIND_BITS) | kind: the minimum is the smallest entry, with ITS kind
+static const char *const pe_what[] = {"", "index 0 (indices are 1-based)", "locus index out of range", "cell index out of range",
+                                      "count above 65535 not supported"};
+inline const char *pe_kind_text(unsigned long long packed)
+{
+    const unsigned kind = (unsigned)(packed & ((1u << PE_KIND_BITS) - 1));
+    return pe_what[kind <= PE_COUNT ? kind : 0];
+}
 
 __global__ __launch_bounds__(PB) void k_pair_check(uint64_t n, const uint32_t *__restrict__ l1, const uint32_t *__restrict__ c1,
                                                    const uint32_t *__restrict__ a, const uint32_t *__restrict__ r,
                                                    uint64_t total_loci, uint64_t total_cells, uint64_t cb, uint64_t ce,
                                                    uint64_t *__restrict__ keep, unsigned long long *__restrict__ first_bad,
-                                                   uint32_t *__restrict__ bad_kind, uint32_t *__restrict__ unsorted)
+                                                   uint32_t *__restrict__ unsorted)
 {
     const uint64_t i = (uint64_t)blockIdx.x * PB + threadIdx.x;
     if (i > n) return;
@@ -178,7 +186,7 @@ __global__ __launch_bounds__(PB) void k_pair_check(uint64_t n, const uint32_t *_
     else if (c1[i] > total_cells) kind = PE_CELL;
     else if (a[i] > CELLECTOR_MAX_COUNT || r[i] > CELLECTOR_MAX_COUNT) kind = PE_COUNT;
     if (kind != PE_NONE) {
-        if (atomicMin(first_bad, (unsigned long long)i) > i) *bad_kind = kind;  // best effort: kind of the smallest seen
+        atomicMin(first_bad, ((unsigned long long)i << PE_KIND_BITS) | kind);  // entry and kind in one word: the smallest entry's own kind
         if (keep) keep[i] = 0;
         return;
     }
@@ -948,7 +956,7 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     S->r_dev[rank] = nullptr;
     // ---- 3. zip + validation of this shard's lines, in place
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(count + 1)), dim3(PB), 0, c->stream, count, l1 + lo, c1 + lo, a + lo, rk + lo, TL, TC,
-                       (uint64_t)0, TC, (uint64_t *)nullptr, bad + 2, flags, flags + 1);
+                       (uint64_t)0, TC, (uint64_t *)nullptr, bad + 2, flags + 1);
     uint32_t edge[2] = {0, 0};
     e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, c->stream);
@@ -956,8 +964,8 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     if (e == hipSuccess && count) e = hipMemcpyAsync(&edge[1], l1 + lo + count - 1, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)));
-    S->bad_z[rank] = h_bad[2] == ~0ull ? ~0ull : glo + h_bad[2];
-    S->bad_kind[rank] = h_flags[0]; S->unsorted[rank] = h_flags[1];
+    S->bad_z[rank] = h_bad[2] == ~0ull ? ~0ull : glo + (h_bad[2] >> PE_KIND_BITS);  // (local entry -> global, the kind beside it)
+    S->bad_kind[rank] = (uint32_t)(h_bad[2] & ((1u << PE_KIND_BITS) - 1)); S->unsorted[rank] = h_flags[1];
     S->first_locus[rank] = edge[0]; S->last_locus[rank] = edge[1]; S->lines[rank] = count;
     SBARRIER();
     {
@@ -965,10 +973,8 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
         for (int k = 0; k < n; k++)
             if (S->bad_z[k] != ~0ull && (worst < 0 || S->bad_z[k] < S->bad_z[worst])) worst = k;
         if (worst >= 0) {
-            static const char *what[] = {"", "index 0 (indices are 1-based)", "locus index out of range", "cell index out of range",
-                                         "count above 65535 not supported"};
             (void)S->bar->barrier();
-            return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", S->bad_z[worst], what[S->bad_kind[worst] <= 4 ? S->bad_kind[worst] : 0]);
+            return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", S->bad_z[worst], pe_kind_text(S->bad_kind[worst]));
         }
         bool sorted = true;
         uint32_t prev_last = 0;
@@ -1192,7 +1198,7 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     const bool all_cells = c->cell_begin == 0 && c->cell_end >= c->total_cells;
     if (!all_cells) CHK(dev_alloc(c, &keep, n + 1));
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(n + 1)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->total_loci, c->total_cells,
-                       c->cell_begin, c->cell_end, keep, bad + 2, flags, flags + 1);
+                       c->cell_begin, c->cell_end, keep, bad + 2, flags + 1);
     // the validation result is read BEHIND k_pair_check on the ctx's stream (a caller-supplied non-blocking stream does
     // not order against null-stream copies: the range check could be read before the kernel ran)
     e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
@@ -1200,9 +1206,7 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
     if (h_bad[2] != ~0ull) {
-        static const char *what[] = {"", "index 0 (indices are 1-based)", "locus index out of range", "cell index out of range",
-                                     "count above 65535 not supported"};
-        return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", h_bad[2], what[h_flags[0] <= 4 ? h_flags[0] : 0]);
+        return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", h_bad[2] >> PE_KIND_BITS, pe_kind_text(h_bad[2]));
     }
     c->coo_sorted = h_flags[1] == 0;
     if (all_cells) {
