@@ -243,6 +243,7 @@ cellector_status cellector_create(cellector_ctx **out, int device_id)
     cellector_ctx *c = new (std::nothrow) cellector_ctx();
     if (!c) return CELLECTOR_ENOMEM;
     c->device = device_id;
+    (void)hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device_id);
     // ln(FCACHE[x]), x = 0..170: statrs' factorial cache, logs taken with the host libm like the reference
     double lf[LF_TABLE_N], f = 1.0;
     lf[0] = std::log(1.0);

@@ -84,7 +84,7 @@ enum { DC_N_FILTERED = 0, DC_N_MIN = 4 /* members of this shard's new exclusion 
        DC_N_ADD = 5 /* ... of them not in the old set (k_flag's change list, front) */,
        DC_N_RES = 6 /* cells of the old set not in the new one (rescued; the change list's back end) */ };
 
-#define T_ROWS_PER_TILE 1024  // rows (cells) of a tile of the tiled layout (= T_BC in kernels_tiled.hip)
+#define T_ROWS_PER_TILE 1024  // rows (cells) of a tile of the tiled layout (= T_BC in tiled.h)
 #define CELLECTOR_TILE_WORK_STRIDE 64  // column counters per table set of the persistent tile kernel (= T_GROUPS_MAX)
 
 #define LF_TABLE_N 171  // ln(FCACHE[0..170]) — statrs ln_factorial cache, SURVEY Appendix B.2
@@ -115,8 +115,8 @@ struct CtxOptions {
     bool tally_delta = true;    // option "tally_delta": engine 2 keeps the exclusion set's per-(locus, code) counts across
                                 // iterations and updates them from the set's change (0: recounts every iteration; A/B)
     bool bank_order = true;  // option "bank_order": the tile builder orders every row's entries against LDS bank conflicts (tile_bank_order)
-    int tile_groups_opt = 0;  // option tile_groups: 0 = chosen per matrix (tiled_setup), else forced (multiple of 8)
-    int tile_sb_opt = 0;  // option tile_sb: 0 = cell blocks per column of the tile kernel chosen per launch (run_tile_pass), 2 or 4 forced (tests)
+    int tile_groups_opt = 0;  // option tile_groups: 0 = chosen per matrix (tile_groups_for), else forced (multiple of 8)
+    int tile_sb_opt = 0;  // option tile_sb: 0 = cell blocks per column of the tile kernel chosen per launch (tile_geometry), 2 or 4 forced (tests)
     // option sharded_select: a ctx with a communicator exchanges digit histograms (1) or all-gathers NORM (0); -1 = by the
     // number of ranks (use_sharded_select)
     int sharded_select = -1;
@@ -203,7 +203,7 @@ struct CtxMatrix {
     uint64_t n_masked_loci = 0;
 };
 
-// ---- engine v2: table-driven tiled layout (kernels_tiled.hip): what tiled_build makes ----
+// ---- engine v2: table-driven tiled layout: what tiled_build (kernels_tiled_build.hip) makes for the passes of kernels_tiled.hip ----
 struct CtxTiled {
     bool tiled_ready = false;
     uint32_t t_nb = 0, t_nj = 0, t_groups = 0, t_cpg = 0;  // cell blocks, locus chunks, chunk groups, chunks/group
@@ -237,7 +237,7 @@ struct CtxTiled {
     DevBuf<uint32_t> t2_pmask;       // [L] bit c2: the pair occurs at the locus (static)
     DevBuf<uint32_t> cnt2;           // [L][32] ... of the cells of the exclusion set (k_t2_minority; kept across iterations, see tally_valid)
     DevBuf<double> tab2;             // [L][48] per pass: log-pmfs of the pairs that occur + expected terms, six 64-byte sectors per locus
-    // tier-2 TILES (deep coverage; kernels_tiled.hip, geo_t2): the cell side of the totals 5..t2_tiles walks a second tile set with
+    // tier-2 TILES (deep coverage; tiled.h, geo_t2): the cell side of the totals 5..t2_tiles walks a second tile set with
     // its own chunk tables in LDS instead of evaluating those entries one by one (k_ovf_cell_wide keeps the other totals)
     int t2_tiles = 0;                // 0, 6 or 8: in use (tiled_build)
     uint32_t t2_nj = 0, t2_groups = 0, t2_cpg = 0;  // chunks of geo_t2::BLU loci, chunk groups, chunks per group
@@ -306,6 +306,7 @@ struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
     bool owns_stream = false;  // the stream was created by the library (a shard of a root ctx)
     bool ingest_all_cells = false;  // begin_ingest: this shard stages ALL cells for now (multi-device text ingest parses once)
     int device = 0;
+    int n_cu = 256;  // the device's compute units (read once, with the device): persistent grids are sized by it
     hipStream_t stream = nullptr;
     // side stream for the small overflow kernels that run next to the tile kernel (fork/join with events)
     hipStream_t side = nullptr;
@@ -443,7 +444,7 @@ cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const c
 cellector_status dev_exclusive_scan_u64(cellector_ctx *c, uint64_t *data, uint64_t n, uint64_t *total_out_host);
 cellector_status dev_sort_pairs_u32_u64(cellector_ctx *c, uint32_t *keys_in, uint32_t *keys_out,
                                         uint64_t *vals_in, uint64_t *vals_out, uint64_t n, int end_bit);
-// engine v2 (kernels_tiled.hip)
+// engine v2 (kernels_tiled_build.hip, once per ingest; then kernels_tiled.hip)
 cellector_status tiled_build(cellector_ctx *c);
 cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em);
 cellector_status tiled_locus_pass(cellector_ctx *c);

@@ -1,4 +1,5 @@
-// Engine v2: table-driven passes over a tiled 16-bit matrix layout (gfx950, wave64).
+// Engine v2: table-driven passes over a tiled 16-bit matrix layout (gfx950, wave64).  This file: what an iteration runs;
+// kernels_tiled_build.hip: tiled_build, which makes the layout once per ingest; tiled.h: what the two share.
 //
 // Observation: under one (alpha_l, beta_l) the log-pmf of an entry depends only on (alt, ref), and vartrix counts
 // are tiny (n = alt+ref <= 4 for ~99 % of entries).  So per EM iteration and locus we tabulate the 14 log-pmfs of
@@ -25,53 +26,13 @@
 //               24/32-bit entries (cell | code) past the exclusion bitmask in LDS (k_locus_stats2); chosen on the device.
 //   overflow    entries with n == 0 or n > 4 (~1 %) live in a small CSR/CSC in the v1 packed format; the cell side
 //               evaluates them itself, the locus side from per-locus cumulative-log tables (see below).
-#include <algorithm>
-#include <type_traits>
-
 #include <hip/hip_ext.h>
 
-#include "ctx.h"
-#include "device_math.h"
-
-#define T_K 4           // entries with 1 <= alt+ref <= T_K are "regular": log-pmf and expected term come from tables
-#define T_NCODE 14      // (alt, ref) combinations with 1 <= n <= T_K: K(K+3)/2
-#ifndef T_LROW
-#define T_LROW 18       // table doubles per locus: the T_NCODE log-pmfs, then the T_K expected terms
-#endif
-#ifndef T_BL
-#define T_BL 640        // locus slots per chunk (the table is T_BL * T_LROW * 8 B = 90 KB of LDS); the last slot is all zeros
-#endif
-#define T_BLU (T_BL - 1)  // loci per chunk
-#define T_BC 1024       // cells per block == threads per workgroup
-#define T_THREADS 1024
-static_assert(T_BC == T_ROWS_PER_TILE, "cellector_engine_info derives the lookup count from this");
-#define T_SB_MAX 4      // cell blocks per workgroup sharing one staged table (2 or 4: chosen per launch)
-#define T_GROUPS_MAX 64 // upper bound of the chunk groups of a launch
-#define T_GROUPS 8      // chunk groups beyond this many are charged for their partial sums (tiled_build's cost model)
-#define T_NE 15         // entries per cell of a slice held in registers (two 16-byte loads); longer slices: slow path
-// A u16 entry = n-1 << 14 | locus slot << 4 | code: log-pmf at table[slot * T_LROW + code], expected term at
-// table[slot * T_LROW + T_NCODE + (n-1)].
-#define T_NULL ((uint16_t)(T_BLU << 4))  // padding entry: code 0, n-1 = 0 of the zero slot
-// A slice in `tiles` is 64 rows of K+1 u16 (K odd): row i = [cell (0..1023) that lane i works for, K entries of that cell,
-// padded with T_NULL].  Tile header (fixed stride, in u16 units): 16 slices x {u64 first u16 of the slice in `tiles`,
-// u32 K, u32 pad}.
-#define T_HDR 128
-#define TAB_ELEMS ((uint64_t)T_LROW * T_BL)  // table doubles per chunk
+#include "tiled.h"
 
 // code = n(n+1)/2 - 1 + ref:  n=1: (1,0)(0,1)  n=2: (2,0)(1,1)(0,2)  n=3: (3,0)..(0,3)  n=4: (4,0)..(0,4)
 __device__ __constant__ uint8_t T_A_OF[T_NCODE] = {1, 0, 2, 1, 0, 3, 2, 1, 0, 4, 3, 2, 1, 0};
 __device__ __constant__ uint8_t T_R_OF[T_NCODE] = {0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4};
-
-__device__ __forceinline__ bool ent_regular(uint64_t e)
-{
-    const uint32_t n = ENT_ALT(e) + ENT_REF(e);
-    return n >= 1u && n <= (uint32_t)T_K;
-}
-__device__ __forceinline__ uint32_t ent_code(uint64_t e)
-{
-    const uint32_t r = ENT_REF(e), n = ENT_ALT(e) + r;
-    return n * (n + 1u) / 2u - 1u + r;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // tables, laid out [chunk][locus slot][18] so that a chunk is one contiguous block the tile kernel copies straight into
@@ -91,7 +52,6 @@ struct ab_src_t {
 };
 // Six waves per 64 loci, each with its share of a locus' 18 values (about equal arithmetic): one thread per locus left
 // three waves per SIMD, too few to hide the dependent divisions and logs (75 us at 200k loci).
-#define TB_PARTS 6
 template <bool PAIRS>
 __global__ __launch_bounds__(64 * TB_PARTS) void k_build_tables(uint64_t L, uint32_t nj, const double2 *__restrict__ ab,
                                                                 const double *__restrict__ lf, double *__restrict__ tab,
@@ -164,23 +124,6 @@ __global__ __launch_bounds__(64 * TB_PARTS) void k_build_tables(uint64_t L, uint
 #else
 #define TILE_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #endif
-
-// Table / entry geometry of a tile set.  geo_reg: the regular entries (totals 1..T_K): 18 doubles per locus, u16 entry =
-// n-1 << 14 | slot << 4 | code.  geo_t2<NMAX>: the tier-2 tiles of a deep-coverage matrix (totals 5..NMAX, tiled_build):
-// NMAX = 8: 30 log-pmfs + 4 expected terms per locus, 338 loci per chunk, entry = n-5 << 14 | slot << 5 | pair;
-// NMAX = 6: 13 + 2 doubles per locus, 767 loci per chunk, entry = n-5 << 14 | slot << 4 | pair.
-struct geo_reg {
-    static constexpr uint32_t LROW = T_LROW, BL = T_BL, NCODE = T_NCODE, SHIFT = 4, SMASK = 1023u, CMASK = 15u;
-    static constexpr uint32_t BLU = BL - 1, NLO = 1, NHI = T_K;  // loci per chunk (the last slot is all zeros); totals covered
-};
-template <int NMAX>
-struct geo_t2 {
-    static_assert(NMAX == 6 || NMAX == 8, "tier-2 tile geometries");
-    static constexpr uint32_t NCODE = NMAX == 8 ? 30 : 13, NE = NMAX - 4, LROW = NCODE + NE;
-    static constexpr uint32_t BL = NMAX == 8 ? 339 : 768, SHIFT = NMAX == 8 ? 5 : 4, SMASK = NMAX == 8 ? 511u : 1023u,
-                              CMASK = NMAX == 8 ? 31u : 15u;
-    static constexpr uint32_t BLU = BL - 1, NLO = 5, NHI = NMAX;
-};
 
 struct __attribute__((packed, aligned(4))) tile_u4 { uint32_t x, y, z, w; };  // 16-byte load at a 4-byte aligned address
 
@@ -491,32 +434,12 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
 //               the locus (the lanes of a locus share its table row).  Only the EM pass needs the tables, and only at the
 //               locus finalize: the table kernel follows the cell side on the side stream.
 // ---------------------------------------------------------------------------------------------------------
-#define LF_LANES 16  // lanes that share a locus (k_locus_finalize) or a row (k_ovf_cell_wide)
 template <typename T>
 __device__ __forceinline__ T group16_sum(T v)
 {
 #pragma unroll
     for (int m = LF_LANES / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, LF_LANES);
     return v;
-}
-#define OV_NT 18  // cumulative tables cover counts 0..17; larger counts take the generic device_math path
-#define OV_NE 17  // expected terms E(n) tabulated for n = 4..17
-#define OV_FAST_N DM_CHUNK  // the cell side's fast kernel takes totals up to this (99 % of the overflow entries)
-
-// tier 2 (see k_t2_tables below)
-#define T2_NMIN 5u
-#define T2_NMAX 8u
-#define T2_NCODE 30    // (alt, ref) pairs with 5 <= alt+ref <= 8; code = n(n+1)/2 - 15 + ref
-#define T2_CSTRIDE 32  // u32 counters per locus (hist_all2, cnt2)
-#define T2_ROW 48      // table doubles per locus
-static_assert(T2_NMAX == (unsigned)OV_FAST_N, "the tier lists take the totals above tier 2");
-__device__ __forceinline__ bool t2_total(uint32_t n) { return n - T2_NMIN <= T2_NMAX - T2_NMIN; }
-__device__ __forceinline__ uint32_t t2_code(uint32_t n, uint32_t r) { return n * (n + 1u) / 2u - 15u + r; }
-// position of the pair's log-pmf in the locus' table row; its sector's first double is E(n)
-__device__ __forceinline__ uint32_t t2_pos(uint32_t n, uint32_t r)
-{
-    const uint32_t hi = r >= 7u ? 1u : 0u;
-    return ((n - T2_NMIN) + (n == 8u ? 1u : 0u) + hi) * 8u + 1u + (hi ? r - 7u : r);
 }
 
 // rare cases kept out of line so that the common path stays small
@@ -553,9 +476,6 @@ __device__ __forceinline__ double ov_expected_rec(double alpha, double beta, uin
 // [64..] E(n) for n = 4..OV_NE.  Two dense kernels (a fused one left most lanes of a wave idle while a few ran the long
 // loops): k_ovf_tables = one thread per (locus, family A / B / AB) running the 17 logs and their prefix sums;
 // k_ovf_tables_e = one thread per (locus, n) for the totals n that occur among the locus' overflow entries (nmask: static).
-#define OV_ROW 128
-#define OV_EOFF 64
-#define OV_REC 8  // the cell side's per-locus record: alpha, beta, E(5..8), pad = ONE 64-byte sector per overflow entry
 __global__ __launch_bounds__(256) void k_ovf_tables(uint64_t L, const double2 *__restrict__ ab, const uint32_t *__restrict__ nmask,
                                                     double *__restrict__ otab)
 {
@@ -628,34 +548,6 @@ __global__ __launch_bounds__(256) void k_ovf_values(uint64_t n_ovf, const uint32
     lp_out[i] = lp;
 }
 
-// locus of every overflow entry (by-locus order): wave per locus
-__global__ __launch_bounds__(256) void k_ovf_locus_ids(uint64_t L, const uint64_t *__restrict__ ovc_ptr, uint32_t *__restrict__ ovc_locus)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t l = wave0; l < L; l += nwaves)
-        for (uint64_t i = ovc_ptr[l] + lane; i < ovc_ptr[l + 1]; i += 64) ovc_locus[i] = (uint32_t)l;
-}
-
-// nmask[l]: bit (n - 4) set iff an overflow entry of locus l has alt+ref == n, 4 <= n <= OV_NE (static)
-__global__ __launch_bounds__(256) void k_ovf_nmask(uint64_t L, const uint64_t *__restrict__ ovc_ptr,
-                                                   const uint64_t *__restrict__ ovc_ent, uint32_t *__restrict__ nmask)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t l = wave0; l < L; l += nwaves) {
-        uint32_t m = 0;
-        for (uint64_t i = ovc_ptr[l] + lane; i < ovc_ptr[l + 1]; i += 64) {
-            const uint64_t en = ovc_ent[i];
-            const uint32_t n = ENT_ALT(en) + ENT_REF(en);
-            if (n >= 4u && n <= (uint32_t)OV_NE) m |= 1u << (n - 4u);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m |= (uint32_t)__shfl_xor((int)m, off, 64);
-        if (lane == 0) nmask[l] = m;
-    }
-}
-
 // cell side of the overflow entries: a thread per cell row evaluates them itself from (alpha, beta) of their loci (a 16-byte
 // gather out of a table of L x 16 B that stays in L2) — one log of a ratio of short products per entry — in ascending-locus
 // order (sequential: deterministic), and takes the expected terms from the compact E table.  The row's 8-byte entries are
@@ -669,7 +561,6 @@ __global__ __launch_bounds__(256) void k_ovf_nmask(uint64_t L, const uint64_t *_
 // The rows' entries come from a 64-row ELLPACK copy (ovf_ell: entry k of the 64 rows of a group side by side, padded with
 // all-ones to the group's longest row): a wave's loads are coalesced and every line is used once.  Reading the CSR row by
 // row, a lane per row, re-fetched each row's 128-byte line for every one of its entries (measured 2.1 GB for 0.13 GB).
-#define OVF_PAD (~0ull)
 // PACKED (a big shard's EM pass): alpha, beta and the expected terms out of ONE 64-byte record per locus (k_ovf_tables_e).
 // Gathered from two tables an entry fetches two sectors — 2.0 GB per pass at cfg4 on the fabric the tile kernel streams
 // through, 1.0 GB this way.  The variant needs 64 VGPRs, i.e. one wave per SIMD beside the tile kernel: all a big shard's
@@ -902,44 +793,6 @@ __global__ __launch_bounds__(256) void k_t2_tile_add(uint64_t n_rows, uint32_t g
     if (EXPECTED) o_ell[row] += e;
 }
 
-// the two lists, from the static pair histogram: a thread per locus.  COUNT: pairs / sectors of the locus; FILL: at the offsets
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_t2_lists(uint64_t L, const uint32_t *__restrict__ hist_all2, uint64_t *__restrict__ np,
-                                                  uint64_t *__restrict__ ns, uint32_t *__restrict__ plist, uint32_t *__restrict__ slist,
-                                                  uint32_t *__restrict__ pmask /*FILL: bit c2 = the pair occurs at the locus*/)
-{
-    const uint64_t l = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (l >= L) return;
-    uint64_t kp = FILL ? np[l] : 0, ks = FILL ? ns[l] : 0;
-    uint32_t secs = 0, pm = 0;
-    for (uint32_t c2 = 0; c2 < (uint32_t)T2_NCODE; c2++) {
-        if (hist_all2[l * T2_CSTRIDE + c2] == 0u) continue;
-        const uint32_t n = 5u + (c2 >= 6u) + (c2 >= 13u) + (c2 >= 21u), r = c2 - t2_code(n, 0u);
-        secs |= 1u << (t2_pos(n, r) >> 3);
-        pm |= 1u << c2;
-        if (FILL) plist[kp] = (uint32_t)(l << 5) | c2;
-        kp++;
-    }
-    for (uint32_t sec = 0; sec < 6u; sec++) {
-        if (!((secs >> sec) & 1u)) continue;
-        if (FILL) slist[ks] = (uint32_t)(l << 3) | sec;
-        ks++;
-    }
-    if (!FILL) { np[l] = kp; ns[l] = ks; }
-    else pmask[l] = pm;
-}
-
-// static: how often every tier-2 pair occurs at every locus (all cells of the shard); a thread per overflow entry (by-locus order)
-__global__ __launch_bounds__(256) void k_t2_hist(uint64_t n_ovf, const uint32_t *__restrict__ ovc_locus, const uint64_t *__restrict__ ovc_ent,
-                                                 uint32_t *__restrict__ hist_all2)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_ovf) return;
-    const uint64_t en = ovc_ent[i];
-    const uint32_t r = ENT_REF(en), n = ENT_ALT(en) + r;
-    if (t2_total(n)) atomicAdd(&hist_all2[(uint64_t)ovc_locus[i] * T2_CSTRIDE + t2_code(n, r)], 1u);
-}
-
 // cell side: a thread per cell row of the 64-row ELLPACK copy (coalesced entry loads), four entries' lookups in flight;
 // sums in the row's order (ascending locus): deterministic.  Entries of other totals (0, above 8) are skipped.
 // One-wave blocks that stride over the 64-row groups: the launch's grid size sets how many gathers are in flight chip-wide.
@@ -1026,64 +879,8 @@ __global__ __launch_bounds__(256) void k_ovx_values(uint64_t n_ovx, const uint32
     lp_out[i] = lp;
 }
 
-// 64-row ELLPACK copy of the overflow CSR.  COUNT: slots of group g = 64 x its longest row; FILL: lane = row & 63 writes
-// its entries at ell_ptr[g] + k * 64 + lane and pads.  One wave per group.
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_ovf_ell_build(uint64_t n_rows, const uint64_t *__restrict__ ovf_ptr,
-                                                       const uint64_t *__restrict__ ovf_ent, uint64_t *__restrict__ ell_ptr,
-                                                       uint64_t *__restrict__ ell)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t grp = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const uint64_t n_grp = (n_rows + 63) >> 6;
-    if (grp >= n_grp) return;
-    const uint64_t row = grp * 64 + lane;
-    uint64_t beg = 0, len = 0;
-    if (row < n_rows) { beg = ovf_ptr[row]; len = ovf_ptr[row + 1] - beg; }
-    uint64_t kmax = len;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kmax = max(kmax, (uint64_t)__shfl_xor((long long)kmax, off, 64));
-    if (!FILL) {
-        if (lane == 0) ell_ptr[grp] = kmax * 64;
-        return;
-    }
-    const uint64_t base = ell_ptr[grp] + lane;
-    for (uint64_t k = 0; k < kmax; k++) ell[base + k * 64] = k < len ? ovf_ent[beg + k] : OVF_PAD;
-}
-
-// The overflow entries the fast kernel leaves out, as two small lists in row order (static): tier 0 = totals 9..OV_NE (longer
-// products; expected term still tabulated), tier 1 = totals above OV_NE (generic paths).  COUNT: entries per row and tier;
-// FILL: (row, entry) pairs at the row's offset.  A thread per row.
-__device__ __forceinline__ int ovf_tier(uint64_t en)
-{
-    const uint32_t n = ENT_ALT(en) + ENT_REF(en);
-    return n <= (uint32_t)OV_FAST_N ? -1 : (n <= (uint32_t)OV_NE ? 0 : 1);
-}
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_ovf_tier_lists(uint64_t n_rows, const uint64_t *__restrict__ ovf_ptr,
-                                                        const uint64_t *__restrict__ ovf_ent,
-                                                        uint64_t *__restrict__ cnt0 /*count: out; fill: offsets*/,
-                                                        uint64_t *__restrict__ cnt1, uint32_t *__restrict__ row0,
-                                                        uint64_t *__restrict__ ent0, uint32_t *__restrict__ row1,
-                                                        uint64_t *__restrict__ ent1)
-{
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n_rows) return;
-    uint64_t k0 = FILL ? cnt0[row] : 0, k1 = FILL ? cnt1[row] : 0;
-    for (uint64_t i = ovf_ptr[row], end = ovf_ptr[row + 1]; i < end; i++) {
-        const uint64_t en = ovf_ent[i];
-        const int t = ovf_tier(en);
-        if (t == 0) {
-            if (FILL) { row0[k0] = (uint32_t)row; ent0[k0] = en; }
-            k0++;
-        } else if (t == 1) {
-            if (FILL) { row1[k1] = (uint32_t)row; ent1[k1] = en; }
-            k1++;
-        }
-    }
-    if (!FILL) { cnt0[row] = k0; cnt1[row] = k1; }
-}
-// Their log-pmfs and expected terms, added to the rows' sums: a thread per listed entry; the thread of a row's FIRST listed
+// The tier lists (k_ovf_tier_lists: the overflow entries the fast kernel leaves out, in row order; tier 0 = totals 9..OV_NE, tier 1 =
+// above).  Their log-pmfs and expected terms, added to the rows' sums: a thread per listed entry; the thread of a row's FIRST listed
 // entry walks the row's run (entries of a row are adjacent, in ascending-locus order: deterministic) and updates the row.
 // GENERIC = false (tier 0): call-free and light enough to run beside the tile kernel; true (tier 1): dm_* generic paths.
 template <bool EXPECTED, bool GENERIC>
@@ -1237,34 +1034,7 @@ __global__ __launch_bounds__(256) void k_cell_finalize(uint64_t n_rows, uint32_t
 // locus pass over the compact CSC.  Two entry widths: 24 bits (cell 20 | code 4; four entries = three dwords) when
 // the shard has at most 2^20 cells, else 32 bits (cell 28 | code 4).  The pass is a pure HBM stream, so bytes matter.
 // ---------------------------------------------------------------------------------------------------------
-template <int EB>
-__device__ __forceinline__ void c4_read1(const uint32_t *__restrict__ base, uint64_t i, uint32_t *cell, uint32_t *code)
-{
-    if (EB == 32) {
-        const uint32_t x = base[i];
-        *cell = x & 0x0fffffffu;
-        *code = x >> 28;
-    } else {
-        const uint8_t *b = reinterpret_cast<const uint8_t *>(base) + 3 * i;
-        const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
-        *cell = v & 0xfffffu;
-        *code = v >> 20;
-    }
-}
-template <int EB>
-__device__ __forceinline__ void c4_write1(uint32_t *__restrict__ base, uint64_t i, uint32_t cell, uint32_t code)
-{
-    if (EB == 32) {
-        base[i] = cell | (code << 28);
-    } else {
-        uint8_t *b = reinterpret_cast<uint8_t *>(base) + 3 * i;
-        const uint32_t v = cell | (code << 20);
-        b[0] = (uint8_t)v; b[1] = (uint8_t)(v >> 8); b[2] = (uint8_t)(v >> 16);
-    }
-}
-// Form of the locus pass, decided on the device from this shard's exclusion-set size (see k_minority_hist below)
-#define LM_NUM 1  // minority-driven when n_min / nloc <= LM_NUM / LM_DEN
-#define LM_DEN 8
+// Form of the locus pass, decided on the device from this shard's exclusion-set size (LM_NUM / LM_DEN)
 // (n_sub = partial planes of the minority-driven form; sub_cap = cells of a subset, i.e. what its 16-bit LDS counters hold: a
 // cell adds to one counter as many times as it has entries at one locus — a file may list a (locus, cell) pair any number of
 // times, every line being an entry — so a subset takes at most 65535 / (the most entries a cell of this matrix has at one
@@ -1453,74 +1223,9 @@ __global__ __launch_bounds__(LS_THREADS) void k_locus_stats2(uint64_t L, uint32_
 // bit-identical to the streamed form.  Cost: the excluded cells' entries instead of all of them.  The form is chosen
 // on the device from this shard's exclusion-set size (no host round trip); the kernels of the other form return at once.
 // ---------------------------------------------------------------------------------------------------------
-// A (cell, range) segment is a short run inside a long row and memory comes in 128-byte lines, so short segments waste
-// most of what they fetch (measured at 1024 loci per range: 80-byte segments, 2 GB fetched for 0.8 GB of entries, the
-// kernel at the HBM rate).  Hence wide ranges, with 16-bit counters so that the histogram still fits in LDS.
-#define LR_LOCI 4096     // loci per range: the LDS histogram is 14 codes x LR_LOCI x u16 = 112 KB
-#define LR_SUB_MAX 16    // at most this many subsets of the exclusion set (partial planes); chosen per matrix
-#define LR_THREADS 1024  // one workgroup per CU, 128 VGPRs: 16 entry loads per lane stay in flight
-#define LR_GROUP 64      // lanes per (cell, range) segment: ~41 entries at 1 % density (a tail loop would serialise)
-#define LR_ROW (LR_LOCI + 2)  // u16 counters per code row (even: a row starts on a word)
-
-// compact by-cell entries for k_minority_ranges: locus | code << 28 (code 15: an overflow entry, not counted there) —
-// half the bytes of the packed CSR entry, and that kernel runs at the memory rate
-__global__ __launch_bounds__(256) void k_cell_compact(uint64_t nnz, const uint64_t *__restrict__ csr_ent, uint16_t *__restrict__ c4r)
-{
-    static_assert(LR_LOCI == 4096, "12 bits of locus inside its range + 4 bits of code");
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nnz) return;
-    const uint64_t e = csr_ent[i];
-    c4r[i] = (uint16_t)((ENT_IDX(e) % LR_LOCI) | ((ent_regular(e) ? ent_code(e) : 15u) << 12));
-}
-
-// roff[cell][r] = number of the row's entries with locus < r * LR_LOCI, r = 0..R (row sorted by locus).  Wave per row.
-__global__ __launch_bounds__(256) void k_range_offsets(uint64_t n_rows, uint32_t R, uint32_t width,
-                                                       const uint64_t *__restrict__ csr_ptr,
-                                                       const uint64_t *__restrict__ csr_ent, uint32_t *__restrict__ roff)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = wave0; row < n_rows; row += nwaves) {
-        const uint64_t beg = csr_ptr[row], end = csr_ptr[row + 1];
-        uint32_t *o = roff + row * (R + 1);
-        // position i (0..len): ranges above that of entry i-1 up to that of entry i start at i (entry -1: range -1,
-        // entry len: range R)
-        for (uint64_t i0 = beg; i0 <= end; i0 += 64) {
-            const uint64_t i = i0 + lane;
-            if (i > end) continue;
-            const int r_prev = i > beg ? (int)(ENT_IDX(csr_ent[i - 1]) / width) : -1;
-            const int r_here = i < end ? (int)(ENT_IDX(csr_ent[i]) / width) : (int)R;
-            for (int r = r_prev + 1; r <= r_here; r++) o[r] = (uint32_t)(i - beg);
-        }
-    }
-}
-
-// The most entries any cell has at ONE locus (1 unless the file repeats a (locus, cell) pair): rows are sorted by locus, so
-// the entries of a pair are a run; the lane at a run's first entry measures it.  Wave per row; out: one u32, zeroed.
-__global__ __launch_bounds__(256) void k_max_pair_entries(uint64_t n_rows, const uint64_t *__restrict__ csr_ptr,
-                                                          const uint64_t *__restrict__ csr_ent, uint32_t *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    uint32_t best = 1;
-    for (uint64_t row = wave0; row < n_rows; row += nwaves) {
-        const uint64_t beg = csr_ptr[row], end = csr_ptr[row + 1];
-        for (uint64_t i = beg + 1 + lane; i < end; i += 64) {
-            const uint64_t l = ENT_IDX(csr_ent[i]);
-            if (ENT_IDX(csr_ent[i - 1]) != l) continue;               // not repeated (nearly always)
-            if (i - 1 > beg && ENT_IDX(csr_ent[i - 2]) == l) continue;  // inside a run: its second entry measures it
-            uint32_t run = 2;
-            for (uint64_t k = i + 1; k < end && ENT_IDX(csr_ent[k]) == l; k++) run++;
-            best = max(best, run);
-        }
-    }
-    if (best > 1) atomicMax(out, best);
-}
-
 // The excluded cells' offset rows, gathered and transposed: mroff[r][k] for the k-th cell of minlist, mbeg[k] = start of its
 // row.  k_minority_ranges then reads its range's offsets as contiguous runs instead of one 64-byte line per (cell, range)
 // out of the big per-cell table (measured: those line fetches were a third of that kernel's traffic).
-#define LT_CELLS 64
 __global__ __launch_bounds__(256) void k_minority_offsets(int locus_mode, int valid, uint64_t nloc, uint32_t n_sub, uint32_t sub_cap, uint32_t R,
                                                           uint64_t mstride, const uint32_t *__restrict__ tc,
                                                           const uint32_t *__restrict__ minlist, const uint32_t *__restrict__ chg,
@@ -1878,536 +1583,45 @@ __global__ __launch_bounds__(256) void k_posterior_finalize(uint64_t n_rows, con
     if (sdbl) sdbl[row] = s_dbl;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// build: tiles + overflow CSR from the by-cell CSR; compact CSC + overflow CSC + per-locus code histogram
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t row_lower_bound(const uint64_t *__restrict__ ent, uint64_t lo, uint64_t hi, uint32_t locus)
-{
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (ENT_IDX(ent[mid]) < locus) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// One 1024-thread block per tile, thread = cell of the block.  The cells are ordered by their number of regular entries
-// in this chunk (stable counting sort: deterministic layout), every 64 of them form a slice of 64 rows [cell, K entries]
-// with K = the slice's longest cell rounded up to odd.  FILL = false: tile size; FILL = true: write slices + header.
-#define TB_BINS 64  // entry counts >= TB_BINS-1 share the last bin (they sort to the end, in cell order)
-// which entries a tile set takes, and their 16-bit form inside chunk j
-template <class G>
-__device__ __forceinline__ bool geo_take(uint64_t e)
-{
-    const uint32_t n = ENT_ALT(e) + ENT_REF(e);
-    return n - G::NLO <= G::NHI - G::NLO;
-}
-template <class G>
-__device__ __forceinline__ uint16_t geo_encode(uint64_t e, uint32_t j)
-{
-    const uint32_t r = ENT_REF(e), n = ENT_ALT(e) + r;
-    const uint32_t code = G::NLO == 1 ? ent_code(e) : t2_code(n, r);
-    return (uint16_t)(((n - G::NLO) << 14) | ((ENT_IDX(e) - j * G::BLU) << G::SHIFT) | code);
-}
-template <bool FILL, class G = geo_reg>
-__global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj, uint64_t tile0,
-                                                     const uint64_t *__restrict__ csr_ptr,
-                                                     const uint64_t *__restrict__ csr_ent,
-                                                     uint64_t *__restrict__ tile_elems /*count pass: out; fill: tile_ptr*/,
-                                                     uint16_t *__restrict__ tiles, uint16_t *__restrict__ thdr,
-                                                     const uint32_t *__restrict__ toff /*[row][nj + 1] or null*/)
-{
-    __shared__ uint32_t s_cnt[T_BC / 64][TB_BINS];  // cells per (source wave, bin)
-    __shared__ uint32_t s_base[TB_BINS];            // first rank of a bin
-    __shared__ uint32_t s_kmax[T_BC / 64];          // longest cell of a slice
-    __shared__ uint32_t s_sbase[T_BC / 64 + 1];     // first entry of a slice inside the tile
-    const uint64_t t = tile0 + blockIdx.x;
-    const uint32_t b = (uint32_t)(t / nj), j = (uint32_t)(t % nj);
-    const uint32_t cl = threadIdx.x, lane = cl & 63, wv = cl >> 6;
-    const uint64_t row = (uint64_t)b * T_BC + cl;
-    for (uint32_t i = cl; i < (T_BC / 64) * TB_BINS; i += T_BC) (&s_cnt[0][0])[i] = 0;
-    if (cl < T_BC / 64) s_kmax[cl] = 0;
-    uint64_t lo = 0, hi = 0;
-    uint32_t len = 0;
-    if (row < nloc) {
-        const uint64_t beg = csr_ptr[row], end = csr_ptr[row + 1];
-        if (toff) {  // where the row's entries of every chunk start (k_range_offsets): two reads instead of two searches
-            lo = beg + toff[row * (nj + 1) + j];
-            hi = beg + toff[row * (nj + 1) + j + 1];
-        } else {
-            lo = row_lower_bound(csr_ent, beg, end, j * G::BLU);
-            hi = row_lower_bound(csr_ent, lo, end, (j + 1u) * G::BLU);
-        }
-        for (uint64_t i = lo; i < hi; i++) len += geo_take<G>(csr_ent[i]) ? 1u : 0u;
-    }
-    __syncthreads();
-    // stable counting sort by bin = min(len, TB_BINS-1): rank inside (wave, bin) from ballots
-    const uint32_t bin = min(len, (uint32_t)TB_BINS - 1u);
-    uint32_t within = 0;
-    {
-        unsigned long long todo = ~0ull;  // lanes whose bin has not been handled yet
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            const uint32_t v = (uint32_t)__shfl((int)bin, src, 64);
-            const unsigned long long m = __ballot(bin == v);
-            if (bin == v) within = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if ((int)lane == src) s_cnt[wv][v] = (uint32_t)__popcll(m);
-            todo &= ~m;
-        }
-    }
-    __syncthreads();
-    if (cl < TB_BINS) {  // exclusive prefix over bins of the bin totals
-        uint32_t tot = 0;
-        for (int w = 0; w < T_BC / 64; w++) tot += s_cnt[w][cl];
-        uint32_t inc = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if ((int)cl >= off) inc += o;
-        }
-        s_base[cl] = inc - tot;
-    }
-    __syncthreads();
-    uint32_t rank = s_base[bin] + within;
-    for (uint32_t w = 0; w < wv; w++) rank += s_cnt[w][bin];
-    const uint32_t dw = rank >> 6, dl = rank & 63;  // destination slice and lane
-    atomicMax(&s_kmax[dw], len);
-    __syncthreads();
-    if (cl == 0) {
-        uint32_t acc = 0;
-        for (int w = 0; w < T_BC / 64; w++) {
-            s_sbase[w] = acc;
-            acc += 64u * ((s_kmax[w] | 1u) + 1u);
-        }
-        s_sbase[T_BC / 64] = acc;
-    }
-    __syncthreads();
-    if (!FILL) {
-        if (cl == 0) tile_elems[t] = (uint64_t)s_sbase[T_BC / 64];  // a multiple of 128 u16
-        return;
-    }
-    const uint64_t tbase = tile_elems[t];
-    uint16_t *hp = thdr + t * T_HDR;
-    if (cl < T_BC / 64) {
-        uint32_t *hd = reinterpret_cast<uint32_t *>(hp) + 4 * cl;
-        const uint64_t first = tbase + s_sbase[cl];
-        hd[0] = (uint32_t)first;
-        hd[1] = (uint32_t)(first >> 32);
-        hd[2] = s_kmax[cl] | 1u;  // K: padded entries per cell of the slice (odd: a row is K + 1 u16)
-        hd[3] = s_kmax[cl] == 0u;  // no row of the slice has an entry (the nearly empty tier-2 tiles of a deep matrix: most slices)
-    }
-    const uint32_t K = s_kmax[dw] | 1u;
-    uint16_t *dst = tiles + tbase + s_sbase[dw] + dl * (K + 1u);  // this cell's row
-    dst[0] = (uint16_t)cl;
-    uint32_t k = 0;
-    for (uint64_t i = lo; i < hi; i++) {
-        const uint64_t e = csr_ent[i];
-        if (geo_take<G>(e)) dst[1 + k++] = geo_encode<G>(e, j);
-    }
-    for (; k < K; k++) dst[1 + k] = (uint16_t)(G::BLU << G::SHIFT);  // padding: the chunk's all-zero slot
-}
-
-// Bank-aware order of the entries inside the rows of one slice (option "bank_order"; a wave per slice, lane = row, the slice's rows
-// in LDS).  The tile kernel's lookup step k reads, for the 32 lanes of a half-wave, the log-pmf at slot * 18 + code and the
-// expected term at slot * 18 + 14 + (n - 1): two 8-byte LDS reads per lane, served at one cycle per DISTINCT address on the busiest
-// of the 32 bank pairs.  In file order the banks are random — 3.3 cycles per step and half-wave instead of 1 — and those conflicts
-// are 42 % of the kernel's time (SQ_LDS_BANK_CONFLICT).  A row's sum does not care about the order of its entries beyond rounding,
-// so the builder picks it: step by step, every lane whose entry of this step is still open proposes the cheapest of its remaining
-// entries given the bank loads of the lanes already placed in the step; of the proposers that share a bank pair the lowest lane is
-// placed, the others propose again; after four rounds whoever is left takes its proposal.  Simulated (tools/probe/bank_sim.py):
-// 3.3 -> 2.4 cycles per step, the same as placing the lanes one after the other.  Deterministic; the order inside a row then depends
-// on the 31 rows that share its half-wave, i.e. on the shard's cell set: per-cell sums of differently sharded runs differ in the
-// last bits (as they already do between different chunk-group counts).
-#define TBO_ROUNDS 4
-__device__ __forceinline__ void tbo_banks(uint32_t e, uint32_t *a, uint32_t *b)
-{
-    const uint32_t base = ((e >> 4) & 1023u) * (uint32_t)T_LROW;
-    *a = (base + (e & 15u)) & 31u;
-    *b = (base + (uint32_t)T_NCODE + (e >> 14)) & 31u;
-}
-// Which lane of its slice a row takes (any permutation of a slice's 64 rows is a valid layout).  The tile kernel adds a row's
-// sums to its cell's accumulator in LDS with one 16-byte read and one 16-byte write per lane: address = cell * 16, served in
-// groups of 16 lanes (read: {0-3,12-15,20-27}, {4-11,16-19,28-31}, and the same + 32) resp. 8 contiguous lanes (write), one cycle
-// per distinct address on a bank quad = cell mod 16.  Rows in count order carry arbitrary cells — 2.7 addresses on the busiest
-// quad of a read group.  Here the slice's rows are ranked by (cell mod 16, lane) and dealt round-robin to the four read groups,
-// the second and fourth group shifted by half a group so that two rows of one class never share a write group either: classes of
-// up to four rows (the average) become conflict-free.  Returns the row count that now belongs to this lane.
-__device__ uint32_t tile_lane_assign(uint16_t *slice /*64 rows of Kw + 1 u16*/, uint32_t Kw, uint32_t lane, uint32_t cnt, uint32_t *scr)
-{
-#define TLA_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-    const uint32_t cls = (uint32_t)slice[lane * (Kw + 1u)] & 15u;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < 16u; c++) {
-        const unsigned long long m = __ballot(cls == c);
-        if (c < cls) t += (uint32_t)__popcll(m);
-        else if (c == cls) t += (uint32_t)__popcll(m & lt);
-    }
-    const uint32_t g = t & 3u, pp = ((t >> 2) + ((g & 1u) ? 8u : 0u)) & 15u;
-    // lane number pp of read group g & 1 (G0 = 0-3, 12-15, 20-27; G1 = 4-11, 16-19, 28-31), upper half for g >= 2
-    const uint32_t l0 = pp < 4u ? pp : (pp < 8u ? pp + 8u : pp + 12u);          // G0: 0..3 | 12..15 | 20..27
-    const uint32_t l1 = pp < 8u ? pp + 4u : (pp < 12u ? pp + 8u : pp + 16u);    // G1: 4..11 | 16..19 | 28..31
-    const uint32_t dst = ((g & 1u) ? l1 : l0) + ((g & 2u) ? 32u : 0u);
-    scr[dst] = lane;
-    scr[64 + dst] = cnt;
-    TLA_SYNC();
-    const uint32_t src = scr[lane], cnt_new = scr[64 + lane];
-    for (uint32_t k = 0; k <= Kw; k++) {  // column by column: all of a column's reads before its writes
-        const uint16_t v = slice[src * (Kw + 1u) + k];
-        TLA_SYNC();
-        slice[lane * (Kw + 1u) + k] = v;
-        TLA_SYNC();
-    }
-    return cnt_new;
-#undef TLA_SYNC
-}
-
-#define TBO_WIN 4  // candidates per lane and round: its next four remaining entries (the whole rest is no better: 2.46 vs 2.50 cycles)
-__device__ void tile_bank_order(uint16_t *row /*this lane's K entries*/, uint32_t K, uint32_t cnt /*real entries: the first cnt*/,
-                                uint32_t lane, uint32_t *scr /*[256]: this wave's bank loads and claims*/)
-{
-    const uint32_t h = lane >> 5;
-    uint32_t *ld_a = scr + h * 64, *ld_b = ld_a + 32, *win_a = scr + 128 + h * 64, *win_b = win_a + 32;
-    // (one wave: its LDS operations complete in program order; the asm statements only keep the compiler from moving them)
-#define TBO_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-    if (K <= 1u) return;  // (wave-uniform) nothing to choose
-    for (uint32_t k = 0; k + 1u < K; k++) {
-        if (__ballot(k + 1u < cnt) == 0ull) break;  // no lane has two entries left to choose from
-        scr[lane] = 0u; scr[64 + lane] = 0u;  // the step's loads
-        // this lane's candidates: its next TBO_WIN remaining entries, and their bank pairs
-        uint32_t e[TBO_WIN], ca[TBO_WIN], cb[TBO_WIN];
-#pragma unroll
-        for (uint32_t u = 0; u < (uint32_t)TBO_WIN; u++) {
-            e[u] = k + u < cnt ? (uint32_t)row[k + u] : 0xffffffffu;
-            tbo_banks(e[u], &ca[u], &cb[u]);
-        }
-        bool open = k < cnt;  // (a row out of real entries keeps its padding entry: one shared address)
-        TBO_SYNC();
-        for (uint32_t rd = 0; rd < (uint32_t)TBO_ROUNDS; rd++) {
-            if (__ballot(open) == 0ull) break;
-            scr[128 + lane] = ~0u; scr[192 + lane] = ~0u;  // the round's claims
-            uint32_t cost[TBO_WIN];
-#pragma unroll
-            for (uint32_t u = 0; u < (uint32_t)TBO_WIN; u++) cost[u] = ld_a[ca[u]] + ld_b[cb[u]];
-            uint32_t best = 0, bc = cost[0];
-#pragma unroll
-            for (uint32_t u = 1; u < (uint32_t)TBO_WIN; u++)
-                if (e[u] != 0xffffffffu && cost[u] < bc) { bc = cost[u]; best = u; }
-            uint32_t ba = ca[0], bb = cb[0];
-#pragma unroll
-            for (uint32_t u = 1; u < (uint32_t)TBO_WIN; u++)
-                if (best == u) { ba = ca[u]; bb = cb[u]; }
-            TBO_SYNC();
-            if (open) {
-                atomicMin(&win_a[ba], lane);
-                atomicMin(&win_b[bb], lane);
-            }
-            TBO_SYNC();
-            if (open && (rd == (uint32_t)TBO_ROUNDS - 1u || (win_a[ba] == lane && win_b[bb] == lane))) {
-                if (best) {  // swap the chosen entry into position k
-                    uint32_t eb = e[0];
-#pragma unroll
-                    for (uint32_t u = 1; u < (uint32_t)TBO_WIN; u++)
-                        if (best == u) eb = e[u];
-                    row[k] = (uint16_t)eb;
-                    row[k + best] = (uint16_t)e[0];
-                }
-                atomicAdd(&ld_a[ba], 1u);
-                atomicAdd(&ld_b[bb], 1u);
-                open = false;
-            }
-            TBO_SYNC();
-        }
-    }
-#undef TBO_SYNC
-}
-
-// The same tiles, built the way the memory system likes (used whenever the per-(cell, chunk) offsets table exists):
-//   * a PERSISTENT workgroup takes whole cell blocks and walks a block's tiles chunk by chunk: a thread's reads of its row move
-//     forward through one cache line after the other (a grid of one workgroup per tile spread the chunks of a block over the
-//     XCDs, and every tile fetched its 1024 row segments afresh: 2.5x the bytes);
-//   * it reads the 2-byte compact by-cell entries (c4r: locus mod 4096 | code << 12, code 15 = not a table entry) instead of the
-//     8-byte packed ones — the chunk is narrower than 4096 loci, so the slot inside it follows from the low 12 bits;
-//   * the slices are assembled in LDS and leave as whole 16-byte stores (rows written two bytes at a time straight to global
-//     memory cost 65x their bytes in partial-line traffic: 0.35 TB for 5.3 GB of tiles at 10^6 cells x 200k loci).
-// Same layout, bit for bit, as k_tile_build.
-#define TB_STAGE (24 * 1024)  // u16 of a tile staged in LDS (48 KB: two workgroups per CU); a bigger tile is written directly (rows of hundreds of entries)
-__device__ __constant__ uint8_t T_NM1_OF[16] = {0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 3, 0, 0};  // alt+ref-1 of a code
-template <bool FILL, bool ORDER = false>
-__global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t nb, uint32_t nj, const uint64_t *__restrict__ csr_ptr,
-                                                      const uint16_t *__restrict__ c4r, const uint32_t *__restrict__ toff /*[row][nj + 1]*/,
-                                                      uint64_t *__restrict__ tile_elems /*count pass: out; fill: tile_ptr*/,
-                                                      uint16_t *__restrict__ tiles, uint16_t *__restrict__ thdr)
-{
-    static_assert(T_BLU < LR_LOCI, "a chunk's loci are told apart by their low 12 bits");
-    __shared__ uint32_t s_cnt[T_BC / 64][TB_BINS];
-    __shared__ uint32_t s_base[TB_BINS];
-    __shared__ uint32_t s_kmax[T_BC / 64];
-    __shared__ uint32_t s_sbase[T_BC / 64 + 1];
-    __shared__ __attribute__((aligned(16))) uint16_t s_tile[FILL ? TB_STAGE : 8];
-    __shared__ uint32_t s_scr[ORDER ? (T_BC / 64) * 256 : 1];  // bank-aware order: a wave's loads and claims
-    __shared__ uint16_t s_rcnt[ORDER ? T_BC : 1];              // ... real entries of every row of the tile, by (slice, lane)
-    const uint32_t cl = threadIdx.x, lane = cl & 63, wv = cl >> 6;
-    for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
-        const uint64_t row = (uint64_t)b * T_BC + cl;
-        const bool have = row < nloc;
-        const uint64_t beg = have ? csr_ptr[row] : 0;
-        const uint32_t *orow = toff + (have ? row : 0) * ((uint64_t)nj + 1);
-        uint32_t o_lo = have ? orow[0] : 0u, o_hi = have ? orow[1] : 0u;
-        for (uint32_t j = 0; j < nj; j++) {
-            const uint64_t t = (uint64_t)b * nj + j;
-            for (uint32_t i = cl; i < (T_BC / 64) * TB_BINS; i += T_BC) (&s_cnt[0][0])[i] = 0;
-            if (cl < T_BC / 64) s_kmax[cl] = 0;
-            const uint32_t o_next = have ? orow[min(j + 2u, nj)] : 0u;  // (the next chunk's end, requested a step ahead)
-            const uint64_t lo = beg + o_lo, hi = beg + o_hi;
-            // the segment's first TB_SEG entries with independent loads (one memory latency instead of one per entry); longer
-            // segments finish in loops
-            constexpr uint32_t TB_SEG = 16;
-            uint32_t seg[TB_SEG];
-            if (FILL) {
-#pragma unroll
-                for (uint32_t u = 0; u < TB_SEG; u++) seg[u] = lo + u < hi ? (uint32_t)c4r[lo + u] : 0xffffu;  // (all ones: code 15)
-            }
-            // The sort key and the row length are the segment's length INCLUDING its few overflow entries (0.8 %): the size pass then
-            // reads the offsets table only, and a row that holds one gets a padding entry in its place — sums unchanged to the bit
-            // (a row's entries stay in locus order, a padding entry adds an exact zero), 0.3 % more tile bytes.
-            const uint32_t len = o_hi - o_lo;
-            __syncthreads();
-            // stable counting sort by bin = min(len, TB_BINS-1): rank inside (wave, bin) from ballots
-            const uint32_t bin = min(len, (uint32_t)TB_BINS - 1u);
-            uint32_t within = 0;
-            {
-                unsigned long long todo = ~0ull;
-                while (todo) {
-                    const int src = __ffsll((long long)todo) - 1;
-                    const uint32_t v = (uint32_t)__shfl((int)bin, src, 64);
-                    const unsigned long long m = __ballot(bin == v);
-                    if (bin == v) within = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                    if ((int)lane == src) s_cnt[wv][v] = (uint32_t)__popcll(m);
-                    todo &= ~m;
-                }
-            }
-            __syncthreads();
-            if (cl < TB_BINS) {
-                uint32_t tot = 0;
-                for (int w = 0; w < T_BC / 64; w++) tot += s_cnt[w][cl];
-                uint32_t inc = tot;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t o = __shfl_up(inc, off, 64);
-                    if ((int)cl >= off) inc += o;
-                }
-                s_base[cl] = inc - tot;
-            }
-            __syncthreads();
-            uint32_t rank = s_base[bin] + within;
-            for (uint32_t w = 0; w < wv; w++) rank += s_cnt[w][bin];
-            const uint32_t dw = rank >> 6, dl = rank & 63;
-            atomicMax(&s_kmax[dw], len);
-            __syncthreads();
-            if (cl == 0) {
-                uint32_t acc = 0;
-                for (int w = 0; w < T_BC / 64; w++) {
-                    s_sbase[w] = acc;
-                    acc += 64u * ((s_kmax[w] | 1u) + 1u);
-                }
-                s_sbase[T_BC / 64] = acc;
-            }
-            __syncthreads();
-            const uint32_t total = s_sbase[T_BC / 64];  // a multiple of 128 u16
-            if (!FILL) {
-                if (cl == 0) tile_elems[t] = (uint64_t)total;
-            } else {
-                const uint64_t tbase = tile_elems[t];
-                if (cl < T_BC / 64) {
-                    uint32_t *hd = reinterpret_cast<uint32_t *>(thdr + t * T_HDR) + 4 * cl;
-                    const uint64_t first = tbase + s_sbase[cl];
-                    hd[0] = (uint32_t)first;
-                    hd[1] = (uint32_t)(first >> 32);
-                    hd[2] = s_kmax[cl] | 1u;
-                    hd[3] = s_kmax[cl] == 0u;
-                }
-                const uint32_t K = s_kmax[dw] | 1u;
-                const bool staged = total <= (uint32_t)TB_STAGE;  // (uniform)
-                uint16_t *dst = (staged ? s_tile : tiles + tbase) + s_sbase[dw] + dl * (K + 1u);
-                dst[0] = (uint16_t)cl;
-                uint32_t k = 0;
-                const uint32_t cbase = (j * (uint32_t)T_BLU) & (LR_LOCI - 1u);
-#define TB_PUT(E)                                                                                                       \
-                do {                                                                                                   \
-                    const uint32_t e__ = (E), code__ = e__ >> 12;                                                      \
-                    if (code__ < (uint32_t)T_NCODE)                                                                    \
-                        dst[1 + k++] = (uint16_t)(((uint32_t)T_NM1_OF[code__] << 14) |                                 \
-                                                  ((((e__ & (LR_LOCI - 1u)) - cbase) & (LR_LOCI - 1u)) << 4) | code__); \
-                } while (0)
-#pragma unroll
-                for (uint32_t u = 0; u < TB_SEG; u++) TB_PUT(seg[u]);
-                for (uint64_t i = lo + TB_SEG; i < hi; i++) TB_PUT((uint32_t)c4r[i]);
-#undef TB_PUT
-                if (ORDER) s_rcnt[rank] = (uint16_t)k;
-                for (; k < K; k++) dst[1 + k] = T_NULL;
-                if (staged) {
-                    __syncthreads();
-                    if (ORDER) {  // wave wv = slice wv, lane = row
-                        const uint32_t Kw = s_kmax[wv] | 1u;
-                        const uint32_t rc = tile_lane_assign(s_tile + s_sbase[wv], Kw, lane, s_rcnt[wv * 64 + lane], s_scr + wv * 256);
-                        tile_bank_order(s_tile + s_sbase[wv] + lane * (Kw + 1u) + 1u, Kw, rc, lane, s_scr + wv * 256);
-                        __syncthreads();
-                    }
-                    uint4 *out = reinterpret_cast<uint4 *>(tiles + tbase);  // (tile starts are multiples of 128 u16)
-                    const uint4 *in = reinterpret_cast<const uint4 *>(s_tile);
-                    for (uint32_t i = cl; i < total / 8u; i += T_BC) out[i] = in[i];
-                }
-            }
-            __syncthreads();  // (the sort's arrays and the staged tile are reused by the next chunk)
-            o_lo = o_hi;
-            o_hi = o_next;
-        }
-    }
-}
-
-// wave per row/column: count entries that are NOT regular (FILL = false) or copy them in order (FILL = true);
-// REST > 0: only those outside the totals 5..REST as well (8: tier 2, i.e. totals 0 and above 8 remain)
-template <bool FILL, int REST = 0>
-__global__ __launch_bounds__(256) void k_ovf_build(uint64_t n_rows, const uint64_t *__restrict__ ptr,
-                                                   const uint64_t *__restrict__ ent, uint64_t *__restrict__ optr,
-                                                   uint64_t *__restrict__ oent)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = wave0; row < n_rows; row += nwaves) {
-        const uint64_t beg = ptr[row], end = ptr[row + 1];
-        uint64_t base = FILL ? optr[row] : 0, cnt = 0;
-        for (uint64_t i0 = beg; i0 < end; i0 += 64) {
-            const uint64_t i = i0 + lane;
-            const uint64_t e = i < end ? ent[i] : 0;
-            const bool ov = i < end && !ent_regular(e) && !(REST && ENT_ALT(e) + ENT_REF(e) - T2_NMIN <= (uint32_t)REST - T2_NMIN);
-            const unsigned long long m = __ballot(ov);
-            if (FILL && ov) oent[base + __popcll(m & ((1ull << lane) - 1ull))] = e;
-            base += __popcll(m);
-            cnt += __popcll(m);
-        }
-        if (!FILL && lane == 0) optr[row] = cnt;
-    }
-}
-
-// wave per locus column: regular entries -> compact u32 (cell | code<<28) in order; per-code histogram
-template <bool FILL, int EB>
-__global__ __launch_bounds__(256) void k_c4_build(uint64_t L, const uint64_t *__restrict__ csc_ptr,
-                                                  const uint64_t *__restrict__ csc_ent, uint64_t *__restrict__ c4_ptr,
-                                                  uint32_t *__restrict__ c4_ent, uint32_t *__restrict__ hist_all)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t l = wave0; l < L; l += nwaves) {
-        const uint64_t beg = csc_ptr[l], end = csc_ptr[l + 1];
-        uint64_t base = FILL ? c4_ptr[l] : 0, cnt = 0;
-        uint32_t myhist = 0;
-        for (uint64_t i0 = beg; i0 < end; i0 += 64) {
-            const uint64_t i = i0 + lane;
-            const uint64_t e = i < end ? csc_ent[i] : 0;
-            const bool reg = i < end && ent_regular(e);
-            const uint32_t code = reg ? ent_code(e) : 0xffu;
-            const unsigned long long m = __ballot(reg);
-            if (FILL) {
-                if (reg) c4_write1<EB>(c4_ent, base + __popcll(m & ((1ull << lane) - 1ull)), ENT_IDX(e), code);
-            } else {
-#pragma unroll
-                for (int k = 0; k < T_NCODE; k++) {
-                    const unsigned long long mk = __ballot(code == (uint32_t)k);
-                    if (lane == k) myhist += (uint32_t)__popcll(mk);
-                }
-            }
-            base += __popcll(m);
-            cnt += __popcll(m);
-        }
-        if (!FILL) {
-            if (lane == 0) c4_ptr[l] = (cnt + 3) & ~3ull;  // whole 16-byte vectors
-            if (lane < T_NCODE) hist_all[l * T_NCODE + lane] = myhist;
-        } else if ((uint64_t)lane < ((4 - (cnt & 3)) & 3)) {
-            c4_write1<EB>(c4_ent, c4_ptr[l] + cnt + lane, EB == 32 ? 0x0fffffffu : 0xfffffu, 15u);  // padding: code 15 = no entry
-        }
-    }
-}
-
 // ===========================================================================================================
-static inline unsigned gcap(uint64_t n, unsigned per_block, unsigned cap = 1u << 20)
+// Launch geometry of a tile pass over nb cell blocks and `groups` chunk groups: sb cell blocks per column (several blocks
+// amortise the table staging; with few blocks, i.e. a small shard, more columns are worth more: sb is halved while the columns
+// x groups keep less than 90 % of the CUs busy; option tile_sb forces it), the columns, and a grid of persistent workgroups:
+// one per CU, an equal number for every chunk group, never more than there are columns.
+struct TileGeo {
+    int sb;
+    uint32_t n_cols;
+    unsigned grid;
+};
+static TileGeo tile_geometry(const cellector_ctx *c, uint32_t nb, uint32_t groups)
 {
-    uint64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
+    int sb = T_SB_MAX;
+    while (sb > 2 && (uint64_t)((nb + sb - 1) / sb) * groups * 10 < (uint64_t)c->n_cu * 9) sb >>= 1;
+    if (c->tile_sb_opt) sb = c->tile_sb_opt;
+    const uint32_t n_cols = (nb + sb - 1) / sb;
+    const uint32_t per_group = std::min(std::max((uint32_t)c->n_cu / groups, 1u), n_cols);
+    return {sb, n_cols, per_group * groups};
 }
-
-// Chunk groups of a tile pass (see tiled_build): the count with the shortest modelled makespan of the persistent workgroups.
-static uint32_t tile_groups_for(const cellector_ctx *c, uint32_t nb, uint32_t nj)
-{
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-    const uint64_t cols = (nb + T_SB_MAX - 1) / T_SB_MAX;
-    uint64_t groups = 1;
-    double best = 1e300;
-    for (uint64_t g = 1; g <= T_GROUPS_MAX && g <= (uint64_t)nj; g++) {
-        uint64_t per = (uint64_t)ncu / g;
-        if (per < 1) per = 1;
-        if (per > cols) per = cols;
-        const uint64_t rounds = (cols + per - 1) / per, chunks = ((uint64_t)nj + g - 1) / g;
-        const double cost = (double)(rounds * (chunks + 3)) * (1.0 + 0.03 * (g > T_GROUPS ? (double)(g - T_GROUPS) / T_GROUPS : 0.0));
-        if (cost < best) { best = cost; groups = g; }
-    }
-    if (c->tile_groups_opt > 0) groups = (uint64_t)c->tile_groups_opt;  // (A/B runs)
-    if (groups > nj) groups = nj;
-    return (uint32_t)groups;
-}
-
-// ---- tier-2 tiles (deep coverage): a second tile set over the overflow CSR's entries with totals 5..G::NHI ----
-// Built with the per-tile builder (one workgroup per tile, two searches per row in the short overflow rows); the rows keep
-// their file order.  A tile holds all 1024 rows of its block, most of them with one padding entry: 4 bytes per row.
+// the tile kernel of geometry class G over one tile set.  t_a, t_b: a timer's events, which ride on the dispatch (no barrier
+// packets around the kernel; regular tiles only)
 template <class G>
-static cellector_status t2_tiles_build(cellector_ctx *c)
+static void launch_tile_ll(cellector_ctx *c, bool expected, const TileGeo &tg, uint32_t nj, uint32_t cpg, uint32_t groups, uint32_t *work,
+                           const uint16_t *thdr, const uint16_t *tiles, const double *tab, double *part_ll, double *part_ell,
+                           hipEvent_t t_a = nullptr, hipEvent_t t_b = nullptr)
 {
-    const uint64_t nloc = c->nloc, L = c->L;
-    c->t2_nj = (uint32_t)((L + G::BLU - 1) / G::BLU);
-    if (c->t2_nj == 0) c->t2_nj = 1;
-    c->t2_groups = tile_groups_for(c, c->t_nb, c->t2_nj);
-    c->t2_cpg = (c->t2_nj + c->t2_groups - 1) / c->t2_groups;
-    c->t2_groups = (c->t2_nj + c->t2_cpg - 1) / c->t2_cpg;
-    const uint64_t nt = (uint64_t)c->t_nb * c->t2_nj, maxg = 1ull << 30;
-    CHK(dev_alloc(c, &c->tile2_ptr, nt + 1));
-    HIPCHK(c, hipMemsetAsync(c->tile2_ptr + nt, 0, 8, c->stream));
-    for (uint64_t t0 = 0; t0 < nt; t0 += maxg) {
-        const uint64_t g = nt - t0 < maxg ? nt - t0 : maxg;
-        hipLaunchKernelGGL((k_tile_build<false, G>), dim3((unsigned)g), dim3(T_BC), 0, c->stream, nloc, c->t2_nj, t0, c->ovf_ptr, c->ovf_ent,
-                           c->tile2_ptr, (uint16_t *)nullptr, (uint16_t *)nullptr, (const uint32_t *)nullptr);
-    }
-    HIPCHK(c, hipGetLastError());
-    uint64_t elems = 0;
-    CHK(dev_exclusive_scan_u64(c, c->tile2_ptr, nt + 1, &elems));
-    CHK(dev_alloc(c, &c->tiles2, elems + 64));  // tail pad: the 16-byte load of the last row runs past its end
-    CHK(dev_alloc(c, &c->thdr2, nt * T_HDR));
-    for (uint64_t t0 = 0; t0 < nt; t0 += maxg) {
-        const uint64_t g = nt - t0 < maxg ? nt - t0 : maxg;
-        hipLaunchKernelGGL((k_tile_build<true, G>), dim3((unsigned)g), dim3(T_BC), 0, c->stream, nloc, c->t2_nj, t0, c->ovf_ptr, c->ovf_ent,
-                           c->tile2_ptr, c->tiles2, c->thdr2, (const uint32_t *)nullptr);
-    }
-    HIPCHK(c, hipGetLastError());
-    const uint64_t tab_elems = (uint64_t)c->t2_nj * G::LROW * G::BL + 4 * T_THREADS;  // tail pad: the partial last table load
-    CHK(dev_alloc(c, &c->tab2c, tab_elems));
-    HIPCHK(c, hipMemsetAsync(c->tab2c, 0, tab_elems * sizeof(double), c->stream));  // (zero slots and the slots beyond L stay zero)
-    CHK(dev_alloc(c, &c->part2, 3ull * 2 * c->t2_groups * c->t_npad));
-    CHK(dev_alloc(c, &c->tile_work2, T_GROUPS_MAX));
-    // what the tiles leave to the per-entry kernel (totals 0 and above G::NHI), as a by-cell CSR of its own: walking the whole
-    // overflow CSR and skipping the tiles' entries kept that kernel's waves as long as before (a wave waits for its slowest lane)
-    CHK(dev_alloc(c, &c->ovr_ptr, nloc + 1));
-    HIPCHK(c, hipMemsetAsync(c->ovr_ptr + nloc, 0, 8, c->stream));
-    hipLaunchKernelGGL((k_ovf_build<false, (int)G::NHI>), dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, c->ovr_ptr,
-                       (uint64_t *)nullptr);
-    CHK(dev_exclusive_scan_u64(c, c->ovr_ptr, nloc + 1, &c->ovr_n));
-    CHK(dev_alloc(c, &c->ovr_ent, c->ovr_n));
-    hipLaunchKernelGGL((k_ovf_build<true, (int)G::NHI>), dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, c->ovr_ptr,
-                       c->ovr_ent);
-    HIPCHK(c, hipGetLastError());
-    return CELLECTOR_OK;
+    with_bool(expected, [&](auto E) {
+        with_bool(tg.sb == 4, [&](auto WIDE) {
+            constexpr int SB = WIDE.value ? 4 : 2;
+            if constexpr (std::is_same<G, geo_reg>::value)
+                if (t_a) {
+                    hipExtLaunchKernelGGL((k_tile_ll<E.value, SB, G>), dim3(tg.grid), dim3(T_THREADS), 0, c->stream, t_a, t_b, 0, c->t_nb, nj, cpg,
+                                          groups, tg.n_cols, work, thdr, tiles, tab, c->t_npad, part_ll, part_ell);
+                    return;
+                }
+            hipLaunchKernelGGL((k_tile_ll<E.value, SB, G>), dim3(tg.grid), dim3(T_THREADS), 0, c->stream, c->t_nb, nj, cpg, groups, tg.n_cols,
+                               work, thdr, tiles, tab, c->t_npad, part_ll, part_ell);
+        });
+    });
 }
 
 // one tier-2 tile pass on the main stream: this pass' chunked tables, then the tile kernel over the second tile set
@@ -2416,33 +1630,14 @@ static cellector_status t2_tiles_pass_g(cellector_ctx *c, const double2 *ab, int
 {
     constexpr uint32_t NE = G::NHI - G::NLO + 1;
     const unsigned gp = gcap(c->L * G::NCODE, 256, 0x7fffffffu), ge = expected ? gcap(c->L * NE, 256, 0x7fffffffu) : 0u;
-    if (expected)
-        hipLaunchKernelGGL((k_t2c_tables<true, G>), dim3(gp + ge), dim3(256), 0, c->stream, c->L, gp, ab, (const double *)c->lf, c->tab2c);
-    else
-        hipLaunchKernelGGL((k_t2c_tables<false, G>), dim3(gp), dim3(256), 0, c->stream, c->L, gp, ab, (const double *)c->lf, c->tab2c);
+    with_bool(expected, [&](auto E) {
+        hipLaunchKernelGGL((k_t2c_tables<E.value, G>), dim3(gp + ge), dim3(256), 0, c->stream, c->L, gp, ab, (const double *)c->lf, c->tab2c);
+    });
     double *part_ll = c->part2 + (uint64_t)set * 2 * c->t2_groups * c->t_npad;
     double *part_ell = part_ll + (uint64_t)c->t2_groups * c->t_npad;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-    int sb = T_SB_MAX;
-    while (sb > 2 && (uint64_t)((c->t_nb + sb - 1) / sb) * c->t2_groups * 10 < (uint64_t)ncu * 9) sb >>= 1;
-    if (c->tile_sb_opt) sb = c->tile_sb_opt;
-    const uint32_t n_cols = (c->t_nb + sb - 1) / sb;
-    uint32_t per_group = (uint32_t)ncu / c->t2_groups;
-    if (per_group < 1) per_group = 1;
-    if (per_group > n_cols) per_group = n_cols;
-    const dim3 grid(per_group * c->t2_groups);
+    const TileGeo tg = tile_geometry(c, c->t_nb, c->t2_groups);
     HIPCHK(c, hipMemsetAsync(c->tile_work2, 0, T_GROUPS_MAX * sizeof(uint32_t), c->stream));
-#define LAUNCH_TILE2(E, S)                                                                                                 \
-    hipLaunchKernelGGL((k_tile_ll<E, S, G>), grid, dim3(T_THREADS), 0, c->stream, c->t_nb, c->t2_nj, c->t2_cpg, c->t2_groups, n_cols, \
-                       c->tile_work2, (const uint16_t *)c->thdr2, (const uint16_t *)c->tiles2, (const double *)c->tab2c, c->t_npad,    \
-                       part_ll, part_ell)
-    if (expected) {
-        if (sb == 4) LAUNCH_TILE2(true, 4); else LAUNCH_TILE2(true, 2);
-    } else {
-        if (sb == 4) LAUNCH_TILE2(false, 4); else LAUNCH_TILE2(false, 2);
-    }
-#undef LAUNCH_TILE2
+    launch_tile_ll<G>(c, expected, tg, c->t2_nj, c->t2_cpg, c->t2_groups, c->tile_work2, c->thdr2, c->tiles2, c->tab2c, part_ll, part_ell);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
 }
@@ -2457,319 +1652,11 @@ static cellector_status t2_tiles_add(cellector_ctx *c, int set, bool expected)
     if (!c->t2_tiles) return CELLECTOR_OK;
     double *part_ll = c->part2 + (uint64_t)set * 2 * c->t2_groups * c->t_npad, *part_ell = part_ll + (uint64_t)c->t2_groups * c->t_npad;
     double *o_ll = c->ovf_sum + (uint64_t)set * 2 * c->nloc, *o_ell = o_ll + c->nloc;
-    const unsigned g = gcap(c->nloc, 256, 0x7fffffffu);
-    if (expected)
-        hipLaunchKernelGGL(k_t2_tile_add<true>, dim3(g), dim3(256), 0, c->stream, c->nloc, c->t2_groups, c->t_npad, part_ll, part_ell, o_ll, o_ell);
-    else
-        hipLaunchKernelGGL(k_t2_tile_add<false>, dim3(g), dim3(256), 0, c->stream, c->nloc, c->t2_groups, c->t_npad, part_ll, part_ell, o_ll, o_ell);
+    with_bool(expected, [&](auto E) {
+        hipLaunchKernelGGL(k_t2_tile_add<E.value>, dim3(gcap(c->nloc, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->nloc, c->t2_groups, c->t_npad,
+                           part_ll, part_ell, o_ll, o_ell);
+    });
     HIPCHK(c, hipGetLastError());
-    return CELLECTOR_OK;
-}
-
-cellector_status tiled_build(cellector_ctx *c)
-{
-    const uint64_t nloc = c->nloc, L = c->L;
-    if (nloc >= (1ull << 28)) return ctx_fail(c, CELLECTOR_EINVAL, "tiled engine: more than 2^28 cells per shard");
-    if (L >= (1ull << 28)) return ctx_fail(c, CELLECTOR_EINVAL, "tiled engine: more than 2^28 loci");
-    c->t_nb = (uint32_t)((nloc + T_BC - 1) / T_BC);
-    c->t_nj = (uint32_t)((L + T_BLU - 1) / T_BLU);
-    if (c->t_nb == 0) c->t_nb = 1;
-    if (c->t_nj == 0) c->t_nj = 1;
-    // Chunk groups.  The tile kernel runs one persistent workgroup per CU, each bound to a group of locus chunks and fetching
-    // columns of T_SB_MAX cell blocks from the group's counter; a cell gets one partial sum per group.  Every workgroup of a
-    // group walks the group's chunks once per column it fetches, so the kernel takes about rounds(g) x (chunks(g) + 3)
-    // chunk-steps with rounds = ceil(columns / workgroups per group) — a column costs its chunks plus a fixed part
-    // (accumulators cleared and written out as partial sums), put at three chunk-steps.  Any count from 1 up is taken, the one
-    // with the shortest makespan wins (ties: fewer groups), charging 3 % per 8 groups beyond 8 for the additional partial
-    // sums (16 bytes more per cell and pass written by the tile kernel and read by the finalize).  Measured (ms per EM
-    // iteration): 10^6 cells x 200k loci (245 columns, 313 chunks): 1 group 2.33, 2: 2.34, 4: 2.36, 7: 2.43, 8: 2.44, 32:
-    // 2.59 — with one group every workgroup does one column over all chunks: no ragged last round, no partial sums to add
-    // up; 200k cells x 100k loci (49 columns, 157 chunks): 5 groups 0.394 (245 workgroups, one round), 8: 0.430 (two rounds,
-    // the second half empty), 2: 0.48, 1: 0.73 (49 CUs busy).  Groups used to be multiples of 8 so that a group's workgroups
-    // shared an XCD's L2 for the table reads (workgroup i runs on XCD i mod 8): the figures above show no such need — the
-    // workgroups of a group walk the chunks in step, a table chunk is fetched once per XCD either way.
-    c->t_groups = tile_groups_for(c, c->t_nb, c->t_nj);
-    c->t_cpg = (c->t_nj + c->t_groups - 1) / c->t_groups;
-    c->t_groups = (c->t_nj + c->t_cpg - 1) / c->t_cpg;
-    c->t_npad = (uint64_t)c->t_nb * T_BC;
-    const uint64_t nt = (uint64_t)c->t_nb * c->t_nj;
-
-    // ---- tiles
-    CHK(dev_alloc(c, &c->tile_ptr, nt + 1));
-    HIPCHK(c, hipMemsetAsync(c->tile_ptr + nt, 0, 8, c->stream));
-    // every (cell, chunk) pair's first entry, once per row: the two builder passes searched each row per tile (two binary
-    // searches of ~11 scattered probes per cell and tile: 1.4 TB through the L2 at 1M x 200k, 0.2 s)
-    DevBuf<uint32_t> toff;  // (stays empty when there is no room for the table: the builder searches)
-    if (nloc && dev_alloc(c, &toff, nloc * ((uint64_t)c->t_nj + 1)) == CELLECTOR_OK)
-        hipLaunchKernelGGL(k_range_offsets, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->t_nj, (uint32_t)T_BLU, c->csr_ptr,
-                           c->csr_ent, toff);
-    // the compact by-cell entries (also the minority-driven locus pass' input): with the offsets table the builder reads these
-    CHK(dev_alloc(c, &c->c4r, c->nnz));
-    if (c->nnz)
-        hipLaunchKernelGGL(k_cell_compact, dim3(gcap(c->nnz, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->nnz, c->csr_ent, c->c4r);
-    int ncu_b = 256;
-    (void)hipDeviceGetAttribute(&ncu_b, hipDeviceAttributeMultiprocessorCount, c->device);
-    const unsigned bgrid = (unsigned)std::min<uint64_t>(c->t_nb, (uint64_t)ncu_b * 8);  // (one block per CU at a time: LDS)
-    const uint64_t maxg = 1ull << 30;
-    if (toff) {
-        hipLaunchKernelGGL(k_tile_build2<false>, dim3(bgrid), dim3(T_BC), 0, c->stream, nloc, c->t_nb, c->t_nj, c->csr_ptr, c->c4r, toff,
-                           c->tile_ptr, (uint16_t *)nullptr, (uint16_t *)nullptr);
-    } else {
-        for (uint64_t t0 = 0; t0 < nt; t0 += maxg) {
-            const uint64_t g = nt - t0 < maxg ? nt - t0 : maxg;
-            hipLaunchKernelGGL(k_tile_build<false>, dim3((unsigned)g), dim3(T_BC), 0, c->stream, nloc, c->t_nj, t0, c->csr_ptr,
-                               c->csr_ent, c->tile_ptr, (uint16_t *)nullptr, (uint16_t *)nullptr, toff);
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    uint64_t elems = 0;
-    CHK(dev_exclusive_scan_u64(c, c->tile_ptr, nt + 1, &elems));
-    CHK(dev_alloc(c, &c->tiles, elems + 64));  // tail pad: the 16-byte load of the last row runs past its end
-    CHK(dev_alloc(c, &c->thdr, nt * T_HDR));
-    c->t_elems = elems;
-    if (toff) {
-        if (c->bank_order)
-            hipLaunchKernelGGL((k_tile_build2<true, true>), dim3(bgrid), dim3(T_BC), 0, c->stream, nloc, c->t_nb, c->t_nj, c->csr_ptr, c->c4r,
-                               toff, c->tile_ptr, c->tiles, c->thdr);
-        else
-            hipLaunchKernelGGL((k_tile_build2<true, false>), dim3(bgrid), dim3(T_BC), 0, c->stream, nloc, c->t_nb, c->t_nj, c->csr_ptr, c->c4r,
-                               toff, c->tile_ptr, c->tiles, c->thdr);
-    } else {
-        for (uint64_t t0 = 0; t0 < nt; t0 += maxg) {
-            const uint64_t g = nt - t0 < maxg ? nt - t0 : maxg;
-            hipLaunchKernelGGL(k_tile_build<true>, dim3((unsigned)g), dim3(T_BC), 0, c->stream, nloc, c->t_nj, t0, c->csr_ptr,
-                               c->csr_ent, c->tile_ptr, c->tiles, c->thdr, toff);
-        }
-    }
-    if (toff) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // (the block goes back to the allocation cache: no kernel may still read it)
-        toff.reset();
-    }
-    HIPCHK(c, hipGetLastError());
-
-    // ---- overflow CSR
-    CHK(dev_alloc(c, &c->ovf_ptr, nloc + 1));
-    HIPCHK(c, hipMemsetAsync(c->ovf_ptr + nloc, 0, 8, c->stream));
-    if (nloc)
-        hipLaunchKernelGGL(k_ovf_build<false>, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->csr_ptr, c->csr_ent,
-                           c->ovf_ptr, (uint64_t *)nullptr);
-    CHK(dev_exclusive_scan_u64(c, c->ovf_ptr, nloc + 1, &c->ovf_n));
-    CHK(dev_alloc(c, &c->ovf_ent, c->ovf_n));
-    if (nloc)
-        hipLaunchKernelGGL(k_ovf_build<true>, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, c->csr_ptr, c->csr_ent,
-                           c->ovf_ptr, c->ovf_ent);
-    HIPCHK(c, hipGetLastError());
-
-    // ---- compact CSC + histogram, overflow CSC
-    uint64_t n4 = 0, novc = 0;
-    CHK(dev_alloc(c, &c->c4_ptr, L + 1));
-    CHK(dev_alloc(c, &c->ovc_ptr, L + 1));
-    CHK(dev_alloc(c, &c->hist_all, L * T_NCODE));
-    HIPCHK(c, hipMemsetAsync(c->c4_ptr + L, 0, 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ovc_ptr + L, 0, 8, c->stream));
-    if (L) {
-        hipLaunchKernelGGL((k_c4_build<false, 32>), dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->csc_ptr, c->csc_ent,
-                           c->c4_ptr, (uint32_t *)nullptr, c->hist_all);
-        hipLaunchKernelGGL(k_ovf_build<false>, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->csc_ptr, c->csc_ent,
-                           c->ovc_ptr, (uint64_t *)nullptr);
-    }
-    HIPCHK(c, hipGetLastError());
-    CHK(dev_exclusive_scan_u64(c, c->c4_ptr, L + 1, &n4));
-    CHK(dev_exclusive_scan_u64(c, c->ovc_ptr, L + 1, &novc));
-    if (novc != c->ovf_n || n4 < c->nnz - novc)
-        return ctx_fail(c, CELLECTOR_EDEVICE, "internal: tiled build entry counts inconsistent (%llu + %llu vs %llu, ovf %llu)",
-                        (unsigned long long)n4, (unsigned long long)novc, (unsigned long long)c->nnz,
-                        (unsigned long long)c->ovf_n);
-    c->c4_bits = (nloc <= (1ull << 20) && c->c4_bits_opt != 32) ? 24 : 32;
-    CHK(dev_alloc(c, &c->c4_ent, c->c4_bits == 32 ? n4 : (n4 * 3 + 3) / 4 + 4));
-    CHK(dev_alloc(c, &c->ovc_ent, novc));
-    if (L) {
-        if (c->c4_bits == 32)
-            hipLaunchKernelGGL((k_c4_build<true, 32>), dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->csc_ptr, c->csc_ent,
-                               c->c4_ptr, c->c4_ent, c->hist_all);
-        else
-            hipLaunchKernelGGL((k_c4_build<true, 24>), dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->csc_ptr, c->csc_ent,
-                               c->c4_ptr, c->c4_ent, c->hist_all);
-        hipLaunchKernelGGL(k_ovf_build<true>, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->csc_ptr, c->csc_ent,
-                           c->ovc_ptr, c->ovc_ent);
-    }
-    HIPCHK(c, hipGetLastError());
-
-    // ---- overflow entries: which paths they take
-    if (c->ovf_n >= (1ull << 32)) return ctx_fail(c, CELLECTOR_EINVAL, "tiled engine: more than 2^32 overflow entries per shard");
-    // deep coverage: more than 3 % of the entries outside the tables (0.8 % with vartrix-like totals 1 + Geometric(0.7),
-    // 13 % with 1 + Geometric(0.4)) — the side-stream arrangement built for "a few entries per row" no longer hides them
-    c->ovf_deep = c->ovf_deep_opt >= 0 ? c->ovf_deep_opt != 0 : (c->ovf_n * 100 > c->nnz * 3);
-    // tier 2 (k_t2_tables): on by default.  A deep matrix takes it on the LOCUS side only (counts instead of 1300 per-entry
-    // evaluations per locus: locus pass 1.6 -> 1.0 ms at 10^6 cells x 200k loci deep); its cell side stays with the arithmetic
-    // kernel — 2.3e8 lookups of a line each out of a 77 MB table cost more than evaluating the entries (measured: 9.8 vs 6.1 ms).
-    c->t2 = c->ovf_n != 0 && L != 0 && L < (1ull << 27) /* the pair list's keys */ && (c->t2_opt >= 0 ? c->t2_opt != 0 : true);
-    // tier-2 tiles: the cell side of the totals 5..8 (or 5..6) of a deep matrix walks tiles of its own (t2_tiles_build)
-    c->t2_tiles = 0;
-    if (c->ovf_deep && c->ovf_deep_wide && c->ovf_n && nloc && L) c->t2_tiles = c->t2_tiles_opt < 0 ? 8 : c->t2_tiles_opt;
-    if (c->t2_tiles == 8) CHK(t2_tiles_build<geo_t2<8>>(c));
-    else if (c->t2_tiles == 6) CHK(t2_tiles_build<geo_t2<6>>(c));
-    CHK(dev_alloc(c, &c->ovf_sum, 3 * 2 * nloc));
-    CHK(dev_alloc(c, &c->ovf_tab, L * OV_ROW));
-    CHK(dev_alloc(c, &c->ovc_locus, c->ovf_n));
-    if (L && c->ovf_n)
-        hipLaunchKernelGGL(k_ovf_locus_ids, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovc_ptr, c->ovc_locus);
-    if (!(c->t2 && !c->ovf_deep)) {  // (the per-entry paths of a shard without tier 2, and the deep forms)
-        CHK(dev_alloc(c, &c->ovf_lp, c->ovf_n));
-        CHK(dev_alloc(c, &c->ovf_etab, L * OV_REC));
-    }
-    CHK(dev_alloc(c, &c->ovf_nmask, L));
-    c->ovx_n = 0;
-    if (c->t2) {
-        // tier 2: static pair histogram, per-iteration counters and table; the by-locus CSC of the entries outside it
-        CHK(dev_alloc(c, &c->hist_all2, L * T2_CSTRIDE));
-        CHK(dev_alloc(c, &c->cnt2, L * T2_CSTRIDE));
-        CHK(dev_alloc(c, &c->tab2, L * T2_ROW));
-        HIPCHK(c, hipMemsetAsync(c->hist_all2, 0, L * T2_CSTRIDE * sizeof(uint32_t), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->cnt2, 0, L * T2_CSTRIDE * sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(k_t2_hist, dim3(gcap(c->ovf_n, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->ovf_n, c->ovc_locus, c->ovc_ent,
-                           c->hist_all2);
-        {
-            DevBuf<uint64_t> np, ns;
-            uint64_t tot_p = 0, tot_s = 0;
-            CHK(dev_alloc(c, &np, L + 1));
-            CHK(dev_alloc(c, &ns, L + 1));
-            HIPCHK(c, hipMemsetAsync(np + L, 0, 8, c->stream));
-            HIPCHK(c, hipMemsetAsync(ns + L, 0, 8, c->stream));
-            hipLaunchKernelGGL(k_t2_lists<false>, dim3(gcap(L, 256)), dim3(256), 0, c->stream, L, c->hist_all2, np, ns, (uint32_t *)nullptr,
-                               (uint32_t *)nullptr, (uint32_t *)nullptr);
-            CHK(dev_exclusive_scan_u64(c, np, L + 1, &tot_p));
-            CHK(dev_exclusive_scan_u64(c, ns, L + 1, &tot_s));
-            CHK(dev_alloc(c, &c->t2_plist, tot_p));
-            CHK(dev_alloc(c, &c->t2_slist, tot_s));
-            CHK(dev_alloc(c, &c->t2_pmask, L));
-            hipLaunchKernelGGL(k_t2_lists<true>, dim3(gcap(L, 256)), dim3(256), 0, c->stream, L, c->hist_all2, np, ns, c->t2_plist, c->t2_slist,
-                               c->t2_pmask);
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "tier-2 list build failed");
-            c->t2_np = (uint32_t)tot_p; c->t2_ns = (uint32_t)tot_s;
-        }
-        CHK(dev_alloc(c, &c->ovx_ptr, L + 1));
-        HIPCHK(c, hipMemsetAsync(c->ovx_ptr + L, 0, 8, c->stream));
-        hipLaunchKernelGGL((k_ovf_build<false, 8>), dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovc_ptr, c->ovc_ent, c->ovx_ptr,
-                           (uint64_t *)nullptr);
-        CHK(dev_exclusive_scan_u64(c, c->ovx_ptr, L + 1, &c->ovx_n));
-        CHK(dev_alloc(c, &c->ovx_ent, c->ovx_n));
-        CHK(dev_alloc(c, &c->ovx_locus, c->ovx_n));
-        CHK(dev_alloc(c, &c->ovx_lp, c->ovx_n));
-        hipLaunchKernelGGL((k_ovf_build<true, 8>), dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovc_ptr, c->ovc_ent, c->ovx_ptr,
-                           c->ovx_ent);
-        if (c->ovx_n)
-            hipLaunchKernelGGL(k_ovf_locus_ids, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovx_ptr, c->ovx_locus);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ovc_locus.reset();  // (only the histogram needed it)
-    }
-    {
-        const uint64_t n_grp = (nloc + 63) / 64;
-        uint64_t slots = 0;
-        CHK(dev_alloc(c, &c->ovf_ell_ptr, n_grp + 1));
-        HIPCHK(c, hipMemsetAsync(c->ovf_ell_ptr + n_grp, 0, 8, c->stream));
-        if (nloc)
-            hipLaunchKernelGGL(k_ovf_ell_build<false>, dim3(gcap(n_grp * 64, 256, 0x7fffffffu)), dim3(256), 0, c->stream, nloc,
-                               c->ovf_ptr, c->ovf_ent, c->ovf_ell_ptr, (uint64_t *)nullptr);
-        CHK(dev_exclusive_scan_u64(c, c->ovf_ell_ptr, n_grp + 1, &slots));
-        CHK(dev_alloc(c, &c->ovf_ell, slots));
-        if (nloc)
-            hipLaunchKernelGGL(k_ovf_ell_build<true>, dim3(gcap(n_grp * 64, 256, 0x7fffffffu)), dim3(256), 0, c->stream, nloc,
-                               c->ovf_ptr, c->ovf_ent, c->ovf_ell_ptr, c->ovf_ell);
-        HIPCHK(c, hipGetLastError());
-    }
-    // the tier lists of the entries the fast cell-side kernel leaves out
-    c->ovf_n_tier[0] = c->ovf_n_tier[1] = 0;
-    if (nloc && c->ovf_n) {
-        DevBuf<uint64_t> cnt0, cnt1;
-        CHK(dev_alloc(c, &cnt0, nloc + 1));
-        CHK(dev_alloc(c, &cnt1, nloc + 1));
-        HIPCHK(c, hipMemsetAsync(cnt0 + nloc, 0, 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(cnt1 + nloc, 0, 8, c->stream));
-        const unsigned g = gcap(nloc, 256, 0x7fffffffu);
-        hipLaunchKernelGGL(k_ovf_tier_lists<false>, dim3(g), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, cnt0, cnt1,
-                           (uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
-        CHK(dev_exclusive_scan_u64(c, cnt0, nloc + 1, &c->ovf_n_tier[0]));
-        CHK(dev_exclusive_scan_u64(c, cnt1, nloc + 1, &c->ovf_n_tier[1]));
-        for (int t = 0; t < 2; t++) {
-            CHK(dev_alloc(c, &c->ovf_tier_row[t], c->ovf_n_tier[t]));
-            CHK(dev_alloc(c, &c->ovf_tier_ent[t], c->ovf_n_tier[t]));
-        }
-        hipLaunchKernelGGL(k_ovf_tier_lists<true>, dim3(g), dim3(256), 0, c->stream, nloc, c->ovf_ptr, c->ovf_ent, cnt0, cnt1,
-                           c->ovf_tier_row[0], c->ovf_tier_ent[0], c->ovf_tier_row[1], c->ovf_tier_ent[1]);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "tier list build failed");
-        cnt0.reset(); cnt1.reset();
-        CHK(dev_alloc(c, &c->ovf_tier_val, 2 * c->ovf_n_tier[1]));  // (log-pmf, expected term) of the tier-1 entries, per pass
-    }
-    // which totals the per-entry tables (k_ovf_tables, k_ovf_tables_e) must cover at every locus: those of the entries that
-    // take these paths
-    if (L && c->ovf_n) {
-        if (c->t2 && !c->ovf_deep)  // (a deep matrix' cell side evaluates every overflow entry: its tables cover all totals)
-            hipLaunchKernelGGL(k_ovf_nmask, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovx_ptr, c->ovx_ent, c->ovf_nmask);
-        else
-            hipLaunchKernelGGL(k_ovf_nmask, dim3(gcap(L, 4)), dim3(256), 0, c->stream, L, c->ovc_ptr, c->ovc_ent, c->ovf_nmask);
-    }
-    HIPCHK(c, hipGetLastError());
-
-    // ---- per-iteration workspaces
-    // tables: three log-pmf-only sets (posterior passes; set 0 also serves an EM pass without the expected column),
-    // then one set of (log-pmf, expected) pairs; tail pad for the unconditional partial last table load
-    const uint64_t tab_elems = (uint64_t)c->t_nj * TAB_ELEMS;
-    CHK(dev_alloc(c, &c->tab, 4 * tab_elems + 4 * T_THREADS));
-    c->tab_em = c->tab;
-    c->tab_em_stride = 1;
-    CHK(dev_alloc(c, &c->part, 3ull * 2 * c->t_groups * c->t_npad));
-    CHK(dev_alloc(c, &c->ab3, 3 * L));
-    CHK(dev_alloc(c, &c->masked_cnt, nloc));
-    CHK(dev_alloc(c, &c->flag_bits, (nloc + 31) / 32 + 1));
-    CHK(dev_alloc(c, &c->tile_work, 3 * T_GROUPS_MAX));
-    CHK(dev_alloc(c, &c->minlist, nloc));
-    CHK(dev_alloc(c, &c->chg, nloc));
-    CHK(dev_alloc(c, &c->tally, L * 16));
-    {
-        // subsets of the exclusion set: enough (range, subset) workgroups to fill the chip once
-        int ncu = 256;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        const uint32_t R = (uint32_t)((L + LR_LOCI - 1) / LR_LOCI);
-        uint32_t sub = R ? (uint32_t)ncu / R : 1;  // one workgroup per CU (LDS): at most one round of them
-        if (sub < 1) sub = 1;
-        if (sub > LR_SUB_MAX) sub = LR_SUB_MAX;
-        c->lr_sub = sub;
-        CHK(dev_alloc(c, &c->hist_min, (uint64_t)sub * L * 16));
-        CHK(dev_alloc(c, &c->roff, nloc * (R + 1)));
-        // what a subset may hold (locus_by_minority): its u16 counters take 65535 / (most entries of a cell at one locus)
-        DevBuf<uint32_t> pair_max;
-        CHK(dev_alloc(c, &pair_max, 1));
-        HIPCHK(c, hipMemsetAsync(pair_max, 0, sizeof(uint32_t), c->stream));
-        if (nloc) {
-            hipLaunchKernelGGL(k_range_offsets, dim3(gcap(nloc, 4)), dim3(256), 0, c->stream, nloc, R, (uint32_t)LR_LOCI, c->csr_ptr, c->csr_ent,
-                               c->roff);
-            hipLaunchKernelGGL(k_max_pair_entries, dim3(gcap(nloc, 4, 1u << 16)), dim3(256), 0, c->stream, nloc, c->csr_ptr, c->csr_ent,
-                               pair_max.get());
-        }
-        HIPCHK(c, hipGetLastError());
-        uint32_t h_pair_max = 0;
-        HIPCHK(c, hipMemcpyAsync(&h_pair_max, pair_max, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->lr_cap = std::min<uint32_t>(32767u, 65535u / std::max<uint32_t>(1u, h_pair_max));
-        // the transposed offsets of the excluded cells, sized for the largest exclusion set the automatic choice hands to the
-        // minority-driven form (allocated here, not in the first iteration's locus pass: that cost the first iteration a
-        // stream synchronisation and two allocations — and a run has few iterations)
-        if (nloc && (c->locus_mode != 1 || c->tally_delta)) {
-            c->mroff_cap = ((nloc * LM_NUM / LM_DEN + LT_CELLS) + 63) & ~63ull;
-            CHK(dev_alloc(c, &c->mroff, (uint64_t)(R + 1) * c->mroff_cap));
-            CHK(dev_alloc(c, &c->mbeg, c->mroff_cap));
-        }
-    }
-    HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (nloc ? nloc : 1) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flag_bits, 0, ((nloc + 31) / 32 + 1) * 4, c->stream));
-    if (L) HIPCHK(c, hipMemsetAsync(c->tally, 0, L * 16 * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->tiled_ready = true;
-    // before the first iteration the exclusion set is empty (cellector_ingest_finish): the zeroed counts (tally, cnt2) are its
-    // counts.  (A build after engine-1 iterations is followed by the engine option's invalidation.)
-    c->tally_valid = c->iteration == 0;
     return CELLECTOR_OK;
 }
 
@@ -2781,83 +1668,52 @@ static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2
     double *o_ll = c->ovf_sum + (uint64_t)set * 2 * c->nloc, *o_ell = o_ll + c->nloc;
     const unsigned g = gcap(c->nloc, 256, 0x7fffffffu), eg = gcap(c->L * 16, 256, 0x7fffffffu);
     const bool deep = c->ovf_deep;  // the overflow share is large: full form, never throttled, no tier-0 list
-    if (c->t2 && !deep) {
-        // tier 2: the pairs' table of this pass, then the rows' lookups (writes the sums); the other totals ADD to them
-        const unsigned gp = gcap(c->t2_np, 256, 0x7fffffffu), gs = expected ? gcap(c->t2_ns, 256, 0x7fffffffu) : 0u;
-        // (side_lds > 0: a request for dynamic LDS the lookup kernel does not use, to limit its blocks per CU in A/B runs)
-        const size_t lds_req = c->side_lds > 0 ? (size_t)c->side_lds : 0;
-        // waves of the lookup kernel: all groups at once when it has the machine to itself, option t2_waves (default 512) beside the tile kernel
-        const uint64_t n_grp = (c->nloc + 63) / 64;
-        const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)c->t2_waves : 0x7fffffffull);
-        const bool need_e = expected && c->ovf_n_tier[0];  // E(9..17) of the tier-0 entries
-#define T2_CELL(E)                                                                                                         \
-        do {                                                                                                               \
-            hipLaunchKernelGGL(k_t2_tables<E>, dim3(gp + gs), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp, ab, c->lf, \
-                               c->tab2);                                                                                   \
-            hipLaunchKernelGGL(k_t2_cell<E>, dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2, o_ll, o_ell); \
-            if (need_e)                                                                                                    \
-                hipLaunchKernelGGL(k_ovf_tables_e, dim3(eg), dim3(256), 0, st, c->L, ab, c->ovf_nmask, c->ovf_tab, c->ovf_etab); \
-            if (c->ovf_n_tier[0])                                                                                          \
-                hipLaunchKernelGGL((k_ovf_cell_listed<E, false>), dim3(gcap(c->ovf_n_tier[0], 256, 0x7fffffffu)), dim3(256), 0, st, \
-                                   c->ovf_n_tier[0], c->ovf_tier_row[0], c->ovf_tier_ent[0], ab, c->lf, c->ovf_tab, o_ll, o_ell); \
-            if (c->ovf_n_tier[1]) {                                                                                        \
-                hipLaunchKernelGGL(k_ovf_listed_values<E>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st, \
-                                   c->ovf_n_tier[1], c->ovf_tier_ent[1], ab, c->lf, c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1]); \
-                hipLaunchKernelGGL(k_ovf_listed_add<E>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st, c->ovf_n_tier[1], \
-                                   c->ovf_tier_row[1], c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1], o_ll, o_ell);  \
-            }                                                                                                              \
-        } while (0)
-        if (expected) T2_CELL(true); else T2_CELL(false);
-#undef T2_CELL
-        return;
-    }
-    if (expected) {
-        hipLaunchKernelGGL(k_ovf_tables_e, dim3(eg), dim3(256), 0, st, c->L, ab, c->ovf_nmask, c->ovf_tab, c->ovf_etab);
-        // Residency throttle: a request for dynamic LDS it does not use leaves room for only ONE block of this kernel beside
-        // a tile workgroup (one wave per SIMD instead of two).  On a big shard the kernel still ends well inside the tile
-        // kernel and disturbs it less (cfg4: 2.83 -> 2.78 ms per iteration); a small shard's tile kernel is too short for that.
-        const size_t lds_req = deep ? 0 : c->side_lds >= 0 ? (size_t)c->side_lds : (st == c->side && c->nloc >= (1ull << 19) ? 5000 : 0);
-        if (deep && c->ovf_deep_wide)
-            hipLaunchKernelGGL(k_ovf_cell_wide<true>, dim3(gcap(c->nloc * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, st, c->nloc, c->t2_tiles ? c->ovr_ptr : c->ovf_ptr,
-                               c->t2_tiles ? c->ovr_ent : c->ovf_ent, ab, c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        else if (deep)
-            hipLaunchKernelGGL((k_ovf_cell_direct<true, false, true>), dim3(g), dim3(256), 0, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, ab,
-                               c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        else if (lds_req)  // one block per CU: the 64-VGPR form with the packed per-locus record
-            hipLaunchKernelGGL((k_ovf_cell_direct<true, true, false>), dim3(g), dim3(256), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell,
-                               ab, c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        else
-            hipLaunchKernelGGL((k_ovf_cell_direct<true, false, false>), dim3(g), dim3(256), 0, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, ab,
-                               c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        if (c->ovf_n_tier[0] && !deep)
-            hipLaunchKernelGGL((k_ovf_cell_listed<true, false>), dim3(gcap(c->ovf_n_tier[0], 256, 0x7fffffffu)), dim3(256), 0, st,
-                               c->ovf_n_tier[0], c->ovf_tier_row[0], c->ovf_tier_ent[0], ab, c->lf, c->ovf_tab, o_ll, o_ell);
-        if (c->ovf_n_tier[1]) {
-            hipLaunchKernelGGL(k_ovf_listed_values<true>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st,
-                               c->ovf_n_tier[1], c->ovf_tier_ent[1], ab, c->lf, c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1]);
-            hipLaunchKernelGGL(k_ovf_listed_add<true>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st, c->ovf_n_tier[1],
-                               c->ovf_tier_row[1], c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1], o_ll, o_ell);
+    const uint64_t n0 = deep ? 0 : c->ovf_n_tier[0], n1 = c->ovf_n_tier[1];  // the listed entries this pass evaluates
+    auto tables_e = [&] { hipLaunchKernelGGL(k_ovf_tables_e, dim3(eg), dim3(256), 0, st, c->L, ab, c->ovf_nmask, c->ovf_tab, c->ovf_etab); };
+    with_bool(expected, [&](auto E) {
+        constexpr bool EXP = E.value;
+        if (c->t2 && !deep) {
+            // tier 2: the pairs' table of this pass, then the rows' lookups (writes the sums); the other totals ADD to them
+            const unsigned gp = gcap(c->t2_np, 256, 0x7fffffffu), gs = EXP ? gcap(c->t2_ns, 256, 0x7fffffffu) : 0u;
+            // (side_lds > 0: a request for dynamic LDS the lookup kernel does not use, to limit its blocks per CU in A/B runs)
+            const size_t lds_req = c->side_lds > 0 ? (size_t)c->side_lds : 0;
+            // waves of the lookup kernel: all groups at once when it has the machine to itself, option t2_waves (default 512) beside the tile kernel
+            const uint64_t n_grp = (c->nloc + 63) / 64;
+            const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)c->t2_waves : 0x7fffffffull);
+            hipLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp, ab, c->lf,
+                               c->tab2);
+            hipLaunchKernelGGL(k_t2_cell<EXP>, dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2, o_ll, o_ell);
+            if (EXP && n0) tables_e();  // E(9..17) of the tier-0 entries
+        } else {
+            if (EXP) tables_e();
+            // Residency throttle (EM pass): a request for dynamic LDS it does not use leaves room for only ONE block of this kernel beside
+            // a tile workgroup (one wave per SIMD instead of two).  On a big shard the kernel still ends well inside the tile
+            // kernel and disturbs it less (cfg4: 2.83 -> 2.78 ms per iteration); a small shard's tile kernel is too short for that.
+            const size_t lds_req =
+                !EXP || deep ? 0 : c->side_lds >= 0 ? (size_t)c->side_lds : (st == c->side && c->nloc >= (1ull << 19) ? 5000 : 0);
+            auto direct = [&](auto PACKED, auto FULL) {
+                hipLaunchKernelGGL((k_ovf_cell_direct<EXP, PACKED.value, FULL.value>), dim3(g), dim3(256), lds_req, st, c->nloc, c->ovf_ell_ptr,
+                                   c->ovf_ell, ab, c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
+            };
+            if (deep && c->ovf_deep_wide)
+                hipLaunchKernelGGL(k_ovf_cell_wide<EXP>, dim3(gcap(c->nloc * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, st, c->nloc,
+                                   c->t2_tiles ? c->ovr_ptr : c->ovf_ptr, c->t2_tiles ? c->ovr_ent : c->ovf_ent, ab, c->lf, c->ovf_etab,
+                                   c->ovf_tab, o_ll, o_ell);
+            else if (deep) direct(std::false_type(), std::true_type());
+            else if (!lds_req) direct(std::false_type(), std::false_type());
+            else if constexpr (EXP) direct(std::true_type(), std::false_type());  // one block per CU: the 64-VGPR form, packed record
         }
-    } else {
-        if (deep && c->ovf_deep_wide)
-            hipLaunchKernelGGL(k_ovf_cell_wide<false>, dim3(gcap(c->nloc * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, st, c->nloc, c->t2_tiles ? c->ovr_ptr : c->ovf_ptr,
-                               c->t2_tiles ? c->ovr_ent : c->ovf_ent, ab, c->lf, c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        else if (deep)
-            hipLaunchKernelGGL((k_ovf_cell_direct<false, false, true>), dim3(g), dim3(256), 0, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, ab, c->lf,
-                               c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        else
-            hipLaunchKernelGGL((k_ovf_cell_direct<false, false, false>), dim3(g), dim3(256), 0, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, ab, c->lf,
-                               c->ovf_etab, c->ovf_tab, o_ll, o_ell);
-        if (c->ovf_n_tier[0] && !deep)
-            hipLaunchKernelGGL((k_ovf_cell_listed<false, false>), dim3(gcap(c->ovf_n_tier[0], 256, 0x7fffffffu)), dim3(256), 0, st,
-                               c->ovf_n_tier[0], c->ovf_tier_row[0], c->ovf_tier_ent[0], ab, c->lf, c->ovf_tab, o_ll, o_ell);
-        if (c->ovf_n_tier[1]) {
-            hipLaunchKernelGGL(k_ovf_listed_values<false>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st,
-                               c->ovf_n_tier[1], c->ovf_tier_ent[1], ab, c->lf, c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1]);
-            hipLaunchKernelGGL(k_ovf_listed_add<false>, dim3(gcap(c->ovf_n_tier[1], 256, 0x7fffffffu)), dim3(256), 0, st, c->ovf_n_tier[1],
-                               c->ovf_tier_row[1], c->ovf_tier_val, c->ovf_tier_val + c->ovf_n_tier[1], o_ll, o_ell);
+        // the totals the kernels above leave out, as two short static lists: tier 0 (9..17) and tier 1 (above)
+        if (n0)
+            hipLaunchKernelGGL((k_ovf_cell_listed<EXP, false>), dim3(gcap(n0, 256, 0x7fffffffu)), dim3(256), 0, st, n0, c->ovf_tier_row[0],
+                               c->ovf_tier_ent[0], ab, c->lf, c->ovf_tab, o_ll, o_ell);
+        if (n1) {
+            hipLaunchKernelGGL(k_ovf_listed_values<EXP>, dim3(gcap(n1, 256, 0x7fffffffu)), dim3(256), 0, st, n1, c->ovf_tier_ent[1], ab, c->lf,
+                               c->ovf_tier_val, c->ovf_tier_val + n1);
+            hipLaunchKernelGGL(k_ovf_listed_add<EXP>, dim3(gcap(n1, 256, 0x7fffffffu)), dim3(256), 0, st, n1, c->ovf_tier_row[1], c->ovf_tier_val,
+                               c->ovf_tier_val + n1, o_ll, o_ell);
         }
-    }
+    });
 }
 // locus side: the per-locus cumulative-log tables that k_locus_finalize evaluates the overflow entries' log-pmfs from, on stream `st`
 static void launch_overflow_locus_values(cellector_ctx *c, hipStream_t st, const double2 *ab)
@@ -2903,7 +1759,6 @@ static cellector_status side_join(cellector_ctx *c)
 static cellector_status build_tile_tables(cellector_ctx *c, const double2 *ab, int set, bool expected, bool form_ab = false,
                                           const uint8_t *mask = nullptr, hipEvent_t done = nullptr /*rides on the dispatch*/)
 {
-    c->tab_event_valid = false;
     const uint64_t tab_elems = (uint64_t)c->t_nj * TAB_ELEMS;
     double *tab = expected ? c->tab + 3 * tab_elems : c->tab + (uint64_t)set * tab_elems;
     const unsigned tgrid = gcap((uint64_t)c->t_nj * T_BL, 64);
@@ -2917,18 +1772,14 @@ static cellector_status build_tile_tables(cellector_ctx *c, const double2 *ab, i
         src.tile_work = c->tile_work; src.n_work = 3u * T_GROUPS_MAX;
         c->work_zeroed = true;
     }
-    if (done) {  // (an event RECORDED behind the kernel is a barrier packet of its own: ~6 us of idle queue in front of the next kernel)
-        if (expected)
-            hipExtLaunchKernelGGL(k_build_tables<true>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, nullptr, done, 0, c->L, c->t_nj, ab,
+    with_bool(expected, [&](auto E) {
+        if (done)  // (an event RECORDED behind the kernel is a barrier packet of its own: ~6 us of idle queue in front of the next kernel)
+            hipExtLaunchKernelGGL(k_build_tables<E.value>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, nullptr, done, 0, c->L, c->t_nj, ab,
                                   (const double *)c->lf, tab, src);
         else
-            hipExtLaunchKernelGGL(k_build_tables<false>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, nullptr, done, 0, c->L, c->t_nj, ab,
-                                  (const double *)c->lf, tab, src);
-        c->tab_event_valid = true;
-    } else if (expected)
-        hipLaunchKernelGGL(k_build_tables<true>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, c->L, c->t_nj, ab, c->lf, tab, src);
-    else
-        hipLaunchKernelGGL(k_build_tables<false>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, c->L, c->t_nj, ab, c->lf, tab, src);
+            hipLaunchKernelGGL(k_build_tables<E.value>, dim3(tgrid), dim3(64 * TB_PARTS), 0, c->stream, c->L, c->t_nj, ab, c->lf, tab, src);
+    });
+    c->tab_event_valid = done != nullptr;
     if (set == 0) {  // the locus pass of this iteration reads the log-pmfs of the EM pass' table
         c->tab_em = tab;
         c->tab_em_stride = expected ? 2 : 1;
@@ -2944,40 +1795,13 @@ static cellector_status run_tile_pass(cellector_ctx *c, int set, bool expected)
     double *tab = expected ? c->tab + 3 * tab_elems : c->tab + (uint64_t)set * tab_elems;
     double *part_ll = c->part + (uint64_t)set * 2 * c->t_groups * c->t_npad;
     double *part_ell = part_ll + (uint64_t)c->t_groups * c->t_npad;
-    // several cell blocks per column amortise the table staging; with few blocks (small shard) prefer more columns
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-    int sb = T_SB_MAX;
-    while (sb > 2 && (uint64_t)((c->t_nb + sb - 1) / sb) * c->t_groups * 10 < (uint64_t)ncu * 9) sb >>= 1;  // < 90 % of the CUs busy
-    if (c->tile_sb_opt) sb = c->tile_sb_opt;  // option tile_sb: the width forced (tests)
-    const uint32_t n_cols = (c->t_nb + sb - 1) / sb;
-    // persistent workgroups: one per CU, an equal number for every chunk group, never more than there are columns
-    uint32_t per_group = (uint32_t)ncu / c->t_groups;
-    if (per_group < 1) per_group = 1;
-    if (per_group > n_cols) per_group = n_cols;
-    const dim3 grid(per_group * c->t_groups);
+    const TileGeo tg = tile_geometry(c, c->t_nb, c->t_groups);
     uint32_t *work = c->tile_work + (size_t)set * T_GROUPS_MAX;
-    static_assert(T_GROUPS_MAX == CELLECTOR_TILE_WORK_STRIDE, "k_alpha_beta resets the counters with this stride");
     if (!(set == 0 && c->work_zeroed))  // else: reset by this iteration's k_alpha_beta
         HIPCHK(c, hipMemsetAsync(work, 0, T_GROUPS_MAX * sizeof(uint32_t), c->stream));
-    hipEvent_t t_a = nullptr, t_b = nullptr;  // the timer's events ride on the dispatch: no barrier packets around the kernel
-    const bool timed = timer_take(c, CELLECTOR_K_TILE_LL, &t_a, &t_b);
-#define LAUNCH_TILE(E, S)                                                                                                  \
-    do {                                                                                                                   \
-        if (timed)                                                                                                         \
-            hipExtLaunchKernelGGL((k_tile_ll<E, S>), grid, dim3(T_THREADS), 0, c->stream, t_a, t_b, 0, c->t_nb, c->t_nj, c->t_cpg, \
-                                  c->t_groups, n_cols, work, (const uint16_t *)c->thdr, (const uint16_t *)c->tiles,        \
-                                  (const double *)tab, c->t_npad, part_ll, part_ell);                                      \
-        else                                                                                                               \
-            hipLaunchKernelGGL((k_tile_ll<E, S>), grid, dim3(T_THREADS), 0, c->stream, c->t_nb, c->t_nj, c->t_cpg, c->t_groups, \
-                               n_cols, work, c->thdr, c->tiles, tab, c->t_npad, part_ll, part_ell);                        \
-    } while (0)
-    if (expected) {
-        if (sb == 4) LAUNCH_TILE(true, 4); else LAUNCH_TILE(true, 2);
-    } else {
-        if (sb == 4) LAUNCH_TILE(false, 4); else LAUNCH_TILE(false, 2);
-    }
-#undef LAUNCH_TILE
+    hipEvent_t t_a = nullptr, t_b = nullptr;
+    timer_take(c, CELLECTOR_K_TILE_LL, &t_a, &t_b);  // (both stay null when the launch is not timed)
+    launch_tile_ll<geo_reg>(c, expected, tg, c->t_nj, c->t_cpg, c->t_groups, work, c->thdr, c->tiles, tab, part_ll, part_ell, t_a, t_b);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
 }
@@ -3044,12 +1868,10 @@ cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *no
     double *part_ll = c->part, *part_ell = c->part + (uint64_t)c->t_groups * c->t_npad;
     const double *o_ll = ovf ? c->ovf_sum : nullptr, *o_ell = ovf ? c->ovf_sum + c->nloc : nullptr;
     const unsigned grid = gcap((c->nloc + 1) / 2, 256, 0x7fffffffu);
-    if (c->compute_expected)
-        hipLaunchKernelGGL(k_cell_finalize<true>, dim3(grid), dim3(256), 0, c->stream, c->nloc, c->t_groups, c->t_npad, part_ll,
+    with_bool(c->compute_expected, [&](auto E) {
+        hipLaunchKernelGGL(k_cell_finalize<E.value>, dim3(grid), dim3(256), 0, c->stream, c->nloc, c->t_groups, c->t_npad, part_ll,
                            part_ell, o_ll, o_ell, c->csr_ptr, c->masked_cnt, c->ll, c->ell, c->nloci, norm_out);
-    else
-        hipLaunchKernelGGL(k_cell_finalize<false>, dim3(grid), dim3(256), 0, c->stream, c->nloc, c->t_groups, c->t_npad, part_ll,
-                           part_ell, o_ll, o_ell, c->csr_ptr, c->masked_cnt, c->ll, c->ell, c->nloci, norm_out);
+    });
     timer_end(c, CELLECTOR_K_CELL_LL);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
@@ -3070,9 +1892,7 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     if (!valid && c->t2) HIPCHK(c, hipMemsetAsync(c->cnt2, 0, c->L * T2_CSTRIDE * sizeof(uint32_t), c->stream));
     // (k_flag wrote the exclusion bitmask flag_bits along with the flags)
     const size_t lds = (size_t)words * 4;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-    unsigned grid = (unsigned)ncu;
+    unsigned grid = (unsigned)c->n_cu;
     const uint64_t need = (c->L + LS_THREADS / 64 - 1) / (LS_THREADS / 64);
     if (grid > need) grid = (unsigned)(need ? need : 1);
 #define LAUNCH_LS(INLDS, EBV, GRID, LDSB)                                                                              \
@@ -3132,17 +1952,15 @@ cellector_status tiled_locus_pass(cellector_ctx *c)
     const uint64_t *w_ptr = c->t2 ? (c->ovx_n ? c->ovx_ptr : nullptr) : (c->ovf_n ? c->ovc_ptr : nullptr);
     const uint64_t *w_ent = c->t2 ? c->ovx_ent : c->ovc_ent;
     const double *w_lp = c->t2 ? c->ovx_lp : c->ovf_lp;
-#define LAUNCH_LF(INL)                                                                                                             \
-    hipLaunchKernelGGL(k_locus_finalize<INL>, dim3(gcap(c->L * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->L, c->locus_mode, \
-                       valid, c->nloc, c->lr_sub, c->lr_cap, c->d_counters + DC_N_MIN, c->hist_min, c->tally, c->flag_bits, c->hist_all, \
-                       c->tab_em,                                                                                                  \
-                       (uint32_t)c->tab_em_stride, c->mask, w_ptr, w_ent, w_lp, c->ovf_tab, c->lf, c->ab, c->x_locus,              \
-                       c->t2 ? c->cnt2 : (uint32_t *)nullptr, c->hist_all2, c->t2_pmask, c->tab2,                                    \
-                       c->filter_fused ? c->mask_next : (uint8_t *)nullptr, c->d_counters)
     // (a ctx that holds all cells and has no communicator: nothing is exchanged between the finalize and the filter)
     c->filter_fused = !comm_active(c->comm) && c->nloc == c->total_cells && c->fuse_filter;
-    if (c->ovf_deep) LAUNCH_LF(true); else LAUNCH_LF(false);
-#undef LAUNCH_LF
+    with_bool(c->ovf_deep, [&](auto INL) {
+        hipLaunchKernelGGL(k_locus_finalize<INL.value>, dim3(gcap(c->L * LF_LANES, 256, 0x7fffffffu)), dim3(256), 0, c->stream, c->L,
+                           c->locus_mode, valid, c->nloc, c->lr_sub, c->lr_cap, c->d_counters + DC_N_MIN, c->hist_min, c->tally, c->flag_bits,
+                           c->hist_all, c->tab_em, (uint32_t)c->tab_em_stride, c->mask, w_ptr, w_ent, w_lp, c->ovf_tab, c->lf, c->ab,
+                           c->x_locus, c->t2 ? c->cnt2 : (uint32_t *)nullptr, c->hist_all2, c->t2_pmask, c->tab2,
+                           c->filter_fused ? c->mask_next : (uint8_t *)nullptr, c->d_counters);
+    });
     timer_end(c, CELLECTOR_K_LOCUS_STATS);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
@@ -3160,18 +1978,22 @@ cellector_status tiled_prebuild_tables(cellector_ctx *c)
     return CELLECTOR_OK;
 }
 
+// masked_cnt += the entries of the loci that mask_old has and mask_new has not
+static cellector_status launch_masked_update(cellector_ctx *c, const uint8_t *mask_old, const uint8_t *mask_new)
+{
+    with_bool(c->c4_bits == 24, [&](auto NARROW) {
+        hipLaunchKernelGGL(k_masked_update<NARROW.value ? 24 : 32>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, mask_old, mask_new,
+                           c->c4_ptr, c->c4_ent, c->ovc_ptr, c->ovc_ent, c->masked_cnt);
+    });
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
+
 // called after the locus filter with mask = this iteration's mask, mask_next = filtered mask
 cellector_status tiled_masked_update(cellector_ctx *c)
 {
     if (c->L == 0) return CELLECTOR_OK;
-    if (c->c4_bits == 24)
-        hipLaunchKernelGGL(k_masked_update<24>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, c->mask, c->mask_next,
-                           c->c4_ptr, c->c4_ent, c->ovc_ptr, c->ovc_ent, c->masked_cnt);
-    else
-        hipLaunchKernelGGL(k_masked_update<32>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, c->mask, c->mask_next,
-                           c->c4_ptr, c->c4_ent, c->ovc_ptr, c->ovc_ent, c->masked_cnt);
-    HIPCHK(c, hipGetLastError());
-    return CELLECTOR_OK;
+    return launch_masked_update(c, c->mask, c->mask_next);
 }
 
 // a caller's mask (cellector_set_loci_mask): the counts from scratch — zeroed, then one update from an all-ones "old" mask to c->mask
@@ -3180,14 +2002,7 @@ cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones)
     HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (c->nloc ? c->nloc : 1) * 4, c->stream));
     if (c->L == 0 || c->nloc == 0) return CELLECTOR_OK;
     HIPCHK(c, hipMemsetAsync(ones, 1, c->L, c->stream));
-    if (c->c4_bits == 24)
-        hipLaunchKernelGGL(k_masked_update<24>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, ones, c->mask.get(),
-                           c->c4_ptr.get(), c->c4_ent.get(), c->ovc_ptr.get(), c->ovc_ent.get(), c->masked_cnt.get());
-    else
-        hipLaunchKernelGGL(k_masked_update<32>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, ones, c->mask.get(),
-                           c->c4_ptr.get(), c->c4_ent.get(), c->ovc_ptr.get(), c->ovc_ent.get(), c->masked_cnt.get());
-    HIPCHK(c, hipGetLastError());
-    return CELLECTOR_OK;
+    return launch_masked_update(c, ones, c->mask);
 }
 
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl)

@@ -1,0 +1,176 @@
+// Engine v2, shared by its two halves: kernels_tiled.hip (the passes an iteration runs) and kernels_tiled_build.hip (what
+// tiled_build makes once per ingest).  Constants, entry encodings and the host-side launch helpers.  Internal.
+#pragma once
+#include <algorithm>
+#include <initializer_list>
+#include <type_traits>
+
+#include "ctx.h"
+#include "device_math.h"
+
+#define T_K 4           // entries with 1 <= alt+ref <= T_K are "regular": log-pmf and expected term come from tables
+#define T_NCODE 14      // (alt, ref) combinations with 1 <= n <= T_K: K(K+3)/2
+#ifndef T_LROW
+#define T_LROW 18       // table doubles per locus: the T_NCODE log-pmfs, then the T_K expected terms
+#endif
+#ifndef T_BL
+#define T_BL 640        // locus slots per chunk (the table is T_BL * T_LROW * 8 B = 90 KB of LDS); the last slot is all zeros
+#endif
+#define T_BLU (T_BL - 1)  // loci per chunk
+#define T_BC 1024       // cells per block == threads per workgroup
+#define T_THREADS 1024
+static_assert(T_BC == T_ROWS_PER_TILE, "cellector_engine_info derives the lookup count from this");
+#define T_SB_MAX 4      // cell blocks per workgroup sharing one staged table (2 or 4: chosen per launch)
+#define T_GROUPS_MAX 64 // upper bound of the chunk groups of a launch
+static_assert(T_GROUPS_MAX == CELLECTOR_TILE_WORK_STRIDE, "k_alpha_beta resets the counters with this stride");
+#define T_GROUPS 8      // chunk groups beyond this many are charged for their partial sums (tiled_build's cost model)
+#define T_NE 15         // entries per cell of a slice held in registers (two 16-byte loads); longer slices: slow path
+// A u16 entry = n-1 << 14 | locus slot << 4 | code: log-pmf at table[slot * T_LROW + code], expected term at
+// table[slot * T_LROW + T_NCODE + (n-1)].
+#define T_NULL ((uint16_t)(T_BLU << 4))  // padding entry: code 0, n-1 = 0 of the zero slot
+// A slice in `tiles` is 64 rows of K+1 u16 (K odd): row i = [cell (0..1023) that lane i works for, K entries of that cell,
+// padded with T_NULL].  Tile header (fixed stride, in u16 units): 16 slices x {u64 first u16 of the slice in `tiles`,
+// u32 K, u32 pad}.
+#define T_HDR 128
+#define TAB_ELEMS ((uint64_t)T_LROW * T_BL)  // table doubles per chunk
+
+__device__ __forceinline__ bool ent_regular(uint64_t e)
+{
+    const uint32_t n = ENT_ALT(e) + ENT_REF(e);
+    return n >= 1u && n <= (uint32_t)T_K;
+}
+__device__ __forceinline__ uint32_t ent_code(uint64_t e)
+{
+    const uint32_t r = ENT_REF(e), n = ENT_ALT(e) + r;
+    return n * (n + 1u) / 2u - 1u + r;
+}
+
+#define TB_PARTS 6  // waves of a k_build_tables workgroup: each takes its share of a locus' 18 values
+
+// Table / entry geometry of a tile set.  geo_reg: the regular entries (totals 1..T_K): 18 doubles per locus, u16 entry =
+// n-1 << 14 | slot << 4 | code.  geo_t2<NMAX>: the tier-2 tiles of a deep-coverage matrix (totals 5..NMAX, tiled_build):
+// NMAX = 8: 30 log-pmfs + 4 expected terms per locus, 338 loci per chunk, entry = n-5 << 14 | slot << 5 | pair;
+// NMAX = 6: 13 + 2 doubles per locus, 767 loci per chunk, entry = n-5 << 14 | slot << 4 | pair.
+struct geo_reg {
+    static constexpr uint32_t LROW = T_LROW, BL = T_BL, NCODE = T_NCODE, SHIFT = 4, SMASK = 1023u, CMASK = 15u;
+    static constexpr uint32_t BLU = BL - 1, NLO = 1, NHI = T_K;  // loci per chunk (the last slot is all zeros); totals covered
+};
+template <int NMAX>
+struct geo_t2 {
+    static_assert(NMAX == 6 || NMAX == 8, "tier-2 tile geometries");
+    static constexpr uint32_t NCODE = NMAX == 8 ? 30 : 13, NE = NMAX - 4, LROW = NCODE + NE;
+    static constexpr uint32_t BL = NMAX == 8 ? 339 : 768, SHIFT = NMAX == 8 ? 5 : 4, SMASK = NMAX == 8 ? 511u : 1023u,
+                              CMASK = NMAX == 8 ? 31u : 15u;
+    static constexpr uint32_t BLU = BL - 1, NLO = 5, NHI = NMAX;
+};
+
+// overflow entries (alt+ref == 0 or > T_K)
+#define LF_LANES 16  // lanes that share a locus (k_locus_finalize) or a row (k_ovf_cell_wide)
+#define OV_NT 18  // cumulative tables cover counts 0..17; larger counts take the generic device_math path
+#define OV_NE 17  // expected terms E(n) tabulated for n = 4..17
+#define OV_FAST_N DM_CHUNK  // the cell side's fast kernel takes totals up to this (99 % of the overflow entries)
+#define OV_ROW 128  // doubles of a locus' overflow table row (k_ovf_tables); its E(n) start at OV_EOFF
+#define OV_EOFF 64
+#define OV_REC 8  // the cell side's per-locus record: alpha, beta, E(5..8), pad = ONE 64-byte sector per overflow entry
+#define OVF_PAD (~0ull)  // padding slot of the 64-row ELLPACK copy (k_ovf_ell_build)
+
+// tier 2: the overflow entries with totals 5..8 (k_t2_tables)
+#define T2_NMIN 5u
+#define T2_NMAX 8u
+#define T2_NCODE 30    // (alt, ref) pairs with 5 <= alt+ref <= 8; code = n(n+1)/2 - 15 + ref
+#define T2_CSTRIDE 32  // u32 counters per locus (hist_all2, cnt2)
+#define T2_ROW 48      // table doubles per locus
+static_assert(T2_NMAX == (unsigned)OV_FAST_N, "the tier lists take the totals above tier 2");
+__device__ __forceinline__ bool t2_total(uint32_t n) { return n - T2_NMIN <= T2_NMAX - T2_NMIN; }
+__device__ __forceinline__ uint32_t t2_code(uint32_t n, uint32_t r) { return n * (n + 1u) / 2u - 15u + r; }
+// position of the pair's log-pmf in the locus' table row; its sector's first double is E(n)
+__device__ __forceinline__ uint32_t t2_pos(uint32_t n, uint32_t r)
+{
+    const uint32_t hi = r >= 7u ? 1u : 0u;
+    return ((n - T2_NMIN) + (n == 8u ? 1u : 0u) + hi) * 8u + 1u + (hi ? r - 7u : r);
+}
+// the tier list an overflow entry goes to (k_ovf_tier_lists): none, 0 = totals 9..OV_NE, 1 = above
+__device__ __forceinline__ int ovf_tier(uint64_t en)
+{
+    const uint32_t n = ENT_ALT(en) + ENT_REF(en);
+    return n <= (uint32_t)OV_FAST_N ? -1 : (n <= (uint32_t)OV_NE ? 0 : 1);
+}
+
+// compact CSC entry of the locus pass: 24 bits (cell 20 | code 4) or 32 bits (cell 28 | code 4)
+template <int EB>
+__device__ __forceinline__ void c4_read1(const uint32_t *__restrict__ base, uint64_t i, uint32_t *cell, uint32_t *code)
+{
+    if (EB == 32) {
+        const uint32_t x = base[i];
+        *cell = x & 0x0fffffffu;
+        *code = x >> 28;
+    } else {
+        const uint8_t *b = reinterpret_cast<const uint8_t *>(base) + 3 * i;
+        const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+        *cell = v & 0xfffffu;
+        *code = v >> 20;
+    }
+}
+template <int EB>
+__device__ __forceinline__ void c4_write1(uint32_t *__restrict__ base, uint64_t i, uint32_t cell, uint32_t code)
+{
+    if (EB == 32) {
+        base[i] = cell | (code << 28);
+    } else {
+        uint8_t *b = reinterpret_cast<uint8_t *>(base) + 3 * i;
+        const uint32_t v = cell | (code << 20);
+        b[0] = (uint8_t)v; b[1] = (uint8_t)(v >> 8); b[2] = (uint8_t)(v >> 16);
+    }
+}
+// Form of the locus pass, decided on the device from this shard's exclusion-set size (locus_by_minority)
+#define LM_NUM 1  // minority-driven when n_min / nloc <= LM_NUM / LM_DEN
+#define LM_DEN 8
+
+// Locus ranges of the minority-driven locus pass.  A (cell, range) segment is a short run inside a long row and memory comes in 128-byte lines, so short segments waste
+// most of what they fetch (measured at 1024 loci per range: 80-byte segments, 2 GB fetched for 0.8 GB of entries, the
+// kernel at the HBM rate).  Hence wide ranges, with 16-bit counters so that the histogram still fits in LDS.
+#define LR_LOCI 4096     // loci per range: the LDS histogram is 14 codes x LR_LOCI x u16 = 112 KB
+#define LR_SUB_MAX 16    // at most this many subsets of the exclusion set (partial planes); chosen per matrix
+#define LR_THREADS 1024  // one workgroup per CU, 128 VGPRs: 16 entry loads per lane stay in flight
+#define LR_GROUP 64      // lanes per (cell, range) segment: ~41 entries at 1 % density (a tail loop would serialise)
+#define LR_ROW (LR_LOCI + 2)  // u16 counters per code row (even: a row starts on a word)
+#define LT_CELLS 64  // cells per workgroup of k_minority_offsets
+#define TB_BINS 64  // entry counts >= TB_BINS-1 share the last bin (they sort to the end, in cell order)
+// u16 of a tile staged in LDS (48 KB: two workgroups per CU); a bigger tile is written directly (rows of hundreds of entries)
+#define TB_STAGE (24 * 1024)
+
+// ---- host side ----
+static inline unsigned gcap(uint64_t n, unsigned per_block, unsigned cap = 1u << 20)
+{
+    uint64_t g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
+
+// A run-time bool as a template argument: f is a generic lambda, called with std::true_type or std::false_type, so that a launch
+// and its argument list are written once.  Only what f names for each of the two gets instantiated.
+template <class F>
+static inline void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type());
+    else f(std::false_type());
+}
+
+// The build's recurring step for an output in CSR form.  Every array of `a` is [n + 1] with its last slot zeroed by the caller:
+// pass(false) launches the kernels that COUNT into [0, n) (it gets the payload pointers as they are then: not dereferenced), an
+// exclusive scan per array, in the order listed, turns the counts into offsets and slot n into the total, payload() allocates from
+// the totals and pass(true) launches the same kernels to FILL.
+struct CountedPtr { uint64_t *ptr, *total; };
+template <class Pass, class Payload>
+static inline cellector_status count_scan_fill(cellector_ctx *c, uint64_t n, std::initializer_list<CountedPtr> a, Pass pass,
+                                               Payload payload)
+{
+    pass(std::false_type());
+    HIPCHK(c, hipGetLastError());
+    for (const CountedPtr &p : a) CHK(dev_exclusive_scan_u64(c, p.ptr, n + 1, p.total));
+    CHK(payload());
+    pass(std::true_type());
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
