@@ -1256,15 +1256,43 @@ cellector_status cellector_cell_log_likelihoods(cellector_ctx *c, const double *
     c->tables_prebuilt = false;  // this pass overwrites alpha/beta and the tables
     c->work_zeroed = false;
     CHK(launch_ab_from_host(c, alpha, beta, mask));
-    // the tiled engine derives the used-locus count from the ctx's own mask; with a caller mask use the CSR kernel
-    if (c->engine == 2 && !mask && c->n_masked_loci == 0) CHK(tiled_cell_pass(c, c->ab, nullptr, false));
-    else CHK(launch_cell_ll(c, c->ab, nullptr));
+    // the tiled engine subtracts every cell's entries at masked loci from its used-locus count: the counts of THIS call's mask
+    // go into scratch (the ctx's own masked_cnt belongs to the loop's mask and stays)
+    if (c->engine == 2) {
+        DevBuf<uint32_t> cnt;
+        CHK(dev_alloc(c, &cnt, c->nloc));
+        CHK(tiled_call_masked_count(c, mask, cnt.get()));
+        CHK(tiled_cell_pass(c, c->ab, nullptr, false, cnt.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (the scratch goes)
+    } else CHK(launch_cell_ll(c, c->ab, nullptr));
     const size_t b = c->nloc * 8;
     if (ll) CHK(d2h(c, ll, c->ll, b));
     if (ell) CHK(d2h(c, ell, c->ell, b));
     if (nl) CHK(d2h(c, nl, c->nloci, b));
     if (c->timing) timer_collect(c);
     return CELLECTOR_OK;
+}
+
+// PMFData (main.rs:527-539) of listed cells: kernels_pmfs.hip
+cellector_status cellector_cell_pmfs(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
+                                     uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt,
+                                     uint32_t *ref, double *log_pmf, double *expected_log_pmf, double *expected_log_variance)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi)
+        return multi_cell_pmfs(c, alpha, beta, mask, cells, n_cells, rec_ptr, capacity, locus_index, alt, ref, log_pmf, expected_log_pmf,
+                               expected_log_variance);
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "cell_pmfs: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, (alpha && beta) || c->L == 0, "cell_pmfs: null alpha/beta");
+    REQUIRE(c, rec_ptr && (cells || n_cells == 0), "cell_pmfs: null rec_ptr or cell list");
+    for (uint64_t j = 0; j < n_cells; j++)  // every id before anything is written or launched
+        if (cells[j] >= c->nloc)
+            return ctx_fail(c, CELLECTOR_EINVAL, "cell_pmfs: cell id %u (list position %llu) out of range: %llu cells", cells[j],
+                            (unsigned long long)j, (unsigned long long)c->nloc);
+    SETDEV(c);
+    return pmfs_run(c, alpha, beta, mask, cells, n_cells, rec_ptr, capacity, locus_index, alt, ref, log_pmf, expected_log_pmf,
+                    expected_log_variance);
 }
 
 // ---- posteriors ---------------------------------------------------------------------------------------
@@ -1280,6 +1308,32 @@ static PosteriorPriors posterior_priors(const cellector_ctx *c)
     p.lp_min = std::log(mf);                                              // main.rs:264-265
     p.lp_maj = std::log(1.0 - mf);
     return p;
+}
+
+cellector_status cellector_posterior_alpha_betas(cellector_ctx *c, int which, double *alpha, double *beta)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) {  // per-locus state is replicated: shard 0 answers
+        cellector_ctx *s0 = multi_shard0(c);
+        const cellector_status st = cellector_posterior_alpha_betas(s0, which, alpha, beta);
+        if (st != CELLECTOR_OK) c->err = s0->err;
+        return st;
+    }
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "posterior_alpha_betas: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, which >= 0 && which <= 2, "posterior_alpha_betas: which is 0 (minority), 1 (majority) or 2 (doublet)");
+    SETDEV(c);
+    const uint64_t L = c->L;
+    DevBuf<double> ab6;  // the kernel's [8 L] layout: min, maj, dbl pairs and a pad per locus
+    CHK(dev_alloc(c, &ab6, 8 * L));
+    CHK(launch_ab_posterior_into(c, posterior_priors(c).mf0, ab6.get()));
+    std::vector<double> h(8 * L);
+    CHK(d2h(c, h.data(), ab6, 8 * L * sizeof(double)));
+    for (uint64_t l = 0; l < L; l++) {
+        if (alpha) alpha[l] = h[8 * l + 2 * (uint64_t)which];
+        if (beta) beta[l] = h[8 * l + 2 * (uint64_t)which + 1];
+    }
+    return CELLECTOR_OK;
 }
 
 // the posterior phase of a single-device ctx; sdbl (device, [nloc] or null): the doublet set's per-cell sums as well

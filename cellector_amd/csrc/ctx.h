@@ -405,6 +405,11 @@ cellector_status launch_ab_from_host(cellector_ctx *c, const double *alpha, cons
 // sdbl: [nloc] or null — the doublet set's per-cell sums as well (option resolve_posteriors' mark kernel reads them)
 cellector_status launch_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj,
                                    double lp_dbl, double *sdbl);
+cellector_status launch_ab_posterior_into(cellector_ctx *c, double mf0, double *ab6 /*[8 L] device scratch*/);
+// cellector_cell_pmfs on one device (kernels_pmfs.hip): validated ids; scratch of its own, the ctx's state stays
+cellector_status pmfs_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
+                          uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt, uint32_t *ref,
+                          double *log_pmf, double *expected_log_pmf, double *expected_log_variance);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);
@@ -446,11 +451,14 @@ cellector_status dev_sort_pairs_u32_u64(cellector_ctx *c, uint32_t *keys_in, uin
                                         uint64_t *vals_in, uint64_t *vals_out, uint64_t n, int end_bit);
 // engine v2 (kernels_tiled_build.hip, once per ingest; then kernels_tiled.hip)
 cellector_status tiled_build(cellector_ctx *c);
-cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em);
+// masked_cnt: [nloc] entries of every cell at the pass' masked loci; null = the ctx's own (the loop's mask)
+cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em, const uint32_t *masked_cnt = nullptr);
 cellector_status tiled_locus_pass(cellector_ctx *c);
 cellector_status tiled_masked_update(cellector_ctx *c);
 // masked_cnt from scratch under c->mask (cellector_set_loci_mask); ones: [L] device scratch, allocated before the mask was written
 cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones);
+// ... under the mask of one call, into the caller's scratch cnt [nloc] (host_mask [L] or null = all used); the ctx's own stay
+cellector_status tiled_call_masked_count(cellector_ctx *c, const uint8_t *host_mask, uint32_t *cnt);
 cellector_status tiled_prebuild_tables(cellector_ctx *c);
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl);
 // device-side mtx text parse (kernels_parse.hip)

@@ -152,3 +152,110 @@ __device__ inline double dm_expected_log_pmf_ref(const double *lf, double alpha,
     for (uint32_t k = 1; k <= n; ++k) e = dm_logsumexp(e, 2.0 * dm_log_bb_pmf_ref(lf, alpha, beta, k, n - k));
     return e;
 }
+
+// ---- the per-entry moments of PMFData (main.rs:527-539; cellector_cell_pmfs) ------------------------------------------------
+// expected_log_beta_binomial_pmf (stats.rs:8-33) returns two numbers for (alpha, beta, n): the expected term E = ln sum_k pmf(k)^2
+// above, and the "variance" of stats.rs:23-28, which centres on that E (quirk Q7), not on a mean:
+//
+//   V = sum_k pmf(k) (ln pmf(k) - E)^2
+//
+// ln pmf(k) has to stay finite where pmf(k) underflows (the reference holds the log-pmfs themselves, so such a term adds 0):
+// a term whose pmf is zero in f64 is skipped.
+// Totals up to DM_MOM_SMALL: the ratio recurrence from pmf(0), the arithmetic of dm_expected_log_pmf's short form (the same bits
+// for n <= DM_CHUNK), run once for E and once more for V.
+#define DM_MOM_SMALL 17
+__device__ __forceinline__ double dm_pmf_step_up(double alpha, double beta, uint32_t n, uint32_t k)  // pmf(k+1) / pmf(k)
+{
+    return ((double)(n - k) * (alpha + (double)k)) / ((double)(k + 1) * (beta + (double)(n - k - 1)));
+}
+__device__ __forceinline__ double dm_pmf_step_down(double alpha, double beta, uint32_t n, uint32_t k)  // pmf(k-1) / pmf(k)
+{
+    return ((double)k * (beta + (double)(n - k))) / ((double)(n - k + 1) * (alpha + (double)(k - 1)));
+}
+__device__ inline void dm_pmf_moments_small(double alpha, double beta, uint32_t n, bool want_v, double *e_out, double *v_out)
+{
+    const double ab = alpha + beta;
+    double num = 1.0, den = 1.0;
+    for (uint32_t j = 0; j < n; ++j) {
+        num *= beta + (double)j;
+        den *= ab + (double)j;
+    }
+    const double p0 = num / den;
+    double p = p0;
+    double s = p * p;
+    for (uint32_t k = 0; k < n; ++k) {
+        p *= dm_pmf_step_up(alpha, beta, n, k);
+        s += p * p;
+    }
+    const double e = log(s);
+    *e_out = e;
+    if (!want_v) return;
+    double v = 0.0;
+    p = p0;
+    for (uint32_t k = 0;; ++k) {
+        if (p > 0.0) {
+            const double d = log(p) - e;
+            v += p * (d * d);
+        }
+        if (k == n) break;
+        p *= dm_pmf_step_up(alpha, beta, n, k);
+    }
+    *v_out = v;
+}
+
+__device__ __forceinline__ double wave_all_sum(double v) { return __shfl(wave_sum(v), 0, 64); }
+
+// Larger totals, by ALL 64 lanes of a wave for ONE entry (every lane calls it with the same arguments; `lane` is its own):
+// the pmfs relative to the one at k* = round(n alpha / (alpha + beta)), t_k = pmf(k) / pmf(k*), by the ratio recurrence upwards
+// and downwards from k* (engine 2's form of the expected term for these totals: no t_k overflows, one that underflows belongs
+// to a term that adds nothing).  Each direction's steps are cut into 64 contiguous segments; a lane multiplies its segment's
+// ratios, the exclusive prefix product over the lanes gives the t its segment starts from, and it walks the segment again:
+//   E = ln(sum_k t_k^2) + 2 ln pmf(k*),   ln pmf(k) - E = ln t_k - (ln sum t^2 + ln pmf(k*)),   V = pmf(k*) sum_k t_k (...)^2
+// so a total of 65535 is 1024 steps per lane and pass instead of 65535 on one lane with 63 waiting.
+__device__ inline void dm_pmf_moments_wave(const double *lf, double alpha, double beta, uint32_t n, int lane, bool want_v,
+                                           double *e_out, double *v_out)
+{
+    uint32_t ks = (uint32_t)((double)n * alpha / (alpha + beta) + 0.5);
+    if (!(ks <= n)) ks = n;
+    const double lstar = dm_log_bb_pmf(lf, alpha, beta, ks, n - ks);
+    double start[2], s2 = 0.0;
+    uint32_t lo[2], hi[2];
+#pragma unroll
+    for (int dir = 0; dir < 2; dir++) {  // 0: k* + 1 .. n, 1: k* - 1 .. 0; step m of a direction starts at k* +- m
+        const uint32_t cnt = dir == 0 ? n - ks : ks, seg = (cnt + 63u) / 64u;
+        lo[dir] = min(cnt, (uint32_t)lane * seg);
+        hi[dir] = min(cnt, lo[dir] + seg);
+        double prod = 1.0;
+        for (uint32_t m = lo[dir]; m < hi[dir]; ++m)
+            prod *= dir == 0 ? dm_pmf_step_up(alpha, beta, n, ks + m) : dm_pmf_step_down(alpha, beta, n, ks - m);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double o = __shfl_up(prod, off, 64);
+            if (lane >= off) prod *= o;
+        }
+        const double before = __shfl_up(prod, 1, 64);
+        start[dir] = lane == 0 ? 1.0 : before;
+        double t = start[dir];
+        for (uint32_t m = lo[dir]; m < hi[dir]; ++m) {
+            t *= dir == 0 ? dm_pmf_step_up(alpha, beta, n, ks + m) : dm_pmf_step_down(alpha, beta, n, ks - m);
+            s2 += t * t;
+        }
+    }
+    const double ln_s = log(1.0 + wave_all_sum(s2));
+    *e_out = ln_s + 2.0 * lstar;
+    if (!want_v) return;
+    const double c = ln_s + lstar;
+    double v = 0.0;
+#pragma unroll
+    for (int dir = 0; dir < 2; dir++) {
+        double t = start[dir];
+        for (uint32_t m = lo[dir]; m < hi[dir]; ++m) {
+            t *= dir == 0 ? dm_pmf_step_up(alpha, beta, n, ks + m) : dm_pmf_step_down(alpha, beta, n, ks - m);
+            if (t > 0.0) {
+                const double d = log(t) - c;
+                v += t * (d * d);
+            }
+        }
+    }
+    *v_out = exp(lstar) * (c * c + wave_all_sum(v));
+}

@@ -490,6 +490,17 @@ cellector_status launch_iter_summary(cellector_ctx *c)
     return CELLECTOR_OK;
 }
 
+// the posterior phase's first kernel alone, into the caller's scratch of [8 L] (cellector_posterior_alpha_betas); c->ab6 stays
+cellector_status launch_ab_posterior_into(cellector_ctx *c, double mf0, double *ab6)
+{
+    const uint64_t L = c->L;
+    if (L)
+        hipLaunchKernelGGL(k_ab_posterior, dim3(grid_for(L, 256)), dim3(256), 0, c->stream, L, c->s_alt, c->s_ref,
+                           c->x_locus + LB_ALT_MIN * L, c->x_locus + LB_REF_MIN * L, mf0, ab6);
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
+
 cellector_status launch_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl)
 {
     const uint64_t L = c->L;

@@ -1852,7 +1852,7 @@ static cellector_status cell_pass_launch(cellector_ctx *c, const double2 *ab, bo
     return CELLECTOR_OK;
 }
 
-cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em)
+cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *norm_out, bool for_em, const uint32_t *masked_cnt)
 {
     if (c->nloc == 0) return CELLECTOR_OK;
     const bool ovf = have_overflow(c);
@@ -1870,7 +1870,7 @@ cellector_status tiled_cell_pass(cellector_ctx *c, const double2 *ab, double *no
     const unsigned grid = gcap((c->nloc + 1) / 2, 256, 0x7fffffffu);
     with_bool(c->compute_expected, [&](auto E) {
         hipLaunchKernelGGL(k_cell_finalize<E.value>, dim3(grid), dim3(256), 0, c->stream, c->nloc, c->t_groups, c->t_npad, part_ll,
-                           part_ell, o_ll, o_ell, c->csr_ptr, c->masked_cnt, c->ll, c->ell, c->nloci, norm_out);
+                           part_ell, o_ll, o_ell, c->csr_ptr, masked_cnt ? masked_cnt : c->masked_cnt.get(), c->ll, c->ell, c->nloci, norm_out);
     });
     timer_end(c, CELLECTOR_K_CELL_LL);
     HIPCHK(c, hipGetLastError());
@@ -1978,12 +1978,12 @@ cellector_status tiled_prebuild_tables(cellector_ctx *c)
     return CELLECTOR_OK;
 }
 
-// masked_cnt += the entries of the loci that mask_old has and mask_new has not
-static cellector_status launch_masked_update(cellector_ctx *c, const uint8_t *mask_old, const uint8_t *mask_new)
+// target += the entries of the loci that mask_old has and mask_new has not
+static cellector_status launch_masked_update(cellector_ctx *c, const uint8_t *mask_old, const uint8_t *mask_new, uint32_t *target)
 {
     with_bool(c->c4_bits == 24, [&](auto NARROW) {
         hipLaunchKernelGGL(k_masked_update<NARROW.value ? 24 : 32>, dim3(gcap(c->L, 4)), dim3(256), 0, c->stream, c->L, mask_old, mask_new,
-                           c->c4_ptr, c->c4_ent, c->ovc_ptr, c->ovc_ent, c->masked_cnt);
+                           c->c4_ptr, c->c4_ent, c->ovc_ptr, c->ovc_ent, target);
     });
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
@@ -1993,7 +1993,7 @@ static cellector_status launch_masked_update(cellector_ctx *c, const uint8_t *ma
 cellector_status tiled_masked_update(cellector_ctx *c)
 {
     if (c->L == 0) return CELLECTOR_OK;
-    return launch_masked_update(c, c->mask, c->mask_next);
+    return launch_masked_update(c, c->mask, c->mask_next, c->masked_cnt);
 }
 
 // a caller's mask (cellector_set_loci_mask): the counts from scratch — zeroed, then one update from an all-ones "old" mask to c->mask
@@ -2002,7 +2002,23 @@ cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones)
     HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (c->nloc ? c->nloc : 1) * 4, c->stream));
     if (c->L == 0 || c->nloc == 0) return CELLECTOR_OK;
     HIPCHK(c, hipMemsetAsync(ones, 1, c->L, c->stream));
-    return launch_masked_update(c, ones, c->mask);
+    return launch_masked_update(c, ones, c->mask, c->masked_cnt);
+}
+
+// the counts under the mask of ONE call (cellector_cell_log_likelihoods): cnt [nloc] is the caller's scratch, host_mask [L] or
+// null = all used.  The ctx's own masked_cnt, mask and n_masked_loci are not touched.  Complete on return.
+cellector_status tiled_call_masked_count(cellector_ctx *c, const uint8_t *host_mask, uint32_t *cnt)
+{
+    HIPCHK(c, hipMemsetAsync(cnt, 0, (c->nloc ? c->nloc : 1) * 4, c->stream));
+    if (!host_mask || c->L == 0 || c->nloc == 0) return CELLECTOR_OK;
+    DevBuf<uint8_t> ones, m;
+    CHK(dev_alloc(c, &ones, c->L));
+    CHK(dev_alloc(c, &m, c->L));
+    HIPCHK(c, hipMemsetAsync(ones, 1, c->L, c->stream));
+    HIPCHK(c, hipMemcpyAsync(m, host_mask, c->L, hipMemcpyHostToDevice, c->stream));
+    CHK(launch_masked_update(c, ones, m, cnt));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the two scratch masks go)
+    return CELLECTOR_OK;
 }
 
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl)

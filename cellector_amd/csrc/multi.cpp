@@ -431,6 +431,76 @@ cellector_status multi_cell_log_likelihoods(cellector_ctx *root, const double *a
         return cellector_cell_log_likelihoods(s, alpha, beta, mask, ll ? ll + b : nullptr, ell ? ell + b : nullptr, nl ? nl + b : nullptr);
     });
 }
+// The list is routed to the owning shards (global ids made local, list order kept inside a shard); every shard counts, the
+// counts give rec_ptr in list order, every shard fills arrays of its own and its cells' records are copied to their places.
+cellector_status multi_cell_pmfs(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
+                                 uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt, uint32_t *ref,
+                                 double *log_pmf, double *expected_log_pmf, double *expected_log_variance)
+{
+    const auto &sh = root->multi->shards;
+    const size_t S = sh.size();
+    if (!rec_ptr || (!cells && n_cells)) return ctx_fail(root, CELLECTOR_EINVAL, "cell_pmfs: null rec_ptr or cell list");
+    const uint64_t N = sh[0]->total_cells;
+    for (uint64_t j = 0; j < n_cells; j++)
+        if (cells[j] >= N)
+            return ctx_fail(root, CELLECTOR_EINVAL, "cell_pmfs: cell id %u (list position %llu) out of range: %llu cells", cells[j],
+                            (unsigned long long)j, (unsigned long long)N);
+    try {
+        std::vector<std::vector<uint32_t>> ids(S);
+        std::vector<std::vector<uint64_t>> at(S), rp(S);
+        for (uint64_t j = 0; j < n_cells; j++)
+            for (size_t r = 0; r < S; r++)
+                if (cells[j] >= sh[r]->cell_begin && cells[j] < sh[r]->cell_end) {
+                    ids[r].push_back((uint32_t)(cells[j] - sh[r]->cell_begin));
+                    at[r].push_back(j);
+                    break;
+                }
+        for (size_t r = 0; r < S; r++) rp[r].assign(ids[r].size() + 1, 0);
+        cellector_status st = run_all(root, [&](cellector_ctx *s, int r) {
+            return cellector_cell_pmfs(s, alpha, beta, mask, ids[(size_t)r].data(), ids[(size_t)r].size(), rp[(size_t)r].data(), 0, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr);
+        });
+        if (st != CELLECTOR_OK) return st;
+        rec_ptr[0] = 0;
+        for (size_t r = 0; r < S; r++)
+            for (size_t q = 0; q < at[r].size(); q++) rec_ptr[at[r][q] + 1] = rp[r][q + 1] - rp[r][q];
+        for (uint64_t j = 0; j < n_cells; j++) rec_ptr[j + 1] += rec_ptr[j];
+        if (!locus_index && !alt && !ref && !log_pmf && !expected_log_pmf && !expected_log_variance) return CELLECTOR_OK;
+        if (capacity < rec_ptr[n_cells])
+            return ctx_fail(root, CELLECTOR_EINVAL, "cell_pmfs: capacity %llu is below the %llu records of the list",
+                            (unsigned long long)capacity, (unsigned long long)rec_ptr[n_cells]);
+        std::vector<std::vector<uint32_t>> u[3];
+        std::vector<std::vector<double>> f[3];
+        uint32_t *const o_u[3] = {locus_index, alt, ref};
+        double *const o_f[3] = {log_pmf, expected_log_pmf, expected_log_variance};
+        for (int i = 0; i < 3; i++) {
+            u[i].resize(S);
+            f[i].resize(S);
+            for (size_t r = 0; r < S; r++) {
+                if (o_u[i]) u[i][r].resize(rp[r].back());
+                if (o_f[i]) f[i][r].resize(rp[r].back());
+            }
+        }
+        st = run_all(root, [&](cellector_ctx *s, int rr) {
+            const size_t r = (size_t)rr;
+            return cellector_cell_pmfs(s, alpha, beta, mask, ids[r].data(), ids[r].size(), rp[r].data(), rp[r].back(),
+                                       o_u[0] ? u[0][r].data() : nullptr, o_u[1] ? u[1][r].data() : nullptr, o_u[2] ? u[2][r].data() : nullptr,
+                                       o_f[0] ? f[0][r].data() : nullptr, o_f[1] ? f[1][r].data() : nullptr, o_f[2] ? f[2][r].data() : nullptr);
+        });
+        if (st != CELLECTOR_OK) return st;
+        for (size_t r = 0; r < S; r++)
+            for (size_t q = 0; q < at[r].size(); q++) {
+                const uint64_t src = rp[r][q], n = rp[r][q + 1] - src, dst = rec_ptr[at[r][q]];
+                for (int i = 0; i < 3; i++) {
+                    if (o_u[i]) std::copy_n(u[i][r].data() + src, n, o_u[i] + dst);
+                    if (o_f[i]) std::copy_n(f[i][r].data() + src, n, o_f[i] + dst);
+                }
+            }
+    } catch (const std::bad_alloc &) {
+        return ctx_fail(root, CELLECTOR_ENOMEM, "cell_pmfs: the list's records do not fit in host memory");
+    }
+    return CELLECTOR_OK;
+}
 cellector_status multi_posteriors(cellector_ctx *root, double *posterior, double *doublet, double *ll_maj, double *ll_min)
 {
     return per_cell(root, [=](cellector_ctx *s, uint64_t b) {

@@ -20,6 +20,9 @@ cellector_status multi_excluded(const cellector_ctx *root, uint8_t *out);
 cellector_status multi_iter_cell_outputs(const cellector_ctx *root, double *ll, double *ell, double *nl, double *norm);
 cellector_status multi_cell_log_likelihoods(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask,
                                             double *ll, double *ell, double *nl);
+cellector_status multi_cell_pmfs(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
+                                 uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt, uint32_t *ref,
+                                 double *log_pmf, double *expected_log_pmf, double *expected_log_variance);
 cellector_status multi_posteriors(cellector_ctx *root, double *posterior, double *doublet, double *ll_maj, double *ll_min);
 cellector_status multi_csr_rows(const cellector_ctx *root, uint64_t rb, uint64_t re, uint64_t *row_ptr, uint64_t *entries, uint64_t capacity);
 cellector_status multi_em_iteration(cellector_ctx *root, double iqr_multiple, cellector_iter_summary *out);

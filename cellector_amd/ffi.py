@@ -61,6 +61,8 @@ SIGNATURES = {
     "cellector_excluded": (_i, [_vp, _vp]),
     "cellector_alpha_betas": (_i, [_vp, _vp, _vp]),
     "cellector_cell_log_likelihoods": (_i, [_vp] + [_vp] * 6),
+    "cellector_cell_pmfs": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64] + [_vp] * 6),
+    "cellector_posterior_alpha_betas": (_i, [_vp, _i, _vp, _vp]),
     "cellector_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
@@ -379,6 +381,39 @@ class Cellector:
         ll, ell, nl = (np.empty(n, np.float64) for _ in range(3))
         self._ck(self._lib.cellector_cell_log_likelihoods(self.h, _p(alpha), _p(beta), _p(mask), _p(ll), _p(ell), _p(nl)))
         return ll, ell, nl
+
+    def cell_pmfs(self, cells, alpha=None, beta=None, mask=None):
+        """The reference's PMFData of the listed cells (cellector_cell_pmfs): one record per entry at a used locus, cells in
+        list order, entries in the by-cell CSR's order.  alpha / beta / mask default to alpha_betas() and loci_mask(), i.e. the
+        records the next em_begin would produce.  Returns a dict of arrays: rec_ptr [len(cells) + 1], then locus_index, alt,
+        ref, log_pmf, expected_log_pmf, expected_log_variance of rec_ptr[-1] records each."""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
+        if alpha is None or beta is None:
+            a0, b0 = self.alpha_betas()
+            alpha = a0 if alpha is None else alpha
+            beta = b0 if beta is None else beta
+            mask = self.loci_mask() if mask is None else mask
+        alpha = np.ascontiguousarray(alpha, np.float64)
+        beta = np.ascontiguousarray(beta, np.float64)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        rp = np.zeros(len(cells) + 1, np.uint64)
+        head = (self.h, _p(alpha), _p(beta), _p(mask), _p(cells), len(cells), _p(rp))
+        self._ck(self._lib.cellector_cell_pmfs(*head, 0, None, None, None, None, None, None))
+        n = int(rp[-1])
+        ints = [np.zeros(n, np.uint32) for _ in range(3)]
+        flts = [np.zeros(n, np.float64) for _ in range(3)]
+        if n:
+            self._ck(self._lib.cellector_cell_pmfs(*head, n, *[_p(a) for a in ints + flts]))
+        keys = ["locus_index", "alt", "ref", "log_pmf", "expected_log_pmf", "expected_log_variance"]
+        return dict(rec_ptr=rp, **dict(zip(keys, ints + flts)))
+
+    def posterior_alpha_betas(self, which):
+        """(alpha, beta) of calculate_posteriors' distribution `which` for the current exclusion set: 0 minority, 1 majority,
+        2 doublet (cellector_posterior_alpha_betas)"""
+        L = self.dims().loci_used
+        a, b = np.empty(L, np.float64), np.empty(L, np.float64)
+        self._ck(self._lib.cellector_posterior_alpha_betas(self.h, int(which), _p(a), _p(b)))
+        return a, b
 
     def posteriors(self, fetch=True):
         if not fetch:  # (the phase on the device only: benchmarks)

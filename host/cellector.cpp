@@ -174,6 +174,7 @@ struct Params {
     bool resolve_near_ties = false;                    // extension: option resolve_ties (single GPU)
     int resolve_assignments = 0;                       // extension: options resolve_ties + resolve_posteriors = 1 (true) / 2 (all)
     std::optional<std::string> initial_minority;       // extension: barcodes of the initial exclusion set (main.rs:37 starts from none)
+    std::optional<std::string> cell_detail;            // extension: barcodes whose per-locus records go to cell_detail.tsv (main.rs:176's TODO)
 };
 
 const char *USAGE =
@@ -208,7 +209,13 @@ const char *USAGE =
     "        --initial_minority <file>                                      start the loop from these cells as the excluded (minority) set\n"
     "                                                                       instead of the empty set: one barcode per line, first tab-separated\n"
     "                                                                       column (a filtered cellector_assignments.tsv works), blank lines\n"
-    "                                                                       ignored (not in the reference)\n";
+    "                                                                       ignored (not in the reference)\n"
+    "        --cell_detail <file>                                               write <output_directory>/cell_detail.tsv: one row per matrix entry of\n"
+    "                                                                       each listed cell with its log-pmf, expected log-pmf and variance\n"
+    "                                                                       under the final alpha / beta and its log-pmf under the minority,\n"
+    "                                                                       majority and doublet distributions of the posterior; one barcode\n"
+    "                                                                       per line, first tab-separated column, blank lines ignored (not in\n"
+    "                                                                       the reference)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -233,7 +240,7 @@ Params load_params(int argc, char **argv)
     static const char *known[] = {"output_directory", "ref", "alt", "barcodes", "min_alt", "min_ref", "ground_truth",
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
-                                  "resolve_near_ties", "resolve_assignments", "initial_minority"};
+                                  "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -292,6 +299,7 @@ Params load_params(int argc, char **argv)
         p.resolve_assignments = v == "true" ? 1 : (v == "all" ? 2 : 0);
     }
     if (got.count("initial_minority")) p.initial_minority = got["initial_minority"];
+    if (got.count("cell_detail")) p.cell_detail = got["cell_detail"];
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_assignments " + got["resolve_assignments"] +
                    "' works on one GPU and cannot be used with '--devices <a,b,...>'");
@@ -411,21 +419,28 @@ int main(int argc, char **argv)
         }
     }
 
-    // --initial_minority: the cells the loop starts from as excluded_cells (main.rs:37 has `HashSet::new()`)
-    std::vector<uint32_t> initial_minority;
-    if (params.initial_minority) {
-        Lines in(*params.initial_minority);
+    // a barcode list of an extension flag: one per line, first tab-separated column, blank lines ignored; file order, repeats kept
+    auto read_barcode_list = [&](const char *flag, const std::string &path) {
+        std::vector<uint32_t> cells;
+        Lines in(path);
         std::string line;
         for (size_t line_no = 1; in.next(line); line_no++) {
             const std::string bc = line.substr(0, line.find('\t'));
             if (bc.empty()) continue;
             const size_t cell = barcode_to_cell(bc);
             if (cell == SIZE_MAX)
-                die(1, "error: --initial_minority " + *params.initial_minority + " line " + std::to_string(line_no) + ": barcode '" + bc +
+                die(1, std::string("error: --") + flag + " " + path + " line " + std::to_string(line_no) + ": barcode '" + bc +
                            "' is not in the barcodes file " + params.barcodes);
-            initial_minority.push_back((uint32_t)cell);
+            cells.push_back((uint32_t)cell);
         }
-    }
+        return cells;
+    };
+    // --initial_minority: the cells the loop starts from as excluded_cells (main.rs:37 has `HashSet::new()`)
+    std::vector<uint32_t> initial_minority;
+    if (params.initial_minority) initial_minority = read_barcode_list("initial_minority", *params.initial_minority);
+    // --cell_detail: the cells whose per-locus records are written after the posterior phase
+    std::vector<uint32_t> detail_cells;
+    if (params.cell_detail) detail_cells = read_barcode_list("cell_detail", *params.cell_detail);
 
     // CELLECTOR_TIMING=1: phase wall times on stderr (not part of the reference's output)
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;
@@ -655,6 +670,58 @@ int main(int argc, char **argv)
     }
 
     lap("final tallies + cellector.vcf");
+    // --cell_detail (main.rs:176: "TODO add detailed output for incorrectly assigned cells"): the PMFData of the listed cells
+    // (main.rs:527-539) at every locus of the matrix — under the alpha / beta the loop ended with, `used` = the final loci
+    // mask, the three value columns "na" at a locus the filter masked — and each entry's log-pmf under the three distributions
+    // of calculate_posteriors, whose mask is all-true (main.rs:303).  Cells in file order, entries in the by-cell CSR's order.
+    if (params.cell_detail) {
+        for (const uint32_t cell : detail_cells)
+            if (cell >= N)
+                die(1, "error: --cell_detail: barcode '" + std::string(barcodes[cell]) + "' is line " + std::to_string(cell + 1) +
+                           " of the barcodes file but the matrix has " + std::to_string(N) + " cells");
+        if (params.vcf)
+            for (uint64_t l = 0; l < L; l++)
+                if (locus_ids[l] >= vcf_data.size()) die(EXIT_PANIC, "index out of bounds: vcf has fewer records than loci");
+        std::vector<uint8_t> used(L);
+        std::vector<double> alpha(L), beta(L), pa(L), pb(L);
+        g.ck(cellector_loci_mask(g.c, used.data()), "loci_mask");
+        g.ck(cellector_alpha_betas(g.c, alpha.data(), beta.data()), "alpha_betas");
+        const uint64_t nc = detail_cells.size();
+        std::vector<uint64_t> rec_ptr(nc + 1, 0);
+        g.ck(cellector_cell_pmfs(g.c, alpha.data(), beta.data(), nullptr, detail_cells.data(), nc, rec_ptr.data(), 0, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr), "cell_detail");
+        const uint64_t nr = rec_ptr[nc];
+        std::vector<uint32_t> li(nr), alt(nr), ref(nr);
+        std::vector<double> lp(nr), elp(nr), var(nr), lp3[3];
+        g.ck(cellector_cell_pmfs(g.c, alpha.data(), beta.data(), nullptr, detail_cells.data(), nc, rec_ptr.data(), nr, li.data(), alt.data(),
+                                 ref.data(), lp.data(), elp.data(), var.data()), "cell_detail");
+        for (int w = 0; w < 3; w++) {
+            lp3[w].resize(nr);
+            g.ck(cellector_posterior_alpha_betas(g.c, w, pa.data(), pb.data()), "posterior_alpha_betas");
+            g.ck(cellector_cell_pmfs(g.c, pa.data(), pb.data(), nullptr, detail_cells.data(), nc, rec_ptr.data(), nr, nullptr, nullptr, nullptr,
+                                     lp3[w].data(), nullptr, nullptr), "cell_detail");
+        }
+        std::vector<uint32_t> cell_of(nr);
+        for (uint64_t j = 0; j < nc; j++)
+            for (uint64_t i = rec_ptr[j]; i < rec_ptr[j + 1]; i++) cell_of[i] = detail_cells[j];
+        FILE *f = create(od + "/cell_detail.tsv");
+        fputs("cell_id\tbarcode\tlocus_id\tchrom\tpos\talt\tref\tused\talpha\tbeta\tlog_pmf\texpected_log_pmf\texpected_log_variance\t"
+              "minority_log_pmf\tmajority_log_pmf\tdoublet_log_pmf\n", f);
+        write_rows(f, nr, [&](uint64_t i, std::string &o) {
+            const uint32_t c = cell_of[i], l = li[i];
+            put(o, (uint64_t)c); o += '\t'; o += barcodes[c]; o += '\t'; put(o, locus_ids[l]); o += '\t';
+            if (params.vcf) { o += vcf_data[locus_ids[l]].chrom; o += '\t'; o += vcf_data[locus_ids[l]].pos; }
+            else o += "na\tna";
+            o += '\t'; put(o, (uint64_t)alt[i]); o += '\t'; put(o, (uint64_t)ref[i]); o += '\t'; o += used[l] ? '1' : '0';
+            o += '\t'; put(o, alpha[l]); o += '\t'; put(o, beta[l]);
+            if (used[l]) { o += '\t'; put(o, lp[i]); o += '\t'; put(o, elp[i]); o += '\t'; put(o, var[i]); }
+            else o += "\tna\tna\tna";
+            for (int w = 0; w < 3; w++) { o += '\t'; put(o, lp3[w][i]); }
+            o += '\n';
+        });
+        fclose(f);
+        lap("cell_detail.tsv");
+    }
     // output_final_assignments (main.rs:133-174)
     std::map<std::string, std::map<std::string, uint64_t>> assignment_gt_counts;
     std::map<std::string, uint64_t> gt_counts;

@@ -318,13 +318,51 @@ cellector_status cellector_excluded(const cellector_ctx *ctx, uint8_t *out /*[lo
 /* alpha/beta that the NEXT em_begin will use = init_alpha_betas(current excluded), main.rs:598 */
 cellector_status cellector_alpha_betas(const cellector_ctx *ctx, double *alpha, double *beta /*[L]*/);
 
-/* get_cell_log_likelihoods (main.rs:541-591) alone under caller alpha/beta/mask (host arrays). */
+/* get_cell_log_likelihoods (main.rs:541-591) alone under caller alpha/beta/mask (host arrays).  Engine 2 runs its tile pass
+ * whatever the mask: the per-cell counts of entries at the CALL's masked loci are formed in scratch for the call, the ctx's
+ * own mask and counts (the loop's, cellector_set_loci_mask's) are left as they are.  Engine 1 runs the CSR kernel. */
 cellector_status cellector_cell_log_likelihoods(cellector_ctx *ctx, const double *alpha,
                                                 const double *beta, const uint8_t *mask /*[L] or NULL*/,
                                                 double *ll, double *expected_ll,
                                                 double *loci_used_per_cell /*[local cells]*/);
 
+/* ---- the per-entry records behind those sums ---------------------------------------------------
+ * PMFData (main.rs:527-539) of the listed cells under caller alpha/beta/mask: what get_cell_log_likelihoods pushes into
+ * all_pmfs (main.rs:556-575), i.e. one record per entry at a USED locus, none at a masked one.  The arguments are those of
+ * cellector_cell_log_likelihoods plus a cell list.
+ *   rec_ptr is required and always written: rec_ptr[0] = 0, rec_ptr[j + 1] - rec_ptr[j] = the records of cells[j].  With all
+ *   six record pointers NULL the call only counts and capacity is ignored (the two-call pattern of cellector_csr_rows);
+ *   otherwise capacity >= rec_ptr[n_cells], else CELLECTOR_EINVAL with rec_ptr still valid.  A column whose pointer is NULL
+ *   is not computed.
+ *   Order: cells in the order of the list (a cell listed twice gets its records twice); inside a cell the by-cell CSR's row
+ *   order: ascending locus index, repeated (locus, cell) lines in file order.  For a locus-major (vartrix) file that is the
+ *   order of cell_loci_data; for any other file it is NOT file order.
+ *   The other PMFData fields are implied: cell_id by rec_ptr, alpha / beta = the caller's arrays at locus_index, locus =
+ *   cellector_locus_ids at locus_index, excluded = cellector_excluded.
+ *   Cell ids are local cell indices (global ones on a multi-device ctx, like cellector_assign; local ones on a ctx with a
+ *   communicator or a cellector_set_shard range).  Every id is checked before anything is written or launched: one out of
+ *   range gives CELLECTOR_EINVAL and the message names it.  n_cells == 0 is legal; an empty row or an all-masked mask gives
+ *   zero records.
+ *   Needs a loaded matrix and no iteration in flight; works on engines 1 and 2.  The call uses scratch of its own and leaves
+ *   the ctx exactly as it was; it runs on the ctx's stream and returns when the arrays are written.  Device scratch is
+ *   allocated for exactly the counted records; a list whose records do not fit fails with CELLECTOR_ENOMEM before the fill
+ *   pass is launched.
+ *   Values: log_pmf is the product form of the cell pass (it does not change with option ref_arith); expected_log_pmf is
+ *   ln sum_k pmf(k)^2 (stats.rs:19-22) by the ratio recurrence (totals up to 17 from pmf(0), above anchored at the mode);
+ *   expected_log_variance follows stats.rs:23-28 to the letter: sum_k pmf(k) (ln pmf(k) - expected_log_pmf)^2, centred on the
+ *   expected term, not on a mean.  A term whose pmf underflows adds 0.  An entry with alt + ref == 0 gives 0, 0, 0. */
+cellector_status cellector_cell_pmfs(cellector_ctx *ctx, const double *alpha, const double *beta /*[L]*/,
+                                     const uint8_t *mask /*[L] or NULL = all used*/,
+                                     const uint32_t *cells, uint64_t n_cells,
+                                     uint64_t *rec_ptr /*[n_cells + 1]*/, uint64_t capacity,
+                                     uint32_t *locus_index, uint32_t *alt, uint32_t *ref, double *log_pmf,
+                                     double *expected_log_pmf, double *expected_log_variance /*[capacity] each, any may be NULL*/);
+
 /* ---- calculate_posteriors (main.rs:228-280) with the current exclusion set -------------------- */
+/* the three distributions of calculate_posteriors for the current exclusion set (main.rs:239-254):
+ * which = 0 minority, 1 majority (scaled by max(minority_fraction, 0.01)), 2 doublet.  With cellector_cell_pmfs they give the
+ * per-locus log-likelihood ratio behind a cell's posterior.  Formed in scratch: the ctx is left as it was. */
+cellector_status cellector_posterior_alpha_betas(cellector_ctx *ctx, int which, double *alpha, double *beta /*[L]*/);
 cellector_status cellector_posteriors(cellector_ctx *ctx, double *posterior, double *doublet_posterior,
                                       double *ll_majority, double *ll_minority /*[local cells]*/);
 
