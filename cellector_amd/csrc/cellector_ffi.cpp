@@ -600,31 +600,22 @@ cellector_status cellector_ingest_coo(cellector_ctx *c, uint64_t total_loci, uin
     return CELLECTOR_OK;
 }
 
-// CELLECTOR_TIMING=1: phase wall times of the ingest on stderr
-static double lap_s(std::chrono::steady_clock::time_point *t)
-{
-    const auto now = std::chrono::steady_clock::now();
-    const double s = std::chrono::duration<double>(now - *t).count();
-    *t = now;
-    return s;
-}
-
 cellector_status cellector_ingest_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path)
 {
     if (!c) return CELLECTOR_EINVAL;
     if (c->multi) return multi_ingest_mtx(c, alt_path, ref_path);
     REQUIRE(c, alt_path && ref_path, "null path");
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr && c->comm.rank == 0;
-    auto t = std::chrono::steady_clock::now();
+    LapTimer t;
     MtxInput *in = nullptr;
     uint64_t tl = 0, tc = 0;
-    CHK(mtx_input_open(c, alt_path, ref_path, &in, &tl, &tc));
-    if (timing) fprintf(stderr, "[timing]   open / inflate          %8.3f s\n", lap_s(&t));
+    CHK(ctx_mtx_open(c, alt_path, ref_path, &in, &tl, &tc));
+    if (timing) fprintf(stderr, "[timing]   open / inflate          %8.3f s\n", t.lap());
     cellector_status s = begin_ingest(c, tl, tc);
     if (s == CELLECTOR_OK) s = ingest_stage_mtx_device(c, in);  // tokenised and converted on the GPU
     mtx_input_close(in);
     CHK(s);
-    if (timing) fprintf(stderr, "[timing]   upload + device parse   %8.3f s\n", lap_s(&t));
+    if (timing) fprintf(stderr, "[timing]   upload + device parse   %8.3f s\n", t.lap());
     CHK(ingest_pass1(c));
     c->state = cellector_ctx::ST_STAGED;
     return CELLECTOR_OK;
@@ -638,7 +629,7 @@ cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path,
     REQUIRE(c, alt_path && ref_path, "null path");
     MtxInput *in = nullptr;
     uint64_t tl = 0, tc = 0;
-    CHK(mtx_input_open(c, alt_path, ref_path, &in, &tl, &tc));
+    CHK(ctx_mtx_open(c, alt_path, ref_path, &in, &tl, &tc));
     c->ingest_all_cells = true;
     cellector_status s = begin_ingest(c, tl, tc);
     if (s == CELLECTOR_OK) s = ingest_stage_mtx_device(c, in, helper);
@@ -647,13 +638,10 @@ cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path,
     return s;
 }
 // ... step 2: a shard takes over its routed entries (arrays on its own device, cell index local, file order) as its staged COO.
-cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, DevBuf<uint32_t> locus,
-                                  DevBuf<uint32_t> cell, DevBuf<uint16_t> alt, DevBuf<uint16_t> ref, uint64_t n, bool sorted)
+cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, StagedCoo &&coo)
 {
     CHK(begin_ingest(c, total_loci, total_cells));
-    c->coo_locus = std::move(locus); c->coo_cell = std::move(cell); c->coo_alt = std::move(alt); c->coo_ref = std::move(ref);
-    c->coo_n = n;
-    c->coo_sorted = sorted;
+    c->coo = std::move(coo);
     CHK(ingest_pass1(c));
     c->state = cellector_ctx::ST_STAGED;
     return CELLECTOR_OK;
@@ -691,13 +679,13 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
     REQUIRE(c, c->state == cellector_ctx::ST_STAGED, "ingest_finish without a staged matrix");
     SETDEV(c);
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr && c->comm.rank == 0;
-    auto t = std::chrono::steady_clock::now();
+    LapTimer t;
     if (comm_active(c->comm)) {  // exchange point 1: global pass-1 counts and allele totals (every shard applies the same locus filter)
         CHK((cellector_status)comm_allreduce_sum(c, c->x_pass1, (uint64_t)P1_PLANES * c->total_loci));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     CHK(ingest_build(c, min_alt, min_ref));
-    if (timing) fprintf(stderr, "[timing]   CSC / CSR build         %8.3f s\n", lap_s(&t));
+    if (timing) fprintf(stderr, "[timing]   CSC / CSR build         %8.3f s\n", t.lap());
     const uint64_t L = c->L, n = c->nloc;
     CHK(dev_alloc(c, &c->ab, L)); CHK(dev_alloc(c, &c->ab6, 8 * L));
     CHK(dev_alloc(c, &c->mask, L)); CHK(dev_alloc(c, &c->mask_next, L));
@@ -744,7 +732,7 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
         // its compact CSC and overflow CSC from it.  Engine 1 must therefore be chosen BEFORE the ingest.
         c->csc_ent.reset();
     }
-    if (timing) fprintf(stderr, "[timing]   tiled layouts           %8.3f s\n", lap_s(&t));
+    if (timing) fprintf(stderr, "[timing]   tiled layouts           %8.3f s\n", t.lap());
     dev_cache_trim(c->device);  // the ingest's big temporaries are done: hand this device's cached blocks back
     c->state = cellector_ctx::ST_READY;
     c->em_phase = 0; c->iteration = 0; c->have_iter = false; c->n_excluded_global = 0;

@@ -1,10 +1,9 @@
 // Internal state of a cellector_ctx (one shard on one GPU) and the launch wrappers that the
 // C-ABI layer (cellector_ffi.cpp) calls.  Not part of the public ABI.
 #pragma once
-#include <cstring>
-
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -97,6 +96,21 @@ struct KernelTimer {
     bool open = false;   // timer_begin recorded a start event for the launch in progress
 };
 
+// A staged COO: the entries of a shard before the CSC / CSR build (all loci; cell index local, or global while a multi-device
+// text ingest still routes them), in file order.  Move-only, like its buffers.
+struct CooView { const uint32_t *locus, *cell; const uint16_t *alt, *ref; uint64_t n; };  // not owning: for offset pointers
+struct StagedCoo {
+    DevBuf<uint32_t> locus, cell;
+    DevBuf<uint16_t> alt, ref;
+    uint64_t n = 0;
+    bool sorted = false;  // locus-major
+    cellector_status alloc(cellector_ctx *c, uint64_t n_entries);  // the four arrays for n_entries (defined behind dev_alloc)
+    void reset() { locus.reset(); cell.reset(); alt.reset(); ref.reset(); n = 0; }
+    CooView view() const { return {locus, cell, alt, ref, n}; }
+    // m entries of src (on src_dev) to entry `at` of this one, on the receiving shard c's stream, complete on return
+    hipError_t copy_from(const cellector_ctx *c, uint64_t at, const StagedCoo &src, int src_dev, uint64_t m);
+};
+
 struct MultiCtx;  // multi.cpp: the shards and worker threads of a ctx made by cellector_create_multi
 
 // ---- the state of a ctx, grouped by lifetime ------------------------------------------------------------------------------
@@ -152,11 +166,7 @@ struct CtxMatrix {
     // this shard's cells: the requested range, the communicator's or all of them (ingest_all_cells), clamped to the matrix
     uint64_t cell_begin = 0, cell_end = UINT64_MAX;
 
-    // staged COO of this shard (all loci; cell index local)
-    uint64_t coo_n = 0;
-    DevBuf<uint32_t> coo_locus, coo_cell;
-    DevBuf<uint16_t> coo_alt, coo_ref;
-    bool coo_sorted = false;
+    StagedCoo coo;  // staged COO of this shard (all loci; cell index local)
 
     // matrix
     DevBuf<uint64_t> csr_ptr, csr_ent;   // [nloc+1], [nnz]
@@ -386,7 +396,32 @@ static inline hipError_t dev_copy_sync(hipStream_t st, void *dst, int dst_dev, c
     return e;
 }
 
+inline cellector_status StagedCoo::alloc(cellector_ctx *c, uint64_t n_entries)
+{
+    n = n_entries;
+    CHK(dev_alloc(c, &locus, n)); CHK(dev_alloc(c, &cell, n));
+    CHK(dev_alloc(c, &alt, n)); CHK(dev_alloc(c, &ref, n));
+    return CELLECTOR_OK;
+}
+inline hipError_t StagedCoo::copy_from(const cellector_ctx *c, uint64_t at, const StagedCoo &src, int src_dev, uint64_t m)
+{
+    hipError_t e = dev_copy_sync(c->stream, locus + at, c->device, src.locus, src_dev, m * 4);
+    if (e == hipSuccess) e = dev_copy_sync(c->stream, cell + at, c->device, src.cell, src_dev, m * 4);
+    if (e == hipSuccess) e = dev_copy_sync(c->stream, alt + at, c->device, src.alt, src_dev, m * 2);
+    if (e == hipSuccess) e = dev_copy_sync(c->stream, ref + at, c->device, src.ref, src_dev, m * 2);
+    return e;
+}
+
 // ---- timing -----------------------------------------------------------------------------------
+struct LapTimer {  // CELLECTOR_TIMING=1: phase wall times of the ingest on stderr; lap() = seconds since the last one
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    double lap()
+    {
+        const auto was = t;
+        t = std::chrono::steady_clock::now();
+        return std::chrono::duration<double>(t - was).count();
+    }
+};
 void timer_begin(cellector_ctx *c, int which);
 void timer_end(cellector_ctx *c, int which);
 bool timer_take(cellector_ctx *c, int which, hipEvent_t *start, hipEvent_t *stop);
@@ -431,16 +466,13 @@ cellector_status assign_resolve(cellector_ctx *c, int mode, double threshold, do
 cellector_status ingest_stage_host_coo(cellector_ctx *c, uint64_t nnz, const uint32_t *locus0,
                                        const uint32_t *cell0, const uint32_t *alt, const uint32_t *ref);
 cellector_status ingest_pass1(cellector_ctx *c);
-// the entries of cells [cb, ce) out of n staged ones of ALL cells (cell index global), into four new arrays on c's device: cell
-// index made local, order kept; `keep` is caller scratch of n + 1 words
-cellector_status ingest_split_coo(cellector_ctx *c, const uint32_t *locus, const uint32_t *cell, const uint16_t *alt, const uint16_t *ref,
-                                  uint64_t n, uint64_t cb, uint64_t ce, uint64_t *keep, DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell,
-                                  DevBuf<uint16_t> *o_alt, DevBuf<uint16_t> *o_ref, uint64_t *n_out);
+// the entries of cells [cb, ce) out of the staged ones of ALL cells (cell index global), into a new COO on c's device: cell
+// index made local, order kept; `keep` is caller scratch of all.n + 1 words
+cellector_status ingest_split_coo(cellector_ctx *c, const CooView &all, uint64_t cb, uint64_t ce, uint64_t *keep, StagedCoo *out);
 cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell, uint64_t n, uint64_t total_cells, std::vector<uint32_t> *out);
 // multi-device text ingest (cellector_ffi.cpp): stage the whole pair on one shard / hand a shard its routed entries
 cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path, const char *ref_path, cellector_ctx *helper);
-cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, DevBuf<uint32_t> locus,
-                                  DevBuf<uint32_t> cell, DevBuf<uint16_t> alt, DevBuf<uint16_t> ref, uint64_t n, bool sorted);
+cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, StagedCoo &&coo);
 cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_ref);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
@@ -461,17 +493,15 @@ cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones);
 cellector_status tiled_call_masked_count(cellector_ctx *c, const uint8_t *host_mask, uint32_t *cnt);
 cellector_status tiled_prebuild_tables(cellector_ctx *c);
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl);
-// device-side mtx text parse (kernels_parse.hip)
+// device-side mtx text parse (kernels_parse.hip); the pair's bytes and header: mtx_bytes.h
 struct MtxInput;
-cellector_status mtx_input_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out,
-                                uint64_t *total_loci, uint64_t *total_cells);
+cellector_status ctx_mtx_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out,
+                              uint64_t *total_loci, uint64_t *total_cells);  // mtx_input_open, its failure into c->err
 void mtx_input_close(MtxInput *in);
 // split ingest of a multi-device ctx (kernels_parse.hip): every shard tokenises a range of windows of both files
 struct MtxSplit;
 MtxSplit *mtx_split_new(int n_shards, LocalGroup *thread_barrier, bool balance /*cut the cells by entries, not by count*/);
 void mtx_split_delete(MtxSplit *s);
 bool mtx_input_windowed(const MtxInput *in, int64_t parse_window_opt);
-cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *s, int rank, uint64_t parse_window,
-                                        DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell, DevBuf<uint16_t> *o_alt,
-                                        DevBuf<uint16_t> *o_ref, uint64_t *o_n, bool *o_sorted);
+cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *s, int rank, uint64_t parse_window, StagedCoo *out);
 cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellector_ctx *helper = nullptr /*parses the ref file*/);

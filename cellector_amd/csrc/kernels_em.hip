@@ -525,9 +525,9 @@ cellector_status launch_posteriors(cellector_ctx *c, double mf0, double lp_min, 
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out)
 {
     HIPCHK(c, hipMemsetAsync(d_out, 0, 4 * c->total_loci * 8, c->stream));
-    if (c->coo_n)
-        hipLaunchKernelGGL(k_final_tallies, dim3(grid_for(c->coo_n, 256)), dim3(256), 0, c->stream, c->coo_n,
-                           c->total_loci, c->coo_locus, c->coo_cell, c->coo_alt, c->coo_ref, c->flags,
+    if (c->coo.n)
+        hipLaunchKernelGGL(k_final_tallies, dim3(grid_for(c->coo.n, 256)), dim3(256), 0, c->stream, c->coo.n,
+                           c->total_loci, c->coo.locus, c->coo.cell, c->coo.alt, c->coo.ref, c->flags,
                            (unsigned long long *)d_out);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;

@@ -313,15 +313,13 @@ cellector_status ingest_stage_host_coo(cellector_ctx *c, uint64_t nnz, const uin
         ha.push_back((uint16_t)alt[i]); hr.push_back((uint16_t)ref[i]);
     }
     const uint64_t n = hl.size();
-    c->coo_n = n;
-    c->coo_sorted = sorted;
-    CHK(dev_alloc(c, &c->coo_locus, n)); CHK(dev_alloc(c, &c->coo_cell, n));
-    CHK(dev_alloc(c, &c->coo_alt, n)); CHK(dev_alloc(c, &c->coo_ref, n));
+    c->coo.sorted = sorted;
+    CHK(c->coo.alloc(c, n));
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->coo_locus, hl.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->coo_cell, hc.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->coo_alt, ha.data(), n * 2, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->coo_ref, hr.data(), n * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->coo.locus, hl.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->coo.cell, hc.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->coo.alt, ha.data(), n * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->coo.ref, hr.data(), n * 2, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return CELLECTOR_OK;
@@ -374,23 +372,20 @@ cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell,
     return CELLECTOR_OK;
 }
 
-cellector_status ingest_split_coo(cellector_ctx *c, const uint32_t *locus, const uint32_t *cell, const uint16_t *alt, const uint16_t *ref,
-                                  uint64_t n, uint64_t cb, uint64_t ce, uint64_t *keep, DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell,
-                                  DevBuf<uint16_t> *o_alt, DevBuf<uint16_t> *o_ref, uint64_t *n_out)
+cellector_status ingest_split_coo(cellector_ctx *c, const CooView &all, uint64_t cb, uint64_t ce, uint64_t *keep, StagedCoo *out)
 {
+    const uint64_t n = all.n;
     const unsigned g = (unsigned)((n + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_coo_in_range, dim3(g), dim3(256), 0, c->stream, n, cell, cb, ce, keep);
+    hipLaunchKernelGGL(k_coo_in_range, dim3(g), dim3(256), 0, c->stream, n, all.cell, cb, ce, keep);
     HIPCHK(c, hipGetLastError());
     uint64_t kept = 0;
     CHK(dev_exclusive_scan_u64(c, keep, n + 1, &kept));
-    CHK(dev_alloc(c, o_locus, kept)); CHK(dev_alloc(c, o_cell, kept));
-    CHK(dev_alloc(c, o_alt, kept)); CHK(dev_alloc(c, o_ref, kept));
+    CHK(out->alloc(c, kept));
     if (n)
-        hipLaunchKernelGGL(k_coo_take_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, locus, cell, alt, ref, cb, ce,
-                           keep, o_locus->get(), o_cell->get(), o_alt->get(), o_ref->get());
+        hipLaunchKernelGGL(k_coo_take_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, all.locus, all.cell, all.alt,
+                           all.ref, cb, ce, keep, out->locus.get(), out->cell.get(), out->alt.get(), out->ref.get());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n_out = kept;
     return CELLECTOR_OK;
 }
 
@@ -398,13 +393,13 @@ cellector_status ingest_pass1(cellector_ctx *c)
 {
     const uint64_t TL = c->total_loci;
     HIPCHK(c, hipMemsetAsync(c->x_pass1, 0, P1_PLANES * TL * 8, c->stream));
-    if (c->coo_n) {
-        if (c->coo_sorted)
-            hipLaunchKernelGGL(k_pass1<true>, dim3(g1(c->coo_n)), dim3(IB), 0, c->stream, c->coo_n, TL, c->coo_locus,
-                               c->coo_alt, c->coo_ref, c->x_pass1);
+    if (c->coo.n) {
+        if (c->coo.sorted)
+            hipLaunchKernelGGL(k_pass1<true>, dim3(g1(c->coo.n)), dim3(IB), 0, c->stream, c->coo.n, TL, c->coo.locus,
+                               c->coo.alt, c->coo.ref, c->x_pass1);
         else
-            hipLaunchKernelGGL(k_pass1<false>, dim3(g1(c->coo_n)), dim3(IB), 0, c->stream, c->coo_n, TL, c->coo_locus,
-                               c->coo_alt, c->coo_ref, c->x_pass1);
+            hipLaunchKernelGGL(k_pass1<false>, dim3(g1(c->coo.n)), dim3(IB), 0, c->stream, c->coo.n, TL, c->coo.locus,
+                               c->coo.alt, c->coo.ref, c->x_pass1);
         HIPCHK(c, hipGetLastError());
     }
     return CELLECTOR_OK;
@@ -412,15 +407,13 @@ cellector_status ingest_pass1(cellector_ctx *c)
 
 cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_ref)
 {
-    const uint64_t TL = c->total_loci, n = c->coo_n, nloc = c->nloc;
+    const uint64_t TL = c->total_loci, n = c->coo.n, nloc = c->nloc;
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr
-    auto t_prev = std::chrono::steady_clock::now();
+    LapTimer t;
     auto lap = [&](const char *what) {
         if (!timing) return;
         (void)hipStreamSynchronize(c->stream);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[timing]     %-22s %8.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-        t_prev = now;
+        fprintf(stderr, "[timing]     %-22s %8.3f s\n", what, t.lap());
     };
     // ---- filter + compaction map
     CHK(dev_alloc(c, &c->to_used, TL + 1));
@@ -441,7 +434,7 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
     if (c->resolve_ties || c->resolve_posteriors) CHK(resolve_build_file_order(c));
 
     // ---- unsorted input: stable sort of the staged COO by locus
-    if (!c->coo_sorted && n) {
+    if (!c->coo.sorted && n) {
         DevBuf<uint32_t> k_out, cell_o;
         DevBuf<uint16_t> alt_o, ref_o;
         DevBuf<uint64_t> perm, perm_o;
@@ -449,14 +442,14 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
         hipLaunchKernelGGL(k_iota_u64, dim3(g1(n)), dim3(IB), 0, c->stream, n, perm);
         int bits = 1;
         while (bits < 32 && (1ull << bits) < TL) bits++;
-        CHK(dev_sort_pairs_u32_u64(c, c->coo_locus, k_out, perm, perm_o, n, bits));
+        CHK(dev_sort_pairs_u32_u64(c, c->coo.locus, k_out, perm, perm_o, n, bits));
         CHK(dev_alloc(c, &cell_o, n)); CHK(dev_alloc(c, &alt_o, n)); CHK(dev_alloc(c, &ref_o, n));
-        hipLaunchKernelGGL(k_permute_coo, dim3(g1(n)), dim3(IB), 0, c->stream, n, perm_o, c->coo_cell, c->coo_alt,
-                           c->coo_ref, cell_o, alt_o, ref_o);
+        hipLaunchKernelGGL(k_permute_coo, dim3(g1(n)), dim3(IB), 0, c->stream, n, perm_o, c->coo.cell, c->coo.alt,
+                           c->coo.ref, cell_o, alt_o, ref_o);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->coo_locus = std::move(k_out); c->coo_cell = std::move(cell_o); c->coo_alt = std::move(alt_o); c->coo_ref = std::move(ref_o);
-        c->coo_sorted = true;  // (perm, perm_o go with this block)
+        c->coo.locus = std::move(k_out); c->coo.cell = std::move(cell_o); c->coo.alt = std::move(alt_o); c->coo.ref = std::move(ref_o);
+        c->coo.sorted = true;  // (perm, perm_o go with this block)
     }
 
     lap("filter + compaction");
@@ -467,7 +460,7 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
     CHK(dev_alloc(c, &c->csc_ptr, L + 1));
     HIPCHK(c, hipMemsetAsync(loc_cnt, 0, (TL + 1) * 8, c->stream));
     if (n)
-        hipLaunchKernelGGL(k_count, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo_locus, (unsigned long long *)loc_cnt.get());
+        hipLaunchKernelGGL(k_count, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo.locus, (unsigned long long *)loc_cnt.get());
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_gather_used_counts, dim3(g1(L + 1)), dim3(IB), 0, c->stream, L, c->locus_ids, loc_cnt,
                        c->csc_ptr);
@@ -485,8 +478,8 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
     CHK(dev_alloc(c, &key, c->nnz)); CHK(dev_alloc(c, &key_o, c->nnz)); CHK(dev_alloc(c, &val, c->nnz));
     lap("allocations");
     if (n)
-        hipLaunchKernelGGL(k_fill, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo_locus, c->coo_cell, c->coo_alt,
-                           c->coo_ref, c->to_used, loc_cnt, c->csc_ptr, c->csc_ent, key, val);
+        hipLaunchKernelGGL(k_fill, dim3(g1(n)), dim3(IB), 0, c->stream, n, c->coo.locus, c->coo.cell, c->coo.alt,
+                           c->coo.ref, c->to_used, loc_cnt, c->csc_ptr, c->csc_ent, key, val);
     HIPCHK(c, hipGetLastError());
     lap("CSC fill");
     int bits = 1;
@@ -500,9 +493,6 @@ cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_r
     lap("sort by cell");
     key.reset(); key_o.reset(); val.reset(); loc_cnt.reset();
     lap("frees");
-    if (!c->keep_coo) {
-        c->coo_locus.reset(); c->coo_cell.reset(); c->coo_alt.reset(); c->coo_ref.reset();
-        c->coo_n = 0;
-    }
+    if (!c->keep_coo) c->coo.reset();
     return CELLECTOR_OK;
 }

@@ -1,7 +1,7 @@
 // Device-side parse of the vartrix alt.mtx / ref.mtx text (rows A1 and f2 of the scope table).
 //
 // The host only brings bytes (mmap for plain files, zlib inflate for ".gz", multi-member) and reads the three header
-// lines; the data lines are tokenised and converted on the GPU:
+// lines (mtx_bytes.cpp); the data lines are tokenised and converted on the GPU:
 //   k_nl_count               newlines per 128-byte segment, scanned: the index of the first line that starts in a segment;
 //   k_parse_lines            a thread per segment, for every line that starts there: split_whitespace + parse::<usize>() of the tokens the reference reads
 //                            (load_data.rs:190-204): alt file tokens 0,1,2 (locus, cell, alt count), ref file token 2 only
@@ -9,20 +9,13 @@
 //   k_pair_check / k_pair_fill   zip the two files (shorter one wins, like izip!), range checks, this shard's cell range,
 //                            ordered compaction into the staged COO (locus u32, cell_local u32, alt u16, ref u16).
 // The text contract is the reference's; errors come back as CELLECTOR_EPARSE / CELLECTOR_EINVAL with the line number.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-
-#include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
 
 #include "ctx.h"
 #include "device_math.h"
+#include "mtx_bytes.h"
 
 #define PB 256
 
@@ -230,218 +223,6 @@ __global__ __launch_bounds__(PB) void k_pair_take(uint64_t n, uint32_t *__restri
 // ===============================================================================================================
 namespace {
 
-// the bytes of one input file: inflated into `owned` (.gz), mapped (plain, below FB_UNMAPPED), or — a plain file of
-// FB_UNMAPPED bytes and more — not mapped at all: its windows are pread() straight into the pinned upload buffers.  (Mapping 2 x 31 GB meant
-// 15 M page-table entries to fault in and to tear down again: the munmap alone took 0.7 s, during which the runtime's
-// own allocations queue for the address-space lock.)
-#define FB_UNMAPPED (1ull << 30)
-struct FileBytes {
-    const uint8_t *data = nullptr;  // null: unmapped, use read()
-    size_t size = 0;
-    void *map = nullptr;
-    size_t map_len = 0;
-    int fd = -1;
-    std::vector<uint8_t> owned;  // .gz: the inflated file; unmapped: its first FB_HEAD bytes (the header lines)
-    size_t head_len = 0;
-    ~FileBytes()
-    {
-        if (map) munmap(map, map_len);
-        if (fd >= 0) close(fd);
-    }
-    const uint8_t *head() const { return data ? data : owned.data(); }
-    size_t head_size() const { return data ? size : head_len; }
-    bool read(size_t off, size_t len, uint8_t *dst) const
-    {
-        if (data) {
-            memcpy(dst, data + off, len);
-            return true;
-        }
-        while (len) {
-            const ssize_t got = pread(fd, dst, len, (off_t)off);
-            if (got <= 0) return false;
-            dst += got; off += (size_t)got; len -= (size_t)got;
-        }
-        return true;
-    }
-};
-#define FB_HEAD (1u << 20)
-
-// A ".gz" whose members all carry the BGZF extra field (bgzip: blocks of at most 64 KB, each a gzip member with its own
-// compressed size in a 'B','C' subfield — the reference's MultiGzDecoder reads such a file like any multi-member gzip,
-// load_data.rs:246) is inflated block-parallel: the member boundaries are found by hopping over the size fields, the
-// output offsets are the prefix sums of the members' ISIZE trailers, and host threads inflate ranges of blocks straight
-// into place (raw deflate, CRC-32 and length of every block checked like gzread does).  A single zlib stream inflates at
-// ~0.35 GB/s of text; a plain gzip file has no such index and keeps the serial path below.
-struct BgzfBlock { size_t off, clen; uint32_t xlen, isize; size_t out; };
-bool bgzf_index(const uint8_t *f, size_t n, std::vector<BgzfBlock> *blocks, size_t *total)
-{
-    size_t pos = 0, out = 0;
-    while (pos < n) {
-        if (n - pos < 18 || f[pos] != 0x1f || f[pos + 1] != 0x8b || f[pos + 2] != 8 || !(f[pos + 3] & 4)) return false;
-        if (f[pos + 3] & ~4u) return false;  // (name / comment / header CRC: not what bgzip writes — leave it to zlib)
-        const uint32_t xlen = f[pos + 10] | ((uint32_t)f[pos + 11] << 8);
-        if (n - pos < 12 + (size_t)xlen + 8) return false;
-        uint32_t bsize = 0;
-        bool have = false;
-        for (size_t q = pos + 12, e = pos + 12 + xlen; q + 4 <= e;) {
-            const uint32_t slen = f[q + 2] | ((uint32_t)f[q + 3] << 8);
-            if (f[q] == 'B' && f[q + 1] == 'C' && slen == 2 && q + 6 <= e) { bsize = f[q + 4] | ((uint32_t)f[q + 5] << 8); have = true; }
-            q += 4 + slen;
-        }
-        const size_t clen = (size_t)bsize + 1;
-        if (!have || clen < 12 + (size_t)xlen + 8 || n - pos < clen) return false;
-        const uint8_t *tr = f + pos + clen - 4;
-        const uint32_t isize = tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        if (isize > 65536u) return false;  // (bgzip never puts more than 64 KB into a block: not BGZF, leave it to zlib)
-        blocks->push_back({pos, clen, xlen, isize, out});
-        out += isize;
-        pos += clen;
-    }
-    *total = out;
-    return !blocks->empty();
-}
-bool bgzf_inflate(const uint8_t *f, const std::vector<BgzfBlock> &blocks, uint8_t *dst)
-{
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 32) nt = 32;
-    if ((size_t)nt > blocks.size()) nt = (unsigned)blocks.size();
-    std::atomic<bool> ok(true);
-    auto work = [&](size_t b0, size_t b1) {
-        z_stream z;
-        memset(&z, 0, sizeof z);
-        if (inflateInit2(&z, -15) != Z_OK) { ok = false; return; }
-        for (size_t b = b0; b < b1 && ok; b++) {
-            const BgzfBlock &k = blocks[b];
-            z.next_in = const_cast<Bytef *>(f + k.off + 12 + k.xlen);
-            z.avail_in = (uInt)(k.clen - 12 - k.xlen - 8);
-            z.next_out = dst + k.out;
-            z.avail_out = k.isize;
-            const int r = k.isize || z.avail_in ? inflate(&z, Z_FINISH) : Z_STREAM_END;
-            const uint8_t *tr = f + k.off + k.clen - 8;
-            const uint32_t crc = tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-            if (r != Z_STREAM_END || z.avail_out != 0 || (uint32_t)crc32(crc32(0L, Z_NULL, 0), dst + k.out, k.isize) != crc) ok = false;
-            inflateReset(&z);
-        }
-        inflateEnd(&z);
-    };
-    std::vector<std::thread> th;
-    const size_t per = (blocks.size() + nt - 1) / nt;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, std::min(blocks.size(), t * per), std::min(blocks.size(), (t + 1) * per));
-    work(0, std::min(blocks.size(), per));
-    for (auto &t : th) t.join();
-    return ok;
-}
-
-// reader (load_data.rs:240-251): ".gz" by extension (multi-member), plain otherwise
-bool load_bytes(const char *path, FileBytes *fb)
-{
-    const size_t n = strlen(path);
-    if (n >= 3 && strcmp(path + n - 3, ".gz") == 0) {
-        {   // block-compressed (bgzip)?  then in parallel
-            const int fd = open(path, O_RDONLY);
-            struct stat st;
-            if (fd >= 0 && fstat(fd, &st) == 0 && st.st_size > 0 && !getenv("CELLECTOR_NO_BGZF")) {
-                void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-                if (m != MAP_FAILED) {
-                    std::vector<BgzfBlock> blocks;
-                    size_t total = 0;
-                    bool done = false;
-                    try {
-                        if (bgzf_index((const uint8_t *)m, (size_t)st.st_size, &blocks, &total)) {
-                            fb->owned.resize(total ? total : 1);
-                            done = bgzf_inflate((const uint8_t *)m, blocks, fb->owned.data());
-                            if (done) { fb->data = fb->owned.data(); fb->size = total; }
-                        }
-                    } catch (const std::exception &) {  // (no room for the index or the text: the serial reader decides)
-                        done = false;
-                    }
-                    munmap(m, (size_t)st.st_size);
-                    if (done) { close(fd); return true; }
-                    fb->owned.clear();  // (a damaged block: the serial reader below reports what zlib makes of the file)
-                }
-            }
-            if (fd >= 0) close(fd);
-        }
-        gzFile gz = gzopen(path, "rb");
-        if (!gz) return false;
-        gzbuffer(gz, 1 << 20);
-        size_t cap = 1 << 24, len = 0;
-        fb->owned.resize(cap);
-        for (;;) {
-            if (len == cap) fb->owned.resize(cap *= 2);
-            const int got = gzread(gz, fb->owned.data() + len, (unsigned)std::min<size_t>(cap - len, 1u << 30));
-            if (got < 0) {  // a damaged stream (CRC, truncated member): the reference's decoder fails the read as well
-                gzclose(gz);
-                return false;
-            }
-            if (got == 0) break;
-            len += (size_t)got;
-        }
-        gzclose(gz);
-        fb->data = fb->owned.data();
-        fb->size = len;
-        return true;
-    }
-    fb->fd = open(path, O_RDONLY);
-    if (fb->fd < 0) return false;
-    struct stat st;
-    if (fstat(fb->fd, &st) != 0) return false;
-    fb->size = (size_t)st.st_size;
-    const char *um = getenv("CELLECTOR_UNMAPPED_MIN");  // (tests: the unmapped path on small files)
-    if (fb->size >= (um ? (size_t)strtoull(um, nullptr, 10) : (size_t)FB_UNMAPPED) && fb->size > 0) {
-        fb->head_len = std::min<size_t>(fb->size, FB_HEAD);
-        fb->owned.resize(fb->head_len);
-        return fb->read(0, fb->head_len, fb->owned.data());
-    }
-    if (fb->size) {
-        fb->map = mmap(nullptr, fb->size, PROT_READ, MAP_PRIVATE, fb->fd, 0);
-        if (fb->map == MAP_FAILED) { fb->map = nullptr; return false; }
-        fb->map_len = fb->size;
-        madvise(fb->map, fb->size, MADV_SEQUENTIAL);
-        fb->data = (const uint8_t *)fb->map;
-    }
-    return true;
-}
-
-// consume_mtx_header (load_data.rs:206-223): exactly three lines; returns the offset of the first data byte
-size_t skip_header(const FileBytes &fb, std::string *third)
-{
-    size_t pos = 0;
-    for (int x = 0; x < 3; x++) {
-        // (an unmapped file: the three lines are looked for in its first FB_HEAD bytes)
-        const uint8_t *hd = fb.head();
-        const size_t hn = fb.head_size();
-        const void *nl = pos < hn ? memchr(hd + pos, '\n', hn - pos) : nullptr;
-        const size_t end = nl ? (size_t)((const uint8_t *)nl - hd) : hn;
-        if (x == 2 && third) third->assign((const char *)hd + pos, end - pos);
-        pos = nl ? end + 1 : hn;
-    }
-    return pos;
-}
-
-bool host_tok_u64(const std::string &s, int idx, uint64_t *out)
-{
-    size_t p = 0;
-    for (int t = 0;; t++) {
-        while (p < s.size() && isspace((unsigned char)s[p])) p++;
-        if (p >= s.size()) return false;
-        size_t b = p;
-        while (p < s.size() && !isspace((unsigned char)s[p])) p++;
-        if (t == idx) {
-            if (s[b] == '+') b++;
-            if (b == p) return false;
-            uint64_t v = 0;
-            for (; b < p; b++) {
-                if (s[b] < '0' || s[b] > '9') return false;
-                v = v * 10 + (uint64_t)(s[b] - '0');
-            }
-            *out = v;
-            return true;
-        }
-    }
-}
-
 struct DevText {
     DevBuf<uint8_t> text;
     uint64_t n = 0, n_lines = 0;
@@ -539,6 +320,44 @@ cellector_status split_lines(cellector_ctx *c, const FileBytes &fb, DevText *dt)
 #define PW_SPLIT_WINDOW (32ull << 20)  // largest window of the split ingest of a multi-device ctx (every shard has its own ring)
 #define PW_MIN (1ull << 30)  // data sections from this size on go through the windows
 #define PW_THREADS 8  // host threads filling a pinned buffer (pread out of the page cache; 16 threads measured no faster)
+
+inline uint64_t pw_windows(uint64_t bytes, uint64_t win) { return (bytes + win - 1) / win; }
+// buffers of the ring of a parser that takes n_win windows
+inline int pw_ring(uint64_t n_win) { return (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, n_win)); }
+// the window: 1/div of the bigger file's data section, lo .. hi bytes; the environment (in MB), then option parse_window override it
+uint64_t pw_window(const MtxInput *in, uint64_t div, uint64_t lo, uint64_t hi, const char *env, uint64_t parse_window)
+{
+    uint64_t win = std::max(in->fa.size - in->off_a, in->fr.size - in->off_r) / div;
+    win = std::min<uint64_t>(hi, std::max<uint64_t>(lo, win));
+    if (const char *e_mb = getenv(env)) win = (uint64_t)atoll(e_mb) << 20;
+    if (parse_window > 0) win = parse_window;
+    if (win < 4 * NL_SEG) win = 4 * NL_SEG;
+    return win & ~(uint64_t)(NL_SEG - 1);
+}
+
+// the status words of a parse on the device and their host copies.  bad[0] alt file, [1] ref file: smallest line that does not
+// parse; [2] zip stage: smallest refused entry << PE_KIND_BITS | its kind.  flags[1]: the file order is not locus-major.
+struct ParseStatus {
+    DevBuf<unsigned long long> bad;
+    DevBuf<uint32_t> flags;
+    unsigned long long h_bad[3] = {~0ull, ~0ull, ~0ull};
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    cellector_status init(cellector_ctx *c, bool with_flags = true)
+    {
+        CHK(dev_alloc(c, &bad, 3));
+        if (with_flags) CHK(dev_alloc(c, &flags, 4));
+        return copy(c, bad, h_bad, flags, h_flags, with_flags, hipMemcpyHostToDevice);
+    }
+    // (read BEHIND the kernels on the ctx's stream: a caller-supplied non-blocking stream does not order against null-stream copies)
+    cellector_status read(cellector_ctx *c, bool with_flags) { return copy(c, h_bad, bad, h_flags, flags, with_flags, hipMemcpyDeviceToHost); }
+    cellector_status copy(cellector_ctx *c, void *dbad, const void *sbad, void *dflags, const void *sflags, bool with_flags, hipMemcpyKind kind)
+    {
+        hipError_t e = hipMemcpyAsync(dbad, sbad, sizeof h_bad, kind, c->stream);
+        if (e == hipSuccess && with_flags) e = hipMemcpyAsync(dflags, sflags, sizeof h_flags, kind, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        return e == hipSuccess ? CELLECTOR_OK : ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+    }
+};
 
 // the windows' buffers, shared by the two files of a pair (pinning 3 x 257 MB takes ~0.05 s)
 struct PwBuffers {
@@ -731,49 +550,6 @@ cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t da
 
 }  // namespace
 
-struct MtxInput {
-    FileBytes fa, fr;
-    size_t off_a = 0, off_r = 0;
-    uint64_t total_loci = 0, total_cells = 0;
-    uint64_t nnz_hint = 0;  // third number of the size line (0: absent); a capacity hint, never trusted
-};
-
-// open both files (bytes only) and read the dims from the REF file's third header line (load_data.rs:216-220)
-cellector_status mtx_input_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out,
-                                uint64_t *total_loci, uint64_t *total_cells)
-{
-    MtxInput *in = new (std::nothrow) MtxInput();
-    if (!in) return ctx_fail(c, CELLECTOR_ENOMEM, "out of host memory");
-    cellector_status st = CELLECTOR_OK;
-    std::string third;
-    bool ok_a = false, ok_r = false;
-    {   // the two files are independent byte streams: inflate / map them concurrently
-        std::thread ta([&] { ok_a = load_bytes(alt_path, &in->fa); });
-        ok_r = load_bytes(ref_path, &in->fr);
-        ta.join();
-    }
-    if (!ok_a) st = ctx_fail(c, CELLECTOR_EIO, "couldn't open file %s", alt_path);
-    else if (!ok_r) st = ctx_fail(c, CELLECTOR_EIO, "couldn't open file %s", ref_path);
-    else {
-        in->off_a = skip_header(in->fa, nullptr);
-        in->off_r = skip_header(in->fr, &third);
-        if (!host_tok_u64(third, 0, &in->total_loci) || !host_tok_u64(third, 1, &in->total_cells))
-            st = ctx_fail(c, CELLECTOR_EPARSE, "cannot parse the matrix market size line of %s", ref_path);
-        else if (!host_tok_u64(third, 2, &in->nnz_hint) || in->nnz_hint > (in->fr.size - in->off_r) / 4)
-            in->nnz_hint = 0;  // (a line holds at least "1 1 1": a hint beyond the bytes there are is nonsense)
-    }
-    if (st != CELLECTOR_OK) {
-        delete in;
-        return st;
-    }
-    *total_loci = in->total_loci;
-    *total_cells = in->total_cells;
-    *out = in;
-    return CELLECTOR_OK;
-}
-
-void mtx_input_close(MtxInput *in) { delete in; }
-
 // a file small enough to sit on the device whole: one upload, one scan of its newlines, one tokeniser launch
 template <bool ALT>
 static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_t data_off, DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1,
@@ -793,6 +569,16 @@ static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_
     }
     *n_lines = n;
     return st;
+}
+
+// one file's tokens, through B's windows (made by the caller; [w_begin, w_end): see parse_windowed) or whole
+template <bool ALT>
+static cellector_status parse_file(cellector_ctx *c, const FileBytes &fb, size_t data_off, bool windowed, PwBuffers &B, uint64_t cap_hint,
+                                   DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1, DevBuf<uint32_t> *o2, uint64_t *n_lines,
+                                   unsigned long long *bad, uint64_t w_begin = 0, uint64_t w_end = ~0ull)
+{
+    return windowed ? parse_windowed<ALT>(c, fb, data_off, B, cap_hint, o0, o1, o2, n_lines, bad, w_begin, w_end)
+                    : parse_whole<ALT>(c, fb, data_off, o0, o1, o2, n_lines, bad);
 }
 
 // ---- split ingest of a multi-device ctx -------------------------------------------------------------------------------------
@@ -818,10 +604,7 @@ struct MtxSplit {
     uint64_t lines[CELLECTOR_MAX_SHARDS] = {};
     uint32_t *r_dev[CELLECTOR_MAX_SHARDS] = {};  // (each shard's ref counts, owned by the shard)
     int device[CELLECTOR_MAX_SHARDS] = {};
-    // [from][to]: the piece of shard `from`'s lines meant for shard `to`, on `from`'s device
-    DevBuf<uint32_t> pl[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS], pc[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS];
-    DevBuf<uint16_t> pa[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS], pr[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS];
-    uint64_t cnt[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS] = {};
+    StagedCoo piece[CELLECTOR_MAX_SHARDS][CELLECTOR_MAX_SHARDS];  // [from][to]: shard `from`'s lines meant for shard `to`, on `from`'s device
     bool balance = false;                             // cut the cells so that every shard gets about the same number of entries
     std::vector<uint32_t> hist[CELLECTOR_MAX_SHARDS];  // ... from every parser's entries per cell
 };
@@ -832,6 +615,16 @@ MtxSplit *mtx_split_new(int n, LocalGroup *bar, bool balance)
     return S;
 }
 void mtx_split_delete(MtxSplit *S) { delete S; }
+cellector_status ctx_mtx_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out, uint64_t *total_loci,
+                              uint64_t *total_cells)
+{
+    std::string msg;
+    const cellector_status st = mtx_input_open(alt_path, ref_path, out, &msg);
+    if (st != CELLECTOR_OK) return ctx_fail(c, st, "%s", msg.c_str());
+    *total_loci = (*out)->total_loci;
+    *total_cells = (*out)->total_cells;
+    return CELLECTOR_OK;
+}
 // both files go through the windowed parser (big, or the parse_window option forces it): the split ingest needs that
 bool mtx_input_windowed(const MtxInput *in, int64_t parse_window_opt)
 {
@@ -839,23 +632,13 @@ bool mtx_input_windowed(const MtxInput *in, int64_t parse_window_opt)
     return na > 0 && nr > 0 && (parse_window_opt > 0 || (na >= PW_MIN && nr >= PW_MIN));
 }
 
-static cellector_status copy_between(cellector_ctx *c, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes)
-{
-    if (!bytes) return CELLECTOR_OK;
-    const hipError_t e = dev_copy_sync(c->stream, dst, dst_dev, src, src_dev, bytes);  // (c = the receiving shard, its device current)
-    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "copy between shards failed: %s", hipGetErrorString(e));
-    return CELLECTOR_OK;
-}
-
-cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *S, int rank, uint64_t parse_window,
-                                        DevBuf<uint32_t> *o_locus, DevBuf<uint32_t> *o_cell, DevBuf<uint16_t> *o_alt,
-                                        DevBuf<uint16_t> *o_ref, uint64_t *o_n, bool *o_sorted)
+cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *S, int rank, uint64_t parse_window, StagedCoo *out)
 {
     const int n = S->n;
     const uint64_t TL = in->total_loci, TC = in->total_cells;
-    DevBuf<uint32_t> l1, c1, a, r, rk, flags;
+    DevBuf<uint32_t> l1, c1, a, r, rk;
     DevBuf<uint16_t> alt16, ref16;
-    DevBuf<unsigned long long> bad;
+    ParseStatus ps;
     DevBuf<uint64_t> keep;
     // (on a failure the pieces this shard cut for the others stay until the MtxSplit goes: a peer may still be reading them)
 #define SCHK(expr)                     \
@@ -876,50 +659,36 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     }
     S->device[rank] = c->device;
     const bool timing = rank == 0 && getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times of shard 0 on stderr
-    auto t_prev = std::chrono::steady_clock::now();
+    LapTimer t;
     auto lap = [&](const char *what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[timing]     split: %-26s %8.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-        t_prev = now;
+        if (timing) fprintf(stderr, "[timing]     split: %-26s %8.3f s\n", what, t.lap());
     };
-    SCHK(dev_alloc(c, &bad, 3)); SCHK(dev_alloc(c, &flags, 4));
-    unsigned long long h_bad[3] = {~0ull, ~0ull, ~0ull};
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(bad, h_bad, sizeof h_bad, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, h_flags, sizeof h_flags, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)));
+    SCHK(ps.init(c));
+    unsigned long long *const bad = ps.bad, *const h_bad = ps.h_bad;
+    hipError_t e = hipSuccess;
     // ---- 1. this shard's windows of both files
     // (n shards pin their upload buffers at the same time and the driver pins them one after the other: 4 x 3 x 256 MB took
     //  0.2-0.5 s per shard on one box — 4 logical shards, 2 x 2.9 GB: 1.1 s with 256 MB windows, 0.32 s with 16 MB)
-    uint64_t win = std::max(in->fa.size - in->off_a, in->fr.size - in->off_r) / ((uint64_t)n * 32);
-    win = std::min<uint64_t>(PW_SPLIT_WINDOW, std::max<uint64_t>(16ull << 20, win));
-    if (const char *e_mb = getenv("CELLECTOR_SPLIT_WINDOW_MB")) win = (uint64_t)atoll(e_mb) << 20;  // (tools/split_check.sh)
-    if (parse_window > 0) win = parse_window;
-    if (win < 4 * NL_SEG) win = 4 * NL_SEG;
-    win &= ~(uint64_t)(NL_SEG - 1);
+    const uint64_t win = pw_window(in, (uint64_t)n * 32, 16ull << 20, PW_SPLIT_WINDOW, "CELLECTOR_SPLIT_WINDOW_MB" /*tools/split_check.sh*/,
+                                   parse_window);
     uint64_t ma = 0, mr = 0;
     {
         const uint64_t nb_a = in->fa.size - in->off_a, nb_r = in->fr.size - in->off_r;
-        const uint64_t nw_a = (nb_a + win - 1) / win, nw_r = (nb_r + win - 1) / win;
+        const uint64_t nw_a = pw_windows(nb_a, win), nw_r = pw_windows(nb_r, win);
         const uint64_t hint = in->nnz_hint ? in->nnz_hint / (uint64_t)n + in->nnz_hint / (uint64_t)(8 * n) + 1024 : 0;
         PwBuffers B;
-        const uint64_t longest = std::max(nw_a, nw_r) / (uint64_t)n + 1;
-        SCHK(B.make(c, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, longest))));
+        SCHK(B.make(c, win, pw_ring(std::max(nw_a, nw_r) / (uint64_t)n + 1)));
         lap("upload buffers");
         // ranges of ceil(n_win / n) windows: rank 0 always holds window 0 (= line 0); late ranks of a short file may hold none
         const uint64_t pa = (nw_a + n - 1) / n, pr = (nw_r + n - 1) / n;
-        SCHK((parse_windowed<true>(c, in->fa, in->off_a, B, hint ? hint : nb_a / (12 * (uint64_t)n) + 1024, &l1, &c1, &a, &ma, bad,
-                                   std::min(nw_a, pa * rank), std::min(nw_a, pa * (rank + 1)))));
+        SCHK((parse_file<true>(c, in->fa, in->off_a, true, B, hint ? hint : nb_a / (12 * (uint64_t)n) + 1024, &l1, &c1, &a, &ma, bad,
+                               std::min(nw_a, pa * rank), std::min(nw_a, pa * (rank + 1)))));
         lap("alt range (upload + tokens)");
-        SCHK((parse_windowed<false>(c, in->fr, in->off_r, B, hint ? hint : nb_r / (12 * (uint64_t)n) + 1024, nullptr, nullptr, &r, &mr,
-                                    bad + 1, std::min(nw_r, pr * rank), std::min(nw_r, pr * (rank + 1)))));
+        SCHK((parse_file<false>(c, in->fr, in->off_r, true, B, hint ? hint : nb_r / (12 * (uint64_t)n) + 1024, nullptr, nullptr, &r, &mr,
+                                bad + 1, std::min(nw_r, pr * rank), std::min(nw_r, pr * (rank + 1)))));
         lap("ref range (upload + tokens)");
     }
-    e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)));
+    SCHK(ps.read(c, false));
     S->ma[rank] = ma; S->mr[rank] = mr; S->bad_a[rank] = h_bad[0]; S->bad_r[rank] = h_bad[1]; S->r_dev[rank] = r;
     lap("release buffers");
     SBARRIER();
@@ -948,7 +717,8 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     for (int k = 0; k < n; k++) {
         const uint64_t s0 = std::max(glo, g_lo(rbase, k)), s1 = std::min(ghi, g_hi(rbase, k));
         if (s0 >= s1) continue;
-        SCHK(copy_between(c, rk + (s0 - abase[rank]), c->device, S->r_dev[k] + (s0 - rbase[k]), S->device[k], (s1 - s0) * sizeof(uint32_t)));
+        e = dev_copy_sync(c->stream, rk + (s0 - abase[rank]), c->device, S->r_dev[k] + (s0 - rbase[k]), S->device[k], (s1 - s0) * sizeof(uint32_t));
+        if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "copy between shards failed: %s", hipGetErrorString(e)));
     }
     SBARRIER();  // (every shard has fetched what it needs out of the others' ref counts)
     lap("fetch ref counts");
@@ -956,16 +726,14 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     S->r_dev[rank] = nullptr;
     // ---- 3. zip + validation of this shard's lines, in place
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(count + 1)), dim3(PB), 0, c->stream, count, l1 + lo, c1 + lo, a + lo, rk + lo, TL, TC,
-                       (uint64_t)0, TC, (uint64_t *)nullptr, bad + 2, flags + 1);
-    uint32_t edge[2] = {0, 0};
-    e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && count) e = hipMemcpyAsync(&edge[0], l1 + lo, 4, hipMemcpyDeviceToHost, c->stream);
+                       (uint64_t)0, TC, (uint64_t *)nullptr, bad + 2, ps.flags + 1);
+    uint32_t edge[2] = {0, 0};  // (the first and the last locus token, queued in front of the status words' copy and its synchronise)
+    if (count) e = hipMemcpyAsync(&edge[0], l1 + lo, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && count) e = hipMemcpyAsync(&edge[1], l1 + lo + count - 1, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e)));
+    SCHK(ps.read(c, true));
     S->bad_z[rank] = h_bad[2] == ~0ull ? ~0ull : glo + (h_bad[2] >> PE_KIND_BITS);  // (local entry -> global, the kind beside it)
-    S->bad_kind[rank] = (uint32_t)(h_bad[2] & ((1u << PE_KIND_BITS) - 1)); S->unsorted[rank] = h_flags[1];
+    S->bad_kind[rank] = (uint32_t)(h_bad[2] & ((1u << PE_KIND_BITS) - 1)); S->unsorted[rank] = ps.h_flags[1];
     S->first_locus[rank] = edge[0]; S->last_locus[rank] = edge[1]; S->lines[rank] = count;
     SBARRIER();
     {
@@ -986,7 +754,7 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
             prev_last = S->last_locus[k];
             have_prev = true;
         }
-        *o_sorted = sorted;
+        out->sorted = sorted;
     }
     SCHK(dev_alloc(c, &alt16, count)); SCHK(dev_alloc(c, &ref16, count));
     if (count) hipLaunchKernelGGL(k_pair_take, dim3(pgrid(count)), dim3(PB), 0, c->stream, count, l1 + lo, c1 + lo, a + lo, rk + lo, alt16, ref16);
@@ -1009,36 +777,25 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
     for (int d = 0; d < n; d++) {
         uint64_t cb, ce;
         comm_range(c->comm, TC, d, &cb, &ce);
-        SCHK(ingest_split_coo(c, l1 + lo, c1 + lo, alt16, ref16, count, cb, ce, keep, &S->pl[rank][d], &S->pc[rank][d], &S->pa[rank][d],
-                              &S->pr[rank][d], &S->cnt[rank][d]));
+        SCHK(ingest_split_coo(c, CooView{l1 + lo, c1 + lo, alt16, ref16, count}, cb, ce, keep, &S->piece[rank][d]));
     }
     lap("zip + cut by owner");
     SBARRIER();
     // ---- 5. this shard's entries = the pieces meant for it, in rank order (= file order)
     uint64_t total = 0;
-    for (int k = 0; k < n; k++) total += S->cnt[k][rank];
-    DevBuf<uint32_t> fl, fc;
-    DevBuf<uint16_t> fa16, fr16;
-    SCHK(dev_alloc(c, &fl, total));
-    SCHK(dev_alloc(c, &fc, total));
-    SCHK(dev_alloc(c, &fa16, total));
-    SCHK(dev_alloc(c, &fr16, total));
+    for (int k = 0; k < n; k++) total += S->piece[k][rank].n;
+    SCHK(out->alloc(c, total));
     uint64_t at = 0;
     for (int k = 0; k < n; k++) {
-        const uint64_t m = S->cnt[k][rank];
-        SCHK(copy_between(c, fl + at, c->device, S->pl[k][rank], S->device[k], m * 4));
-        SCHK(copy_between(c, fc + at, c->device, S->pc[k][rank], S->device[k], m * 4));
-        SCHK(copy_between(c, fa16 + at, c->device, S->pa[k][rank], S->device[k], m * 2));
-        SCHK(copy_between(c, fr16 + at, c->device, S->pr[k][rank], S->device[k], m * 2));
+        const uint64_t m = S->piece[k][rank].n;
+        e = out->copy_from(c, at, S->piece[k][rank], S->device[k], m);
+        if (e != hipSuccess) SCHK(ctx_fail(c, CELLECTOR_EDEVICE, "copy between shards failed: %s", hipGetErrorString(e)));
         at += m;
     }
     SBARRIER();  // (the pieces this shard made have been fetched by their destinations)
-    for (int d = 0; d < n; d++) {
-        S->pl[rank][d].reset(); S->pc[rank][d].reset(); S->pa[rank][d].reset(); S->pr[rank][d].reset();
-    }
-    l1.reset(); c1.reset(); a.reset(); rk.reset(); flags.reset(); bad.reset(); keep.reset(); alt16.reset(); ref16.reset();
+    for (int d = 0; d < n; d++) S->piece[rank][d].reset();
+    l1.reset(); c1.reset(); a.reset(); rk.reset(); ps.flags.reset(); ps.bad.reset(); keep.reset(); alt16.reset(); ref16.reset();
     lap("gather own pieces");
-    *o_locus = std::move(fl); *o_cell = std::move(fc); *o_alt = std::move(fa16); *o_ref = std::move(fr16); *o_n = total;
 #undef SCHK
 #undef SBARRIER
     return CELLECTOR_OK;
@@ -1052,28 +809,16 @@ static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size
                                      DevBuf<uint32_t> *r_out, uint64_t *n_r, unsigned long long *bad_host)
 {
     HIPCHK(h, hipSetDevice(h->device));
-    DevBuf<unsigned long long> bad;
-    CHK(dev_alloc(h, &bad, 1));
-    unsigned long long none = ~0ull;
-    hipError_t e = hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    cellector_status st = e == hipSuccess ? CELLECTOR_OK : ctx_fail(h, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
-    if (st == CELLECTOR_OK) {
-        if (windowed) {
-            PwBuffers B;
-            st = B.make(h, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (fr.size - off_r + win - 1) / win)));
-            if (st == CELLECTOR_OK)
-                st = parse_windowed<false>(h, fr, off_r, B, nnz_hint, nullptr, nullptr, r_out, n_r, bad);
-        } else {
-            st = parse_whole<false>(h, fr, off_r, nullptr, nullptr, r_out, n_r, bad);
-        }
+    ParseStatus ps;  // (the helper uses word 0 for its file)
+    CHK(ps.init(h, false));
+    {
+        PwBuffers B;
+        if (windowed) CHK(B.make(h, win, pw_ring(pw_windows(fr.size - off_r, win))));
+        CHK((parse_file<false>(h, fr, off_r, windowed, B, nnz_hint, nullptr, nullptr, r_out, n_r, ps.bad)));
     }
-    if (st == CELLECTOR_OK) {
-        e = hipMemcpyAsync(bad_host, bad, sizeof none, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) st = ctx_fail(h, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
-    }
-    return st;
+    CHK(ps.read(h, false));
+    *bad_host = ps.h_bad[0];
+    return CELLECTOR_OK;
 }
 
 cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellector_ctx *helper)
@@ -1081,37 +826,26 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     FileBytes &fa = in->fa, &fr = in->fr;
     const size_t off_a = in->off_a, off_r = in->off_r;
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr
-    auto t_prev = std::chrono::steady_clock::now();
+    LapTimer t;
     auto lap = [&](const char *what) {
         if (!timing) return;
         (void)hipDeviceSynchronize();
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[timing]     %-22s %8.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-        t_prev = now;
+        fprintf(stderr, "[timing]     %-22s %8.3f s\n", what, t.lap());
     };
-    DevBuf<uint32_t> l1, c1, a, r, flags;
-    DevBuf<unsigned long long> bad;  // [0] alt file, [1] ref file: smallest line that does not parse; [2] zip stage
+    DevBuf<uint32_t> l1, c1, a, r;
+    ParseStatus ps;
     DevBuf<uint64_t> keep;
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(dev_alloc(c, &bad, 3)); CHK(dev_alloc(c, &flags, 4));
-    unsigned long long h_bad[3] = {~0ull, ~0ull, ~0ull};
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(bad, h_bad, sizeof h_bad, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, h_flags, sizeof h_flags, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+    CHK(ps.init(c));
+    unsigned long long *const bad = ps.bad, *const h_bad = ps.h_bad;
     // a multi-GB file goes through the device in windows (option parse_window forces a window size: tests); the token
     // arrays' capacity comes from the size line's entry count (a hint only: the reference never reads it)
     uint64_t n_a = 0, n_r = 0;
     // window: 1/96 of the bigger file, 32 MB .. PW_WINDOW.  (Pinning and releasing 3 x 256 MB of upload buffers is 0.1-0.15 s
     // of a 0.39 s ingest of 2 x 2.9 GB: 32 MB windows take 0.245 s there; at 2 x 31 GB the window size makes no difference,
     // 256 MB stays.  tools/window_sweep.sh)
-    uint64_t win = std::max(fa.size - off_a, fr.size - off_r) / 96;
-    win = std::min<uint64_t>(PW_WINDOW, std::max<uint64_t>(32ull << 20, win));
-    if (const char *e_mb = getenv("CELLECTOR_WINDOW_MB")) win = (uint64_t)atoll(e_mb) << 20;  // (the sweep)
-    if (c->parse_window_opt > 0) win = (uint64_t)c->parse_window_opt;
-    if (win < 4 * NL_SEG) win = 4 * NL_SEG;
-    win &= ~(uint64_t)(NL_SEG - 1);
+    const uint64_t win = pw_window(in, 96, 32ull << 20, PW_WINDOW, "CELLECTOR_WINDOW_MB" /*the sweep*/,
+                                   c->parse_window_opt > 0 ? (uint64_t)c->parse_window_opt : 0);
     const bool win_a = c->parse_window_opt > 0 || !fa.data || fa.size - off_a >= PW_MIN;
     const bool win_r = c->parse_window_opt > 0 || !fr.data || fr.size - off_r >= PW_MIN;
     if (helper) {  // the ref file on the helper's device, concurrently (its own ring of window buffers, its own stream)
@@ -1122,10 +856,8 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
         cellector_status st_a = CELLECTOR_OK;
         {
             PwBuffers B;
-            if (win_a) st_a = B.make(c, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (fa.size - off_a + win - 1) / win)));
-            if (st_a == CELLECTOR_OK)
-                st_a = win_a ? parse_windowed<true>(c, fa, off_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad)
-                             : parse_whole<true>(c, fa, off_a, &l1, &c1, &a, &n_a, bad);
+            if (win_a) st_a = B.make(c, win, pw_ring(pw_windows(fa.size - off_a, win)));
+            if (st_a == CELLECTOR_OK) st_a = parse_file<true>(c, fa, off_a, win_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad);
         }
         th.join();
         (void)hipSetDevice(c->device);
@@ -1173,23 +905,17 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
         PwBuffers B;  // one ring of window buffers for both files
         if (win_a || win_r) {
             const uint64_t longest = std::max(win_a ? fa.size - off_a : 0, win_r ? fr.size - off_r : 0);
-            CHK(B.make(c, win, (int)std::min<uint64_t>(PW_NB, std::max<uint64_t>(1, (longest + win - 1) / win))));
+            CHK(B.make(c, win, pw_ring(pw_windows(longest, win))));
         }
-        if (win_a) CHK((parse_windowed<true>(c, fa, off_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad)));
-        else CHK((parse_whole<true>(c, fa, off_a, &l1, &c1, &a, &n_a, bad)));
+        CHK((parse_file<true>(c, fa, off_a, win_a, B, in->nnz_hint, &l1, &c1, &a, &n_a, bad)));
         lap("alt file (upload + tokens)");
-        if (win_r)
-            CHK((parse_windowed<false>(c, fr, off_r, B, in->nnz_hint, nullptr, nullptr, &r, &n_r, bad + 1)));
-        else
-            CHK((parse_whole<false>(c, fr, off_r, nullptr, nullptr, &r, &n_r, bad + 1)));
+        CHK((parse_file<false>(c, fr, off_r, win_r, B, in->nnz_hint, nullptr, nullptr, &r, &n_r, bad + 1)));
         lap("ref file (upload + tokens)");
         if (premap.joinable()) premap.join();
         lap("wait for the pre-mapped blocks");
     }
     const uint64_t n = std::min(n_a, n_r);  // izip!: stops at the shorter file
-    e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+    CHK(ps.read(c, false));
     {   // (a line beyond the shorter file is never read by the reference: only failures among the first n count)
         const unsigned long long first = std::min(h_bad[0], h_bad[1]);
         if (first < n)
@@ -1198,34 +924,27 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     const bool all_cells = c->cell_begin == 0 && c->cell_end >= c->total_cells;
     if (!all_cells) CHK(dev_alloc(c, &keep, n + 1));
     hipLaunchKernelGGL(k_pair_check, dim3(pgrid(n + 1)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->total_loci, c->total_cells,
-                       c->cell_begin, c->cell_end, keep, bad + 2, flags + 1);
-    // the validation result is read BEHIND k_pair_check on the ctx's stream (a caller-supplied non-blocking stream does
-    // not order against null-stream copies: the range check could be read before the kernel ran)
-    e = hipMemcpyAsync(h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+                       c->cell_begin, c->cell_end, keep, bad + 2, ps.flags + 1);
+    CHK(ps.read(c, true));  // (the range check's result)
     if (h_bad[2] != ~0ull) {
         return ctx_fail(c, CELLECTOR_EINVAL, "mtx entry %llu: %s", h_bad[2] >> PE_KIND_BITS, pe_kind_text(h_bad[2]));
     }
-    c->coo_sorted = h_flags[1] == 0;
+    c->coo.sorted = ps.h_flags[1] == 0;
     if (all_cells) {
-        c->coo_n = n;
-        CHK(dev_alloc(c, &c->coo_alt, n)); CHK(dev_alloc(c, &c->coo_ref, n));
-        if (n) hipLaunchKernelGGL(k_pair_take, dim3(pgrid(n)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->coo_alt, c->coo_ref);
-        c->coo_locus = std::move(l1);  // (the token arrays are the staged COO)
-        c->coo_cell = std::move(c1);
+        c->coo.n = n;
+        CHK(dev_alloc(c, &c->coo.alt, n)); CHK(dev_alloc(c, &c->coo.ref, n));
+        if (n) hipLaunchKernelGGL(k_pair_take, dim3(pgrid(n)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->coo.alt, c->coo.ref);
+        c->coo.locus = std::move(l1);  // (the token arrays are the staged COO)
+        c->coo.cell = std::move(c1);
     } else {
         uint64_t kept = 0;
         CHK(dev_exclusive_scan_u64(c, keep, n + 1, &kept));
-        c->coo_n = kept;
-        CHK(dev_alloc(c, &c->coo_locus, kept)); CHK(dev_alloc(c, &c->coo_cell, kept));
-        CHK(dev_alloc(c, &c->coo_alt, kept)); CHK(dev_alloc(c, &c->coo_ref, kept));
+        CHK(c->coo.alloc(c, kept));
         if (n)
             hipLaunchKernelGGL(k_pair_fill, dim3(pgrid(n)), dim3(PB), 0, c->stream, n, l1, c1, a, r, c->cell_begin, c->cell_end,
-                               keep, c->coo_locus, c->coo_cell, c->coo_alt, c->coo_ref);
+                               keep, c->coo.locus, c->coo.cell, c->coo.alt, c->coo.ref);
     }
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     lap("tokenise + zip + filter");
     if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));

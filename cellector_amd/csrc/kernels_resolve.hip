@@ -204,18 +204,18 @@ __global__ void k_res_scatter(uint64_t n, const uint32_t *__restrict__ locus, co
 cellector_status resolve_build_file_order(cellector_ctx *c)
 {
     c->res_ent.reset();
-    const uint64_t n = c->coo_n;
+    const uint64_t n = c->coo.n;
     DevBuf<uint64_t> pos, val;
     DevBuf<uint32_t> key, key_o;
     CHK(dev_alloc(c, &pos, n + 1));
-    hipLaunchKernelGGL(k_res_used, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, c->stream, n, c->coo_locus, c->to_used, pos);
+    hipLaunchKernelGGL(k_res_used, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, c->stream, n, c->coo.locus, c->to_used, pos);
     HIPCHK(c, hipGetLastError());
     uint64_t m = 0;
     CHK(dev_exclusive_scan_u64(c, pos, n + 1, &m));
     CHK(dev_alloc(c, &key, m)); CHK(dev_alloc(c, &key_o, m)); CHK(dev_alloc(c, &val, m)); CHK(dev_alloc(c, &c->res_ent, m));
     if (n)
-        hipLaunchKernelGGL(k_res_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, c->coo_locus, c->coo_cell,
-                           c->coo_alt, c->coo_ref, c->to_used, pos, key, val);
+        hipLaunchKernelGGL(k_res_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, c->coo.locus, c->coo.cell,
+                           c->coo.alt, c->coo.ref, c->to_used, pos, key, val);
     HIPCHK(c, hipGetLastError());
     int bits = 1;
     while (bits < 32 && (1ull << bits) < c->nloc) bits++;

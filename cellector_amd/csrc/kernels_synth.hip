@@ -175,14 +175,12 @@ cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed,
     HIPCHK(c, hipGetLastError());
     uint64_t n = 0;
     CHK(dev_exclusive_scan_u64(c, tiles, ntiles + 1, &n));
-    c->coo_n = n;
-    c->coo_sorted = true;
-    CHK(dev_alloc(c, &c->coo_locus, n)); CHK(dev_alloc(c, &c->coo_cell, n));
-    CHK(dev_alloc(c, &c->coo_alt, n)); CHK(dev_alloc(c, &c->coo_ref, n));
+    c->coo.sorted = true;
+    CHK(c->coo.alloc(c, n));
     for (uint64_t t0 = 0; t0 < ntiles; t0 += max_grid) {
         const uint64_t g = ntiles - t0 < max_grid ? ntiles - t0 : max_grid;
-        hipLaunchKernelGGL(k_synth_fill, dim3((unsigned)g), dim3(SY_BLOCK), 0, c->stream, p, t0, tiles, c->coo_locus,
-                           c->coo_cell, c->coo_alt, c->coo_ref);
+        hipLaunchKernelGGL(k_synth_fill, dim3((unsigned)g), dim3(SY_BLOCK), 0, c->stream, p, t0, tiles, c->coo.locus,
+                           c->coo.cell, c->coo.alt, c->coo.ref);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -226,8 +224,8 @@ __global__ __launch_bounds__(256) void k_mtx_lines(uint64_t n, uint64_t cell_beg
 
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path)
 {
-    if (!c->coo_locus && c->coo_n) return ctx_fail(c, CELLECTOR_EINVAL, "write_staged_mtx: no staged matrix (option keep_coo=1)");
-    const uint64_t n = c->coo_n, CH = 1ull << 25;  // 32M lines per chunk: at most 26 bytes each
+    if (!c->coo.locus && c->coo.n) return ctx_fail(c, CELLECTOR_EINVAL, "write_staged_mtx: no staged matrix (option keep_coo=1)");
+    const uint64_t n = c->coo.n, CH = 1ull << 25;  // 32M lines per chunk: at most 26 bytes each
     FILE *f[2] = {fopen(alt_path, "wb"), fopen(ref_path, "wb")};
     DevBuf<uint64_t> off;
     DevBuf<uint8_t> dbuf;
@@ -244,15 +242,15 @@ cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const c
         const uint64_t m = n - i0 < CH ? n - i0 : CH;
         const unsigned g = (unsigned)((m + 255) / 256);
         for (int k = 0; k < 2 && st == CELLECTOR_OK; k++) {
-            const uint16_t *val = (k == 0 ? c->coo_alt : c->coo_ref) + i0;
+            const uint16_t *val = (k == 0 ? c->coo.alt : c->coo.ref) + i0;
             uint64_t bytes = 0;
             hipError_t e = hipMemsetAsync(off + m, 0, 8, c->stream);
-            hipLaunchKernelGGL(k_mtx_lines<false>, dim3(g), dim3(256), 0, c->stream, m, c->cell_begin, c->coo_locus + i0,
-                               c->coo_cell + i0, val, off, (uint8_t *)nullptr);
+            hipLaunchKernelGGL(k_mtx_lines<false>, dim3(g), dim3(256), 0, c->stream, m, c->cell_begin, c->coo.locus + i0,
+                               c->coo.cell + i0, val, off, (uint8_t *)nullptr);
             if (e == hipSuccess) st = dev_exclusive_scan_u64(c, off, m + 1, &bytes);
             if (st != CELLECTOR_OK) break;
-            hipLaunchKernelGGL(k_mtx_lines<true>, dim3(g), dim3(256), 0, c->stream, m, c->cell_begin, c->coo_locus + i0,
-                               c->coo_cell + i0, val, off, dbuf);
+            hipLaunchKernelGGL(k_mtx_lines<true>, dim3(g), dim3(256), 0, c->stream, m, c->cell_begin, c->coo.locus + i0,
+                               c->coo.cell + i0, val, off, dbuf);
             if (e == hipSuccess) e = hipMemcpyAsync(hbuf, dbuf, bytes, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { st = ctx_fail(c, CELLECTOR_EDEVICE, "write_staged_mtx: %s", hipGetErrorString(e)); break; }

@@ -257,7 +257,7 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
             MtxInput *in = nullptr;
             uint64_t tl = 0, tc = 0;
             if (hipSetDevice(s0->device) != hipSuccess) return ctx_fail(root, CELLECTOR_EDEVICE, "hipSetDevice failed");
-            cellector_status st = mtx_input_open(s0, alt_path, ref_path, &in, &tl, &tc);
+            cellector_status st = ctx_mtx_open(s0, alt_path, ref_path, &in, &tl, &tc);
             if (st != CELLECTOR_OK) { root->err = s0->err; return st; }
             if (mtx_input_windowed(in, s0->parse_window_opt)) {
                 const int n = (int)m->shards.size();
@@ -269,13 +269,10 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
                 if (!S) { mtx_input_close(in); return ctx_fail(root, CELLECTOR_ENOMEM, "out of host memory"); }
                 const uint64_t window = s0->parse_window_opt > 0 ? (uint64_t)s0->parse_window_opt : 0;
                 st = run_all(root, [=](cellector_ctx *s, int rank) {
-                    DevBuf<uint32_t> pl, pc;
-                    DevBuf<uint16_t> pa, pr;
-                    uint64_t cnt = 0;
-                    bool sorted = false;
-                    cellector_status r = ingest_stage_mtx_split(s, in, S, rank, window, &pl, &pc, &pa, &pr, &cnt, &sorted);
+                    StagedCoo mine;
+                    cellector_status r = ingest_stage_mtx_split(s, in, S, rank, window, &mine);
                     if (r != CELLECTOR_OK) return r;
-                    return ffi_adopt_staged(s, tl, tc, std::move(pl), std::move(pc), std::move(pa), std::move(pr), cnt, sorted);
+                    return ffi_adopt_staged(s, tl, tc, std::move(mine));
                 });
                 if (st == CELLECTOR_ECOMM)  // (report the shard that failed, not one of those it released)
                     for (size_t r = 0; r < m->shards.size(); r++)
@@ -305,22 +302,17 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
     cellector_status st = ffi_stage_mtx_all_cells(s0, alt_path, ref_path, helper);
     if (st != CELLECTOR_OK) return fail(s0, st);
     // detach the all-cells arrays from shard 0 (its own piece is cut from them like the others')
-    cellector_ctx all;  // (a plain holder: no device state of its own is created or destroyed)
-    all.device = s0->device; all.stream = s0->stream;
-    all.coo_locus = std::move(s0->coo_locus); all.coo_cell = std::move(s0->coo_cell);
-    all.coo_alt = std::move(s0->coo_alt); all.coo_ref = std::move(s0->coo_ref);
-    all.coo_n = s0->coo_n;
-    const bool sorted = s0->coo_sorted;
+    StagedCoo all = std::move(s0->coo);
+    s0->coo.reset();
     const uint64_t TL = s0->total_loci, TC = s0->total_cells;
-    s0->coo_n = 0;
     DevBuf<uint64_t> keep;
-    st = dev_alloc(&all, &keep, all.coo_n + 1);
+    st = dev_alloc(s0, &keep, all.n + 1);
     const int n = (int)m->shards.size();
     if (st == CELLECTOR_OK && m->balance && !m->user_partition && n > 1) {  // the ranges: cut by entries per cell
         std::vector<uint32_t> epc;
-        st = ingest_cell_histogram(&all, all.coo_cell, all.coo_n, TC, &epc);
+        st = ingest_cell_histogram(s0, all.cell, all.n, TC, &epc);
         if (st == CELLECTOR_OK) set_ranges(m, epc.data(), TC);
-        else root->err = all.err;
+        else root->err = s0->err;
     } else if (st == CELLECTOR_OK) {
         set_ranges(m, nullptr, TC);
     }
@@ -328,39 +320,31 @@ cellector_status multi_ingest_mtx(cellector_ctx *root, const char *alt_path, con
         cellector_ctx *s = m->shards[(size_t)r];
         uint64_t cb, ce;
         comm_range(s->comm, TC, r, &cb, &ce);
-        DevBuf<uint32_t> pl, pc;
-        DevBuf<uint16_t> pa, pr;
-        uint64_t cnt = 0;
-        (void)hipSetDevice(all.device);
-        st = ingest_split_coo(&all, all.coo_locus, all.coo_cell, all.coo_alt, all.coo_ref, all.coo_n, cb, ce, keep, &pl, &pc, &pa, &pr, &cnt);
-        if (st != CELLECTOR_OK) { root->err = all.err; break; }
-        if (s->device != all.device) {  // move the piece to the shard's device
-            DevBuf<uint32_t> ql, qc;
-            DevBuf<uint16_t> qa, qr;
+        StagedCoo piece;
+        (void)hipSetDevice(s0->device);
+        st = ingest_split_coo(s0, all.view(), cb, ce, keep, &piece);
+        if (st != CELLECTOR_OK) { root->err = s0->err; break; }
+        if (s->device != s0->device) {  // move the piece to the shard's device
+            StagedCoo there;
             (void)hipSetDevice(s->device);
-            st = dev_alloc(s, &ql, cnt);
-            if (st == CELLECTOR_OK) st = dev_alloc(s, &qc, cnt);
-            if (st == CELLECTOR_OK) st = dev_alloc(s, &qa, cnt);
-            if (st == CELLECTOR_OK) st = dev_alloc(s, &qr, cnt);
-            if (st == CELLECTOR_OK && cnt &&
-                (dev_copy_sync(s->stream, ql, s->device, pl, all.device, cnt * 4) != hipSuccess ||
-                 dev_copy_sync(s->stream, qc, s->device, pc, all.device, cnt * 4) != hipSuccess ||
-                 dev_copy_sync(s->stream, qa, s->device, pa, all.device, cnt * 2) != hipSuccess ||
-                 dev_copy_sync(s->stream, qr, s->device, pr, all.device, cnt * 2) != hipSuccess))
-                st = ctx_fail(s, CELLECTOR_EDEVICE, "peer copy of the shard's entries failed: %s", hipGetErrorString(hipGetLastError()));
-            (void)hipSetDevice(all.device);
-            pl.reset(); pc.reset(); pa.reset(); pr.reset();
+            st = there.alloc(s, piece.n);
+            if (st == CELLECTOR_OK) {
+                const hipError_t e = there.copy_from(s, 0, piece, s0->device, piece.n);
+                if (e != hipSuccess) st = ctx_fail(s, CELLECTOR_EDEVICE, "peer copy of the shard's entries failed: %s", hipGetErrorString(e));
+            }
+            (void)hipSetDevice(s0->device);
+            piece.reset();
             if (st != CELLECTOR_OK) { fail(s, st); break; }
-            pl = std::move(ql); pc = std::move(qc); pa = std::move(qa); pr = std::move(qr);
+            piece = std::move(there);
         }
+        piece.sorted = all.sorted;
         (void)hipSetDevice(s->device);
-        st = ffi_adopt_staged(s, TL, TC, std::move(pl), std::move(pc), std::move(pa), std::move(pr), cnt, sorted);
+        st = ffi_adopt_staged(s, TL, TC, std::move(piece));
         if (st != CELLECTOR_OK) fail(s, st);
     }
-    (void)hipSetDevice(all.device);
+    (void)hipSetDevice(s0->device);
     keep.reset();
-    all.coo_locus.reset(); all.coo_cell.reset(); all.coo_alt.reset(); all.coo_ref.reset();
-    all.stream = nullptr;
+    all.reset();
     return st;
 }
 cellector_status multi_ingest_coo(cellector_ctx *root, uint64_t total_loci, uint64_t total_cells, uint64_t nnz, const uint32_t *locus0,

@@ -23,7 +23,7 @@ The contract
            shorter file's line count is never read and is no error.
 
 Not covered: Unicode whitespace and bytes that are not UTF-8 (the Rust reader treats them differently from an ASCII
-tokeniser), and the .gz readers.
+tokeniser).  The .gz readers: tests/test_host_mtx_bytes.py.
 """
 import random
 from collections import namedtuple
