@@ -380,6 +380,9 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         if (v && (c->multi || comm_active(c->comm)))
             return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties works on a single-device ctx: a sharded run would need the candidates of every shard");
         if (c->multi) return CELLECTOR_OK;  // (0 on a multi-device ctx: nothing to switch off)
+        if (v && c->normalization)
+            return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties with normalization 1: the reference has no arithmetic of the z-score "
+                                                 "mode to resolve to (set normalization 0 first)");
         if (v && c->state == cellector_ctx::ST_READY && c->nnz && !c->res_ent)
             return ctx_fail(c, CELLECTOR_EINVAL, "resolve_ties keeps every cell's entries in file order at the ingest: set it before the ingest");
         if (v && !ref_log_matches_host())
@@ -403,7 +406,24 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         return CELLECTOR_OK;
     }
     if (c->multi) return multi_set_option(c, key, v);
-    if (!strcmp(key, "compute_expected")) c->compute_expected = v != 0;
+    if (!strcmp(key, "compute_expected")) {
+        if (!v && c->normalization)
+            return ctx_fail(c, CELLECTOR_EINVAL, "compute_expected 0 with normalization 1: the z-score needs the expected term "
+                                                 "(set normalization 0 first)");
+        c->compute_expected = v != 0;
+    }
+    else if (!strcmp(key, "cell_variance")) c->cell_variance = v != 0;
+    else if (!strcmp(key, "normalization")) {
+        if (v != 0 && v != 1)
+            return ctx_fail(c, CELLECTOR_EINVAL, "normalization must be 0 (log-likelihood per used locus, main.rs:316) or 1 (z-score, main.rs:317-318)");
+        if (v && c->resolve_ties)
+            return ctx_fail(c, CELLECTOR_EINVAL, "normalization 1 with resolve_ties %d: the reference has no arithmetic of the z-score "
+                                                 "mode to resolve to (set resolve_ties 0 first)", c->resolve_ties);
+        if (v && !c->compute_expected)
+            return ctx_fail(c, CELLECTOR_EINVAL, "normalization 1 with compute_expected 0: the z-score needs the expected term "
+                                                 "(set compute_expected 1 first)");
+        c->normalization = (int)v;
+    }
     else if (!strcmp(key, "ref_arith")) {
         if (v && c->engine != 1) return ctx_fail(c, CELLECTOR_EINVAL, "ref_arith evaluates every entry with the reference's ln_gamma arithmetic: an engine 1 option (set engine 1 first)");
         c->ref_arith = v != 0;
@@ -904,6 +924,10 @@ cellector_status cellector_em_begin(cellector_ctx *c)
                                          : launch_cell_ll(c, c->ab, c->x_norm + c->cell_begin);
     c->work_zeroed = false;  // (only this iteration's first tile pass may rely on k_alpha_beta's reset)
     CHK(st);
+    // options cell_variance / normalization: expected_log_variances under this iteration's alpha/beta, and the z-scores over
+    // this shard's slice of NORM (main.rs:317-318)
+    c->iter_var = c->cell_variance || c->normalization != 0;
+    if (c->iter_var) CHK(launch_cell_variance(c, c->normalization != 0, c->x_norm + c->cell_begin));
     c->em_phase = 1;
     return CELLECTOR_OK;
 }
@@ -1000,6 +1024,7 @@ cellector_status cellector_em_finish(cellector_ctx *c, cellector_iter_summary *o
     c->n_excluded_global = (uint64_t)cnt[LC_N_EXCLUDED];
     c->iteration++;
     c->have_iter = true;
+    c->var_formed = c->iter_var;
     c->em_phase = 0;
     // (timers are read out when asked for — cellector_kernel_time — not here: waiting for the last event pair and destroying
     //  the events is host time on the path to the next iteration's first launch; a long run is drained now and then)
@@ -1120,11 +1145,13 @@ cellector_status cellector_em_reset(cellector_ctx *c)
     HIPCHK(c, hipMemsetAsync(c->nloci, 0, (n ? n : 1) * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (c->n_norm ? c->n_norm : 1) * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->x_locus, 0, ((uint64_t)LB_PLANES * L + LC_COUNTERS) * 8, c->stream));
+    if (c->var) HIPCHK(c, hipMemsetAsync(c->var, 0, (n ? n : 1) * 8, c->stream));
     if (c->tiled_ready) {
         HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (n ? n : 1) * 4, c->stream));
         HIPCHK(c, hipMemsetAsync(c->flag_bits, 0, ((n + 31) / 32 + 1) * 4, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->var_formed = false;
     c->iteration = 0; c->have_iter = false; c->n_excluded_global = 0; c->n_masked_loci = 0;
     c->last_median = c->last_iqr = c->last_thr = 0;
     return CELLECTOR_OK;
@@ -1281,6 +1308,33 @@ cellector_status cellector_cell_pmfs(cellector_ctx *c, const double *alpha, cons
     SETDEV(c);
     return pmfs_run(c, alpha, beta, mask, cells, n_cells, rec_ptr, capacity, locus_index, alt, ref, log_pmf, expected_log_pmf,
                     expected_log_variance);
+}
+
+// expected_log_variances (main.rs:587) under caller alpha/beta/mask: kernels_variance.hip
+cellector_status cellector_cell_log_variances(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask,
+                                              double *expected_log_variance)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return multi_cell_log_variances(c, alpha, beta, mask, expected_log_variance);
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "cell_log_variances: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, (alpha && beta) || c->L == 0, "cell_log_variances: null alpha/beta");
+    REQUIRE(c, expected_log_variance || c->nloc == 0, "cell_log_variances: null output");
+    SETDEV(c);
+    return variance_run(c, alpha, beta, mask, expected_log_variance);
+}
+
+cellector_status cellector_iter_cell_variances(const cellector_ctx *c, double *out)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return multi_iter_cell_variances(c, out);
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "iter_cell_variances: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, c->var_formed, "iter_cell_variances: not formed (the last finished iteration ran with options cell_variance and "
+                              "normalization both 0, or none has finished since the load / cellector_em_reset)");
+    REQUIRE(c, out || c->nloc == 0, "iter_cell_variances: null output");
+    if (c->nloc == 0) return CELLECTOR_OK;
+    return d2h(c, out, c->var, c->nloc * 8);
 }
 
 // ---- posteriors ---------------------------------------------------------------------------------------

@@ -144,6 +144,11 @@ struct CtxOptions {
     // option resolve_posteriors (kernels_assign.hip; single device): cellector_assign evaluates the cells whose label or qual
     // could differ from the reference's (1) or every cell (2) with the reference's arithmetic.  0 off.
     int resolve_posteriors = 0;
+    // option cell_variance (kernels_variance.hip): every cell pass of the loop also forms expected_log_variances (main.rs:587)
+    bool cell_variance = false;
+    // option normalization: 0 = ll / loci_used (main.rs:316), 1 = the z-score of main.rs:317-318 (implies the variance pass);
+    // read by em_begin
+    int normalization = 0;
     int side_lds = -1;               // option "side_lds": dynamic LDS bytes requested by the cell-side overflow kernel (residency
                                      // throttle; -1 = automatic)
     int ovf_deep_opt = -1;           // option "ovf_deep": -1 = decided per matrix (tiled_build), 0 / 1 = forced
@@ -184,6 +189,8 @@ struct CtxMatrix {
     DevBuf<uint8_t> flags, flags_new;  // [nloc] exclusion set
     DevBuf<double> ll, ell, nloci;     // [nloc]
     DevBuf<double> post;               // [4*nloc] posterior, doublet, ll_maj, ll_min
+    DevBuf<double> var;                // [nloc] expected_log_variances of the last cell pass that formed them (made on first use)
+    DevBuf<double> var_tab;            // [L][18] that pass' per-locus variances of the totals 0..17, then [L][4] a compact copy of 1..4 (k_var_tables)
 
     // exchange buffers: the library's own (x_*_own) or one the caller bound (a bound PASS1 buffer is kept across a reload)
     double *x_pass1 = nullptr, *x_norm = nullptr, *x_locus = nullptr;
@@ -301,6 +308,8 @@ struct CtxCarry {
     bool tally_valid = false;   // tally / cnt2 hold the counts of the current exclusion set (flags): set by em_finish, cleared by
                                 // the locus pass (until its flag swap), a reload and an engine switch
     int res_last_mode = 0;      // resolve_ties of the last iteration (cellector_iter_resolution)
+    bool iter_var = false;      // the iteration in flight formed c->var (em_begin)
+    bool var_formed = false;    // ... and so did the last finished one (cellector_iter_cell_variances); cleared by em_reset
     // what the last cellector_assign resolved (cellector_assign_resolution / _resolved_cells)
     int pa_last_mode = 0;
     uint64_t pa_labels_changed = 0, pa_qual_changed = 0;
@@ -445,6 +454,10 @@ cellector_status launch_ab_posterior_into(cellector_ctx *c, double mf0, double *
 cellector_status pmfs_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
                           uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt, uint32_t *ref,
                           double *log_pmf, double *expected_log_pmf, double *expected_log_variance);
+// expected_log_variances (kernels_variance.hip): the loop's pass into c->var under c->ab, with zscore also main.rs:317-318 over
+// norm_out; and cellector_cell_log_variances on one device, scratch of its own
+cellector_status launch_cell_variance(cellector_ctx *c, bool zscore, double *norm_out);
+cellector_status variance_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, double *out /*[nloc] host*/);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);

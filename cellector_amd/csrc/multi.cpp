@@ -415,6 +415,16 @@ cellector_status multi_cell_log_likelihoods(cellector_ctx *root, const double *a
         return cellector_cell_log_likelihoods(s, alpha, beta, mask, ll ? ll + b : nullptr, ell ? ell + b : nullptr, nl ? nl + b : nullptr);
     });
 }
+cellector_status multi_cell_log_variances(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, double *out)
+{
+    if (!out) return ctx_fail(root, CELLECTOR_EINVAL, "cell_log_variances: null output");
+    return per_cell(root, [=](cellector_ctx *s, uint64_t b) { return cellector_cell_log_variances(s, alpha, beta, mask, out + b); });
+}
+cellector_status multi_iter_cell_variances(const cellector_ctx *root, double *out)
+{
+    if (!out) return ctx_fail(root, CELLECTOR_EINVAL, "iter_cell_variances: null output");
+    return per_cell(root, [=](cellector_ctx *s, uint64_t b) { return cellector_iter_cell_variances(s, out + b); });
+}
 // The list is routed to the owning shards (global ids made local, list order kept inside a shard); every shard counts, the
 // counts give rec_ptr in list order, every shard fills arrays of its own and its cells' records are copied to their places.
 cellector_status multi_cell_pmfs(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,

@@ -18,6 +18,8 @@ cellector_status multi_dims(const cellector_ctx *root, cellector_dims_t *o);
 cellector_status multi_entries_per_cell(const cellector_ctx *root, uint32_t *out);
 cellector_status multi_excluded(const cellector_ctx *root, uint8_t *out);
 cellector_status multi_iter_cell_outputs(const cellector_ctx *root, double *ll, double *ell, double *nl, double *norm);
+cellector_status multi_iter_cell_variances(const cellector_ctx *root, double *out);
+cellector_status multi_cell_log_variances(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, double *out);
 cellector_status multi_cell_log_likelihoods(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask,
                                             double *ll, double *ell, double *nl);
 cellector_status multi_cell_pmfs(cellector_ctx *root, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CELLECTOR_HIP_LIB") or os.path.join(_HERE, "libcellector_hip.so")
 
 XCHG_PASS1, XCHG_NORM, XCHG_LOCUS = 0, 1, 2
-K_CELL_LL, K_LOCUS_STATS, K_SELECT, K_POSTERIOR, K_TILE_LL = 0, 1, 2, 3, 4
+K_CELL_LL, K_LOCUS_STATS, K_SELECT, K_POSTERIOR, K_TILE_LL, K_CELL_VAR = 0, 1, 2, 3, 4, 5
 STATUS_NAMES = {0: "OK", 1: "EINVAL", 2: "EIO", 3: "EPARSE", 4: "ENOMEM", 5: "EDEVICE", 6: "ECOMM"}
 
 # every entry point include/cellector_ffi.h declares: name -> (restype, argtypes)
@@ -62,6 +62,8 @@ SIGNATURES = {
     "cellector_alpha_betas": (_i, [_vp, _vp, _vp]),
     "cellector_cell_log_likelihoods": (_i, [_vp] + [_vp] * 6),
     "cellector_cell_pmfs": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64] + [_vp] * 6),
+    "cellector_cell_log_variances": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "cellector_iter_cell_variances": (_i, [_vp, _vp]),
     "cellector_posterior_alpha_betas": (_i, [_vp, _i, _vp, _vp]),
     "cellector_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
@@ -406,6 +408,28 @@ class Cellector:
             self._ck(self._lib.cellector_cell_pmfs(*head, n, *[_p(a) for a in ints + flts]))
         keys = ["locus_index", "alt", "ref", "log_pmf", "expected_log_pmf", "expected_log_variance"]
         return dict(rec_ptr=rp, **dict(zip(keys, ints + flts)))
+
+    def _per_cell_f64(self):
+        """an output array of the local cells; None before a load (the library then refuses the call with its own message)"""
+        return np.zeros(self.n_local, np.float64) if self.dims().total_cells else None
+
+    def cell_log_variances(self, alpha, beta, mask=None):
+        """expected_log_variances, the fourth vector of get_cell_log_likelihoods (main.rs:587), under the given alpha / beta /
+        mask (cellector_cell_log_variances): per local cell the sum of cell_pmfs()'s expected_log_variance column.  The ctx is
+        left as it was."""
+        alpha = np.ascontiguousarray(alpha, np.float64)
+        beta = np.ascontiguousarray(beta, np.float64)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = self._per_cell_f64()
+        self._ck(self._lib.cellector_cell_log_variances(self.h, _p(alpha), _p(beta), _p(mask), _p(out)))
+        return out
+
+    def cell_variances(self):
+        """The last iteration's expected_log_variances (cellector_iter_cell_variances); an error unless that iteration ran with
+        option cell_variance or normalization set."""
+        out = self._per_cell_f64()
+        self._ck(self._lib.cellector_iter_cell_variances(self.h, _p(out)))
+        return out
 
     def posterior_alpha_betas(self, which):
         """(alpha, beta) of calculate_posteriors' distribution `which` for the current exclusion set: 0 minority, 1 majority,

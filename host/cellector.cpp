@@ -173,6 +173,7 @@ struct Params {
     bool devices_auto = false;                         // --devices auto: as many visible GPUs as the input can feed
     bool resolve_near_ties = false;                    // extension: option resolve_ties (single GPU)
     int resolve_assignments = 0;                       // extension: options resolve_ties + resolve_posteriors = 1 (true) / 2 (all)
+    bool zscore = false;                               // extension: option normalization = 1 (main.rs:317-318)
     std::optional<std::string> initial_minority;       // extension: barcodes of the initial exclusion set (main.rs:37 starts from none)
     std::optional<std::string> cell_detail;            // extension: barcodes whose per-locus records go to cell_detail.tsv (main.rs:176's TODO)
 };
@@ -206,6 +207,13 @@ const char *USAGE =
     "                                                                       own arithmetic: cellector_assignments.tsv then has the reference's\n"
     "                                                                       labels and quals (all: its bytes) (not in the reference; default\n"
     "                                                                       false; one GPU)\n"
+    "        --normalization <per_locus|zscore>                             the outlier score of a cell: its log likelihood per used locus (the\n"
+    "                                                                       reference's, default) or the z-score (log likelihood - expected) /\n"
+    "                                                                       sqrt(expected variance) the reference's author left commented out;\n"
+    "                                                                       zscore adds a column expected_log_variance to iteration_N.tsv and\n"
+    "                                                                       cannot be used with --resolve_near_ties true / --resolve_assignments\n"
+    "                                                                       (not in the reference; --interquartile_range_multiple's default was\n"
+    "                                                                       chosen for per_locus)\n"
     "        --initial_minority <file>                                      start the loop from these cells as the excluded (minority) set\n"
     "                                                                       instead of the empty set: one barcode per line, first tab-separated\n"
     "                                                                       column (a filtered cellector_assignments.tsv works), blank lines\n"
@@ -240,7 +248,7 @@ Params load_params(int argc, char **argv)
     static const char *known[] = {"output_directory", "ref", "alt", "barcodes", "min_alt", "min_ref", "ground_truth",
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
-                                  "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail"};
+                                  "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -298,6 +306,17 @@ Params load_params(int argc, char **argv)
             die(EXIT_PANIC, "invalid value '" + v + "' for --resolve_assignments: expected true, false or all");
         p.resolve_assignments = v == "true" ? 1 : (v == "all" ? 2 : 0);
     }
+    if (got.count("normalization")) {
+        const std::string &v = got["normalization"];
+        if (v != "per_locus" && v != "zscore") die(EXIT_PANIC, "invalid value '" + v + "' for --normalization: expected per_locus or zscore");
+        p.zscore = v == "zscore";
+    }
+    if (p.zscore && p.resolve_near_ties)
+        die(1, "error: The argument '--normalization zscore' cannot be used with '--resolve_near_ties true': the reference has no "
+               "arithmetic of that score to resolve to");
+    if (p.zscore && p.resolve_assignments)
+        die(1, "error: The argument '--normalization zscore' cannot be used with '--resolve_assignments " + got["resolve_assignments"] +
+                   "': the reference has no arithmetic of that score to resolve to");
     if (got.count("initial_minority")) p.initial_minority = got["initial_minority"];
     if (got.count("cell_detail")) p.cell_detail = got["cell_detail"];
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
@@ -489,6 +508,7 @@ int main(int argc, char **argv)
         g.ck(cellector_set_option(g.c, "resolve_ties", params.resolve_assignments), "resolve_assignments");
         g.ck(cellector_set_option(g.c, "resolve_posteriors", params.resolve_assignments), "resolve_assignments");
     }
+    if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
     lap("barcodes + device init");
     g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     lap("load_mtx (text -> device)");
@@ -529,7 +549,7 @@ int main(int argc, char **argv)
     }
 
     // cellector() (main.rs:36-50)
-    std::vector<double> ll(N), ell(N), nloci(N), norm(N);
+    std::vector<double> ll(N), ell(N), nloci(N), norm(N), var(params.zscore ? N : 0);
     std::vector<double> c_min(L), c_maj(L);
     std::vector<uint64_t> n_min(L), n_maj(L), a_min(L), r_min(L), a_maj(L), r_maj(L);
     const std::string &od = params.output_directory;
@@ -546,6 +566,7 @@ int main(int argc, char **argv)
                             "the reference's\n", (unsigned long long)(iteration + 1), (unsigned long long)s.n_near_threshold,
                     fmt(s.threshold).c_str());
         g.ck(cellector_iter_cell_outputs(g.c, ll.data(), ell.data(), nloci.data(), norm.data()), "cell outputs");
+        if (params.zscore) g.ck(cellector_iter_cell_variances(g.c, var.data()), "cell variances");
         g.ck(cellector_iter_locus_outputs(g.c, c_min.data(), c_maj.data(), n_min.data(), n_maj.data(), a_min.data(),
                                           r_min.data(), a_maj.data(), r_maj.data()), "locus outputs");
         {   // locus_filter_and_output_locus_data (main.rs:422-498)
@@ -589,10 +610,13 @@ int main(int argc, char **argv)
         }
         {   // output_iteration_tsv (main.rs:349-366)
             FILE *f = create(od + "/iteration_" + std::to_string(iteration) + ".tsv");
-            fputs("cell_id\tbarcode\tassignment\tlog_likelihood\texpected_log_likelihood\tnum_loci_used\n", f);
+            fputs(params.zscore ? "cell_id\tbarcode\tassignment\tlog_likelihood\texpected_log_likelihood\tnum_loci_used\texpected_log_variance\n"
+                                : "cell_id\tbarcode\tassignment\tlog_likelihood\texpected_log_likelihood\tnum_loci_used\n", f);
             write_rows(f, N, [&](uint64_t c, std::string &o) {
                 put(o, c); o += '\t'; o += barcodes[c]; o += '\t'; o += ground_truth[c];
-                o += '\t'; put(o, ll[c]); o += '\t'; put(o, ell[c]); o += '\t'; put(o, nloci[c]); o += '\n';
+                o += '\t'; put(o, ll[c]); o += '\t'; put(o, ell[c]); o += '\t'; put(o, nloci[c]);
+                if (params.zscore) { o += '\t'; put(o, var[c]); }
+                o += '\n';
             });
             fclose(f);
             f = create(od + "/iteration_" + std::to_string(iteration) + "_threshold.tsv");

@@ -138,7 +138,21 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * ingest (either of the two options being non-zero at the ingest keeps it); 1 / 2 after an ingest without it, other values,
  * a multi-device ctx, a communicator of more than one rank or a host with another C library log are refused with
  * CELLECTOR_EINVAL.  cellector_posteriors is not changed by it.  Off: no launches, no allocations.
- * See cellector_assign_resolution). */
+ * See cellector_assign_resolution),
+ * "cell_variance" (engines 1 and 2, default 0: 1 = every cell pass of the loop, cellector_em_begin, is followed by a pass over
+ * the by-cell CSR that forms expected_log_variances, the fourth vector of get_cell_log_likelihoods (main.rs:587):
+ * cellector_iter_cell_variances.  No other output changes.  Off, with normalization 0: no launches, no allocations),
+ * "normalization" (default 0 = log_likelihood / loci_used, main.rs:316, the form the reference runs; 1 = the z-score its
+ * author left beside it, main.rs:317-318: (log_likelihood - expected_log_likelihood) / sqrt(expected_log_variance), 0 for a
+ * cell without used loci (main.rs:320-322) and for one whose variance is 0; other values: CELLECTOR_EINVAL.  1 implies the
+ * variance pass.  The z-scores are then the keys of the median, the quartiles, the threshold, the exclusion flags and
+ * n_near_threshold, and the `normalized` column of cellector_iter_cell_outputs.  Read by cellector_em_begin; works on
+ * single-device, multi-device and communicator ctxs and on a cellector_set_shard ctx whose host drives the exchanges (the
+ * NORM slice holds per-cell keys either way).  Refused with CELLECTOR_EINVAL, in whichever order the options are set:
+ * normalization 1 together with resolve_ties 1 / 2 (the reference has no arithmetic of this mode to resolve to) and
+ * normalization 1 together with compute_expected 0 (the z-score needs the expected term); resolve_posteriors is
+ * independent.  n_near_threshold keeps its formula in this mode but has no reference counterpart there: no reference run
+ * scores by these keys.  interquartile_range_multiple's default of 5 was chosen for the per-locus scale, not for this one). */
 cellector_status cellector_set_option(cellector_ctx *ctx, const char *key, int64_t value);
 
 /* ---- sharding (before ingest) --------------------------------------------------------------- */
@@ -358,6 +372,28 @@ cellector_status cellector_cell_pmfs(cellector_ctx *ctx, const double *alpha, co
                                      uint32_t *locus_index, uint32_t *alt, uint32_t *ref, double *log_pmf,
                                      double *expected_log_pmf, double *expected_log_variance /*[capacity] each, any may be NULL*/);
 
+/* ---- the fourth per-cell vector: expected_log_variances -------------------------------------------
+ * get_cell_log_likelihoods (main.rs:541-591) returns log_likelihoods, loci_used_per_cell, expected_log_likelihoods and
+ * expected_log_variances (main.rs:561, :581, :587): per cell, the sum over its entries at used loci of the variance of
+ * stats.rs:23-28, sum_k pmf(k) (ln pmf(k) - expected_log_pmf)^2 — the expected_log_variance column of cellector_cell_pmfs
+ * summed per cell.  It is the denominator of the z-score of main.rs:316-318 (option normalization).
+ *   Totals up to 17 come from a per-locus table of that column's bits; a lane of the cell's wave adds every 64th entry of the
+ *   by-cell CSR row in row order and the 64 partial sums are folded pairwise, so a cell's value depends on its row alone: it
+ *   is the same to the bit on any shard, on either engine and under either bank_order.
+ * cellector_cell_log_variances: the vector alone under caller alpha/beta/mask (host arrays), the arguments of
+ * cellector_cell_log_likelihoods.  Needs a loaded matrix and no iteration in flight; engines 1 and 2.  Unlike
+ * cellector_cell_log_likelihoods it uses scratch of its own and leaves the ctx exactly as it was (alpha/beta, tables,
+ * iteration outputs).  An all-masked mask gives zeros, and so does an empty row.  Global cell order on a multi-device ctx; the
+ * local cells of a ctx with a communicator or a cellector_set_shard range. */
+cellector_status cellector_cell_log_variances(cellector_ctx *ctx, const double *alpha, const double *beta /*[L]*/,
+                                              const uint8_t *mask /*[L] or NULL = all used*/,
+                                              double *expected_log_variance /*[local cells]*/);
+/* ... of the last finished iteration, formed under that iteration's alpha/beta and mask (options cell_variance or
+ * normalization).  CELLECTOR_EINVAL ("not formed") when that iteration ran with both options 0, before the first iteration
+ * and after cellector_em_reset until an iteration has finished.  Global cell order on a multi-device ctx, like
+ * cellector_iter_cell_outputs. */
+cellector_status cellector_iter_cell_variances(const cellector_ctx *ctx, double *out /*[local cells]*/);
+
 /* ---- calculate_posteriors (main.rs:228-280) with the current exclusion set -------------------- */
 /* the three distributions of calculate_posteriors for the current exclusion set (main.rs:239-254):
  * which = 0 minority, 1 majority (scaled by max(minority_fraction, 0.01)), 2 doublet.  With cellector_cell_pmfs they give the
@@ -418,7 +454,8 @@ typedef enum {
     CELLECTOR_K_SELECT = 2,      /* order statistics                           */
     CELLECTOR_K_POSTERIOR = 3,   /* fused 3-distribution pass + posteriors     */
     CELLECTOR_K_TILE_LL = 4,     /* engine 2: the tiled table-lookup kernel alone (inside K_CELL_LL) */
-    CELLECTOR_K_COUNT = 5
+    CELLECTOR_K_CELL_VAR = 5,    /* options cell_variance / normalization: k_var_tables + k_cell_variance (not inside K_CELL_LL; k_zscore not inside) */
+    CELLECTOR_K_COUNT = 6
 } cellector_kernel_id;
 cellector_status cellector_kernel_time(cellector_ctx *ctx, cellector_kernel_id which,
                                        double *total_ms, uint64_t *launches);
