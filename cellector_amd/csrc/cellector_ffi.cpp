@@ -372,6 +372,22 @@ static bool ref_log_matches_host()
     return ok != 0;
 }
 
+// The locus moments sum count planes over all cells: one device holding every cell.  (Summing the planes across shards needs an
+// exchange the public LOCUS buffer has no room for.)
+static cellector_status locus_moments_scope(const cellector_ctx *c, const char *what)
+{
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "%s works on a single-device ctx: the shards' count planes are not exchanged", what);
+    if (comm_active(c->comm))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s works on a ctx without a communicator: the shards' count planes are not exchanged", what);
+    if (c->state == cellector_ctx::ST_READY ? c->nloc != c->total_cells : c->req_cell_begin != 0)
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s works on a ctx that holds all cells, not on a cellector_set_shard range: the shards' "
+                                             "count planes are not exchanged", what);
+    if (c->state == cellector_ctx::ST_READY && c->nnz >= (1ull << 32))  // (kernels_locus_moments.hip refuses the same: no counter may wrap)
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: %llu entries, the locus histograms count in 32 bits (below 2^32 entries)", what,
+                        (unsigned long long)c->nnz);
+    return CELLECTOR_OK;
+}
+
 cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t v)
 {
     if (!c || !key) return CELLECTOR_EINVAL;
@@ -403,6 +419,13 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
             return ctx_fail(c, CELLECTOR_EINVAL, "resolve_posteriors: this host's C library log differs from the one ref_log.h repeats "
                                                  "(glibc >= 2.28, FMA variant), so the reference's bits cannot be promised");
         c->resolve_posteriors = (int)v;
+        return CELLECTOR_OK;
+    }
+    if (!strcmp(key, "locus_moments")) {
+        if (v != 0 && v != 1) return ctx_fail(c, CELLECTOR_EINVAL, "locus_moments must be 0 (off) or 1");
+        if (v) CHK(locus_moments_scope(c, "locus_moments 1"));
+        if (c->multi) return CELLECTOR_OK;  // (0 on a multi-device ctx: nothing to switch off)
+        c->locus_moments = v != 0;
         return CELLECTOR_OK;
     }
     if (c->multi) return multi_set_option(c, key, v);
@@ -560,6 +583,7 @@ cellector_status cellector_set_shard(cellector_ctx *c, uint64_t b, uint64_t e)
         return ctx_fail(c, CELLECTOR_EINVAL, "a ctx with a communicator shards the cells itself (contiguous ranges by rank: cellector_set_partition)");
     REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "set_shard must precede ingest");
     REQUIRE(c, b <= e, "empty or inverted shard range");
+    REQUIRE(c, !(c->locus_moments && b != 0), "set_shard: option locus_moments 1 works on a ctx that holds all cells (set it 0 first)");
     c->req_cell_begin = b;
     c->req_cell_end = e;
     c->tally_valid = false;  // (the ingest that must follow rebuilds the counts anyway)
@@ -938,6 +962,7 @@ cellector_status cellector_em_threshold(cellector_ctx *c, double iqr_multiple)
     if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "a multi-device ctx runs whole iterations: cellector_em_iteration");
     READY(c);
     REQUIRE(c, c->em_phase == 1, "em_threshold without em_begin");
+    if (c->locus_moments) CHK(locus_moments_scope(c, "locus_moments 1"));  // (before anything of this phase is queued)
     SETDEV(c);
     const uint64_t n = c->total_cells;
     REQUIRE(c, n > 0, "no cells");
@@ -962,6 +987,11 @@ cellector_status cellector_em_threshold(cellector_ctx *c, double iqr_multiple)
     CHK(launch_flag(c, c->sel_out + 10));
     if (c->engine == 2) CHK(tiled_locus_pass(c));
     else CHK(launch_locus_stats(c));
+    // option locus_moments: the expected contribution and variance per locus under this iteration's alpha/beta and mask and the
+    // new exclusion set.  Here c->ab still is the cell pass' (em_finish queues the next iteration's table kernel, which rewrites
+    // it) and flags_new the new set (em_finish swaps it in).
+    c->iter_lm = c->locus_moments;
+    if (c->iter_lm) CHK(launch_locus_moments(c));
     c->em_phase = 2;
     return CELLECTOR_OK;
 }
@@ -1025,6 +1055,7 @@ cellector_status cellector_em_finish(cellector_ctx *c, cellector_iter_summary *o
     c->iteration++;
     c->have_iter = true;
     c->var_formed = c->iter_var;
+    c->lm_formed = c->iter_lm;
     c->em_phase = 0;
     // (timers are read out when asked for — cellector_kernel_time — not here: waiting for the last event pair and destroying
     //  the events is host time on the path to the next iteration's first launch; a long run is drained now and then)
@@ -1152,6 +1183,7 @@ cellector_status cellector_em_reset(cellector_ctx *c)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->var_formed = false;
+    c->lm_formed = false;
     c->iteration = 0; c->have_iter = false; c->n_excluded_global = 0; c->n_masked_loci = 0;
     c->last_median = c->last_iqr = c->last_thr = 0;
     return CELLECTOR_OK;
@@ -1335,6 +1367,46 @@ cellector_status cellector_iter_cell_variances(const cellector_ctx *c, double *o
     REQUIRE(c, out || c->nloc == 0, "iter_cell_variances: null output");
     if (c->nloc == 0) return CELLECTOR_OK;
     return d2h(c, out, c->var, c->nloc * 8);
+}
+
+// ---- locus moments: kernels_locus_moments.hip -----------------------------------------------------------
+cellector_status cellector_locus_moments(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint8_t *flags,
+                                         double *exp_min, double *exp_maj, double *var_min, double *var_maj)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(locus_moments_scope(c, "locus_moments"));
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "locus_moments: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, (alpha && beta) || c->L == 0, "locus_moments: null alpha/beta");
+    REQUIRE(c, flags || c->nloc == 0, "locus_moments: null flags");
+    SETDEV(c);
+    return locus_moments_run(c, alpha, beta, mask, flags, exp_min, exp_maj, var_min, var_maj);
+}
+
+cellector_status cellector_locus_total_counts(cellector_ctx *c, const uint8_t *flags, uint32_t *out)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(locus_moments_scope(c, "locus_total_counts"));
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "locus_total_counts: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, out || c->L == 0, "locus_total_counts: null output");
+    SETDEV(c);
+    return locus_total_counts_run(c, flags, out);
+}
+
+cellector_status cellector_iter_locus_moments(const cellector_ctx *c, double *exp_min, double *exp_maj, double *var_min, double *var_maj)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(locus_moments_scope(c, "iter_locus_moments"));
+    READY(c);
+    REQUIRE(c, c->em_phase == 0, "iter_locus_moments: iteration in flight (finish it with cellector_em_finish)");
+    REQUIRE(c, c->lm_formed, "iter_locus_moments: not formed (the last finished iteration ran with option locus_moments 0, or none "
+                             "has finished since the load / cellector_em_reset)");
+    const uint64_t L = c->L;
+    double *const out[4] = {exp_min, exp_maj, var_min, var_maj};
+    for (int k = 0; k < 4; k++)
+        if (out[k] && L) CHK(d2h(c, out[k], c->lm_out + (uint64_t)k * L, L * 8));
+    return CELLECTOR_OK;
 }
 
 // ---- posteriors ---------------------------------------------------------------------------------------

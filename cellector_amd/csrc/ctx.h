@@ -149,6 +149,9 @@ struct CtxOptions {
     // option normalization: 0 = ll / loci_used (main.rs:316), 1 = the z-score of main.rs:317-318 (implies the variance pass);
     // read by em_begin
     int normalization = 0;
+    // option locus_moments (kernels_locus_moments.hip; single device, all cells): cellector_em_threshold also forms the per-locus
+    // expected contribution and variance of the new exclusion set and of the rest
+    bool locus_moments = false;
     int side_lds = -1;               // option "side_lds": dynamic LDS bytes requested by the cell-side overflow kernel (residency
                                      // throttle; -1 = automatic)
     int ovf_deep_opt = -1;           // option "ovf_deep": -1 = decided per matrix (tiled_build), 0 / 1 = forced
@@ -191,6 +194,15 @@ struct CtxMatrix {
     DevBuf<double> post;               // [4*nloc] posterior, doublet, ll_maj, ll_min
     DevBuf<double> var;                // [nloc] expected_log_variances of the last cell pass that formed them (made on first use)
     DevBuf<double> var_tab;            // [L][18] that pass' per-locus variances of the totals 0..17, then [L][4] a compact copy of 1..4 (k_var_tables)
+    // locus moments (kernels_locus_moments.hip), made on first use.  Static per matrix (cache, not state):
+    bool lm_static_ready = false;
+    DevBuf<uint32_t> lm_hist_all;      // [L][18] entries per (locus, total 0..17), all cells
+    DevBuf<uint64_t> lm_far_ptr;       // [L+1] the locus' segment of lm_far_ent
+    DevBuf<uint64_t> lm_far_ent;       // the entries with a total above 17: local cell << 32 | total; by locus, ascending cell inside
+    uint64_t lm_far_n = 0;
+    // ... and the loop's pass (option locus_moments):
+    DevBuf<uint32_t> lm_hist_min;      // [L][18] ... of the cells of the new exclusion set
+    DevBuf<double> lm_out;             // [4][L] expected minority / majority, variance minority / majority of the last pass
 
     // exchange buffers: the library's own (x_*_own) or one the caller bound (a bound PASS1 buffer is kept across a reload)
     double *x_pass1 = nullptr, *x_norm = nullptr, *x_locus = nullptr;
@@ -310,6 +322,8 @@ struct CtxCarry {
     int res_last_mode = 0;      // resolve_ties of the last iteration (cellector_iter_resolution)
     bool iter_var = false;      // the iteration in flight formed c->var (em_begin)
     bool var_formed = false;    // ... and so did the last finished one (cellector_iter_cell_variances); cleared by em_reset
+    bool iter_lm = false;       // the iteration in flight formed c->lm_out (em_threshold)
+    bool lm_formed = false;     // ... and so did the last finished one (cellector_iter_locus_moments); cleared by em_reset
     // what the last cellector_assign resolved (cellector_assign_resolution / _resolved_cells)
     int pa_last_mode = 0;
     uint64_t pa_labels_changed = 0, pa_qual_changed = 0;
@@ -458,6 +472,12 @@ cellector_status pmfs_run(cellector_ctx *c, const double *alpha, const double *b
 // norm_out; and cellector_cell_log_variances on one device, scratch of its own
 cellector_status launch_cell_variance(cellector_ctx *c, bool zscore, double *norm_out);
 cellector_status variance_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, double *out /*[nloc] host*/);
+// locus moments (kernels_locus_moments.hip): the loop's pass into c->lm_out under c->ab and flags_new; cellector_locus_moments
+// and cellector_locus_total_counts on one device, scratch of their own (host arrays; out: [L][19])
+cellector_status launch_locus_moments(cellector_ctx *c);
+cellector_status locus_moments_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint8_t *flags,
+                                   double *exp_min, double *exp_maj, double *var_min, double *var_maj);
+cellector_status locus_total_counts_run(cellector_ctx *c, const uint8_t *flags, uint32_t *out);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);

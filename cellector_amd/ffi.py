@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CELLECTOR_HIP_LIB") or os.path.join(_HERE, "libcellector_hip.so")
 
 XCHG_PASS1, XCHG_NORM, XCHG_LOCUS = 0, 1, 2
-K_CELL_LL, K_LOCUS_STATS, K_SELECT, K_POSTERIOR, K_TILE_LL, K_CELL_VAR = 0, 1, 2, 3, 4, 5
+K_CELL_LL, K_LOCUS_STATS, K_SELECT, K_POSTERIOR, K_TILE_LL, K_CELL_VAR, K_LOCUS_MOM = 0, 1, 2, 3, 4, 5, 6
 STATUS_NAMES = {0: "OK", 1: "EINVAL", 2: "EIO", 3: "EPARSE", 4: "ENOMEM", 5: "EDEVICE", 6: "ECOMM"}
 
 # every entry point include/cellector_ffi.h declares: name -> (restype, argtypes)
@@ -64,6 +64,9 @@ SIGNATURES = {
     "cellector_cell_pmfs": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64] + [_vp] * 6),
     "cellector_cell_log_variances": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_iter_cell_variances": (_i, [_vp, _vp]),
+    "cellector_locus_moments": (_i, [_vp] + [_vp] * 8),
+    "cellector_locus_total_counts": (_i, [_vp, _vp, _vp]),
+    "cellector_iter_locus_moments": (_i, [_vp] + [_vp] * 4),
     "cellector_posterior_alpha_betas": (_i, [_vp, _i, _vp, _vp]),
     "cellector_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
@@ -430,6 +433,51 @@ class Cellector:
         out = self._per_cell_f64()
         self._ck(self._lib.cellector_iter_cell_variances(self.h, _p(out)))
         return out
+
+    _LM_KEYS = ("exp_min", "exp_maj", "var_min", "var_maj")
+
+    def locus_moments(self, alpha, beta, mask, flags):
+        """Per used locus the expected log-likelihood contribution and its variance of the flagged cells (min) and of the rest
+        (maj) under the given alpha / beta / mask (cellector_locus_moments): what main.rs:398/404 would hold had main.rs:394
+        pushed expected_log_pmf, and the matching sums of expected_log_variance.  mask None = all loci used.  Returns a dict of
+        four [L] arrays: exp_min, exp_maj, var_min, var_maj.  The ctx is left as it was."""
+        L = self.dims().loci_used
+        alpha = np.ascontiguousarray(alpha, np.float64)
+        beta = np.ascontiguousarray(beta, np.float64)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        flags = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+        if alpha.shape != (L,) or beta.shape != (L,) or (mask is not None and mask.shape != (L,)):
+            raise ValueError(f"locus_moments: alpha, beta and mask of {L} loci expected")
+        if flags.shape != (self.n_local,):
+            raise ValueError(f"locus_moments: {self.n_local} flags expected, got shape {flags.shape}")
+        out = [np.zeros(L, np.float64) for _ in range(4)]
+        self._ck(self._lib.cellector_locus_moments(self.h, _p(alpha), _p(beta), _p(mask), _p(flags), *[_p(a) for a in out]))
+        return dict(zip(self._LM_KEYS, out))
+
+    def iter_locus_moments(self):
+        """The four vectors of the last finished iteration (cellector_iter_locus_moments): under that iteration's alpha / beta
+        and mask and its new exclusion set; an error unless it ran with option locus_moments set."""
+        out = [np.zeros(self.dims().loci_used, np.float64) for _ in range(4)]
+        self._ck(self._lib.cellector_iter_locus_moments(self.h, *[_p(a) for a in out]))
+        return dict(zip(self._LM_KEYS, out))
+
+    def locus_total_counts(self, flags=None):
+        """[L, 19] uint32 (cellector_locus_total_counts): entries of the flagged cells (None: all cells) per used locus and
+        total alt + ref = 0..17; column 18 = their entries with a larger total."""
+        if flags is not None:
+            flags = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+            if flags.shape != (self.n_local,):
+                raise ValueError(f"locus_total_counts: {self.n_local} flags expected, got shape {flags.shape}")
+        out = np.zeros((self.dims().loci_used, 19), np.uint32)
+        self._ck(self._lib.cellector_locus_total_counts(self.h, _p(flags), _p(out)))
+        return out
+
+    @staticmethod
+    def locus_zscore(contrib, exp, var, cells):
+        """(contrib - exp) / sqrt(var) where cells > 0 and var > 0, else 0: the form of main.rs:317-322 on the locus side"""
+        contrib, exp, var = (np.asarray(a, np.float64) for a in (contrib, exp, var))
+        ok = (np.asarray(cells) > 0) & (var > 0)
+        return np.where(ok, (contrib - exp) / np.sqrt(np.where(ok, var, 1.0)), 0.0)
 
     def posterior_alpha_betas(self, which):
         """(alpha, beta) of calculate_posteriors' distribution `which` for the current exclusion set: 0 minority, 1 majority,

@@ -174,6 +174,7 @@ struct Params {
     bool resolve_near_ties = false;                    // extension: option resolve_ties (single GPU)
     int resolve_assignments = 0;                       // extension: options resolve_ties + resolve_posteriors = 1 (true) / 2 (all)
     bool zscore = false;                               // extension: option normalization = 1 (main.rs:317-318)
+    bool locus_expected = false;                       // extension: option locus_moments = 1 (the sums main.rs:394 meant to form)
     std::optional<std::string> initial_minority;       // extension: barcodes of the initial exclusion set (main.rs:37 starts from none)
     std::optional<std::string> cell_detail;            // extension: barcodes whose per-locus records go to cell_detail.tsv (main.rs:176's TODO)
 };
@@ -214,6 +215,12 @@ const char *USAGE =
     "                                                                       cannot be used with --resolve_near_ties true / --resolve_assignments\n"
     "                                                                       (not in the reference; --interquartile_range_multiple's default was\n"
     "                                                                       chosen for per_locus)\n"
+    "        --locus_expected <true|false>                                  iteration_N_locus_contribution.tsv: the columns expected_loglike_minority /\n"
+    "                                                                       _majority hold the expected log likelihood of the locus' entries (the\n"
+    "                                                                       reference fills them with a copy of the two columns before them), and\n"
+    "                                                                       four columns are appended: variance_minority, variance_majority,\n"
+    "                                                                       zscore_minority, zscore_majority = (log likelihood - expected) /\n"
+    "                                                                       sqrt(variance) (not in the reference; default false; one GPU)\n"
     "        --initial_minority <file>                                      start the loop from these cells as the excluded (minority) set\n"
     "                                                                       instead of the empty set: one barcode per line, first tab-separated\n"
     "                                                                       column (a filtered cellector_assignments.tsv works), blank lines\n"
@@ -248,7 +255,8 @@ Params load_params(int argc, char **argv)
     static const char *known[] = {"output_directory", "ref", "alt", "barcodes", "min_alt", "min_ref", "ground_truth",
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
-                                  "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization"};
+                                  "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
+                                  "locus_expected"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -317,11 +325,18 @@ Params load_params(int argc, char **argv)
     if (p.zscore && p.resolve_assignments)
         die(1, "error: The argument '--normalization zscore' cannot be used with '--resolve_assignments " + got["resolve_assignments"] +
                    "': the reference has no arithmetic of that score to resolve to");
+    if (got.count("locus_expected")) {
+        const std::string &v = got["locus_expected"];
+        if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --locus_expected: expected true or false");
+        p.locus_expected = v == "true";
+    }
     if (got.count("initial_minority")) p.initial_minority = got["initial_minority"];
     if (got.count("cell_detail")) p.cell_detail = got["cell_detail"];
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_assignments " + got["resolve_assignments"] +
                    "' works on one GPU and cannot be used with '--devices <a,b,...>'");
+    if (p.locus_expected && (p.devices_auto || p.devices.size() > 1))
+        die(1, "error: The argument '--locus_expected true' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.resolve_near_ties && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_near_ties true' works on one GPU and cannot be used with '--devices <a,b,...>'");
     return p;
@@ -509,6 +524,7 @@ int main(int argc, char **argv)
         g.ck(cellector_set_option(g.c, "resolve_posteriors", params.resolve_assignments), "resolve_assignments");
     }
     if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
+    if (params.locus_expected) g.ck(cellector_set_option(g.c, "locus_moments", 1), "locus_expected");
     lap("barcodes + device init");
     g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     lap("load_mtx (text -> device)");
@@ -551,6 +567,8 @@ int main(int argc, char **argv)
     // cellector() (main.rs:36-50)
     std::vector<double> ll(N), ell(N), nloci(N), norm(N), var(params.zscore ? N : 0);
     std::vector<double> c_min(L), c_maj(L);
+    const bool lx = params.locus_expected;
+    std::vector<double> e_min(lx ? L : 0), e_maj(lx ? L : 0), v_min(lx ? L : 0), v_maj(lx ? L : 0);
     std::vector<uint64_t> n_min(L), n_maj(L), a_min(L), r_min(L), a_maj(L), r_maj(L);
     const std::string &od = params.output_directory;
     for (uint64_t iteration = 0;; iteration++) {
@@ -569,12 +587,14 @@ int main(int argc, char **argv)
         if (params.zscore) g.ck(cellector_iter_cell_variances(g.c, var.data()), "cell variances");
         g.ck(cellector_iter_locus_outputs(g.c, c_min.data(), c_maj.data(), n_min.data(), n_maj.data(), a_min.data(),
                                           r_min.data(), a_maj.data(), r_maj.data()), "locus outputs");
+        if (lx) g.ck(cellector_iter_locus_moments(g.c, e_min.data(), e_maj.data(), v_min.data(), v_maj.data()), "locus moments");
         {   // locus_filter_and_output_locus_data (main.rs:422-498)
             FILE *f = create(od + "/iteration_" + std::to_string(iteration) + "_locus_contribution.tsv");
             fputs("locus_id\tchrom\tpos\tlog_likelihood_minority\tlog_likelihood_majority\texpected_loglike_minority\t"
                   "expected_loglike_majority\tminority_cellcount\tmajority_cellcount\tlog_likelihood_minority_per_cell\t"
                   "log_likelihood_majority_per_cell\tminority_alt\tminority_ref\tmajority_alt\tmajority_ref\tminority_af\t"
-                  "majority_af\n", f);
+                  "majority_af", f);
+            fputs(lx ? "\tvariance_minority\tvariance_majority\tzscore_minority\tzscore_majority\n" : "\n", f);
             std::vector<double> pc_min(L), pc_maj(L), for_thr;
             for (uint64_t l = 0; l < L; l++) {
                 if (n_min[l]) { pc_min[l] = c_min[l] / (double)n_min[l]; for_thr.push_back(pc_min[l]); } else pc_min[l] = 0.0;
@@ -600,11 +620,18 @@ int main(int argc, char **argv)
                 if (params.vcf) { o += vcf_data[locus_ids[l]].chrom; o += '\t'; o += vcf_data[locus_ids[l]].pos; }
                 else o += "na\tna";
                 o += '\t'; put(o, c_min[l]); o += '\t'; put(o, c_maj[l]);
-                o += '\t'; put(o, c_min[l]); o += '\t'; put(o, c_maj[l]);  // quirk Q6: "expected" == plain contribution
+                if (lx) { o += '\t'; put(o, e_min[l]); o += '\t'; put(o, e_maj[l]); }  // the sums main.rs:394 meant to form
+                else { o += '\t'; put(o, c_min[l]); o += '\t'; put(o, c_maj[l]); }  // quirk Q6: "expected" == plain contribution
                 o += '\t'; put(o, n_min[l]); o += '\t'; put(o, n_maj[l]);
                 o += '\t'; put(o, pc_min[l]); o += '\t'; put(o, pc_maj[l]);
                 o += '\t'; put(o, a_min[l]); o += '\t'; put(o, r_min[l]); o += '\t'; put(o, a_maj[l]); o += '\t'; put(o, r_maj[l]);
-                o += '\t'; put(o, af_min); o += '\t'; put(o, af_maj); o += '\n';
+                o += '\t'; put(o, af_min); o += '\t'; put(o, af_maj);
+                if (lx) {  // the z-score of main.rs:317-322 on the locus side: 0 without cells of the class or without variance
+                    const double z_min = n_min[l] && v_min[l] > 0.0 ? (c_min[l] - e_min[l]) / std::sqrt(v_min[l]) : 0.0;
+                    const double z_maj = n_maj[l] && v_maj[l] > 0.0 ? (c_maj[l] - e_maj[l]) / std::sqrt(v_maj[l]) : 0.0;
+                    o += '\t'; put(o, v_min[l]); o += '\t'; put(o, v_maj[l]); o += '\t'; put(o, z_min); o += '\t'; put(o, z_maj);
+                }
+                o += '\n';
             });
             fclose(f);
         }

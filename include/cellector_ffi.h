@@ -152,7 +152,13 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * normalization 1 together with resolve_ties 1 / 2 (the reference has no arithmetic of this mode to resolve to) and
  * normalization 1 together with compute_expected 0 (the z-score needs the expected term); resolve_posteriors is
  * independent.  n_near_threshold keeps its formula in this mode but has no reference counterpart there: no reference run
- * scores by these keys.  interquartile_range_multiple's default of 5 was chosen for the per-locus scale, not for this one). */
+ * scores by these keys.  interquartile_range_multiple's default of 5 was chosen for the per-locus scale, not for this one),
+ * "locus_moments" (engines 1 and 2, default 0: 1 = cellector_em_threshold, behind its locus pass, also forms the per-locus
+ * expected contribution and variance of the new exclusion set and of the rest, under the alpha/beta and mask of the iteration's
+ * cell pass: cellector_iter_locus_moments.  No other output changes; independent of compute_expected, ref_arith,
+ * resolve_ties, resolve_posteriors, cell_variance and normalization.  A single-device ctx that holds all cells: 1 is refused
+ * with CELLECTOR_EINVAL on a multi-device ctx, with a communicator of more than one rank and with a cellector_set_shard
+ * range, whichever is set first.  Off: no launches, no allocations). */
 cellector_status cellector_set_option(cellector_ctx *ctx, const char *key, int64_t value);
 
 /* ---- sharding (before ingest) --------------------------------------------------------------- */
@@ -394,6 +400,40 @@ cellector_status cellector_cell_log_variances(cellector_ctx *ctx, const double *
  * cellector_iter_cell_outputs. */
 cellector_status cellector_iter_cell_variances(const cellector_ctx *ctx, double *out /*[local cells]*/);
 
+/* ---- locus moments: the per-locus expected log-likelihood and its variance --------------------------
+ * get_locus_log_likelihoods (main.rs:368-420) declares locus_expected_contribution_minority / _majority and fills them with a
+ * copy of log_pmf (main.rs:394).  These calls return what main.rs:398/404 would hold had line 394 pushed
+ * pmf_data.expected_log_pmf, and the matching sums of expected_log_variance.  For a used locus l and a class of cells (min: the
+ * flagged cells, maj: the rest), one term per entry of a cell of the class at l (a repeated (locus, cell) line counts as often
+ * as it occurs), with n = alt + ref of the entry:
+ *   exp_c[l] = sum E(alpha_l, beta_l, n)    E = expected_log_pmf, stats.rs:19-22
+ *   var_c[l] = sum V(alpha_l, beta_l, n)    V = expected_log_variance, stats.rs:23-28
+ * E and V are the values cellector_cell_pmfs returns in those two columns (the same device functions, the same bits).  A
+ * masked locus gives 0 in all four (no PMFData exists there, main.rs:556); an entry with n = 0 adds 0.
+ *   Evaluation, fixed so that the result depends on the matrix, the flags and alpha/beta alone (not on the engine, bank_order
+ *   or the grid): per locus and class s = 0; for n = 1..17 ascending s = s + (double)count_c[l][n] * T[l][n], a rounded product
+ *   and a rounded sum (no fused multiply-add); then the locus' entries with n > 17 in ascending local cell index, a repeated
+ *   pair in CSR row order, each adding its own E (V).  count_maj = count_all - count_min, as integers.
+ * cellector_locus_moments: under caller alpha/beta/mask/flags (host arrays), the locus-side counterpart of
+ * cellector_cell_log_variances.  Scratch of its own; the ctx is left exactly as it was (it may build and keep the all-cells
+ * histogram and the list of the entries above 17 of this matrix: cache, not state).  Needs a loaded matrix and no iteration in
+ * flight; engines 1 and 2; a single-device ctx that holds all cells (else CELLECTOR_EINVAL, like option locus_moments), with
+ * fewer than 2^32 entries (the histograms count in 32 bits; else CELLECTOR_EINVAL). */
+cellector_status cellector_locus_moments(cellector_ctx *ctx, const double *alpha, const double *beta /*[L]*/,
+                                         const uint8_t *mask /*[L] or NULL = all used*/, const uint8_t *flags /*[local cells]*/,
+                                         double *exp_min, double *exp_maj, double *var_min,
+                                         double *var_maj /*[L] each, any may be NULL*/);
+/* the histogram itself, a diagnostic like cellector_csr_rows: out[l][n] = entries of the flagged cells (NULL: all cells) at
+ * used locus l with alt + ref = n for n = 0..17, out[l][18] = their entries with a larger total.  Mask-independent. */
+cellector_status cellector_locus_total_counts(cellector_ctx *ctx, const uint8_t *flags /*[local cells] or NULL = all cells*/,
+                                              uint32_t *out /*[L][19]*/);
+/* ... the four vectors of the last finished iteration (option locus_moments): under the alpha/beta its cell pass used, its
+ * mask and its NEW exclusion set, the inputs of main.rs:343 (quirk Q9).  CELLECTOR_EINVAL ("not formed") when that iteration
+ * ran with the option at 0, before the first iteration and after cellector_em_reset until an iteration has finished.  After
+ * cellector_set_excluded / cellector_set_loci_mask it keeps returning the last iteration's, like cellector_iter_cell_outputs. */
+cellector_status cellector_iter_locus_moments(const cellector_ctx *ctx, double *exp_min, double *exp_maj, double *var_min,
+                                              double *var_maj /*[L] each, any may be NULL*/);
+
 /* ---- calculate_posteriors (main.rs:228-280) with the current exclusion set -------------------- */
 /* the three distributions of calculate_posteriors for the current exclusion set (main.rs:239-254):
  * which = 0 minority, 1 majority (scaled by max(minority_fraction, 0.01)), 2 doublet.  With cellector_cell_pmfs they give the
@@ -455,7 +495,8 @@ typedef enum {
     CELLECTOR_K_POSTERIOR = 3,   /* fused 3-distribution pass + posteriors     */
     CELLECTOR_K_TILE_LL = 4,     /* engine 2: the tiled table-lookup kernel alone (inside K_CELL_LL) */
     CELLECTOR_K_CELL_VAR = 5,    /* options cell_variance / normalization: k_var_tables + k_cell_variance (not inside K_CELL_LL; k_zscore not inside) */
-    CELLECTOR_K_COUNT = 6
+    CELLECTOR_K_LOCUS_MOM = 6,   /* option locus_moments: k_lm_count + k_lm_finalize of the loop's pass (not inside K_LOCUS_STATS) */
+    CELLECTOR_K_COUNT = 7
 } cellector_kernel_id;
 cellector_status cellector_kernel_time(cellector_ctx *ctx, cellector_kernel_id which,
                                        double *total_ms, uint64_t *launches);
