@@ -329,7 +329,7 @@ void cellector_destroy(cellector_ctx *c)
     drop_matrix(c);
     c->lf.reset(); c->d_counters.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
     c->sel_list.reset(); c->seld_hist.reset(); c->seld_state.reset();
-    c->res_cnt.reset(); c->res_dev.reset();
+    c->res_cnt.reset(); c->res_dev.reset(); c->cell_origin.reset();
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
@@ -601,6 +601,7 @@ static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint
         drop_matrix(c);
         if (bound) { c->x_pass1 = bound; c->n_pass1 = nb; }
     }
+    c->cell_origin.reset();  // an ingest from outside: cellector_cell_origin is the identity again
     REQUIRE(c, total_loci <= 0xffffffffull && total_cells <= 0xffffffffull, "dims exceed 32-bit indices");
     c->total_loci = total_loci;
     c->total_cells = total_cells;
@@ -871,6 +872,117 @@ cellector_status cellector_csr_rows(const cellector_ctx *c, uint64_t rb, uint64_
     if (entries) {
         REQUIRE(c, capacity >= cnt, "entries capacity too small");
         CHK(d2h(c, entries, c->csr_ent + base, cnt * 8));
+    }
+    return CELLECTOR_OK;
+}
+
+// ---- re-staging the resident matrix -------------------------------------------------------------------
+// cellector_restage works where one device holds every cell (the conditions of locus_moments_scope, without its entry limit)
+static cellector_status restage_scope(const cellector_ctx *c)
+{
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a single-device ctx: the staged entries of a multi-device ctx are sharded");
+    if (comm_active(c->comm)) return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a ctx without a communicator: every rank stages its own cells");
+    if (c->state == cellector_ctx::ST_EMPTY) return ctx_fail(c, CELLECTOR_EINVAL, "restage without a staged matrix");
+    if (c->nloc != c->total_cells)
+        return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a ctx that holds all cells, not on a cellector_set_shard range");
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "restage between cellector_em_begin and cellector_em_finish");
+    if (c->state == cellector_ctx::ST_READY && !c->coo.locus)
+        return ctx_fail(c, CELLECTOR_EINVAL, "restage of a loaded matrix needs its staged COO (option keep_coo=1 before the ingest)");
+    return CELLECTOR_OK;
+}
+
+// READY -> STAGED on the entries the ctx still holds: everything the built matrix owned goes as in a reload (drop_matrix); the
+// staged COO, the dims and PASS1 (ingest_build only read it) stay
+static void unbuild_matrix(cellector_ctx *c)
+{
+    StagedCoo coo = std::move(c->coo);
+    DevBuf<double> own = std::move(c->x_pass1_own);
+    double *const p1 = c->x_pass1;
+    const uint64_t tl = c->total_loci, tc = c->total_cells, cb = c->cell_begin, ce = c->cell_end, nloc = c->nloc, np1 = c->n_pass1;
+    drop_matrix(c);
+    c->coo = std::move(coo);
+    c->x_pass1_own = std::move(own);
+    c->x_pass1 = p1; c->n_pass1 = np1;
+    c->total_loci = tl; c->total_cells = tc; c->cell_begin = cb; c->cell_end = ce; c->nloc = nloc;
+    c->state = cellector_ctx::ST_STAGED;
+}
+
+cellector_status cellector_restage(cellector_ctx *c, const uint8_t *keep, double downsample_rate, uint64_t seed)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(restage_scope(c));
+    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
+        return ctx_fail(c, CELLECTOR_EINVAL, "restage: downsample_rate %g is not in [0, 1]", downsample_rate);
+    const uint64_t tc = c->total_cells;
+    uint64_t n_keep = tc;
+    if (keep) {
+        n_keep = 0;
+        for (uint64_t i = 0; i < tc; i++) n_keep += keep[i] != 0;
+        if (n_keep == 0) return ctx_fail(c, CELLECTOR_EINVAL, "restage: the selection keeps none of the %llu cells", (unsigned long long)tc);
+        if (n_keep == tc) keep = nullptr;  // every cell stays: nothing to renumber
+    }
+    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
+    SETDEV(c);
+    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
+    LapTimer t;
+    auto lap = [&](const char *what) {
+        if (timing) fprintf(stderr, "[timing]   restage: %-22s %8.4f s\n", what, t.lap());
+    };
+    // ---- validated: from here the ctx changes.  The built matrix goes first, then the new COO is made beside the old one
+    if (c->state == cellector_ctx::ST_READY) {
+        unbuild_matrix(c);  // (its blocks stay in the cache: the new COO and the finish that follows take them from there)
+        lap("drop built matrix");
+    }
+    if (keep) {
+        DevBuf<uint8_t> keep01;
+        DevBuf<uint32_t> rank, origin;
+        StagedCoo neu;
+        CHK(restage_cell_ranks(c, keep, tc, n_keep, c->cell_origin, &keep01, &rank, &origin));
+        lap("cell ranks");
+        CHK(restage_select(c, c->coo.view(), tc, keep01, rank, T, seed, &neu));  // (a failure up to here leaves the old entries staged)
+        lap("count + scan + write");
+        neu.sorted = c->coo.sorted;  // (a subsequence of a locus-major order is locus-major)
+        c->coo = std::move(neu);
+        c->cell_origin = std::move(origin);
+        c->total_cells = n_keep; c->cell_begin = 0; c->cell_end = n_keep; c->nloc = n_keep;
+    } else {
+        CHK(restage_thin(c, &c->coo, T, seed));
+        lap("thin");
+    }
+    CHK(ingest_pass1(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lap("release + PASS1");
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_cell_origin(const cellector_ctx *c, uint32_t *out)
+{
+    if (!c || !out) return CELLECTOR_EINVAL;
+    cellector_dims_t d;
+    CHK(cellector_dims(c, &d));
+    if (!c->multi && c->cell_origin) return d2h(c, out, c->cell_origin, d.total_cells * 4);
+    for (uint64_t i = 0; i < d.total_cells; i++) out[i] = (uint32_t)i;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_staged_coo(const cellector_ctx *c, uint64_t *n, uint32_t *locus0, uint32_t *cell0, uint32_t *alt, uint32_t *ref,
+                                      uint64_t capacity)
+{
+    if (!c || !n) return CELLECTOR_EINVAL;
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "staged_coo works on a single-device ctx (the staged entries of a multi-device ctx are sharded)");
+    REQUIRE(c, c->state != cellector_ctx::ST_EMPTY && c->coo.locus, "staged_coo without a staged matrix (option keep_coo=1)");
+    *n = c->coo.n;
+    if (!locus0 && !cell0 && !alt && !ref) return CELLECTOR_OK;
+    REQUIRE(c, capacity >= c->coo.n, "staged_coo: capacity too small");
+    const uint64_t m = c->coo.n;
+    if (locus0) CHK(d2h(c, locus0, c->coo.locus, m * 4));
+    if (cell0) CHK(d2h(c, cell0, c->coo.cell, m * 4));
+    std::vector<uint16_t> h(m);
+    for (int k = 0; k < 2; k++) {
+        uint32_t *dst = k ? ref : alt;
+        if (!dst) continue;
+        CHK(d2h(c, h.data(), k ? c->coo.ref.get() : c->coo.alt.get(), m * 2));
+        for (uint64_t i = 0; i < m; i++) dst[i] = h[i];
     }
     return CELLECTOR_OK;
 }

@@ -346,6 +346,9 @@ struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_sum = nullptr;
     hipEvent_t ev_tab = nullptr;   // completion of the table kernel queued ahead by em_finish, attached to its dispatch (no barrier packet)
     mutable std::string err;
+    // cellector_cell_origin: per current cell its index in the matrix of the last ingest from outside; null = identity.  Not
+    // part of CtxMatrix: begin_ingest clears it, cellector_restage composes it and carries it over its own reset
+    DevBuf<uint32_t> cell_origin;
 
     DevBuf<double> lf;            // [LF_TABLE_N] ln factorial table
     DevBuf<uint32_t> d_counters;  // [8] device scratch counters
@@ -507,6 +510,15 @@ cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell,
 cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path, const char *ref_path, cellector_ctx *helper);
 cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, StagedCoo &&coo);
 cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_ref);
+// cellector_restage (kernels_restage.hip).  host_keep [tc] with n_keep non-zero bytes -> keep01 [tc] 0 / 1, rank [tc] the new
+// index of a kept cell (~0u: dropped), origin [n_keep] = old_origin (device, null: identity) at the kept cells
+cellector_status restage_cell_ranks(cellector_ctx *c, const uint8_t *host_keep, uint64_t tc, uint64_t n_keep, const uint32_t *old_origin,
+                                    DevBuf<uint8_t> *keep01, DevBuf<uint32_t> *rank, DevBuf<uint32_t> *origin);
+// ... the entries of the kept cells into a new COO, order kept, cells renumbered, counts thinned (T = 0: copied)
+cellector_status restage_select(cellector_ctx *c, const CooView &in, uint64_t tc, const uint8_t *keep01, const uint32_t *rank, uint64_t T,
+                                uint64_t seed, StagedCoo *out);
+// ... all cells: the two counts thinned where they are
+cellector_status restage_thin(cellector_ctx *c, StagedCoo *coo, uint64_t T, uint64_t seed);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);

@@ -14,11 +14,11 @@
 //   alt(l,c)      = #{i < n : 16-bit field i of h3 < af16}, h3 = mix(h2 + GOLD), rehashed every 4 fields
 //   ref           = n - alt
 #include "ctx.h"
+#include "mix64.h"  // GOLD, mix64
 
 #define SY_BLOCK 256
 #define SY_CELLS_PER_THREAD 64
 #define SY_CHUNK (SY_BLOCK * SY_CELLS_PER_THREAD)  // 16384 cells per tile
-#define GOLD 0x9E3779B97F4A7C15ull
 
 #define SY_GEOM_MAX 64
 struct SynthParams {
@@ -29,14 +29,6 @@ struct SynthParams {
     uint32_t n_geom;       // thresholds in geom[1..n_geom-1]
     uint32_t geom[SY_GEOM_MAX];
 };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
 
 static const uint32_t SY_GEOM[19] = {0u, 1288490188u, 386547056u, 115964116u, 34789235u, 10436770u, 3131031u,
                                      939309u, 281792u, 84537u, 25361u, 7608u, 2282u, 684u, 205u, 61u, 18u, 5u, 1u};
@@ -126,14 +118,6 @@ __global__ __launch_bounds__(SY_BLOCK) void k_synth_fill(SynthParams p, uint64_t
     }
 }
 
-static uint64_t host_mix64(uint64_t z)
-{
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction)
 {
@@ -143,9 +127,9 @@ cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed,
     if (c->total_loci == 0 || c->total_loci > 0xffffffffull || c->nloc == 0)
         return ctx_fail(c, CELLECTOR_EINVAL, "synthetic: unsupported dims");
     SynthParams p;
-    const uint64_t base = host_mix64(seed * GOLD + 0x5EEDull);
-    p.s_lc = host_mix64(base + 1); p.s_min = host_mix64(base + 2); p.s_dbl = host_mix64(base + 3);
-    p.s_gmaj = host_mix64(base + 4); p.s_gmin = host_mix64(base + 5);
+    const uint64_t base = mix64(seed * GOLD + 0x5EEDull);
+    p.s_lc = mix64(base + 1); p.s_min = mix64(base + 2); p.s_dbl = mix64(base + 3);
+    p.s_gmaj = mix64(base + 4); p.s_gmin = mix64(base + 5);
     p.thr_density = (uint32_t)(density * 16777216.0 + 0.5);
     p.thr_min = (uint32_t)(minority_fraction * 16777216.0 + 0.5);
     p.thr_dbl = (uint32_t)(doublet_fraction * 16777216.0 + 0.5);

@@ -44,6 +44,9 @@ SIGNATURES = {
     "cellector_locus_counts": (_i, [_vp, _vp]),
     "cellector_entries_per_cell": (_i, [_vp, _vp]),
     "cellector_csr_rows": (_i, [_vp, _u64, _u64, _vp, _vp, _u64]),
+    "cellector_restage": (_i, [_vp, _vp, _d, _u64]),
+    "cellector_cell_origin": (_i, [_vp, _vp]),
+    "cellector_staged_coo": (_i, [_vp, C.POINTER(_u64), _vp, _vp, _vp, _vp, _u64]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -277,6 +280,35 @@ class Cellector:
         ent = np.empty(int(rp[-1]), np.uint64)
         self._ck(self._lib.cellector_csr_rows(self.h, row_begin, row_end, _p(rp), _p(ent), len(ent)))
         return rp, ent
+
+    # ---- re-staging the resident matrix (cell subset, per-read downsampling) without the files
+    def restage(self, keep=None, downsample_rate=0.0, seed=4):
+        """A new staged matrix from the one the ctx holds (cellector_restage): the cells with keep != 0 (None: all), renumbered
+        in ascending order, every read removed with probability downsample_rate (the combiner's meaning; restage.restage_coo is
+        the bit-identical numpy twin).  The ctx is then STAGED: call ingest_finish(min_alt, min_ref) next.  A peel is three calls:
+        c.restage(keep=c.excluded() == 0); c.ingest_finish(); c.run()."""
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            n = self.dims().total_cells
+            if keep.shape != (n,):
+                raise ValueError(f"restage: {n} keep flags expected, got shape {keep.shape}")
+        self._ck(self._lib.cellector_restage(self.h, _p(keep), float(downsample_rate), int(seed)))
+
+    def cell_origin(self):
+        """per current cell its index in the matrix of the last ingest from outside (cellector_cell_origin); identity until a
+        restage drops cells, composed over repeated restages"""
+        out = np.zeros(self.dims().total_cells, np.uint32)
+        self._ck(self._lib.cellector_cell_origin(self.h, _p(out)))
+        return out
+
+    def staged_coo(self):
+        """(locus0, cell0, alt, ref) uint32 arrays of the staged entries in staged order (cellector_staged_coo; diagnostic)"""
+        n = C.c_uint64(0)
+        self._ck(self._lib.cellector_staged_coo(self.h, C.byref(n), None, None, None, None, 0))
+        arrs = [np.zeros(n.value, np.uint32) for _ in range(4)]
+        if n.value:
+            self._ck(self._lib.cellector_staged_coo(self.h, C.byref(n), *[_p(a) for a in arrs], n.value))
+        return tuple(arrs)
 
     def exchange_buffer(self, which):
         ptr, n = C.c_void_p(), C.c_uint64()

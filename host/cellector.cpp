@@ -177,6 +177,10 @@ struct Params {
     bool locus_expected = false;                       // extension: option locus_moments = 1 (the sums main.rs:394 meant to form)
     std::optional<std::string> initial_minority;       // extension: barcodes of the initial exclusion set (main.rs:37 starts from none)
     std::optional<std::string> cell_detail;            // extension: barcodes whose per-locus records go to cell_detail.tsv (main.rs:176's TODO)
+    std::optional<std::string> cells;                  // extension: run on these barcodes only (cellector_restage; combiner main.rs:257-280's mask)
+    std::optional<double> downsample_rate;             // extension: probability that a read is removed (combiner's --downsample_rate, main.rs:83-88)
+    uint64_t seed = 4;                                 // ... and its --seed
+    bool restage() const { return cells || downsample_rate; }
 };
 
 const char *USAGE =
@@ -230,7 +234,16 @@ const char *USAGE =
     "                                                                       under the final alpha / beta and its log-pmf under the minority,\n"
     "                                                                       majority and doublet distributions of the posterior; one barcode\n"
     "                                                                       per line, first tab-separated column, blank lines ignored (not in\n"
-    "                                                                       the reference)\n";
+    "                                                                       the reference)\n"
+    "        --cells <file>                                                 run on the listed cells only, as if barcodes.tsv held only these\n"
+    "                                                                       lines (in its own order) and both matrices only these columns,\n"
+    "                                                                       renumbered; the matrix is cut on the GPU after the load; one barcode\n"
+    "                                                                       per line, first tab-separated column, blank lines ignored (not in\n"
+    "                                                                       the reference; one GPU)\n"
+    "        --downsample_rate <r>                                          remove every read with probability r in [0, 1] after the load, the\n"
+    "                                                                       meaning of the combiner's flag of this name (not in the reference;\n"
+    "                                                                       one GPU)\n"
+    "        --seed <n>                                                     seed of --downsample_rate's draw (default 4)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -256,7 +269,7 @@ Params load_params(int argc, char **argv)
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
-                                  "locus_expected"};
+                                  "locus_expected", "cells", "downsample_rate", "seed"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -332,6 +345,16 @@ Params load_params(int argc, char **argv)
     }
     if (got.count("initial_minority")) p.initial_minority = got["initial_minority"];
     if (got.count("cell_detail")) p.cell_detail = got["cell_detail"];
+    if (got.count("cells")) p.cells = got["cells"];
+    if (got.count("downsample_rate")) {
+        const double r = parse_f64("downsample_rate", got["downsample_rate"]);
+        if (!(r >= 0.0 && r <= 1.0)) die(1, "error: Invalid value '" + got["downsample_rate"] + "' for '--downsample_rate <r>': expected a number in [0, 1]");
+        p.downsample_rate = r;
+    }
+    if (got.count("seed")) p.seed = parse_usize("seed", got["seed"]);
+    for (const char *flag : {"cells", "downsample_rate"})
+        if (got.count(flag) && (p.devices_auto || p.devices.size() > 1))
+            die(1, std::string("error: The argument '--") + flag + "' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_assignments " + got["resolve_assignments"] +
                    "' works on one GPU and cannot be used with '--devices <a,b,...>'");
@@ -420,7 +443,8 @@ int main(int argc, char **argv)
     std::vector<std::string_view> barcodes = split_lines(barcode_text);
     std::vector<uint32_t> bc_slot;  // line index + 1 of the LAST line with that barcode, 0 = empty
     size_t n_distinct = 0;
-    {
+    auto index_barcodes = [&]() {
+        n_distinct = 0;
         size_t cap = 16;
         while (cap < 2 * barcodes.size() + 2) cap <<= 1;
         bc_slot.assign(cap, 0u);
@@ -432,12 +456,48 @@ int main(int argc, char **argv)
                 if (barcodes[bc_slot[h] - 1] == barcodes[i]) { bc_slot[h] = (uint32_t)i + 1; break; }
             }
         }
-    }
+    };
+    index_barcodes();
     auto barcode_to_cell = [&](std::string_view key) -> size_t {  // SIZE_MAX: not a barcode
         const size_t cap = bc_slot.size();
         for (size_t h = std::hash<std::string_view>{}(key) & (cap - 1);; h = (h + 1) & (cap - 1)) {
             if (!bc_slot[h]) return SIZE_MAX;
             if (barcodes[bc_slot[h] - 1] == key) return bc_slot[h] - 1;
+        }
+    };
+    // --cells: from here on the barcodes file IS its listed lines, in its own order: the ground truth, the barcode lists of the
+    // other flags and every output see only them, exactly as on a filtered barcodes.tsv.  The matrix follows after the load
+    // (cellector_restage); all_barcodes / all_slot keep the whole file to name a barcode that --cells dropped.
+    std::vector<std::string_view> all_barcodes;
+    std::vector<uint32_t> all_slot, kept_lines;  // kept_lines: the line index of every kept barcode, ascending
+    if (params.cells) {
+        all_barcodes = barcodes;
+        std::vector<uint8_t> listed(barcodes.size(), 0);
+        Lines in(*params.cells);
+        std::string line;
+        for (size_t line_no = 1; in.next(line); line_no++) {
+            const std::string bc = line.substr(0, line.find('\t'));
+            if (bc.empty()) continue;
+            const size_t cell = barcode_to_cell(bc);
+            if (cell == SIZE_MAX)
+                die(1, "error: --cells " + *params.cells + " line " + std::to_string(line_no) + ": barcode '" + bc +
+                           "' is not in the barcodes file " + params.barcodes);
+            listed[cell] = 1;
+        }
+        for (size_t i = 0; i < listed.size(); i++)
+            if (listed[i]) kept_lines.push_back((uint32_t)i);
+        if (kept_lines.empty()) die(1, "error: --cells " + *params.cells + " lists no barcode");
+        all_slot = bc_slot;
+        barcodes.clear();
+        for (const uint32_t i : kept_lines) barcodes.push_back(all_barcodes[i]);
+        index_barcodes();
+    }
+    auto dropped_by_cells = [&](std::string_view key) {  // a barcode of the whole file that --cells left out
+        if (all_slot.empty()) return false;
+        const size_t cap = all_slot.size();
+        for (size_t h = std::hash<std::string_view>{}(key) & (cap - 1);; h = (h + 1) & (cap - 1)) {
+            if (!all_slot[h]) return false;
+            if (all_barcodes[all_slot[h] - 1] == key) return true;
         }
     };
     // load_ground_truth (load_data.rs:85-107): one label per DISTINCT barcode (the vector has the map's length)
@@ -462,6 +522,9 @@ int main(int argc, char **argv)
             const std::string bc = line.substr(0, line.find('\t'));
             if (bc.empty()) continue;
             const size_t cell = barcode_to_cell(bc);
+            if (cell == SIZE_MAX && dropped_by_cells(bc))
+                die(1, std::string("error: --") + flag + " " + path + " line " + std::to_string(line_no) + ": barcode '" + bc +
+                           "' is not among the cells --cells " + *params.cells + " keeps");
             if (cell == SIZE_MAX)
                 die(1, std::string("error: --") + flag + " " + path + " line " + std::to_string(line_no) + ": barcode '" + bc +
                            "' is not in the barcodes file " + params.barcodes);
@@ -526,7 +589,30 @@ int main(int argc, char **argv)
     if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
     if (params.locus_expected) g.ck(cellector_set_option(g.c, "locus_moments", 1), "locus_expected");
     lap("barcodes + device init");
-    g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
+    if (!params.restage()) {
+        g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
+    } else {  // --cells / --downsample_rate: the staged matrix is cut and thinned on the device before the locus filter sees it
+        g.ck(cellector_ingest_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str()), "load_cell_data");
+        cellector_dims_t staged;
+        g.ck(cellector_dims(g.c, &staged), "dims");
+        std::vector<uint8_t> keep;
+        if (params.cells) {
+            keep.assign(staged.total_cells, 0);
+            for (const uint32_t i : kept_lines) {
+                if (i >= staged.total_cells)
+                    die(1, "error: --cells: barcode '" + std::string(all_barcodes[i]) + "' is line " + std::to_string(i + 1) +
+                               " of the barcodes file but the matrix has " + std::to_string(staged.total_cells) + " cells");
+                keep[i] = 1;
+            }
+        }
+        g.ck(cellector_restage(g.c, params.cells ? keep.data() : nullptr, params.downsample_rate.value_or(0.0), params.seed), "restage");
+        if (params.cells) {  // the barcodes above were filtered by the same rule the library renumbers by: cellector_cell_origin says so
+            std::vector<uint32_t> origin(kept_lines.size());
+            g.ck(cellector_cell_origin(g.c, origin.data()), "cell_origin");
+            if (origin != kept_lines) die(EXIT_PANIC, "--cells: the restaged cells are not the listed barcodes in file order");
+        }
+        g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
+    }
     lap("load_mtx (text -> device)");
     cellector_dims_t dm;
     g.ck(cellector_dims(g.c, &dm), "dims");

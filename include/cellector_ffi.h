@@ -220,6 +220,48 @@ cellector_status cellector_entries_per_cell(const cellector_ctx *ctx, uint32_t *
 cellector_status cellector_csr_rows(const cellector_ctx *ctx, uint64_t row_begin, uint64_t row_end,
                                     uint64_t *row_ptr /*[rows+1]*/, uint64_t *entries, uint64_t capacity);
 
+/* ---- re-staging the resident matrix: a cell subset and per-read downsampling without the files ---------
+ * The reference's cell set is whatever load_barcodes read (load_data.rs `load_barcodes`): dropping cells — the peel of the cells
+ * called minority, a doublet or empty-droplet list, a barcode whitelist — means rewriting barcodes.tsv and both matrices and
+ * loading again.  Its companion `combiner` samples cells (select_cells, combiner/src/main.rs:246-255; a barcode mask,
+ * main.rs:257-280) and thins the reads (main.rs:83-88 and main.rs:102-107), again from files into files.  cellector_restage does both on
+ * the staged COO the ctx still holds.
+ *   keep: [total_cells] of the matrix now staged, non-zero = keep, NULL = all cells.  Kept cells are renumbered in ascending
+ *   order of their old index; an entry survives iff its cell is kept, the survivors keep their relative order; a kept cell
+ *   without entries stays as an empty row.
+ *   downsample_rate: the probability that a read is REMOVED (the combiner's --downsample_rate), in [0, 1].  For the entry at
+ *   position i of the staged arrays the call reads (before the compaction), allele a (0 = ref, 1 = alt, the order of
+ *   main.rs:83-88) and read r = 0..count-1:  x = mix64(mix64((seed * GOLD) ^ ((i + 1) * GOLD)) + (2 r + a + 1) * GOLD), the read
+ *   is removed iff (x >> 11) < (uint64_t)(downsample_rate * 2^53); mix64 = the splitmix64 finaliser, GOLD = 0x9E3779B97F4A7C15
+ *   (the synthetic generator's).  All-integer: cellector_amd/restage.py is the bit-identical numpy twin.  Rate 0 draws nothing
+ *   and copies the counts, rate 1 leaves every count 0.  An entry whose two counts both reach 0 STAYS, as the combiner writes it.
+ *   The draw is keyed by position: it does not depend on keep, the launch grid or the engine.
+ *   Staged order is file order.  For an input that was not locus-major it is, after a finished ingest, the stable sort by locus
+ *   the ingest made: a restage before and after cellector_ingest_finish then draws differently — for such an input and only
+ *   for such an input — and the order options resolve_ties / resolve_posteriors then call "file order" is the sorted one.
+ * Afterwards the ctx is the one cellector_ingest_coo would have left for the restaged entries: state STAGED, total_cells = the
+ * number of kept cells, total_loci unchanged, PASS1 formed again from the new entries, everything the former matrix owned
+ * dropped exactly as a reload drops it (caller-bound NORM / LOCUS buffers are unbound, the iteration state is gone), options
+ * keep their values.  The caller then calls cellector_ingest_finish(min_alt, min_ref): the locus filter, L, locus_counts, the
+ * layouts, the near-tie band and the file-order copy of the resolve options are those of the restaged matrix.
+ * keep == NULL with rate 0 is legal: the same entries, staged again — the way back from a loaded matrix to another min_alt.
+ *   Allowed in state STAGED (after cellector_ingest_*) always, and on a loaded matrix when it kept its staged COO (option
+ *   keep_coo 1 at the ingest) and no iteration is in flight.  A single-device ctx without a communicator that holds all cells.
+ *   CELLECTOR_EINVAL with a message, the ctx untouched: a multi-device ctx, a communicator of more than one rank, a
+ *   cellector_set_shard range, no staged matrix, a loaded matrix without its COO, a call between cellector_em_begin and
+ *   cellector_em_finish, a rate outside [0, 1] or NaN, a selection of zero cells.
+ *   Memory: after validation the built matrix is dropped FIRST, then the new COO is allocated beside the old one (peak: both
+ *   COOs, 12 B per entry each, plus 18 B per cell and 8 B per 4096 entries) and the old one released.  On CELLECTOR_ENOMEM
+ *   the ctx is left STAGED holding the OLD entries and dims, ready for cellector_ingest_finish.  With keep == NULL (or every
+ *   cell kept) nothing is allocated: the counts are thinned where they are. */
+cellector_status cellector_restage(cellector_ctx *ctx, const uint8_t *keep, double downsample_rate, uint64_t seed);
+/* per current cell, its index in the matrix of the last ingest from outside (mtx / coo / synthetic); identity after such an
+ * ingest; composed over repeated restages */
+cellector_status cellector_cell_origin(const cellector_ctx *ctx, uint32_t *out /*[total_cells]*/);
+/* diagnostic like cellector_csr_rows: the staged entries in staged order; all four arrays NULL = count only */
+cellector_status cellector_staged_coo(const cellector_ctx *ctx, uint64_t *n, uint32_t *locus0, uint32_t *cell0,
+                                      uint32_t *alt, uint32_t *ref, uint64_t capacity);
+
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
     CELLECTOR_XCHG_PASS1 = 0, /* [5*total_loci]: cells_ref | cells_alt | sum_ref | sum_alt | n_entries */
