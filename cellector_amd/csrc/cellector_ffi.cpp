@@ -329,7 +329,7 @@ void cellector_destroy(cellector_ctx *c)
     drop_matrix(c);
     c->lf.reset(); c->d_counters.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
     c->sel_list.reset(); c->seld_hist.reset(); c->seld_state.reset();
-    c->res_cnt.reset(); c->res_dev.reset(); c->cell_origin.reset();
+    c->res_cnt.reset(); c->res_dev.reset(); c->cell_origin.reset(); c->cell_source.reset();
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
@@ -597,11 +597,13 @@ static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint
     {
         // keep a caller-bound PASS1 buffer across the reset
         double *bound = c->x_pass1 != c->x_pass1_own.get() ? c->x_pass1 : nullptr;
-        const uint64_t nb = c->n_pass1;
+        const uint64_t nb = c->pass1_bound_cap;  // (its whole capacity: n_pass1 is what the last matrix used of it)
         drop_matrix(c);
         if (bound) { c->x_pass1 = bound; c->n_pass1 = nb; }
     }
     c->cell_origin.reset();  // an ingest from outside: cellector_cell_origin is the identity again
+    c->cell_source.reset();  // ... cellector_cell_source all 0, no combine counted
+    c->n_combines = 0;
     REQUIRE(c, total_loci <= 0xffffffffull && total_cells <= 0xffffffffull, "dims exceed 32-bit indices");
     c->total_loci = total_loci;
     c->total_cells = total_cells;
@@ -936,14 +938,17 @@ cellector_status cellector_restage(cellector_ctx *c, const uint8_t *keep, double
     if (keep) {
         DevBuf<uint8_t> keep01;
         DevBuf<uint32_t> rank, origin;
+        DevBuf<uint8_t> source;
         StagedCoo neu;
         CHK(restage_cell_ranks(c, keep, tc, n_keep, c->cell_origin, &keep01, &rank, &origin));
+        if (c->cell_source) CHK(combine_source_select(c, tc, n_keep, rank, c->cell_source, &source));
         lap("cell ranks");
         CHK(restage_select(c, c->coo.view(), tc, keep01, rank, T, seed, &neu));  // (a failure up to here leaves the old entries staged)
         lap("count + scan + write");
         neu.sorted = c->coo.sorted;  // (a subsequence of a locus-major order is locus-major)
         c->coo = std::move(neu);
         c->cell_origin = std::move(origin);
+        if (c->cell_source) c->cell_source = std::move(source);
         c->total_cells = n_keep; c->cell_begin = 0; c->cell_end = n_keep; c->nloc = n_keep;
     } else {
         CHK(restage_thin(c, &c->coo, T, seed));
@@ -987,6 +992,133 @@ cellector_status cellector_staged_coo(const cellector_ctx *c, uint64_t *n, uint3
     return CELLECTOR_OK;
 }
 
+// ---- merging a second staged matrix in ---------------------------------------------------------------------
+// why a ctx cannot take part in cellector_combine (the conditions of restage_scope), or null
+static const char *combine_scope(const cellector_ctx *c)
+{
+    if (c->multi) return "is a multi-device ctx: its staged entries are sharded";
+    if (comm_active(c->comm)) return "has a communicator: every rank stages its own cells";
+    if (c->state == cellector_ctx::ST_EMPTY) return "has no staged matrix";
+    if (c->nloc != c->total_cells) return "holds a cellector_set_shard range, not all cells";
+    if (c->em_phase != 0) return "is between cellector_em_begin and cellector_em_finish";
+    if (!c->coo.locus) return "is a loaded matrix without its staged COO (option keep_coo=1 before the ingest)";
+    return nullptr;
+}
+
+cellector_status cellector_combine(cellector_ctx *c, const cellector_ctx *src, const uint8_t *src_keep, const uint32_t *locus_map,
+                                   uint64_t total_loci_out, double downsample_rate, uint64_t seed)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (!src) return ctx_fail(c, CELLECTOR_EINVAL, "combine: src is NULL");
+    if (c == src) return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx and src are the same ctx");
+    if (const char *why = combine_scope(c)) return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx %s", why);
+    if (const char *why = combine_scope(src)) return ctx_fail(c, CELLECTOR_EINVAL, "combine: src %s", why);
+    if (c->device != src->device)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx is on device %d, src on device %d", c->device, src->device);
+    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: downsample_rate %g is not in [0, 1]", downsample_rate);
+    const uint64_t n_ctx = c->total_cells, tc_src = src->total_cells, tl_src = src->total_loci;
+    uint64_t n_kept = tc_src;
+    if (src_keep) {
+        n_kept = 0;
+        for (uint64_t i = 0; i < tc_src; i++) n_kept += src_keep[i] != 0;
+    }
+    if (n_kept == 0) return ctx_fail(c, CELLECTOR_EINVAL, "combine: the selection keeps none of src's %llu cells", (unsigned long long)tc_src);
+    if (total_loci_out < c->total_loci)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: total_loci_out %llu is below ctx's total_loci %llu", (unsigned long long)total_loci_out,
+                        (unsigned long long)c->total_loci);
+    if (total_loci_out > 0xffffffffull)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: total_loci_out %llu exceeds 32-bit indices", (unsigned long long)total_loci_out);
+    if (locus_map) {
+        for (uint64_t j = 0; j < tl_src; j++)
+            if (locus_map[j] >= total_loci_out)
+                return ctx_fail(c, CELLECTOR_EINVAL, "combine: locus_map[%llu] = %u is not below total_loci_out %llu", (unsigned long long)j,
+                                locus_map[j], (unsigned long long)total_loci_out);
+    } else if (tl_src > total_loci_out) {
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: without a locus_map src's total_loci %llu must not exceed total_loci_out %llu",
+                        (unsigned long long)tl_src, (unsigned long long)total_loci_out);
+    }
+    if (n_ctx + n_kept > 0xffffffffull)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: %llu + %llu cells exceed 32-bit indices", (unsigned long long)n_ctx,
+                        (unsigned long long)n_kept);
+    if (c->n_combines >= 255) return ctx_fail(c, CELLECTOR_EINVAL, "combine: 255 combines since the last ingest from outside (cell_source is a byte)");
+    const uint64_t need_p1 = (uint64_t)P1_PLANES * total_loci_out;
+    const bool p1_bound = c->x_pass1 != c->x_pass1_own.get();
+    if (p1_bound && c->pass1_bound_cap < need_p1)
+        return ctx_fail(c, CELLECTOR_EINVAL, "combine: the bound PASS1 exchange buffer holds %llu values, total_loci_out %llu needs %llu",
+                        (unsigned long long)c->pass1_bound_cap, (unsigned long long)total_loci_out, (unsigned long long)need_p1);
+    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
+    SETDEV(c);
+    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
+    LapTimer t;
+    auto lap = [&](const char *what) {
+        if (timing) fprintf(stderr, "[timing]   combine: %-22s %8.4f s\n", what, t.lap());
+    };
+    HIPCHK(c, hipStreamSynchronize(src->stream));  // (src is only read from here on, on ctx's stream)
+    // ---- validated: from here ctx changes.  The built matrix goes first; everything new is made beside the old entries and
+    // moved in at the end, so a failure on the way leaves ctx STAGED with its old entries and dims
+    if (c->state == cellector_ctx::ST_READY) {
+        unbuild_matrix(c);
+        lap("drop built matrix");
+    }
+    StagedCoo sel, own_sorted, sel_sorted, merged;
+    DevBuf<uint32_t> origin;
+    DevBuf<uint8_t> source;
+    DevBuf<double> p1;
+    {
+        // src's side: the selection and the draw are cellector_restage's, on src's arrays; then the renumbering
+        std::vector<uint8_t> all;
+        if (!src_keep) { all.assign(tc_src, 1); src_keep = all.data(); }
+        DevBuf<uint8_t> keep01;
+        DevBuf<uint32_t> rank, src_origin, d_map;
+        CHK(restage_cell_ranks(c, src_keep, tc_src, n_kept, src->cell_origin, &keep01, &rank, &src_origin));
+        CHK(combine_cells(c, n_ctx, n_kept, c->cell_origin, src_origin, c->cell_source, (uint8_t)(c->n_combines + 1), &origin, &source));
+        lap("cell ranks");
+        CHK(restage_select(c, src->coo.view(), tc_src, keep01, rank, T, seed, &sel));
+        lap("select src");
+        if (locus_map) {
+            CHK(dev_alloc(c, &d_map, tl_src));
+            HIPCHK(c, hipMemcpyAsync(d_map, locus_map, tl_src * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        CHK(combine_map(c, &sel, locus_map ? d_map.get() : nullptr, tl_src, (uint32_t)n_ctx));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (d_map and the host map are read)
+        lap("map");
+    }
+    CooView a = c->coo.view(), b = sel.view();
+    bool asc_a = true, asc_b = true;
+    CHK(combine_ascending(c, a, b, &asc_a, &asc_b));
+    if (!asc_a) { CHK(combine_sort(c, a, &own_sorted)); a = own_sorted.view(); }
+    if (!asc_b) { CHK(combine_sort(c, b, &sel_sorted)); sel.reset(); b = sel_sorted.view(); }
+    lap("order check / sort");
+    CHK(combine_merge(c, a, b, &merged));
+    lap("merge");
+    if (!p1_bound && need_p1 != c->n_pass1) CHK(dev_alloc(c, &p1, need_p1));
+    // ---- nothing below fails for memory
+    c->coo = std::move(merged);
+    c->cell_origin = std::move(origin);
+    c->cell_source = std::move(source);
+    c->n_combines++;
+    if (p1) { c->x_pass1_own = std::move(p1); c->x_pass1 = c->x_pass1_own; }
+    c->n_pass1 = need_p1;
+    c->total_loci = total_loci_out;
+    c->total_cells = n_ctx + n_kept; c->cell_begin = 0; c->cell_end = c->total_cells; c->nloc = c->total_cells;
+    c->state = cellector_ctx::ST_STAGED;
+    CHK(ingest_pass1(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lap("release + PASS1");
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_cell_source(const cellector_ctx *c, uint8_t *out)
+{
+    if (!c || !out) return CELLECTOR_EINVAL;
+    cellector_dims_t d;
+    CHK(cellector_dims(c, &d));
+    if (!c->multi && c->cell_source) return d2h(c, out, c->cell_source, d.total_cells);
+    memset(out, 0, d.total_cells);
+    return CELLECTOR_OK;
+}
+
 // ---- exchange buffers ---------------------------------------------------------------------------------
 cellector_status cellector_exchange_buffer(cellector_ctx *c, cellector_xchg which, void **dev_ptr, uint64_t *n)
 {
@@ -1018,7 +1150,7 @@ cellector_status cellector_bind_exchange_buffer(cellector_ctx *c, cellector_xchg
     case CELLECTOR_XCHG_PASS1:
         REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "bind PASS1 before ingest");
         c->x_pass1_own.reset();
-        c->x_pass1 = p; c->n_pass1 = n;
+        c->x_pass1 = p; c->n_pass1 = n; c->pass1_bound_cap = n;
         break;
     case CELLECTOR_XCHG_NORM:
         REQUIRE(c, c->state != cellector_ctx::ST_READY || n >= c->total_cells, "NORM buffer too small");

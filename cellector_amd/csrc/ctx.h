@@ -349,6 +349,12 @@ struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
     // cellector_cell_origin: per current cell its index in the matrix of the last ingest from outside; null = identity.  Not
     // part of CtxMatrix: begin_ingest clears it, cellector_restage composes it and carries it over its own reset
     DevBuf<uint32_t> cell_origin;
+    // cellector_cell_source: per current cell 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine
+    // since; null = all 0.  Same lifetime as cell_origin; n_combines counts the combines since that ingest (at most 255)
+    DevBuf<uint8_t> cell_source;
+    uint32_t n_combines = 0;
+    // the capacity (f64 values) of a PASS1 buffer the caller bound; n_pass1 is what the staged matrix uses of it
+    uint64_t pass1_bound_cap = 0;
 
     DevBuf<double> lf;            // [LF_TABLE_N] ln factorial table
     DevBuf<uint32_t> d_counters;  // [8] device scratch counters
@@ -519,6 +525,21 @@ cellector_status restage_select(cellector_ctx *c, const CooView &in, uint64_t tc
                                 uint64_t seed, StagedCoo *out);
 // ... all cells: the two counts thinned where they are
 cellector_status restage_thin(cellector_ctx *c, StagedCoo *coo, uint64_t T, uint64_t seed);
+// cellector_combine (kernels_combine.hip).  The selected src entries renumbered where they are: locus through d_map [n_map]
+// (device; null: identity), cell + cell_add
+cellector_status combine_map(cellector_ctx *c, StagedCoo *coo, const uint32_t *d_map, uint64_t n_map, uint32_t cell_add);
+// ... is the key locus << 32 | cell strictly ascending over the entries of a, of b?  (one launch, one round trip)
+cellector_status combine_ascending(cellector_ctx *c, const CooView &a, const CooView &b, bool *a_ascending, bool *b_ascending);
+// ... the entries sorted by (locus, cell, ref, alt) into a new COO
+cellector_status combine_sort(cellector_ctx *c, const CooView &v, StagedCoo *out);
+// ... two sides, each ascending by (locus, cell), merged by that key into a new COO (side a first among equals)
+cellector_status combine_merge(cellector_ctx *c, const CooView &a, const CooView &b, StagedCoo *out);
+// ... origin / source [n_ctx + n_kept]: the ctx's own (null: identity / 0), then src_origin [n_kept] / k
+cellector_status combine_cells(cellector_ctx *c, uint64_t n_ctx, uint64_t n_kept, const uint32_t *old_origin, const uint32_t *src_origin,
+                               const uint8_t *old_source, uint8_t k, DevBuf<uint32_t> *origin, DevBuf<uint8_t> *source);
+// ... a restage's source [n_keep]: old_source [tc] at the kept cells (rank as restage_cell_ranks made it)
+cellector_status combine_source_select(cellector_ctx *c, uint64_t tc, uint64_t n_keep, const uint32_t *rank, const uint8_t *old_source,
+                                       DevBuf<uint8_t> *source);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);

@@ -47,6 +47,8 @@ SIGNATURES = {
     "cellector_restage": (_i, [_vp, _vp, _d, _u64]),
     "cellector_cell_origin": (_i, [_vp, _vp]),
     "cellector_staged_coo": (_i, [_vp, C.POINTER(_u64), _vp, _vp, _vp, _vp, _u64]),
+    "cellector_combine": (_i, [_vp, _vp, _vp, _vp, _u64, _d, _u64]),
+    "cellector_cell_source": (_i, [_vp, _vp]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -309,6 +311,35 @@ class Cellector:
         if n.value:
             self._ck(self._lib.cellector_staged_coo(self.h, C.byref(n), *[_p(a) for a in arrs], n.value))
         return tuple(arrs)
+
+    # ---- merging a second staged matrix in (the other half of the reference's combiner)
+    def combine(self, src, keep=None, locus_map=None, total_loci=None, downsample_rate=0.0, seed=4):
+        """The staged entries of `src` (another Cellector on the same GPU; only read) join this ctx's (cellector_combine): src's
+        cells with keep != 0 (None: all) behind this ctx's cells, src's loci through locus_map (None: identity), src's reads
+        thinned with downsample_rate; everything then ascends by (locus, cell, ref, alt) (combine.combine_coo is the
+        bit-identical numpy twin).  total_loci defaults to the larger of this ctx's total_loci and src's (no map) or
+        1 + locus_map.max() (with one).  The ctx is then STAGED: call ingest_finish(min_alt, min_ref) next.  A titration point:
+        c.combine(minority, keep); c.ingest_finish(); c.run(); c.restage(keep=c.cell_source() == 0)."""
+        sd = src.dims()
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if keep.shape != (sd.total_cells,):
+                raise ValueError(f"combine: {sd.total_cells} keep flags expected, got shape {keep.shape}")
+        if locus_map is not None:
+            locus_map = np.ascontiguousarray(locus_map, dtype=np.uint32)
+            if locus_map.shape != (sd.total_loci,):
+                raise ValueError(f"combine: {sd.total_loci} map values expected, got shape {locus_map.shape}")
+        if total_loci is None:
+            theirs = sd.total_loci if locus_map is None else (1 + int(locus_map.max()) if locus_map.size else 0)
+            total_loci = max(self.dims().total_loci, theirs)
+        self._ck(self._lib.cellector_combine(self.h, src.h, _p(keep), _p(locus_map), int(total_loci), float(downsample_rate), int(seed)))
+
+    def cell_source(self):
+        """per current cell 0 = from the last ingest from outside, k = brought in by the k-th combine since
+        (cellector_cell_source); restages compose it like cell_origin"""
+        out = np.zeros(self.dims().total_cells, np.uint8)
+        self._ck(self._lib.cellector_cell_source(self.h, _p(out)))
+        return out
 
     def exchange_buffer(self, which):
         ptr, n = C.c_void_p(), C.c_uint64()

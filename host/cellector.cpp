@@ -181,6 +181,10 @@ struct Params {
     std::optional<double> downsample_rate;             // extension: probability that a read is removed (combiner's --downsample_rate, main.rs:83-88)
     uint64_t seed = 4;                                 // ... and its --seed
     bool restage() const { return cells || downsample_rate; }
+    // extension: a second dataset merged in on the GPU (cellector_combine; the combiner's --alt2 / --ref2 / --barcodes2 and, for
+    // --mix_cells, its barcode mask) with the identity locus map: both datasets come from the same variant VCF
+    std::optional<std::string> mix_alt, mix_ref, mix_barcodes, mix_cells;
+    bool mix() const { return mix_alt.has_value(); }
 };
 
 const char *USAGE =
@@ -243,7 +247,18 @@ const char *USAGE =
     "        --downsample_rate <r>                                          remove every read with probability r in [0, 1] after the load, the\n"
     "                                                                       meaning of the combiner's flag of this name (not in the reference;\n"
     "                                                                       one GPU)\n"
-    "        --seed <n>                                                     seed of --downsample_rate's draw (default 4)\n";
+    "        --seed <n>                                                     seed of --downsample_rate's draw (default 4)\n"
+    "        --mix_alt <alt2> --mix_ref <ref2> --mix_barcodes <barcodes2>   merge a second dataset in on the GPU after the load, as the combiner\n"
+    "                                                                       writes two datasets into one: its cells behind the first one's, its\n"
+    "                                                                       barcodes with the last character replaced by 2; both datasets must\n"
+    "                                                                       come from the same variant VCF (equal locus counts).  The three are\n"
+    "                                                                       given together.  barcodes.tsv and gt.tsv (majority / minority) of\n"
+    "                                                                       the mixture are written to the output directory; without -g that\n"
+    "                                                                       gt.tsv is the ground truth.  --cells, --downsample_rate and --seed\n"
+    "                                                                       act on the first dataset, --mix_cells and the same rate and seed on\n"
+    "                                                                       the second (not in the reference; one GPU)\n"
+    "        --mix_cells <file>                                             take only the listed cells of the second dataset (its own barcodes,\n"
+    "                                                                       one per line, first tab-separated column, blank lines ignored)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -269,7 +284,8 @@ Params load_params(int argc, char **argv)
                                   "vcf", "posterior_threshold", "interquartile_range_multiple", "min_alleles_posterior",
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
-                                  "locus_expected", "cells", "downsample_rate", "seed"};
+                                  "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
+                                  "mix_cells"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -352,7 +368,16 @@ Params load_params(int argc, char **argv)
         p.downsample_rate = r;
     }
     if (got.count("seed")) p.seed = parse_usize("seed", got["seed"]);
-    for (const char *flag : {"cells", "downsample_rate"})
+    if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
+    if (got.count("mix_ref")) p.mix_ref = got["mix_ref"];
+    if (got.count("mix_barcodes")) p.mix_barcodes = got["mix_barcodes"];
+    if (got.count("mix_cells")) p.mix_cells = got["mix_cells"];
+    if (p.mix_alt || p.mix_ref || p.mix_barcodes || p.mix_cells)
+        for (const char *flag : {"mix_alt", "mix_ref", "mix_barcodes"})
+            if (!got.count(flag))
+                die(1, std::string("error: The arguments '--mix_alt', '--mix_ref' and '--mix_barcodes' are given together: '--") + flag +
+                           " <file>' was not provided");
+    for (const char *flag : {"cells", "downsample_rate", "mix_alt"})
         if (got.count(flag) && (p.devices_auto || p.devices.size() > 1))
             die(1, std::string("error: The argument '--") + flag + "' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
@@ -492,6 +517,46 @@ int main(int argc, char **argv)
         for (const uint32_t i : kept_lines) barcodes.push_back(all_barcodes[i]);
         index_barcodes();
     }
+    // --mix_*: the second dataset's barcodes (those --mix_cells lists, in their file's order) follow the first one's, the last
+    // character replaced by 2 (combiner/src/main.rs:174-184); from here on the barcodes file IS that list, as the combiner
+    // writes it into its output's barcodes.tsv
+    const size_t n_first = barcodes.size();
+    std::string mix_text;
+    std::vector<uint8_t> mix_keep;        // [lines of --mix_barcodes] with --mix_cells
+    std::vector<std::string> mix_names;   // the renamed barcodes of the cells taken
+    size_t mix_lines = 0;
+    if (params.mix()) {
+        mix_text = read_whole(*params.mix_barcodes);
+        const std::vector<std::string_view> theirs = split_lines(mix_text);
+        mix_lines = theirs.size();
+        if (params.mix_cells) {
+            std::map<std::string_view, size_t> line_of;  // (a later duplicate overwrites an earlier one, as load_barcodes)
+            for (size_t i = 0; i < theirs.size(); i++) line_of[theirs[i]] = i;
+            mix_keep.assign(theirs.size(), 0);
+            Lines in(*params.mix_cells);
+            std::string line;
+            for (size_t line_no = 1; in.next(line); line_no++) {
+                const std::string bc = line.substr(0, line.find('\t'));
+                if (bc.empty()) continue;
+                const auto at = line_of.find(std::string_view(bc));
+                if (at == line_of.end())
+                    die(1, "error: --mix_cells " + *params.mix_cells + " line " + std::to_string(line_no) + ": barcode '" + bc +
+                               "' is not in the barcodes file " + *params.mix_barcodes);
+                mix_keep[at->second] = 1;
+            }
+            if (std::find(mix_keep.begin(), mix_keep.end(), 1) == mix_keep.end())
+                die(1, "error: --mix_cells " + *params.mix_cells + " lists no barcode");
+        }
+        for (size_t i = 0; i < theirs.size(); i++) {
+            if (params.mix_cells && !mix_keep[i]) continue;
+            std::string bc(theirs[i]);
+            if (!bc.empty()) bc.pop_back();
+            bc += '2';
+            mix_names.push_back(std::move(bc));
+        }
+        for (const std::string &bc : mix_names) barcodes.push_back(bc);  // (mix_names is complete: the views stay valid)
+        index_barcodes();
+    }
     auto dropped_by_cells = [&](std::string_view key) {  // a barcode of the whole file that --cells left out
         if (all_slot.empty()) return false;
         const size_t cap = all_slot.size();
@@ -511,6 +576,40 @@ int main(int argc, char **argv)
             const size_t cell = barcode_to_cell(cols[0]);
             if (cell != SIZE_MAX && cell < ground_truth.size()) ground_truth[cell] = cols[1];
         }
+    }
+    if (params.mix()) {  // the combiner's barcodes.tsv and gt.tsv of the mixture (main.rs:155-186); without -g the run's ground truth
+        std::string bc_out, gt_out;
+        for (size_t i = 0; i < barcodes.size(); i++) {
+            const char *label = i < n_first ? "majority" : "minority";
+            bc_out += barcodes[i]; bc_out += '\n';
+            gt_out += barcodes[i]; gt_out += '\t'; gt_out += label; gt_out += '\n';
+            if (!params.ground_truth) {
+                const size_t cell = barcode_to_cell(barcodes[i]);
+                if (cell < ground_truth.size()) ground_truth[cell] = label;
+            }
+        }
+        // an input of this run under one of the two names in the output directory would be lost: refuse before either is written
+        for (const char *name : {"barcodes.tsv", "gt.tsv"}) {
+            const std::string path = params.output_directory + "/" + name;
+            struct stat mine, theirs;
+            if (stat(path.c_str(), &mine) != 0) continue;
+            for (const auto &[flag, in] : std::vector<std::pair<const char *, std::optional<std::string>>>{
+                     {"--barcodes", params.barcodes}, {"--ground_truth", params.ground_truth}, {"--mix_barcodes", params.mix_barcodes},
+                     {"--mix_cells", params.mix_cells}, {"--cells", params.cells}, {"--initial_minority", params.initial_minority},
+                     {"--cell_detail", params.cell_detail}})
+                if (in && stat(in->c_str(), &theirs) == 0 && mine.st_dev == theirs.st_dev && mine.st_ino == theirs.st_ino)
+                    die(1, std::string("error: the mixture's ") + name + " would overwrite the " + flag + " file " + *in +
+                               ": choose another --output_directory");
+        }
+        auto write_text = [&](const char *name, const std::string &text) {
+            const std::string path = params.output_directory + "/" + name;
+            FILE *f = fopen(path.c_str(), "w");
+            if (!f) die(EXIT_PANIC, "Unable to create file " + path);
+            fwrite(text.data(), 1, text.size(), f);
+            fclose(f);
+        };
+        write_text("barcodes.tsv", bc_out);
+        write_text("gt.tsv", gt_out);
     }
 
     // a barcode list of an extension flag: one per line, first tab-separated column, blank lines ignored; file order, repeats kept
@@ -589,7 +688,7 @@ int main(int argc, char **argv)
     if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
     if (params.locus_expected) g.ck(cellector_set_option(g.c, "locus_moments", 1), "locus_expected");
     lap("barcodes + device init");
-    if (!params.restage()) {
+    if (!params.restage() && !params.mix()) {
         g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     } else {  // --cells / --downsample_rate: the staged matrix is cut and thinned on the device before the locus filter sees it
         g.ck(cellector_ingest_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str()), "load_cell_data");
@@ -610,6 +709,34 @@ int main(int argc, char **argv)
             std::vector<uint32_t> origin(kept_lines.size());
             g.ck(cellector_cell_origin(g.c, origin.data()), "cell_origin");
             if (origin != kept_lines) die(EXIT_PANIC, "--cells: the restaged cells are not the listed barcodes in file order");
+        }
+        if (params.mix()) {  // the second dataset: staged in a ctx of its own on the same GPU, merged in, released
+            Ctx second;
+            if (cellector_create(&second.c, devices[0]) != CELLECTOR_OK) die(EXIT_PANIC, "cellector: no second context on the device");
+            second.ck(cellector_ingest_mtx(second.c, params.mix_alt->c_str(), params.mix_ref->c_str()), "load_cell_data (--mix_alt / --mix_ref)");
+            cellector_dims_t ours, theirs;
+            g.ck(cellector_dims(g.c, &ours), "dims");
+            second.ck(cellector_dims(second.c, &theirs), "dims");
+            if (ours.total_loci != theirs.total_loci)
+                die(1, "error: --mix_alt " + *params.mix_alt + " has " + std::to_string(theirs.total_loci) + " loci, --alt " + params.alt_mtx +
+                           " has " + std::to_string(ours.total_loci) + " loci: both datasets must come from the same variant VCF");
+            if (mix_lines < theirs.total_cells)
+                die(EXIT_PANIC, "index out of bounds: the barcodes file " + *params.mix_barcodes + " has " + std::to_string(mix_lines) +
+                                    " lines but the matrix has " + std::to_string(theirs.total_cells) + " cells");
+            std::vector<uint8_t> take;
+            if (params.mix_cells) {
+                for (size_t i = theirs.total_cells; i < mix_keep.size(); i++)
+                    if (mix_keep[i])
+                        die(1, "error: --mix_cells: a listed barcode is line " + std::to_string(i + 1) + " of " + *params.mix_barcodes +
+                                   " but the matrix has " + std::to_string(theirs.total_cells) + " cells");
+                take.assign(mix_keep.begin(), mix_keep.begin() + (ptrdiff_t)theirs.total_cells);
+            } else if (mix_lines != theirs.total_cells) {
+                die(EXIT_PANIC, "the barcodes file " + *params.mix_barcodes + " has " + std::to_string(mix_lines) + " lines but the matrix has " +
+                                    std::to_string(theirs.total_cells) + " cells");
+            }
+            g.ck(cellector_combine(g.c, second.c, params.mix_cells ? take.data() : nullptr, nullptr, ours.total_loci,
+                                   params.downsample_rate.value_or(0.0), params.seed), "combine");
+            cellector_destroy(second.c);
         }
         g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
     }

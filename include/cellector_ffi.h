@@ -262,6 +262,50 @@ cellector_status cellector_cell_origin(const cellector_ctx *ctx, uint32_t *out /
 cellector_status cellector_staged_coo(const cellector_ctx *ctx, uint64_t *n, uint32_t *locus0, uint32_t *cell0,
                                       uint32_t *alt, uint32_t *ref, uint64_t capacity);
 
+/* ---- merging a second staged matrix in: the other half of the reference's `combiner` ---------------------
+ * The combiner takes a second dataset, renumbers its loci into the first one's numbering (get_locus_mapping,
+ * combiner/src/main.rs:197-231), puts its cells behind the first one's (main.rs:161-186) and writes everything in the order of
+ * lines.sort() (main.rs:111), from files into files.  cellector_combine does that between two ctxs on one GPU: the entries of
+ * `src`'s staged COO join those of `ctx`; `src` is only read and is left exactly as it was, including a matrix it has built.
+ *   src_keep: [src total_cells], non-zero = take the cell, NULL = all.  downsample_rate / seed: src's reads only.  Selection and
+ *   thinning are exactly cellector_restage's — renumbering by ascending old index, the same all-integer draw — keyed by the
+ *   position i in SRC's staged arrays before the selection: restage.restage_coo on src's arrays is the twin of this step.  The
+ *   caller thins ctx's own reads beforehand with cellector_restage(ctx, NULL, rate, seed).
+ *   locus_map: [src total_loci], src's 0-based locus -> the 0-based locus of the result, NULL = identity.  It need not be
+ *   monotone or injective (two src loci may fold into one).  combine.locus_map_from_vcfs builds the combiner's map.
+ *   A surviving src entry (l, c, alt, ref) becomes (locus_map[l], n_ctx + rank(c), alt, ref), n_ctx = ctx's total_cells before
+ *   the call; ctx's own entries keep their indices.  total_cells becomes n_ctx + n_kept, total_loci becomes total_loci_out.
+ *   Staged order afterwards: ALL entries ascending by (locus, cell, ref, alt), the combiner's sort on the tuple it pushes.  The
+ *   order is unique: it depends neither on the order either side was staged in nor on the grid.  (The two sides' cell ranges
+ *   are disjoint: each side is taken as it stands when its (locus, cell) pairs ascend strictly — every vartrix file, the
+ *   synthetic generator and any restage of either — and sorted by the tuple otherwise; the sides are then merged by
+ *   (locus, cell).)  The staged COO is locus-major afterwards.
+ *   cellector_cell_origin of a new cell is SRC's cell_origin of the cell it came from; ctx's cells keep theirs.
+ *   cellector_cell_source is 0 for every cell after an ingest from outside; a cell brought in by the k-th combine since that
+ *   ingest gets k, ctx's cells keep theirs, the values src's cells had in src are not carried over.  cellector_restage composes
+ *   the source the way it composes the origin; an ingest from outside clears it and the combine count.
+ * Afterwards, as after a restage: state STAGED, PASS1 formed again from all entries, everything the former matrix of ctx owned
+ * dropped as a reload drops it, options keep their values; cellector_ingest_finish follows.
+ *   Both ctxs: single-device, on the same GPU, without a communicator or a cellector_set_shard range, holding a staged COO
+ *   (state STAGED, or a loaded matrix that kept it: option keep_coo 1), not between cellector_em_begin and cellector_em_finish.
+ *   CELLECTOR_EINVAL with a message (on ctx), BOTH ctxs untouched: ctx == src, different devices, a multi-device, communicator
+ *   or sharded ctx on either side, no staged COO on either side, an iteration in flight on either side, a rate outside [0, 1]
+ *   or NaN, a selection of zero cells, total_loci_out below ctx's total_loci or above 2^32 - 1, a map value >= total_loci_out
+ *   (the message names the first one), a NULL map with src's total_loci > total_loci_out, n_ctx + n_kept > 2^32 - 1, more than
+ *   255 combines since the last ingest from outside, a caller-bound PASS1 buffer smaller than 5 * total_loci_out (the
+ *   size it was bound with counts, not what the last ingest used of it).
+ *   Memory: after validation ctx's built matrix is dropped FIRST, then everything new is allocated beside ctx's entries: the
+ *   selected src entries (12 B each) and the merged COO (12 B per entry of the result), so the peak is 24 B per ctx entry and
+ *   24 B per selected src entry, plus 5 B per cell of the result, 18 B per src cell, 8 B per 4096 src entries and per 2048
+ *   entries of the result; a side that has to be sorted adds 32 B per entry of that side (and the radix sort's scratch) while it is sorted, 12 B after.  On
+ *   CELLECTOR_ENOMEM ctx is left STAGED holding its OLD entries, dims, origin and source, ready for cellector_ingest_finish. */
+cellector_status cellector_combine(cellector_ctx *ctx, const cellector_ctx *src,
+                                   const uint8_t *src_keep /*[src total_cells] or NULL = all*/,
+                                   const uint32_t *locus_map /*[src total_loci] or NULL = identity*/,
+                                   uint64_t total_loci_out, double downsample_rate, uint64_t seed);
+/* per current cell: 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine since */
+cellector_status cellector_cell_source(const cellector_ctx *ctx, uint8_t *out /*[total_cells]*/);
+
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
     CELLECTOR_XCHG_PASS1 = 0, /* [5*total_loci]: cells_ref | cells_alt | sum_ref | sum_alt | n_entries */
