@@ -1109,6 +1109,91 @@ cellector_status cellector_combine(cellector_ctx *c, const cellector_ctx *src, c
     return CELLECTOR_OK;
 }
 
+// ---- synthetic doublets from resident cells -----------------------------------------------------------------
+cellector_status cellector_add_doublets(cellector_ctx *c, const uint32_t *cell_a, const uint32_t *cell_b, uint64_t n_pairs,
+                                        double downsample_rate, uint64_t seed)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (const char *why = combine_scope(c)) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: ctx %s", why);
+    if (n_pairs == 0) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: no pairs");
+    if (!cell_a || !cell_b) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: %s is NULL", cell_a ? "cell_b" : "cell_a");
+    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
+        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: downsample_rate %g is not in [0, 1]", downsample_rate);
+    const uint64_t n_ctx = c->total_cells;
+    if (n_ctx + n_pairs > 0xffffffffull || n_ctx + n_pairs < n_ctx)
+        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: %llu + %llu cells exceed 32-bit indices", (unsigned long long)n_ctx,
+                        (unsigned long long)n_pairs);
+    for (uint64_t j = 0; j < n_pairs; j++) {
+        if (cell_a[j] >= n_ctx || cell_b[j] >= n_ctx)
+            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu (%u, %u) names a cell that is not below total_cells %llu",
+                            (unsigned long long)j, cell_a[j], cell_b[j], (unsigned long long)n_ctx);
+        if (cell_a[j] == cell_b[j])
+            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu names cell %u twice", (unsigned long long)j, cell_a[j]);
+    }
+    if (c->n_combines >= 255)
+        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: 255 combines since the last ingest from outside (cell_source is a byte)");
+    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
+    SETDEV(c);
+    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
+    LapTimer t;
+    auto lap = [&](const char *what) {
+        if (timing) fprintf(stderr, "[timing]   add_doublets: %-22s %8.4f s\n", what, t.lap());
+    };
+    // ---- the doublet side, beside a built matrix that stays: a sum above CELLECTOR_MAX_COUNT is known only now and must leave
+    // the ctx as it was
+    StagedCoo dbl, own_sorted, merged;
+    DevBuf<uint32_t> dbl_origin, origin;
+    DevBuf<uint8_t> source;
+    {
+        // the fan table: cell c is side s of pair j for the values 2 j + s of fan_val[fan_ptr[c] .. fan_ptr[c + 1])
+        std::vector<uint64_t> fan_ptr(n_ctx + 1, 0), fan_val(2 * n_pairs);
+        for (uint64_t j = 0; j < n_pairs; j++) { fan_ptr[cell_a[j] + 1]++; fan_ptr[cell_b[j] + 1]++; }
+        for (uint64_t i = 0; i < n_ctx; i++) fan_ptr[i + 1] += fan_ptr[i];
+        {
+            std::vector<uint64_t> at(fan_ptr.begin(), fan_ptr.end() - 1);
+            for (uint64_t j = 0; j < n_pairs; j++) { fan_val[at[cell_a[j]]++] = 2 * j; fan_val[at[cell_b[j]]++] = 2 * j + 1; }
+        }
+        bool overflow = false;
+        uint64_t over_pair = 0;
+        uint32_t over_locus = 0;
+        int over_allele = 0;
+        CHK(doublets_build(c, c->coo.view(), n_ctx, c->total_loci, fan_ptr.data(), fan_val.data(), fan_val.size(), T, seed, &dbl, &overflow,
+                           &over_pair, &over_locus, &over_allele));
+        if (overflow)
+            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu (%u, %u): the summed %s count at locus %u exceeds %u",
+                            (unsigned long long)over_pair, over_pair < n_pairs ? cell_a[over_pair] : 0u,
+                            over_pair < n_pairs ? cell_b[over_pair] : 0u, over_allele ? "alt" : "ref", over_locus, CELLECTOR_MAX_COUNT);
+        CHK(doublets_origin(c, cell_a, n_pairs, n_ctx, c->cell_origin, &dbl_origin));
+        lap("doublet side");
+    }
+    // ---- validated: from here ctx changes.  The built matrix goes; everything else new is made beside the old entries and moved
+    // in at the end, so a failure on the way leaves ctx STAGED with its old entries and dims
+    if (c->state == cellector_ctx::ST_READY) {
+        unbuild_matrix(c);
+        lap("drop built matrix");
+    }
+    CHK(combine_cells(c, n_ctx, n_pairs, c->cell_origin, dbl_origin, c->cell_source, (uint8_t)(c->n_combines + 1), &origin, &source));
+    CooView a = c->coo.view(), b = dbl.view();
+    bool asc_a = true, asc_b = true;
+    CHK(combine_ascending(c, a, b, &asc_a, &asc_b));
+    if (!asc_b) return ctx_fail(c, CELLECTOR_EDEVICE, "add_doublets: the doublet side does not ascend by (locus, cell)");
+    if (!asc_a) { CHK(combine_sort(c, a, &own_sorted)); a = own_sorted.view(); }
+    lap("order check / sort");
+    CHK(combine_merge(c, a, b, &merged));
+    lap("merge");
+    // ---- nothing below fails for memory
+    c->coo = std::move(merged);
+    c->cell_origin = std::move(origin);
+    c->cell_source = std::move(source);
+    c->n_combines++;
+    c->total_cells = n_ctx + n_pairs; c->cell_begin = 0; c->cell_end = c->total_cells; c->nloc = c->total_cells;
+    c->state = cellector_ctx::ST_STAGED;
+    CHK(ingest_pass1(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lap("release + PASS1");
+    return CELLECTOR_OK;
+}
+
 cellector_status cellector_cell_source(const cellector_ctx *c, uint8_t *out)
 {
     if (!c || !out) return CELLECTOR_EINVAL;

@@ -540,6 +540,15 @@ cellector_status combine_cells(cellector_ctx *c, uint64_t n_ctx, uint64_t n_kept
 // ... a restage's source [n_keep]: old_source [tc] at the kept cells (rank as restage_cell_ranks made it)
 cellector_status combine_source_select(cellector_ctx *c, uint64_t tc, uint64_t n_keep, const uint32_t *rank, const uint8_t *old_source,
                                        DevBuf<uint8_t> *source);
+// cellector_add_doublets (kernels_doublets.hip).  The doublet side: for every value 2 j + s of host_fan_val [n_fan] in the range
+// host_fan_ptr [tc + 1] gives cell c, every staged entry of c summed into (locus, tc + j), thinned per (entry, pair, side);
+// strictly ascending by (locus, cell).  *overflow: a sum exceeds CELLECTOR_MAX_COUNT; the first one in output order is named
+cellector_status doublets_build(cellector_ctx *c, const CooView &in, uint64_t tc, uint64_t total_loci, const uint64_t *host_fan_ptr,
+                                const uint64_t *host_fan_val, uint64_t n_fan, uint64_t T, uint64_t seed, StagedCoo *out,
+                                bool *overflow, uint64_t *over_pair, uint32_t *over_locus, int *over_allele);
+// ... origin [n_pairs] of the new cells: old_origin (device, null: identity) at host_cell_a
+cellector_status doublets_origin(cellector_ctx *c, const uint32_t *host_cell_a, uint64_t n_pairs, uint64_t tc, const uint32_t *old_origin,
+                                 DevBuf<uint32_t> *origin);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);

@@ -49,6 +49,7 @@ SIGNATURES = {
     "cellector_staged_coo": (_i, [_vp, C.POINTER(_u64), _vp, _vp, _vp, _vp, _u64]),
     "cellector_combine": (_i, [_vp, _vp, _vp, _vp, _u64, _d, _u64]),
     "cellector_cell_source": (_i, [_vp, _vp]),
+    "cellector_add_doublets": (_i, [_vp, _vp, _vp, _u64, _d, _u64]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -340,6 +341,27 @@ class Cellector:
         out = np.zeros(self.dims().total_cells, np.uint8)
         self._ck(self._lib.cellector_cell_source(self.h, _p(out)))
         return out
+
+    # ---- synthetic doublets from resident cells
+    def add_doublets(self, cell_a, cell_b, downsample_rate=0.0, seed=4):
+        """One new cell per pair behind the ctx's cells (cellector_add_doublets): at every locus either parent covers it holds the
+        sum of the counts of cell_a[j] and cell_b[j], every parent read removed on its way with probability downsample_rate,
+        independently per (pair, side); the parents stay as they are and everything then ascends by (locus, cell, ref, alt)
+        (doublets.add_doublets_coo is the bit-identical numpy twin).  The call counts as a combine: the new cells' cell_source()
+        is the next number, their cell_origin() that of cell_a[j].  The ctx is then STAGED: call ingest_finish(min_alt, min_ref)
+        next.  c.add_doublets(a, b, 0.5); c.ingest_finish(); c.run(); ...; c.restage(keep=c.cell_source() != k) takes them out."""
+        pair = []
+        for name, v in (("cell_a", cell_a), ("cell_b", cell_b)):
+            v = np.asarray(v)
+            if v.ndim != 1 or (v.size and v.dtype.kind not in "iu"):
+                raise ValueError(f"add_doublets: {name} is not a list of cell indices")
+            v = v.astype(np.int64) if v.dtype != np.uint64 else v
+            if v.size and (int(v.min()) < 0 or int(v.max()) > 0xFFFFFFFF):
+                raise ValueError(f"add_doublets: {name} holds an index outside 32 bits")
+            pair.append(np.ascontiguousarray(v, dtype=np.uint32))
+        if pair[0].shape != pair[1].shape:
+            raise ValueError(f"add_doublets: {pair[0].size} cells a, {pair[1].size} cells b")
+        self._ck(self._lib.cellector_add_doublets(self.h, _p(pair[0]), _p(pair[1]), pair[0].size, float(downsample_rate), int(seed)))
 
     def exchange_buffer(self, which):
         ptr, n = C.c_void_p(), C.c_uint64()

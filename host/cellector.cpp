@@ -185,6 +185,10 @@ struct Params {
     // --mix_cells, its barcode mask) with the identity locus map: both datasets come from the same variant VCF
     std::optional<std::string> mix_alt, mix_ref, mix_barcodes, mix_cells;
     bool mix() const { return mix_alt.has_value(); }
+    // extension: synthetic doublets of the run's own cells, made on the GPU after everything else (cellector_add_doublets; what
+    // combiner/src/main.rs:43 announces), thinned with their own rate and the shared --seed
+    std::optional<std::string> doublets;
+    double doublet_downsample_rate = 0.0;
 };
 
 const char *USAGE =
@@ -258,7 +262,20 @@ const char *USAGE =
     "                                                                       act on the first dataset, --mix_cells and the same rate and seed on\n"
     "                                                                       the second (not in the reference; one GPU)\n"
     "        --mix_cells <file>                                             take only the listed cells of the second dataset (its own barcodes,\n"
-    "                                                                       one per line, first tab-separated column, blank lines ignored)\n";
+    "                                                                       one per line, first tab-separated column, blank lines ignored)\n"
+    "        --doublets <file>                                              add one synthetic doublet per line of the file on the GPU, after\n"
+    "                                                                       --cells, --downsample_rate and --mix_*: two barcodes per line,\n"
+    "                                                                       tab-separated, blank lines ignored, named as the run's cells are\n"
+    "                                                                       after those flags (as in the run's barcodes.tsv).  The new cell\n"
+    "                                                                       <A>+<B> holds the sum of the two cells' counts at every locus either\n"
+    "                                                                       covers and follows all other cells; a pair may be listed once.\n"
+    "                                                                       barcodes.tsv and gt.tsv are written to the output directory: the\n"
+    "                                                                       cells there before keep their label (-g's, else the mixture's, else\n"
+    "                                                                       singlet), the new cells get doublet unless -g names them; that\n"
+    "                                                                       gt.tsv is the run's ground truth (not in the reference; one GPU)\n"
+    "        --doublet_downsample_rate <r>                                  remove every read of a parent with probability r in [0, 1] on its\n"
+    "                                                                       way into a doublet, independently per pair and parent (default 0;\n"
+    "                                                                       --seed is shared)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -285,7 +302,7 @@ Params load_params(int argc, char **argv)
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
-                                  "mix_cells"};
+                                  "mix_cells", "doublets", "doublet_downsample_rate"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -377,7 +394,15 @@ Params load_params(int argc, char **argv)
             if (!got.count(flag))
                 die(1, std::string("error: The arguments '--mix_alt', '--mix_ref' and '--mix_barcodes' are given together: '--") + flag +
                            " <file>' was not provided");
-    for (const char *flag : {"cells", "downsample_rate", "mix_alt"})
+    if (got.count("doublets")) p.doublets = got["doublets"];
+    if (got.count("doublet_downsample_rate")) {
+        const double r = parse_f64("doublet_downsample_rate", got["doublet_downsample_rate"]);
+        if (!(r >= 0.0 && r <= 1.0))
+            die(1, "error: Invalid value '" + got["doublet_downsample_rate"] + "' for '--doublet_downsample_rate <r>': expected a number in [0, 1]");
+        p.doublet_downsample_rate = r;
+        if (!p.doublets) die(1, "error: The argument '--doublet_downsample_rate <r>' requires '--doublets <file>'");
+    }
+    for (const char *flag : {"cells", "downsample_rate", "mix_alt", "doublets"})
         if (got.count(flag) && (p.devices_auto || p.devices.size() > 1))
             die(1, std::string("error: The argument '--") + flag + "' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.resolve_assignments && (p.devices_auto || p.devices.size() > 1))
@@ -557,6 +582,42 @@ int main(int argc, char **argv)
         for (const std::string &bc : mix_names) barcodes.push_back(bc);  // (mix_names is complete: the views stay valid)
         index_barcodes();
     }
+    // --doublets: the pairs, by the names the cells carry now; the new cells <A>+<B> follow all others, and from here on the
+    // barcodes file IS that list.  The matrix follows after the load (cellector_add_doublets)
+    const size_t n_before_doublets = barcodes.size();
+    std::vector<uint32_t> dbl_a, dbl_b;
+    std::vector<std::string> dbl_names;
+    if (params.doublets) {
+        Lines in(*params.doublets);
+        std::string line;
+        std::map<std::string, size_t> seen;  // name -> line
+        for (size_t line_no = 1; in.next(line); line_no++) {
+            if (line.empty()) continue;
+            const std::string where = "error: --doublets " + *params.doublets + " line " + std::to_string(line_no) + ": ";
+            auto cols = split(line, '\t');
+            if (cols.size() != 2 || cols[0].empty() || cols[1].empty())
+                die(1, where + "two tab-separated barcodes expected, got '" + line + "'");
+            size_t cell[2];
+            for (int k = 0; k < 2; k++) {
+                cell[k] = barcode_to_cell(cols[k]);
+                if (cell[k] == SIZE_MAX)
+                    die(1, where + "barcode '" + cols[k] + "' is not among the run's cells (the barcodes file " + params.barcodes +
+                               (params.cells ? " after --cells" : "") + (params.mix() ? ", then --mix_barcodes" : "") + ")");
+            }
+            if (cell[0] == cell[1]) die(1, where + "barcode '" + cols[0] + "' is paired with itself");
+            std::string name = cols[0] + "+" + cols[1];
+            const auto [at, fresh] = seen.emplace(name, line_no);
+            if (!fresh)
+                die(1, where + "the pair is line " + std::to_string(at->second) + " already: the cell '" + name + "' would exist twice");
+            if (barcode_to_cell(name) != SIZE_MAX) die(1, where + "the run has a cell named '" + name + "' already");
+            dbl_a.push_back((uint32_t)cell[0]);
+            dbl_b.push_back((uint32_t)cell[1]);
+            dbl_names.push_back(std::move(name));
+        }
+        if (dbl_names.empty()) die(1, "error: --doublets " + *params.doublets + " lists no pair");
+        for (const std::string &bc : dbl_names) barcodes.push_back(bc);  // (dbl_names is complete: the views stay valid)
+        index_barcodes();
+    }
     auto dropped_by_cells = [&](std::string_view key) {  // a barcode of the whole file that --cells left out
         if (all_slot.empty()) return false;
         const size_t cap = all_slot.size();
@@ -577,16 +638,19 @@ int main(int argc, char **argv)
             if (cell != SIZE_MAX && cell < ground_truth.size()) ground_truth[cell] = cols[1];
         }
     }
-    if (params.mix()) {  // the combiner's barcodes.tsv and gt.tsv of the mixture (main.rs:155-186); without -g the run's ground truth
+    // the combiner's barcodes.tsv and gt.tsv of the mixture (main.rs:155-186); without -g the run's ground truth.  With --doublets
+    // the cells there before keep the label in force (-g's, else the mixture's, else singlet) and the new ones are doublet
+    if (params.mix() || params.doublets) {
         std::string bc_out, gt_out;
         for (size_t i = 0; i < barcodes.size(); i++) {
-            const char *label = i < n_first ? "majority" : "minority";
+            std::string label = i >= n_before_doublets ? "doublet" : params.mix() ? (i < n_first ? "majority" : "minority") : "singlet";
+            const size_t cell = barcode_to_cell(barcodes[i]);
+            if (params.doublets && params.ground_truth && cell < ground_truth.size()) {  // -g's label; a new cell it does not name stays doublet
+                if (i < n_before_doublets || ground_truth[cell] != "na") label = ground_truth[cell];
+            }
             bc_out += barcodes[i]; bc_out += '\n';
             gt_out += barcodes[i]; gt_out += '\t'; gt_out += label; gt_out += '\n';
-            if (!params.ground_truth) {
-                const size_t cell = barcode_to_cell(barcodes[i]);
-                if (cell < ground_truth.size()) ground_truth[cell] = label;
-            }
+            if ((!params.ground_truth || i >= n_before_doublets) && cell < ground_truth.size()) ground_truth[cell] = label;
         }
         // an input of this run under one of the two names in the output directory would be lost: refuse before either is written
         for (const char *name : {"barcodes.tsv", "gt.tsv"}) {
@@ -595,10 +659,11 @@ int main(int argc, char **argv)
             if (stat(path.c_str(), &mine) != 0) continue;
             for (const auto &[flag, in] : std::vector<std::pair<const char *, std::optional<std::string>>>{
                      {"--barcodes", params.barcodes}, {"--ground_truth", params.ground_truth}, {"--mix_barcodes", params.mix_barcodes},
-                     {"--mix_cells", params.mix_cells}, {"--cells", params.cells}, {"--initial_minority", params.initial_minority},
+                     {"--mix_cells", params.mix_cells}, {"--cells", params.cells}, {"--doublets", params.doublets},
+                     {"--initial_minority", params.initial_minority},
                      {"--cell_detail", params.cell_detail}})
                 if (in && stat(in->c_str(), &theirs) == 0 && mine.st_dev == theirs.st_dev && mine.st_ino == theirs.st_ino)
-                    die(1, std::string("error: the mixture's ") + name + " would overwrite the " + flag + " file " + *in +
+                    die(1, std::string(params.mix() ? "error: the mixture's " : "error: the run's ") + name + " would overwrite the " + flag + " file " + *in +
                                ": choose another --output_directory");
         }
         auto write_text = [&](const char *name, const std::string &text) {
@@ -688,7 +753,7 @@ int main(int argc, char **argv)
     if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
     if (params.locus_expected) g.ck(cellector_set_option(g.c, "locus_moments", 1), "locus_expected");
     lap("barcodes + device init");
-    if (!params.restage() && !params.mix()) {
+    if (!params.restage() && !params.mix() && !params.doublets) {
         g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     } else {  // --cells / --downsample_rate: the staged matrix is cut and thinned on the device before the locus filter sees it
         g.ck(cellector_ingest_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str()), "load_cell_data");
@@ -737,6 +802,23 @@ int main(int argc, char **argv)
             g.ck(cellector_combine(g.c, second.c, params.mix_cells ? take.data() : nullptr, nullptr, ours.total_loci,
                                    params.downsample_rate.value_or(0.0), params.seed), "combine");
             cellector_destroy(second.c);
+        }
+        if (params.doublets) {  // last: the pairs name the cells as they are now
+            cellector_dims_t now;
+            g.ck(cellector_dims(g.c, &now), "dims");
+            for (size_t j = 0; j < dbl_a.size(); j++)
+                for (const uint32_t cell : {dbl_a[j], dbl_b[j]})
+                    if (cell >= now.total_cells)
+                        die(1, "error: --doublets: barcode '" + std::string(barcodes[cell]) + "' is line " + std::to_string(cell + 1) +
+                                   " of the run's barcodes but the matrix has " + std::to_string(now.total_cells) + " cells");
+            if (n_before_doublets != now.total_cells)  // (the new cells' lines must follow the matrix' last cell)
+                die(EXIT_PANIC, "the run's barcodes are " + std::to_string(n_before_doublets) + " lines but the matrix has " +
+                                    std::to_string(now.total_cells) + " cells");
+            const cellector_status st = cellector_add_doublets(g.c, dbl_a.data(), dbl_b.data(), dbl_a.size(), params.doublet_downsample_rate,
+                                                               params.seed);
+            if (st == CELLECTOR_EINVAL)  // (a summed count above 65535: the library names pair, locus and allele)
+                die(1, "error: --doublets " + *params.doublets + ": " + cellector_last_error(g.c));
+            g.ck(st, "add_doublets");
         }
         g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
     }

@@ -303,8 +303,58 @@ cellector_status cellector_combine(cellector_ctx *ctx, const cellector_ctx *src,
                                    const uint8_t *src_keep /*[src total_cells] or NULL = all*/,
                                    const uint32_t *locus_map /*[src total_loci] or NULL = identity*/,
                                    uint64_t total_loci_out, double downsample_rate, uint64_t seed);
-/* per current cell: 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine since */
+/* per current cell: 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine (or
+ * cellector_add_doublets, which counts as one) since */
 cellector_status cellector_cell_source(const cellector_ctx *ctx, uint8_t *out /*[total_cells]*/);
+
+/* ---- synthetic doublets from resident cells: what the combiner announces and never does -------------------
+ * combiner/src/main.rs:43 reads "decide which cells are doublets and that mapping", and nothing follows it.  A synthetic
+ * doublet is two droplets' reads in one barcode: cellector_add_doublets appends, for j = 0..n_pairs-1, a cell n_ctx + j
+ * (n_ctx = total_cells before the call) that holds at every locus the SUM of the counts of cell_a[j] and cell_b[j], so that
+ * the doublet posterior (calculate_posteriors, main.rs:239-276) can be exercised on a real matrix at a chosen depth.
+ *   Entries: for every locus at which cell_a[j] or cell_b[j] has at least one staged entry the new cell gets exactly ONE
+ *   entry; its alt is the sum of the (thinned) alt of ALL entries of both parents at that locus — repeated (locus, cell) lines
+ *   of a parent all count — its ref likewise.  An entry whose two sums are 0 STAYS, as in restage and combine.  A locus
+ *   neither parent has gives no entry; a parent with an empty row adds nothing; two empty parents give an empty row.  The
+ *   parents' own entries are never changed.  The same pair listed twice is legal: two cells with independent draws.
+ *   downsample_rate: the probability that a parent's read is REMOVED on its way into the doublet, in [0, 1].  For the parent
+ *   entry at position i of ctx's staged arrays as the call reads them, pair j, side s (0 = cell_a, 1 = cell_b), allele a
+ *   (0 = ref, 1 = alt) and read r = 0..count-1:
+ *     h = mix64(mix64((seed * GOLD) ^ ((i + 1) * GOLD)) ^ ((2 j + s + 1) * GOLD)),  x = mix64(h + (2 r + a + 1) * GOLD),
+ *   the read is removed iff (x >> 11) < (uint64_t)(downsample_rate * 2^53); mix64 and GOLD are cellector_restage's, in
+ *   uint64 wrap-around arithmetic.  The draw is independent per (pair, side), also where one cell is a parent in many pairs.
+ *   All-integer: cellector_amd/doublets.py is the bit-identical numpy twin.  Rate 0 draws nothing, rate 1 leaves every
+ *   doublet count 0.
+ *   Staged order is file order.  For an input that was not locus-major it is, after a finished ingest, the stable sort by locus
+ *   the ingest made: a call before and after cellector_ingest_finish then draws differently — for such an input and only
+ *   for such an input (the caveat of cellector_restage, verbatim).
+ *   Staged order afterwards: ALL entries ascending by (locus, cell, ref, alt), exactly as after cellector_combine: ctx's side is
+ *   taken as it stands if its (locus, cell) pairs ascend strictly and sorted by the tuple otherwise, the doublet side ascends
+ *   strictly by construction, the cell ranges are disjoint and the two are merged by (locus, cell).  The result is unique: it
+ *   depends neither on the grid nor on the order of equal keys in the intermediate sort (integer sums commute).
+ *   total_cells becomes n_ctx + n_pairs, total_loci is unchanged.  cellector_cell_origin of a new cell is that of cell_a[j].
+ *   The call counts as a combine in the numbering of cellector_cell_source: new cells get n_combines + 1, ctx's cells keep
+ *   theirs; cellector_restage composes both as it does today.  The caller keeps the pair list.
+ * Afterwards, as after restage and combine: state STAGED, PASS1 formed again from all entries, everything the built matrix owned
+ * dropped as a reload drops it, options keep their values; cellector_ingest_finish follows.
+ *   The ctx: single-device, without a communicator or a cellector_set_shard range, holding a staged COO (state STAGED, or a
+ *   loaded matrix that kept it: option keep_coo 1), not between cellector_em_begin and cellector_em_finish.
+ *   CELLECTOR_EINVAL with a message, the ctx untouched (still READY with its built matrix if it had one): any of those
+ *   conditions, n_pairs == 0, a NULL list, an index >= n_ctx (the message names the first such pair), cell_a[j] == cell_b[j]
+ *   (the message names the pair), a rate outside [0, 1] or NaN, n_ctx + n_pairs > 2^32 - 1, more than 255 combines since the
+ *   last ingest from outside, a summed count above 65535 (the message names pair, locus and allele of the first such entry in
+ *   output order; ref before alt inside one entry).
+ *   Memory: the doublet side is built FIRST, beside a built matrix that stays, so that the last refusal leaves the ctx as it
+ *   was: 16 B per cell of ctx and per pair for the fan table, 8 B per 2048 ctx entries, then per emitted record (one per parent
+ *   entry and pair it is in) 24 B and the radix sort's scratch while the records are sorted, 20 B while they are summed, plus
+ *   20 B per doublet entry; 12 B per doublet entry remain.  Then the built matrix is dropped and the merged COO (12 B per entry
+ *   of the result) is allocated beside ctx's entries and the doublet side: the peak there is 24 B per ctx entry and per doublet
+ *   entry, plus 5 B per cell of the result and 8 B per 2048 entries of the result; a ctx side that has to be sorted adds 32 B per
+ *   entry (and the radix sort's scratch) while it is sorted, 12 B after.  On CELLECTOR_ENOMEM before the drop the ctx is
+ *   untouched; after it the ctx is left STAGED holding its OLD entries, dims, origin and source, ready for
+ *   cellector_ingest_finish. */
+cellector_status cellector_add_doublets(cellector_ctx *ctx, const uint32_t *cell_a /*[n_pairs]*/, const uint32_t *cell_b /*[n_pairs]*/,
+                                        uint64_t n_pairs, double downsample_rate, uint64_t seed);
 
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
