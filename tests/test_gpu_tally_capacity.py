@@ -29,8 +29,9 @@ def mods(oracle_lib, hip_lib_path):
     return dict(Cellector=Cellector, ffi=ffi, hip=hip)
 
 
-def _place(mods, g, chosen, n_cells):
-    """one EM iteration whose exclusion set is `chosen` (a boolean array); returns the summary"""
+def _place(mods, g, chosen, n_cells, quiet_filter=True):
+    """one EM iteration whose exclusion set is `chosen` (a boolean array); returns the summary.  quiet_filter False: the caller's
+    matrix has loci the -80 filter takes (tests/test_gpu_locus_sweep.py) and it checks the filter's outcome itself."""
     assert 0 < chosen.sum() < n_cells / 4
     g.em_begin()
     ptr, m = g.exchange_buffer(mods["ffi"].XCHG_NORM)
@@ -42,7 +43,8 @@ def _place(mods, g, chosen, n_cells):
     assert (s.iqr, s.threshold) == (0.0, -1.0)
     assert s.n_excluded == int(chosen.sum())
     assert np.array_equal(g.excluded(), chosen.astype(np.uint8))
-    assert s.n_loci_filtered == 0 and g.loci_mask().all()  # (single reads: no locus comes near the -80 filter)
+    if quiet_filter:
+        assert s.n_loci_filtered == 0 and g.loci_mask().all()  # (single reads: no locus comes near the -80 filter)
     return s
 
 
