@@ -103,13 +103,11 @@ void timer_collect(cellector_ctx *c)
     }
 }
 
-// A reload (and cellector_destroy) drops the matrix, engine 2's layouts and what the calls left for each other as a whole:
-// every device buffer of the three groups goes back, every other field of them returns to its default.
+// A reload (and cellector_destroy) drops what was built and what was staged, each group as a whole (ctx.h).
 static void drop_matrix(cellector_ctx *c)
 {
-    static_cast<CtxCarry &>(*c) = CtxCarry();
-    static_cast<CtxTiled &>(*c) = CtxTiled();
-    static_cast<CtxMatrix &>(*c) = CtxMatrix();
+    drop_built(c);
+    static_cast<CtxStaged &>(*c) = CtxStaged();
 }
 
 // the side stream gets the lowest priority the device offers: its kernels should only fill slots the main stream's
@@ -120,12 +118,6 @@ static bool create_side_stream(hipStream_t *out)
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
     return hipStreamCreateWithPriority(out, hipStreamNonBlocking, least) == hipSuccess;
 }
-
-#define REQUIRE(c, cond, msg)                                        \
-    do {                                                             \
-        if (!(cond)) return ctx_fail((c), CELLECTOR_EINVAL, "%s", msg); \
-    } while (0)
-#define SETDEV(c) HIPCHK((c), hipSetDevice((c)->device))
 
 // ---- caching layer under dev_alloc / DevBuf (see ctx.h) ---------------------------------------------------------
 namespace {
@@ -329,7 +321,7 @@ void cellector_destroy(cellector_ctx *c)
     drop_matrix(c);
     c->lf.reset(); c->d_counters.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
     c->sel_list.reset(); c->seld_hist.reset(); c->seld_state.reset();
-    c->res_cnt.reset(); c->res_dev.reset(); c->cell_origin.reset(); c->cell_source.reset();
+    c->res_cnt.reset(); c->res_dev.reset();
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
@@ -594,16 +586,9 @@ cellector_status cellector_set_shard(cellector_ctx *c, uint64_t b, uint64_t e)
 static cellector_status begin_ingest(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells)
 {
     SETDEV(c);
-    {
-        // keep a caller-bound PASS1 buffer across the reset
-        double *bound = c->x_pass1 != c->x_pass1_own.get() ? c->x_pass1 : nullptr;
-        const uint64_t nb = c->pass1_bound_cap;  // (its whole capacity: n_pass1 is what the last matrix used of it)
-        drop_matrix(c);
-        if (bound) { c->x_pass1 = bound; c->n_pass1 = nb; }
-    }
-    c->cell_origin.reset();  // an ingest from outside: cellector_cell_origin is the identity again
-    c->cell_source.reset();  // ... cellector_cell_source all 0, no combine counted
-    c->n_combines = 0;
+    drop_matrix(c);  // (an ingest from outside: cellector_cell_origin is the identity again, cellector_cell_source all 0)
+    // a caller-bound PASS1 buffer serves every matrix, with its whole capacity (n_pass1 is what the last one used of it)
+    if (c->pass1_bound) { c->x_pass1 = c->pass1_bound; c->n_pass1 = c->pass1_bound_cap; }
     REQUIRE(c, total_loci <= 0xffffffffull && total_cells <= 0xffffffffull, "dims exceed 32-bit indices");
     c->total_loci = total_loci;
     c->total_cells = total_cells;
@@ -694,6 +679,23 @@ cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_
     return CELLECTOR_OK;
 }
 
+// The EM state a load leaves, queued on the stream: all loci used, no cell excluded, the outputs zero (cellector_ingest_finish,
+// cellector_em_reset)
+static cellector_status em_state_clear(cellector_ctx *c)
+{
+    const uint64_t L = c->L, n = c->nloc;
+    HIPCHK(c, hipMemsetAsync(c->mask, 1, L ? L : 1, c->stream));  // load_data.rs:176-179: all loci used
+    HIPCHK(c, hipMemsetAsync(c->mask_next, 1, L ? L : 1, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->flags, 0, n ? n : 1, c->stream));   // main.rs:37: the empty set
+    HIPCHK(c, hipMemsetAsync(c->flags_new, 0, n ? n : 1, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ll, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ell, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->nloci, 0, (n ? n : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (c->n_norm ? c->n_norm : 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->x_locus, 0, ((uint64_t)LB_PLANES * L + LC_COUNTERS) * 8, c->stream));
+    return CELLECTOR_OK;
+}
+
 extern "C" {
 
 cellector_status cellector_ingest_synthetic(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells,
@@ -739,13 +741,6 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
     CHK(dev_alloc(c, &c->flags, n)); CHK(dev_alloc(c, &c->flags_new, n));
     CHK(dev_alloc(c, &c->ll, n)); CHK(dev_alloc(c, &c->ell, n)); CHK(dev_alloc(c, &c->nloci, n));
     CHK(dev_alloc(c, &c->post, 4 * n));
-    HIPCHK(c, hipMemsetAsync(c->mask, 1, L ? L : 1, c->stream));  // load_data.rs:176-179: all loci used
-    HIPCHK(c, hipMemsetAsync(c->mask_next, 1, L ? L : 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flags, 0, n ? n : 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flags_new, 0, n ? n : 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ll, 0, (n ? n : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ell, 0, (n ? n : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->nloci, 0, (n ? n : 1) * 8, c->stream));
     // (with a communicator every rank owns an equal slot of NORM: the in-place all-gather's layout)
     const uint64_t need_norm = comm_active(c->comm) ? comm_cells_per_rank(c->total_cells, c->comm.n) * (uint64_t)c->comm.n : c->total_cells;
     const uint64_t need_locus = (uint64_t)LB_PLANES * L + LC_COUNTERS;
@@ -755,8 +750,7 @@ cellector_status cellector_ingest_finish(cellector_ctx *c, uint64_t min_alt, uin
     else { CHK(dev_alloc(c, &c->x_locus_own, need_locus)); c->x_locus = c->x_locus_own; }
     c->n_norm = need_norm;
     c->n_locus = need_locus;
-    HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (need_norm ? need_norm : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_locus, 0, need_locus * 8, c->stream));
+    CHK(em_state_clear(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     {
         // The near-tie band of cellector_iter_summary.n_near_threshold follows the matrix' depth: the reference's ln_gamma
@@ -810,14 +804,6 @@ cellector_status cellector_dims(const cellector_ctx *c, cellector_dims_t *o)
     return CELLECTOR_OK;
 }
 
-static cellector_status d2h(const cellector_ctx *c, void *dst, const void *src, size_t bytes)
-{
-    if (!bytes) return CELLECTOR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CELLECTOR_OK;
-}
 #define READY(c) REQUIRE(c, (c) && (c)->state == cellector_ctx::ST_READY, "no matrix loaded")
 // per-locus state is replicated on every shard: shard 0 of a multi-device ctx answers
 #define SHARD0(c, call)                                                      \
@@ -878,332 +864,6 @@ cellector_status cellector_csr_rows(const cellector_ctx *c, uint64_t rb, uint64_
     return CELLECTOR_OK;
 }
 
-// ---- re-staging the resident matrix -------------------------------------------------------------------
-// cellector_restage works where one device holds every cell (the conditions of locus_moments_scope, without its entry limit)
-static cellector_status restage_scope(const cellector_ctx *c)
-{
-    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a single-device ctx: the staged entries of a multi-device ctx are sharded");
-    if (comm_active(c->comm)) return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a ctx without a communicator: every rank stages its own cells");
-    if (c->state == cellector_ctx::ST_EMPTY) return ctx_fail(c, CELLECTOR_EINVAL, "restage without a staged matrix");
-    if (c->nloc != c->total_cells)
-        return ctx_fail(c, CELLECTOR_EINVAL, "restage works on a ctx that holds all cells, not on a cellector_set_shard range");
-    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "restage between cellector_em_begin and cellector_em_finish");
-    if (c->state == cellector_ctx::ST_READY && !c->coo.locus)
-        return ctx_fail(c, CELLECTOR_EINVAL, "restage of a loaded matrix needs its staged COO (option keep_coo=1 before the ingest)");
-    return CELLECTOR_OK;
-}
-
-// READY -> STAGED on the entries the ctx still holds: everything the built matrix owned goes as in a reload (drop_matrix); the
-// staged COO, the dims and PASS1 (ingest_build only read it) stay
-static void unbuild_matrix(cellector_ctx *c)
-{
-    StagedCoo coo = std::move(c->coo);
-    DevBuf<double> own = std::move(c->x_pass1_own);
-    double *const p1 = c->x_pass1;
-    const uint64_t tl = c->total_loci, tc = c->total_cells, cb = c->cell_begin, ce = c->cell_end, nloc = c->nloc, np1 = c->n_pass1;
-    drop_matrix(c);
-    c->coo = std::move(coo);
-    c->x_pass1_own = std::move(own);
-    c->x_pass1 = p1; c->n_pass1 = np1;
-    c->total_loci = tl; c->total_cells = tc; c->cell_begin = cb; c->cell_end = ce; c->nloc = nloc;
-    c->state = cellector_ctx::ST_STAGED;
-}
-
-cellector_status cellector_restage(cellector_ctx *c, const uint8_t *keep, double downsample_rate, uint64_t seed)
-{
-    if (!c) return CELLECTOR_EINVAL;
-    CHK(restage_scope(c));
-    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
-        return ctx_fail(c, CELLECTOR_EINVAL, "restage: downsample_rate %g is not in [0, 1]", downsample_rate);
-    const uint64_t tc = c->total_cells;
-    uint64_t n_keep = tc;
-    if (keep) {
-        n_keep = 0;
-        for (uint64_t i = 0; i < tc; i++) n_keep += keep[i] != 0;
-        if (n_keep == 0) return ctx_fail(c, CELLECTOR_EINVAL, "restage: the selection keeps none of the %llu cells", (unsigned long long)tc);
-        if (n_keep == tc) keep = nullptr;  // every cell stays: nothing to renumber
-    }
-    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
-    SETDEV(c);
-    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
-    LapTimer t;
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing]   restage: %-22s %8.4f s\n", what, t.lap());
-    };
-    // ---- validated: from here the ctx changes.  The built matrix goes first, then the new COO is made beside the old one
-    if (c->state == cellector_ctx::ST_READY) {
-        unbuild_matrix(c);  // (its blocks stay in the cache: the new COO and the finish that follows take them from there)
-        lap("drop built matrix");
-    }
-    if (keep) {
-        DevBuf<uint8_t> keep01;
-        DevBuf<uint32_t> rank, origin;
-        DevBuf<uint8_t> source;
-        StagedCoo neu;
-        CHK(restage_cell_ranks(c, keep, tc, n_keep, c->cell_origin, &keep01, &rank, &origin));
-        if (c->cell_source) CHK(combine_source_select(c, tc, n_keep, rank, c->cell_source, &source));
-        lap("cell ranks");
-        CHK(restage_select(c, c->coo.view(), tc, keep01, rank, T, seed, &neu));  // (a failure up to here leaves the old entries staged)
-        lap("count + scan + write");
-        neu.sorted = c->coo.sorted;  // (a subsequence of a locus-major order is locus-major)
-        c->coo = std::move(neu);
-        c->cell_origin = std::move(origin);
-        if (c->cell_source) c->cell_source = std::move(source);
-        c->total_cells = n_keep; c->cell_begin = 0; c->cell_end = n_keep; c->nloc = n_keep;
-    } else {
-        CHK(restage_thin(c, &c->coo, T, seed));
-        lap("thin");
-    }
-    CHK(ingest_pass1(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    lap("release + PASS1");
-    return CELLECTOR_OK;
-}
-
-cellector_status cellector_cell_origin(const cellector_ctx *c, uint32_t *out)
-{
-    if (!c || !out) return CELLECTOR_EINVAL;
-    cellector_dims_t d;
-    CHK(cellector_dims(c, &d));
-    if (!c->multi && c->cell_origin) return d2h(c, out, c->cell_origin, d.total_cells * 4);
-    for (uint64_t i = 0; i < d.total_cells; i++) out[i] = (uint32_t)i;
-    return CELLECTOR_OK;
-}
-
-cellector_status cellector_staged_coo(const cellector_ctx *c, uint64_t *n, uint32_t *locus0, uint32_t *cell0, uint32_t *alt, uint32_t *ref,
-                                      uint64_t capacity)
-{
-    if (!c || !n) return CELLECTOR_EINVAL;
-    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "staged_coo works on a single-device ctx (the staged entries of a multi-device ctx are sharded)");
-    REQUIRE(c, c->state != cellector_ctx::ST_EMPTY && c->coo.locus, "staged_coo without a staged matrix (option keep_coo=1)");
-    *n = c->coo.n;
-    if (!locus0 && !cell0 && !alt && !ref) return CELLECTOR_OK;
-    REQUIRE(c, capacity >= c->coo.n, "staged_coo: capacity too small");
-    const uint64_t m = c->coo.n;
-    if (locus0) CHK(d2h(c, locus0, c->coo.locus, m * 4));
-    if (cell0) CHK(d2h(c, cell0, c->coo.cell, m * 4));
-    std::vector<uint16_t> h(m);
-    for (int k = 0; k < 2; k++) {
-        uint32_t *dst = k ? ref : alt;
-        if (!dst) continue;
-        CHK(d2h(c, h.data(), k ? c->coo.ref.get() : c->coo.alt.get(), m * 2));
-        for (uint64_t i = 0; i < m; i++) dst[i] = h[i];
-    }
-    return CELLECTOR_OK;
-}
-
-// ---- merging a second staged matrix in ---------------------------------------------------------------------
-// why a ctx cannot take part in cellector_combine (the conditions of restage_scope), or null
-static const char *combine_scope(const cellector_ctx *c)
-{
-    if (c->multi) return "is a multi-device ctx: its staged entries are sharded";
-    if (comm_active(c->comm)) return "has a communicator: every rank stages its own cells";
-    if (c->state == cellector_ctx::ST_EMPTY) return "has no staged matrix";
-    if (c->nloc != c->total_cells) return "holds a cellector_set_shard range, not all cells";
-    if (c->em_phase != 0) return "is between cellector_em_begin and cellector_em_finish";
-    if (!c->coo.locus) return "is a loaded matrix without its staged COO (option keep_coo=1 before the ingest)";
-    return nullptr;
-}
-
-cellector_status cellector_combine(cellector_ctx *c, const cellector_ctx *src, const uint8_t *src_keep, const uint32_t *locus_map,
-                                   uint64_t total_loci_out, double downsample_rate, uint64_t seed)
-{
-    if (!c) return CELLECTOR_EINVAL;
-    if (!src) return ctx_fail(c, CELLECTOR_EINVAL, "combine: src is NULL");
-    if (c == src) return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx and src are the same ctx");
-    if (const char *why = combine_scope(c)) return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx %s", why);
-    if (const char *why = combine_scope(src)) return ctx_fail(c, CELLECTOR_EINVAL, "combine: src %s", why);
-    if (c->device != src->device)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: ctx is on device %d, src on device %d", c->device, src->device);
-    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: downsample_rate %g is not in [0, 1]", downsample_rate);
-    const uint64_t n_ctx = c->total_cells, tc_src = src->total_cells, tl_src = src->total_loci;
-    uint64_t n_kept = tc_src;
-    if (src_keep) {
-        n_kept = 0;
-        for (uint64_t i = 0; i < tc_src; i++) n_kept += src_keep[i] != 0;
-    }
-    if (n_kept == 0) return ctx_fail(c, CELLECTOR_EINVAL, "combine: the selection keeps none of src's %llu cells", (unsigned long long)tc_src);
-    if (total_loci_out < c->total_loci)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: total_loci_out %llu is below ctx's total_loci %llu", (unsigned long long)total_loci_out,
-                        (unsigned long long)c->total_loci);
-    if (total_loci_out > 0xffffffffull)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: total_loci_out %llu exceeds 32-bit indices", (unsigned long long)total_loci_out);
-    if (locus_map) {
-        for (uint64_t j = 0; j < tl_src; j++)
-            if (locus_map[j] >= total_loci_out)
-                return ctx_fail(c, CELLECTOR_EINVAL, "combine: locus_map[%llu] = %u is not below total_loci_out %llu", (unsigned long long)j,
-                                locus_map[j], (unsigned long long)total_loci_out);
-    } else if (tl_src > total_loci_out) {
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: without a locus_map src's total_loci %llu must not exceed total_loci_out %llu",
-                        (unsigned long long)tl_src, (unsigned long long)total_loci_out);
-    }
-    if (n_ctx + n_kept > 0xffffffffull)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: %llu + %llu cells exceed 32-bit indices", (unsigned long long)n_ctx,
-                        (unsigned long long)n_kept);
-    if (c->n_combines >= 255) return ctx_fail(c, CELLECTOR_EINVAL, "combine: 255 combines since the last ingest from outside (cell_source is a byte)");
-    const uint64_t need_p1 = (uint64_t)P1_PLANES * total_loci_out;
-    const bool p1_bound = c->x_pass1 != c->x_pass1_own.get();
-    if (p1_bound && c->pass1_bound_cap < need_p1)
-        return ctx_fail(c, CELLECTOR_EINVAL, "combine: the bound PASS1 exchange buffer holds %llu values, total_loci_out %llu needs %llu",
-                        (unsigned long long)c->pass1_bound_cap, (unsigned long long)total_loci_out, (unsigned long long)need_p1);
-    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
-    SETDEV(c);
-    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
-    LapTimer t;
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing]   combine: %-22s %8.4f s\n", what, t.lap());
-    };
-    HIPCHK(c, hipStreamSynchronize(src->stream));  // (src is only read from here on, on ctx's stream)
-    // ---- validated: from here ctx changes.  The built matrix goes first; everything new is made beside the old entries and
-    // moved in at the end, so a failure on the way leaves ctx STAGED with its old entries and dims
-    if (c->state == cellector_ctx::ST_READY) {
-        unbuild_matrix(c);
-        lap("drop built matrix");
-    }
-    StagedCoo sel, own_sorted, sel_sorted, merged;
-    DevBuf<uint32_t> origin;
-    DevBuf<uint8_t> source;
-    DevBuf<double> p1;
-    {
-        // src's side: the selection and the draw are cellector_restage's, on src's arrays; then the renumbering
-        std::vector<uint8_t> all;
-        if (!src_keep) { all.assign(tc_src, 1); src_keep = all.data(); }
-        DevBuf<uint8_t> keep01;
-        DevBuf<uint32_t> rank, src_origin, d_map;
-        CHK(restage_cell_ranks(c, src_keep, tc_src, n_kept, src->cell_origin, &keep01, &rank, &src_origin));
-        CHK(combine_cells(c, n_ctx, n_kept, c->cell_origin, src_origin, c->cell_source, (uint8_t)(c->n_combines + 1), &origin, &source));
-        lap("cell ranks");
-        CHK(restage_select(c, src->coo.view(), tc_src, keep01, rank, T, seed, &sel));
-        lap("select src");
-        if (locus_map) {
-            CHK(dev_alloc(c, &d_map, tl_src));
-            HIPCHK(c, hipMemcpyAsync(d_map, locus_map, tl_src * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        CHK(combine_map(c, &sel, locus_map ? d_map.get() : nullptr, tl_src, (uint32_t)n_ctx));
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // (d_map and the host map are read)
-        lap("map");
-    }
-    CooView a = c->coo.view(), b = sel.view();
-    bool asc_a = true, asc_b = true;
-    CHK(combine_ascending(c, a, b, &asc_a, &asc_b));
-    if (!asc_a) { CHK(combine_sort(c, a, &own_sorted)); a = own_sorted.view(); }
-    if (!asc_b) { CHK(combine_sort(c, b, &sel_sorted)); sel.reset(); b = sel_sorted.view(); }
-    lap("order check / sort");
-    CHK(combine_merge(c, a, b, &merged));
-    lap("merge");
-    if (!p1_bound && need_p1 != c->n_pass1) CHK(dev_alloc(c, &p1, need_p1));
-    // ---- nothing below fails for memory
-    c->coo = std::move(merged);
-    c->cell_origin = std::move(origin);
-    c->cell_source = std::move(source);
-    c->n_combines++;
-    if (p1) { c->x_pass1_own = std::move(p1); c->x_pass1 = c->x_pass1_own; }
-    c->n_pass1 = need_p1;
-    c->total_loci = total_loci_out;
-    c->total_cells = n_ctx + n_kept; c->cell_begin = 0; c->cell_end = c->total_cells; c->nloc = c->total_cells;
-    c->state = cellector_ctx::ST_STAGED;
-    CHK(ingest_pass1(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    lap("release + PASS1");
-    return CELLECTOR_OK;
-}
-
-// ---- synthetic doublets from resident cells -----------------------------------------------------------------
-cellector_status cellector_add_doublets(cellector_ctx *c, const uint32_t *cell_a, const uint32_t *cell_b, uint64_t n_pairs,
-                                        double downsample_rate, uint64_t seed)
-{
-    if (!c) return CELLECTOR_EINVAL;
-    if (const char *why = combine_scope(c)) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: ctx %s", why);
-    if (n_pairs == 0) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: no pairs");
-    if (!cell_a || !cell_b) return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: %s is NULL", cell_a ? "cell_b" : "cell_a");
-    if (!(downsample_rate >= 0.0 && downsample_rate <= 1.0))  // (NaN fails both comparisons)
-        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: downsample_rate %g is not in [0, 1]", downsample_rate);
-    const uint64_t n_ctx = c->total_cells;
-    if (n_ctx + n_pairs > 0xffffffffull || n_ctx + n_pairs < n_ctx)
-        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: %llu + %llu cells exceed 32-bit indices", (unsigned long long)n_ctx,
-                        (unsigned long long)n_pairs);
-    for (uint64_t j = 0; j < n_pairs; j++) {
-        if (cell_a[j] >= n_ctx || cell_b[j] >= n_ctx)
-            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu (%u, %u) names a cell that is not below total_cells %llu",
-                            (unsigned long long)j, cell_a[j], cell_b[j], (unsigned long long)n_ctx);
-        if (cell_a[j] == cell_b[j])
-            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu names cell %u twice", (unsigned long long)j, cell_a[j]);
-    }
-    if (c->n_combines >= 255)
-        return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: 255 combines since the last ingest from outside (cell_source is a byte)");
-    const uint64_t T = (uint64_t)(downsample_rate * 9007199254740992.0);  // 2^53
-    SETDEV(c);
-    const bool timing = getenv("CELLECTOR_TIMING") != nullptr;  // phase wall times on stderr (every phase ends synchronised)
-    LapTimer t;
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing]   add_doublets: %-22s %8.4f s\n", what, t.lap());
-    };
-    // ---- the doublet side, beside a built matrix that stays: a sum above CELLECTOR_MAX_COUNT is known only now and must leave
-    // the ctx as it was
-    StagedCoo dbl, own_sorted, merged;
-    DevBuf<uint32_t> dbl_origin, origin;
-    DevBuf<uint8_t> source;
-    {
-        // the fan table: cell c is side s of pair j for the values 2 j + s of fan_val[fan_ptr[c] .. fan_ptr[c + 1])
-        std::vector<uint64_t> fan_ptr(n_ctx + 1, 0), fan_val(2 * n_pairs);
-        for (uint64_t j = 0; j < n_pairs; j++) { fan_ptr[cell_a[j] + 1]++; fan_ptr[cell_b[j] + 1]++; }
-        for (uint64_t i = 0; i < n_ctx; i++) fan_ptr[i + 1] += fan_ptr[i];
-        {
-            std::vector<uint64_t> at(fan_ptr.begin(), fan_ptr.end() - 1);
-            for (uint64_t j = 0; j < n_pairs; j++) { fan_val[at[cell_a[j]]++] = 2 * j; fan_val[at[cell_b[j]]++] = 2 * j + 1; }
-        }
-        bool overflow = false;
-        uint64_t over_pair = 0;
-        uint32_t over_locus = 0;
-        int over_allele = 0;
-        CHK(doublets_build(c, c->coo.view(), n_ctx, c->total_loci, fan_ptr.data(), fan_val.data(), fan_val.size(), T, seed, &dbl, &overflow,
-                           &over_pair, &over_locus, &over_allele));
-        if (overflow)
-            return ctx_fail(c, CELLECTOR_EINVAL, "add_doublets: pair %llu (%u, %u): the summed %s count at locus %u exceeds %u",
-                            (unsigned long long)over_pair, over_pair < n_pairs ? cell_a[over_pair] : 0u,
-                            over_pair < n_pairs ? cell_b[over_pair] : 0u, over_allele ? "alt" : "ref", over_locus, CELLECTOR_MAX_COUNT);
-        CHK(doublets_origin(c, cell_a, n_pairs, n_ctx, c->cell_origin, &dbl_origin));
-        lap("doublet side");
-    }
-    // ---- validated: from here ctx changes.  The built matrix goes; everything else new is made beside the old entries and moved
-    // in at the end, so a failure on the way leaves ctx STAGED with its old entries and dims
-    if (c->state == cellector_ctx::ST_READY) {
-        unbuild_matrix(c);
-        lap("drop built matrix");
-    }
-    CHK(combine_cells(c, n_ctx, n_pairs, c->cell_origin, dbl_origin, c->cell_source, (uint8_t)(c->n_combines + 1), &origin, &source));
-    CooView a = c->coo.view(), b = dbl.view();
-    bool asc_a = true, asc_b = true;
-    CHK(combine_ascending(c, a, b, &asc_a, &asc_b));
-    if (!asc_b) return ctx_fail(c, CELLECTOR_EDEVICE, "add_doublets: the doublet side does not ascend by (locus, cell)");
-    if (!asc_a) { CHK(combine_sort(c, a, &own_sorted)); a = own_sorted.view(); }
-    lap("order check / sort");
-    CHK(combine_merge(c, a, b, &merged));
-    lap("merge");
-    // ---- nothing below fails for memory
-    c->coo = std::move(merged);
-    c->cell_origin = std::move(origin);
-    c->cell_source = std::move(source);
-    c->n_combines++;
-    c->total_cells = n_ctx + n_pairs; c->cell_begin = 0; c->cell_end = c->total_cells; c->nloc = c->total_cells;
-    c->state = cellector_ctx::ST_STAGED;
-    CHK(ingest_pass1(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    lap("release + PASS1");
-    return CELLECTOR_OK;
-}
-
-cellector_status cellector_cell_source(const cellector_ctx *c, uint8_t *out)
-{
-    if (!c || !out) return CELLECTOR_EINVAL;
-    cellector_dims_t d;
-    CHK(cellector_dims(c, &d));
-    if (!c->multi && c->cell_source) return d2h(c, out, c->cell_source, d.total_cells);
-    memset(out, 0, d.total_cells);
-    return CELLECTOR_OK;
-}
-
 // ---- exchange buffers ---------------------------------------------------------------------------------
 cellector_status cellector_exchange_buffer(cellector_ctx *c, cellector_xchg which, void **dev_ptr, uint64_t *n)
 {
@@ -1235,7 +895,7 @@ cellector_status cellector_bind_exchange_buffer(cellector_ctx *c, cellector_xchg
     case CELLECTOR_XCHG_PASS1:
         REQUIRE(c, c->state == cellector_ctx::ST_EMPTY, "bind PASS1 before ingest");
         c->x_pass1_own.reset();
-        c->x_pass1 = p; c->n_pass1 = n; c->pass1_bound_cap = n;
+        c->x_pass1 = c->pass1_bound = p; c->n_pass1 = c->pass1_bound_cap = n;
         break;
     case CELLECTOR_XCHG_NORM:
         REQUIRE(c, c->state != cellector_ctx::ST_READY || n >= c->total_cells, "NORM buffer too small");
@@ -1494,17 +1154,9 @@ cellector_status cellector_em_reset(cellector_ctx *c)
     if (c->multi) return multi_em_reset(c);
     CHK(state_call_check(c, "em_reset"));
     SETDEV(c);
-    const uint64_t L = c->L, n = c->nloc;
+    const uint64_t n = c->nloc;
     state_drop_carried(c);
-    HIPCHK(c, hipMemsetAsync(c->mask, 1, L ? L : 1, c->stream));  // load_data.rs:176-179: all loci used
-    HIPCHK(c, hipMemsetAsync(c->mask_next, 1, L ? L : 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flags, 0, n ? n : 1, c->stream));   // main.rs:37: the empty set
-    HIPCHK(c, hipMemsetAsync(c->flags_new, 0, n ? n : 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ll, 0, (n ? n : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ell, 0, (n ? n : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->nloci, 0, (n ? n : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_norm, 0, (c->n_norm ? c->n_norm : 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_locus, 0, ((uint64_t)LB_PLANES * L + LC_COUNTERS) * 8, c->stream));
+    CHK(em_state_clear(c));
     if (c->var) HIPCHK(c, hipMemsetAsync(c->var, 0, (n ? n : 1) * 8, c->stream));
     if (c->tiled_ready) {
         HIPCHK(c, hipMemsetAsync(c->masked_cnt, 0, (n ? n : 1) * 4, c->stream));

@@ -1,10 +1,12 @@
 // Internal state of a cellector_ctx (one shard on one GPU) and the launch wrappers that the
-// C-ABI layer (cellector_ffi.cpp) calls.  Not part of the public ABI.
+// C-ABI layer (cellector_ffi.cpp, cellector_restage.cpp) calls.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -114,9 +116,11 @@ struct StagedCoo {
 struct MultiCtx;  // multi.cpp: the shards and worker threads of a ctx made by cellector_create_multi
 
 // ---- the state of a ctx, grouped by lifetime ------------------------------------------------------------------------------
-// The groups are base structs of cellector_ctx, so the code names every field as c->field.  A reload (begin_ingest) replaces
-// CtxMatrix, CtxTiled and CtxCarry with default-constructed ones: their device buffers go back to the cache, every other
-// field returns to its default.
+// CtxOptions and the four groups behind it are base structs of cellector_ctx, so the code names every field as c->field.  A group
+// is dropped as a whole, by assigning a default-constructed one: its device buffers go back to the cache, every other field returns
+// to its default.  READY -> STAGED (drop_built: cellector_restage, _combine, _add_doublets) drops CtxBuilt, CtxTiled and CtxCarry;
+// a reload (begin_ingest) drops those and CtxStaged.  A field goes where its lifetime is: nothing is saved around a drop, and what
+// outlives a reload (the options, the caller's PASS1 binding, streams, workspaces) is in none of the four.
 
 // the caller's option values (cellector_set_option, cellector_set_shard): kept across reloads
 struct CtxOptions {
@@ -166,15 +170,33 @@ struct CtxOptions {
     uint64_t req_cell_begin = 0, req_cell_end = UINT64_MAX;
 };
 
-// what one ingest makes
-struct CtxMatrix {
+// what a staging call makes: an ingest from outside, or cellector_restage / _combine / _add_doublets on the entries held
+struct CtxStaged {
     // dims
-    uint64_t total_loci = 0, total_cells = 0, L = 0, nloc = 0, nnz = 0;
+    uint64_t total_loci = 0, total_cells = 0, nloc = 0;
     enum { ST_EMPTY, ST_STAGED, ST_READY } state = ST_EMPTY;
     // this shard's cells: the requested range, the communicator's or all of them (ingest_all_cells), clamped to the matrix
     uint64_t cell_begin = 0, cell_end = UINT64_MAX;
 
     StagedCoo coo;  // staged COO of this shard (all loci; cell index local)
+
+    // PASS1 exchange buffer: the library's own or the one the caller bound (pass1_bound); the staged matrix uses n_pass1 values of it
+    double *x_pass1 = nullptr;
+    DevBuf<double> x_pass1_own;
+    uint64_t n_pass1 = 0;
+
+    // cellector_cell_origin: per current cell its index in the matrix of the last ingest from outside; null = identity
+    // (cellector_restage composes it)
+    DevBuf<uint32_t> cell_origin;
+    // cellector_cell_source: per current cell 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine
+    // since; null = all 0.  n_combines counts the combines since that ingest (at most 255)
+    DevBuf<uint8_t> cell_source;
+    uint32_t n_combines = 0;
+};
+
+// what cellector_ingest_finish builds from the staged matrix, and what later calls make from that
+struct CtxBuilt {
+    uint64_t L = 0, nnz = 0;  // used loci, their entries
 
     // matrix
     DevBuf<uint64_t> csr_ptr, csr_ent;   // [nloc+1], [nnz]
@@ -204,10 +226,10 @@ struct CtxMatrix {
     DevBuf<uint32_t> lm_hist_min;      // [L][18] ... of the cells of the new exclusion set
     DevBuf<double> lm_out;             // [4][L] expected minority / majority, variance minority / majority of the last pass
 
-    // exchange buffers: the library's own (x_*_own) or one the caller bound (a bound PASS1 buffer is kept across a reload)
-    double *x_pass1 = nullptr, *x_norm = nullptr, *x_locus = nullptr;
-    DevBuf<double> x_pass1_own, x_norm_own, x_locus_own;
-    uint64_t n_pass1 = 0, n_norm = 0, n_locus = 0;
+    // NORM / LOCUS exchange buffers: the library's own (x_*_own) or one the caller bound (forgotten with the built matrix)
+    double *x_norm = nullptr, *x_locus = nullptr;
+    DevBuf<double> x_norm_own, x_locus_own;
+    uint64_t n_norm = 0, n_locus = 0;
 
     double near_rel = CELLECTOR_NEAR_TIE_REL;  // near-tie band of this matrix, relative to max(1, |threshold|) (cellector_ingest_finish)
     // option resolve_ties (kernels_resolve.hip)
@@ -330,7 +352,7 @@ struct CtxCarry {
     std::vector<uint32_t> pa_ids;
 };
 
-struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
+struct cellector_ctx : CtxOptions, CtxStaged, CtxBuilt, CtxTiled, CtxCarry {
     // a ROOT ctx (cellector_create_multi with more than one shard) owns no device state of its own: every entry point
     // fans out to its shards (multi.cpp) and returns arrays in global cell order
     MultiCtx *multi = nullptr;
@@ -346,14 +368,9 @@ struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_sum = nullptr;
     hipEvent_t ev_tab = nullptr;   // completion of the table kernel queued ahead by em_finish, attached to its dispatch (no barrier packet)
     mutable std::string err;
-    // cellector_cell_origin: per current cell its index in the matrix of the last ingest from outside; null = identity.  Not
-    // part of CtxMatrix: begin_ingest clears it, cellector_restage composes it and carries it over its own reset
-    DevBuf<uint32_t> cell_origin;
-    // cellector_cell_source: per current cell 0 = from the last ingest from outside, k = brought in by the k-th cellector_combine
-    // since; null = all 0.  Same lifetime as cell_origin; n_combines counts the combines since that ingest (at most 255)
-    DevBuf<uint8_t> cell_source;
-    uint32_t n_combines = 0;
-    // the capacity (f64 values) of a PASS1 buffer the caller bound; n_pass1 is what the staged matrix uses of it
+    // the PASS1 buffer the caller bound (cellector_bind_exchange_buffer) and its capacity in f64 values; null = none.  It outlives
+    // reloads: begin_ingest points x_pass1 at it again
+    double *pass1_bound = nullptr;
     uint64_t pass1_bound_cap = 0;
 
     DevBuf<double> lf;            // [LF_TABLE_N] ln factorial table
@@ -386,6 +403,14 @@ struct cellector_ctx : CtxOptions, CtxMatrix, CtxTiled, CtxCarry {
     std::vector<hipEvent_t> ev_pool;  // collected timer events, reused (creating a pair costs microseconds before a launch)
 };
 
+// READY -> STAGED, and the first half of a reload: what was built from the staged matrix goes as a whole
+inline void drop_built(cellector_ctx *c)
+{
+    static_cast<CtxCarry &>(*c) = CtxCarry();
+    static_cast<CtxTiled &>(*c) = CtxTiled();
+    static_cast<CtxBuilt &>(*c) = CtxBuilt();
+}
+
 #define SEL_T 6
 #define CELLECTOR_SUM_SEQ 31
 #define CELLECTOR_SEL_HIST_WORDS (4096 + SEL_T * 1024 + 64)
@@ -404,6 +429,21 @@ cellector_status ctx_fail(const cellector_ctx *c, cellector_status s, const char
         cellector_status s__ = (expr);                                                           \
         if (s__ != CELLECTOR_OK) return s__;                                                     \
     } while (0)
+
+#define REQUIRE(c, cond, msg)                                        \
+    do {                                                             \
+        if (!(cond)) return ctx_fail((c), CELLECTOR_EINVAL, "%s", msg); \
+    } while (0)
+#define SETDEV(c) HIPCHK((c), hipSetDevice((c)->device))
+
+static inline cellector_status d2h(const cellector_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    if (!bytes) return CELLECTOR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CELLECTOR_OK;
+}
 
 // n elements of T into *p (the block *p held before is released first)
 template <typename T>
@@ -453,6 +493,12 @@ struct LapTimer {  // CELLECTOR_TIMING=1: phase wall times of the ingest on stde
         t = std::chrono::steady_clock::now();
         return std::chrono::duration<double>(t - was).count();
     }
+};
+struct CallLaps {  // ... and of a re-staging call, under the call's name (every phase ends synchronised)
+    const char *call;
+    const bool on = getenv("CELLECTOR_TIMING") != nullptr;
+    LapTimer t;
+    void operator()(const char *what) { if (on) fprintf(stderr, "[timing]   %s: %-22s %8.4f s\n", call, what, t.lap()); }
 };
 void timer_begin(cellector_ctx *c, int which);
 void timer_end(cellector_ctx *c, int which);

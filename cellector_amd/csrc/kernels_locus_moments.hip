@@ -182,7 +182,7 @@ static void lm_launch_count(cellector_ctx *c, const uint8_t *flags, uint32_t *hi
                        c->csr_ptr.get(), c->csr_ent.get(), flags, hist);
 }
 
-// The all-cells histogram and the far list of this matrix, made on first use (cache: a reload drops them with CtxMatrix).
+// The all-cells histogram and the far list of this matrix, made on first use (cache: dropped with CtxBuilt).
 static cellector_status lm_static(cellector_ctx *c)
 {
     if (c->lm_static_ready) return CELLECTOR_OK;

@@ -397,3 +397,67 @@ def test_refusals_leave_the_ctx_unchanged(env, full):
     assert tuple(getattr(s1, k) for k, _ in s1._fields_) == tuple(getattr(s2, k) for k, _ in s2._fields_)
     assert np.array_equal(g.excluded(), f.excluded())
     g.close(); f.close()
+
+
+def test_the_staged_group_across_unbuilds_with_a_bound_pass1(env):
+    """What the ctx keeps when a READY matrix goes back to STAGED, with a caller-bound PASS1 buffer: the binding (pointer, length),
+    PASS1's contents (those of a fresh ctx, with a buffer of its own, that ingests the twin's arrays; exactly), cell_origin and
+    cell_source; and what the next ingest from outside resets.  4 loci x 3 cells, six entries, finished with min_alt = min_ref = 1
+    (three cells cannot meet the default of 4)."""
+    import ctypes as C
+    import torch
+    from cellector_amd import doublets
+    ffi = env["ffi"]
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemcpy.restype = C.c_int
+    TL, P1_PLANES = 4, 5
+
+    def fresh_pass1(n_cells, coo):
+        f = _make(env)
+        f.ingest_coo(TL, n_cells, *coo)
+        ptr, n = f.exchange_buffer(ffi.XCHG_PASS1)
+        out = np.empty(n)
+        assert n == P1_PLANES * TL and hip.hipMemcpy(out.ctypes.data, ptr, n * 8, 2) == 0  # device to host
+        f.close()
+        return out
+
+    def bound_pass1(g):
+        assert g.exchange_buffer(ffi.XCHG_PASS1) == (buf.data_ptr(), P1_PLANES * TL)  # the same buffer, all of it in use
+        torch.cuda.synchronize()
+        return buf.cpu().numpy()
+
+    u32 = lambda *v: np.array(v, np.uint32)
+    coo = [u32(0, 0, 1, 2, 2, 3), u32(0, 2, 1, 0, 1, 2), u32(1, 2, 0, 3, 1, 2), u32(2, 0, 4, 1, 1, 5)]
+    buf = torch.zeros(P1_PLANES * TL, dtype=torch.float64, device="cuda:0")
+    g = _make(env)
+    g.bind_exchange_buffer(ffi.XCHG_PASS1, buf.data_ptr(), buf.numel())
+    g.ingest_coo(TL, 3, *coo)
+    g.ingest_finish(1, 1)
+    # 1. a restage from READY
+    keep = np.array([1, 0, 1], np.uint8)
+    t1 = env["restage"].restage_coo(*coo, 3, keep)
+    g.restage(keep)
+    assert bound_pass1(g).tobytes() == fresh_pass1(t1[4], t1[:4]).tobytes()
+    assert g.cell_origin().tolist() == [0, 2] and t1[5].tolist() == [0, 2]
+    for got, want in zip(g.staged_coo(), t1[:4]):
+        assert np.array_equal(got, want)
+    # 2. add_doublets from READY
+    g.ingest_finish(1, 1)
+    t2 = doublets.add_doublets_coo(t1[:4], t1[4], [0], [1], origin=t1[5])
+    g.add_doublets([0], [1])
+    assert bound_pass1(g).tobytes() == fresh_pass1(t2[4], t2[:4]).tobytes()
+    assert g.cell_source().tolist() == [0, 0, 1] and g.cell_origin().tolist() == [0, 2, 0] == t2[5].tolist()
+    for got, want in zip(g.staged_coo(), t2[:4]):
+        assert np.array_equal(got, want)
+    # 3. an ingest from outside: origin and source start again, and so does the combine counter
+    other = [u32(0, 1, 3), u32(1, 0, 2), u32(1, 1, 2), u32(0, 3, 1)]
+    g.ingest_coo(TL, 3, *other)
+    assert g.cell_origin().tolist() == [0, 1, 2] and g.cell_source().tolist() == [0, 0, 0]
+    assert bound_pass1(g).tobytes() == fresh_pass1(3, other).tobytes()
+    s = _make(env)
+    s.ingest_coo(TL, 1, u32(2), u32(0), u32(1), u32(1))
+    g.combine(s)
+    assert g.cell_source().tolist() == [0, 0, 0, 1]
+    bound_pass1(g)
+    g.close(); s.close()
