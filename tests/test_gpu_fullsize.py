@@ -17,6 +17,8 @@ abs 1e-6 (north_star).
 import numpy as np
 import pytest
 
+from posterior_reference import posterior_alpha_betas as _posterior_alpha_betas  # (the statement of main.rs:239-254)
+
 pytestmark = pytest.mark.gpu
 
 LL_ATOL = 1e-7
@@ -26,21 +28,6 @@ POST_ATOL = 1e-6
 def _lse(a, b):
     m = np.maximum(a, b)
     return m + np.log(np.exp(a - m) + np.exp(b - m))
-
-
-def _posterior_alpha_betas(lc, alt_min, ref_min, n_excluded, n_cells):
-    """The three alpha/beta sets of calculate_posteriors (main.rs:239-254) from the per-locus totals and the
-    minority tallies, in the reference's operation order."""
-    s_ref, s_alt = lc[:, 0], lc[:, 1]
-    a_maj, b_maj = (s_alt + 1.0) - alt_min, (s_ref + 1.0) - ref_min
-    a_min, b_min = (s_alt + 1.0) - (s_alt - alt_min), (s_ref + 1.0) - (s_ref - ref_min)
-    mf0 = (n_excluded + 1.0) / (n_cells + 1.0)
-    a_dbl = (a_maj - 1.0) * mf0 + (a_min - 1.0) + 1.0
-    b_dbl = (b_maj - 1.0) * mf0 + (b_min - 1.0) + 1.0
-    mf = max(mf0, 0.01)
-    a_maj, b_maj = (a_maj - 1.0) * mf + 1.0, (b_maj - 1.0) * mf + 1.0
-    lp_dbl = np.log(n_cells / 1000.0 / 100.0 * max(mf, 0.1))
-    return (a_min, b_min), (a_maj, b_maj), (a_dbl, b_dbl), (np.log(mf), np.log(1.0 - mf), lp_dbl)
 
 
 def dm_nnz(g):

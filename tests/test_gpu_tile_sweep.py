@@ -525,10 +525,13 @@ def test_em_and_posteriors(mods, case):
         the locus filter left (locus 5 is masked: its table rows are zero and its entries leave loci_used);
       * ll_minority and ll_majority of the posterior phase, which runs over ALL loci (quirk Q1: get_loci_used_for_posterior_calc,
         main.rs:282-306, returns all-true) with alpha / beta from the exclusion set's tallies over all loci, formed as
-        test_gpu_fullsize._posterior_alpha_betas does."""
-    import test_gpu_fullsize as F
+        posterior_reference.posterior_alpha_betas does (posterior_alpha_betas(0 / 1 / 2) must return those bits);
+      * posterior and doublet_posterior of every cell within the relative bound of tests/posterior_reference.py, which is how the
+        doublet set's sum — table set 2 of the phase, not returned by the ABI — is seen."""
+    import posterior_reference as pr
     import test_gpu_parity as T
     tag, L, N, coo, opts = list(_em_cases())[case]
+    post = None
     lo, ce, al, re = coo
     ob = mods["ob"]
     ob.set_threads(ob.host_threads())
@@ -556,17 +559,23 @@ def test_em_and_posteriors(mods, case):
             worst = _check(f"{tag} tile_sb {sb}: last EM pass", (co["ll"], co["expected_ll"], co["loci_used"]), ref, G)
             pg, _ = T._check_posteriors(dict(mods, engine=2), g, o)
             exc = g.excluded() != 0
-            sel = exc[ce]
-            alt_min = np.bincount(lo[sel], weights=al[sel].astype(np.float64), minlength=L)
-            ref_min = np.bincount(lo[sel], weights=re[sel].astype(np.float64), minlength=L)
-            (a_min, b_min), (a_maj, b_maj), _, _ = F._posterior_alpha_betas(g.locus_counts(), alt_min, ref_min, int(exc.sum()), N)
-            for name, a, b in (("ll_minority", a_min, b_min), ("ll_majority", a_maj, b_maj)):
-                ref = tr.cell_reference(N, *coo, a, b)
+            if post is None:  # (the reference of the posterior phase: once per case, the set is the same under both widths)
+                post = pr.reference(L, N, coo, exc)
+            assert np.array_equal(exc, post["excluded"]) and np.array_equal(g.locus_counts(), post["locus_counts"])
+            for which in (0, 1, 2):
+                a, b = g.posterior_alpha_betas(which)
+                assert np.array_equal(a, post["ab"][which][0]) and np.array_equal(b, post["ab"][which][1]), (tag, which)
+            for name, ref in (("ll_minority", post["sums"][0]), ("ll_majority", post["sums"][1])):
                 bound = tr.cell_bound(ref, G)[0] + 0.5 * np.spacing(np.abs(ref["ll"]))
                 d = np.abs(pg[name] - ref["ll"])
                 worst = max(worst, _ratio(d, bound))
                 bad = np.nonzero(d > bound)[0]
                 assert bad.size == 0, (tag, sb, name, bad[:6], pg[name][bad[:6]], ref["ll"][bad[:6]], bound[bad[:6]])
+            # posterior and doublet_posterior by the relative rule of tests/posterior_reference.py: the only outputs the doublet
+            # set's sum reaches
+            res = pr.compare(post, pg, G)
+            assert all(bad.size == 0 for _, bad in res.values()), f"{tag} tile_sb {sb}: " + pr.describe(post, pg, res, G)
+            print(f"  {tag} tile_sb {sb}: posterior phase worst / bound " + ", ".join(f"{k} {res[k][0]:.3f}" for k in pr.OUTPUTS))
             print(f"  {tag} tile_sb {sb}: {iters} iterations, {int(exc.sum())} excluded, {int((used == 0).sum())} loci masked; "
                   f"EM pass and posterior sums worst / bound = {worst:.3f}")
             g.close(); o.close()

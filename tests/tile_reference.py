@@ -256,8 +256,8 @@ def expected_bound(alpha, beta, n, e):
 def cell_reference(n_cells, locus, cell, alt, ref, alpha, beta, mask=None):
     """The cell pass over COO arrays (load order; a (locus, cell) pair listed twice is two entries).
 
-    Returns a dict of per-cell arrays: ll, expected_ll (double, rounded from the longdouble sums), loci_used, count (= loci_used as
-    integers), abs_ll / abs_ell (sum of |term|), b_ll / b_ell (sum of the per-term device bounds), and the per-entry arrays
+    Returns a dict of per-cell arrays: ll, expected_ll (double, rounded from the longdouble sums), ll_ld (the longdouble sum of ll
+    before it is rounded), loci_used, count (= loci_used as integers), abs_ll / abs_ell (sum of |term|), b_ll / b_ell (sum of the per-term device bounds), and the per-entry arrays
     term / eterm / bterm / ebterm (doubles, for probes) with `keep` (the entries at unmasked loci)."""
     locus = np.asarray(locus, np.int64)
     cell = np.asarray(cell, np.int64)
@@ -293,8 +293,9 @@ def cell_reference(n_cells, locus, cell, alt, ref, alpha, beta, mask=None):
             out[nz] = np.add.reduceat(v, starts[nz])
         return out
 
+    ll_ld = per_cell(t)
     return dict(
-        ll=per_cell(t).astype(np.float64), expected_ll=per_cell(e).astype(np.float64),
+        ll=ll_ld.astype(np.float64), ll_ld=ll_ld, expected_ll=per_cell(e).astype(np.float64),
         loci_used=cnt.astype(np.float64), count=cnt,
         abs_ll=per_cell(np.abs(t)).astype(np.float64), abs_ell=per_cell(np.abs(e)).astype(np.float64),
         b_ll=per_cell(bt), b_ell=per_cell(be),
