@@ -13,8 +13,8 @@
 //               cell-per-lane walk in file order — and a lane fetches its row with one or two 16-byte loads.
 //               A u16 entry is n-1 << 14 | locus slot << 4 | code; padding points at an all-zero slot.
 //               A persistent 1024-thread workgroup takes columns of four cell blocks and a group of chunks: the chunk's
-//               table lives in LDS locus-major (144 B per locus: the log-pmf and the expected term of an entry are two
-//               8-byte reads near each other); a lane keeps its cell's entries of the tile in registers (prefetched two
+//               table lives in LDS code-major (18 planes of 640 slots: the log-pmf and the expected term of an entry are two
+//               8-byte reads on the SAME bank pair, slot mod 32, whatever the code; tiled.h); a lane keeps its cell's entries of the tile in registers (prefetched two
 //               tiles ahead) and adds the tile's sum to the cell's accumulator in LDS (the lane <-> cell assignment
 //               changes from tile to tile).  No transcendental, no atomics; a cell's sum runs over its chunks in order
 //               and inside a chunk in ascending-locus order: bit-deterministic (the number of chunk groups fixes how
@@ -35,8 +35,9 @@ __device__ __constant__ uint8_t T_A_OF[T_NCODE] = {1, 0, 2, 1, 0, 3, 2, 1, 0, 4,
 __device__ __constant__ uint8_t T_R_OF[T_NCODE] = {0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4};
 
 // ---------------------------------------------------------------------------------------------------------
-// tables, laid out [chunk][locus slot][18] so that a chunk is one contiguous block the tile kernel copies straight into
-// LDS: per locus the 14 log-pmfs, then (PAIRS) the 4 expected terms.  All zero for masked loci (alpha < 0), for the
+// tables, laid out [chunk][the chunk's image] so that a chunk is one contiguous block the tile kernel copies straight into
+// LDS.  The image is the geometry's (tiled.h, tab_pmf / tab_exp): code-major for the regular entries, i.e. 18 planes of T_BL
+// doubles, the 4 expected terms' (PAIRS; else zero) before the 14 log-pmfs'.  All zero for masked loci (alpha < 0), for the
 // padding beyond L and in the last slot of every chunk (the padding entries' target).
 // ---------------------------------------------------------------------------------------------------------
 // In an EM iteration the kernel is the iteration's FIRST one: it then also forms alpha/beta (init_alpha_betas,
@@ -79,10 +80,10 @@ __global__ __launch_bounds__(64 * TB_PARTS) void k_build_tables(uint64_t L, uint
         }
     }
     const bool live = p.x >= 0.0;
-    double *row = tab + chunk * TAB_ELEMS + slot * T_LROW;
+    double *img = tab + chunk * TAB_ELEMS;  // (code-major: a wave's 64 slots of a plane are one contiguous store)
     // code w <-> (alt, ref) as in T_A_OF / T_R_OF, written out so that the products unroll
-#define TB_PMF(W, A, R) row[W] = live ? dm_log_bb_pmf(lf, p.x, p.y, A, R) : 0.0
-#define TB_EXP(N) row[T_NCODE + N - 1] = (PAIRS && live) ? dm_expected_log_pmf(lf, p.x, p.y, N) : 0.0
+#define TB_PMF(W, A, R) img[tab_pmf<geo_reg>((uint32_t)slot, W)] = live ? dm_log_bb_pmf(lf, p.x, p.y, A, R) : 0.0
+#define TB_EXP(N) img[tab_exp<geo_reg>((uint32_t)slot, N - 1)] = (PAIRS && live) ? dm_expected_log_pmf(lf, p.x, p.y, N) : 0.0
     switch (part) {
     case 0: TB_EXP(4u); TB_PMF(0, 1u, 0u); break;
     case 1: TB_EXP(3u); TB_PMF(1, 0u, 1u); break;
@@ -265,9 +266,9 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
 #else
 #define TILE_LOOKUP(V, E16)                                                                                      \
     do {                                                                                                         \
-        const uint32_t b__ = (((E16) >> G::SHIFT) & G::SMASK) * G::LROW;                                         \
-        if constexpr (EXPECTED) V = make_double2(s_tab[b__ + ((E16) & G::CMASK)], s_tab[b__ + G::NCODE + ((E16) >> 14)]); \
-        else V = s_tab[b__ + ((E16) & G::CMASK)];                                                                \
+        const uint32_t s__ = ((E16) >> G::SHIFT) & G::SMASK;                                                     \
+        if constexpr (EXPECTED) V = make_double2(s_tab[tab_pmf<G>(s__, (E16) & G::CMASK)], s_tab[tab_exp<G>(s__, (E16) >> 14)]); \
+        else V = s_tab[tab_pmf<G>(s__, (E16) & G::CMASK)];                                                       \
     } while (0)
 #endif
 #define TILE_RD(V, KK)                                                                                           \
@@ -764,7 +765,7 @@ __global__ __launch_bounds__(256) void k_t2c_tables(uint64_t L, uint32_t gp, con
             }
             v = (lf[n] - lf[a] - lf[r]) + log(num / den);
         }
-        tabc[(l / G::BLU) * ELEMS + (l % G::BLU) * G::LROW + c2] = v;
+        tabc[(l / G::BLU) * ELEMS + tab_pmf<G>((uint32_t)(l % G::BLU), c2)] = v;
     } else if (EXPECTED) {
         constexpr uint32_t NE = G::NHI - G::NLO + 1;
         const uint64_t i = (uint64_t)(blockIdx.x - gp) * 256 + threadIdx.x;
@@ -772,7 +773,7 @@ __global__ __launch_bounds__(256) void k_t2c_tables(uint64_t L, uint32_t gp, con
         if (l >= L) return;
         const uint32_t n = G::NLO + (uint32_t)(i % NE);
         const double2 p = ab[l];
-        tabc[(l / G::BLU) * ELEMS + (l % G::BLU) * G::LROW + G::NCODE + (n - G::NLO)] = p.x >= 0.0 ? ov_expected_rec(p.x, p.y, n) : 0.0;
+        tabc[(l / G::BLU) * ELEMS + tab_exp<G>((uint32_t)(l % G::BLU), n - G::NLO)] = p.x >= 0.0 ? ov_expected_rec(p.x, p.y, n) : 0.0;
     }
 }
 
@@ -1407,7 +1408,7 @@ __global__ __launch_bounds__(256) void k_locus_finalize(uint64_t L, int locus_mo
         if (in && (n_planes || tp.fresh)) tally[l * 16 + j] = cnt;  // the counts of the new set, kept for the next iteration
         const uint32_t h_all = hist_all[l * T_NCODE + j];
         // (element stride 2 when the table holds (log-pmf, expected) pairs)
-        const double t_code = tab[(l / T_BLU) * TAB_ELEMS + (l % T_BLU) * T_LROW + j];
+        const double t_code = tab[(l / T_BLU) * TAB_ELEMS + tab_pmf<geo_reg>((uint32_t)(l % T_BLU), j)];
         amin = (uint64_t)cnt * T_A_OF[j];
         rmin = (uint64_t)cnt * T_R_OF[j];
         if (live) {

@@ -131,22 +131,24 @@ __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj,
 }
 
 // Bank-aware order of the entries inside the rows of one slice (option "bank_order"; a wave per slice, lane = row, the slice's rows
-// in LDS).  The tile kernel's lookup step k reads, for the 32 lanes of a half-wave, the log-pmf at slot * 18 + code and the
-// expected term at slot * 18 + 14 + (n - 1): two 8-byte LDS reads per lane, served at one cycle per DISTINCT address on the busiest
-// of the 32 bank pairs.  In file order the banks are random — 3.3 cycles per step and half-wave instead of 1 — and those conflicts
+// in LDS).  The tile kernel's lookup step k reads, for the 32 lanes of a half-wave, the log-pmf and the expected term of the lane's
+// entry (tab_pmf / tab_exp of the geometry, tiled.h): two 8-byte LDS reads per lane, served at one cycle per DISTINCT address on the
+// busiest of the 32 bank pairs.  In file order the banks are random — 3.3 cycles per step and half-wave instead of 1 — and those conflicts
 // are 42 % of the kernel's time (SQ_LDS_BANK_CONFLICT).  A row's sum does not care about the order of its entries beyond rounding,
 // so the builder picks it: step by step, every lane whose entry of this step is still open proposes the cheapest of its remaining
 // entries given the bank loads of the lanes already placed in the step; of the proposers that share a bank pair the lowest lane is
 // placed, the others propose again; after four rounds whoever is left takes its proposal.  Simulated (tools/probe/bank_sim.py):
-// 3.3 -> 2.4 cycles per step, the same as placing the lanes one after the other.  Deterministic; the order inside a row then depends
+// 3.3 -> 2.4 cycles per step, the same as placing the lanes one after the other (locus-major, 18 doubles per locus; with the
+// code-major image 3.06 -> 2.17).  Deterministic; the order inside a row then depends
 // on the 31 rows that share its half-wave, i.e. on the shard's cell set: per-cell sums of differently sharded runs differ in the
 // last bits (as they already do between different chunk-group counts).
 #define TBO_ROUNDS 4
 __device__ __forceinline__ void tbo_banks(uint32_t e, uint32_t *a, uint32_t *b)
 {
-    const uint32_t base = ((e >> 4) & 1023u) * (uint32_t)T_LROW;
-    *a = (base + (e & 15u)) & 31u;
-    *b = (base + (uint32_t)T_NCODE + (e >> 14)) & 31u;
+    // (the tile kernel's own address function; code-major: both are the slot's bank pair, slot mod 32)
+    const uint32_t slot = (e >> geo_reg::SHIFT) & geo_reg::SMASK;
+    *a = tab_pmf<geo_reg>(slot, e & geo_reg::CMASK) & 31u;
+    *b = tab_exp<geo_reg>(slot, e >> 14) & 31u;
 }
 // Which lane of its slice a row takes (any permutation of a slice's 64 rows is a valid layout).  The tile kernel adds a row's
 // sums to its cell's accumulator in LDS with one 16-byte read and one 16-byte write per lane: address = cell * 16, served in

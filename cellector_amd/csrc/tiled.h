@@ -25,8 +25,8 @@ static_assert(T_BC == T_ROWS_PER_TILE, "cellector_engine_info derives the lookup
 static_assert(T_GROUPS_MAX == CELLECTOR_TILE_WORK_STRIDE, "k_alpha_beta resets the counters with this stride");
 #define T_GROUPS 8      // chunk groups beyond this many are charged for their partial sums (tiled_build's cost model)
 #define T_NE 15         // entries per cell of a slice held in registers (two 16-byte loads); longer slices: slow path
-// A u16 entry = n-1 << 14 | locus slot << 4 | code: log-pmf at table[slot * T_LROW + code], expected term at
-// table[slot * T_LROW + T_NCODE + (n-1)].
+// A u16 entry = n-1 << 14 | locus slot << 4 | code; where its log-pmf and its expected term sit in the chunk's table is the
+// geometry's business (tab_pmf / tab_exp below).
 #define T_NULL ((uint16_t)(T_BLU << 4))  // padding entry: code 0, n-1 = 0 of the zero slot
 // A slice in `tiles` is 64 rows of K+1 u16 (K odd): row i = [cell (0..1023) that lane i works for, K entries of that cell,
 // padded with T_NULL].  Tile header (fixed stride, in u16 units): 16 slices x {u64 first u16 of the slice in `tiles`,
@@ -51,9 +51,20 @@ __device__ __forceinline__ uint32_t ent_code(uint64_t e)
 // n-1 << 14 | slot << 4 | code.  geo_t2<NMAX>: the tier-2 tiles of a deep-coverage matrix (totals 5..NMAX, tiled_build):
 // NMAX = 8: 30 log-pmfs + 4 expected terms per locus, 338 loci per chunk, entry = n-5 << 14 | slot << 5 | pair;
 // NMAX = 6: 13 + 2 doubles per locus, 767 loci per chunk, entry = n-5 << 14 | slot << 4 | pair.
+// The image of a chunk's table (in global memory and, copied as it is, in LDS) is a property of the geometry:
+//   locus-major  [slot][LROW]: a locus' log-pmfs, then its expected terms;
+//   code-major   [LROW planes][BL]: the expected-term planes first, the log-pmf planes after them, plane p at p * BL + slot.  A
+//                lookup's bank pair is then slot mod 32 whatever the code (locus-major at an even LROW: the expected term of an
+//                n = 1 entry, 70 % of them, only ever reaches the even bank pairs), and the plane's byte offset is code x (BL x 8)
+//                added onto slot x 8 by one multiply-add — the constant part of both lookups (0 and NE planes) fits the 16-bit
+//                offset field of a DS instruction.
+#ifndef TILE_CM
+#define TILE_CM 1  // regular geometry: 1 = code-major table image, 0 = locus-major (the measurement's other arm)
+#endif
 struct geo_reg {
     static constexpr uint32_t LROW = T_LROW, BL = T_BL, NCODE = T_NCODE, SHIFT = 4, SMASK = 1023u, CMASK = 15u;
     static constexpr uint32_t BLU = BL - 1, NLO = 1, NHI = T_K;  // loci per chunk (the last slot is all zeros); totals covered
+    static constexpr bool CODE_MAJOR = TILE_CM != 0;
 };
 template <int NMAX>
 struct geo_t2 {
@@ -62,7 +73,20 @@ struct geo_t2 {
     static constexpr uint32_t BL = NMAX == 8 ? 339 : 768, SHIFT = NMAX == 8 ? 5 : 4, SMASK = NMAX == 8 ? 511u : 1023u,
                               CMASK = NMAX == 8 ? 31u : 15u;
     static constexpr uint32_t BLU = BL - 1, NLO = 5, NHI = NMAX;
+    static constexpr bool CODE_MAJOR = false;
 };
+// THE index function of a chunk's table: element of the log-pmf of `code` resp. of the expected term number `ne` (= n - G::NLO)
+// of locus slot `slot`.  Everything that writes or reads a chunk table goes through these two.
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tab_pmf(uint32_t slot, uint32_t code)
+{
+    return G::CODE_MAJOR ? (G::LROW - G::NCODE + code) * G::BL + slot : slot * G::LROW + code;
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tab_exp(uint32_t slot, uint32_t ne)
+{
+    return G::CODE_MAJOR ? ne * G::BL + slot : slot * G::LROW + G::NCODE + ne;
+}
 
 // overflow entries (alt+ref == 0 or > T_K)
 #define LF_LANES 16  // lanes that share a locus (k_locus_finalize) or a row (k_ovf_cell_wide)

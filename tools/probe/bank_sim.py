@@ -1,13 +1,30 @@
 #!/usr/bin/env python3
 """Simulation of the LDS bank conflicts of k_tile_ll's table lookups for different orders of the entries inside the rows of a
-slice (tile-build time), table strides 18 / 19 doubles per locus.  A lookup step of a half-wave = 32 lanes each reading 8 bytes:
-cycles = max over the 32 bank pairs of the number of DISTINCT addresses on it (MI355X_MICROARCH.md, LDS).  Two lookups per entry:
-log-pmf at slot*S + code, expected term at slot*S + 14 + (n-1)."""
+slice (tile-build time) and different table images.  A lookup step of a half-wave = 32 lanes each reading 8 bytes:
+cycles = max over the 32 bank pairs of the number of DISTINCT addresses on it (MI355X_MICROARCH.md, LDS).  Two lookups per entry.
+The image is the parameter S of everything below (csrc/tiled.h, tab_pmf / tab_exp):
+  an integer      locus-major with that many doubles per locus (18, 19): log-pmf at slot*S + code, expected term at slot*S + 14 + (n-1);
+  "cm"            code-major, planes of CM_BL = 640 slots, the four expected-term planes first: log-pmf at (4 + code)*640 + slot,
+                  expected term at (n-1)*640 + slot — both on bank pair slot mod 32."""
 import sys
 import numpy as np
 
 rng = np.random.default_rng(1)
 NSLOT, DENS = 639, 0.01
+CM_BL = 640
+LAYOUTS = (18, 19, "cm")
+
+
+def addr_pair(e, S):
+    """(log-pmf address, expected-term address) in doubles of entry e = (slot, code, n-1) under image S; None: a padding entry"""
+    slot, code, nm1 = (NSLOT, 0, 0) if e is None else (int(e[0]), int(e[1]), int(e[2]))
+    if S == "cm":
+        return (4 + code) * CM_BL + slot, nm1 * CM_BL + slot
+    return slot * S + code, slot * S + 14 + nm1
+
+
+def layout_name(S):
+    return f"code-major, {CM_BL} slots" if S == "cm" else f"stride {S}"
 
 
 def make_tile():
@@ -43,11 +60,7 @@ def cost_half(ent, S):
         for which in (0, 1):
             per_bank = {}
             for lane in range(32):
-                e = ent[lane][k]
-                if e is None:
-                    addr = NSLOT * S + (0 if which == 0 else 14)
-                else:
-                    addr = e[0] * S + (e[1] if which == 0 else 14 + e[2])
+                addr = addr_pair(ent[lane][k], S)[which]
                 per_bank.setdefault(addr % 32, set()).add(addr)
             tot += max(len(v) for v in per_bank.values())
     return tot
@@ -71,7 +84,7 @@ def greedy_seq(rs, K, S, both=True):
             slack = (K - k) - len(rem[lane])
             best, bc = None, None
             for idx, e in enumerate(rem[lane]):
-                a, b = (e[0] * S + e[1]), (e[0] * S + 14 + e[2])
+                a, b = addr_pair(e, S)
                 ca = len(load_a.get(a % 32, set()) - {a})
                 cb = len(load_b.get(b % 32, set()) - {b}) if both else 0
                 c = ca + cb
@@ -81,31 +94,29 @@ def greedy_seq(rs, K, S, both=True):
                 continue
             e = rem[lane].pop(best)
             out[lane][k] = e
-            a, b = (e[0] * S + e[1]), (e[0] * S + 14 + e[2])
+            a, b = addr_pair(e, S)
             load_a.setdefault(a % 32, set()).add(a)
             load_b.setdefault(b % 32, set()).add(b)
     return out
 
 
 def main():
+    """per image: file order, the sequential greedy, and the builder's order (csrc/kernels_tiled_build.hip tile_bank_order: parallel
+    proposals, TBO_ROUNDS = 4 rounds, a window of TBO_WIN = 4 entries) — every image over the same tiles"""
     n_tiles = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    res = {}
-    for S in (18, 19):
-        base = greedy = free = 0
-        for _ in range(n_tiles):
-            rows = make_tile()
-            for rs, K in slices_of(rows):
+    tiles = [slices_of(make_tile()) for _ in range(n_tiles)]
+    for S in LAYOUTS:
+        base = greedy = built = free = 0
+        for sl in tiles:
+            for rs, K in sl:
                 for h in (0, 32):
                     half = rs[h:h + 32]
                     base += cost_half(pad(half, K), S)
                     greedy += cost_half(greedy_seq(half, K, S), S)
+                    built += cost_half(greedy_par_w(half, K, S, 4, 4), S)
                     free += 2 * K  # conflict-free: one cycle per lookup instruction and half-wave
-        res[S] = (base, greedy, free)
-        print(f"stride {S}: file order {base / free:.2f} cycles per lookup group, sequential greedy {greedy / free:.2f} (conflict-free = 1.00)")
-
-
-if __name__ == "__main__":
-    main()
+        print(f"{layout_name(S)}: file order {base / free:.2f} cycles per lookup group, sequential greedy {greedy / free:.2f}, "
+              f"builder's order {built / free:.2f} (conflict-free = 1.00)")
 
 
 def step_cost(col, S):
@@ -114,7 +125,7 @@ def step_cost(col, S):
     for which in (0, 1):
         per_bank = {}
         for e in col:
-            addr = (NSLOT * S + (0 if which == 0 else 14)) if e is None else (e[0] * S + (e[1] if which == 0 else 14 + e[2]))
+            addr = addr_pair(e, S)[which]
             per_bank.setdefault(addr % 32, set()).add(addr)
         tot += max(len(v) for v in per_bank.values())
     return tot
@@ -149,7 +160,7 @@ def local_search(ent, S, rounds=3):
 
 def main2():
     n_tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    for S in (18, 19):
+    for S in LAYOUTS:
         base = greedy = ls = free = 0
         for _ in range(n_tiles):
             rows = make_tile()
@@ -161,7 +172,7 @@ def main2():
                     greedy += cost_half(g, S)
                     ls += local_search(g, S)
                     free += 2 * K
-        print(f"stride {S}: file order {base / free:.2f}, greedy {greedy / free:.2f}, greedy + swaps {ls / free:.2f}")
+        print(f"{layout_name(S)}: file order {base / free:.2f}, greedy {greedy / free:.2f}, greedy + swaps {ls / free:.2f}")
 
 
 if __name__ == "__main__" and len(sys.argv) > 2:
@@ -182,7 +193,7 @@ def greedy_par(rs, K, S, rounds=4):
             for lane in todo:
                 best, bc = None, None
                 for idx, e in enumerate(rem[lane]):
-                    a, b = (e[0] * S + e[1]), (e[0] * S + 14 + e[2])
+                    a, b = addr_pair(e, S)
                     c = len(load_a.get(a % 32, set()) - {a}) + len(load_b.get(b % 32, set()) - {b})
                     if bc is None or c < bc:
                         best, bc = idx, c
@@ -191,14 +202,14 @@ def greedy_par(rs, K, S, rounds=4):
             won_a, won_b, placed = set(), set(), []
             for lane in todo:  # ascending lane: the lowest proposer of a bank pair wins it
                 e = rem[lane][props[lane]]
-                a, b = (e[0] * S + e[1]) % 32, (e[0] * S + 14 + e[2]) % 32
+                a, b = (x % 32 for x in addr_pair(e, S))
                 if last or (a not in won_a and b not in won_b):
                     won_a.add(a); won_b.add(b)
                     placed.append(lane)
             for lane in placed:
                 e = rem[lane].pop(props[lane])
                 out[lane][k] = e
-                a, b = (e[0] * S + e[1]), (e[0] * S + 14 + e[2])
+                a, b = addr_pair(e, S)
                 load_a.setdefault(a % 32, set()).add(a)
                 load_b.setdefault(b % 32, set()).add(b)
             todo = [l for l in todo if l not in placed]
@@ -209,7 +220,7 @@ def greedy_par(rs, K, S, rounds=4):
 
 def main3():
     n_tiles = 1
-    for S in (18, 19):
+    for S in LAYOUTS:
         for rounds in (2, 4, 8):
             base = par = free = 0
             rows = make_tile()
@@ -219,7 +230,7 @@ def main3():
                     base += cost_half(pad(half, K), S)
                     par += cost_half(greedy_par(half, K, S, rounds), S)
                     free += 2 * K
-            print(f"stride {S} rounds {rounds}: file order {base / free:.2f}, parallel proposals {par / free:.2f}")
+            print(f"{layout_name(S)} rounds {rounds}: file order {base / free:.2f}, parallel proposals {par / free:.2f}")
 
 
 if __name__ == "__main__" and len(sys.argv) > 3:
@@ -237,7 +248,7 @@ def greedy_par_w(rs, K, S, rounds=4, window=99):
             for lane in todo:
                 best, bc = None, None
                 for idx, e in enumerate(rem[lane][:window]):
-                    a, b = (e[0] * S + e[1]) % 32, (e[0] * S + 14 + e[2]) % 32
+                    a, b = (x % 32 for x in addr_pair(e, S))
                     c = load_a.get(a, 0) + load_b.get(b, 0)   # (counts, not distinct addresses: what the GPU version does)
                     if bc is None or c < bc:
                         best, bc = idx, c
@@ -246,14 +257,14 @@ def greedy_par_w(rs, K, S, rounds=4, window=99):
             won_a, won_b, placed = set(), set(), []
             for lane in todo:
                 e = rem[lane][props[lane]]
-                a, b = (e[0] * S + e[1]) % 32, (e[0] * S + 14 + e[2]) % 32
+                a, b = (x % 32 for x in addr_pair(e, S))
                 if last or (a not in won_a and b not in won_b):
                     won_a.add(a); won_b.add(b)
                     placed.append(lane)
             for lane in placed:
                 e = rem[lane].pop(props[lane])
                 out[lane][k] = e
-                a, b = (e[0] * S + e[1]) % 32, (e[0] * S + 14 + e[2]) % 32
+                a, b = (x % 32 for x in addr_pair(e, S))
                 load_a[a] = load_a.get(a, 0) + 1
                 load_b[b] = load_b.get(b, 0) + 1
             todo = [l for l in todo if l not in placed]
@@ -274,8 +285,12 @@ def main4():
                     base += cost_half(pad(half, K), S)
                     par += cost_half(greedy_par_w(half, K, S, rounds, window), S)
                     free += 2 * K
-            print(f"stride {S} rounds {rounds} window {window}: file order {base / free:.2f}, parallel proposals {par / free:.2f}")
+            print(f"{layout_name(S)} rounds {rounds} window {window}: file order {base / free:.2f}, parallel proposals {par / free:.2f}")
 
 
 if __name__ == "__main__" and len(sys.argv) > 4:
     main4()
+
+
+if __name__ == "__main__" and len(sys.argv) <= 2:
+    main()
