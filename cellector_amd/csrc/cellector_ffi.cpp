@@ -507,6 +507,10 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         if (v != 0 && v != 1) return ctx_fail(c, CELLECTOR_EINVAL, "tally_delta must be 0 (recount every iteration) or 1");
         c->tally_delta = v != 0;
     }
+    else if (!strcmp(key, "class_delta")) {
+        if (v != 0 && v != 1) return ctx_fail(c, CELLECTOR_EINVAL, "class_delta must be 0 (recount every refine step) or 1");
+        c->class_delta = v != 0;
+    }
     else if (!strcmp(key, "compact_bits")) {
         if (v != 0 && v != 32) return ctx_fail(c, CELLECTOR_EINVAL, "compact_bits must be 0 (automatic) or 32");
         c->c4_bits_opt = (int)v;
@@ -1388,6 +1392,80 @@ cellector_status cellector_iter_locus_moments(const cellector_ctx *c, double *ex
     for (int k = 0; k < 4; k++)
         if (out[k] && L) CHK(d2h(c, out[k], c->lm_out + (uint64_t)k * L, L * 8));
     return CELLECTOR_OK;
+}
+
+// ---- K-genotype classes: kernels_classes.hip ------------------------------------------------------------
+// what every class call checks before anything is written or launched
+static cellector_status class_call_check(cellector_ctx *c, const char *what, const uint8_t *labels, uint32_t K, const double *scale,
+                                         const double *log_prior)
+{
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    if (!labels) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null labels", what);
+    if (K < 1 || K > 16) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u classes, 1..16 are supported", what, K);
+    bool any = false;
+    for (uint64_t i = 0; i < c->nloc; i++) {
+        if (labels[i] >= K && labels[i] != 255)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: cell %llu has label %u, neither below the %u classes nor 255 (unlabelled)", what,
+                            (unsigned long long)i, (unsigned)labels[i], K);
+        any = any || labels[i] != 255;
+    }
+    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "%s: every cell is unlabelled: all %u classes are dead", what, K);
+    for (uint32_t k = 0; scale && k < K; k++)
+        if (!std::isfinite(scale[k]) || scale[k] < 0.0)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: scale[%u] = %g is not a finite value >= 0", what, k, scale[k]);
+    for (uint32_t k = 0; log_prior && k < K; k++)
+        if (std::isnan(log_prior[k])) return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior[%u] is NaN", what, k);
+    return CELLECTOR_OK;
+}
+
+// step 1 of the class model: the exact integer tallies of a labelling (main.rs:598-611 sums the same counts for two classes)
+cellector_status cellector_class_tallies(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, uint64_t *cells, uint64_t *alt,
+                                         uint64_t *ref)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(class_call_check(c, "class_tallies", labels, n_classes, nullptr, nullptr));
+    SETDEV(c);
+    return classes_tallies_run(c, labels, n_classes, nullptr, cells, alt, ref, nullptr, nullptr);
+}
+
+// step 2: init_alpha_betas (main.rs:598-611) for K classes
+cellector_status cellector_class_alpha_betas(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const double *scale, double *alpha,
+                                             double *beta)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(class_call_check(c, "class_alpha_betas", labels, n_classes, scale, nullptr));
+    SETDEV(c);
+    return classes_tallies_run(c, labels, n_classes, scale, nullptr, nullptr, nullptr, alpha, beta);
+}
+
+// steps 1-6: get_cell_log_likelihoods (main.rs:541-591) per class and the prior / logsumexp chain of main.rs:264-276 over K terms
+cellector_status cellector_class_posteriors(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const double *scale,
+                                            const double *log_prior, const uint8_t *mask, double *ll, double *posterior, uint8_t *best,
+                                            uint64_t *qual)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(class_call_check(c, "class_posteriors", labels, n_classes, scale, log_prior));
+    SETDEV(c);
+    const cellector_status st = classes_run(c, labels, n_classes, scale, log_prior, mask, 0, 1, nullptr, nullptr, ll, posterior, best, qual);
+    if (c->timing) timer_collect(c);
+    return st;
+}
+
+// step 7: the hard-EM loop over steps 1-6 (the outer loop of main.rs:42-46, with K classes in place of the exclusion set)
+cellector_status cellector_refine_classes(cellector_ctx *c, uint8_t *labels, uint32_t n_classes, const double *scale, const double *log_prior,
+                                          const uint8_t *mask, uint32_t max_iter, uint64_t min_loci, cellector_refine_summary *out, double *ll,
+                                          double *posterior, uint64_t *qual)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(class_call_check(c, "refine_classes", labels, n_classes, scale, log_prior));
+    REQUIRE(c, min_loci >= 1, "refine_classes: min_loci must be at least 1");
+    SETDEV(c);
+    const cellector_status st = classes_run(c, labels, n_classes, scale, log_prior, mask, max_iter, min_loci, labels, out, ll, posterior,
+                                            nullptr, qual);
+    if (c->timing) timer_collect(c);
+    return st;
 }
 
 // ---- posteriors ---------------------------------------------------------------------------------------

@@ -132,6 +132,8 @@ struct CtxOptions {
     bool fuse_filter = true;   // option "fuse_filter": an unsharded ctx applies the -80 locus filter inside k_locus_finalize (A/B)
     bool tally_delta = true;    // option "tally_delta": engine 2 keeps the exclusion set's per-(locus, code) counts across
                                 // iterations and updates them from the set's change (0: recounts every iteration; A/B)
+    bool class_delta = true;    // option "class_delta": cellector_refine_classes updates the class tallies from the cells that moved
+                                // between two steps (0: recounts every step; A/B)
     bool bank_order = true;  // option "bank_order": the tile builder orders every row's entries against LDS bank conflicts (tile_bank_order)
     int tile_groups_opt = 0;  // option tile_groups: 0 = chosen per matrix (tile_groups_for), else forced (multiple of 8)
     int tile_sb_opt = 0;  // option tile_sb: 0 = cell blocks per column of the tile kernel chosen per launch (tile_geometry), 2 or 4 forced (tests)
@@ -533,6 +535,14 @@ cellector_status launch_locus_moments(cellector_ctx *c);
 cellector_status locus_moments_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint8_t *flags,
                                    double *exp_min, double *exp_maj, double *var_min, double *var_maj);
 cellector_status locus_total_counts_run(cellector_ctx *c, const uint8_t *flags, uint32_t *out);
+// K-genotype classes (kernels_classes.hip) on one device holding all cells; validated arguments, host arrays, scratch of their own.
+// The tallies / alpha-betas of a labelling (any output may be null) ...
+cellector_status classes_tallies_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const double *scale, uint64_t *cells, uint64_t *alt,
+                                     uint64_t *ref, double *alpha, double *beta);
+// ... and the posterior chain (max_iter 0) or the hard-EM loop over it; labels_out / sum: refine only
+cellector_status classes_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const double *scale, const double *log_prior,
+                             const uint8_t *mask, uint32_t max_iter, uint64_t min_loci, uint8_t *labels_out, cellector_refine_summary *sum,
+                             double *ll, double *posterior, uint8_t *best, uint64_t *qual);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);

@@ -75,6 +75,10 @@ SIGNATURES = {
     "cellector_iter_locus_moments": (_i, [_vp] + [_vp] * 4),
     "cellector_posterior_alpha_betas": (_i, [_vp, _i, _vp, _vp]),
     "cellector_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "cellector_class_tallies": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "cellector_class_alpha_betas": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "cellector_class_posteriors": (_i, [_vp, _vp, C.c_uint32] + [_vp] * 7),
+    "cellector_refine_classes": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _u64] + [_vp] * 4),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -108,6 +112,11 @@ class Resolution(C.Structure):
 class AssignResolution(C.Structure):
     _fields_ = [("n_evaluated", _u64), ("n_labels_changed", _u64), ("n_qual_changed", _u64), ("mode", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class RefineSummary(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("converged", C.c_uint32), ("n_moved_last", _u64), ("n_moved_total", _u64),
+                ("n_recounts", _u64), ("class_cells", _u64 * 16)]
 
 
 class CellectorError(RuntimeError):
@@ -580,6 +589,65 @@ class Cellector:
         p, dp, lmaj, lmin = (np.empty(n, np.float64) for _ in range(4))
         self._ck(self._lib.cellector_posteriors(self.h, _p(p), _p(dp), _p(lmaj), _p(lmin)))
         return dict(posterior=p, doublet_posterior=dp, ll_majority=lmaj, ll_minority=lmin)
+
+    # ---- K-genotype classes: labels 0..K-1 or 255 (unlabelled) per cell; classes.py is the numpy twin
+    def _class_args(self, labels, n_classes, scale=None, log_prior=None, mask=None):
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        if self.dims().total_cells and labels.shape != (self.n_local,):
+            raise ValueError(f"{self.n_local} labels expected, got shape {labels.shape}")
+        K, L = int(n_classes), self.dims().loci_used
+        vec = []
+        for name, v in (("scale", scale), ("log_prior", log_prior)):
+            v = None if v is None else np.ascontiguousarray(v, np.float64)
+            if v is not None and v.shape != (K,):
+                raise ValueError(f"{name}: {K} values expected, got shape {v.shape}")
+            vec.append(v)
+        mask = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask is not None and mask.shape != (L,):
+            raise ValueError(f"mask: {L} entries expected, got shape {mask.shape}")
+        return labels, max(K, 0), vec[0], vec[1], mask
+
+    def class_tallies(self, labels, n_classes):
+        """(cells [K], alt [K, L], ref [K, L]) uint64: the per-class per-locus allele tallies of a labelling
+        (cellector_class_tallies); unlabelled cells (255) are in none"""
+        labels, K, _, _, _ = self._class_args(labels, n_classes)
+        Ka, L = min(K, 16), self.dims().loci_used
+        cells, alt, ref = np.zeros(Ka, np.uint64), np.zeros((Ka, L), np.uint64), np.zeros((Ka, L), np.uint64)
+        self._ck(self._lib.cellector_class_tallies(self.h, _p(labels), K, _p(cells), _p(alt), _p(ref)))
+        return cells, alt, ref
+
+    def class_alpha_betas(self, labels, n_classes, scale=None):
+        """(alpha [K, L], beta [K, L]): alt_k * scale_k + 1, ref_k * scale_k + 1 (cellector_class_alpha_betas)"""
+        labels, K, scale, _, _ = self._class_args(labels, n_classes, scale)
+        Ka, L = min(K, 16), self.dims().loci_used
+        a, b = np.zeros((Ka, L), np.float64), np.zeros((Ka, L), np.float64)
+        self._ck(self._lib.cellector_class_alpha_betas(self.h, _p(labels), K, _p(scale), _p(a), _p(b)))
+        return a, b
+
+    def class_posteriors(self, labels, n_classes, scale=None, log_prior=None, mask=None):
+        """Every cell against the K classes of a labelling (cellector_class_posteriors): dict of ll [K, cells], posterior
+        [K, cells], best [cells] uint8, qual [cells] uint64.  mask None = all loci used, as in the reference's posterior phase;
+        log_prior None = log((n_k + 1) / (labelled cells + live classes)).  A class without a cell is dead: ll -inf, posterior 0."""
+        labels, K, scale, log_prior, mask = self._class_args(labels, n_classes, scale, log_prior, mask)
+        Ka, n = min(K, 16), (self.n_local if self.dims().total_cells else 0)  # (before a load the library refuses the call itself)
+        ll, post = np.zeros((Ka, n), np.float64), np.zeros((Ka, n), np.float64)
+        best, qual = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+        self._ck(self._lib.cellector_class_posteriors(self.h, _p(labels), K, _p(scale), _p(log_prior), _p(mask), _p(ll), _p(post),
+                                                      _p(best), _p(qual)))
+        return dict(ll=ll, posterior=post, best=best, qual=qual)
+
+    def refine_classes(self, labels, n_classes, scale=None, log_prior=None, mask=None, max_iter=100, min_loci=1):
+        """Hard EM over class_posteriors (cellector_refine_classes): every labelled cell with at least min_loci entries at used
+        loci moves to its best class until nothing moves or max_iter steps have run.  Returns a dict: labels (the result; the
+        argument is not changed), summary (RefineSummary) and ll / posterior / qual of the last step."""
+        labels, K, scale, log_prior, mask = self._class_args(labels, n_classes, scale, log_prior, mask)
+        labels = labels.copy()
+        Ka, n = min(K, 16), (self.n_local if self.dims().total_cells else 0)  # (before a load the library refuses the call itself)
+        ll, post, qual = np.zeros((Ka, n), np.float64), np.zeros((Ka, n), np.float64), np.zeros(n, np.uint64)
+        s = RefineSummary()
+        self._ck(self._lib.cellector_refine_classes(self.h, _p(labels), K, _p(scale), _p(log_prior), _p(mask), int(max_iter),
+                                                    int(min_loci), C.byref(s), _p(ll), _p(post), _p(qual)))
+        return dict(labels=labels, summary=s, ll=ll, posterior=post, qual=qual)
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

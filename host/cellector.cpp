@@ -189,6 +189,9 @@ struct Params {
     // combiner/src/main.rs:43 announces), thinned with their own rate and the shared --seed
     std::optional<std::string> doublets;
     double doublet_downsample_rate = 0.0;
+    // extension: K-genotype class scoring after the ordinary run (cellector_class_posteriors / cellector_refine_classes; one GPU)
+    std::optional<std::string> classes;               // barcode<TAB>label, at most 16 distinct labels
+    uint64_t refine_classes = 0;                       // hard-EM steps at most (0: score the given labelling only)
 };
 
 const char *USAGE =
@@ -275,7 +278,20 @@ const char *USAGE =
     "                                                                       gt.tsv is the run's ground truth (not in the reference; one GPU)\n"
     "        --doublet_downsample_rate <r>                                  remove every read of a parent with probability r in [0, 1] on its\n"
     "                                                                       way into a doublet, independently per pair and parent (default 0;\n"
-    "                                                                       --seed is shared)\n";
+    "                                                                       --seed is shared)\n"
+    "        --classes <file>                                               after the ordinary run, score every cell against the genotype\n"
+    "                                                                       classes of this file: barcode<TAB>label per line, at most 16\n"
+    "                                                                       distinct labels (numbered by first appearance); a barcode not\n"
+    "                                                                       listed is unlabelled.  Writes <output_directory>/\n"
+    "                                                                       cellector_classes.tsv: barcode, input label, class_assignment\n"
+    "                                                                       (the best class' label when its posterior exceeds\n"
+    "                                                                       --posterior_threshold and the cell has at least\n"
+    "                                                                       --min_loci_for_assignment entries, else unassigned), qual, the\n"
+    "                                                                       K log-likelihoods, the K posteriors.  No other output changes\n"
+    "                                                                       (not in the reference; one GPU)\n"
+    "        --refine_classes <max_iter>                                    with --classes: move every cell to its best class and score\n"
+    "                                                                       again, until no cell moves or max_iter steps have run (default\n"
+    "                                                                       0); one stderr line per step: cells moved, class sizes\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -302,7 +318,7 @@ Params load_params(int argc, char **argv)
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
-                                  "mix_cells", "doublets", "doublet_downsample_rate"};
+                                  "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -385,6 +401,12 @@ Params load_params(int argc, char **argv)
         p.downsample_rate = r;
     }
     if (got.count("seed")) p.seed = parse_usize("seed", got["seed"]);
+    if (got.count("classes")) p.classes = got["classes"];
+    if (got.count("refine_classes")) {
+        p.refine_classes = parse_usize("refine_classes", got["refine_classes"]);
+        if (!p.classes) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
+        if (p.refine_classes > 0xffffffffull) die(1, "error: Invalid value '" + got["refine_classes"] + "' for '--refine_classes <max_iter>'");
+    }
     if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
     if (got.count("mix_ref")) p.mix_ref = got["mix_ref"];
     if (got.count("mix_barcodes")) p.mix_barcodes = got["mix_barcodes"];
@@ -702,6 +724,29 @@ int main(int argc, char **argv)
     // --cell_detail: the cells whose per-locus records are written after the posterior phase
     std::vector<uint32_t> detail_cells;
     if (params.cell_detail) detail_cells = read_barcode_list("cell_detail", *params.cell_detail);
+
+    // --classes: barcode<TAB>label, parsed like load_ground_truth (load_data.rs:85-107): a line without exactly two columns is an
+    // error, a barcode the run does not have is ignored, a later line of a barcode replaces an earlier one.  Labels are numbered by
+    // first appearance; a cell no line names is unlabelled (255)
+    std::vector<uint8_t> class_label;
+    std::vector<std::string> class_names;
+    if (params.classes) {
+        class_label.assign(n_distinct, 255);
+        Lines in(*params.classes);
+        std::string line;
+        while (in.next(line)) {
+            auto cols = split(line, '\t');
+            if (cols.size() != 2) die(EXIT_PANIC, "Invalid line format: " + line + "\nThe correct format is: barcode\tlabel");
+            size_t k = std::find(class_names.begin(), class_names.end(), cols[1]) - class_names.begin();
+            if (k == class_names.size()) {
+                if (k == 16) die(1, "error: --classes " + *params.classes + ": more than 16 distinct labels ('" + cols[1] + "' is the 17th)");
+                class_names.push_back(cols[1]);
+            }
+            const size_t cell = barcode_to_cell(cols[0]);
+            if (cell != SIZE_MAX && cell < class_label.size()) class_label[cell] = (uint8_t)k;
+        }
+        if (class_names.empty()) die(1, "error: --classes " + *params.classes + ": no label");
+    }
 
     // CELLECTOR_TIMING=1: phase wall times on stderr (not part of the reference's output)
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;
@@ -1127,6 +1172,40 @@ int main(int argc, char **argv)
         }
         sb += std::string(xoffset, ' ') + "|" + std::string(header.size() - 1, '-') + "|\n";
         printf("\n\n%s\n", sb.c_str());
+    }
+    // --classes / --refine_classes: the K-class posteriors of every cell under the file's labelling, refined one step at a time so
+    // that every step gets its stderr line; then the scoring of the labelling in force
+    if (params.classes) {
+        const uint32_t K = (uint32_t)class_names.size();
+        std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), in_lab = lab, best(N);
+        for (uint64_t it = 0; it < params.refine_classes; it++) {
+            cellector_refine_summary rs;
+            g.ck(cellector_refine_classes(g.c, lab.data(), K, nullptr, nullptr, nullptr, 1, 1, &rs, nullptr, nullptr, nullptr), "refine_classes");
+            std::string msg = "refine_classes step " + std::to_string(it + 1) + ": moved " + std::to_string(rs.n_moved_last) + ", class sizes";
+            for (uint32_t k = 0; k < K; k++) msg += " " + class_names[k] + "=" + std::to_string(rs.class_cells[k]);
+            fprintf(stderr, "%s\n", msg.c_str());
+            if (rs.converged) break;
+        }
+        std::vector<double> cll((uint64_t)K * N), cpost((uint64_t)K * N);
+        std::vector<uint64_t> cqual(N);
+        g.ck(cellector_class_posteriors(g.c, lab.data(), K, nullptr, nullptr, nullptr, cll.data(), cpost.data(), best.data(), cqual.data()),
+             "class_posteriors");
+        FILE *f = create(od + "/cellector_classes.tsv");
+        std::string head = "barcode\tinput_label\tclass_assignment\tqual";
+        for (uint32_t k = 0; k < K; k++) head += "\tlog_likelihood_" + class_names[k];
+        for (uint32_t k = 0; k < K; k++) head += "\tposterior_" + class_names[k];
+        head += '\n';
+        fputs(head.c_str(), f);
+        write_rows(f, N, [&](uint64_t c, std::string &o) {
+            const bool assigned = cpost[(uint64_t)best[c] * N + c] > params.posterior_threshold && entries_per_cell[c] >= params.min_loci_used;
+            o += barcodes[c]; o += '\t'; o += in_lab[c] == 255 ? "na" : class_names[in_lab[c]].c_str(); o += '\t';
+            o += assigned ? class_names[best[c]].c_str() : "unassigned"; o += '\t'; put(o, cqual[c]);
+            for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, cll[(uint64_t)k * N + c]); }
+            for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, cpost[(uint64_t)k * N + c]); }
+            o += '\n';
+        });
+        fclose(f);
+        lap("cellector_classes.tsv");
     }
     // Every output file is closed: leave without tearing the context down.  Handing ~150 GB of device memory back block
     // by block (and destroying the host vectors) was half a second of the 1M x 200k run; the driver reclaims a dead

@@ -88,6 +88,9 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * "tally_delta" (engine 2, default 1: those counts are kept from one iteration to the next and updated with the cells
  * whose exclusion changed — nothing to count once the set stops moving; the device recounts the whole set when the change
  * is larger than the new set, and after a reload or an engine switch; 0 = recount every iteration; bit-identical — A/B),
+ * "class_delta" (engines 1 and 2, default 1: cellector_refine_classes updates the per-class tallies between two steps from the
+ * rows of the cells that moved, and recounts when more cells moved than a recount would walk; 0 = recount every step;
+ * the same integers either way — A/B),
  * "overlap" (engine 2, default 1: the kernels of the few entries with alt+ref = 0 or > 4 run on a side
  * stream beside the table-lookup kernel; 2 = their locus-side part only after that kernel; 0 = everything
  * in one stream; same results to the bit),
@@ -596,6 +599,66 @@ typedef struct {
 cellector_status cellector_assign_resolution(const cellector_ctx *ctx, cellector_assign_resolution_t *out);
 /* ... and which cells it evaluated: n_evaluated local cell indices (order unspecified); nothing when it was off. */
 cellector_status cellector_assign_resolved_cells(const cellector_ctx *ctx, uint32_t *ids /*[n_evaluated]*/);
+
+/* ---- K-genotype classes: class tallies, posteriors, refine ------------------------------------------
+ * calculate_posteriors (main.rs:228-280) is hard-wired to two classes and their doublet.  These calls score every cell of the
+ * loaded matrix against K classes given as labels: cellector's own beta-binomial (init_alpha_betas, main.rs:598-611;
+ * get_cell_log_likelihoods, main.rs:541-591; the prior / logsumexp chain of main.rs:264-276) generalised from {minority,
+ * majority} to K.  The labels may come from peels (cellector_restage + cellector_cell_origin), from cellector_cell_source, from
+ * cell hashing or from a clustering with k > 2.  Doublet classes are NOT formed: they need K (K - 1) / 2 further distributions
+ * and a prior nobody has argued for.
+ *   labels [cells]: 0..K-1, or 255 = unlabelled; 1 <= K <= 16.  scale [K] or NULL = all 1.0; log_prior [K] or NULL = default;
+ *   mask [L] or NULL = all L loci used, which is what the reference's posterior phase uses (main.rs:255, :303), not the loop's
+ *   filtered mask.
+ *   1 tallies: alt_k[l] / ref_k[l] = the sums of the allele counts of the entries of class k's cells at used-locus index l, u64; a
+ *     repeated (locus, cell) line counts each time; tallies ignore the mask.  n_k = cells labelled k.  Unlabelled cells are in no
+ *     tally: over the classes and the unlabelled cells the tallies add up to cellector_locus_counts.
+ *   2 distributions (init_alpha_betas, main.rs:598-611): alpha_k[l] = (double)alt_k[l] * scale_k + 1.0, beta_k[l] likewise from
+ *     ref_k: a rounded product and a rounded sum.  K = 2, class 0 the exclusion set, scale = {1, max(mf0, 0.01)}: the bits of
+ *     cellector_posterior_alpha_betas(which = 0 / 1).
+ *   3 ll_k[c] = get_cell_log_likelihoods (main.rs:541-591) under (alpha_k, beta_k, mask): the cell pass' product-form log-pmf
+ *     summed over the cell's entries at used loci.  A cell's own counts are inside its own class's tallies.
+ *   4 a class with n_k == 0 is dead: ll column -inf, posterior column 0, no part in 5-7, attracts no cell.  All classes dead
+ *     (every cell unlabelled) is CELLECTOR_EINVAL.
+ *   5 priors: log_prior as given, else lp_k = log((n_k + 1) / (N_lab + K_live)) with the host's log; N_lab = labelled cells.
+ *   6 posterior (main.rs:264-276 over K terms), live classes in ascending k: x_k = lp_k + ll_k, m = max x_k, den = m +
+ *     log(sum_k exp(x_k - m)), posterior_k = exp(x_k - den), best = the smallest k attaining m, qual = (uint64) min(-10 log10(rest),
+ *     255) with rest = sum_{k != best} exp(x_k - den) (rest == 0: 255).  A cell with no entry at a used locus gets the prior.
+ *   7 refine (hard EM), one step: 1-6 from the current labels; a labelled cell with at least min_loci (>= 1) entries at used loci
+ *     (a repeated pair counts as often as it occurs, like loci_used_per_cell) takes the label best, every other cell keeps its
+ *     label, 255 included; n_moved = labels changed.  Repeated until n_moved == 0 (converged) or max_iter steps have run;
+ *     max_iter == 0 does 1-6 only.  scale and a caller's log_prior stay fixed; default priors and dead classes follow the
+ *     current labels.  Between two steps the tallies are updated from the moved cells' rows (option class_delta).
+ * Needs a loaded matrix and no iteration in flight; engines 1 and 2; a single-device ctx that holds all cells (else
+ * CELLECTOR_EINVAL, like cellector_locus_moments).  CELLECTOR_EINVAL with a message, nothing written or launched, also for K
+ * outside 1..16, a label that is neither < K nor 255 (the message names the first such cell), a non-finite or negative scale, a
+ * NaN prior, min_loci == 0, NULL labels.  Device scratch is allocated before anything is written: on CELLECTOR_ENOMEM the ctx and
+ * the caller's labels are as they were.
+ * The calls never touch the EM state: the exclusion set, the loop's mask, the kept counts of option tally_delta, the per-cell
+ * masked counts and the iteration number all stay, and an EM loop interrupted by a class call continues with the same bits.
+ * cellector_class_posteriors and cellector_refine_classes overwrite exactly what cellector_cell_log_likelihoods overwrites (the
+ * tables and the per-cell outputs of the last pass; the alpha/beta of the next em_begin are formed again from the state) and
+ * invalidate the same caches (the tables built ahead by em_finish, the zeroed column counters). */
+cellector_status cellector_class_tallies(cellector_ctx *ctx, const uint8_t *labels /*[cells]*/, uint32_t n_classes,
+                                         uint64_t *cells /*[K]*/, uint64_t *alt /*[K][L]*/,
+                                         uint64_t *ref /*[K][L]*/); /* any output may be NULL */
+cellector_status cellector_class_alpha_betas(cellector_ctx *ctx, const uint8_t *labels, uint32_t n_classes,
+                                             const double *scale, double *alpha /*[K][L]*/, double *beta /*[K][L]*/);
+cellector_status cellector_class_posteriors(cellector_ctx *ctx, const uint8_t *labels, uint32_t n_classes, const double *scale,
+                                            const double *log_prior, const uint8_t *mask, double *ll /*[K][cells]*/,
+                                            double *posterior /*[K][cells]*/, uint8_t *best /*[cells]*/,
+                                            uint64_t *qual /*[cells]*/); /* any output may be NULL */
+typedef struct {
+    uint32_t iterations, converged;  /* steps run; 1 = the last one moved no cell                                  */
+    uint64_t n_moved_last, n_moved_total;
+    uint64_t n_recounts;             /* steps whose tallies were counted from scratch (the others: delta updates)  */
+    uint64_t class_cells[16];        /* cells per class under the returned labels                                  */
+} cellector_refine_summary;
+/* labels: in = the start, out = the result; ll / posterior / qual: of the last step (under the labels that step started from) */
+cellector_status cellector_refine_classes(cellector_ctx *ctx, uint8_t *labels, uint32_t n_classes, const double *scale,
+                                          const double *log_prior, const uint8_t *mask, uint32_t max_iter, uint64_t min_loci,
+                                          cellector_refine_summary *out, double *ll, double *posterior,
+                                          uint64_t *qual /*any output may be NULL*/);
 
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
