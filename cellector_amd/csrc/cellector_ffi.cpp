@@ -1468,6 +1468,71 @@ cellector_status cellector_refine_classes(cellector_ctx *c, uint8_t *labels, uin
     return st;
 }
 
+// ---- doublet classes over the K classes: the second half of kernels_classes.hip ------------------------------
+// what the doublet calls check on top of class_call_check: a live class must remain once the held cells are out
+static cellector_status doublet_call_check(cellector_ctx *c, const char *what, const uint8_t *labels, const uint8_t *held, uint32_t K,
+                                           const double *scale, const double *pair_scale, const double *log_prior,
+                                           const double *log_pair_prior)
+{
+    CHK(class_call_check(c, what, labels, K, scale, log_prior));
+    bool any = !held;
+    for (uint64_t i = 0; held && !any && i < c->nloc; i++) any = labels[i] != 255 && !held[i];
+    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "%s: every labelled cell is held: all %u classes are dead", what, K);
+    for (uint32_t k = 0; pair_scale && k < K; k++)
+        if (!std::isfinite(pair_scale[k]) || pair_scale[k] < 0.0)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: pair_scale[%u] = %g is not a finite value >= 0", what, k, pair_scale[k]);
+    for (uint32_t p = 0; log_pair_prior && p < K * (K - 1) / 2; p++)
+        if (std::isnan(log_pair_prior[p])) return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_pair_prior[%u] is NaN", what, p);
+    return CELLECTOR_OK;
+}
+
+// step 3 of the doublet model: the P pair distributions (main.rs:245-246 for K = 2)
+cellector_status cellector_class_pair_alpha_betas(cellector_ctx *c, const uint8_t *labels, const uint8_t *held, uint32_t n_classes,
+                                                  const double *pair_scale, double *alpha, double *beta)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(doublet_call_check(c, "class_pair_alpha_betas", labels, held, n_classes, nullptr, pair_scale, nullptr, nullptr));
+    SETDEV(c);
+    return class_pairs_run(c, labels, held, n_classes, pair_scale, alpha, beta);
+}
+
+// steps 1-6: the K singlets and the P pairs in one chain (calculate_posteriors, main.rs:228-280, is K = 2), and the call of
+// main.rs:150
+cellector_status cellector_class_doublets(cellector_ctx *c, const uint8_t *labels, const uint8_t *held, uint32_t n_classes,
+                                          const double *scale, const double *pair_scale, const double *log_prior,
+                                          const double *log_pair_prior, const uint8_t *mask, double *ll, double *ll_pair, double *posterior,
+                                          double *doublet_posterior, uint8_t *best, uint8_t *best_pair, uint8_t *call, uint64_t *qual)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(doublet_call_check(c, "class_doublets", labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior));
+    SETDEV(c);
+    const cellector_status st = class_doublets_run(c, labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior, mask, 0.5, 0, 1,
+                                                   nullptr, nullptr, nullptr, ll, ll_pair, posterior, doublet_posterior, best, best_pair, call,
+                                                   qual);
+    if (c->timing) timer_collect(c);
+    return st;
+}
+
+// step 7: the held-out refine
+cellector_status cellector_refine_class_doublets(cellector_ctx *c, uint8_t *labels, uint8_t *held, uint32_t n_classes, const double *scale,
+                                                 const double *pair_scale, const double *log_prior, const double *log_pair_prior,
+                                                 const uint8_t *mask, double doublet_threshold, uint32_t max_iter, uint64_t min_loci,
+                                                 cellector_refine_doublets_summary *out, double *ll, double *ll_pair, double *posterior,
+                                                 double *doublet_posterior, uint8_t *best_pair, uint64_t *qual)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(doublet_call_check(c, "refine_class_doublets", labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior));
+    REQUIRE(c, min_loci >= 1, "refine_class_doublets: min_loci must be at least 1");
+    if (!(doublet_threshold >= 0.0 && doublet_threshold <= 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "refine_class_doublets: doublet_threshold = %g is not within [0, 1]", doublet_threshold);
+    SETDEV(c);
+    const cellector_status st = class_doublets_run(c, labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior, mask,
+                                                   doublet_threshold, max_iter, min_loci, labels, held, out, ll, ll_pair, posterior,
+                                                   doublet_posterior, nullptr, best_pair, nullptr, qual);
+    if (c->timing) timer_collect(c);
+    return st;
+}
+
 // ---- posteriors ---------------------------------------------------------------------------------------
 // the minority fraction and the three log priors of calculate_posteriors, from the current exclusion set
 struct PosteriorPriors { double mf0, lp_min, lp_maj, lp_dbl; };

@@ -543,6 +543,15 @@ cellector_status classes_tallies_run(cellector_ctx *c, const uint8_t *labels, ui
 cellector_status classes_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const double *scale, const double *log_prior,
                              const uint8_t *mask, uint32_t max_iter, uint64_t min_loci, uint8_t *labels_out, cellector_refine_summary *sum,
                              double *ll, double *posterior, uint8_t *best, uint64_t *qual);
+// ... and with the doublet classes of the K (K - 1) / 2 pairs: the pair distributions of a (labels, held) state, and the chain with
+// the call (max_iter 0) or the held-out refine; labels_out / held_out / sum: refine only
+cellector_status class_pairs_run(cellector_ctx *c, const uint8_t *labels, const uint8_t *held, uint32_t K, const double *pair_scale,
+                                 double *alpha, double *beta);
+cellector_status class_doublets_run(cellector_ctx *c, const uint8_t *labels, const uint8_t *held, uint32_t K, const double *scale,
+                                    const double *pair_scale, const double *log_prior, const double *log_pair_prior, const uint8_t *mask,
+                                    double threshold, uint32_t max_iter, uint64_t min_loci, uint8_t *labels_out, uint8_t *held_out,
+                                    cellector_refine_doublets_summary *sum, double *ll, double *ll_pair, double *posterior,
+                                    double *doublet_posterior, uint8_t *best, uint8_t *best_pair, uint8_t *call, uint64_t *qual);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);

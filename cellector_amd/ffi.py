@@ -79,6 +79,10 @@ SIGNATURES = {
     "cellector_class_alpha_betas": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "cellector_class_posteriors": (_i, [_vp, _vp, C.c_uint32] + [_vp] * 7),
     "cellector_refine_classes": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _u64] + [_vp] * 4),
+    "cellector_class_pair_alpha_betas": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "cellector_class_doublets": (_i, [_vp, _vp, _vp, C.c_uint32] + [_vp] * 13),
+    "cellector_refine_class_doublets": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint32, _u64]
+                                        + [_vp] * 7),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -117,6 +121,11 @@ class AssignResolution(C.Structure):
 class RefineSummary(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("converged", C.c_uint32), ("n_moved_last", _u64), ("n_moved_total", _u64),
                 ("n_recounts", _u64), ("class_cells", _u64 * 16)]
+
+
+class RefineDoubletsSummary(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("converged", C.c_uint32), ("n_moved_last", _u64), ("n_moved_total", _u64),
+                ("n_recounts", _u64), ("class_cells", _u64 * 16), ("n_held", _u64)]
 
 
 class CellectorError(RuntimeError):
@@ -648,6 +657,65 @@ class Cellector:
         self._ck(self._lib.cellector_refine_classes(self.h, _p(labels), K, _p(scale), _p(log_prior), _p(mask), int(max_iter),
                                                     int(min_loci), C.byref(s), _p(ll), _p(post), _p(qual)))
         return dict(labels=labels, summary=s, ll=ll, posterior=post, qual=qual)
+
+    # ---- ... and the doublet classes of their K (K - 1) / 2 pairs; held [cells]: non-zero = kept out of every tally
+    def _doublet_args(self, labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior, mask):
+        labels, K, scale, log_prior, mask = self._class_args(labels, n_classes, scale, log_prior, mask)
+        held = None if held is None else np.ascontiguousarray(np.asarray(held) != 0, dtype=np.uint8)
+        if held is not None and held.shape != labels.shape:
+            raise ValueError(f"held: shape {labels.shape} expected, got {held.shape}")
+        Ka = min(K, 16)
+        P = Ka * (Ka - 1) // 2
+        pair_scale = None if pair_scale is None else np.ascontiguousarray(pair_scale, np.float64)
+        if pair_scale is not None and pair_scale.shape != (K,):
+            raise ValueError(f"pair_scale: {K} values expected, got shape {pair_scale.shape}")
+        log_pair_prior = None if log_pair_prior is None else np.ascontiguousarray(log_pair_prior, np.float64)
+        if log_pair_prior is not None and log_pair_prior.shape != (P,):
+            raise ValueError(f"log_pair_prior: {P} values expected, got shape {log_pair_prior.shape}")
+        return labels, held, K, Ka, P, scale, pair_scale, log_prior, log_pair_prior, mask
+
+    def class_pair_alpha_betas(self, labels, n_classes, held=None, pair_scale=None):
+        """dict of alpha [P, L], beta [P, L]: the doublet distributions of the P = K (K - 1) / 2 pairs, row p(a, b) = a (2K - a - 1)
+        / 2 + (b - a - 1) (cellector_class_pair_alpha_betas); pair_scale None = every class at the weight of the smallest"""
+        labels, held, K, Ka, P, _, pair_scale, _, _, _ = self._doublet_args(labels, held, n_classes, None, pair_scale, None, None, None)
+        L = self.dims().loci_used
+        a, b = np.zeros((P, L), np.float64), np.zeros((P, L), np.float64)
+        self._ck(self._lib.cellector_class_pair_alpha_betas(self.h, _p(labels), _p(held), K, _p(pair_scale), _p(a), _p(b)))
+        return dict(alpha=a, beta=b)
+
+    def class_doublets(self, labels, n_classes, held=None, scale=None, pair_scale=None, log_prior=None, log_pair_prior=None, mask=None):
+        """Every cell against the K classes of a labelling and the P doublet classes of their pairs (cellector_class_doublets):
+        dict of ll [K, cells], ll_pair [P, cells], posterior [K, cells], doublet_posterior, best, best_pair [cells, 2] (255, 255
+        without a live pair), call (1 = doublet_posterior > 0.5) and qual."""
+        labels, held, K, Ka, P, scale, pair_scale, log_prior, log_pair_prior, mask = self._doublet_args(
+            labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior, mask)
+        n = self.n_local if self.dims().total_cells else 0  # (before a load the library refuses the call itself)
+        ll, llp, post = np.zeros((Ka, n), np.float64), np.zeros((P, n), np.float64), np.zeros((Ka, n), np.float64)
+        dp, best, bp = np.zeros(n, np.float64), np.zeros(n, np.uint8), np.zeros((n, 2), np.uint8)
+        call, qual = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+        self._ck(self._lib.cellector_class_doublets(self.h, _p(labels), _p(held), K, _p(scale), _p(pair_scale), _p(log_prior),
+                                                    _p(log_pair_prior), _p(mask), _p(ll), _p(llp), _p(post), _p(dp), _p(best), _p(bp),
+                                                    _p(call), _p(qual)))
+        return dict(ll=ll, ll_pair=llp, posterior=post, doublet_posterior=dp, best=best, best_pair=bp, call=call, qual=qual)
+
+    def refine_class_doublets(self, labels, n_classes, held=None, scale=None, pair_scale=None, log_prior=None, log_pair_prior=None,
+                              mask=None, doublet_threshold=0.5, max_iter=100, min_loci=1):
+        """The held-out refine (cellector_refine_class_doublets): every labelled cell with at least min_loci entries at used loci
+        moves to its best class and is held out of the tallies while its doublet posterior exceeds doublet_threshold, until
+        nothing changes or max_iter steps have run.  Returns a dict: labels and held (the result; the arguments are not changed),
+        summary (RefineDoubletsSummary) and ll / ll_pair / posterior / doublet_posterior / best_pair / qual of the last step."""
+        labels, held, K, Ka, P, scale, pair_scale, log_prior, log_pair_prior, mask = self._doublet_args(
+            labels, held, n_classes, scale, pair_scale, log_prior, log_pair_prior, mask)
+        labels = labels.copy()
+        held = np.zeros(labels.shape, np.uint8) if held is None else held.copy()
+        n = self.n_local if self.dims().total_cells else 0  # (before a load the library refuses the call itself)
+        ll, llp, post = np.zeros((Ka, n), np.float64), np.zeros((P, n), np.float64), np.zeros((Ka, n), np.float64)
+        dp, bp, qual = np.zeros(n, np.float64), np.zeros((n, 2), np.uint8), np.zeros(n, np.uint64)
+        s = RefineDoubletsSummary()
+        self._ck(self._lib.cellector_refine_class_doublets(self.h, _p(labels), _p(held), K, _p(scale), _p(pair_scale), _p(log_prior),
+                                                           _p(log_pair_prior), _p(mask), float(doublet_threshold), int(max_iter),
+                                                           int(min_loci), C.byref(s), _p(ll), _p(llp), _p(post), _p(dp), _p(bp), _p(qual)))
+        return dict(labels=labels, held=held, summary=s, ll=ll, ll_pair=llp, posterior=post, doublet_posterior=dp, best_pair=bp, qual=qual)
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

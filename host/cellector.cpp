@@ -192,6 +192,7 @@ struct Params {
     // extension: K-genotype class scoring after the ordinary run (cellector_class_posteriors / cellector_refine_classes; one GPU)
     std::optional<std::string> classes;               // barcode<TAB>label, at most 16 distinct labels
     uint64_t refine_classes = 0;                       // hard-EM steps at most (0: score the given labelling only)
+    bool class_doublets = false;                       // the pairs' doublet classes beside them (cellector_class_doublets)
 };
 
 const char *USAGE =
@@ -291,7 +292,13 @@ const char *USAGE =
     "                                                                       (not in the reference; one GPU)\n"
     "        --refine_classes <max_iter>                                    with --classes: move every cell to its best class and score\n"
     "                                                                       again, until no cell moves or max_iter steps have run (default\n"
-    "                                                                       0); one stderr line per step: cells moved, class sizes\n";
+    "                                                                       0); one stderr line per step: cells moved, class sizes\n"
+    "        --class_doublets <true|false>                                  with --classes: score the doublet class of every pair of classes\n"
+    "                                                                       beside them; class_assignment is doublet where the doublet\n"
+    "                                                                       posterior exceeds 0.5, cellector_classes.tsv gains the columns\n"
+    "                                                                       doublet_posterior and doublet_pair (<labelA>+<labelB> or na), and\n"
+    "                                                                       --refine_classes holds the called doublets out of the classes'\n"
+    "                                                                       tallies (its stderr line gains held=<n>) (default false)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -318,7 +325,8 @@ Params load_params(int argc, char **argv)
                                   "expected_percent_minority", "min_loci_for_assignment", "device", "devices",
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
-                                  "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes"};
+                                  "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
+                                  "class_doublets"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -402,6 +410,12 @@ Params load_params(int argc, char **argv)
     }
     if (got.count("seed")) p.seed = parse_usize("seed", got["seed"]);
     if (got.count("classes")) p.classes = got["classes"];
+    if (got.count("class_doublets")) {
+        const std::string &v = got["class_doublets"];
+        if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --class_doublets: expected true or false");
+        p.class_doublets = v == "true";
+        if (p.class_doublets && !p.classes) die(1, "error: The argument '--class_doublets true' requires '--classes <file>'");
+    }
     if (got.count("refine_classes")) {
         p.refine_classes = parse_usize("refine_classes", got["refine_classes"]);
         if (!p.classes) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
@@ -1178,30 +1192,56 @@ int main(int argc, char **argv)
     if (params.classes) {
         const uint32_t K = (uint32_t)class_names.size();
         std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), in_lab = lab, best(N);
+        const bool dbl = params.class_doublets;
+        std::vector<uint8_t> held(dbl ? N : 0, 0), call(dbl ? N : 0), bpair(dbl ? 2 * N : 0);
+        std::vector<double> dpost(dbl ? N : 0);
         for (uint64_t it = 0; it < params.refine_classes; it++) {
             cellector_refine_summary rs;
-            g.ck(cellector_refine_classes(g.c, lab.data(), K, nullptr, nullptr, nullptr, 1, 1, &rs, nullptr, nullptr, nullptr), "refine_classes");
+            std::string tail;
+            if (dbl) {  // the held-out refine: the called doublets (doublet posterior > 0.5) stay out of every tally
+                cellector_refine_doublets_summary ds;
+                g.ck(cellector_refine_class_doublets(g.c, lab.data(), held.data(), K, nullptr, nullptr, nullptr, nullptr, nullptr, 0.5, 1, 1, &ds,
+                                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "refine_class_doublets");
+                rs.n_moved_last = ds.n_moved_last;
+                rs.converged = ds.converged;
+                for (uint32_t k = 0; k < K; k++) rs.class_cells[k] = ds.class_cells[k];
+                tail = " held=" + std::to_string(ds.n_held);
+            } else
+                g.ck(cellector_refine_classes(g.c, lab.data(), K, nullptr, nullptr, nullptr, 1, 1, &rs, nullptr, nullptr, nullptr), "refine_classes");
             std::string msg = "refine_classes step " + std::to_string(it + 1) + ": moved " + std::to_string(rs.n_moved_last) + ", class sizes";
             for (uint32_t k = 0; k < K; k++) msg += " " + class_names[k] + "=" + std::to_string(rs.class_cells[k]);
+            msg += tail;
             fprintf(stderr, "%s\n", msg.c_str());
             if (rs.converged) break;
         }
         std::vector<double> cll((uint64_t)K * N), cpost((uint64_t)K * N);
         std::vector<uint64_t> cqual(N);
-        g.ck(cellector_class_posteriors(g.c, lab.data(), K, nullptr, nullptr, nullptr, cll.data(), cpost.data(), best.data(), cqual.data()),
-             "class_posteriors");
+        if (dbl)
+            g.ck(cellector_class_doublets(g.c, lab.data(), held.data(), K, nullptr, nullptr, nullptr, nullptr, nullptr, cll.data(), nullptr,
+                                          cpost.data(), dpost.data(), best.data(), bpair.data(), call.data(), cqual.data()), "class_doublets");
+        else
+            g.ck(cellector_class_posteriors(g.c, lab.data(), K, nullptr, nullptr, nullptr, cll.data(), cpost.data(), best.data(), cqual.data()),
+                 "class_posteriors");
         FILE *f = create(od + "/cellector_classes.tsv");
         std::string head = "barcode\tinput_label\tclass_assignment\tqual";
         for (uint32_t k = 0; k < K; k++) head += "\tlog_likelihood_" + class_names[k];
         for (uint32_t k = 0; k < K; k++) head += "\tposterior_" + class_names[k];
+        if (dbl) head += "\tdoublet_posterior\tdoublet_pair";
         head += '\n';
         fputs(head.c_str(), f);
         write_rows(f, N, [&](uint64_t c, std::string &o) {
             const bool assigned = cpost[(uint64_t)best[c] * N + c] > params.posterior_threshold && entries_per_cell[c] >= params.min_loci_used;
             o += barcodes[c]; o += '\t'; o += in_lab[c] == 255 ? "na" : class_names[in_lab[c]].c_str(); o += '\t';
-            o += assigned ? class_names[best[c]].c_str() : "unassigned"; o += '\t'; put(o, cqual[c]);
+            // (main.rs:150-153: the doublet call overrides the label, and too few loci override both)
+            const bool doublet = dbl && call[c] && entries_per_cell[c] >= params.min_loci_used;
+            o += doublet ? "doublet" : assigned ? class_names[best[c]].c_str() : "unassigned"; o += '\t'; put(o, cqual[c]);
             for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, cll[(uint64_t)k * N + c]); }
             for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, cpost[(uint64_t)k * N + c]); }
+            if (dbl) {
+                o += '\t'; put(o, dpost[c]); o += '\t';
+                if (bpair[2 * c] == 255) o += "na";
+                else { o += class_names[bpair[2 * c]]; o += '+'; o += class_names[bpair[2 * c + 1]]; }
+            }
             o += '\n';
         });
         fclose(f);

@@ -605,8 +605,8 @@ cellector_status cellector_assign_resolved_cells(const cellector_ctx *ctx, uint3
  * loaded matrix against K classes given as labels: cellector's own beta-binomial (init_alpha_betas, main.rs:598-611;
  * get_cell_log_likelihoods, main.rs:541-591; the prior / logsumexp chain of main.rs:264-276) generalised from {minority,
  * majority} to K.  The labels may come from peels (cellector_restage + cellector_cell_origin), from cellector_cell_source, from
- * cell hashing or from a clustering with k > 2.  Doublet classes are NOT formed: they need K (K - 1) / 2 further distributions
- * and a prior nobody has argued for.
+ * cell hashing or from a clustering with k > 2.  These four calls form no doublet classes; the block after them
+ * (cellector_class_doublets) adds the K (K - 1) / 2 pair distributions and their prior.
  *   labels [cells]: 0..K-1, or 255 = unlabelled; 1 <= K <= 16.  scale [K] or NULL = all 1.0; log_prior [K] or NULL = default;
  *   mask [L] or NULL = all L loci used, which is what the reference's posterior phase uses (main.rs:255, :303), not the loop's
  *   filtered mask.
@@ -659,6 +659,76 @@ cellector_status cellector_refine_classes(cellector_ctx *ctx, uint8_t *labels, u
                                           const double *log_prior, const uint8_t *mask, uint32_t max_iter, uint64_t min_loci,
                                           cellector_refine_summary *out, double *ll, double *posterior,
                                           uint64_t *qual /*any output may be NULL*/);
+
+/* ---- K-class doublets: pair distributions, calls, held-out refine ---------------------------------------
+ * calculate_posteriors scores minority, majority and their doublet (main.rs:242-248, :259, :270-276), and
+ * output_final_assignments lets doublet_posterior > 0.5 override the label (main.rs:150-152).  These calls do the same over K
+ * classes: beside the K singlet distributions of the block above, one doublet distribution per unordered pair of classes, all
+ * K + P hypotheses in one posterior chain, a doublet call, and a refine that keeps the called doublets out of every tally.
+ *   labels [cells], 1 <= K <= 16, scale [K], log_prior [K], mask [L]: as cellector_class_posteriors.
+ *   held [cells] or NULL = none: a non-zero entry marks a labelled cell that stays out of every tally and is scored like any other.
+ *   pair_scale [K] or NULL = default; log_pair_prior [P] or NULL = default.
+ *   Pairs are the unordered (a, b), 0 <= a < b < K: P = K (K - 1) / 2 of them, p(a, b) = a (2K - a - 1) / 2 + (b - a - 1).
+ *   1 tallies: as step 1 above over the cells with a label < K and held == 0.  Held cells count with the unlabelled ones (slot K):
+ *     over the classes and slot K the tallies still add up to cellector_locus_counts.  n_k = unheld cells of class k.  A class with
+ *     n_k == 0 is dead; a pair with a dead member is dead: ll_pair column -inf, no part in the chain.  No live class (every
+ *     labelled cell held) is CELLECTOR_EINVAL.
+ *   2 singlet distributions: unchanged, alpha_k = (double)alt_k * scale_k + 1.0.
+ *   3 pair distributions: alpha_ab[l] = ((double)alt_a[l] * ps_a + (double)alt_b[l] * ps_b) + 1.0, beta_ab likewise from the ref
+ *     tallies: two rounded products, a rounded sum, then + 1.0, no contraction.  ps = pair_scale; NULL: ps_k = (double)n_min /
+ *     (double)n_k with n_min the smallest live n_k (a dead class: 0), which brings every class to the weight of the smallest, as
+ *     main.rs:245 does with minority_fraction.  cellector_class_pair_alpha_betas returns all P rows by this formula, dead pairs
+ *     included.  K = 2, class 0 the exclusion set, pair_scale = {1, mf0}, mf0 = (n_excl + 1) / (N + 1) unclamped: the bits of
+ *     cellector_posterior_alpha_betas(which = 2).
+ *   4 ll_k as above; ll_ab = the same cell pass under (alpha_ab, beta_ab, mask).
+ *   5 priors.  Singlets: log_prior as given, else log(f_k), f_k = (n_k + 1) / (N_lab + K_live) from the unheld counts.  Pairs:
+ *     log_pair_prior as given, else log(((double)N / 1000.0 / 100.0) * fmax(fmin(f_a, f_b), 0.1)) with N = all cells of the matrix
+ *     and the host's log: main.rs:259 with the smaller class of the pair in the place of the minority.  Like the reference's, these
+ *     priors are NOT normalised: the doublet rate N / 100 000 passes 1 at 10^5 cells, and a caller with 10^6 cells should pass
+ *     priors of their own.
+ *   6 chain.  Terms: the live singlets in ascending k, then the live pairs in ascending p.  x_t = prior + ll, m = max over all
+ *     terms, S = sum exp(x_t - m) in that order, den = m + log S; posterior_k = exp(x_k - den); q_p = exp(y_p - den) with y_p the x
+ *     of pair p; doublet_posterior = sum_p q_p in ascending p (0 without a live pair); best = the smallest k attaining the singlet
+ *     maximum; best_pair = the (a, b) of the smallest p attaining the pair maximum, (255, 255) without one; call = 1 iff
+ *     doublet_posterior > 0.5 (strict, main.rs:150); qual = (uint64) min(-10 log10(rest), 255), 255 where rest == 0, with rest =
+ *     (sum_{k != best} posterior_k in ascending k) + doublet_posterior for call 0 and rest = sum_k posterior_k for call 1 (a sum,
+ *     never 1 - x).  Dead columns: posterior 0.
+ *   7 held-out refine, one step: 1-6 from the current (labels, held); a labelled cell with at least min_loci entries at used loci
+ *     takes label = best and held = doublet_posterior > doublet_threshold; every other cell keeps both its label and its flag;
+ *     n_moved = cells whose label or flag changed.  Repeated until n_moved == 0 or max_iter steps have run (max_iter == 0: 1-6
+ *     only).  A held cell keeps being scored and comes back when its doublet posterior falls.  Between two steps the tallies are
+ *     updated from the rows of the moved cells, each leaving its effective class (held ? slot K : label) and joining its new one;
+ *     the recount rule and option class_delta are those of cellector_refine_classes, over the effective classes.
+ * Scope, refusals and what the calls leave alone and overwrite: exactly as the class calls above.  CELLECTOR_EINVAL with a
+ * message, nothing written or launched, also for a non-finite or negative pair_scale, a NaN pair prior, a doublet_threshold outside
+ * [0, 1] or NaN.  K = 1 is legal: P = 0, doublet_posterior 0, best_pair (255, 255), call 0.  Every device buffer is allocated before
+ * the first write; the caller's labels and held are written once, at the end (held flags come back as 0 / 1).
+ * Device scratch beyond the class calls' own: P * 8 B per cell (the pair columns), 16 B per locus (ONE pair distribution at a time),
+ * 2 B per cell (the held flags and their successors), and the outputs' 8 + 2 + 1 B per cell (doublet_posterior, best_pair, call). */
+cellector_status cellector_class_pair_alpha_betas(cellector_ctx *ctx, const uint8_t *labels, const uint8_t *held, uint32_t n_classes,
+                                                  const double *pair_scale, double *alpha /*[P][L]*/, double *beta /*[P][L]*/);
+cellector_status cellector_class_doublets(cellector_ctx *ctx, const uint8_t *labels, const uint8_t *held, uint32_t n_classes,
+                                          const double *scale, const double *pair_scale, const double *log_prior,
+                                          const double *log_pair_prior, const uint8_t *mask, double *ll /*[K][cells]*/,
+                                          double *ll_pair /*[P][cells]*/, double *posterior /*[K][cells]*/,
+                                          double *doublet_posterior /*[cells]*/, uint8_t *best /*[cells]*/,
+                                          uint8_t *best_pair /*[cells][2]*/, uint8_t *call /*[cells]*/,
+                                          uint64_t *qual /*[cells]*/); /* any output may be NULL */
+typedef struct {
+    uint32_t iterations, converged;  /* steps run; 1 = the last one moved no cell                                  */
+    uint64_t n_moved_last, n_moved_total; /* cells whose label or held flag changed                                */
+    uint64_t n_recounts;             /* steps whose tallies were counted from scratch (the others: delta updates)  */
+    uint64_t class_cells[16];        /* unheld cells per class under the returned labels and flags                 */
+    uint64_t n_held;                 /* labelled cells held under the returned flags                               */
+} cellector_refine_doublets_summary;
+/* labels: in = the start, out = the result; held: likewise, NULL in = none held and then not returned; the other outputs: of the
+ * last step (under the labels and flags that step started from) */
+cellector_status cellector_refine_class_doublets(cellector_ctx *ctx, uint8_t *labels, uint8_t *held, uint32_t n_classes,
+                                                 const double *scale, const double *pair_scale, const double *log_prior,
+                                                 const double *log_pair_prior, const uint8_t *mask, double doublet_threshold,
+                                                 uint32_t max_iter, uint64_t min_loci, cellector_refine_doublets_summary *out,
+                                                 double *ll, double *ll_pair, double *posterior, double *doublet_posterior,
+                                                 uint8_t *best_pair, uint64_t *qual /*any output may be NULL*/);
 
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
