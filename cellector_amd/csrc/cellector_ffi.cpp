@@ -18,6 +18,7 @@
 #include "multi.h"
 #include "ref_log.h"
 #include "assign_host.h"
+#include "genotype_host.h"
 
 cellector_status ctx_fail(const cellector_ctx *c, cellector_status s, const char *fmt, ...)
 {
@@ -1531,6 +1532,62 @@ cellector_status cellector_refine_class_doublets(cellector_ctx *c, uint8_t *labe
                                                    doublet_posterior, nullptr, best_pair, nullptr, qual);
     if (c->timing) timer_collect(c);
     return st;
+}
+
+// ---- class genotypes: kernels_genotypes.hip and genotype_host.h ---------------------------------------------
+// load_mtx_final + the rule of output_final_vcf (main.rs:52-131) for the K classes of a labelling
+cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, double ambient, double gt_threshold,
+                                           uint64_t *cells, uint64_t *alt, uint64_t *ref, uint8_t *gt, double *gp, double *gp3)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(class_call_check(c, "class_genotypes", labels, n_classes, nullptr, nullptr));
+    if (!(ambient >= 0.0 && ambient <= 1.0)) return ctx_fail(c, CELLECTOR_EINVAL, "class_genotypes: ambient = %g is not within [0, 1]", ambient);
+    if (!(gt_threshold >= 0.0 && gt_threshold <= 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "class_genotypes: gt_threshold = %g is not within [0, 1]", gt_threshold);
+    REQUIRE(c, c->keep_coo && (c->coo.locus || !c->nnz), "final tallies need the staged COO (option keep_coo=1)");
+    SETDEV(c);
+    const uint32_t K = n_classes;
+    const uint64_t TL = c->total_loci, n = c->nloc, planes = (uint64_t)(K + 1) * 2;
+    // every buffer first: on CELLECTOR_ENOMEM nothing has been written
+    DevBuf<uint64_t> d_acc;
+    DevBuf<uint8_t> d_lab;
+    CHK(dev_alloc(c, &d_acc, planes * TL));
+    CHK(dev_alloc(c, &d_lab, n));
+    std::vector<uint64_t> h;
+    try {
+        if (alt || ref || gt || gp || gp3) h.resize(planes * TL);
+    } catch (const std::bad_alloc &) {
+        return ctx_fail(c, CELLECTOR_ENOMEM, "class_genotypes: out of host memory");
+    }
+    if (n) HIPCHK(c, hipMemcpyAsync(d_lab, labels, n, hipMemcpyHostToDevice, c->stream));
+    CHK(launch_genotype_tallies(c, d_lab, K, d_acc));
+    const bool rule = gt || gp || gp3;
+    if ((alt || ref || rule) && TL) CHK(d2h(c, h.data(), d_acc, planes * TL * 8));
+    else HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's labels have been read, the scratch may go)
+    d_acc.reset();
+    d_lab.reset();
+    if (cells) {
+        for (uint32_t k = 0; k <= K; k++) cells[k] = 0;
+        for (uint64_t i = 0; i < n; i++) cells[labels[i] == 255 ? K : labels[i]]++;
+    }
+    for (uint32_t k = 0; k <= K && TL; k++) {
+        if (alt) memcpy(alt + (uint64_t)k * TL, h.data() + (uint64_t)k * 2 * TL, TL * 8);
+        if (ref) memcpy(ref + (uint64_t)k * TL, h.data() + ((uint64_t)k * 2 + 1) * TL, TL * 8);
+    }
+    if (!rule) return CELLECTOR_OK;
+    for (uint64_t l = 0; l < TL; l++) {
+        uint64_t A = 0, R = 0;
+        for (uint32_t k = 0; k <= K; k++) { A += h[(uint64_t)k * 2 * TL + l]; R += h[((uint64_t)k * 2 + 1) * TL + l]; }
+        const GenotypeLocus g = genotype_locus(A, R, ambient);
+        for (uint32_t k = 0; k < K; k++) {
+            const GenotypeCall q = genotype_call(g, h[(uint64_t)k * 2 * TL + l], h[((uint64_t)k * 2 + 1) * TL + l], gt_threshold);
+            const uint64_t o = (uint64_t)k * TL + l;
+            if (gt) gt[o] = q.gt;
+            if (gp) gp[o] = q.gp;
+            if (gp3) { gp3[3 * o] = q.q[0]; gp3[3 * o + 1] = q.q[1]; gp3[3 * o + 2] = q.q[2]; }
+        }
+    }
+    return CELLECTOR_OK;
 }
 
 // ---- posteriors ---------------------------------------------------------------------------------------

@@ -553,6 +553,8 @@ cellector_status class_doublets_run(cellector_ctx *c, const uint8_t *labels, con
                                     cellector_refine_doublets_summary *sum, double *ll, double *ll_pair, double *posterior,
                                     double *doublet_posterior, uint8_t *best, uint8_t *best_pair, uint8_t *call, uint64_t *qual);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
+// the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
+cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);
 // order statistics: exact values at SEL_T 0-based ranks of n keys

@@ -83,6 +83,7 @@ SIGNATURES = {
     "cellector_class_doublets": (_i, [_vp, _vp, _vp, C.c_uint32] + [_vp] * 13),
     "cellector_refine_class_doublets": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint32, _u64]
                                         + [_vp] * 7),
+    "cellector_class_genotypes": (_i, [_vp, _vp, C.c_uint32, _d, _d] + [_vp] * 6),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -716,6 +717,23 @@ class Cellector:
                                                            _p(log_pair_prior), _p(mask), float(doublet_threshold), int(max_iter),
                                                            int(min_loci), C.byref(s), _p(ll), _p(llp), _p(post), _p(dp), _p(bp), _p(qual)))
         return dict(labels=labels, held=held, summary=s, ll=ll, ll_pair=llp, posterior=post, doublet_posterior=dp, best_pair=bp, qual=qual)
+
+    # ---- ... and their genotypes over ALL loci of the matrix; genotypes.py is the numpy twin
+    def class_genotypes(self, labels, n_classes, ambient=0.03, gt_threshold=0.99, genotypes=True):
+        """The K classes' allele tallies over all loci of the matrix, from the staged COO, and the genotype call of
+        output_final_vcf per class and locus (cellector_class_genotypes).  Returns a dict: cells [K + 1], alt / ref [K + 1,
+        total_loci] uint64 (slot K: the cells labelled 255) and, with genotypes, gt [K, total_loci] uint8 (1 = 1/1, 2 = 0/1, 3 = 0/0,
+        0 = ./.: genotypes.GT_STRINGS), gp [K, total_loci] (the largest of the three posteriors) and gp3 [K, total_loci, 3] (hom-alt,
+        het, hom-ref).  Cells held out as doublets are passed as 255."""
+        labels, K, _, _, _ = self._class_args(labels, n_classes)
+        Ka, TL = min(K, 16), self.dims().total_loci
+        cells, alt, ref = np.zeros(Ka + 1, np.uint64), np.zeros((Ka + 1, TL), np.uint64), np.zeros((Ka + 1, TL), np.uint64)
+        out = dict(cells=cells, alt=alt, ref=ref)
+        if genotypes:
+            out.update(gt=np.zeros((Ka, TL), np.uint8), gp=np.zeros((Ka, TL), np.float64), gp3=np.zeros((Ka, TL, 3), np.float64))
+        self._ck(self._lib.cellector_class_genotypes(self.h, _p(labels), K, float(ambient), float(gt_threshold), _p(cells), _p(alt),
+                                                     _p(ref), _p(out.get("gt")), _p(out.get("gp")), _p(out.get("gp3"))))
+        return out
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

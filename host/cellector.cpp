@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../include/cellector_ffi.h"
+#include "genotype_host.h"
 
 namespace {
 
@@ -193,6 +194,7 @@ struct Params {
     std::optional<std::string> classes;               // barcode<TAB>label, at most 16 distinct labels
     uint64_t refine_classes = 0;                       // hard-EM steps at most (0: score the given labelling only)
     bool class_doublets = false;                       // the pairs' doublet classes beside them (cellector_class_doublets)
+    bool class_genotypes = false;                      // cellector_classes.vcf: the classes' genotypes (cellector_class_genotypes)
 };
 
 const char *USAGE =
@@ -298,7 +300,14 @@ const char *USAGE =
     "                                                                       posterior exceeds 0.5, cellector_classes.tsv gains the columns\n"
     "                                                                       doublet_posterior and doublet_pair (<labelA>+<labelB> or na), and\n"
     "                                                                       --refine_classes holds the called doublets out of the classes'\n"
-    "                                                                       tallies (its stderr line gains held=<n>) (default false)\n";
+    "                                                                       tallies (its stderr line gains held=<n>) (default false)\n"
+    "        --class_genotypes <true|false>                                 with --classes and --vcf: writes cellector_classes.vcf, the input\n"
+    "                                                                       vcf with one sample column GT:GP:AO:RO per class, called like\n"
+    "                                                                       the two of cellector.vcf from the reads of the cells whose\n"
+    "                                                                       class_assignment is that class (doublet and unassigned cells\n"
+    "                                                                       are in none), and cellector_class_concordance.tsv: per pair of\n"
+    "                                                                       classes the loci both are called at and those where the calls\n"
+    "                                                                       differ (default false; one GPU)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -326,7 +335,7 @@ Params load_params(int argc, char **argv)
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
-                                  "class_doublets"};
+                                  "class_doublets", "class_genotypes"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -416,6 +425,13 @@ Params load_params(int argc, char **argv)
         p.class_doublets = v == "true";
         if (p.class_doublets && !p.classes) die(1, "error: The argument '--class_doublets true' requires '--classes <file>'");
     }
+    if (got.count("class_genotypes")) {
+        const std::string &v = got["class_genotypes"];
+        if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --class_genotypes: expected true or false");
+        p.class_genotypes = v == "true";
+        if (p.class_genotypes && !p.classes) die(1, "error: The argument '--class_genotypes true' requires '--classes <file>'");
+        if (p.class_genotypes && !p.vcf) die(1, "error: The argument '--class_genotypes true' requires '--vcf <vcf>'");
+    }
     if (got.count("refine_classes")) {
         p.refine_classes = parse_usize("refine_classes", got["refine_classes"]);
         if (!p.classes) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
@@ -446,44 +462,13 @@ Params load_params(int argc, char **argv)
                    "' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.locus_expected && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--locus_expected true' works on one GPU and cannot be used with '--devices <a,b,...>'");
+    if (p.class_genotypes && (p.devices_auto || p.devices.size() > 1))
+        die(1, "error: The argument '--class_genotypes true' works on one GPU and cannot be used with '--devices <a,b,...>'");
     if (p.resolve_near_ties && (p.devices_auto || p.devices.size() > 1))
         die(1, "error: The argument '--resolve_near_ties true' works on one GPU and cannot be used with '--devices <a,b,...>'");
     return p;
 }
 
-// ---- statrs pieces for the VCF genotype rule -----------------------------------
-double ln_gamma(double x)
-{
-    static const double dk[11] = {2.48574089138753565546e-5,  1.05142378581721974210,    -3.45687097222016235469,
-                                  4.51227709466894823700,     -2.98285225323576655721,   1.05639711577126713077,
-                                  -1.95428773191645869583e-1, 1.70970543404441224307e-2, -5.71926117404305781283e-4,
-                                  4.63399473359905636708e-6,  -2.71994908488607703910e-9};
-    double s = dk[0];
-    for (int i = 1; i <= 10; i++) s += dk[i] / (x + (double)i - 1.0);
-    return std::log(s) + 0.6207822376352452223455184457816472122518527279025978 +
-           (x - 0.5) * std::log((x - 0.5 + 10.900511) / 2.71828182845904523536028747135266250);
-}
-double ln_factorial(uint64_t x)
-{
-    struct Cache {  // statrs FCACHE: running f64 product (built once; thread-safe initialisation)
-        double v[171];
-        Cache()
-        {
-            v[0] = 1.0;
-            for (int i = 1; i <= 170; i++) v[i] = v[i - 1] * (double)i;
-        }
-    };
-    static const Cache cache;
-    return x <= 170 ? std::log(cache.v[x]) : ln_gamma((double)x + 1.0);
-}
-double binomial_pmf(double p, uint64_t n, uint64_t k)
-{
-    if (k > n) return 0.0;
-    if (p == 0.0) return k == 0 ? 1.0 : 0.0;
-    if (std::fabs(p - 1.0) <= 4 * 2.220446049250313e-16) return k == n ? 1.0 : 0.0;
-    const double lnb = ln_factorial(n) - ln_factorial(k) - ln_factorial(n - k);
-    return std::exp(lnb + (double)k * std::log(p) + (double)(n - k) * std::log(1.0 - p));
-}
 // statrs Data::median on a copy (main.rs:442-443); NaN for empty data
 double median_of(std::vector<double> v)
 {
@@ -491,6 +476,33 @@ double median_of(std::vector<double> v)
     std::sort(v.begin(), v.end());
     const size_t k = v.size() / 2;
     return v.size() % 2 ? v[k] : (v[k - 1] + v[k]) / 2.0;
+}
+
+// the lines of the input vcf for the two VCF writers (main.rs:64-77): rec_of = META for a "##" line, CHROM for the "#CHROM" line,
+// else the record's index, which is its locus; more records than loci is the reference's index panic
+struct VcfLines {
+    static constexpr uint64_t META = ~0ull, CHROM = ~0ull - 1;
+    std::vector<std::string> lines;
+    std::vector<uint64_t> rec_of;
+};
+VcfLines read_vcf_lines(const std::string &path, uint64_t total_loci)
+{
+    VcfLines v;
+    Lines in(path);
+    std::string line;
+    uint64_t rec = 0;
+    while (in.next(line)) {
+        uint64_t kind = VcfLines::META;
+        if (line.rfind("##", 0) == 0) kind = VcfLines::META;
+        else if (line.rfind("#CHROM", 0) == 0) kind = VcfLines::CHROM;
+        else {
+            if (rec >= total_loci) die(EXIT_PANIC, "index out of bounds: vcf has more records than the matrix has loci");
+            kind = rec++;
+        }
+        v.lines.push_back(line);
+        v.rec_of.push_back(kind);
+    }
+    return v;
 }
 
 struct Ctx {
@@ -1028,48 +1040,19 @@ int main(int argc, char **argv)
         const uint64_t TL = dm.total_loci;
         std::vector<uint64_t> amin(TL), rmin(TL), amaj(TL), rmaj(TL);
         g.ck(cellector_final_allele_tallies(g.c, amin.data(), rmin.data(), amaj.data(), rmaj.data()), "load_mtx_final");
-        Lines in(*params.vcf);
         FILE *f = create(od + "/cellector.vcf");
-        std::string line;
-        uint64_t rec = 0;
         const double ambient = 0.03, gt_thr = 0.99;
-        // the lines first (kind: 0 = "##" line, 1 = "#CHROM" line, 2 = record with its index), then formatted in parallel
-        std::vector<std::string> lines;
-        std::vector<uint64_t> rec_of;
-        while (in.next(line)) {
-            uint64_t kind = ~0ull;
-            if (line.rfind("##", 0) == 0) kind = ~0ull;
-            else if (line.rfind("#CHROM", 0) == 0) kind = ~0ull - 1;
-            else {
-                if (rec >= TL) die(EXIT_PANIC, "index out of bounds: vcf has more records than the matrix has loci");
-                kind = rec++;
-            }
-            lines.push_back(line);
-            rec_of.push_back(kind);
-        }
-        write_rows(f, lines.size(), [&](uint64_t i, std::string &o) {
-            const std::string &ln = lines[i];
-            if (rec_of[i] == ~0ull) { o += ln; o += '\n'; return; }
-            if (rec_of[i] == ~0ull - 1) { o += ln; o += "\tmajority\tminority\n"; return; }
-            const uint64_t r_ = rec_of[i];
-            const uint64_t tot_alt = amin[r_] + amaj[r_], tot_ref = rmin[r_] + rmaj[r_];
-            const double soup = tot_alt + tot_ref > 0 ? (double)tot_alt / (double)(tot_alt + tot_ref) : 0.5;
-            const double p_alt = (1.0 - ambient) * 0.99 + ambient * soup, p_het = (1.0 - ambient) * 0.5 + ambient * soup,
-                         p_ref = (1.0 - ambient) * 0.01 + ambient * soup;
-            const char *gt[2];
-            double mx[2];
-            for (int w = 0; w < 2; w++) {  // 0 = majority, 1 = minority
-                const uint64_t a = w ? amin[r_] : amaj[r_], r = w ? rmin[r_] : rmaj[r_];
-                const double l_alt = binomial_pmf(p_alt, a + r, a), l_het = binomial_pmf(p_het, a + r, a),
-                             l_ref = binomial_pmf(p_ref, a + r, a);
-                const double den = 1.0 / 3.0 * l_alt + 1.0 / 3.0 * l_het + 1.0 / 3.0 * l_ref;
-                const double q_alt = l_alt * 1.0 / 3.0 / den, q_het = l_het * 1.0 / 3.0 / den, q_ref = l_ref * 1.0 / 3.0 / den;
-                mx[w] = std::fmax(std::fmax(q_alt, q_het), q_ref);
-                gt[w] = q_alt > gt_thr ? "1/1" : q_het > gt_thr ? "0/1" : q_ref > gt_thr ? "0/0" : "./.";
-            }
+        const VcfLines v = read_vcf_lines(*params.vcf, TL);
+        write_rows(f, v.lines.size(), [&](uint64_t i, std::string &o) {
+            const std::string &ln = v.lines[i];
+            if (v.rec_of[i] == VcfLines::META) { o += ln; o += '\n'; return; }
+            if (v.rec_of[i] == VcfLines::CHROM) { o += ln; o += "\tmajority\tminority\n"; return; }
+            const uint64_t r_ = v.rec_of[i];
+            const GenotypeLocus g = genotype_locus(amin[r_] + amaj[r_], rmin[r_] + rmaj[r_], ambient);
+            const GenotypeCall maj = genotype_call(g, amaj[r_], rmaj[r_], gt_thr), min = genotype_call(g, amin[r_], rmin[r_], gt_thr);
             o += ln; o += "\tGT:GP:AO:RO\t";
-            o += gt[0]; o += ':'; put(o, mx[0]); o += ':'; put(o, amaj[r_]); o += ':'; put(o, rmaj[r_]); o += '\t';
-            o += gt[1]; o += ':'; put(o, mx[1]); o += ':'; put(o, amin[r_]); o += ':'; put(o, rmin[r_]); o += '\n';
+            o += genotype_string(maj.gt); o += ':'; put(o, maj.gp); o += ':'; put(o, amaj[r_]); o += ':'; put(o, rmaj[r_]); o += '\t';
+            o += genotype_string(min.gt); o += ':'; put(o, min.gp); o += ':'; put(o, amin[r_]); o += ':'; put(o, rmin[r_]); o += '\n';
         });
         fclose(f);
     }
@@ -1246,6 +1229,62 @@ int main(int argc, char **argv)
         });
         fclose(f);
         lap("cellector_classes.tsv");
+        // --class_genotypes: a cell counts in the class its class_assignment names; doublet and unassigned cells are in none
+        if (params.class_genotypes) {
+            const uint64_t TL = dm.total_loci;
+            std::vector<uint8_t> glab(N);
+            for (uint64_t c = 0; c < N; c++) {
+                const bool assigned = cpost[(uint64_t)best[c] * N + c] > params.posterior_threshold && entries_per_cell[c] >= params.min_loci_used;
+                const bool doublet = dbl && call[c] && entries_per_cell[c] >= params.min_loci_used;
+                glab[c] = !doublet && assigned ? best[c] : 255;
+            }
+            // (a run that assigned no cell to any class ends here with the library's refusal: all classes are dead)
+            std::vector<uint64_t> galt((uint64_t)(K + 1) * TL), gref((uint64_t)(K + 1) * TL);
+            g.ck(cellector_class_genotypes(g.c, glab.data(), K, 0.03, 0.99, nullptr, galt.data(), gref.data(), nullptr, nullptr, nullptr),
+                 "class_genotypes");
+            const double ambient = 0.03, gt_thr = 0.99;
+            const VcfLines v = read_vcf_lines(*params.vcf, TL);
+            std::vector<uint8_t> gts((uint64_t)K * TL, 0);  // by locus, for the concordance (a locus without a record: no call)
+            FILE *fv = create(od + "/cellector_classes.vcf");
+            write_rows(fv, v.lines.size(), [&](uint64_t i, std::string &o) {
+                const std::string &ln = v.lines[i];
+                if (v.rec_of[i] == VcfLines::META) { o += ln; o += '\n'; return; }
+                if (v.rec_of[i] == VcfLines::CHROM) {
+                    o += ln;
+                    for (uint32_t k = 0; k < K; k++) { o += '\t'; o += class_names[k]; }
+                    o += '\n';
+                    return;
+                }
+                const uint64_t t = v.rec_of[i];
+                uint64_t A = 0, R = 0;
+                for (uint32_t k = 0; k <= K; k++) { A += galt[(uint64_t)k * TL + t]; R += gref[(uint64_t)k * TL + t]; }
+                const GenotypeLocus gl = genotype_locus(A, R, ambient);
+                o += ln; o += "\tGT:GP:AO:RO";
+                for (uint32_t k = 0; k < K; k++) {
+                    const uint64_t a = galt[(uint64_t)k * TL + t], r = gref[(uint64_t)k * TL + t];
+                    const GenotypeCall q = genotype_call(gl, a, r, gt_thr);
+                    gts[(uint64_t)k * TL + t] = q.gt;
+                    o += '\t'; o += genotype_string(q.gt); o += ':'; put(o, q.gp); o += ':'; put(o, a); o += ':'; put(o, r);
+                }
+                o += '\n';
+            });
+            fclose(fv);
+            FILE *fc = create(od + "/cellector_class_concordance.tsv");
+            fputs("class_a\tclass_b\tboth_called\tdiscordant\n", fc);
+            for (uint32_t a = 0; a < K; a++)
+                for (uint32_t b = a + 1; b < K; b++) {
+                    uint64_t both = 0, disc = 0;
+                    for (uint64_t t = 0; t < TL; t++) {
+                        const uint8_t x = gts[(uint64_t)a * TL + t], y = gts[(uint64_t)b * TL + t];
+                        both += x && y;
+                        disc += x && y && x != y;
+                    }
+                    fprintf(fc, "%s\t%s\t%llu\t%llu\n", class_names[a].c_str(), class_names[b].c_str(), (unsigned long long)both,
+                            (unsigned long long)disc);
+                }
+            fclose(fc);
+            lap("cellector_classes.vcf");
+        }
     }
     // Every output file is closed: leave without tearing the context down.  Handing ~150 GB of device memory back block
     // by block (and destroying the host vectors) was half a second of the 1M x 200k run; the driver reclaims a dead

@@ -730,6 +730,40 @@ cellector_status cellector_refine_class_doublets(cellector_ctx *ctx, uint8_t *la
                                                  double *ll, double *ll_pair, double *posterior, double *doublet_posterior,
                                                  uint8_t *best_pair, uint64_t *qual /*any output may be NULL*/);
 
+/* ---- class genotypes: per-class allele tallies over ALL loci and the genotype call ---------------------------
+ * output_final_vcf (main.rs:52-131) re-reads both matrices over all loci (load_mtx_final, load_data.rs:109-132), also those that
+ * failed min_alt / min_ref, and calls one of three genotypes per locus for its two classes under an ambient mix.  This call does
+ * the same for the K classes of a labelling: what a cluster is matched to a donor with.
+ *   labels [cells], 1 <= K <= 16: as cellector_class_posteriors; 255 = in no class.  A caller that holds doublets out (the held
+ *   flags of cellector_refine_class_doublets, or call) passes them as 255: there is no held argument.
+ *   1 tallies: alt_s[t] / ref_s[t] = the sums of the allele counts of the staged entries at locus t (0 <= t < total_loci, the
+ *     matrix' own locus index, not the used-locus index) whose cell has slot s; slot k < K = label k, slot K = the cells labelled
+ *     255; u64, exact; a repeated (locus, cell) line counts each time.  cells[s] = the cells of slot s.  Over the K + 1 slots the
+ *     planes add up to the locus' totals (the four planes of cellector_final_allele_tallies summed); at a used locus the first K
+ *     are cellector_class_tallies'.  One pass over the staged COO whatever K, in any entry order.
+ *   2 per locus: A, R = the sums over ALL K + 1 slots; soup = A + R > 0 ? (double)A / (double)(A + R) : 0.5;
+ *     p_g = (1.0 - ambient) * e_g + ambient * soup with e = {0.99, 0.5, 0.01} for g = hom-alt, het, hom-ref (main.rs:79-92).
+ *   3 per class k with tallies (a, r): l_g = Binomial(a + r, p_g).pmf(a) (statrs; the host's exp and log);
+ *     den = 1.0/3.0 * l_alt + 1.0/3.0 * l_het + 1.0/3.0 * l_ref; q_g = l_g * 1.0 / 3.0 / den; gp = fmax(fmax(q_alt, q_het), q_ref);
+ *     gt = q_alt > gt_threshold ? 1 : q_het > gt_threshold ? 2 : q_ref > gt_threshold ? 3 : 0 (1 = 1/1, 2 = 0/1, 3 = 0/0, 0 = ./.)
+ *     (main.rs:93-124).  ambient 0.03 and gt_threshold 0.99 are the reference's; with them and K = 2, class 0 the exclusion set,
+ *     gt and gp are the two sample columns of cellector.vcf.
+ *   4 a class without a cell has zero planes: its three pmfs are 1, gp is 1/3 and gt is 0, like a locus without reads.
+ *   5 the reference's quirk is kept: at deep tallies all three pmfs can underflow to 0; then den is 0, every q and gp are NaN and
+ *     gt is 0.
+ * The rule runs on one host thread, in the library, and not at all when gt, gp and gp3 are all NULL.
+ * Needs a loaded matrix, no iteration in flight, the staged COO (option keep_coo = 1 at the ingest) and a single-device ctx that
+ * holds all cells.  CELLECTOR_EINVAL with a message, nothing written or launched, for these, for the labels cellector_class_posteriors
+ * refuses, and for an ambient or a gt_threshold that is NaN or outside [0, 1].  Device scratch ((K + 1) * 16 B per locus of the
+ * matrix, 1 B per cell) is allocated before anything is written: on CELLECTOR_ENOMEM the ctx is as it was.
+ * The call reads the staged COO and the labels only: it touches nothing of the EM state, overwrites no table and invalidates no
+ * cache, and an EM loop interrupted by it continues with the same bits. */
+cellector_status cellector_class_genotypes(cellector_ctx *ctx, const uint8_t *labels /*[cells]*/, uint32_t n_classes,
+                                           double ambient, double gt_threshold,
+                                           uint64_t *cells /*[K+1]*/, uint64_t *alt /*[K+1][total_loci]*/, uint64_t *ref /*[K+1][total_loci]*/,
+                                           uint8_t *gt /*[K][total_loci]*/, double *gp /*[K][total_loci]*/,
+                                           double *gp3 /*[K][total_loci][3]: q_alt, q_het, q_ref*/);   /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
