@@ -8,8 +8,9 @@
 //   cell pass   (get_cell_log_likelihoods, main.rs:541-591): the matrix is cut into (1024-cell block x 639-locus
 //               chunk) tiles, stored in a sliced-ELLPACK form with a sorting window of one tile (SELL-64-1024): the
 //               cells of a tile are ordered by their entry count, every 64 of them form a slice whose rows (one per
-//               cell: cell id + entries) are padded to the slice's longest cell, so that all lanes of a wave run the
-//               SAME number of lookups — no divergence and ~10 % padding instead of the ~55 % idle lanes of a
+//               cell) are padded to the slice's longest cell, K entries of either parity (the cell ids ride in the rows when K
+//               is odd and in a block of their own when K is even: tiled.h), so that all lanes of a wave run the
+//               SAME number of lookups — no divergence and ~9 % padding instead of the ~55 % idle lanes of a
 //               cell-per-lane walk in file order — and a lane fetches its row with one or two 16-byte loads.
 //               A u16 entry is n-1 << 14 | locus slot << 4 | code; padding points at an all-zero slot.
 //               A persistent 1024-thread workgroup takes columns of four cell blocks and a group of chunks: the chunk's
@@ -187,9 +188,10 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
     // Software pipeline over the steps t = (chunk, block) of this workgroup: the rows of step t+2 are requested in step
     // t; the slice header they need (wave-uniform: scalar loads) is requested in step t-1.  Two buffers serve the even
     // and the odd steps; a buffer is consumed and then refilled in place.
-    // lo: cell + entries 0..6, hi: entries 7..14; base = first u16 of the slice in `tiles` (wave-uniform, like k: both stay in
-    // scalar registers — the row's own address is only needed again by the rare slice with more than T_NE entries per cell)
-    struct row_t { tile_u4 lo, hi; uint32_t k; uint64_t base; };
+    // lo, hi: the row's first 16 u16 (K odd: cell id + entries 0..14; K even: entries 0..15); cell: the cell id, from the row's
+    // first u16 (odd) or the slice's block of cell ids (even); base = first u16 of the slice in `tiles` (wave-uniform, like k: both
+    // stay in scalar registers — the row's own address is only needed again by the rare slice with rows beyond T_ROW_U16)
+    struct row_t { tile_u4 lo, hi; uint32_t cell, k; uint64_t base; };
     // slice header of a step (beyond the last chunk: the last chunk's; a workgroup at the ragged end re-reads the last block)
     const uint32_t wv_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wv);
 #define HDR_LOAD(H, J, S) /* S: a compile-time block number; J: the chunk (clamped by the caller) */           \
@@ -201,8 +203,10 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
         if (TILE_ABL != 9 || first_rows) /* ablation 9: headers loaded in the prologue only; 10: always the column's first chunk's */ \
         (H) = reinterpret_cast<const uint4 *>(thdr + ((uint64_t)min(b0 + (uint32_t)(S), nb - 1) * nj + (TILE_ABL == 10 ? j0 : (J))) * T_HDR)[sl__]; \
     } while (0)
-    // this lane's row of the slice with header H.  A row of less than 8 u16 is covered by the first load: the second
-    // one then repeats it (never consumed) instead of reading far beyond the row.
+    // this lane's row of the slice with header H (the format follows from K's parity: tiled.h).  A row of at most 8 u16 is covered
+    // by the first load: the second one then repeats it (never consumed) instead of reading far beyond the row.  The cell id: regular
+    // kernels, a 2-byte load of its own in both formats (CELL_LOAD below); tier-2 kernels, the row's first u16 when K is odd and
+    // a 2-byte load out of the slice's block of cell ids, requested here with the row, when K is even.
 #define ROW_LOAD(E, H)                                                                                           \
     do {                                                                                                         \
         (E).k = (SKIP_EMPTY && (H).w) ? 0u : (H).z; /* 0: a slice without entries (tier-2 tiles): the step skips it */ \
@@ -210,13 +214,33 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
         /* (a wave-uniform 64-bit base in scalar registers plus a 32-bit byte offset per lane: the loads take the  */ \
         /*  scalar-base form, and the address costs one multiply instead of 64-bit vector arithmetic)               */ \
         const char *sb__ = reinterpret_cast<const char *>(tiles + (E).base);                                     \
-        const uint32_t off__ = __umul24(lane, ((H).z + 1u) * 2u); /* (full-rate 24-bit multiply) */                     \
+        const uint32_t odd__ = (H).z & 1u, n16__ = (H).z + odd__; /* u16 per row */                                \
+        const uint32_t off__ = __umul24(lane, n16__ * 2u) + (odd__ ? 0u : 128u); /* (full-rate 24-bit multiply) */ \
         if ((!(TILE_ABL == 2 || TILE_ABL == 9) || first_rows) && !(SKIP_EMPTY && (H).w)) { /* ablations 2, 9: rows loaded in the prologue only */ \
+            if constexpr (SKIP_EMPTY) { /* (short steps: an even K's cell id flies with the row, see CELL_LOAD) */ \
+                if (!odd__) (E).cell = *reinterpret_cast<const uint16_t *>(sb__ + lane * 2u);                    \
+            }                                                                                                    \
             (E).lo = *reinterpret_cast<const tile_u4 *>(sb__ + off__);                                           \
-            (E).hi = *reinterpret_cast<const tile_u4 *>(sb__ + ((H).z > 7u ? 16u : 0u) + off__);                 \
+            (E).hi = *reinterpret_cast<const tile_u4 *>(sb__ + (n16__ > 8u ? 16u : 0u) + off__);                 \
         }                                                                                                        \
     } while (0)
 
+    // this lane's cell id of the slice whose rows E was just asked for, regular geometry: the row's first u16 (K odd) or u16 `lane`
+    // of the slice's block of cell ids (K even).  Requested at the END of a step, behind the last use of the buffer's previous cell
+    // id, so that the register is refilled in place: requested with the rows it is a third live cell id per lane (the step's own and
+    // one per row buffer), and the EM pass' kernel leaves its register granule (107 VGPRs for the parent's 102; 103 this way,
+    // measured no slower).  It still has PFD - 1 whole steps to arrive, and vmcnt counts it in issue order behind the rows it belongs
+    // to.  An odd K has the id in the row's first dword as well, and loading it again is work the sums do not need — but taking it from
+    // there (the load for even K only, cell = K odd ? w[0] & 0xffff : loaded) keeps a copy alive beside the buffers: 105 / 91 VGPRs,
+    // out of the granule again; the load is a hit in the line the row came from.
+    // The tier-2 kernels (short steps, mostly K = 1, registers to spare: 107 of 112) do exactly that: ROW_LOAD, TILE_STEP.
+#define CELL_LOAD(E)                                                                                             \
+    do {                                                                                                         \
+        const uint32_t k__ = (E).k, odd__ = k__ & 1u;                                                            \
+        if constexpr (!SKIP_EMPTY)                                                                               \
+        (E).cell = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(tiles + (E).base) +        \
+                                                       __umul24(lane, odd__ ? (k__ + 1u) * 2u : 2u));            \
+    } while (0)
     // PFD = prefetch distance in steps = number of pipeline buffers.  With four blocks per column every block of the chunk has
     // a buffer of its own and the rows are requested a whole chunk ahead.
     // The tier-2 tiles of a deep matrix hold 0.4 entries per row: ten of a tile's sixteen slices (sorted by length) have none, and a
@@ -244,6 +268,10 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
     ROW_LOAD(e1, h1);
     if constexpr (PFD >= 3) ROW_LOAD(e2, h2);
     if constexpr (PFD == 4) ROW_LOAD(e3, h3);
+    CELL_LOAD(e0);
+    CELL_LOAD(e1);
+    if constexpr (PFD >= 3) CELL_LOAD(e2);
+    if constexpr (PFD == 4) CELL_LOAD(e3);
     HDR_STEP(h0, PFD);
     HDR_STEP(h1, PFD + 1);
     if constexpr (PFD >= 3) HDR_STEP(h2, PFD + 2);
@@ -252,8 +280,10 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
     first_rows = false;
 
     // one step: block S of the current chunk, pipeline buffers E / H
-    // lookup of entry KK of the row = u16 number KK + 1 = half (KK + 1) & 1 of dword (KK + 1) >> 1.  The slice's K is odd
-    // and wave-uniform, so the lookups come in pairs behind one scalar branch.
+    // lookup number KK of the ladder = u16 number KK + 1 of the row = half (KK + 1) & 1 of dword (KK + 1) >> 1.  In both row
+    // formats dword p >= 1 holds two consecutive entries and D = (K + 1) >> 1 dwords hold entries (K is wave-uniform), so the
+    // lookups come in pairs behind one scalar branch on D; only dword 0 differs: its high half is an entry in both formats, its
+    // low half is one when K is even (that lookup starts the row's sums).
 #if TILE_ABL == 1 || TILE_ABL == 5  /* ablation: no table lookups */
 #define TILE_LOOKUP(V, E16) do { if constexpr (EXPECTED) V = make_double2((double)(E16), 1.0); else V = (double)(E16); } while (0)
 #elif TILE_ABL == 4  /* ablation: lookups free of bank conflicts (a lane keeps to its own bank pair; wrong values) */
@@ -298,7 +328,7 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
 #define TILE_PIN(V) do { } while (0)
 #endif
 #define TILE_LEVEL(KA, KB, PA, PB, BODY)                                                                         \
-    if (K__ > (KA)) {                                                                                            \
+    if (D__ > (((KA) + 1u) >> 1)) {                                                                              \
         TILE_RD(v##KA, KA); TILE_RD(v##KB, KB);                                                                  \
         TILE_PIN(PA); TILE_PIN(PB);                                                                              \
         TILE_ADD(PA); TILE_ADD(PB);                                                                              \
@@ -308,10 +338,12 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
     do {                                                                                                         \
         /* 1. consume the row requested PFD steps ago: u16 number i of the row sits in half i & 1 of dword i >> 1 */ \
         const uint32_t w__[8] = {(E).lo.x, (E).lo.y, (E).lo.z, (E).lo.w, (E).hi.x, (E).hi.y, (E).hi.z, (E).hi.w}; \
-        const uint32_t K__ = (uint32_t)__builtin_amdgcn_readfirstlane((int)(E).k); /* wave-uniform, odd */       \
+        const uint32_t K__ = (uint32_t)__builtin_amdgcn_readfirstlane((int)(E).k); /* wave-uniform */            \
+        const uint32_t D__ = (K__ + 1u) >> 1; /* dwords of the row that hold entries */                          \
         const uint64_t cur_base__ = (E).base;                                                                    \
-        const uint32_t cell__ = w__[0] & 0xffffu;                                                                \
-        /* 2. issue the next requests: rows of step t+PFD (their header is here), header of step t+2 PFD */      \
+        const uint32_t cell__ = (SKIP_EMPTY && (K__ & 1u)) ? (w__[0] & 0xffffu) : (E).cell;                      \
+        /* 2. issue the next requests: rows of step t+PFD (their header is here; their cell ids: at the end of the step), */ \
+        /*    header of step t+2 PFD */                                                                          \
         ROW_LOAD(E, H);                                                                                          \
         HDR_LOAD(H, min(j + ((S) + 2 * PFD) / T_SB, j1 - 1), ((S) + 2 * PFD) % T_SB);                            \
         /* 3. the cell's accumulator is requested first (LDS answers in order: it has landed when the sums are done), */ \
@@ -321,9 +353,15 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
         if constexpr (TILE_ABL == 8) { if constexpr (EXPECTED) acc__ = make_double2(0.0, 0.0); else acc__ = 0.0; }        \
         else acc__ = s_acc[(S) * T_BC + (TILE_ABL == 6 ? tid : cell__)];                                         \
         double a_ll__ = 0.0, a_el__ = 0.0;                                                                       \
+        if (!(K__ & 1u)) { /* even K: entry 0 sits where the odd format has the cell id; the sums start from it (0.0 + x = x but for x = -0.0, which no table value is: a log-pmf or an expected term is negative or +0.0) */ \
+            tab_t vz__;                                                                                          \
+            TILE_LOOKUP(vz__, w__[0] & 0xffffu);                                                                 \
+            if constexpr (EXPECTED) { a_ll__ = vz__.x; a_el__ = vz__.y; }                                        \
+            else a_ll__ = vz__;                                                                                  \
+        }                                                                                                        \
         /* (written out: a loop with an early exit gets re-rolled and then selects its register at run time) */  \
         TILE_RD(v0, 0);                                                                                          \
-        if (K__ > 1) {                                                                                           \
+        if (D__ > 1u) {                                                                                          \
             TILE_RD(v1, 1); TILE_RD(v2, 2);                                                                      \
             TILE_PIN(v0);                                                                                        \
             TILE_ADD(v0);                                                                                        \
@@ -334,9 +372,14 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
             TILE_LEVEL(11, 12, v9, v10,                                                                          \
             TILE_LEVEL(13, 14, v11, v12,                                                                         \
                 TILE_ADD(v13); TILE_ADD(v14);                                                                    \
-                for (uint32_t k = T_NE; k < K__; k++) { /* rare: a slice with more than T_NE entries per cell */ \
+                const uint32_t n16__ = K__ + (K__ & 1u); /* u16 per row */                                       \
+                for (uint32_t i = T_ROW_U16; i < n16__; i++) { /* rare: a slice whose rows are longer than the registers */ \
                     tab_t v__;                                                                                   \
-                    TILE_LOOKUP(v__, (uint32_t)(tiles + cur_base__ + lane * (K__ + 1u))[k + 1]);                 \
+                    uint32_t x__ = (tiles + cur_base__ + ((K__ & 1u) ? 0u : 64u) + lane * n16__)[i];             \
+                    /* (a value the compiler knows to be 16 bits wide gets SDWA forms, whose constant operands — 1, 15 — */ \
+                    /*  then sit in two VGPRs for the whole kernel) */                                           \
+                    asm volatile("" : "+v"(x__));                                                                \
+                    TILE_LOOKUP(v__, x__);                                                                       \
                     TILE_ADD(v__);                                                                               \
                 } ))))))                                                                                         \
         } else TILE_ADD(v0);                                                                                     \
@@ -346,6 +389,7 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
         else acc__ += a_ll__;                                                                                    \
         if (TILE_ABL != 8 || a_ll__ == 12345.678) s_acc[(S) * T_BC + (TILE_ABL == 6 ? tid : cell__)] = acc__;   \
         }                                                                                                        \
+        CELL_LOAD(E);                                                                                            \
     } while (0)
 
     static_assert(T_SB == 2 || T_SB == 4, "even and odd steps use different pipeline buffers");
@@ -420,6 +464,7 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
 #undef TILE_ADD
 #undef TILE_RD
 #undef TILE_LOOKUP
+#undef CELL_LOAD
 #undef ROW_LOAD
 #undef HDR_LOAD
 #undef TABLE_PREFETCH

@@ -16,8 +16,9 @@ __device__ __forceinline__ uint64_t row_lower_bound(const uint64_t *__restrict__
 }
 
 // One 1024-thread block per tile, thread = cell of the block.  The cells are ordered by their number of regular entries
-// in this chunk (stable counting sort: deterministic layout), every 64 of them form a slice of 64 rows [cell, K entries]
-// with K = the slice's longest cell rounded up to odd.  FILL = false: tile size; FILL = true: write slices + header.
+// in this chunk (stable counting sort: deterministic layout), every 64 of them form a slice of 64 cell ids and 64 rows of K
+// entries, K = the slice's longest cell (at least 1), in the format of K's parity (tiled.h).  FILL = false: tile size; FILL =
+// true: write slices + header.
 // which entries a tile set takes, and their 16-bit form inside chunk j
 template <class G>
 __device__ __forceinline__ bool geo_take(uint64_t e)
@@ -100,13 +101,13 @@ __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj,
         uint32_t acc = 0;
         for (int w = 0; w < T_BC / 64; w++) {
             s_sbase[w] = acc;
-            acc += 64u * ((s_kmax[w] | 1u) + 1u);
+            acc += 64u * (slice_k(s_kmax[w]) + 1u);
         }
         s_sbase[T_BC / 64] = acc;
     }
     __syncthreads();
     if (!FILL) {
-        if (cl == 0) tile_elems[t] = (uint64_t)s_sbase[T_BC / 64];  // a multiple of 128 u16
+        if (cl == 0) tile_elems[t] = (uint64_t)s_sbase[T_BC / 64];  // a multiple of 64 u16
         return;
     }
     const uint64_t tbase = tile_elems[t];
@@ -116,18 +117,18 @@ __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj,
         const uint64_t first = tbase + s_sbase[cl];
         hd[0] = (uint32_t)first;
         hd[1] = (uint32_t)(first >> 32);
-        hd[2] = s_kmax[cl] | 1u;  // K: padded entries per cell of the slice (odd: a row is K + 1 u16)
+        hd[2] = slice_k(s_kmax[cl]);  // K: padded entries per cell of the slice
         hd[3] = s_kmax[cl] == 0u;  // no row of the slice has an entry (the nearly empty tier-2 tiles of a deep matrix: most slices)
     }
-    const uint32_t K = s_kmax[dw] | 1u;
-    uint16_t *dst = tiles + tbase + s_sbase[dw] + dl * (K + 1u);  // this cell's row
-    dst[0] = (uint16_t)cl;
+    const uint32_t K = slice_k(s_kmax[dw]);
+    uint16_t *sl = tiles + tbase + s_sbase[dw], *dst = sl + slice_row_at(K, dl);  // this cell's slice and its row's entries
+    sl[slice_cell_at(K, dl)] = (uint16_t)cl;
     uint32_t k = 0;
     for (uint64_t i = lo; i < hi; i++) {
         const uint64_t e = csr_ent[i];
-        if (geo_take<G>(e)) dst[1 + k++] = geo_encode<G>(e, j);
+        if (geo_take<G>(e)) dst[k++] = geo_encode<G>(e, j);
     }
-    for (; k < K; k++) dst[1 + k] = (uint16_t)(G::BLU << G::SHIFT);  // padding: the chunk's all-zero slot
+    for (; k < K; k++) dst[k] = (uint16_t)(G::BLU << G::SHIFT);  // padding: the chunk's all-zero slot
 }
 
 // Bank-aware order of the entries inside the rows of one slice (option "bank_order"; a wave per slice, lane = row, the slice's rows
@@ -157,10 +158,10 @@ __device__ __forceinline__ void tbo_banks(uint32_t e, uint32_t *a, uint32_t *b)
 // quad of a read group.  Here the slice's rows are ranked by (cell mod 16, lane) and dealt round-robin to the four read groups,
 // the second and fourth group shifted by half a group so that two rows of one class never share a write group either: classes of
 // up to four rows (the average) become conflict-free.  Returns the row count that now belongs to this lane.
-__device__ uint32_t tile_lane_assign(uint16_t *slice /*64 rows of Kw + 1 u16*/, uint32_t Kw, uint32_t lane, uint32_t cnt, uint32_t *scr)
+__device__ uint32_t tile_lane_assign(uint16_t *slice /*64 x (Kw + 1) u16, either format*/, uint32_t Kw, uint32_t lane, uint32_t cnt, uint32_t *scr)
 {
 #define TLA_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-    const uint32_t cls = (uint32_t)slice[lane * (Kw + 1u)] & 15u;
+    const uint32_t cls = (uint32_t)slice[slice_cell_at(Kw, lane)] & 15u;
     const unsigned long long lt = (1ull << lane) - 1ull;
     uint32_t t = 0;
 #pragma unroll
@@ -178,10 +179,10 @@ __device__ uint32_t tile_lane_assign(uint16_t *slice /*64 rows of Kw + 1 u16*/, 
     scr[64 + dst] = cnt;
     TLA_SYNC();
     const uint32_t src = scr[lane], cnt_new = scr[64 + lane];
-    for (uint32_t k = 0; k <= Kw; k++) {  // column by column: all of a column's reads before its writes
-        const uint16_t v = slice[src * (Kw + 1u) + k];
+    for (uint32_t k = 0; k <= Kw; k++) {  // column by column (the cell ids, then entry k - 1): all of a column's reads before its writes
+        const uint16_t v = slice[k ? slice_row_at(Kw, src) + k - 1u : slice_cell_at(Kw, src)];
         TLA_SYNC();
-        slice[lane * (Kw + 1u) + k] = v;
+        slice[k ? slice_row_at(Kw, lane) + k - 1u : slice_cell_at(Kw, lane)] = v;
         TLA_SYNC();
     }
     return cnt_new;
@@ -334,12 +335,12 @@ __global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t
                 uint32_t acc = 0;
                 for (int w = 0; w < T_BC / 64; w++) {
                     s_sbase[w] = acc;
-                    acc += 64u * ((s_kmax[w] | 1u) + 1u);
+                    acc += 64u * (slice_k(s_kmax[w]) + 1u);
                 }
                 s_sbase[T_BC / 64] = acc;
             }
             __syncthreads();
-            const uint32_t total = s_sbase[T_BC / 64];  // a multiple of 128 u16
+            const uint32_t total = s_sbase[T_BC / 64];  // a multiple of 64 u16
             if (!FILL) {
                 if (cl == 0) tile_elems[t] = (uint64_t)total;
             } else {
@@ -349,20 +350,20 @@ __global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t
                     const uint64_t first = tbase + s_sbase[cl];
                     hd[0] = (uint32_t)first;
                     hd[1] = (uint32_t)(first >> 32);
-                    hd[2] = s_kmax[cl] | 1u;
+                    hd[2] = slice_k(s_kmax[cl]);
                     hd[3] = s_kmax[cl] == 0u;
                 }
-                const uint32_t K = s_kmax[dw] | 1u;
+                const uint32_t K = slice_k(s_kmax[dw]);
                 const bool staged = total <= (uint32_t)TB_STAGE;  // (uniform)
-                uint16_t *dst = (staged ? s_tile : tiles + tbase) + s_sbase[dw] + dl * (K + 1u);
-                dst[0] = (uint16_t)cl;
+                uint16_t *sl = (staged ? s_tile : tiles + tbase) + s_sbase[dw], *dst = sl + slice_row_at(K, dl);
+                sl[slice_cell_at(K, dl)] = (uint16_t)cl;
                 uint32_t k = 0;
                 const uint32_t cbase = (j * (uint32_t)T_BLU) & (LR_LOCI - 1u);
 #define TB_PUT(E)                                                                                                       \
                 do {                                                                                                   \
                     const uint32_t e__ = (E), code__ = e__ >> 12;                                                      \
                     if (code__ < (uint32_t)T_NCODE)                                                                    \
-                        dst[1 + k++] = (uint16_t)(((uint32_t)T_NM1_OF[code__] << 14) |                                 \
+                        dst[k++] = (uint16_t)(((uint32_t)T_NM1_OF[code__] << 14) |                                     \
                                                   ((((e__ & (LR_LOCI - 1u)) - cbase) & (LR_LOCI - 1u)) << 4) | code__); \
                 } while (0)
 #pragma unroll
@@ -370,16 +371,16 @@ __global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t
                 for (uint64_t i = lo + TB_SEG; i < hi; i++) TB_PUT((uint32_t)c4r[i]);
 #undef TB_PUT
                 if (ORDER) s_rcnt[rank] = (uint16_t)k;
-                for (; k < K; k++) dst[1 + k] = T_NULL;
+                for (; k < K; k++) dst[k] = T_NULL;
                 if (staged) {
                     __syncthreads();
                     if (ORDER) {  // wave wv = slice wv, lane = row
-                        const uint32_t Kw = s_kmax[wv] | 1u;
+                        const uint32_t Kw = slice_k(s_kmax[wv]);
                         const uint32_t rc = tile_lane_assign(s_tile + s_sbase[wv], Kw, lane, s_rcnt[wv * 64 + lane], s_scr + wv * 256);
-                        tile_bank_order(s_tile + s_sbase[wv] + lane * (Kw + 1u) + 1u, Kw, rc, lane, s_scr + wv * 256);
+                        tile_bank_order(s_tile + s_sbase[wv] + slice_row_at(Kw, lane), Kw, rc, lane, s_scr + wv * 256);
                         __syncthreads();
                     }
-                    uint4 *out = reinterpret_cast<uint4 *>(tiles + tbase);  // (tile starts are multiples of 128 u16)
+                    uint4 *out = reinterpret_cast<uint4 *>(tiles + tbase);  // (tile starts and sizes are multiples of 64 u16)
                     const uint4 *in = reinterpret_cast<const uint4 *>(s_tile);
                     for (uint32_t i = cl; i < total / 8u; i += T_BC) out[i] = in[i];
                 }
@@ -664,7 +665,7 @@ static void launch_tile_build(cellector_ctx *c, uint64_t nt, uint32_t nj, const 
 
 // ---- tier-2 tiles (deep coverage): a second tile set over the overflow CSR's entries with totals 5..G::NHI ----
 // Built with the per-tile builder (the overflow rows are short); the rows keep
-// their file order.  A tile holds all 1024 rows of its block, most of them with one padding entry: 4 bytes per row.
+// their file order.  A tile holds all 1024 rows of its block, most of them with one padding entry: 4 bytes per row (K = 1).
 template <class G>
 static cellector_status t2_tiles_build(cellector_ctx *c)
 {

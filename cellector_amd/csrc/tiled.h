@@ -24,14 +24,25 @@ static_assert(T_BC == T_ROWS_PER_TILE, "cellector_engine_info derives the lookup
 #define T_GROUPS_MAX 64 // upper bound of the chunk groups of a launch
 static_assert(T_GROUPS_MAX == CELLECTOR_TILE_WORK_STRIDE, "k_alpha_beta resets the counters with this stride");
 #define T_GROUPS 8      // chunk groups beyond this many are charged for their partial sums (tiled_build's cost model)
-#define T_NE 15         // entries per cell of a slice held in registers (two 16-byte loads); longer slices: slow path
+#define T_ROW_U16 16    // u16 of a row held in registers (two 16-byte loads): 15 entries behind the cell id (K odd) or 16 (K even);
+                        // longer rows: slow path
 // A u16 entry = n-1 << 14 | locus slot << 4 | code; where its log-pmf and its expected term sit in the chunk's table is the
 // geometry's business (tab_pmf / tab_exp below).
 #define T_NULL ((uint16_t)(T_BLU << 4))  // padding entry: code 0, n-1 = 0 of the zero slot
-// A slice in `tiles` is 64 rows of K+1 u16 (K odd): row i = [cell (0..1023) that lane i works for, K entries of that cell,
-// padded with T_NULL].  Tile header (fixed stride, in u16 units): 16 slices x {u64 first u16 of the slice in `tiles`,
-// u32 K, u32 pad}.
+// A slice in `tiles` is 64 x (K + 1) u16, K = the entries of its longest row, at least 1 (every geometry: a slice without any
+// entry keeps one padding entry per row, 256 bytes, and the kernels need no form for an empty row; the tier-2 kernels skip it by
+// the header's flag).  Rows must start on a dword for the 16-byte loads, so the format follows from K's parity:
+//   K odd   64 rows of K + 1 u16: row i = [cell (0..1023) that lane i works for, K entries of that cell];
+//   K even  the 64 cell ids first (u16 i = lane i's cell), then 64 rows of K u16: the entries alone.
+// Rows are padded with T_NULL to K entries.  Either way a slice is 128 (K + 1) bytes, starts on a 128-byte boundary, and dword
+// p >= 1 of a row holds two consecutive entries; dword 0 holds the cell id and entry 0 (odd) or entries 0 and 1 (even).
+// Tile header (fixed stride, in u16 units): 16 slices x {u64 first u16 of the slice in `tiles`, u32 K, u32 1 = the slice has no
+// entry at all}.
 #define T_HDR 128
+// u16 inside a slice: of row r's cell id, of its first entry; u16 of a row
+__host__ __device__ __forceinline__ constexpr uint32_t slice_cell_at(uint32_t K, uint32_t r) { return (K & 1u) ? r * (K + 1u) : r; }
+__host__ __device__ __forceinline__ constexpr uint32_t slice_row_at(uint32_t K, uint32_t r) { return (K & 1u) ? r * (K + 1u) + 1u : 64u + r * K; }
+__host__ __device__ __forceinline__ constexpr uint32_t slice_k(uint32_t longest) { return longest ? longest : 1u; }
 #define TAB_ELEMS ((uint64_t)T_LROW * T_BL)  // table doubles per chunk
 
 __device__ __forceinline__ bool ent_regular(uint64_t e)

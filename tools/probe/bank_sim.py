@@ -47,7 +47,7 @@ def slices_of(rows):
     out = []
     for s in range(16):
         rs = [rows[i] for i in order[s * 64:(s + 1) * 64]]
-        K = max(len(r) for r in rs) | 1
+        K = max(max(len(r) for r in rs), 1)  # the slice's longest row, either parity (csrc/tiled.h)
         out.append((rs, K))
     return out
 
