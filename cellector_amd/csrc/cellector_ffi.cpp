@@ -1534,6 +1534,87 @@ cellector_status cellector_refine_class_doublets(cellector_ctx *c, uint8_t *labe
     return st;
 }
 
+// ---- genotype clusters without labels: kernels_cluster.hip ----------------------------------------------------
+cellector_status cellector_cluster_default_params(cellector_cluster_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->theta_floor = 0.01;
+    out->anneal_base = 20.0;
+    out->tol = 0.01;
+    out->anneal_steps = 9;
+    out->max_iter = 50;
+    out->min_loci = 1;
+    return CELLECTOR_OK;
+}
+
+// what every cluster call checks before anything is written or launched
+static cellector_status cluster_call_check(cellector_ctx *c, const char *what, double theta_floor)
+{
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    if (!(theta_floor > 0.0 && theta_floor < 0.5))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: theta_floor = %g is not within (0, 0.5)", what, theta_floor);
+    return CELLECTOR_OK;
+}
+static cellector_status cluster_columns_check(cellector_ctx *c, const char *what, uint32_t K, uint32_t R)
+{
+    if (K < 2 || K > 16) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u clusters, 2..16 are supported", what, K);
+    if (R < 1) return ctx_fail(c, CELLECTOR_EINVAL, "%s: at least one restart is needed", what);
+    if ((uint64_t)K * R > 64) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u clusters x %u restarts = %llu columns, at most 64 are supported", what, K, R,
+                                              (unsigned long long)K * R);
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_cluster(cellector_ctx *c, uint32_t n_clusters, uint32_t n_restarts, uint64_t seed, const cellector_cluster_params *p,
+                                   const uint8_t *mask, uint8_t *labels, double *ll, double *posterior, double *theta, double *objective,
+                                   cellector_cluster_summary *out)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_cluster_params prm;
+    cellector_cluster_default_params(&prm);
+    if (p) prm = *p;
+    CHK(cluster_call_check(c, "cluster", prm.theta_floor));
+    CHK(cluster_columns_check(c, "cluster", n_clusters, n_restarts));
+    if (prm.anneal_steps < 1 || prm.anneal_steps > 16)
+        return ctx_fail(c, CELLECTOR_EINVAL, "cluster: anneal_steps = %u is not within 1..16", prm.anneal_steps);
+    if (!std::isfinite(prm.anneal_base) || prm.anneal_base <= 0.0)
+        return ctx_fail(c, CELLECTOR_EINVAL, "cluster: anneal_base = %g is not a finite value > 0", prm.anneal_base);
+    if (!std::isfinite(prm.tol) || prm.tol <= 0.0) return ctx_fail(c, CELLECTOR_EINVAL, "cluster: tol = %g is not a finite value > 0", prm.tol);
+    REQUIRE(c, prm.min_loci >= 1, "cluster: min_loci must be at least 1");
+    SETDEV(c);
+    return cluster_run(c, n_clusters, n_restarts, seed, &prm, mask, labels, ll, posterior, theta, objective, out);
+}
+
+cellector_status cellector_cluster_m_step(cellector_ctx *c, const double *w, uint32_t J, const uint8_t *mask, double theta_floor, double *A,
+                                          double *T, double *theta, double *tab)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(cluster_call_check(c, "cluster_m_step", theta_floor));
+    if (J < 1 || J > 64) return ctx_fail(c, CELLECTOR_EINVAL, "cluster_m_step: %u columns, 1..64 are supported", J);
+    REQUIRE(c, w != nullptr, "cluster_m_step: null w");
+    for (uint64_t i = 0, n = c->nloc * J; i < n; i++)
+        if (!(w[i] >= 0.0))
+            return ctx_fail(c, CELLECTOR_EINVAL, "cluster_m_step: w of cell %llu, column %llu is %g: neither NaN nor a negative value is a weight",
+                            (unsigned long long)(i / J), (unsigned long long)(i % J), w[i]);
+    SETDEV(c);
+    return cluster_m_step_run(c, w, J, mask, theta_floor, A, T, theta, tab);
+}
+
+cellector_status cellector_cluster_e_step(cellector_ctx *c, const double *tab, uint32_t K, uint32_t R, const double *temp, const uint8_t *mask,
+                                          double *s, double *w, double *objective)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(cluster_call_check(c, "cluster_e_step", 0.25));
+    CHK(cluster_columns_check(c, "cluster_e_step", K, R));
+    REQUIRE(c, tab != nullptr, "cluster_e_step: null tab");
+    for (uint64_t i = 0; temp && i < c->nloc; i++)
+        if (!(temp[i] >= 1.0))
+            return ctx_fail(c, CELLECTOR_EINVAL, "cluster_e_step: temp of cell %llu is %g: a temperature is a value >= 1", (unsigned long long)i, temp[i]);
+    SETDEV(c);
+    return cluster_e_step_run(c, tab, K, R, temp, mask, s, w, objective);
+}
+
 // ---- class genotypes: kernels_genotypes.hip and genotype_host.h ---------------------------------------------
 // load_mtx_final + the rule of output_final_vcf (main.rs:52-131) for the K classes of a labelling
 cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, double ambient, double gt_threshold,

@@ -552,6 +552,15 @@ cellector_status class_doublets_run(cellector_ctx *c, const uint8_t *labels, con
                                     double threshold, uint32_t max_iter, uint64_t min_loci, uint8_t *labels_out, uint8_t *held_out,
                                     cellector_refine_doublets_summary *sum, double *ll, double *ll_pair, double *posterior,
                                     double *doublet_posterior, uint8_t *best, uint8_t *best_pair, uint8_t *call, uint64_t *qual);
+// genotype clusters without labels (kernels_cluster.hip) on one device holding all cells; validated arguments, host arrays, scratch
+// of their own (the by-locus list included), nothing of the ctx written: one M step + tables, one E step, the annealed EM over R restarts
+cellector_status cluster_m_step_run(cellector_ctx *c, const double *w, uint32_t J, const uint8_t *mask, double floor, double *A, double *T,
+                                    double *theta, double *tab);
+cellector_status cluster_e_step_run(cellector_ctx *c, const double *tab, uint32_t K, uint32_t R, const double *temp, const uint8_t *mask,
+                                    double *s, double *w, double *objective);
+cellector_status cluster_run(cellector_ctx *c, uint32_t K, uint32_t R, uint64_t seed, const cellector_cluster_params *p, const uint8_t *mask,
+                             uint8_t *labels, double *ll, double *posterior, double *theta, double *objective,
+                             cellector_cluster_summary *out);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
 cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);

@@ -84,6 +84,10 @@ SIGNATURES = {
     "cellector_refine_class_doublets": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint32, _u64]
                                         + [_vp] * 7),
     "cellector_class_genotypes": (_i, [_vp, _vp, C.c_uint32, _d, _d] + [_vp] * 6),
+    "cellector_cluster_default_params": (_i, [_vp]),
+    "cellector_cluster": (_i, [_vp, C.c_uint32, C.c_uint32, _u64] + [_vp] * 8),
+    "cellector_cluster_m_step": (_i, [_vp, _vp, C.c_uint32, _vp, _d] + [_vp] * 4),
+    "cellector_cluster_e_step": (_i, [_vp, _vp, C.c_uint32, C.c_uint32] + [_vp] * 5),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -127,6 +131,16 @@ class RefineSummary(C.Structure):
 class RefineDoubletsSummary(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("converged", C.c_uint32), ("n_moved_last", _u64), ("n_moved_total", _u64),
                 ("n_recounts", _u64), ("class_cells", _u64 * 16), ("n_held", _u64)]
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("theta_floor", _d), ("anneal_base", _d), ("tol", _d), ("anneal_steps", C.c_uint32), ("max_iter", C.c_uint32),
+                ("min_loci", _u64)]
+
+
+class ClusterSummary(C.Structure):
+    _fields_ = [("best_restart", C.c_uint32), ("iterations", C.c_uint32), ("stages", C.c_uint32), ("reserved", C.c_uint32),
+                ("iterations_per_stage", C.c_uint32 * 16), ("cluster_cells", _u64 * 16), ("n_unlabelled", _u64)]
 
 
 class CellectorError(RuntimeError):
@@ -734,6 +748,73 @@ class Cellector:
         self._ck(self._lib.cellector_class_genotypes(self.h, _p(labels), K, float(ambient), float(gt_threshold), _p(cells), _p(alt),
                                                      _p(ref), _p(out.get("gt")), _p(out.get("gp")), _p(out.get("gp3"))))
         return out
+
+    # ---- genotype clusters without labels: a binomial mixture by annealed soft EM over restarts; cluster.py is the numpy twin
+    def _cluster_mask(self, mask):
+        L = self.dims().loci_used
+        mask = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask is not None and mask.shape != (L,):
+            raise ValueError(f"mask: {L} entries expected, got shape {mask.shape}")
+        return mask
+
+    def cluster_default_params(self):
+        p = ClusterParams()
+        self._ck(self._lib.cellector_cluster_default_params(C.byref(p)))
+        return p
+
+    def cluster(self, n_clusters, n_restarts=None, seed=4, mask=None, **params):
+        """K genotype clusters of the loaded matrix without any labels (cellector_cluster): n_restarts random starts side by side
+        (None: min(16, 64 // K)), the best returned.  params: theta_floor, anneal_base, tol, anneal_steps, max_iter, min_loci
+        (ClusterParams; the library's defaults otherwise).  Returns a dict: labels [cells] uint8 (255: fewer than min_loci
+        entries), ll [K, cells], posterior [K, cells], theta [K, L], objective [R] and summary (ClusterSummary)."""
+        K = int(n_clusters)
+        R = min(16, 64 // max(K, 1)) if n_restarts is None else int(n_restarts)
+        p = self.cluster_default_params()
+        for k, v in params.items():
+            if k not in dict(ClusterParams._fields_):
+                raise TypeError(f"cluster: unknown parameter {k!r}")
+            setattr(p, k, v)
+        mask = self._cluster_mask(mask)
+        Ka, Ra = min(max(K, 0), 16), min(max(R, 0), 64)
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used  # (before a load the library refuses the call)
+        labels, ll, post = np.zeros(n, np.uint8), np.zeros((Ka, n), np.float64), np.zeros((Ka, n), np.float64)
+        theta, obj, s = np.zeros((Ka, L), np.float64), np.zeros(Ra, np.float64), ClusterSummary()
+        self._ck(self._lib.cellector_cluster(self.h, max(K, 0), max(R, 0), int(seed), C.byref(p), _p(mask), _p(labels), _p(ll), _p(post),
+                                             _p(theta), _p(obj), C.byref(s)))
+        return dict(labels=labels, ll=ll, posterior=post, theta=theta, objective=obj, summary=s)
+
+    def cluster_m_step(self, w, mask=None, theta_floor=0.01):
+        """One M step from weights w [cells, J] and the tables of its theta (cellector_cluster_m_step): dict of A, T, theta [J, L]
+        and tab [L, J, 2] = (log theta, log(1 - theta))."""
+        w = np.ascontiguousarray(w, np.float64)
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used
+        if w.ndim != 2 or (self.dims().total_cells and w.shape[0] != n):
+            raise ValueError(f"w: shape ({n}, J) expected, got {w.shape}")
+        J = w.shape[1]
+        Ja = min(J, 64)
+        mask = self._cluster_mask(mask)
+        A, T, theta = (np.zeros((Ja, L), np.float64) for _ in range(3))
+        tab = np.zeros((L, Ja, 2), np.float64)
+        self._ck(self._lib.cellector_cluster_m_step(self.h, _p(w), J, _p(mask), float(theta_floor), _p(A), _p(T), _p(theta), _p(tab)))
+        return dict(A=A, T=T, theta=theta, tab=tab)
+
+    def cluster_e_step(self, tab, n_clusters, n_restarts=1, temp=None, mask=None):
+        """One E step on the caller's tables tab [L, J, 2], J = K R (cellector_cluster_e_step): dict of s, w [cells, J] and
+        objective [R]; temp [cells] >= 1 or None = 1 for every cell."""
+        K, R = int(n_clusters), int(n_restarts)
+        tab = np.ascontiguousarray(tab, np.float64)
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used
+        J = K * R
+        if 0 < J <= 64 and self.dims().total_cells and tab.shape != (L, J, 2):
+            raise ValueError(f"tab: shape ({L}, {J}, 2) expected, got {tab.shape}")
+        temp = None if temp is None else np.ascontiguousarray(temp, np.float64)
+        if temp is not None and temp.shape != (n,):
+            raise ValueError(f"temp: {n} values expected, got shape {temp.shape}")
+        mask = self._cluster_mask(mask)
+        Ja = min(max(J, 0), 64)
+        s, w, obj = np.zeros((n, Ja), np.float64), np.zeros((n, Ja), np.float64), np.zeros(min(max(R, 0), 64), np.float64)
+        self._ck(self._lib.cellector_cluster_e_step(self.h, _p(tab), max(K, 0), max(R, 0), _p(temp), _p(mask), _p(s), _p(w), _p(obj)))
+        return dict(s=s, w=w, objective=obj)
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

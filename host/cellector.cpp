@@ -195,6 +195,10 @@ struct Params {
     uint64_t refine_classes = 0;                       // hard-EM steps at most (0: score the given labelling only)
     bool class_doublets = false;                       // the pairs' doublet classes beside them (cellector_class_doublets)
     bool class_genotypes = false;                      // cellector_classes.vcf: the classes' genotypes (cellector_class_genotypes)
+    // extension: K genotype clusters without labels after the ordinary run (cellector_cluster; one GPU)
+    uint64_t cluster = 0;                              // K (0: off)
+    uint64_t cluster_restarts = 0;                     // R (0: min(16, 64 / K))
+    bool cluster_mask_loop = false;                    // --cluster_mask loop: the loci the loop's last iteration used (all: every used locus)
 };
 
 const char *USAGE =
@@ -307,7 +311,20 @@ const char *USAGE =
     "                                                                       class_assignment is that class (doublet and unassigned cells\n"
     "                                                                       are in none), and cellector_class_concordance.tsv: per pair of\n"
     "                                                                       classes the loci both are called at and those where the calls\n"
-    "                                                                       differ (default false; one GPU)\n";
+    "                                                                       differ (default false; one GPU)\n"
+    "        --cluster <K>                                                      after the ordinary run, fit K genotype clusters (2..16) without\n"
+    "                                                                       any labels: a binomial mixture by annealed soft EM over random\n"
+    "                                                                       restarts (--seed is shared).  Writes <output_directory>/\n"
+    "                                                                       cellector_clusters.tsv: barcode, cluster (0..K-1, unassigned for a\n"
+    "                                                                       cell without an entry), the K posteriors, the K log-likelihoods.\n"
+    "                                                                       Without --classes the clusters are the classes of\n"
+    "                                                                       --refine_classes, --class_doublets and --class_genotypes; with\n"
+    "                                                                       --classes it is a usage error.  No other output changes (not in\n"
+    "                                                                       the reference; one GPU)\n"
+    "        --cluster_restarts <R>                                             with --cluster: random restarts run side by side, K R <= 64\n"
+    "                                                                       (default min(16, 64 / K))\n"
+    "        --cluster_mask <all|loop>                                          with --cluster: fit on every used locus, or on the loci the\n"
+    "                                                                       loop's last iteration used (default all)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -335,7 +352,7 @@ Params load_params(int argc, char **argv)
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
-                                  "class_doublets", "class_genotypes"};
+                                  "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -419,22 +436,41 @@ Params load_params(int argc, char **argv)
     }
     if (got.count("seed")) p.seed = parse_usize("seed", got["seed"]);
     if (got.count("classes")) p.classes = got["classes"];
+    if (got.count("cluster")) {
+        p.cluster = parse_usize("cluster", got["cluster"]);
+        if (p.cluster < 2 || p.cluster > 16) die(1, "error: Invalid value '" + got["cluster"] + "' for '--cluster <K>': expected 2..16");
+        if (p.classes) die(1, "error: The argument '--cluster <K>' cannot be used with '--classes <file>'");
+        if (p.devices_auto || p.devices.size() > 1)
+            die(1, "error: The argument '--cluster <K>' works on one GPU and cannot be used with '--devices <a,b,...>'");
+    }
+    if (got.count("cluster_restarts")) {
+        p.cluster_restarts = parse_usize("cluster_restarts", got["cluster_restarts"]);
+        if (!p.cluster) die(1, "error: The argument '--cluster_restarts <R>' requires '--cluster <K>'");
+        if (p.cluster_restarts < 1 || p.cluster_restarts * p.cluster > 64)
+            die(1, "error: Invalid value '" + got["cluster_restarts"] + "' for '--cluster_restarts <R>': expected 1..64 / K");
+    }
+    if (got.count("cluster_mask")) {
+        const std::string &v = got["cluster_mask"];
+        if (v != "all" && v != "loop") die(EXIT_PANIC, "invalid value '" + v + "' for --cluster_mask: expected all or loop");
+        if (!p.cluster) die(1, "error: The argument '--cluster_mask <all|loop>' requires '--cluster <K>'");
+        p.cluster_mask_loop = v == "loop";
+    }
     if (got.count("class_doublets")) {
         const std::string &v = got["class_doublets"];
         if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --class_doublets: expected true or false");
         p.class_doublets = v == "true";
-        if (p.class_doublets && !p.classes) die(1, "error: The argument '--class_doublets true' requires '--classes <file>'");
+        if (p.class_doublets && !p.classes && !p.cluster) die(1, "error: The argument '--class_doublets true' requires '--classes <file>'");
     }
     if (got.count("class_genotypes")) {
         const std::string &v = got["class_genotypes"];
         if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --class_genotypes: expected true or false");
         p.class_genotypes = v == "true";
-        if (p.class_genotypes && !p.classes) die(1, "error: The argument '--class_genotypes true' requires '--classes <file>'");
+        if (p.class_genotypes && !p.classes && !p.cluster) die(1, "error: The argument '--class_genotypes true' requires '--classes <file>'");
         if (p.class_genotypes && !p.vcf) die(1, "error: The argument '--class_genotypes true' requires '--vcf <vcf>'");
     }
     if (got.count("refine_classes")) {
         p.refine_classes = parse_usize("refine_classes", got["refine_classes"]);
-        if (!p.classes) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
+        if (!p.classes && !p.cluster) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
         if (p.refine_classes > 0xffffffffull) die(1, "error: Invalid value '" + got["refine_classes"] + "' for '--refine_classes <max_iter>'");
     }
     if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
@@ -1170,9 +1206,49 @@ int main(int argc, char **argv)
         sb += std::string(xoffset, ' ') + "|" + std::string(header.size() - 1, '-') + "|\n";
         printf("\n\n%s\n", sb.c_str());
     }
-    // --classes / --refine_classes: the K-class posteriors of every cell under the file's labelling, refined one step at a time so
-    // that every step gets its stderr line; then the scoring of the labelling in force
-    if (params.classes) {
+    // --cluster: K genotype clusters of the matrix the run ended on, without labels; with one of the class flags they become the
+    // classes of the block below
+    if (params.cluster) {
+        const uint32_t K = (uint32_t)params.cluster;
+        const uint32_t R = params.cluster_restarts ? (uint32_t)params.cluster_restarts : std::min<uint32_t>(16, 64 / K);
+        std::vector<uint8_t> lmask;
+        if (params.cluster_mask_loop) {
+            lmask.resize(dm.loci_used);
+            g.ck(cellector_loci_mask(g.c, lmask.data()), "loci_mask");
+        }
+        std::vector<uint8_t> lab(N);
+        std::vector<double> kll((uint64_t)K * N), kpost((uint64_t)K * N), obj(R);
+        cellector_cluster_summary cs;
+        g.ck(cellector_cluster(g.c, K, R, params.seed, nullptr, params.cluster_mask_loop ? lmask.data() : nullptr, lab.data(), kll.data(),
+                               kpost.data(), nullptr, obj.data(), &cs), "cluster");
+        std::string msg = "cluster: restart " + std::to_string(cs.best_restart) + " of " + std::to_string(R) + ", " +
+                          std::to_string(cs.iterations) + " iterations, cluster sizes";
+        for (uint32_t k = 0; k < K; k++) msg += " " + std::to_string(k) + "=" + std::to_string(cs.cluster_cells[k]);
+        msg += " unassigned=" + std::to_string(cs.n_unlabelled);
+        fprintf(stderr, "%s\n", msg.c_str());
+        FILE *f = create(od + "/cellector_clusters.tsv");
+        std::string head = "barcode\tcluster";
+        for (uint32_t k = 0; k < K; k++) head += "\tposterior_" + std::to_string(k);
+        for (uint32_t k = 0; k < K; k++) head += "\tlog_likelihood_" + std::to_string(k);
+        head += '\n';
+        fputs(head.c_str(), f);
+        write_rows(f, N, [&](uint64_t c, std::string &o) {
+            o += barcodes[c]; o += '\t';
+            if (lab[c] == 255) o += "unassigned";
+            else put(o, (uint64_t)lab[c]);
+            for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, kpost[(uint64_t)k * N + c]); }
+            for (uint32_t k = 0; k < K; k++) { o += '\t'; put(o, kll[(uint64_t)k * N + c]); }
+            o += '\n';
+        });
+        fclose(f);
+        lap("cellector_clusters.tsv");
+        class_label = lab;
+        class_names.clear();
+        for (uint32_t k = 0; k < K; k++) class_names.push_back(std::to_string(k));
+    }
+    // --classes / --refine_classes: the K-class posteriors of every cell under the file's labelling (or --cluster's), refined one step
+    // at a time so that every step gets its stderr line; then the scoring of the labelling in force
+    if (params.classes || (params.cluster && (params.refine_classes || params.class_doublets || params.class_genotypes))) {
         const uint32_t K = (uint32_t)class_names.size();
         std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), in_lab = lab, best(N);
         const bool dbl = params.class_doublets;

@@ -764,6 +764,81 @@ cellector_status cellector_class_genotypes(cellector_ctx *ctx, const uint8_t *la
                                            uint8_t *gt /*[K][total_loci]*/, double *gp /*[K][total_loci]*/,
                                            double *gp3 /*[K][total_loci][3]: q_alt, q_het, q_ref*/);   /* any output may be NULL */
 
+/* ---- genotype clusters without labels: a binomial mixture fitted by annealed soft EM ----------------------------
+ * Every class call above starts from labels the caller brings.  These calls make a labelling from the loaded matrix alone: K
+ * clusters, each a vector of per-locus alt-allele fractions, fitted by soft EM from random starts; a temperature that grows with a
+ * cell's depth flattens the first stages (deep cells would otherwise freeze the first partition they meet) and is annealed away;
+ * R restarts run side by side and the best is returned.  The result feeds cellector_refine_classes, cellector_class_doublets and
+ * cellector_class_genotypes.  The model below is the specification (cellector_amd/cluster.py repeats it in numpy); no parity with
+ * any other program is claimed.
+ *   K clusters, 2 <= K <= 16; R restarts, R >= 1; J = K R <= 64 columns, column j = r K + k; L used loci; mask [L] or NULL = all
+ *   loci, as in cellector_class_posteriors.  The entries of a cell are those of its by-cell CSR row (cellector_csr_rows) at used,
+ *   unmasked loci, in row order; a repeated (locus, cell) pair counts each time.  All arithmetic is f64 without contraction: every
+ *   product and every sum below rounds once.
+ *   1 depth: n_c = sum (alt + ref) over the cell's entries, an integer; e_c = the number of those entries.
+ *   2 start: u(l, j) = (mix64(mix64(seed GOLD + GOLD) + (l J + j + 1) GOLD) >> 11) 2^-53 with l the used-locus index, u64
+ *     arithmetic that wraps, mix64 = the splitmix64 finaliser and GOLD = 0x9E3779B97F4A7C15 (csrc/mix64.h);
+ *     theta_j[l] = theta_floor + (1.0 - 2.0 theta_floor) u.
+ *   3 tables: la_j[l] = log(theta_j[l]), lb_j[l] = log(1.0 - theta_j[l]) with the device's log, stored interleaved as [L][J][2].  A
+ *     masked locus takes no part anywhere: its table row is (0, 0), its A and T are 0, its theta is 0.5, and no sum visits it.
+ *   4 E step: s_cj = sum over the cell's entries in row order of ((alt la_j[l]) + (ref lb_j[l])): both products rounded, then their
+ *     sum, then that added to the accumulator, strictly sequential per (cell, column) from 0.0; the binomial coefficient is the same
+ *     in every column and is left out.  Within restart r: x_k = s_{c, rK+k} / T_c (IEEE division), m = max_k x_k, den = sum_k
+ *     exp(x_k - m) in ascending k from 0.0, w_{c, rK+k} = exp(x_k - m) / den, o_c = m + log(den).  Uniform priors (the class calls
+ *     add theirs later).  A cell without entries has s = 0, w = 1 / K.  obj_r = sum_c o_c: thread t of 256 adds the cells t, t + 256,
+ *     ... in ascending order, the 256 partial sums are folded pairwise (h = 128, 64, ... 1: p[t] += p[t + h]): the same bits from
+ *     run to run.
+ *   5 M step: A_j[l] = sum w_cj alt, T_j[l] = sum w_cj (alt + ref) over the locus' entries in ascending cell order, file order among
+ *     the repeats of a pair: the product rounded, then added, strictly sequential per (locus, column) from 0.0, no floating-point
+ *     atomics.  theta = min(max((A + 1.0) / (T + 2.0), theta_floor), 1.0 - theta_floor); a locus with no entry gets 0.5.
+ *   6 anneal: S = anneal_steps stages.  In stage s < S - 1, T_c = max(1.0, (double)n_c / (anneal_base 2^s)); in the last stage T_c =
+ *     1 for every cell.  A stage repeats the iteration (3 tables, 4 E step, 5 M step) until, from its second iteration on, every
+ *     restart's |obj_r - obj_r of the stage's previous iteration| < tol, or max_iter iterations have run (max_iter 0: none).  theta
+ *     carries over from stage to stage.  The host reads R doubles per iteration.
+ *   7 result: tables from the final theta and one E step at T = 1; l_r = obj_r - (double)N log((double)K) (the host's log, N = all
+ *     cells); best = the smallest r attaining the maximum.  Of that restart: ll [K][cells] = s, posterior [K][cells] = w,
+ *     labels [cells] = argmax_k s (the smallest k on ties), 255 for a cell with e_c < min_loci; theta [K][L].  objective [R] = l_r.
+ * Defaults (cellector_cluster_default_params): theta_floor 0.01, anneal_base 20, anneal_steps 9, tol 0.01, max_iter 50, min_loci 1.
+ * cellector_cluster_m_step and cellector_cluster_e_step are the two halves cellector_cluster iterates, for a caller's own EM (a
+ * start from a partial labelling, say): the M step takes weights w [cells][J] (any J in 1..64) and returns A, T, theta [J][L] and
+ * the tables of that theta [L][J][2]; the E step takes tables and returns s, w [cells][J] and obj [R], under temp [cells] or NULL
+ * = 1 for every cell.
+ * Scope as cellector_class_posteriors: a loaded matrix, no iteration in flight, engines 1 and 2, a single-device ctx that holds
+ * all cells.  CELLECTOR_EINVAL with a message, nothing written or launched, for these and for K outside 2..16, R == 0, K R > 64,
+ * J != K R (the E step; the M step: J outside 1..64), a theta_floor outside (0, 0.5), anneal_steps outside 1..16, a non-finite or
+ * non-positive anneal_base or tol, min_loci == 0, a NaN or negative value in w or temp, a temp < 1, NULL w / tab.  All device scratch
+ * is allocated before anything is launched: J * 40 B per cell and per locus and 8 B per entry for the by-locus list (a stable sort
+ * of the by-cell CSR by locus, 24 B per entry while it is built, released when the call returns; the step calls build it per
+ * call); on CELLECTOR_ENOMEM the ctx is as it was.  The calls never touch the EM state (the exclusion set, the loop's mask, the kept
+ * tallies, the iteration number: an interrupted EM loop continues with the same bits) and overwrite nothing of the ctx; they
+ * invalidate the caches cellector_cell_log_likelihoods invalidates. */
+typedef struct {
+    double theta_floor;     /* 0.01: theta stays in [floor, 1 - floor]                                              */
+    double anneal_base;     /* 20:   stage s divides a cell's depth by anneal_base 2^s                              */
+    double tol;             /* 0.01: a stage ends when no restart's objective moved by this much                   */
+    uint32_t anneal_steps;  /* 9:    stages, the last one at T = 1                                                  */
+    uint32_t max_iter;      /* 50:   iterations per stage at most                                                   */
+    uint64_t min_loci;      /* 1:    a cell with fewer entries at used, unmasked loci is labelled 255               */
+} cellector_cluster_params;
+typedef struct {
+    uint32_t best_restart, iterations, stages, reserved;  /* iterations: over all stages                           */
+    uint32_t iterations_per_stage[16];
+    uint64_t cluster_cells[16];  /* labelled cells per cluster of the best restart                                  */
+    uint64_t n_unlabelled;       /* cells labelled 255                                                              */
+} cellector_cluster_summary;
+cellector_status cellector_cluster_default_params(cellector_cluster_params *out);
+cellector_status cellector_cluster(cellector_ctx *ctx, uint32_t n_clusters, uint32_t n_restarts, uint64_t seed,
+                                   const cellector_cluster_params *p /*NULL = defaults*/, const uint8_t *mask /*[L] or NULL*/,
+                                   uint8_t *labels /*[cells]*/, double *ll /*[K][cells]*/, double *posterior /*[K][cells]*/,
+                                   double *theta /*[K][L]*/, double *objective /*[R]*/,
+                                   cellector_cluster_summary *out); /* any output may be NULL */
+cellector_status cellector_cluster_m_step(cellector_ctx *ctx, const double *w /*[cells][J]*/, uint32_t J, const uint8_t *mask,
+                                          double theta_floor, double *A /*[J][L]*/, double *T /*[J][L]*/, double *theta /*[J][L]*/,
+                                          double *tab /*[L][J][2]*/); /* any output may be NULL */
+cellector_status cellector_cluster_e_step(cellector_ctx *ctx, const double *tab /*[L][J][2]*/, uint32_t K, uint32_t R,
+                                          const double *temp /*[cells] or NULL = 1*/, const uint8_t *mask, double *s /*[cells][J]*/,
+                                          double *w /*[cells][J]*/, double *objective /*[R]*/); /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
