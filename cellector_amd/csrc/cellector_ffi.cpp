@@ -254,7 +254,11 @@ cellector_status cellector_create(cellector_ctx **out, int device_id)
               hipHostMalloc((void **)&c->h_sel, 32 * sizeof(double)) == hipSuccess &&
               (memset(c->h_sel, 0, 32 * sizeof(double)), true) &&
               hipHostGetDevicePointer((void **)&c->h_sum_dev, c->h_sel, 0) == hipSuccess &&
+              dev_alloc(c, &c->t2_ctr, 3) == CELLECTOR_OK &&
               create_side_stream(&c->side) &&
+              create_side_stream(&c->side2) &&
+              hipEventCreateWithFlags(&c->ev_t2tab, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&c->ev_help, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming) == hipSuccess &&
@@ -315,22 +319,26 @@ void cellector_destroy(cellector_ctx *c)
     if (c->stream && c->owns_stream) (void)hipStreamSynchronize(c->stream);
     comm_destroy(c);
     if (c->side) (void)hipStreamSynchronize(c->side);
+    if (c->side2) (void)hipStreamSynchronize(c->side2);
     timer_collect(c);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     c->ev_pool.clear();
     // (the device buffers go before the streams)
     drop_matrix(c);
-    c->lf.reset(); c->d_counters.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
+    c->lf.reset(); c->d_counters.reset(); c->t2_ctr.reset(); c->sel_hist.reset(); c->sel_state.reset(); c->sel_out.reset();
     c->sel_list.reset(); c->seld_hist.reset(); c->seld_state.reset();
     c->res_cnt.reset(); c->res_dev.reset();
     if (c->h_sel) (void)hipHostFree(c->h_sel);
     if (c->side) (void)hipStreamDestroy(c->side);
+    if (c->side2) (void)hipStreamDestroy(c->side2);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
     if (c->ev_sum) (void)hipEventDestroy(c->ev_sum);
     if (c->ev_tab) (void)hipEventDestroy(c->ev_tab);
+    if (c->ev_t2tab) (void)hipEventDestroy(c->ev_t2tab);
+    if (c->ev_help) (void)hipEventDestroy(c->ev_help);
     delete c;
     dev_cache_trim();
 }
@@ -474,8 +482,12 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
         c->ovf_deep_opt = (int)v;
     }
     else if (!strcmp(key, "t2_waves")) {
-        if (v < 1 || v > (1 << 20)) return ctx_fail(c, CELLECTOR_EINVAL, "t2_waves must be within 1..2^20");
+        if (v < 0 || v > (1 << 20)) return ctx_fail(c, CELLECTOR_EINVAL, "t2_waves must be 0 (automatic) or within 1..2^20");
         c->t2_waves = (int)v;
+    }
+    else if (!strcmp(key, "t2_helper")) {
+        if (v < -1 || v > 64) return ctx_fail(c, CELLECTOR_EINVAL, "t2_helper must be -1 (automatic), 0 (off) or 1..64 blocks per free CU (forced)");
+        c->t2_helper = (int)v;
     }
     else if (!strcmp(key, "t2")) {
         if (v < -1 || v > 1) return ctx_fail(c, CELLECTOR_EINVAL, "t2 must be -1 (automatic), 0 or 1");

@@ -163,7 +163,10 @@ struct CtxOptions {
     int ovf_deep_opt = -1;           // option "ovf_deep": -1 = decided per matrix (tiled_build), 0 / 1 = forced
     bool ovf_deep_wide = true;       // option "ovf_deep_wide": deep form with 16 lanes per row (0: a thread per row; A/B)
     int t2_opt = -1;                 // option "t2": -1 = decided per matrix (tiled_build: on unless the matrix is ovf_deep), 0 / 1 = forced
-    int t2_waves = 512;              // option "t2_waves": one-wave blocks of k_t2_cell when it runs beside the tile kernel
+    int t2_waves = 0;                // option "t2_waves": one-wave blocks of k_t2_cell when it runs beside the tile kernel; 0 = automatic
+                                     // (512, or 256 beside a helper grid)
+    int t2_helper = -1;              // option "t2_helper": blocks of k_t2_cell's helper grid per CU the tile grid leaves free; -1 = automatic
+                                     // (EM pass only), 0 = none, n = forced, on one CU's worth when none is free (tests)
     int t2_tiles_opt = -1;           // option "t2_tiles": -1 = automatic (8 on an ovf_deep matrix), 0 = off, 6 / 8 = totals 5..6 / 5..8
     int c4_bits_opt = 0;             // option "compact_bits": 0 = automatic, 32 = force the 32-bit entries
     int locus_mode = 0;              // option "locus_mode": 0 = chosen on the device per iteration, 1 = stream the compact CSC,
@@ -367,7 +370,9 @@ struct cellector_ctx : CtxOptions, CtxStaged, CtxBuilt, CtxTiled, CtxCarry {
     hipStream_t stream = nullptr;
     // side stream for the small overflow kernels that run next to the tile kernel (fork/join with events)
     hipStream_t side = nullptr;
+    hipStream_t side2 = nullptr;  // ... and one for the helper grid of the tier-2 lookups, which runs BESIDE the side stream's grid
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_sum = nullptr;
+    hipEvent_t ev_t2tab = nullptr, ev_help = nullptr;  // k_t2_tables done (rides on its dispatch) -> helper grid -> its end (side stream waits)
     hipEvent_t ev_tab = nullptr;   // completion of the table kernel queued ahead by em_finish, attached to its dispatch (no barrier packet)
     mutable std::string err;
     // the PASS1 buffer the caller bound (cellector_bind_exchange_buffer) and its capacity in f64 values; null = none.  It outlives
@@ -377,6 +382,7 @@ struct cellector_ctx : CtxOptions, CtxStaged, CtxBuilt, CtxTiled, CtxCarry {
 
     DevBuf<double> lf;            // [LF_TABLE_N] ln factorial table
     DevBuf<uint32_t> d_counters;  // [8] device scratch counters
+    DevBuf<uint32_t> t2_ctr;      // [3] next 64-row group of the tier-2 lookups, per table set (reset by k_t2_tables)
     // cellector_assign's host arrays, kept between calls: a device-to-host copy into memory the process has not touched
     // before costs milliseconds, into a buffer used before microseconds
     struct AssignHost {

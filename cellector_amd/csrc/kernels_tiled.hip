@@ -746,8 +746,10 @@ template <bool EXPECTED>
 __global__ __launch_bounds__(256) void k_t2_tables(uint32_t n_pairs, const uint32_t *__restrict__ plist /*locus << 5 | pair*/,
                                                    uint32_t n_sec, const uint32_t *__restrict__ slist /*locus << 3 | sector*/,
                                                    uint32_t gp, const double2 *__restrict__ ab, const double *__restrict__ lf,
-                                                   double *__restrict__ tab2)
+                                                   double *__restrict__ tab2, uint32_t *__restrict__ grp_ctr /*null: none*/)
 {
+    // (the lookups that follow on this stream deal their row groups from this counter: reset here, no memset of its own)
+    if (grp_ctr && blockIdx.x == 0 && threadIdx.x == 0) *grp_ctr = 0u;
     if (blockIdx.x < gp) {
         const uint32_t i = blockIdx.x * 256 + threadIdx.x;
         if (i >= n_pairs) return;
@@ -841,26 +843,47 @@ __global__ __launch_bounds__(256) void k_t2_tile_add(uint64_t n_rows, uint32_t g
 
 // cell side: a thread per cell row of the 64-row ELLPACK copy (coalesced entry loads), four entries' lookups in flight;
 // sums in the row's order (ascending locus): deterministic.  Entries of other totals (0, above 8) are skipped.
-// One-wave blocks that stride over the 64-row groups: the launch's grid size sets how many gathers are in flight chip-wide.
+// Waves that take one 64-row group after the other: the launch's grid size sets how many gathers are in flight chip-wide.
 // Beside the tile kernel a SMALL grid is the point — every lookup fetches a line out of a table far bigger than an L2, and
 // 1.6e7 of them in a burst (2 GB at 5 TB/s) starve the tile kernel's stream for the burst's duration (+0.2 ms at 10^6 cells x 200k
 // loci); spread over the tile kernel's run time the same lines cost it far less (launch_overflow_cell).
-template <bool EXPECTED>
-__global__ __launch_bounds__(64) void k_t2_cell(uint64_t n_rows, const uint64_t *__restrict__ ell_ptr, const uint64_t *__restrict__ ell,
-                                                const double *__restrict__ tab2, double *__restrict__ o_ll, double *__restrict__ o_ell)
+// A launch on its own strides over the groups by its grid size.  DEAL: the groups are dealt from a device counter (reset by the
+// k_t2_tables launch in front), a group per wave and turn, so that launches of different shapes can share one pass' groups: the
+// small co-resident grid and the helper grid on the CUs the tile grid leaves free (launch_overflow_cell).  Whichever wave takes
+// a group, the row's lane adds the same values in the same order: the output does not depend on the deal.  (U: lookups in
+// flight per lane; padding entries add 0.0, so U changes no bit.  Measured and dropped: the entry stream and the gathers as
+// non-temporal loads, +0.2 ms per iteration at 10^6 cells)
+constexpr unsigned T2_HELP_LDS = 8192;  // dynamic LDS a helper block asks for and does not use: no room beside a tile workgroup
+constexpr unsigned T2_HELP_BLOCKS = 4;  // helper blocks (four waves each) per free CU
+constexpr int T2_HELP_U = 8;            // lookups in flight per lane of a helper block (registers are not scarce on a free CU)
+template <bool EXPECTED, int WAVES, int U, bool DEAL>
+__global__ __launch_bounds__(64 * WAVES) void k_t2_cell(uint64_t n_rows, const uint64_t *__restrict__ ell_ptr,
+                                                        const uint64_t *__restrict__ ell, const double *__restrict__ tab2,
+                                                        double *__restrict__ o_ll, double *__restrict__ o_ell,
+                                                        uint32_t *__restrict__ grp_ctr)
 {
   const uint64_t n_grp = (n_rows + 63) >> 6;
-  for (uint64_t grp = blockIdx.x; grp < n_grp; grp += gridDim.x) {
-    const uint64_t row = grp * 64 + threadIdx.x;
-    if (row >= n_rows) continue;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t turn = 0;; turn++) {  // (bounded: every turn takes a group; nothing waits for another wave)
+    uint64_t grp;
+    if constexpr (DEAL) {
+        uint32_t take = 0;
+        if (lane == 0) take = atomicAdd(grp_ctr, 1u);
+        grp = (uint32_t)__builtin_amdgcn_readfirstlane((int)take);
+    } else {
+        grp = blockIdx.x + turn * gridDim.x;  // (one-wave blocks)
+    }
+    if (grp >= n_grp) break;
+    const uint64_t row = grp * 64 + lane;
+    if (row < n_rows) {
     double s = 0.0, e = 0.0;
-    const uint64_t base = ell_ptr[grp] + (row & 63), end = ell_ptr[grp + 1];
-    constexpr int U = 4;
+    const uint64_t base = ell_ptr[grp] + lane, end = ell_ptr[grp + 1];
     for (uint64_t i = base; i < end; i += (uint64_t)U * 64) {
         uint64_t en[U];
         double lp[U], ev[U];
 #pragma unroll
-        for (int u = 0; u < U; u++) en[u] = i + (uint64_t)u * 64 < end ? ell[i + (uint64_t)u * 64] : OVF_PAD;  // (wave-uniform bound)
+        for (int u = 0; u < U; u++)  // (wave-uniform bound)
+            en[u] = i + (uint64_t)u * 64 < end ? ell[i + (uint64_t)u * 64] : OVF_PAD;
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t r = ENT_REF(en[u]), n = ENT_ALT(en[u]) + r;
@@ -881,6 +904,10 @@ __global__ __launch_bounds__(64) void k_t2_cell(uint64_t n_rows, const uint64_t 
     }
     o_ll[row] = s;
     if (EXPECTED) o_ell[row] = e;
+    }
+    // The lanes of a ragged last group must not go round on their own: the deal at the loop's head is the WAVE's (lane 0 takes,
+    // all read).  With `continue` for those lanes the compiler made an inner loop of them that never saw lane 0's take.
+    __builtin_amdgcn_wave_barrier();
   }
 }
 
@@ -1709,7 +1736,7 @@ static cellector_status t2_tiles_add(cellector_ctx *c, int set, bool expected)
 // Overflow side of one pass: tables -> per-entry values (locus-major) -> per-cell sums.  Launched on the side stream so
 // that these small, latency-bound kernels run next to the tile kernel instead of in front of it.
 // cell side of the overflow entries of one pass, on stream `st`
-static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2 *ab, int set, bool expected)
+static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2 *ab, int set, bool expected, bool em_pass = false)
 {
     double *o_ll = c->ovf_sum + (uint64_t)set * 2 * c->nloc, *o_ell = o_ll + c->nloc;
     const unsigned g = gcap(c->nloc, 256, 0x7fffffffu), eg = gcap(c->L * 16, 256, 0x7fffffffu);
@@ -1723,13 +1750,50 @@ static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2
             const unsigned gp = gcap(c->t2_np, 256, 0x7fffffffu), gs = EXP ? gcap(c->t2_ns, 256, 0x7fffffffu) : 0u;
             // (side_lds > 0: a request for dynamic LDS the lookup kernel does not use, to limit its blocks per CU in A/B runs)
             const size_t lds_req = c->side_lds > 0 ? (size_t)c->side_lds : 0;
-            // waves of the lookup kernel: all groups at once when it has the machine to itself, option t2_waves (default 512) beside the tile kernel
             const uint64_t n_grp = (c->nloc + 63) / 64;
-            const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)c->t2_waves : 0x7fffffffull);
-            hipLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp, ab, c->lf,
-                               c->tab2);
-            hipLaunchKernelGGL(k_t2_cell<EXP>, dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2, o_ll, o_ell);
+            // Helper grid: the tile grid is a whole number of workgroups per chunk group and can leave CUs without one (245 of
+            // 256 at 10^6 cells).  A tile workgroup holds nearly all of its CU's LDS, so blocks that ask for T2_HELP_LDS bytes
+            // (unused) are placed on the free CUs only while the tile kernel runs, anywhere once it has ended.  They take groups
+            // off the same counter as the co-resident grid above: work-conserving, and the same sums whoever looks a row up.
+            // Automatic (t2_helper -1): T2_HELP_BLOCKS blocks per free CU beside the EM pass' tile kernel of a big shard (iteration
+            // 1.838 -> 1.812 ms at 10^6 cells).  Not in the posterior phase, whose three lookup passes run ahead of their tile
+            // kernels (4.8 -> 5.0 ms with it), and not on a small shard, whose tile kernel is too short to hide the two more
+            // cross-stream waits (200k cells: 0.310 -> 0.328 ms).  t2_helper n > 0 forces n blocks per free CU, on one CU's worth
+            // where none is free (tests).
+            const unsigned tile_grid = tile_geometry(c, c->t_nb, c->t_groups).grid;
+            const unsigned free_cu = (unsigned)c->n_cu > tile_grid ? (unsigned)c->n_cu - tile_grid : 0u;
+            const unsigned hg = st != c->side || !c->t2_helper ? 0u
+                                : c->t2_helper < 0             ? (em_pass && c->nloc >= (1ull << 19) ? free_cu * T2_HELP_BLOCKS : 0u)
+                                                               : std::max(free_cu, 1u) * (unsigned)c->t2_helper;
+            // waves of the co-resident grid: all groups at once when it has the machine to itself; beside the tile kernel option
+            // t2_waves, 0 = 512, or 256 where a helper grid takes part of the groups
+            const unsigned side_waves = c->t2_waves > 0 ? (unsigned)c->t2_waves : hg ? 256u : 512u;
+            const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)side_waves : 0x7fffffffull);
+            uint32_t *ctr = c->t2_ctr + set;  // a counter per table set (the EM pass uses set 0, the posterior passes 0..2)
+            if (hg)  // the helper starts behind the tables: an event that rides on their dispatch (no barrier packet)
+                hipExtLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, nullptr, c->ev_t2tab, 0, (uint32_t)c->t2_np,
+                                      (const uint32_t *)c->t2_plist, (uint32_t)c->t2_ns, (const uint32_t *)c->t2_slist, (uint32_t)gp, ab,
+                                      (const double *)c->lf, (double *)c->tab2, ctr);
+            else
+                hipLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp, ab,
+                                   c->lf, c->tab2, ctr);
+            // (without a helper the grid strides over the groups as it always did: 15 000 one-wave blocks alone on the machine
+            //  cost 0.18 ms of an overlap-0 iteration in atomics on the one counter)
+            if (hg)
+                hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, true>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2,
+                                   o_ll, o_ell, ctr);
+            else
+                hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, false>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2,
+                                   o_ll, o_ell, ctr);
+            if (hg) {
+                (void)hipStreamWaitEvent(c->side2, c->ev_t2tab, 0);
+                hipLaunchKernelGGL((k_t2_cell<EXP, 4, T2_HELP_U, true>), dim3(hg), dim3(256), T2_HELP_LDS, c->side2, c->nloc, c->ovf_ell_ptr,
+                                   c->ovf_ell, c->tab2, o_ll, o_ell, ctr);
+                (void)hipEventRecord(c->ev_help, c->side2);
+            }
             if (EXP && n0) tables_e();  // E(9..17) of the tier-0 entries
+            // the kernels below add to the sums the lookups store, and the next pass' tables overwrite what they read
+            if (hg) (void)hipStreamWaitEvent(st, c->ev_help, 0);
         } else {
             if (EXP) tables_e();
             // Residency throttle (EM pass): a request for dynamic LDS it does not use leaves room for only ONE block of this kernel beside
@@ -1772,7 +1836,7 @@ static void launch_overflow_locus_values(cellector_ctx *c, hipStream_t st, const
     }
     if (c->t2)  // deep: the pairs' log-pmfs for the locus finalize's counts (the cell side does not use the table)
         hipLaunchKernelGGL(k_t2_tables<false>, dim3(gcap(c->t2_np, 256, 0x7fffffffu)), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns,
-                           c->t2_slist, gcap(c->t2_np, 256, 0x7fffffffu), ab, c->lf, c->tab2);
+                           c->t2_slist, gcap(c->t2_np, 256, 0x7fffffffu), ab, c->lf, c->tab2, (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_ovf_tables, dim3(gcap(c->L * 3, 256, 0x7fffffffu)), dim3(256), 0, st, c->L, ab, c->ovf_nmask, c->ovf_tab);
     if (!c->ovf_deep)  // shallow coverage: the values are stored here, beside the tile kernel, and the finalize reads them
         hipLaunchKernelGGL(k_ovf_values, dim3(gcap(c->ovf_n, 256, 0x7fffffffu)), dim3(256), 0, st, c->ovf_n, c->ovc_locus, c->ovc_ent, ab,
@@ -1872,7 +1936,7 @@ static cellector_status cell_pass_launch(cellector_ctx *c, const double2 *ab, bo
         CHK(side_fork(c));
         CHK(run_tile_pass(c, 0, c->compute_expected));
         CHK(t2_tiles_pass(c, ab, 0, c->compute_expected));
-        launch_overflow_cell(c, c->side, ab, 0, c->compute_expected);
+        launch_overflow_cell(c, c->side, ab, 0, c->compute_expected, for_em);
         HIPCHK(c, hipEventRecord(c->ev_join, c->side));
         if (for_em && c->overlap == 1) {  // the locus side's values right behind the cell side, beside the tile kernel
             launch_overflow_locus_values(c, c->side, ab);  // (they may end after it: only the locus finalize waits for them)

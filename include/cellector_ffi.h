@@ -116,6 +116,8 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * "balance" (multi-device ctx, default 1: see cellector_set_partition), "ref_arith" (engine 1: every entry with the
  * reference's own ln_gamma arithmetic, stats.rs:41-53, instead of the exact product form), "t2" / "t2_waves" (engine 2:
  * the entries with totals 5..8 through per-(locus, pair) tables, default on unless the matrix has deep coverage),
+ * "t2_helper" (engine 2: blocks of the tier-2 lookup kernel's helper grid per compute unit the tile grid leaves free;
+ * -1 = automatic, 0 = none, n = forced; placement only, the results do not depend on it),
  * "bank_order" (engine 2, default 1: the tile builder orders every row's entries and the rows of a slice against LDS bank
  * conflicts; 0 keeps file order, the layout whose per-cell sums do not depend on which cells share a shard),
  * "t2_tiles" (engine 2, deep coverage: the cell side of the totals 5..8 (8, the default of a matrix with more than 3 % of
