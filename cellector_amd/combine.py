@@ -46,8 +46,8 @@ def combine_coo(dst_coo, n_dst, src_coo, n_src, keep=None, locus_map=None, total
             np.concatenate([own_source, np.full(n_kept, k, np.uint8)]))
 
 
-def _vcf_records(path):
-    """(chrom, pos) of every record line, in file order"""
+def _vcf_records(path, columns=False):
+    """(chrom, pos) of every record line, in file order; columns: (chrom, pos, all the line's columns) instead"""
     opener = gzip.open if str(path).endswith(".gz") else open
     with opener(path, "rt") as f:
         for line in f:
@@ -57,7 +57,7 @@ def _vcf_records(path):
             if not line:
                 continue
             toks = line.split("\t")
-            yield toks[0], int(toks[1])
+            yield (toks[0], int(toks[1]), toks) if columns else (toks[0], int(toks[1]))
 
 
 def locus_map_from_vcfs(vcf1, vcf2):

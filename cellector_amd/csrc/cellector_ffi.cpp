@@ -1627,6 +1627,104 @@ cellector_status cellector_cluster_e_step(cellector_ctx *c, const double *tab, u
     return cluster_e_step_run(c, tab, K, R, temp, mask, s, w, objective);
 }
 
+// ---- donor demultiplexing: kernels_donors.hip -------------------------------------------------------------------
+cellector_status cellector_donor_default_params(cellector_donor_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->err = 0.01;
+    out->ambient = 0.03;
+    out->doublet_rate = 0.1;
+    out->posterior_threshold = 0.999;
+    out->min_loci = 1;
+    return CELLECTOR_OK;
+}
+
+// what every donor call checks before anything is written or launched (the scope first: class_call_check's own for the match)
+static cellector_status donor_args_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t D, const cellector_donor_params *p)
+{
+    if (D < 1 || D > 64) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u donors, 1..64 are supported", what, D);
+    if (!gt) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null gt", what);
+    if (!(p->err > 0.0 && p->err < 0.5)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: err = %g is not within (0, 0.5)", what, p->err);
+    if (!(p->ambient >= 0.0 && p->ambient < 1.0)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: ambient = %g is not within [0, 1)", what, p->ambient);
+    if (!(p->doublet_rate >= 0.0 && p->doublet_rate < 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: doublet_rate = %g is not within [0, 1)", what, p->doublet_rate);
+    if (!(p->posterior_threshold >= 0.0 && p->posterior_threshold <= 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: posterior_threshold = %g is not within [0, 1]", what, p->posterior_threshold);
+    if (p->min_loci < 1) return ctx_fail(c, CELLECTOR_EINVAL, "%s: min_loci must be at least 1", what);
+    const uint64_t TL = c->total_loci;
+    for (uint32_t d = 0; d < D; d++)
+        for (uint64_t t = 0; t < TL; t++)
+            if (gt[(uint64_t)d * TL + t] > 3)
+                return ctx_fail(c, CELLECTOR_EINVAL, "%s: gt of donor %u at locus %llu is %u: 0 = 0/0, 1 = 0/1, 2 = 1/1, 3 = no call", what, d,
+                                (unsigned long long)t, (unsigned)gt[(uint64_t)d * TL + t]);
+    return CELLECTOR_OK;
+}
+static cellector_status donor_call_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t D, const cellector_donor_params *p)
+{
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    return donor_args_check(c, what, gt, D, p);
+}
+
+cellector_status cellector_donor_tables(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *p,
+                                        const uint8_t *mask, double *tab1, double *tab2, uint64_t *packed)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    CHK(donor_call_check(c, "donor_tables", gt, n_donors, &prm));
+    SETDEV(c);
+    return donor_tables_run(c, gt, n_donors, &prm, mask, tab1, tab2, packed);
+}
+
+cellector_status cellector_donor_posteriors(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *p,
+                                            const double *log_prior, const uint8_t *anchor, const uint8_t *mask, double *ll, double *pair_ll,
+                                            double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
+                                            uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
+                                            cellector_donor_summary *out, double *tab1, double *tab2)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    CHK(donor_call_check(c, "donor_posteriors", gt, n_donors, &prm));
+    const uint32_t D = n_donors;
+    double lp[64] = {};
+    bool any = !log_prior;
+    for (uint32_t d = 0; log_prior && d < D; d++) {
+        if (std::isnan(log_prior[d]) || log_prior[d] == INFINITY)
+            return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: log_prior[%u] = %g is neither a finite value nor -inf", d, log_prior[d]);
+        any = any || log_prior[d] != -INFINITY;
+        lp[d] = log_prior[d];
+    }
+    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: log_prior is -inf for every donor");
+    for (uint64_t i = 0; anchor && i < c->nloc; i++)
+        if (anchor[i] >= D)
+            return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: anchor of cell %llu is %u, not below the %u donors", (unsigned long long)i,
+                            (unsigned)anchor[i], D);
+    const double log_singlet = std::log(1.0 - prm.doublet_rate);
+    const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
+    SETDEV(c);
+    return donor_posteriors_run(c, gt, D, &prm, lp, anchor, mask, log_singlet, log_pair, ll, pair_ll, posterior, pair_posterior,
+                                doublet_posterior, best, second, best_pair, n_entries, status, anchor_out, out, tab1, tab2, nullptr);
+}
+
+cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const uint8_t *gt, uint32_t n_donors,
+                                        const cellector_donor_params *p, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
+                                        uint64_t *cells)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    CHK(class_call_check(c, "match_donors", labels, n_classes, nullptr, nullptr));
+    CHK(donor_args_check(c, "match_donors", gt, n_donors, &prm));
+    SETDEV(c);
+    return donor_match_run(c, labels, n_classes, gt, n_donors, &prm, mask, ll, best, margin, cells);
+}
+
 // ---- class genotypes: kernels_genotypes.hip and genotype_host.h ---------------------------------------------
 // load_mtx_final + the rule of output_final_vcf (main.rs:52-131) for the K classes of a labelling
 cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, double ambient, double gt_threshold,

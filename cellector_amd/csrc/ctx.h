@@ -567,6 +567,19 @@ cellector_status cluster_e_step_run(cellector_ctx *c, const double *tab, uint32_
 cellector_status cluster_run(cellector_ctx *c, uint32_t K, uint32_t R, uint64_t seed, const cellector_cluster_params *p, const uint8_t *mask,
                              uint8_t *labels, double *ll, double *posterior, double *theta, double *objective,
                              cellector_cluster_summary *out);
+// donor demultiplexing (kernels_donors.hip) on one device holding all cells; validated arguments, host arrays, scratch of their own,
+// nothing of the ctx written: the packed genotypes and the tables alone, the cell passes with the posterior chain (log_prior never
+// null), the class tallies against the donors
+cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const uint8_t *mask,
+                                  double *tab1, double *tab2, uint64_t *packed);
+cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
+                                      const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair, double *ll,
+                                      double *pair_ll, double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
+                                      uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
+                                      cellector_donor_summary *out, double *tab1, double *tab2, uint64_t *packed);
+cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
+                                 const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
+                                 uint64_t *cells);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
 cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);

@@ -413,6 +413,10 @@ cellector_status cluster_e_step_run(cellector_ctx *c, const double *tab, uint32_
     if (st == CELLECTOR_OK && w) st = d2h(c, w, r.w, r.n * J * 8);
     if (st == CELLECTOR_OK && objective) st = d2h(c, objective, r.obj, (uint64_t)R * 8);
     (void)hipStreamSynchronize(c->stream);
+    if (r.timed && st == CELLECTOR_OK) {
+        r.collect();
+        fprintf(stderr, "[timing]   cluster_e_step: J %u E step %.3f ms\n", J, r.ms_e);
+    }
     return st;
 }
 

@@ -1,0 +1,477 @@
+// Donor demultiplexing (cellector_donor_posteriors, cellector_donor_tables, cellector_match_donors): every cell, and every class of
+// a labelling, scored against D donors whose genotypes are known.  include/cellector_ffi.h states the model completely;
+// cellector_amd/donors.py is its twin.
+//
+// A donor's genotype at a locus is 2 bits.  The D genotypes of a used locus are packed into W = ceil(D / 32) u64 words (donor d at
+// bits 2 (d & 31) of word d >> 5), and a locus has FOUR table rows, one per genotype value, whatever D is: 64 B of singlet table
+// and 256 B of pair table per locus, against the 16 D bytes of a table with a column per donor.
+//   k_donor_pack    gt [D][total_loci] u8 -> packed [L][W], over the used loci
+//   k_donor_tables  tab1 [L][4] and tab2 [L][16] double2 from the locus' alt / ref totals
+//   k_donor_e       rows = cells of the by-cell CSR, a group of DP lanes per cell, lane = donor (the shape of k_cluster_e: a lane
+//                   owns one (cell, donor) sum and walks the row's entries in order).  <DP, false>: the singlet sums, best, second and
+//                   the anchor; <DP, true>: the pair sums (anchor, d) and the posterior chain over the 2 D - 1 hypotheses
+//   k_donor_match   a lane per (class, donor): the class' tallies over ascending loci
+// All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
+#include "ctx.h"
+
+#include <cmath>
+
+#define DN_THREADS 256
+#define DN_WAVES (DN_THREADS / 64)
+#define DN_AHEAD 4  // entries whose loads are issued before the first of their ordered adds (= CK_AHEAD of kernels_cluster.hip)
+#define DN_NONE 255
+
+static inline unsigned dn_grid(uint64_t n, unsigned per_block, unsigned cap)
+{
+    uint64_t g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
+
+// packed[l][w]: donor d = 32 w + i at bits 2 i, from gt[d][locus_ids[l]]; the bits of donors >= D are 0
+__global__ __launch_bounds__(DN_THREADS) void k_donor_pack(uint64_t n /*L W*/, uint32_t D, uint32_t W, uint64_t TL,
+                                                           const uint64_t *__restrict__ locus_ids, const uint8_t *__restrict__ gt,
+                                                           uint64_t *__restrict__ packed)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = i / W, t = locus_ids[l];
+    const uint32_t w = (uint32_t)(i % W);
+    uint64_t word = 0;
+    if (t < TL)
+        for (uint32_t b = 0; b < 32 && 32 * w + b < D; b++) word |= (uint64_t)(gt[(uint64_t)(32 * w + b) * TL + t] & 3u) << (2 * b);
+    packed[i] = word;
+}
+
+// theta_g = (1 - ambient) e_g + ambient soup, e = {err, 0.5, 1 - err, soup}, soup = (A + 1) / ((A + R) + 2) from the locus' totals
+// (whole numbers below 2^53 held as doubles: their sum is exact).  Thread (l, 4 ga + gb): tab2 from 0.5 (theta_ga + theta_gb); the
+// diagonal is tab1 ((x + x) 0.5 == x).  A masked locus carries (0, 0).
+__global__ __launch_bounds__(DN_THREADS) void k_donor_tables(uint64_t n /*16 L*/, const double *__restrict__ s_alt, const double *__restrict__ s_ref,
+                                                             const uint8_t *__restrict__ mask /*or null*/, double err, double ambient,
+                                                             double2 *__restrict__ tab1, double2 *__restrict__ tab2)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = i >> 4;
+    const uint32_t ga = (uint32_t)(i >> 2) & 3u, gb = (uint32_t)i & 3u;
+    double2 out = make_double2(0.0, 0.0);
+    if (!mask || mask[l] != 0) {
+        const double A = s_alt[l], R = s_ref[l];
+        const double num = A + 1.0, tot = A + R, den = tot + 2.0;
+        const double soup = num / den;
+        const double keep = 1.0 - ambient, amb = ambient * soup;
+        const double e2 = 1.0 - err;
+        const double ea = ga == 0 ? err : ga == 1 ? 0.5 : ga == 2 ? e2 : soup;
+        const double eb = gb == 0 ? err : gb == 1 ? 0.5 : gb == 2 ? e2 : soup;
+        const double pa = keep * ea, pb = keep * eb;
+        const double ta = pa + amb, tb = pb + amb;
+        const double sum = ta + tb;
+        const double th = 0.5 * sum;
+        const double rest = 1.0 - th;
+        out = make_double2(log(th), log(rest));
+    }
+    tab2[i] = out;
+    if (ga == gb) tab1[l * 4 + ga] = out;
+}
+
+struct DonorTail {
+    double log_singlet, log_pair, threshold;
+    uint64_t min_loci;
+};
+
+// (value, index) maximum over the group's DP lanes, the smallest index among equal values: every lane of the wave takes part
+template <int DP>
+__device__ __forceinline__ void dn_argmax(double &v, int &idx)
+{
+#pragma unroll
+    for (int off = DP / 2; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(idx, off, 64);
+        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+    }
+}
+
+// The cell pass.  A group of DP lanes per cell, lane = donor d.  acc = the ordered sum of (alt la + ref lb) over the row's entries at
+// unmasked loci, (la, lb) = the table row of the donor's genotype (PAIR: of the anchor's and the donor's).
+// !PAIR: s = acc; u_d = s_d + lp_d; best = argmax u, second = argmax over d != best (smallest d on ties); the anchor, unless given
+//  PAIR: p = acc; x_d = (s_d + lp_d) + log_singlet, y_d = p_d + log_pair (d != anchor), one softmax over the 2 D - 1 terms
+template <int DP, bool PAIR>
+__global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_t D, uint32_t W, const uint64_t *__restrict__ row_ptr,
+                                                        const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
+                                                        const double2 *__restrict__ tab, const uint8_t *__restrict__ mask /*or null*/,
+                                                        const double *__restrict__ lp /*[D]*/, DonorTail tail, bool anchor_given,
+                                                        uint8_t *__restrict__ anchor, double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/,
+                                                        uint8_t *__restrict__ best, uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out,
+                                                        double *__restrict__ p_out, double *__restrict__ post, double *__restrict__ ppost,
+                                                        double *__restrict__ dp_out, uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
+{
+    constexpr int RPW = 64 / DP;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / DP, col = lane % DP;
+    const bool col_ok = (uint32_t)col < D;
+    const int base = sub * DP;
+    const uint32_t my_word = col_ok ? (uint32_t)col >> 5 : 0u, my_shift = 2u * ((uint32_t)col & 31u);
+    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * DN_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * DN_WAVES;
+    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
+        const uint64_t row = g * RPW + sub;
+        const bool have = row < n_rows;
+        const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
+        uint32_t a = 0;
+        if (PAIR && have) a = anchor[row];
+        if (a >= D) a = 0;  // (never: the host checks a given anchor, the singlet pass writes a donor)
+        const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
+        double acc = 0.0;
+        uint32_t cnt = 0;
+        for (uint64_t i = beg; i < end; i += DN_AHEAD) {
+            uint64_t en[DN_AHEAD];
+            double2 t[DN_AHEAD];
+            bool use[DN_AHEAD];
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++) {
+                const bool in = i + q < end;
+                en[q] = in ? ent[i + q] : 0ull;
+                const uint64_t l = ENT_IDX(en[q]);
+                use[q] = in && (!mask || mask[l] != 0);
+                t[q] = make_double2(0.0, 0.0);
+                if (use[q] && col_ok) {
+                    const uint32_t gd = (uint32_t)(packed[l * W + my_word] >> my_shift) & 3u;
+                    if (PAIR) {
+                        const uint32_t ga = (uint32_t)(packed[l * W + a_word] >> a_shift) & 3u;
+                        t[q] = tab[l * 16 + 4 * ga + gd];
+                    } else {
+                        t[q] = tab[l * 4 + gd];
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++) {
+                if (!use[q]) continue;
+                const uint32_t al = ENT_ALT(en[q]), re = ENT_REF(en[q]);
+                const double pa = (double)al * t[q].x, pb = (double)re * t[q].y;
+                const double term = pa + pb;
+                acc = acc + term;
+                cnt++;
+            }
+        }
+        // the tail: every lane of the wave takes part in the shuffles, whatever its row and donor
+        const double prior = col_ok ? lp[col] : 0.0;
+        if (!PAIR) {
+            double v = col_ok ? acc + prior : -INFINITY;
+            int b = col_ok ? col : 0x7fff;
+            const double u = v;
+            dn_argmax<DP>(v, b);
+            double v2 = col_ok && col != b ? u : -INFINITY;
+            int b2 = col_ok && col != b ? col : 0x7fff;
+            dn_argmax<DP>(v2, b2);
+            if (have && col_ok) s[row * D + col] = acc;
+            if (have && col == 0) {
+                best[row] = (uint8_t)b;
+                second[row] = D > 1 ? (uint8_t)b2 : (uint8_t)DN_NONE;
+                if (!anchor_given) anchor[row] = (uint8_t)b;
+                cnt_out[row] = cnt;
+            }
+        } else {
+            const bool pair_ok = col_ok && (uint32_t)col != a;
+            double x = -INFINITY, y = -INFINITY;
+            if (have && col_ok) {
+                const double u = s[row * D + col] + prior;
+                x = u + tail.log_singlet;
+            }
+            if (pair_ok) y = acc + tail.log_pair;
+            double m = fmax(x, y);
+            int dummy = 0;
+            dn_argmax<DP>(m, dummy);
+            if (!have) m = 0.0;
+            const double ex = exp(x - m), ey = exp(y - m);  // a lane that is no hypothesis: exp(-inf) = 0, and den + 0 is den
+            double den = 0.0;
+            for (uint32_t d = 0; d < D; d++) den = den + __shfl(ex, (base + (int)d) & 63, 64);
+            for (uint32_t d = 0; d < D; d++) den = den + __shfl(ey, (base + (int)d) & 63, 64);
+            const double w = ex / den, wp = ey / den;
+            double dp = 0.0;
+            for (uint32_t d = 0; d < D; d++) dp = dp + __shfl(wp, (base + (int)d) & 63, 64);
+            double vy = y;
+            int bp = pair_ok ? col : 0x7fff;
+            dn_argmax<DP>(vy, bp);
+            const int b = have ? (int)best[row] : 0;
+            const double wb = __shfl(w, (base + b) & 63, 64);
+            if (have && col_ok) {
+                p_out[row * D + col] = acc;
+                post[row * D + col] = w;
+                ppost[row * D + col] = wp;
+            }
+            if (have && col == 0) {
+                dp_out[row] = dp;
+                best_pair[row] = D > 1 ? (uint8_t)bp : (uint8_t)DN_NONE;
+                status[row] = (uint64_t)cnt < tail.min_loci ?(uint8_t)DN_NONE : dp > 0.5 ? (uint8_t)1 : wb >= tail.threshold ? (uint8_t)0 : (uint8_t)2;
+            }
+        }
+    }
+}
+
+// ll[k][d] = the ordered sum over ascending unmasked loci of ((a la) + (r lb)), (a, r) the class' tallies, (la, lb) the singlet row of
+// the donor's genotype.  Block k, lane d.
+__global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint32_t W, const unsigned long long *__restrict__ alt /*[K][L]*/,
+                                                    const unsigned long long *__restrict__ ref, const uint64_t *__restrict__ packed,
+                                                    const double2 *__restrict__ tab1, const uint8_t *__restrict__ mask /*or null*/,
+                                                    double *__restrict__ ll /*[K][D]*/)
+{
+    const uint32_t k = blockIdx.x, d = threadIdx.x;
+    if (d >= D) return;
+    const uint32_t my_word = d >> 5, my_shift = 2u * (d & 31u);
+    const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
+    double acc = 0.0;
+    for (uint64_t l0 = 0; l0 < L; l0 += DN_AHEAD) {
+        double av[DN_AHEAD], rv[DN_AHEAD];
+        double2 t[DN_AHEAD];
+        bool use[DN_AHEAD];
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++) {
+            const uint64_t l = l0 + q;
+            use[q] = l < L && (!mask || mask[l] != 0);
+            av[q] = rv[q] = 0.0;
+            t[q] = make_double2(0.0, 0.0);
+            if (use[q]) {
+                av[q] = (double)ak[l];
+                rv[q] = (double)rk[l];
+                t[q] = tab1[l * 4 + ((uint32_t)(packed[l * W + my_word] >> my_shift) & 3u)];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++) {
+            if (!use[q]) continue;
+            const double pa = av[q] * t[q].x, pb = rv[q] * t[q].y;
+            const double term = pa + pb;
+            acc = acc + term;
+        }
+    }
+    ll[(uint64_t)k * D + d] = acc;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+namespace {
+
+int dn_dp(uint32_t D)
+{
+    int dp = 2;
+    while ((uint32_t)dp < D) dp <<= 1;
+    return dp;
+}
+
+// the scratch of one call; alloc() makes all of it before anything is launched
+struct DonorRun {
+    cellector_ctx *c;
+    uint32_t D, W;
+    uint64_t n, L, TL;
+    DevBuf<uint8_t> gt, mask;       // [D][TL], [L]
+    DevBuf<uint64_t> packed;        // [L][W]
+    DevBuf<double2> tab1, tab2;     // [L][4], [L][16]
+    DevBuf<double> lp;              // [D]
+    DevBuf<double> s, p, post, ppost;  // [n][D]
+    DevBuf<double> dp;              // [n]
+    DevBuf<uint8_t> anchor, best, second, best_pair, status;  // [n]
+    DevBuf<uint32_t> cnt;           // [n]
+    DevBuf<unsigned long long> alt, ref;  // [K][L] the class tallies (match)
+    DevBuf<double> ll;              // [K][D]
+    bool have_mask = false;
+    const bool timed = getenv("CELLECTOR_TIMING") != nullptr;
+
+    cellector_status alloc(bool cells, uint32_t K)
+    {
+        CHK(dev_alloc(c, &gt, (uint64_t)D * TL));
+        CHK(dev_alloc(c, &mask, L));
+        CHK(dev_alloc(c, &packed, L * W));
+        CHK(dev_alloc(c, &tab1, L * 4));
+        CHK(dev_alloc(c, &tab2, L * 16));
+        if (cells) {
+            const uint64_t nD = n * D;
+            CHK(dev_alloc(c, &lp, D));
+            CHK(dev_alloc(c, &s, nD)); CHK(dev_alloc(c, &p, nD)); CHK(dev_alloc(c, &post, nD)); CHK(dev_alloc(c, &ppost, nD));
+            CHK(dev_alloc(c, &dp, n));
+            CHK(dev_alloc(c, &anchor, n)); CHK(dev_alloc(c, &best, n)); CHK(dev_alloc(c, &second, n));
+            CHK(dev_alloc(c, &best_pair, n)); CHK(dev_alloc(c, &status, n));
+            CHK(dev_alloc(c, &cnt, n));
+        }
+        if (K) {
+            CHK(dev_alloc(c, &alt, (uint64_t)K * L)); CHK(dev_alloc(c, &ref, (uint64_t)K * L));
+            CHK(dev_alloc(c, &ll, (uint64_t)K * D));
+        }
+        return CELLECTOR_OK;
+    }
+
+    const uint8_t *dmask() const { return have_mask ? mask.get() : nullptr; }
+
+    // one upload of gt, the packing and the tables
+    cellector_status prepare(const uint8_t *host_gt, const uint8_t *host_mask, const cellector_donor_params *prm)
+    {
+        have_mask = host_mask != nullptr;
+        if (have_mask && L) HIPCHK(c, hipMemcpyAsync(mask, host_mask, L, hipMemcpyHostToDevice, c->stream));
+        if (!L) return CELLECTOR_OK;
+        HIPCHK(c, hipMemcpyAsync(gt, host_gt, (uint64_t)D * TL, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * W, D, W, TL,
+                           c->locus_ids.get(), gt.get(), packed.get());
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_donor_tables, dim3(dn_grid(L * 16, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * 16,
+                           c->s_alt.get(), c->s_ref.get(), dmask(), prm->err, prm->ambient, tab1.get(), tab2.get());
+        HIPCHK(c, hipGetLastError());
+        return CELLECTOR_OK;
+    }
+
+    cellector_status pass(bool pair, bool anchor_given, const DonorTail &tail)
+    {
+        if (!n) return CELLECTOR_OK;
+        const int dpw = dn_dp(D);
+        const unsigned grid = dn_grid((n + 64 / dpw - 1) / (64 / dpw), DN_WAVES, (unsigned)c->n_cu * 8);
+#define DN_E(DP, PAIR)                                                                                                                 \
+    hipLaunchKernelGGL((k_donor_e<DP, PAIR>), dim3(grid), dim3(DN_THREADS), 0, c->stream, n, D, W, c->csr_ptr.get(), c->csr_ent.get(), \
+                       packed.get(), PAIR ? tab2.get() : tab1.get(), dmask(), lp.get(), tail, anchor_given, anchor.get(), s.get(),     \
+                       best.get(), second.get(), cnt.get(), p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get())
+#define DN_CASE(DP)                                                                                                                    \
+    case DP:                                                                                                                           \
+        if (pair) DN_E(DP, true);                                                                                                      \
+        else DN_E(DP, false);                                                                                                          \
+        break;
+        switch (dpw) { DN_CASE(2) DN_CASE(4) DN_CASE(8) DN_CASE(16) DN_CASE(32) DN_CASE(64) }
+#undef DN_CASE
+#undef DN_E
+        HIPCHK(c, hipGetLastError());
+        return CELLECTOR_OK;
+    }
+
+    cellector_status fetch_tables(double *h_tab1, double *h_tab2, uint64_t *h_packed)
+    {
+        if (h_tab1) CHK(d2h(c, h_tab1, tab1, L * 4 * 16));
+        if (h_tab2) CHK(d2h(c, h_tab2, tab2, L * 16 * 16));
+        if (h_packed) CHK(d2h(c, h_packed, packed, L * W * 8));
+        return CELLECTOR_OK;
+    }
+};
+
+void donors_invalidate(cellector_ctx *c)
+{
+    c->tables_prebuilt = false;  // what cellector_cell_log_likelihoods invalidates (the calls themselves use scratch of their own)
+    c->work_zeroed = false;
+}
+
+}  // namespace
+
+// cellector_donor_tables: validated arguments; host outputs, any may be null
+cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const uint8_t *mask,
+                                  double *tab1, double *tab2, uint64_t *packed)
+{
+    DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
+    CHK(r.alloc(false, 0));
+    donors_invalidate(c);
+    cellector_status st = r.prepare(gt, mask, prm);
+    if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, packed);
+    (void)hipStreamSynchronize(c->stream);  // (nothing of the scratch may be in use when it goes)
+    return st;
+}
+
+// cellector_donor_posteriors: validated arguments (log_prior never null: the caller's or zeros); host outputs, any may be null
+cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
+                                      const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair, double *ll,
+                                      double *pair_ll, double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
+                                      uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
+                                      cellector_donor_summary *out, double *tab1, double *tab2, uint64_t *packed)
+{
+    LapTimer whole;
+    DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
+    const uint64_t n = r.n;
+    CHK(r.alloc(true, 0));
+    std::vector<uint8_t> h_status(n), h_best(n);
+    donors_invalidate(c);
+    const DonorTail tail = {log_singlet, log_pair, prm->posterior_threshold, prm->min_loci};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (r.timed)
+        for (hipEvent_t &e : ev) (void)hipEventCreate(&e);
+    cellector_status st = r.prepare(gt, mask, prm);
+    if (st == CELLECTOR_OK && hipMemcpyAsync(r.lp, log_prior, (uint64_t)D * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the priors failed");
+    if (st == CELLECTOR_OK && anchor && n && hipMemcpyAsync(r.anchor, anchor, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the anchors failed");
+    if (ev[0]) (void)hipEventRecord(ev[0], c->stream);
+    if (st == CELLECTOR_OK) st = r.pass(false, anchor != nullptr, tail);
+    if (ev[1]) (void)hipEventRecord(ev[1], c->stream);
+    if (st == CELLECTOR_OK) st = r.pass(true, anchor != nullptr, tail);
+    if (ev[2]) (void)hipEventRecord(ev[2], c->stream);
+    const uint64_t nD = n * D;
+    if (st == CELLECTOR_OK && ll) st = d2h(c, ll, r.s, nD * 8);
+    if (st == CELLECTOR_OK && pair_ll) st = d2h(c, pair_ll, r.p, nD * 8);
+    if (st == CELLECTOR_OK && posterior) st = d2h(c, posterior, r.post, nD * 8);
+    if (st == CELLECTOR_OK && pair_posterior) st = d2h(c, pair_posterior, r.ppost, nD * 8);
+    if (st == CELLECTOR_OK && doublet_posterior) st = d2h(c, doublet_posterior, r.dp, n * 8);
+    if (st == CELLECTOR_OK) st = d2h(c, h_best.data(), r.best, n);
+    if (st == CELLECTOR_OK && second) st = d2h(c, second, r.second, n);
+    if (st == CELLECTOR_OK && best_pair) st = d2h(c, best_pair, r.best_pair, n);
+    if (st == CELLECTOR_OK && n_entries) st = d2h(c, n_entries, r.cnt, n * 4);
+    if (st == CELLECTOR_OK) st = d2h(c, h_status.data(), r.status, n);
+    if (st == CELLECTOR_OK && anchor_out) st = d2h(c, anchor_out, r.anchor, n);
+    if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, packed);
+    (void)hipStreamSynchronize(c->stream);
+    if (r.timed && st == CELLECTOR_OK) {
+        float ms1 = 0.f, ms2 = 0.f;
+        if (ev[0] && ev[1] && ev[2] && hipEventElapsedTime(&ms1, ev[0], ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&ms2, ev[1], ev[2]) == hipSuccess)
+            fprintf(stderr, "[timing]   donors: D %u singlet pass %.3f ms, pair pass %.3f ms, whole call %.4f s\n", D, ms1, ms2, whole.lap());
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (st != CELLECTOR_OK) return st;
+    cellector_donor_summary sum = {};
+    for (uint64_t i = 0; i < n; i++) {
+        switch (h_status[i]) {
+        case 0: sum.n_singlet++; sum.donor_cells[h_best[i] < 64 ? h_best[i] : 0]++; break;
+        case 1: sum.n_doublet++; break;
+        case 2: sum.n_ambiguous++; break;
+        default: sum.n_unassigned++; break;
+        }
+    }
+    if (best && n) memcpy(best, h_best.data(), n);
+    if (status && n) memcpy(status, h_status.data(), n);
+    if (out) *out = sum;
+    return CELLECTOR_OK;
+}
+
+// cellector_match_donors: validated arguments; the tallies are cellector_class_tallies' own; host outputs, any may be null
+cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
+                                 const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
+                                 uint64_t *cells)
+{
+    DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
+    const uint64_t L = r.L;
+    CHK(r.alloc(false, K));
+    std::vector<uint64_t> h_alt((uint64_t)K * L), h_ref((uint64_t)K * L), h_cells(K);
+    std::vector<double> h_ll((uint64_t)K * D, 0.0);
+    CHK(classes_tallies_run(c, labels, K, nullptr, h_cells.data(), h_alt.data(), h_ref.data(), nullptr, nullptr));
+    donors_invalidate(c);
+    cellector_status st = r.prepare(gt, mask, prm);
+    if (st == CELLECTOR_OK && L) {
+        if (hipMemcpyAsync(r.alt, h_alt.data(), (uint64_t)K * L * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(r.ref, h_ref.data(), (uint64_t)K * L * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            st = ctx_fail(c, CELLECTOR_EDEVICE, "match_donors: the upload of the tallies failed");
+    }
+    if (st == CELLECTOR_OK) {
+        hipLaunchKernelGGL(k_donor_match, dim3(K), dim3(64), 0, c->stream, L, D, r.W, r.alt.get(), r.ref.get(), r.packed.get(),
+                           r.tab1.get(), r.dmask(), r.ll.get());
+        if (hipGetLastError() != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "match_donors: launch failed");
+    }
+    if (st == CELLECTOR_OK) st = d2h(c, h_ll.data(), r.ll, (uint64_t)K * D * 8);
+    (void)hipStreamSynchronize(c->stream);
+    if (st != CELLECTOR_OK) return st;
+    for (uint32_t k = 0; k < K; k++) {
+        const double *row = h_ll.data() + (uint64_t)k * D;
+        uint32_t b = 0, b2 = DN_NONE;
+        for (uint32_t d = 1; d < D; d++)
+            if (row[d] > row[b]) b = d;
+        for (uint32_t d = 0; d < D; d++)
+            if (d != b && (b2 == DN_NONE || row[d] > row[b2])) b2 = d;
+        const bool live = h_cells[k] > 0;
+        if (best) best[k] = live ? (uint8_t)b : (uint8_t)DN_NONE;
+        if (margin) margin[k] = !live ? 0.0 : b2 == DN_NONE ? INFINITY : row[b] - row[b2];
+        if (cells) cells[k] = h_cells[k];
+    }
+    if (ll) memcpy(ll, h_ll.data(), h_ll.size() * 8);
+    return CELLECTOR_OK;
+}

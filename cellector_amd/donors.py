@@ -1,0 +1,260 @@
+"""Donor demultiplexing on host arrays: the numpy twin of cellector_donor_tables / cellector_donor_posteriors /
+cellector_match_donors (include/cellector_ffi.h states the model; csrc/kernels_donors.hip runs it), and the reader of the donors'
+genotypes from a VCF.
+
+Every cell, and every class of a labelling, is scored against D donors whose genotypes are known: per locus four binomial allele
+fractions (hom-ref, het, hom-alt, no call) under an ambient mix, a singlet sum per (cell, donor), a pair sum per (cell, anchor
+donor, donor), one softmax over the 2 D - 1 hypotheses.
+
+The sums are the library's sums in the library's order (a cell's entries in by-cell CSR row order, a class' loci in ascending
+order, one rounded product and one rounded add at a time): fed the DEVICE's tables, singlet_sums, pair_sums and match_sums carry the
+device's bits.  log and exp are numpy's, not the device's: the tables made here and the posteriors agree with the device's to a few
+ulps.
+"""
+import math
+
+import numpy as np
+
+from . import combine
+from .cluster import Matrix  # noqa: F401  (the matrix in the library's row order; callers build one and pass it in)
+
+NO_CALL = 3
+NONE = 255
+SINGLET, DOUBLET, AMBIGUOUS, UNASSIGNED = 0, 1, 2, 255
+STATUS_NAMES = {SINGLET: "singlet", DOUBLET: "doublet", AMBIGUOUS: "ambiguous", UNASSIGNED: "unassigned"}
+DEFAULTS = dict(err=0.01, ambient=0.03, doublet_rate=0.1, posterior_threshold=0.999, min_loci=1)
+
+
+def _params(params):
+    p = dict(DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError(f"unknown parameter {k!r}")
+        p[k] = v
+    return p
+
+
+# ---- packing and tables ----------------------------------------------------------------------------------------------------------
+def pack(gt, locus_ids):
+    """packed [L, W] uint64, W = ceil(D / 32): donor d of used locus l at bits 2 (d & 31) of word d >> 5, from gt [D, total_loci]"""
+    gt = np.asarray(gt, np.uint8)
+    D = gt.shape[0]
+    g = gt[:, np.asarray(locus_ids, np.int64)].astype(np.uint64)  # [D, L]
+    out = np.zeros((g.shape[1], (D + 31) // 32), np.uint64)
+    for d in range(D):
+        out[:, d >> 5] |= g[d] << np.uint64(2 * (d & 31))
+    return out
+
+
+def unpack(packed, D):
+    """g [L, D] uint8 from packed [L, W]"""
+    packed = np.asarray(packed, np.uint64)
+    return np.stack([(packed[:, d >> 5] >> np.uint64(2 * (d & 31))) & np.uint64(3) for d in range(D)], axis=1).astype(np.uint8)
+
+
+def thetas(alt_total, ref_total, err=0.01, ambient=0.03):
+    """theta [L, 4]: ((1 - ambient) e_g) + (ambient soup), e = (err, 0.5, 1 - err, soup), soup = (A + 1) / ((A + R) + 2)"""
+    A, R = np.asarray(alt_total, np.float64), np.asarray(ref_total, np.float64)
+    soup = (A + 1.0) / ((A + R) + 2.0)
+    keep, amb = 1.0 - ambient, ambient * soup
+    e = np.stack([np.full_like(soup, err), np.full_like(soup, 0.5), np.full_like(soup, 1.0 - err), soup], axis=1)
+    return keep * e + amb[:, None]
+
+
+def tables(alt_total, ref_total, err=0.01, ambient=0.03, mask=None, log=np.log):
+    """(tab1 [L, 4, 2], tab2 [L, 16, 2]) = (log theta, log(1 - theta)); tab2 at 4 g_a + g_b from 0.5 (theta_a + theta_b); a masked
+    locus carries (0, 0)"""
+    th = thetas(alt_total, ref_total, err, ambient)
+    th2 = (0.5 * (th[:, :, None] + th[:, None, :])).reshape(len(th), 16)
+    tab1 = np.stack([log(th), log(1.0 - th)], axis=-1)
+    tab2 = np.stack([log(th2), log(1.0 - th2)], axis=-1)
+    if mask is not None:
+        tab1[np.asarray(mask) == 0] = 0.0
+        tab2[np.asarray(mask) == 0] = 0.0
+    return tab1, tab2
+
+
+# ---- the ordered sums ------------------------------------------------------------------------------------------------------------
+def singlet_sums(mat, tab1, g):
+    """s [cells, D]: per (cell, donor) the sum over the cell's entries in row order of ((alt la) + (ref lb)), (la, lb) =
+    tab1[l][g[l, d]]; mat: a cluster.Matrix over the used loci (built with the call's mask), g [L, D] the donors' genotypes there"""
+    tab1, g = np.asarray(tab1, np.float64), np.asarray(g, np.int64)
+    s = np.zeros((mat.N, g.shape[1]))
+    for rows, ent in mat.rows.steps:
+        l = mat.r_lo[ent]
+        t = tab1[l[:, None], g[l]]  # [m, D, 2]
+        s[rows] = s[rows] + ((mat.r_al[ent, None] * t[:, :, 0]) + (mat.r_re[ent, None] * t[:, :, 1]))
+    return s
+
+
+def pair_sums(mat, tab2, g, anchor):
+    """p [cells, D]: the same sum with tab2[l][4 g[l, anchor_c] + g[l, d]]"""
+    tab2, g, anchor = np.asarray(tab2, np.float64), np.asarray(g, np.int64), np.asarray(anchor, np.int64)
+    p = np.zeros((mat.N, g.shape[1]))
+    for rows, ent in mat.rows.steps:
+        l = mat.r_lo[ent]
+        t = tab2[l[:, None], 4 * g[l, anchor[rows]][:, None] + g[l]]
+        p[rows] = p[rows] + ((mat.r_al[ent, None] * t[:, :, 0]) + (mat.r_re[ent, None] * t[:, :, 1]))
+    return p
+
+
+def match_sums(alt, ref, tab1, g, mask=None):
+    """ll [K, D]: per (class, donor) the sum over ascending unmasked loci of ((a la) + (r lb)) from the class tallies alt, ref [K, L]"""
+    alt, ref = np.asarray(alt).astype(np.float64), np.asarray(ref).astype(np.float64)
+    tab1, g = np.asarray(tab1, np.float64), np.asarray(g, np.int64)
+    K, L = alt.shape
+    ll = np.zeros((K, g.shape[1]))
+    for l in range(L):
+        if mask is not None and not mask[l]:
+            continue
+        t = tab1[l, g[l]]  # [D, 2]
+        ll = ll + ((alt[:, l, None] * t[None, :, 0]) + (ref[:, l, None] * t[None, :, 1]))
+    return ll
+
+
+def _argmax_first(v, exclude=None):
+    """per row the smallest column that attains the maximum over the columns other than exclude[row]"""
+    v = np.asarray(v, np.float64)
+    if exclude is None:
+        return np.argmax(v, axis=1)
+    ok = np.arange(v.shape[1])[None, :] != np.asarray(exclude, np.int64)[:, None]
+    w = np.where(ok, v, -np.inf)
+    return np.argmax(ok & (w == w.max(axis=1)[:, None]), axis=1)
+
+
+# ---- the chain -------------------------------------------------------------------------------------------------------------------
+def best_second(s, log_prior=None):
+    """(best, second) uint8 of u = s + log_prior: the smallest d on ties; second = 255 with one donor"""
+    n, D = s.shape
+    u = s + (np.zeros(D) if log_prior is None else np.asarray(log_prior, np.float64))[None, :]
+    best = _argmax_first(u)
+    second = _argmax_first(u, best).astype(np.uint8) if D > 1 else np.full(n, NONE, np.uint8)
+    return best.astype(np.uint8), second
+
+
+def chain(s, p, anchor, entries, log_prior=None, **params):
+    """dict of posterior, pair_posterior [cells, D], doublet_posterior, best, second, best_pair, status from the sums: the softmax
+    over the D singlets x = (s + log_prior) + log_singlet and the D - 1 pairs y = p + log_pair (d != anchor), in that order"""
+    prm = _params(params)
+    n, D = s.shape
+    anchor = np.asarray(anchor, np.int64)
+    lp = np.zeros(D) if log_prior is None else np.asarray(log_prior, np.float64)
+    rate = float(prm["doublet_rate"])
+    with np.errstate(divide="ignore"):
+        log_singlet = math.log(1.0 - rate)
+        log_pair = (math.log(rate / float(D - 1)) if rate > 0 else -math.inf) if D > 1 else 0.0
+    x = (s + lp[None, :]) + log_singlet
+    y = p + log_pair
+    y[np.arange(n), anchor] = -np.inf
+    m = np.maximum(x.max(axis=1), y.max(axis=1))
+    ex, ey = np.exp(x - m[:, None]), np.exp(y - m[:, None])
+    den = np.zeros(n)
+    for d in range(D):
+        den = den + ex[:, d]
+    for d in range(D):
+        den = den + ey[:, d]
+    post, ppost = ex / den[:, None], ey / den[:, None]
+    dp = np.zeros(n)
+    for d in range(D):
+        dp = dp + ppost[:, d]
+    best, second = best_second(s, log_prior)
+    best_pair = _argmax_first(y, anchor).astype(np.uint8) if D > 1 else np.full(n, NONE, np.uint8)
+    pb = post[np.arange(n), best]
+    status = np.where(np.asarray(entries) < int(prm["min_loci"]), UNASSIGNED,
+                      np.where(dp > 0.5, DOUBLET, np.where(pb >= float(prm["posterior_threshold"]), SINGLET, AMBIGUOUS))).astype(np.uint8)
+    return dict(posterior=post, pair_posterior=ppost, doublet_posterior=dp, best=best, second=second, best_pair=best_pair, status=status,
+                x=x, y=y)
+
+
+def posteriors(mat, gt_used, alt_total, ref_total, log_prior=None, anchor=None, tab1=None, tab2=None, **params):
+    """cellector_donor_posteriors on host arrays.  mat: a cluster.Matrix over the used loci, built with the call's mask; gt_used
+    [D, L] the donors' genotypes at the used loci; alt_total, ref_total [L] the loci's totals (Cellector.locus_counts).  tab1 / tab2:
+    the device's tables, for the device's bits in ll and pair_ll; None = numpy's.  Returns the dict of Cellector.donor_posteriors
+    (summary: a dict)."""
+    prm = _params(params)
+    g = np.asarray(gt_used, np.uint8).T
+    if tab1 is None or tab2 is None:
+        tab1, tab2 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mat.mask)
+    s = singlet_sums(mat, tab1, g)
+    best, _ = best_second(s, log_prior)
+    anchor = best if anchor is None else np.asarray(anchor, np.uint8)
+    p = pair_sums(mat, tab2, g, anchor)
+    out = chain(s, p, anchor, mat.entries, log_prior, **prm)
+    st = out["status"]
+    out.update(ll=s, pair_ll=p, anchor=anchor, n_entries=mat.entries.astype(np.uint32), tab1=tab1, tab2=tab2,
+               summary=dict(n_singlet=int((st == SINGLET).sum()), n_doublet=int((st == DOUBLET).sum()),
+                            n_ambiguous=int((st == AMBIGUOUS).sum()), n_unassigned=int((st == UNASSIGNED).sum()),
+                            donor_cells=np.bincount(out["best"][st == SINGLET], minlength=g.shape[1])))
+    return out
+
+
+def match(alt, ref, cells, gt_used, alt_total, ref_total, mask=None, tab1=None, **params):
+    """cellector_match_donors on host arrays from the class tallies alt, ref [K, L] and cells [K]: dict of ll [K, D], best, margin"""
+    prm = _params(params)
+    g = np.asarray(gt_used, np.uint8).T
+    if tab1 is None:
+        tab1 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mask)[0]
+    ll = match_sums(alt, ref, tab1, g, mask)
+    K, D = ll.shape
+    best = np.argmax(ll, axis=1)
+    if D > 1:
+        rest = ll.copy()
+        rest[np.arange(K), best] = -np.inf
+        margin = ll[np.arange(K), best] - rest.max(axis=1)
+    else:
+        margin = np.full(K, np.inf)
+    live = np.asarray(cells) > 0
+    return dict(ll=ll, best=np.where(live, best, NONE).astype(np.uint8), margin=np.where(live, margin, 0.0))
+
+
+# ---- the donors' genotypes from a VCF ----------------------------------------------------------------------------------------------
+def parse_gt(field, gt_index=0):
+    """0, 1 or 2 = the number of alt alleles of a diploid biallelic GT ("0/1", "1|0", ...) in a sample field; 3 for anything else (a
+    missing or half-missing call, a third allele, another ploidy, no GT at that index)"""
+    parts = field.split(":")
+    if gt_index < 0 or gt_index >= len(parts):
+        return NO_CALL
+    al = parts[gt_index].replace("|", "/").split("/")
+    if len(al) != 2 or any(a not in ("0", "1") for a in al):
+        return NO_CALL
+    return int(al[0]) + int(al[1])
+
+
+def _sample_names(path):
+    import gzip
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt") as f:
+        for line in f:
+            if line.startswith("#CHROM"):
+                return line.rstrip("\n").split("\t")[9:]
+            if not line.startswith("#"):
+                break
+    raise ValueError(f"{path}: no #CHROM header line with sample columns")
+
+
+def read_donor_vcf(donor_vcf, variant_vcf):
+    """(names, gt): the donors' genotypes gt [D, total_loci] uint8 in the row order of the variant VCF the matrix was counted on.  A
+    donor record is matched to the variant VCF's record with the same (chrom, pos, ref, alt); one whose ref and alt are swapped is
+    matched too and its calls are mirrored (0/0 <-> 1/1).  A variant without a donor record, and an unparsable, missing or
+    non-biallelic GT, is 3 (no call); when the donor VCF repeats a record the last one counts."""
+    names = _sample_names(donor_vcf)
+    rows = {}
+    n = 0
+    for chrom, pos, toks in combine._vcf_records(variant_vcf, columns=True):
+        rows[(chrom, pos, toks[3], toks[4])] = n  # (a repeated variant: the last row takes the calls)
+        n += 1
+    gt = np.full((len(names), n), NO_CALL, np.uint8)
+    for chrom, pos, toks in combine._vcf_records(donor_vcf, columns=True):
+        if len(toks) < 10:
+            continue
+        at, swap = rows.get((chrom, pos, toks[3], toks[4])), False
+        if at is None:
+            at, swap = rows.get((chrom, pos, toks[4], toks[3])), True
+        if at is None:
+            continue
+        fmt = toks[8].split(":")
+        gi = fmt.index("GT") if "GT" in fmt else -1
+        for d in range(len(names)):
+            g = parse_gt(toks[9 + d], gi) if 9 + d < len(toks) else NO_CALL
+            gt[d, at] = g if g == NO_CALL or not swap else 2 - g
+    return names, gt

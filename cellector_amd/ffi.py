@@ -88,6 +88,10 @@ SIGNATURES = {
     "cellector_cluster": (_i, [_vp, C.c_uint32, C.c_uint32, _u64] + [_vp] * 8),
     "cellector_cluster_m_step": (_i, [_vp, _vp, C.c_uint32, _vp, _d] + [_vp] * 4),
     "cellector_cluster_e_step": (_i, [_vp, _vp, C.c_uint32, C.c_uint32] + [_vp] * 5),
+    "cellector_donor_default_params": (_i, [_vp]),
+    "cellector_donor_tables": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "cellector_donor_posteriors": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
+    "cellector_match_donors": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -141,6 +145,14 @@ class ClusterParams(C.Structure):
 class ClusterSummary(C.Structure):
     _fields_ = [("best_restart", C.c_uint32), ("iterations", C.c_uint32), ("stages", C.c_uint32), ("reserved", C.c_uint32),
                 ("iterations_per_stage", C.c_uint32 * 16), ("cluster_cells", _u64 * 16), ("n_unlabelled", _u64)]
+
+
+class DonorParams(C.Structure):
+    _fields_ = [("err", _d), ("ambient", _d), ("doublet_rate", _d), ("posterior_threshold", _d), ("min_loci", _u64)]
+
+
+class DonorSummary(C.Structure):
+    _fields_ = [("n_singlet", _u64), ("n_doublet", _u64), ("n_ambiguous", _u64), ("n_unassigned", _u64), ("donor_cells", _u64 * 64)]
 
 
 class CellectorError(RuntimeError):
@@ -815,6 +827,76 @@ class Cellector:
         s, w, obj = np.zeros((n, Ja), np.float64), np.zeros((n, Ja), np.float64), np.zeros(min(max(R, 0), 64), np.float64)
         self._ck(self._lib.cellector_cluster_e_step(self.h, _p(tab), max(K, 0), max(R, 0), _p(temp), _p(mask), _p(s), _p(w), _p(obj)))
         return dict(s=s, w=w, objective=obj)
+
+    # ---- donor demultiplexing: cells and classes against known genotypes gt [D, total_loci] (0 = 0/0, 1 = 0/1, 2 = 1/1, 3 = no
+    # call); donors.py is the numpy twin
+    def donor_default_params(self):
+        p = DonorParams()
+        self._ck(self._lib.cellector_donor_default_params(C.byref(p)))
+        return p
+
+    def _donor_args(self, gt, mask, params):
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        TL = self.dims().total_loci
+        if gt.ndim != 2 or (self.dims().total_cells and gt.shape[1] != TL):
+            raise ValueError(f"gt: shape (D, {TL}) expected, got {gt.shape}")
+        p = self.donor_default_params()
+        for k, v in params.items():
+            if k not in dict(DonorParams._fields_):
+                raise TypeError(f"donors: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return gt, gt.shape[0], self._cluster_mask(mask), p
+
+    def donor_tables(self, gt, mask=None, **params):
+        """The packed genotypes and the per-locus tables of the donor calls alone (cellector_donor_tables): dict of tab1 [L, 4, 2],
+        tab2 [L, 16, 2] = (log theta, log(1 - theta)) and packed [L, W] uint64, W = ceil(D / 32).  params: err, ambient (DonorParams)."""
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        L, W = self.dims().loci_used, (min(max(D, 1), 64) + 31) // 32
+        tab1, tab2, packed = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64), np.zeros((L, W), np.uint64)
+        self._ck(self._lib.cellector_donor_tables(self.h, _p(gt), D, C.byref(p), _p(mask), _p(tab1), _p(tab2), _p(packed)))
+        return dict(tab1=tab1, tab2=tab2, packed=packed)
+
+    def donor_posteriors(self, gt, log_prior=None, anchor=None, mask=None, tables=False, **params):
+        """Every cell against D genotyped donors and the D - 1 doublets of its anchor donor with every other one
+        (cellector_donor_posteriors).  anchor None = the best singlet.  params: err, ambient, doublet_rate, posterior_threshold,
+        min_loci (DonorParams).  Returns a dict: ll, pair_ll, posterior, pair_posterior [cells, D], doublet_posterior, best, second,
+        best_pair, n_entries, status (0 singlet, 1 doublet, 2 ambiguous, 255 unassigned), anchor [cells], summary (DonorSummary) and,
+        with tables, tab1 / tab2."""
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        Da = min(max(D, 1), 64)
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used  # (before a load the library refuses the call)
+        log_prior = None if log_prior is None else np.ascontiguousarray(log_prior, np.float64)
+        if log_prior is not None and log_prior.shape != (D,):
+            raise ValueError(f"log_prior: {D} values expected, got shape {log_prior.shape}")
+        anchor = None if anchor is None else np.ascontiguousarray(anchor, np.uint8)
+        if anchor is not None and anchor.shape != (n,):
+            raise ValueError(f"anchor: {n} values expected, got shape {anchor.shape}")
+        out = {k: np.zeros((n, Da), np.float64) for k in ("ll", "pair_ll", "posterior", "pair_posterior")}
+        out["doublet_posterior"] = np.zeros(n, np.float64)
+        for k in ("best", "second", "best_pair"):
+            out[k] = np.zeros(n, np.uint8)
+        out["n_entries"] = np.zeros(n, np.uint32)
+        out["status"], out["anchor"] = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        if tables:
+            out["tab1"], out["tab2"] = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64)
+        s = DonorSummary()
+        self._ck(self._lib.cellector_donor_posteriors(
+            self.h, _p(gt), D, C.byref(p), _p(log_prior), _p(anchor), _p(mask), _p(out["ll"]), _p(out["pair_ll"]), _p(out["posterior"]),
+            _p(out["pair_posterior"]), _p(out["doublet_posterior"]), _p(out["best"]), _p(out["second"]), _p(out["best_pair"]),
+            _p(out["n_entries"]), _p(out["status"]), _p(out["anchor"]), C.byref(s), _p(out.get("tab1")), _p(out.get("tab2"))))
+        out["summary"] = s
+        return out
+
+    def match_donors(self, labels, n_classes, gt, mask=None, **params):
+        """The K classes of a labelling against D genotyped donors (cellector_match_donors): dict of ll [K, D], best [K] uint8 (255:
+        a class without a cell), margin [K] (best minus runner-up) and cells [K].  Two classes may name the same donor."""
+        labels, K, _, _, _ = self._class_args(labels, n_classes)
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        Ka, Da = min(K, 16), min(max(D, 1), 64)
+        ll, best, margin, cells = np.zeros((Ka, Da), np.float64), np.zeros(Ka, np.uint8), np.zeros(Ka, np.float64), np.zeros(Ka, np.uint64)
+        self._ck(self._lib.cellector_match_donors(self.h, _p(labels), K, _p(gt), D, C.byref(p), _p(mask), _p(ll), _p(best), _p(margin),
+                                                  _p(cells)))
+        return dict(ll=ll, best=best, margin=margin, cells=cells)
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

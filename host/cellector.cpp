@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../include/cellector_ffi.h"
+#include "donor_vcf_host.h"
 #include "genotype_host.h"
 
 namespace {
@@ -199,6 +200,9 @@ struct Params {
     uint64_t cluster = 0;                              // K (0: off)
     uint64_t cluster_restarts = 0;                     // R (0: min(16, 64 / K))
     bool cluster_mask_loop = false;                    // --cluster_mask loop: the loci the loop's last iteration used (all: every used locus)
+    // extension: donor demultiplexing after the ordinary run (cellector_donor_posteriors / cellector_match_donors; one GPU)
+    std::optional<std::string> donors;                 // the donors' genotypes, a VCF with one sample column per donor (needs --vcf)
+    double donor_error = 0.01, donor_ambient = 0.03, donor_doublet_rate = 0.1;
 };
 
 const char *USAGE =
@@ -324,7 +328,20 @@ const char *USAGE =
     "        --cluster_restarts <R>                                             with --cluster: random restarts run side by side, K R <= 64\n"
     "                                                                       (default min(16, 64 / K))\n"
     "        --cluster_mask <all|loop>                                          with --cluster: fit on every used locus, or on the loci the\n"
-    "                                                                       loop's last iteration used (default all)\n";
+    "                                                                       loop's last iteration used (default all)\n"
+    "        --donors <vcf>                                                     after the ordinary run, score every cell against the genotyped\n"
+    "                                                                       donors of the pool: a VCF with one sample column per donor (at\n"
+    "                                                                       most 64), matched to --vcf's records by chrom, pos, ref and alt; a\n"
+    "                                                                       missing record or call counts as no call.  Writes\n"
+    "                                                                       <output_directory>/cellector_donors.tsv: barcode, singlet /\n"
+    "                                                                       doublet / ambiguous / unassigned, donor, second donor, best pair,\n"
+    "                                                                       the three posteriors, n_loci, the donors' log-likelihoods.  With\n"
+    "                                                                       --classes or --cluster also cellector_cluster_donors.tsv: class,\n"
+    "                                                                       cells, donor, margin, the donors' sums.  Needs --vcf.  No other\n"
+    "                                                                       output changes (not in the reference; one GPU)\n"
+    "        --donor_error <e>                                                  with --donors: allele fraction of a homozygous call (default 0.01)\n"
+    "        --donor_ambient <a>                                                with --donors: share of ambient reads (default 0.03)\n"
+    "        --donor_doublet_rate <r>                                           with --donors: prior mass of the doublets (default 0.1)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -352,7 +369,8 @@ Params load_params(int argc, char **argv)
                                   "resolve_near_ties", "resolve_assignments", "initial_minority", "cell_detail", "normalization",
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
-                                  "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask"};
+                                  "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask", "donors",
+                                  "donor_error", "donor_ambient", "donor_doublet_rate"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -473,6 +491,21 @@ Params load_params(int argc, char **argv)
         if (!p.classes && !p.cluster) die(1, "error: The argument '--refine_classes <max_iter>' requires '--classes <file>'");
         if (p.refine_classes > 0xffffffffull) die(1, "error: Invalid value '" + got["refine_classes"] + "' for '--refine_classes <max_iter>'");
     }
+    if (got.count("donors")) {
+        p.donors = got["donors"];
+        if (!p.vcf) die(1, "error: The argument '--donors <vcf>' requires '--vcf <vcf>'");
+        if (p.devices_auto || p.devices.size() > 1)
+            die(1, "error: The argument '--donors <vcf>' works on one GPU and cannot be used with '--devices <a,b,...>'");
+    }
+    for (const char *flag : {"donor_error", "donor_ambient", "donor_doublet_rate"})
+        if (got.count(flag)) {
+            if (!p.donors) die(1, std::string("error: The argument '--") + flag + "' requires '--donors <vcf>'");
+            const double v = parse_f64(flag, got[flag]);
+            const std::string f = flag;
+            const bool ok = f == "donor_error" ? v > 0.0 && v < 0.5 : v >= 0.0 && v < 1.0;
+            if (!ok) die(1, "error: Invalid value '" + got[flag] + "' for '--" + f + "': expected a number in " + (f == "donor_error" ? "(0, 0.5)" : "[0, 1)"));
+            (f == "donor_error" ? p.donor_error : f == "donor_ambient" ? p.donor_ambient : p.donor_doublet_rate) = v;
+        }
     if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
     if (got.count("mix_ref")) p.mix_ref = got["mix_ref"];
     if (got.count("mix_barcodes")) p.mix_barcodes = got["mix_barcodes"];
@@ -1305,6 +1338,7 @@ int main(int argc, char **argv)
         });
         fclose(f);
         lap("cellector_classes.tsv");
+        class_label = lab;  // (--donors names the classes of the labelling in force)
         // --class_genotypes: a cell counts in the class its class_assignment names; doublet and unassigned cells are in none
         if (params.class_genotypes) {
             const uint64_t TL = dm.total_loci;
@@ -1360,6 +1394,81 @@ int main(int argc, char **argv)
                 }
             fclose(fc);
             lap("cellector_classes.vcf");
+        }
+    }
+    // --donors: every cell against the genotyped donors of the pool, and the classes in force (--classes / --cluster, refined if asked)
+    // named by donor
+    if (params.donors) {
+        DonorGenotypes dg;
+        {
+            Lines vin(*params.vcf);
+            std::string line;
+            while (vin.next(line)) dg.add_variant_line(line);
+            Lines din(*params.donors);
+            while (din.next(line)) dg.add_donor_line(line);
+        }
+        const uint32_t D = (uint32_t)dg.names.size();
+        if (D < 1 || D > 64) die(1, "error: --donors " + *params.donors + ": " + std::to_string(dg.names.size()) + " sample columns, 1..64 donors are supported");
+        if (dg.total_loci != dm.total_loci)
+            die(1, "error: --donors: --vcf " + *params.vcf + " has " + std::to_string(dg.total_loci) + " records but the matrix has " +
+                       std::to_string(dm.total_loci) + " loci");
+        cellector_donor_params dp;
+        cellector_donor_default_params(&dp);
+        dp.err = params.donor_error; dp.ambient = params.donor_ambient; dp.doublet_rate = params.donor_doublet_rate;
+        dp.posterior_threshold = params.posterior_threshold;
+        dp.min_loci = std::max<uint64_t>(params.min_loci_used, 1);
+        std::vector<double> dll((uint64_t)N * D), dpost((uint64_t)N * D), dppost((uint64_t)N * D), ddbl(N);
+        std::vector<uint8_t> dbest(N), dsecond(N), dpair(N), dstatus(N);
+        std::vector<uint32_t> dn(N);
+        cellector_donor_summary ds;
+        g.ck(cellector_donor_posteriors(g.c, dg.gt.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(), dppost.data(),
+                                        ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(), dstatus.data(), nullptr, &ds,
+                                        nullptr, nullptr), "donor_posteriors");
+        fprintf(stderr, "donors: %u donors, singlet=%llu doublet=%llu ambiguous=%llu unassigned=%llu\n", D, (unsigned long long)ds.n_singlet,
+                (unsigned long long)ds.n_doublet, (unsigned long long)ds.n_ambiguous, (unsigned long long)ds.n_unassigned);
+        FILE *f = create(od + "/cellector_donors.tsv");
+        std::string head = "barcode\tstatus\tdonor\tsecond_donor\tbest_pair\tposterior\tpair_posterior\tdoublet_posterior\tn_loci";
+        for (uint32_t d = 0; d < D; d++) head += "\tlog_likelihood_" + dg.names[d];
+        head += '\n';
+        fputs(head.c_str(), f);
+        write_rows(f, N, [&](uint64_t c, std::string &o) {
+            static const char *const STATUS[3] = {"singlet", "doublet", "ambiguous"};
+            const uint8_t b = dbest[c];
+            o += barcodes[c]; o += '\t'; o += dstatus[c] < 3 ? STATUS[dstatus[c]] : "unassigned"; o += '\t';
+            o += dg.names[b]; o += '\t';
+            o += dsecond[c] == 255 ? "na" : dg.names[dsecond[c]].c_str(); o += '\t';
+            if (dpair[c] == 255) o += "na";
+            else { o += dg.names[b]; o += '+'; o += dg.names[dpair[c]]; }
+            o += '\t'; put(o, dpost[c * D + b]);
+            o += '\t'; put(o, dpair[c] == 255 ? 0.0 : dppost[c * D + dpair[c]]);
+            o += '\t'; put(o, ddbl[c]);
+            o += '\t'; put(o, (uint64_t)dn[c]);
+            for (uint32_t d = 0; d < D; d++) { o += '\t'; put(o, dll[c * D + d]); }
+            o += '\n';
+        });
+        fclose(f);
+        lap("cellector_donors.tsv");
+        if (params.classes || params.cluster) {
+            const uint32_t K = (uint32_t)class_names.size();
+            std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), mbest(K);
+            std::vector<double> mll((uint64_t)K * D), margin(K);
+            std::vector<uint64_t> mcells(K);
+            g.ck(cellector_match_donors(g.c, lab.data(), K, dg.gt.data(), D, &dp, nullptr, mll.data(), mbest.data(), margin.data(), mcells.data()),
+                 "match_donors");
+            FILE *fm = create(od + "/cellector_cluster_donors.tsv");
+            std::string mh = "class\tcells\tdonor\tmargin";
+            for (uint32_t d = 0; d < D; d++) mh += "\tlog_likelihood_" + dg.names[d];
+            mh += '\n';
+            fputs(mh.c_str(), fm);
+            for (uint32_t k = 0; k < K; k++) {
+                std::string o = class_names[k];
+                o += '\t'; put(o, mcells[k]); o += '\t'; o += mbest[k] == 255 ? "na" : dg.names[mbest[k]].c_str(); o += '\t'; put(o, margin[k]);
+                for (uint32_t d = 0; d < D; d++) { o += '\t'; put(o, mll[(uint64_t)k * D + d]); }
+                o += '\n';
+                fputs(o.c_str(), fm);
+            }
+            fclose(fm);
+            lap("cellector_cluster_donors.tsv");
         }
     }
     // Every output file is closed: leave without tearing the context down.  Handing ~150 GB of device memory back block

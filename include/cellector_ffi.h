@@ -841,6 +841,85 @@ cellector_status cellector_cluster_e_step(cellector_ctx *ctx, const double *tab 
                                           const double *temp /*[cells] or NULL = 1*/, const uint8_t *mask, double *s /*[cells][J]*/,
                                           double *w /*[cells][J]*/, double *objective /*[R]*/); /* any output may be NULL */
 
+/* ---- donor demultiplexing: cells and classes against KNOWN genotypes ---------------------------------------------
+ * The calls above find genotypes nobody told them about.  When the donors of a pool have been genotyped (a SNP array or a WGS VCF
+ * per donor) these calls answer "which donor is this barcode, or is it a doublet of two", and name the classes of a labelling by
+ * donor.  The model below is the specification (cellector_amd/donors.py repeats it in numpy); no parity with any other
+ * demultiplexer is claimed.
+ *   D donors, 1 <= D <= 64.  gt [D][total_loci] u8, indexed by the matrix' own locus index (as the planes of
+ *   cellector_class_genotypes): 0 = 0/0, 1 = 0/1, 2 = 1/1, 3 = no call; any other value is CELLECTOR_EINVAL.  mask [L] or NULL = all
+ *   loci, as in cellector_class_posteriors.  The entries of a cell are those of its by-cell CSR row (cellector_csr_rows) at used,
+ *   unmasked loci, in row order; a repeated (locus, cell) pair counts each time.  All arithmetic is f64 without contraction: every
+ *   product and every sum below rounds once.
+ *   1 packing: gt is uploaded once and packed on the device over the used loci (cellector_locus_ids) into W = ceil(D / 32) u64 words
+ *     per locus, packed [L][W]: donor d at bits 2 (d & 31) of word d >> 5; the bits above the last donor are 0.
+ *   2 per used, unmasked locus l: A, R = the alt and ref sums over all of the locus' entries (whole numbers: what
+ *     cellector_locus_counts returns); soup = ((double)A + 1.0) / ((double)(A + R) + 2.0); e_0 = err, e_1 = 0.5, e_2 = 1.0 - err,
+ *     e_3 = soup; theta_g = ((1.0 - ambient) e_g) + (ambient soup).  A donor without a call is scored at the pool's allele fraction.
+ *   3 tables, with the device's log: tab1 [L][4][2] = (log theta_g, log(1.0 - theta_g)); tab2 [L][16][2] at index 4 g_a + g_b from
+ *     theta = 0.5 (theta_{g_a} + theta_{g_b}).  (x + x) 0.5 is x: tab2[l][5 g] carries the bits of tab1[l][g].  A masked locus' rows
+ *     are (0, 0) and no sum visits it.
+ *   4 singlets: s_cd = the sum over the cell's entries in row order of ((alt la) + (ref lb)), (la, lb) = tab1[l][g_d(l)]: both
+ *     products rounded, then their sum, then that added to the accumulator, strictly sequential per (cell, donor) from 0.0 (step 4
+ *     of the cluster model).  u_d = s_cd + log_prior[d] (NULL: + 0.0).  best = the d that maximises u_d, second = the d != best
+ *     that does (255 with D = 1), the smallest d on ties.
+ *   5 anchor: a_c = anchor[c] if given (< D), else best.
+ *   6 pairs: p_cd = the same sequential sum with tab2[l][4 g_{a_c}(l) + g_d(l)], for every d; column d = a_c is the bits of
+ *     s_{c, a_c} by step 3 and takes no part in the chain.
+ *   7 chain: one softmax over 2 D - 1 hypotheses: the D singlets x_d = u_d + log_singlet, then the D - 1 pairs (a_c, d), d
+ *     ascending, y_d = p_cd + log_pair; log_singlet = log(1.0 - doublet_rate), log_pair = log(doublet_rate / (double)(D - 1)) with
+ *     the host's log (D = 1: no pairs).  m = the maximum of all terms; den = sum exp(t - m) in that order from 0.0;
+ *     posterior_d = exp(x_d - m) / den; pair_posterior_d = exp(y_d - m) / den, 0 at d = a_c; doublet_posterior = the sum of the pair
+ *     posteriors in ascending d from 0.0; best_pair = the d of the largest y_d, the smallest on ties (255 with D = 1).
+ *   8 status: 255 = unassigned when n_entries < min_loci; else 1 = doublet when doublet_posterior > 0.5 (strict, main.rs:150); else
+ *     0 = singlet when posterior[best] >= posterior_threshold; else 2 = ambiguous.  n_entries = the cell's entries at used, unmasked
+ *     loci.  The summary counts the four and, for status 0, the cells per donor.
+ *   Why anchored pairs: all D (D - 1) / 2 pairs are 2016 columns at D = 64.  The chain is exact whenever the best pair contains the
+ *   best singlet; a caller who doubts that sweeps any other donor through the anchor argument (anchor_out returns the one used).
+ *   cellector_match_donors: (a_kl, r_kl) = the tallies of cellector_class_tallies under (labels, K); ll_kd = the sum over ascending
+ *   unmasked l of (((double)a la) + ((double)r lb)) from tab1, strictly sequential from 0.0; best = argmax_d, the smallest d on ties,
+ *   255 for a class without a cell; margin = ll[best] minus the runner-up (+inf with D = 1, 0 for a class without a cell).  It
+ *   solves no assignment problem: two classes may name the same donor, and the caller sees that.
+ * Defaults (cellector_donor_default_params): err 0.01, ambient 0.03, doublet_rate 0.1, posterior_threshold 0.999, min_loci 1.
+ * Scope as cellector_class_posteriors: a loaded matrix, no iteration in flight, engines 1 and 2, a single-device ctx that holds all
+ * cells.  CELLECTOR_EINVAL with a message, nothing written or launched, for these and for D outside 1..64, NULL gt, a gt value above
+ * 3 (the message names the donor and the locus), err outside (0, 0.5), ambient outside [0, 1), doublet_rate outside [0, 1), a
+ * posterior_threshold outside [0, 1], min_loci == 0, a log_prior that is NaN or +inf or -inf for every donor, an anchor >= D, and
+ * the labels cellector_class_tallies refuses.  All device scratch is allocated before anything is launched (D bytes per locus of the
+ * matrix, 8 W + 321 B per used locus, 32 D + 17 B per cell; match: 16 K B per used locus): on CELLECTOR_ENOMEM the ctx is as it
+ * was.  The calls never touch the EM state (an interrupted EM loop continues with the same bits) and overwrite nothing of the ctx;
+ * they invalidate the caches cellector_cell_log_likelihoods invalidates. */
+typedef struct {
+    double err;                  /* 0.01:  the allele fraction of a homozygous-reference donor                  */
+    double ambient;              /* 0.03:  the share of a cell's reads that come from the pool                  */
+    double doublet_rate;         /* 0.1:   prior mass of the D - 1 anchored pairs together                      */
+    double posterior_threshold;  /* 0.999: a singlet is called at this posterior of its best donor              */
+    uint64_t min_loci;           /* 1:     a cell with fewer entries at used, unmasked loci is unassigned (255) */
+} cellector_donor_params;
+typedef struct {
+    uint64_t n_singlet, n_doublet, n_ambiguous, n_unassigned;  /* status 0, 1, 2, 255                            */
+    uint64_t donor_cells[64];    /* status-0 cells per best donor                                               */
+} cellector_donor_summary;
+cellector_status cellector_donor_default_params(cellector_donor_params *out);
+cellector_status cellector_donor_tables(cellector_ctx *ctx, const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                        const cellector_donor_params *p /*NULL = defaults*/, const uint8_t *mask /*[L] or NULL*/,
+                                        double *tab1 /*[L][4][2]*/, double *tab2 /*[L][16][2]*/,
+                                        uint64_t *packed /*[L][W]*/); /* any output may be NULL */
+cellector_status cellector_donor_posteriors(cellector_ctx *ctx, const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                            const cellector_donor_params *p /*NULL = defaults*/, const double *log_prior /*[D] or NULL*/,
+                                            const uint8_t *anchor /*[cells] or NULL*/, const uint8_t *mask /*[L] or NULL*/,
+                                            double *ll /*[cells][D]*/, double *pair_ll /*[cells][D]*/, double *posterior /*[cells][D]*/,
+                                            double *pair_posterior /*[cells][D]*/, double *doublet_posterior /*[cells]*/,
+                                            uint8_t *best /*[cells]*/, uint8_t *second /*[cells]*/, uint8_t *best_pair /*[cells]*/,
+                                            uint32_t *n_entries /*[cells]*/, uint8_t *status /*[cells]*/, uint8_t *anchor_out /*[cells]*/,
+                                            cellector_donor_summary *out, double *tab1 /*[L][4][2]*/,
+                                            double *tab2 /*[L][16][2]*/); /* any output may be NULL */
+cellector_status cellector_match_donors(cellector_ctx *ctx, const uint8_t *labels /*[cells]*/, uint32_t n_classes,
+                                        const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                        const cellector_donor_params *p /*NULL = defaults*/, const uint8_t *mask /*[L] or NULL*/,
+                                        double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
+                                        uint64_t *cells /*[K]*/); /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
