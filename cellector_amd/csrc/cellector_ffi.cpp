@@ -1725,6 +1725,96 @@ cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels,
     return donor_match_run(c, labels, n_classes, gt, n_donors, &prm, mask, ll, best, margin, cells);
 }
 
+// ---- ambient fraction estimation: kernels_ambient.hip --------------------------------------------------------------
+cellector_status cellector_ambient_default_params(cellector_ambient_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->err = 0.01;
+    out->lo = 0.0;
+    out->hi = 0.5;
+    out->grid = 16;
+    out->rounds = 3;
+    out->min_loci = 1;
+    return CELLECTOR_OK;
+}
+
+// what every ambient call checks before anything is written or launched: the scope of the donor calls, then the arguments all share
+static cellector_status ambient_scope_check(cellector_ctx *c, const char *what, uint32_t G, double err)
+{
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    if (G < 4 || G > 32) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u grid points, 4..32 are supported", what, G);
+    if (!(err > 0.0 && err < 0.5)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: err = %g is not within (0, 0.5)", what, err);
+    return CELLECTOR_OK;
+}
+static cellector_status ambient_grid_check(cellector_ctx *c, const char *what, const double *rho, uint32_t G)
+{
+    if (!rho) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null rho", what);
+    for (uint32_t j = 0; j < G; j++)
+        if (!(rho[j] >= 0.0 && rho[j] < 1.0)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: rho[%u] = %g is not within [0, 1)", what, j, rho[j]);
+    return CELLECTOR_OK;
+}
+static cellector_status ambient_sources_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t S, const uint8_t *assign,
+                                              uint64_t min_loci)
+{
+    if (S < 1 || S > 64) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u sources, 1..64 are supported", what, S);
+    if (!gt) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null gt", what);
+    if (!assign) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null assign", what);
+    if (min_loci < 1) return ctx_fail(c, CELLECTOR_EINVAL, "%s: min_loci must be at least 1", what);
+    const uint64_t TL = c->total_loci;
+    for (uint32_t s = 0; s < S; s++)
+        for (uint64_t t = 0; t < TL; t++)
+            if (gt[(uint64_t)s * TL + t] > 3)
+                return ctx_fail(c, CELLECTOR_EINVAL, "%s: gt of source %u at locus %llu is %u: 0 = 0/0, 1 = 0/1, 2 = 1/1, 3 = no call", what, s,
+                                (unsigned long long)t, (unsigned)gt[(uint64_t)s * TL + t]);
+    for (uint64_t i = 0; i < c->nloc; i++)
+        if (assign[i] != 255 && assign[i] >= S)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: assign of cell %llu is %u, neither 255 nor below the %u sources", what,
+                            (unsigned long long)i, (unsigned)assign[i], S);
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_ambient_tables(cellector_ctx *c, const double *rho, uint32_t n_grid, double err, const uint8_t *mask, double *tab)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(ambient_scope_check(c, "ambient_tables", n_grid, err));
+    CHK(ambient_grid_check(c, "ambient_tables", rho, n_grid));
+    SETDEV(c);
+    return ambient_tables_run(c, rho, n_grid, err, mask, tab);
+}
+
+cellector_status cellector_ambient_profile(cellector_ctx *c, const uint8_t *gt, uint32_t n_sources, const uint8_t *assign, const double *rho,
+                                           uint32_t n_grid, double err, uint64_t min_loci, const uint8_t *mask, double *ll, double *total,
+                                           double *source_total, uint64_t *source_cells, uint32_t *n_entries, double *cell_rho,
+                                           double *cell_se, double *tab)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(ambient_scope_check(c, "ambient_profile", n_grid, err));
+    CHK(ambient_grid_check(c, "ambient_profile", rho, n_grid));
+    CHK(ambient_sources_check(c, "ambient_profile", gt, n_sources, assign, min_loci));
+    SETDEV(c);
+    return ambient_profile_run(c, gt, n_sources, assign, rho, n_grid, err, min_loci, mask, ll, total, source_total, source_cells, n_entries,
+                               cell_rho, cell_se, tab);
+}
+
+cellector_status cellector_estimate_ambient(cellector_ctx *c, const uint8_t *gt, uint32_t n_sources, const uint8_t *assign,
+                                            const cellector_ambient_params *params, const uint8_t *mask, cellector_ambient_summary *summary,
+                                            double *cell_rho, double *cell_se, uint32_t *n_entries)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_ambient_params prm;
+    cellector_ambient_default_params(&prm);
+    if (params) prm = *params;
+    CHK(ambient_scope_check(c, "estimate_ambient", prm.grid, prm.err));
+    if (!(prm.lo >= 0.0 && prm.lo < prm.hi && prm.hi < 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "estimate_ambient: lo = %g, hi = %g do not satisfy 0 <= lo < hi < 1", prm.lo, prm.hi);
+    if (prm.rounds < 1 || prm.rounds > 8) return ctx_fail(c, CELLECTOR_EINVAL, "estimate_ambient: %u rounds, 1..8 are supported", prm.rounds);
+    CHK(ambient_sources_check(c, "estimate_ambient", gt, n_sources, assign, prm.min_loci));
+    SETDEV(c);
+    return ambient_estimate_run(c, gt, n_sources, assign, &prm, mask, summary, cell_rho, cell_se, n_entries);
+}
+
 // ---- class genotypes: kernels_genotypes.hip and genotype_host.h ---------------------------------------------
 // load_mtx_final + the rule of output_final_vcf (main.rs:52-131) for the K classes of a labelling
 cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, double ambient, double gt_threshold,

@@ -580,6 +580,16 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint3
 cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
                                  const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
                                  uint64_t *cells);
+cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *d_gt /*[D][total_loci]*/, uint64_t *d_packed /*[L][W]*/);
+// ambient fraction estimation (kernels_ambient.hip) on one device holding all cells; validated arguments, host arrays, scratch of their
+// own, nothing of the ctx written: the tables of a grid alone, one profile over a grid, the zooming grid search
+cellector_status ambient_tables_run(cellector_ctx *c, const double *rho, uint32_t G, double err, const uint8_t *mask, double *tab);
+cellector_status ambient_profile_run(cellector_ctx *c, const uint8_t *gt, uint32_t S, const uint8_t *assign, const double *rho, uint32_t G,
+                                     double err, uint64_t min_loci, const uint8_t *mask, double *ll, double *total, double *source_total,
+                                     uint64_t *source_cells, uint32_t *n_entries, double *cell_rho, double *cell_se, double *tab);
+cellector_status ambient_estimate_run(cellector_ctx *c, const uint8_t *gt, uint32_t S, const uint8_t *assign, const cellector_ambient_params *p,
+                                      const uint8_t *mask, cellector_ambient_summary *out, double *cell_rho, double *cell_se,
+                                      uint32_t *n_entries);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
 cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);

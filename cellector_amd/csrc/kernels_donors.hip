@@ -356,6 +356,18 @@ void donors_invalidate(cellector_ctx *c)
 
 }  // namespace
 
+// the packing alone, for the calls of other files that score cells against packed genotypes (kernels_ambient.hip): d_gt [D][TL] and
+// d_packed [L][W] on the device
+cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *d_gt, uint64_t *d_packed)
+{
+    const uint32_t W = (D + 31) / 32;
+    if (!c->L) return CELLECTOR_OK;
+    hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(c->L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, c->L * W, D, W,
+                       c->total_loci, c->locus_ids.get(), d_gt, d_packed);
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
+
 // cellector_donor_tables: validated arguments; host outputs, any may be null
 cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const uint8_t *mask,
                                   double *tab1, double *tab2, uint64_t *packed)

@@ -92,6 +92,10 @@ SIGNATURES = {
     "cellector_donor_tables": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "cellector_donor_posteriors": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_match_donors": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
+    "cellector_ambient_default_params": (_i, [_vp]),
+    "cellector_ambient_tables": (_i, [_vp, _vp, C.c_uint32, _d, _vp, _vp]),
+    "cellector_ambient_profile": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _d, _u64, _vp] + [_vp] * 8),
+    "cellector_estimate_ambient": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp] + [_vp] * 4),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -153,6 +157,16 @@ class DonorParams(C.Structure):
 
 class DonorSummary(C.Structure):
     _fields_ = [("n_singlet", _u64), ("n_doublet", _u64), ("n_ambiguous", _u64), ("n_unassigned", _u64), ("donor_cells", _u64 * 64)]
+
+
+class AmbientParams(C.Structure):
+    _fields_ = [("err", _d), ("lo", _d), ("hi", _d), ("grid", C.c_uint32), ("rounds", C.c_uint32), ("min_loci", _u64)]
+
+
+class AmbientSummary(C.Structure):
+    _fields_ = [("rho", _d), ("se", _d), ("curvature", _d), ("log_likelihood", _d), ("lo", _d), ("hi", _d), ("j_star", C.c_uint32),
+                ("at_boundary", C.c_uint32), ("rounds", C.c_uint32), ("reserved", C.c_uint32), ("n_cells_used", _u64),
+                ("source_rho", _d * 64), ("source_se", _d * 64), ("source_cells", _u64 * 64)]
 
 
 class CellectorError(RuntimeError):
@@ -897,6 +911,78 @@ class Cellector:
         self._ck(self._lib.cellector_match_donors(self.h, _p(labels), K, _p(gt), D, C.byref(p), _p(mask), _p(ll), _p(best), _p(margin),
                                                   _p(cells)))
         return dict(ll=ll, best=best, margin=margin, cells=cells)
+
+    # ---- ambient fraction estimation: the cells of every source scored at G ambient fractions at once; gt [S, total_loci] coded as
+    # for the donor calls, assign [cells] uint8 (255: the cell takes no part); ambient.py is the numpy twin
+    def ambient_default_params(self):
+        p = AmbientParams()
+        self._ck(self._lib.cellector_ambient_default_params(C.byref(p)))
+        return p
+
+    def _ambient_args(self, gt, assign, mask):
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        TL = self.dims().total_loci
+        n = self.n_local if self.dims().total_cells else 0  # (before a load the library refuses the call)
+        if gt.ndim != 2 or (self.dims().total_cells and gt.shape[1] != TL):
+            raise ValueError(f"gt: shape (S, {TL}) expected, got {gt.shape}")
+        assign = np.ascontiguousarray(assign, dtype=np.uint8)
+        if self.dims().total_cells and assign.shape != (n,):
+            raise ValueError(f"assign: {n} values expected, got shape {assign.shape}")
+        return gt, gt.shape[0], assign, self._cluster_mask(mask), n
+
+    def ambient_tables(self, rho, err=0.01, mask=None):
+        """The per-locus tables of one grid of ambient fractions alone (cellector_ambient_tables): dict of tab [L, 4, G, 2] = (log theta,
+        log(1 - theta)), theta = (1 - rho_j) e_g + rho_j soup."""
+        rho = np.ascontiguousarray(rho, np.float64)
+        if rho.ndim != 1:
+            raise ValueError(f"rho: one dimension expected, got shape {rho.shape}")
+        G = len(rho)
+        tab = np.zeros((self.dims().loci_used, 4, min(max(G, 1), 32), 2), np.float64)
+        self._ck(self._lib.cellector_ambient_tables(self.h, _p(rho), G, float(err), _p(self._cluster_mask(mask)), _p(tab)))
+        return dict(tab=tab)
+
+    def ambient_profile(self, gt, assign, rho, err=0.01, min_loci=1, mask=None, tables=False):
+        """The profile log-likelihood over a caller's grid rho [G] (cellector_ambient_profile).  Returns a dict: ll [cells, G], total
+        [G], source_total [S, G], source_cells [S], n_entries, cell_rho, cell_se [cells] (NaN for a cell that takes no part or has
+        fewer than min_loci entries) and, with tables, tab [L, 4, G, 2]."""
+        gt, S, assign, mask, n = self._ambient_args(gt, assign, mask)
+        rho = np.ascontiguousarray(rho, np.float64)
+        if rho.ndim != 1:
+            raise ValueError(f"rho: one dimension expected, got shape {rho.shape}")
+        G = len(rho)
+        Ga, Sa = min(max(G, 1), 32), min(max(S, 1), 64)
+        out = dict(ll=np.zeros((n, Ga), np.float64), total=np.zeros(Ga, np.float64), source_total=np.zeros((Sa, Ga), np.float64),
+                   source_cells=np.zeros(Sa, np.uint64), n_entries=np.zeros(n, np.uint32), cell_rho=np.zeros(n, np.float64),
+                   cell_se=np.zeros(n, np.float64))
+        if tables:
+            out["tab"] = np.zeros((self.dims().loci_used, 4, Ga, 2), np.float64)
+        self._ck(self._lib.cellector_ambient_profile(
+            self.h, _p(gt), S, _p(assign), _p(rho), G, float(err), int(min_loci), _p(mask), _p(out["ll"]), _p(out["total"]),
+            _p(out["source_total"]), _p(out["source_cells"]), _p(out["n_entries"]), _p(out["cell_rho"]), _p(out["cell_se"]),
+            _p(out.get("tab"))))
+        return out
+
+    def estimate_ambient(self, gt, assign, mask=None, **params):
+        """The pool's ambient fraction by a grid search that zooms in (cellector_estimate_ambient).  params: err, lo, hi, grid, rounds,
+        min_loci (AmbientParams).  Returns a dict: rho, se, curvature, log_likelihood, lo, hi, j_star, at_boundary, rounds,
+        n_cells_used, source_rho, source_se, source_cells [S], the first round's cell_rho, cell_se, n_entries [cells], and summary
+        (AmbientSummary)."""
+        gt, S, assign, mask, n = self._ambient_args(gt, assign, mask)
+        p = self.ambient_default_params()
+        for k, v in params.items():
+            if k not in dict(AmbientParams._fields_):
+                raise TypeError(f"ambient: unknown parameter {k!r}")
+            setattr(p, k, v)
+        s = AmbientSummary()
+        cell_rho, cell_se, cnt = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint32)
+        self._ck(self._lib.cellector_estimate_ambient(self.h, _p(gt), S, _p(assign), C.byref(p), _p(mask), C.byref(s), _p(cell_rho),
+                                                      _p(cell_se), _p(cnt)))
+        Sa = min(max(S, 0), 64)
+        out = {k: getattr(s, k) for k in ("rho", "se", "curvature", "log_likelihood", "lo", "hi", "j_star", "at_boundary", "rounds",
+                                          "n_cells_used")}
+        out.update(source_rho=np.array(s.source_rho[:Sa]), source_se=np.array(s.source_se[:Sa]),
+                   source_cells=np.array(s.source_cells[:Sa], np.uint64), cell_rho=cell_rho, cell_se=cell_se, n_entries=cnt, summary=s)
+        return out
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

@@ -21,6 +21,12 @@ for _i in range(1, 171):
     _FCACHE.append(_FCACHE[-1] * float(_i))
 
 
+def donor_codes(gt):
+    """the codes of cellector_class_genotypes' gt (1 = 1/1, 2 = 0/1, 3 = 0/0, 0 = ./.) in the coding of the donor and the ambient calls
+    (2 = 1/1, 1 = 0/1, 0 = 0/0, 3 = no call), uint8 of the same shape"""
+    return np.array([3, 2, 1, 0], np.uint8)[np.asarray(gt, np.int64)]
+
+
 def class_genotype_tallies(total_loci, coo, labels, n_classes):
     """(cells [K + 1], alt [K + 1, total_loci], ref [K + 1, total_loci]) uint64 from the all-loci COO arrays (locus, cell, alt,
     ref), e.g. Cellector.staged_coo(): per slot the sums of the allele counts of its cells' entries; slot K = the cells labelled

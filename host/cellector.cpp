@@ -203,6 +203,8 @@ struct Params {
     // extension: donor demultiplexing after the ordinary run (cellector_donor_posteriors / cellector_match_donors; one GPU)
     std::optional<std::string> donors;                 // the donors' genotypes, a VCF with one sample column per donor (needs --vcf)
     double donor_error = 0.01, donor_ambient = 0.03, donor_doublet_rate = 0.1;
+    // extension: the pool's ambient fraction measured from the donor pass' singlets (cellector_estimate_ambient)
+    int estimate_ambient = 0;                          // 0 = off, 1 = true: report it, 2 = apply: and score the donors again with it
 };
 
 const char *USAGE =
@@ -341,7 +343,16 @@ const char *USAGE =
     "                                                                       output changes (not in the reference; one GPU)\n"
     "        --donor_error <e>                                                  with --donors: allele fraction of a homozygous call (default 0.01)\n"
     "        --donor_ambient <a>                                                with --donors: share of ambient reads (default 0.03)\n"
-    "        --donor_doublet_rate <r>                                           with --donors: prior mass of the doublets (default 0.1)\n";
+    "        --donor_doublet_rate <r>                                           with --donors: prior mass of the doublets (default 0.1)\n"
+    "        --estimate_ambient <true|apply>                                    with --donors: measure the pool's share of ambient reads from\n"
+    "                                                                       the cells the donor pass calls singlets, each under its best\n"
+    "                                                                       donor (a profile likelihood over a grid that zooms in).  Writes\n"
+    "                                                                       cellector_ambient.tsv (the pool and every donor: cells, rho,\n"
+    "                                                                       se) and cellector_ambient_cells.tsv (barcode, donor, n_loci,\n"
+    "                                                                       rho, se; NA for a cell that took no part).  true: no other\n"
+    "                                                                       output changes.  apply: the donor pass runs again with the\n"
+    "                                                                       pooled estimate as its ambient share and those results are\n"
+    "                                                                       written; not with --donor_ambient (not in the reference)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -370,7 +381,7 @@ Params load_params(int argc, char **argv)
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
                                   "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask", "donors",
-                                  "donor_error", "donor_ambient", "donor_doublet_rate"};
+                                  "donor_error", "donor_ambient", "donor_doublet_rate", "estimate_ambient"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -506,6 +517,15 @@ Params load_params(int argc, char **argv)
             if (!ok) die(1, "error: Invalid value '" + got[flag] + "' for '--" + f + "': expected a number in " + (f == "donor_error" ? "(0, 0.5)" : "[0, 1)"));
             (f == "donor_error" ? p.donor_error : f == "donor_ambient" ? p.donor_ambient : p.donor_doublet_rate) = v;
         }
+    if (got.count("estimate_ambient")) {
+        const std::string &v = got["estimate_ambient"];
+        if (v != "true" && v != "apply" && v != "false")
+            die(EXIT_PANIC, "invalid value '" + v + "' for --estimate_ambient: expected true, apply or false");
+        p.estimate_ambient = v == "true" ? 1 : v == "apply" ? 2 : 0;
+        if (p.estimate_ambient && !p.donors) die(1, "error: The argument '--estimate_ambient <true|apply>' requires '--donors <vcf>'");
+        if (p.estimate_ambient == 2 && got.count("donor_ambient"))
+            die(1, "error: The argument '--estimate_ambient apply' cannot be used with '--donor_ambient <a>'");
+    }
     if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
     if (got.count("mix_ref")) p.mix_ref = got["mix_ref"];
     if (got.count("mix_barcodes")) p.mix_barcodes = got["mix_barcodes"];
@@ -1421,11 +1441,64 @@ int main(int argc, char **argv)
         std::vector<uint8_t> dbest(N), dsecond(N), dpair(N), dstatus(N);
         std::vector<uint32_t> dn(N);
         cellector_donor_summary ds;
-        g.ck(cellector_donor_posteriors(g.c, dg.gt.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(), dppost.data(),
-                                        ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(), dstatus.data(), nullptr, &ds,
-                                        nullptr, nullptr), "donor_posteriors");
-        fprintf(stderr, "donors: %u donors, singlet=%llu doublet=%llu ambiguous=%llu unassigned=%llu\n", D, (unsigned long long)ds.n_singlet,
-                (unsigned long long)ds.n_doublet, (unsigned long long)ds.n_ambiguous, (unsigned long long)ds.n_unassigned);
+        auto donor_pass = [&]() {
+            g.ck(cellector_donor_posteriors(g.c, dg.gt.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(),
+                                            dppost.data(), ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(), dstatus.data(),
+                                            nullptr, &ds, nullptr, nullptr), "donor_posteriors");
+            fprintf(stderr, "donors: %u donors, singlet=%llu doublet=%llu ambiguous=%llu unassigned=%llu\n", D,
+                    (unsigned long long)ds.n_singlet, (unsigned long long)ds.n_doublet, (unsigned long long)ds.n_ambiguous,
+                    (unsigned long long)ds.n_unassigned);
+        };
+        donor_pass();
+        // --estimate_ambient: the pool's ambient fraction from the singlets, each under its best donor; apply: the donors again with it
+        if (params.estimate_ambient) {
+            std::vector<uint8_t> assign(N);
+            for (uint64_t c = 0; c < N; c++) assign[c] = dstatus[c] == 0 ? dbest[c] : (uint8_t)255;
+            cellector_ambient_params ap;
+            cellector_ambient_default_params(&ap);
+            ap.err = params.donor_error;
+            cellector_ambient_summary as;
+            std::vector<double> crho(N), cse(N);
+            std::vector<uint32_t> cn(N);
+            g.ck(cellector_estimate_ambient(g.c, dg.gt.data(), D, assign.data(), &ap, nullptr, &as, crho.data(), cse.data(), cn.data()),
+                 "estimate_ambient");
+            {
+                std::string o = "ambient: rho=";
+                put(o, as.rho); o += " se="; put(o, as.se); o += " cells="; put(o, as.n_cells_used);
+                o += as.at_boundary ? " at_boundary=1\n" : " at_boundary=0\n";
+                fputs(o.c_str(), stdout);
+            }
+            FILE *fa = create(od + "/cellector_ambient.tsv");
+            fputs("source\tcells\trho\tse\n", fa);
+            {
+                std::string o = "pool\t";
+                put(o, as.n_cells_used); o += '\t'; put(o, as.rho); o += '\t'; put(o, as.se); o += '\n';
+                for (uint32_t d = 0; d < D; d++) {
+                    o += dg.names[d]; o += '\t'; put(o, as.source_cells[d]); o += '\t';
+                    if (as.source_cells[d]) { put(o, as.source_rho[d]); o += '\t'; put(o, as.source_se[d]); }
+                    else o += "NA\tNA";
+                    o += '\n';
+                }
+                fputs(o.c_str(), fa);
+            }
+            fclose(fa);
+            FILE *fc = create(od + "/cellector_ambient_cells.tsv");
+            fputs("barcode\tdonor\tn_loci\trho\tse\n", fc);
+            write_rows(fc, N, [&](uint64_t c, std::string &o) {
+                o += barcodes[c]; o += '\t';
+                if (assign[c] == 255) { o += "NA\tNA\tNA\tNA\n"; return; }
+                o += dg.names[assign[c]]; o += '\t'; put(o, (uint64_t)cn[c]); o += '\t';
+                if (crho[c] != crho[c]) o += "NA\tNA";
+                else { put(o, crho[c]); o += '\t'; put(o, cse[c]); }
+                o += '\n';
+            });
+            fclose(fc);
+            lap("cellector_ambient.tsv");
+            if (params.estimate_ambient == 2) {
+                dp.ambient = as.rho;
+                donor_pass();
+            }
+        }
         FILE *f = create(od + "/cellector_donors.tsv");
         std::string head = "barcode\tstatus\tdonor\tsecond_donor\tbest_pair\tposterior\tpair_posterior\tdoublet_posterior\tn_loci";
         for (uint32_t d = 0; d < D; d++) head += "\tlog_likelihood_" + dg.names[d];

@@ -920,6 +920,93 @@ cellector_status cellector_match_donors(cellector_ctx *ctx, const uint8_t *label
                                         double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
                                         uint64_t *cells /*[K]*/); /* any output may be NULL */
 
+/* ---- ambient fraction estimation: a profile likelihood over a grid of rho ------------------------------------------
+ * The donor calls above and cellector_class_genotypes take the ambient fraction (the share of a barcode's reads that come from the
+ * pool and not from its own cell) as a number the caller supplies.  These calls measure it: every cell is scored under the
+ * genotypes of the source it is assigned to at G values of rho at once, the sums are added over the cells, and the maximum of
+ * that profile is the estimate.  The log-likelihood is a sum of logs of functions affine in rho: it is concave, a grid that zooms
+ * in finds its one maximum, and a parabola through the last three points gives the estimate and its standard error.  The model
+ * below is the specification (cellector_amd/ambient.py repeats it in numpy); no parity with any other demultiplexer is claimed.
+ *   S sources, 1 <= S <= 64.  gt [S][total_loci] u8 is coded and packed exactly as for cellector_donor_posteriors (0 = 0/0, 1 = 0/1,
+ *   2 = 1/1, 3 = no call; step 1 there).  A source is a donor, or a class whose genotypes came from cellector_class_genotypes.
+ *   assign [cells] u8: the source a cell is scored under; 255 = the cell takes no part (how the caller passes doublets and
+ *   unassigned cells); any other value >= S is CELLECTOR_EINVAL.  rho [G], 4 <= G <= 32, every value finite and in [0, 1).  mask [L]
+ *   or NULL = all loci.  The entries of a cell are those of its by-cell CSR row at used, unmasked loci, in row order.  All arithmetic
+ *   is f64 without contraction: every product, quotient and sum below rounds once.
+ *   1 tables: per used, unmasked locus soup and e_g are those of step 2 of the donor model: soup = ((double)A + 1.0) /
+ *     ((double)(A + R) + 2.0), e = {err, 0.5, 1.0 - err, soup}.  theta_{g,j} = ((1.0 - rho_j) e_g) + (rho_j soup);
+ *     tab [L][4][G][2] = (log theta, log(1.0 - theta)) with the device's log.  A masked locus' rows are (0, 0) and no sum visits it.
+ *     Where rho_j == ambient, tab[l][g][j] carries the bits of cellector_donor_tables' tab1[l][g].
+ *   2 cell sums: ll_cj = the sum over the cell's entries in row order of ((alt la) + (ref lb)), (la, lb) = tab[l][g_{assign[c]}(l)][j]:
+ *     both products rounded, then their sum, then that added to the accumulator, strictly sequential per (cell, j) from 0.0 (step 4
+ *     of the donor model).  n_entries[c] = the number of those entries.  A cell with assign 255 has a row of 0.0 and n_entries 0.
+ *     ll[c][j] is bit for bit the ll[c][assign[c]] of cellector_donor_posteriors(..., ambient = rho_j).
+ *   3 totals: total[j] = the sum of ll_cj over the cells with assign != 255, folded as the objective of the cluster model: thread t
+ *     of 256 adds its cells t, t + 256, ... in ascending order from 0.0, skipping the cells that take no part; the 256 partial sums
+ *     are then folded pairwise, p_t = p_t + p_{t+h} for t < h, h = 128, 64 ... 1.  source_total[s][j]: the same fold over the cells
+ *     of source s; source_cells[s]: their number.
+ *   4 the vertex rule, per cell on the device: j* = the smallest j that maximises ll_cj; jj = min(max(j*, 1), G - 2);
+ *     x0, x1, x2 = rho[jj - 1], rho[jj], rho[jj + 1]; y0, y1, y2 = ll_c at those.  The parabola through three points that need not
+ *     be equally spaced, in this order of operations:
+ *       h0 = x1 - x0; h1 = x2 - x1; d0 = (y1 - y0) / h0; d1 = (y2 - y1) / h1; c = (2.0 (d1 - d0)) / (h0 + h1)    (the curvature)
+ *       unresolved: where |y1 - y0| <= 2^-40 |y1| and |y2 - y1| <= 2^-40 |y1|, c = 0.0 instead
+ *       c < 0:  v = (0.5 (x0 + x1)) - (d0 / c); cell_rho = min(max(v, x0), x2); cell_se = 1.0 / sqrt(-c)
+ *       else (a flat or degenerate cell, e.g. one whose every entry lies at a no-call locus; a NaN from a grid that repeats a
+ *       value lands here too): cell_rho = rho[j*], cell_se = +inf.
+ *     Why "unresolved": at a no-call locus theta is ((1.0 - rho) soup) + (rho soup), which is soup only up to a rounding that
+ *     differs with rho, so a profile that is flat in exact arithmetic arrives as noise of a few ulps and of either sign, and a
+ *     parabola through noise has whatever curvature the noise gives it.  The sums themselves carry (n + 1) u of rounding per row and
+ *     (cells / 256 + 8) u per fold, near 2^-41 of the value at 10^6 cells: two steps that both stay below 2^-40 of the value cannot
+ *     be told from rounding, and the rule says so (se = +inf) rather than report a standard error made of it.  A profile with signal
+ *     moves by c h^2 / 2 per step, many orders above that on every grid this library builds from data that bear on rho.
+ *     A cell with n_entries < min_loci or assign 255 gets NaN for both.
+ *   5 cellector_estimate_ambient: parameters {err 0.01, lo 0.0, hi 0.5, grid 16, rounds 3, min_loci 1}
+ *     (cellector_ambient_default_params).  lo_0, hi_0 = lo, hi.  Round r builds rho_j = lo_r + ((double)j ((hi_r - lo_r) /
+ *     (double)(G - 1))), runs steps 1 to 3, takes j* = the smallest argmax of total, and sets lo_{r+1} = rho[max(j* - 1, 0)],
+ *     hi_{r+1} = rho[min(j* + 1, G - 1)].  After the last round the pooled rho, se and curvature are the vertex rule of step 4
+ *     applied on the host to total, rho then clamped into [lo, hi] of the parameters; at_boundary = 1 when it lies at lo or hi of
+ *     the parameters.  The same rule gives source_rho[s], source_se[s] from source_total[s]; a source without a cell, and every s
+ *     >= S, gets NaN.  log_likelihood = total at the last round's j*; lo, hi, j_star are the last round's; n_cells_used = the cells
+ *     with assign != 255.  The per-cell outputs are those of ROUND 0, the wide grid: a cell's maximum lies anywhere in it, and its se
+ *     is tens of grid steps of the last round.  The host reads G + S G doubles per round and nothing per cell but the outputs asked for.
+ * Scope as cellector_donor_posteriors: a loaded matrix, no iteration in flight, engines 1 and 2, a single-device ctx that holds all
+ * cells.  CELLECTOR_EINVAL with a message, nothing written or launched, for these and for S outside 1..64, NULL gt / assign / rho, a
+ * gt value above 3, an assign that is neither 255 nor below S, G outside 4..32, a rho value that is NaN or outside [0, 1), err
+ * outside (0, 0.5), lo / hi not satisfying 0 <= lo < hi < 1, rounds outside 1..8, min_loci == 0.  All device scratch is allocated
+ * before anything is launched: S bytes per locus of the matrix, 64 G + 8 W + 1 B per used locus (W = ceil(S / 32)), 8 G + 21 B
+ * per cell and 8 (S + 2) G + 8 (S + 1) B beside them (cellector_ambient_tables: 64 G + 1 B per used locus and 8 G B): on
+ * CELLECTOR_ENOMEM the ctx is as it was.  The calls never touch the EM state (an interrupted EM loop continues with the same bits)
+ * and overwrite nothing of the ctx; they invalidate the caches cellector_cell_log_likelihoods invalidates, as the donor calls do. */
+typedef struct {
+    double err;         /* 0.01: the allele fraction of a homozygous-reference source               */
+    double lo, hi;      /* 0.0, 0.5: the first round's grid spans [lo, hi]; the estimate stays in it */
+    uint32_t grid;      /* 16:   G, the grid points of a round (4..32)                                */
+    uint32_t rounds;    /* 3:    each round's grid spans the two steps around the last one's maximum   */
+    uint64_t min_loci;  /* 1:    a cell with fewer entries at used, unmasked loci gets no cell_rho     */
+} cellector_ambient_params;
+typedef struct {
+    double rho, se, curvature, log_likelihood; /* the pooled estimate, 1 / sqrt(-curvature), total at j_star  */
+    double lo, hi;                             /* the last round's grid                                        */
+    uint32_t j_star, at_boundary, rounds, reserved;
+    uint64_t n_cells_used;                     /* cells with assign != 255                                     */
+    double source_rho[64], source_se[64];      /* NaN for a source without a cell and for s >= S               */
+    uint64_t source_cells[64];
+} cellector_ambient_summary;
+cellector_status cellector_ambient_default_params(cellector_ambient_params *out);
+cellector_status cellector_ambient_tables(cellector_ctx *ctx, const double *rho /*[G]*/, uint32_t n_grid, double err,
+                                          const uint8_t *mask /*[L] or NULL*/, double *tab /*[L][4][G][2]*/);
+cellector_status cellector_ambient_profile(cellector_ctx *ctx, const uint8_t *gt /*[S][total_loci]*/, uint32_t n_sources,
+                                           const uint8_t *assign /*[cells]*/, const double *rho /*[G]*/, uint32_t n_grid, double err,
+                                           uint64_t min_loci, const uint8_t *mask /*[L] or NULL*/, double *ll /*[cells][G]*/,
+                                           double *total /*[G]*/, double *source_total /*[S][G]*/, uint64_t *source_cells /*[S]*/,
+                                           uint32_t *n_entries /*[cells]*/, double *cell_rho /*[cells]*/, double *cell_se /*[cells]*/,
+                                           double *tab /*[L][4][G][2]*/); /* any output may be NULL */
+cellector_status cellector_estimate_ambient(cellector_ctx *ctx, const uint8_t *gt /*[S][total_loci]*/, uint32_t n_sources,
+                                            const uint8_t *assign /*[cells]*/, const cellector_ambient_params *params /*NULL = defaults*/,
+                                            const uint8_t *mask /*[L] or NULL*/, cellector_ambient_summary *summary,
+                                            double *cell_rho /*[cells]*/, double *cell_se /*[cells]*/,
+                                            uint32_t *n_entries /*[cells]*/); /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
