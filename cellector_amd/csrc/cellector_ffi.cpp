@@ -1640,10 +1640,12 @@ cellector_status cellector_donor_default_params(cellector_donor_params *out)
 }
 
 // what every donor call checks before anything is written or launched (the scope first: class_call_check's own for the match)
-static cellector_status donor_args_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t D, const cellector_donor_params *p)
+// (calls: gt, or the gp of a soft call; null_name: what the message calls it)
+static cellector_status donor_params_check(cellector_ctx *c, const char *what, const void *calls, const char *null_name, uint32_t D,
+                                           const cellector_donor_params *p)
 {
     if (D < 1 || D > 64) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u donors, 1..64 are supported", what, D);
-    if (!gt) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null gt", what);
+    if (!calls) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null %s", what, null_name);
     if (!(p->err > 0.0 && p->err < 0.5)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: err = %g is not within (0, 0.5)", what, p->err);
     if (!(p->ambient >= 0.0 && p->ambient < 1.0)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: ambient = %g is not within [0, 1)", what, p->ambient);
     if (!(p->doublet_rate >= 0.0 && p->doublet_rate < 1.0))
@@ -1651,6 +1653,11 @@ static cellector_status donor_args_check(cellector_ctx *c, const char *what, con
     if (!(p->posterior_threshold >= 0.0 && p->posterior_threshold <= 1.0))
         return ctx_fail(c, CELLECTOR_EINVAL, "%s: posterior_threshold = %g is not within [0, 1]", what, p->posterior_threshold);
     if (p->min_loci < 1) return ctx_fail(c, CELLECTOR_EINVAL, "%s: min_loci must be at least 1", what);
+    return CELLECTOR_OK;
+}
+static cellector_status donor_args_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t D, const cellector_donor_params *p)
+{
+    CHK(donor_params_check(c, what, gt, "gt", D, p));
     const uint64_t TL = c->total_loci;
     for (uint32_t d = 0; d < D; d++)
         for (uint64_t t = 0; t < TL; t++)
@@ -1666,6 +1673,30 @@ static cellector_status donor_call_check(cellector_ctx *c, const char *what, con
     if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
     return donor_args_check(c, what, gt, D, p);
 }
+// the soft calls: every row of gp is three NaN (no call) or three finite weights >= 0 that are not all zero
+static cellector_status donor_gp_check(cellector_ctx *c, const char *what, const float *gp, uint32_t D, const cellector_donor_params *p)
+{
+    CHK(donor_params_check(c, what, gp, "gp", D, p));
+    const uint64_t TL = c->total_loci;
+    for (uint32_t d = 0; d < D; d++)
+        for (uint64_t t = 0; t < TL; t++) {
+            const float *r = gp + ((uint64_t)d * TL + t) * 3;
+            if (std::isnan(r[0]) && std::isnan(r[1]) && std::isnan(r[2])) continue;
+            bool fine = r[0] > 0.f || r[1] > 0.f || r[2] > 0.f;
+            for (int g = 0; g < 3; g++) fine = fine && r[g] >= 0.f && std::isfinite(r[g]);
+            if (!fine)
+                return ctx_fail(c, CELLECTOR_EINVAL, "%s: gp of donor %u at locus %llu is (%g, %g, %g): three NaN (no call), or three finite weights >= 0 that are not all zero",
+                                what, d, (unsigned long long)t, (double)r[0], (double)r[1], (double)r[2]);
+        }
+    return CELLECTOR_OK;
+}
+static cellector_status donor_gp_call_check(cellector_ctx *c, const char *what, const float *gp, uint32_t D, const cellector_donor_params *p)
+{
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    return donor_gp_check(c, what, gp, D, p);
+}
 
 cellector_status cellector_donor_tables(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *p,
                                         const uint8_t *mask, double *tab1, double *tab2, uint64_t *packed)
@@ -1679,36 +1710,49 @@ cellector_status cellector_donor_tables(cellector_ctx *c, const uint8_t *gt, uin
     return donor_tables_run(c, gt, n_donors, &prm, mask, tab1, tab2, packed);
 }
 
+// cellector_donor_posteriors (gp null) and cellector_donor_posteriors_gp (gt null): the same checks, the same run
+static cellector_status donor_posteriors_call(cellector_ctx *c, const char *what, const uint8_t *gt, const float *gp, uint32_t n_donors,
+                                              const cellector_donor_params *p, const double *log_prior, const uint8_t *anchor,
+                                              const uint8_t *mask, double *ll, double *pair_ll, double *posterior, double *pair_posterior,
+                                              double *doublet_posterior, uint8_t *best, uint8_t *second, uint8_t *best_pair,
+                                              uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out, cellector_donor_summary *out,
+                                              double *tab1, double *tab2, bool soft)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    if (soft) CHK(donor_gp_call_check(c, what, gp, n_donors, &prm));
+    else CHK(donor_call_check(c, what, gt, n_donors, &prm));
+    const uint32_t D = n_donors;
+    double lp[64] = {};
+    bool any = !log_prior;
+    for (uint32_t d = 0; log_prior && d < D; d++) {
+        if (std::isnan(log_prior[d]) || log_prior[d] == INFINITY)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior[%u] = %g is neither a finite value nor -inf", what, d, log_prior[d]);
+        any = any || log_prior[d] != -INFINITY;
+        lp[d] = log_prior[d];
+    }
+    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior is -inf for every donor", what);
+    for (uint64_t i = 0; anchor && i < c->nloc; i++)
+        if (anchor[i] >= D)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: anchor of cell %llu is %u, not below the %u donors", what, (unsigned long long)i,
+                            (unsigned)anchor[i], D);
+    const double log_singlet = std::log(1.0 - prm.doublet_rate);
+    const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
+    SETDEV(c);
+    return donor_posteriors_run(c, gt, gp, D, &prm, lp, anchor, mask, log_singlet, log_pair, ll, pair_ll, posterior, pair_posterior,
+                                doublet_posterior, best, second, best_pair, n_entries, status, anchor_out, out, tab1, tab2, nullptr);
+}
+
 cellector_status cellector_donor_posteriors(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *p,
                                             const double *log_prior, const uint8_t *anchor, const uint8_t *mask, double *ll, double *pair_ll,
                                             double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
                                             uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
                                             cellector_donor_summary *out, double *tab1, double *tab2)
 {
-    if (!c) return CELLECTOR_EINVAL;
-    cellector_donor_params prm;
-    cellector_donor_default_params(&prm);
-    if (p) prm = *p;
-    CHK(donor_call_check(c, "donor_posteriors", gt, n_donors, &prm));
-    const uint32_t D = n_donors;
-    double lp[64] = {};
-    bool any = !log_prior;
-    for (uint32_t d = 0; log_prior && d < D; d++) {
-        if (std::isnan(log_prior[d]) || log_prior[d] == INFINITY)
-            return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: log_prior[%u] = %g is neither a finite value nor -inf", d, log_prior[d]);
-        any = any || log_prior[d] != -INFINITY;
-        lp[d] = log_prior[d];
-    }
-    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: log_prior is -inf for every donor");
-    for (uint64_t i = 0; anchor && i < c->nloc; i++)
-        if (anchor[i] >= D)
-            return ctx_fail(c, CELLECTOR_EINVAL, "donor_posteriors: anchor of cell %llu is %u, not below the %u donors", (unsigned long long)i,
-                            (unsigned)anchor[i], D);
-    const double log_singlet = std::log(1.0 - prm.doublet_rate);
-    const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
-    SETDEV(c);
-    return donor_posteriors_run(c, gt, D, &prm, lp, anchor, mask, log_singlet, log_pair, ll, pair_ll, posterior, pair_posterior,
-                                doublet_posterior, best, second, best_pair, n_entries, status, anchor_out, out, tab1, tab2, nullptr);
+    return donor_posteriors_call(c, "donor_posteriors", gt, nullptr, n_donors, p, log_prior, anchor, mask, ll, pair_ll, posterior, pair_posterior,
+                                 doublet_posterior, best, second, best_pair, n_entries, status, anchor_out, out, tab1, tab2, false);
 }
 
 cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const uint8_t *gt, uint32_t n_donors,
@@ -1722,7 +1766,42 @@ cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels,
     CHK(class_call_check(c, "match_donors", labels, n_classes, nullptr, nullptr));
     CHK(donor_args_check(c, "match_donors", gt, n_donors, &prm));
     SETDEV(c);
-    return donor_match_run(c, labels, n_classes, gt, n_donors, &prm, mask, ll, best, margin, cells);
+    return donor_match_run(c, labels, n_classes, gt, nullptr, n_donors, &prm, mask, ll, best, margin, cells);
+}
+
+// ---- the donor calls from genotype probabilities: the soft kernels of kernels_donors.hip ------------------------------------------
+cellector_status cellector_donor_posteriors_gp(cellector_ctx *c, const float *gp, uint32_t n_donors, const cellector_donor_params *p,
+                                               const double *log_prior, const uint8_t *anchor, const uint8_t *mask, double *ll, double *pair_ll,
+                                               double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
+                                               uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
+                                               cellector_donor_summary *out, double *tab1, double *tab2)
+{
+    return donor_posteriors_call(c, "donor_posteriors_gp", nullptr, gp, n_donors, p, log_prior, anchor, mask, ll, pair_ll, posterior,
+                                 pair_posterior, doublet_posterior, best, second, best_pair, n_entries, status, anchor_out, out, tab1, tab2, true);
+}
+
+cellector_status cellector_donor_weights(cellector_ctx *c, const float *gp, uint32_t n_donors, double *w, uint8_t *kind)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    CHK(donor_gp_call_check(c, "donor_weights", gp, n_donors, &prm));
+    SETDEV(c);
+    return donor_weights_run(c, gp, n_donors, w, kind);
+}
+
+cellector_status cellector_match_donors_gp(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const float *gp, uint32_t n_donors,
+                                           const cellector_donor_params *p, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
+                                           uint64_t *cells)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    CHK(class_call_check(c, "match_donors_gp", labels, n_classes, nullptr, nullptr));
+    CHK(donor_gp_check(c, "match_donors_gp", gp, n_donors, &prm));
+    SETDEV(c);
+    return donor_match_run(c, labels, n_classes, nullptr, gp, n_donors, &prm, mask, ll, best, margin, cells);
 }
 
 // ---- ambient fraction estimation: kernels_ambient.hip --------------------------------------------------------------

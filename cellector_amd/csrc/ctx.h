@@ -572,14 +572,15 @@ cellector_status cluster_run(cellector_ctx *c, uint32_t K, uint32_t R, uint64_t 
 // null), the class tallies against the donors
 cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const uint8_t *mask,
                                   double *tab1, double *tab2, uint64_t *packed);
-cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
+cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, const float *gp /*or null: then gt*/, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
                                       const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair, double *ll,
                                       double *pair_ll, double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
                                       uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
                                       cellector_donor_summary *out, double *tab1, double *tab2, uint64_t *packed);
-cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
+cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, const float *gp /*or null*/, uint32_t D,
                                  const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
                                  uint64_t *cells);
+cellector_status donor_weights_run(cellector_ctx *c, const float *gp /*[D][total_loci][3]*/, uint32_t D, double *w, uint8_t *kind);
 cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *d_gt /*[D][total_loci]*/, uint64_t *d_packed /*[L][W]*/);
 // ambient fraction estimation (kernels_ambient.hip) on one device holding all cells; validated arguments, host arrays, scratch of their
 // own, nothing of the ctx written: the tables of a grid alone, one profile over a grid, the zooming grid search

@@ -2,8 +2,12 @@
 // its own (the caller feeds it lines).  The rule is cellector_amd/donors.py's read_donor_vcf: a donor record is matched to the variant
 // VCF's record with the same (chrom, pos, ref, alt); one whose ref and alt are swapped is matched too and its calls are mirrored; a
 // variant without a donor record, and a missing, unparsable or non-biallelic GT, is 3 (no call); of repeated records the last counts.
+// With a field (GP, GL or PL; --donor_field) the three weights of every sample are read beside its GT, by read_donor_vcf_gp's rule.
 #pragma once
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <limits>
 #include <map>
 #include <string>
 #include <string_view>
@@ -34,10 +38,63 @@ inline uint8_t donor_parse_gt(std::string_view field, int gt_index)
     return (uint8_t)((g[0] - '0') + (g[2] - '0'));
 }
 
+// a plain decimal number, [+-]digits[.digits][e[+-]digits] or [+-].digits[e...], and nothing else (no nan, no inf, no hex)
+inline bool donor_parse_number(std::string_view s, double *out)
+{
+    size_t i = 0, digits = 0;
+    const auto run = [&]() { size_t n = 0; while (i < s.size() && s[i] >= '0' && s[i] <= '9') { i++; n++; } return n; };
+    if (i < s.size() && (s[i] == '+' || s[i] == '-')) i++;
+    digits = run();
+    if (i < s.size() && s[i] == '.') { i++; const size_t frac = run(); if (!digits && !frac) return false; digits += frac; }
+    if (!digits) return false;
+    if (i < s.size() && (s[i] == 'e' || s[i] == 'E')) {
+        i++;
+        if (i < s.size() && (s[i] == '+' || s[i] == '-')) i++;
+        if (!run()) return false;
+    }
+    if (i != s.size()) return false;
+    *out = strtod(std::string(s).c_str(), nullptr);
+    return true;
+}
+
+// The three weights of a sample field's GP ('P'), GL ('L') or PL ('Q') at position index, in double; false: the field absent, ".",
+// not three plain numbers, a GP or PL below 0, a value that is not finite, or three zeros.  GP: as written.  GL: 10^(GL_g - max GL).
+// PL: 10^(-(PL_g - min PL) / 10).
+inline bool donor_parse_weights(std::string_view field, int index, char kind, double out[3])
+{
+    const std::vector<std::string_view> parts = donor_split(field, ':');
+    if (index < 0 || (size_t)index >= parts.size()) return false;
+    const std::vector<std::string_view> toks = donor_split(parts[(size_t)index], ',');
+    if (toks.size() != 3) return false;
+    double v[3];
+    for (int g = 0; g < 3; g++)
+        if (!donor_parse_number(toks[(size_t)g], &v[g]) || !std::isfinite(v[g]) || (kind != 'L' && v[g] < 0)) return false;
+    const double hi = std::fmax(v[0], std::fmax(v[1], v[2])), lo = std::fmin(v[0], std::fmin(v[1], v[2]));
+    for (int g = 0; g < 3; g++) v[g] = kind == 'L' ? std::pow(10.0, v[g] - hi) : kind == 'Q' ? std::pow(10.0, -(v[g] - lo) / 10.0) : v[g];
+    if (!(v[0] > 0 || v[1] > 0 || v[2] > 0)) return false;
+    for (int g = 0; g < 3; g++) out[g] = v[g];  // (out is written only when the weights count)
+    return true;
+}
+
+// gt [rows] from gp [rows][3]: the argmax of every row, the smallest g on ties, 3 for a no-call (three NaN)
+inline std::vector<uint8_t> donor_hard_codes(const std::vector<float> &gp)
+{
+    std::vector<uint8_t> out(gp.size() / 3, DONOR_NO_CALL);
+    for (size_t i = 0; i < out.size(); i++) {
+        const float *r = gp.data() + 3 * i;
+        if (std::isnan(r[0]) && std::isnan(r[1]) && std::isnan(r[2])) continue;
+        out[i] = r[0] >= r[1] && r[0] >= r[2] ? 0 : r[1] >= r[2] ? 1 : 2;
+    }
+    return out;
+}
+
 struct DonorGenotypes {
     std::vector<std::string> names;  // [D] the sample columns of the donor VCF's #CHROM line
     std::vector<uint8_t> gt;         // [D][total_loci], made (all 3) at that line, filled by the records behind it
     uint64_t total_loci = 0;
+    std::string field;               // "" (GT alone), or "GP", "GL", "PL": set before the donor lines; then gp is filled too
+    std::vector<float> gp;           // [D][total_loci][3], made (all NaN) at the #CHROM line: a sample's weights, else the one-hot of
+                                     // its GT, else three NaN; a record with ref and alt swapped has its three values reversed
 
     // every line of the variant VCF, in file order (header lines are skipped)
     void add_variant_line(std::string_view line)
@@ -57,6 +114,7 @@ struct DonorGenotypes {
                 names.clear();
                 for (size_t i = 9; i < t.size(); i++) names.emplace_back(t[i]);
                 gt.assign(names.size() * total_loci, DONOR_NO_CALL);
+                if (!field.empty()) gp.assign(names.size() * total_loci * 3, std::numeric_limits<float>::quiet_NaN());
             }
             return;
         }
@@ -70,9 +128,20 @@ struct DonorGenotypes {
         int gi = -1;
         for (size_t i = 0; i < fmt.size(); i++)
             if (fmt[i] == "GT") { gi = (int)i; break; }
+        int fi = -1;
+        for (size_t i = 0; i < fmt.size() && !field.empty(); i++)
+            if (fmt[i] == field) { fi = (int)i; break; }
+        const char kind = field == "GL" ? 'L' : field == "PL" ? 'Q' : 'P';
         for (size_t d = 0; d < names.size(); d++) {
             const uint8_t g = 9 + d < t.size() ? donor_parse_gt(t[9 + d], gi) : DONOR_NO_CALL;
             gt[d * total_loci + at->second] = g == DONOR_NO_CALL || !swap ? g : (uint8_t)(2 - g);
+            if (field.empty()) continue;
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            double v[3] = {nan, nan, nan};
+            if (!(9 + d < t.size() && donor_parse_weights(t[9 + d], fi, kind, v)) && g != DONOR_NO_CALL)
+                for (int k = 0; k < 3; k++) v[k] = k == (int)g ? 1.0 : 0.0;
+            float *row = gp.data() + (d * total_loci + at->second) * 3;
+            for (int k = 0; k < 3; k++) row[k] = (float)v[swap ? 2 - k : k];
         }
     }
 

@@ -11,7 +11,8 @@
 //                   owns one (cell, donor) sum and walks the row's entries in order).  <DP, false>: the singlet sums, best, second and
 //                   the anchor; <DP, true>: the pair sums (anchor, d) and the posterior chain over the 2 D - 1 hypotheses
 //   k_donor_match   a lane per (class, donor): the class' tallies over ascending loci
-// All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
+// The same calls from genotype probabilities (three weights per donor and locus in place of a code) are the section behind
+// k_donor_match.  All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
 #include "ctx.h"
 
 #include <cmath>
@@ -92,10 +93,73 @@ __device__ __forceinline__ void dn_argmax(double &v, int &idx)
     }
 }
 
-// The cell pass.  A group of DP lanes per cell, lane = donor d.  acc = the ordered sum of (alt la + ref lb) over the row's entries at
-// unmasked loci, (la, lb) = the table row of the donor's genotype (PAIR: of the anchor's and the donor's).
+// The tail of a cell pass, shared by the hard and the soft kernels: acc = the lane's ordered sum, cnt = the row's entries.  Every lane of
+// the wave takes part in the shuffles, whatever its row and donor.
 // !PAIR: s = acc; u_d = s_d + lp_d; best = argmax u, second = argmax over d != best (smallest d on ties); the anchor, unless given
 //  PAIR: p = acc; x_d = (s_d + lp_d) + log_singlet, y_d = p_d + log_pair (d != anchor), one softmax over the 2 D - 1 terms
+template <int DP, bool PAIR>
+__device__ __forceinline__ void dn_tail(uint64_t row, bool have, int col, bool col_ok, int base, uint32_t D, uint32_t a, double acc, uint32_t cnt,
+                                        const double *__restrict__ lp, const DonorTail &tail, bool anchor_given, uint8_t *__restrict__ anchor,
+                                        double *__restrict__ s, uint8_t *__restrict__ best, uint8_t *__restrict__ second,
+                                        uint32_t *__restrict__ cnt_out, double *__restrict__ p_out, double *__restrict__ post,
+                                        double *__restrict__ ppost, double *__restrict__ dp_out, uint8_t *__restrict__ best_pair,
+                                        uint8_t *__restrict__ status)
+{
+    const double prior = col_ok ? lp[col] : 0.0;
+    if (!PAIR) {
+        double v = col_ok ? acc + prior : -INFINITY;
+        int b = col_ok ? col : 0x7fff;
+        const double u = v;
+        dn_argmax<DP>(v, b);
+        double v2 = col_ok && col != b ? u : -INFINITY;
+        int b2 = col_ok && col != b ? col : 0x7fff;
+        dn_argmax<DP>(v2, b2);
+        if (have && col_ok) s[row * D + col] = acc;
+        if (have && col == 0) {
+            best[row] = (uint8_t)b;
+            second[row] = D > 1 ? (uint8_t)b2 : (uint8_t)DN_NONE;
+            if (!anchor_given) anchor[row] = (uint8_t)b;
+            cnt_out[row] = cnt;
+        }
+    } else {
+        const bool pair_ok = col_ok && (uint32_t)col != a;
+        double x = -INFINITY, y = -INFINITY;
+        if (have && col_ok) {
+            const double u = s[row * D + col] + prior;
+            x = u + tail.log_singlet;
+        }
+        if (pair_ok) y = acc + tail.log_pair;
+        double m = fmax(x, y);
+        int dummy = 0;
+        dn_argmax<DP>(m, dummy);
+        if (!have) m = 0.0;
+        const double ex = exp(x - m), ey = exp(y - m);  // a lane that is no hypothesis: exp(-inf) = 0, and den + 0 is den
+        double den = 0.0;
+        for (uint32_t d = 0; d < D; d++) den = den + __shfl(ex, (base + (int)d) & 63, 64);
+        for (uint32_t d = 0; d < D; d++) den = den + __shfl(ey, (base + (int)d) & 63, 64);
+        const double w = ex / den, wp = ey / den;
+        double dp = 0.0;
+        for (uint32_t d = 0; d < D; d++) dp = dp + __shfl(wp, (base + (int)d) & 63, 64);
+        double vy = y;
+        int bp = pair_ok ? col : 0x7fff;
+        dn_argmax<DP>(vy, bp);
+        const int b = have ? (int)best[row] : 0;
+        const double wb = __shfl(w, (base + b) & 63, 64);
+        if (have && col_ok) {
+            p_out[row * D + col] = acc;
+            post[row * D + col] = w;
+            ppost[row * D + col] = wp;
+        }
+        if (have && col == 0) {
+            dp_out[row] = dp;
+            best_pair[row] = D > 1 ? (uint8_t)bp : (uint8_t)DN_NONE;
+            status[row] = (uint64_t)cnt < tail.min_loci ?(uint8_t)DN_NONE : dp > 0.5 ? (uint8_t)1 : wb >= tail.threshold ? (uint8_t)0 : (uint8_t)2;
+        }
+    }
+}
+
+// The cell pass.  A group of DP lanes per cell, lane = donor d.  acc = the ordered sum of (alt la + ref lb) over the row's entries at
+// unmasked loci, (la, lb) = the table row of the donor's genotype (PAIR: of the anchor's and the donor's); then dn_tail.
 template <int DP, bool PAIR>
 __global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_t D, uint32_t W, const uint64_t *__restrict__ row_ptr,
                                                         const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
@@ -155,58 +219,8 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_
                 cnt++;
             }
         }
-        // the tail: every lane of the wave takes part in the shuffles, whatever its row and donor
-        const double prior = col_ok ? lp[col] : 0.0;
-        if (!PAIR) {
-            double v = col_ok ? acc + prior : -INFINITY;
-            int b = col_ok ? col : 0x7fff;
-            const double u = v;
-            dn_argmax<DP>(v, b);
-            double v2 = col_ok && col != b ? u : -INFINITY;
-            int b2 = col_ok && col != b ? col : 0x7fff;
-            dn_argmax<DP>(v2, b2);
-            if (have && col_ok) s[row * D + col] = acc;
-            if (have && col == 0) {
-                best[row] = (uint8_t)b;
-                second[row] = D > 1 ? (uint8_t)b2 : (uint8_t)DN_NONE;
-                if (!anchor_given) anchor[row] = (uint8_t)b;
-                cnt_out[row] = cnt;
-            }
-        } else {
-            const bool pair_ok = col_ok && (uint32_t)col != a;
-            double x = -INFINITY, y = -INFINITY;
-            if (have && col_ok) {
-                const double u = s[row * D + col] + prior;
-                x = u + tail.log_singlet;
-            }
-            if (pair_ok) y = acc + tail.log_pair;
-            double m = fmax(x, y);
-            int dummy = 0;
-            dn_argmax<DP>(m, dummy);
-            if (!have) m = 0.0;
-            const double ex = exp(x - m), ey = exp(y - m);  // a lane that is no hypothesis: exp(-inf) = 0, and den + 0 is den
-            double den = 0.0;
-            for (uint32_t d = 0; d < D; d++) den = den + __shfl(ex, (base + (int)d) & 63, 64);
-            for (uint32_t d = 0; d < D; d++) den = den + __shfl(ey, (base + (int)d) & 63, 64);
-            const double w = ex / den, wp = ey / den;
-            double dp = 0.0;
-            for (uint32_t d = 0; d < D; d++) dp = dp + __shfl(wp, (base + (int)d) & 63, 64);
-            double vy = y;
-            int bp = pair_ok ? col : 0x7fff;
-            dn_argmax<DP>(vy, bp);
-            const int b = have ? (int)best[row] : 0;
-            const double wb = __shfl(w, (base + b) & 63, 64);
-            if (have && col_ok) {
-                p_out[row * D + col] = acc;
-                post[row * D + col] = w;
-                ppost[row * D + col] = wp;
-            }
-            if (have && col == 0) {
-                dp_out[row] = dp;
-                best_pair[row] = D > 1 ? (uint8_t)bp : (uint8_t)DN_NONE;
-                status[row] = (uint64_t)cnt < tail.min_loci ?(uint8_t)DN_NONE : dp > 0.5 ? (uint8_t)1 : wb >= tail.threshold ? (uint8_t)0 : (uint8_t)2;
-            }
-        }
+        dn_tail<DP, PAIR>(row, have, col, col_ok, base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out, p_out, post,
+                          ppost, dp_out, best_pair, status);
     }
 }
 
@@ -249,6 +263,234 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
     ll[(uint64_t)k * D + d] = acc;
 }
 
+// ---- genotype probabilities (cellector_donor_posteriors_gp, cellector_donor_weights, cellector_match_donors_gp) ------------------
+// A donor's genotype at a locus is three weights, not one code.  include/cellector_ffi.h states the model; donors.py (soft_*) is
+// its twin.
+//   k_donor_weights  gp [D][total_loci][3] f32 -> w [L][D][3] f64 and kind [L][D] u8 over the used loci: kind 0, 1, 2 = the one-hot row
+//                    of that genotype, 3 = no call, 4 = a soft row
+//   k_donor_gp_e     the shape of k_donor_e.  A lane's entry is a lookup (kind < 4: the hard call's bits) or the mixture over the
+//                    genotypes of positive weight, m + log(sum w exp(t - m)).  The terms of DN_AHEAD entries are formed first, the
+//                    lookups of all four in flight together, then exp / log and all where a row is soft: they depend on nothing of
+//                    the sum.  Then they are added in order.
+//   k_donor_gp_match a lane per (class, donor), the same term from the class' tallies
+#define DN_SOFT 4
+
+// thread (l, d).  The host has validated every row; a row it should have refused is counted in bad and held as a no-call.
+__global__ __launch_bounds__(DN_THREADS) void k_donor_weights(uint64_t n /*L D*/, uint32_t D, uint64_t TL, const uint64_t *__restrict__ locus_ids,
+                                                              const float *__restrict__ gp, double *__restrict__ w, uint8_t *__restrict__ kind,
+                                                              uint32_t *__restrict__ bad)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = i / D, t = locus_ids[l];
+    const uint32_t d = (uint32_t)(i % D);
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+    uint8_t k = 3;
+    if (t < TL) {
+        const float *row = gp + ((uint64_t)d * TL + t) * 3;
+        const float f0 = row[0], f1 = row[1], f2 = row[2];
+        const bool none = f0 != f0 && f1 != f1 && f2 != f2;
+        const bool fine = f0 >= 0.f && f1 >= 0.f && f2 >= 0.f && f0 < INFINITY && f1 < INFINITY && f2 < INFINITY && (f0 > 0.f || f1 > 0.f || f2 > 0.f);
+        if (fine) {
+            const double x0 = (double)f0, x1 = (double)f1, x2 = (double)f2;
+            const double s01 = x0 + x1;
+            const double sum = s01 + x2;
+            w0 = x0 / sum; w1 = x1 / sum; w2 = x2 / sum;
+            const int pos = (f0 > 0.f) + (f1 > 0.f) + (f2 > 0.f);
+            k = pos > 1 ? (uint8_t)DN_SOFT : f0 > 0.f ? (uint8_t)0 : f1 > 0.f ? (uint8_t)1 : (uint8_t)2;  // (one positive: x / x is 1.0)
+        } else if (!none) {
+            atomicAdd(bad, 1u);
+        }
+    }
+    w[i * 3] = w0; w[i * 3 + 1] = w1; w[i * 3 + 2] = w2;
+    kind[i] = k;
+}
+
+// the weights of a row over the four table rows: a one-hot row or a no-call is weight 1.0 on its own row
+__device__ __forceinline__ void dn_row_weights(uint32_t k, const double *__restrict__ w3, double (&out)[4])
+{
+#pragma unroll
+    for (uint32_t g = 0; g < 4; g++) out[g] = k < DN_SOFT ? (k == g ? 1.0 : 0.0) : g < 3 ? w3[g] : 0.0;
+}
+
+// the table row a lookup reads: of the donor's kind (PAIR: of the anchor's and the donor's); a soft row reads row 3 and its term is
+// replaced by dn_gp_soft's
+template <bool PAIR>
+__device__ __forceinline__ uint64_t dn_gp_row(uint64_t l, uint32_t ka, uint32_t kd)
+{
+    const uint32_t ga = ka < 3u ? ka : 3u, gd = kd < 3u ? kd : 3u;
+    return PAIR ? l * 16 + 4 * ga + gd : l * 4 + gd;
+}
+
+// one entry's mixture term for donor d of kind kd (PAIR: with anchor a of kind ka; one of the two is soft) at locus l under the counts
+// (al, re)
+template <bool PAIR>
+__device__ __forceinline__ double dn_gp_soft(uint64_t l, uint32_t D, uint32_t d, uint32_t a, uint32_t ka, uint32_t kd,
+                                             const double *__restrict__ w, const double2 *__restrict__ tab, double al, double re)
+{
+    if (!PAIR) {
+        const double *w3 = w + (l * D + d) * 3;
+        double wg[3], tg[3], m = -INFINITY;
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+            wg[g] = w3[g];
+            const double2 t = tab[l * 4 + g];
+            const double pa = al * t.x, pb = re * t.y;
+            tg[g] = pa + pb;
+            if (wg[g] > 0.0 && tg[g] > m) m = tg[g];
+        }
+        double z = 0.0;
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+            if (!(wg[g] > 0.0)) continue;
+            const double dg = tg[g] - m;
+            const double e = exp(dg);
+            const double we = wg[g] * e;
+            z = z + we;
+        }
+        const double lz = log(z);
+        return m + lz;
+    } else {
+        double wa[4], wd[4], tt[16], m = -INFINITY;
+        dn_row_weights(ka, w + (l * D + a) * 3, wa);
+        dn_row_weights(kd, w + (l * D + d) * 3, wd);
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+#pragma unroll
+            for (int h = 0; h < 4; h++) {
+                tt[4 * g + h] = 0.0;
+                if (!(wa[g] > 0.0 && wd[h] > 0.0)) continue;
+                const double2 t = tab[l * 16 + 4 * g + h];
+                const double pa = al * t.x, pb = re * t.y;
+                tt[4 * g + h] = pa + pb;
+                if (tt[4 * g + h] > m) m = tt[4 * g + h];
+            }
+        double z = 0.0;
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+#pragma unroll
+            for (int h = 0; h < 4; h++) {
+                if (!(wa[g] > 0.0 && wd[h] > 0.0)) continue;
+                const double ww = wa[g] * wd[h];
+                const double dg = tt[4 * g + h] - m;
+                const double e = exp(dg);
+                const double we = ww * e;
+                z = z + we;
+            }
+        const double lz = log(z);
+        return m + lz;
+    }
+}
+
+template <int DP, bool PAIR>
+__global__ __launch_bounds__(DN_THREADS) void k_donor_gp_e(uint64_t n_rows, uint32_t D, const uint64_t *__restrict__ row_ptr,
+                                                           const uint64_t *__restrict__ ent, const double *__restrict__ w /*[L][D][3]*/,
+                                                           const uint8_t *__restrict__ kind /*[L][D]*/, const double2 *__restrict__ tab,
+                                                           const uint8_t *__restrict__ mask /*or null*/, const double *__restrict__ lp /*[D]*/,
+                                                           DonorTail tail, bool anchor_given, uint8_t *__restrict__ anchor,
+                                                           double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/, uint8_t *__restrict__ best,
+                                                           uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out, double *__restrict__ p_out,
+                                                           double *__restrict__ post, double *__restrict__ ppost, double *__restrict__ dp_out,
+                                                           uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
+{
+    constexpr int RPW = 64 / DP;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / DP, col = lane % DP;
+    const bool col_ok = (uint32_t)col < D;
+    const int base = sub * DP;
+    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * DN_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * DN_WAVES;
+    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
+        const uint64_t row = g * RPW + sub;
+        const bool have = row < n_rows;
+        const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
+        uint32_t a = 0;
+        if (PAIR && have) a = anchor[row];
+        if (a >= D) a = 0;  // (never: the host checks a given anchor, the singlet pass writes a donor)
+        const bool mine = PAIR && col_ok && (uint32_t)col == a;  // the anchor's own column: a copy of its singlet sum, no pair
+        double acc = 0.0;
+        uint32_t cnt = 0;
+        for (uint64_t i = beg; i < end; i += DN_AHEAD) {
+            uint64_t en[DN_AHEAD];
+            uint32_t ka[DN_AHEAD], kd[DN_AHEAD];
+            double term[DN_AHEAD];
+            bool use[DN_AHEAD], live[DN_AHEAD];
+            // the kinds, then the lookups of all four entries (k_donor_e's loads, in flight together), then the mixtures where a row is soft
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++) {
+                const bool in = i + q < end;
+                en[q] = in ? ent[i + q] : 0ull;
+                const uint64_t l = ENT_IDX(en[q]);
+                use[q] = in && (!mask || mask[l] != 0);
+                live[q] = use[q] && col_ok && !mine;
+                kd[q] = live[q] ? kind[l * D + (uint32_t)col] : 0u;
+                ka[q] = PAIR && live[q] ? kind[l * D + a] : 0u;
+            }
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++) {
+                double2 t = make_double2(0.0, 0.0);
+                if (live[q]) t = tab[dn_gp_row<PAIR>(ENT_IDX(en[q]), ka[q], kd[q])];
+                const double pa = (double)ENT_ALT(en[q]) * t.x, pb = (double)ENT_REF(en[q]) * t.y;
+                term[q] = pa + pb;
+            }
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++)
+                if (live[q] && (kd[q] == DN_SOFT || ka[q] == DN_SOFT))
+                    term[q] = dn_gp_soft<PAIR>(ENT_IDX(en[q]), D, (uint32_t)col, a, ka[q], kd[q], w, tab, (double)ENT_ALT(en[q]), (double)ENT_REF(en[q]));
+#pragma unroll
+            for (int q = 0; q < DN_AHEAD; q++) {
+                if (!use[q]) continue;
+                acc = acc + term[q];
+                cnt++;
+            }
+        }
+        if (mine && have) acc = s[row * D + col];
+        dn_tail<DP, PAIR>(row, have, col, col_ok, base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out, p_out, post,
+                          ppost, dp_out, best_pair, status);
+    }
+}
+
+// ll[k][d] = the ordered sum over ascending unmasked loci of the singlet term under the class' tallies.  Block k, lane d.
+__global__ __launch_bounds__(64) void k_donor_gp_match(uint64_t L, uint32_t D, const unsigned long long *__restrict__ alt /*[K][L]*/,
+                                                       const unsigned long long *__restrict__ ref, const double *__restrict__ w,
+                                                       const uint8_t *__restrict__ kind, const double2 *__restrict__ tab1,
+                                                       const uint8_t *__restrict__ mask /*or null*/, double *__restrict__ ll /*[K][D]*/)
+{
+    const uint32_t k = blockIdx.x, d = threadIdx.x;
+    if (d >= D) return;
+    const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
+    double acc = 0.0;
+    for (uint64_t l0 = 0; l0 < L; l0 += DN_AHEAD) {
+        double av[DN_AHEAD], rv[DN_AHEAD], term[DN_AHEAD];
+        uint32_t kd[DN_AHEAD];
+        bool use[DN_AHEAD];
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++) {
+            const uint64_t l = l0 + q;
+            use[q] = l < L && (!mask || mask[l] != 0);
+            av[q] = use[q] ? (double)ak[l] : 0.0;
+            rv[q] = use[q] ? (double)rk[l] : 0.0;
+            kd[q] = use[q] ? kind[l * D + d] : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++) {
+            double2 t = make_double2(0.0, 0.0);
+            if (use[q]) t = tab1[dn_gp_row<false>(l0 + q, 0u, kd[q])];
+            const double pa = av[q] * t.x, pb = rv[q] * t.y;
+            term[q] = pa + pb;
+        }
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++)
+            if (use[q] && kd[q] == DN_SOFT) term[q] = dn_gp_soft<false>(l0 + q, D, d, 0u, 0u, kd[q], w, tab1, av[q], rv[q]);
+#pragma unroll
+        for (int q = 0; q < DN_AHEAD; q++) {
+            if (!use[q]) continue;
+            acc = acc + term[q];
+        }
+    }
+    ll[(uint64_t)k * D + d] = acc;
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -274,14 +516,26 @@ struct DonorRun {
     DevBuf<uint32_t> cnt;           // [n]
     DevBuf<unsigned long long> alt, ref;  // [K][L] the class tallies (match)
     DevBuf<double> ll;              // [K][D]
-    bool have_mask = false;
+    DevBuf<float> gp;               // [D][TL][3] the soft calls: in place of gt and packed
+    DevBuf<double> w;               // [L][D][3]
+    DevBuf<uint8_t> kind;           // [L][D]
+    DevBuf<uint32_t> bad;           // [1]
+    bool have_mask = false, soft = false;
     const bool timed = getenv("CELLECTOR_TIMING") != nullptr;
 
-    cellector_status alloc(bool cells, uint32_t K)
+    cellector_status alloc(bool cells, uint32_t K, bool soft_calls = false)
     {
-        CHK(dev_alloc(c, &gt, (uint64_t)D * TL));
+        soft = soft_calls;
+        if (soft) {
+            CHK(dev_alloc(c, &gp, (uint64_t)D * TL * 3));
+            CHK(dev_alloc(c, &w, L * D * 3));
+            CHK(dev_alloc(c, &kind, L * D));
+            CHK(dev_alloc(c, &bad, 1));
+        } else {
+            CHK(dev_alloc(c, &gt, (uint64_t)D * TL));
+            CHK(dev_alloc(c, &packed, L * W));
+        }
         CHK(dev_alloc(c, &mask, L));
-        CHK(dev_alloc(c, &packed, L * W));
         CHK(dev_alloc(c, &tab1, L * 4));
         CHK(dev_alloc(c, &tab2, L * 16));
         if (cells) {
@@ -302,15 +556,22 @@ struct DonorRun {
 
     const uint8_t *dmask() const { return have_mask ? mask.get() : nullptr; }
 
-    // one upload of gt, the packing and the tables
-    cellector_status prepare(const uint8_t *host_gt, const uint8_t *host_mask, const cellector_donor_params *prm)
+    // one upload of the calls (gt [D][TL] u8, or gp [D][TL][3] f32 of a soft run), the packing or the weights, and the tables
+    cellector_status prepare(const void *host_calls, const uint8_t *host_mask, const cellector_donor_params *prm)
     {
         have_mask = host_mask != nullptr;
         if (have_mask && L) HIPCHK(c, hipMemcpyAsync(mask, host_mask, L, hipMemcpyHostToDevice, c->stream));
+        if (soft) HIPCHK(c, hipMemsetAsync(bad, 0, 4, c->stream));
         if (!L) return CELLECTOR_OK;
-        HIPCHK(c, hipMemcpyAsync(gt, host_gt, (uint64_t)D * TL, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * W, D, W, TL,
-                           c->locus_ids.get(), gt.get(), packed.get());
+        if (soft) {
+            HIPCHK(c, hipMemcpyAsync(gp, host_calls, (uint64_t)D * TL * 12, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_donor_weights, dim3(dn_grid(L * D, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * D, D, TL,
+                               c->locus_ids.get(), gp.get(), w.get(), kind.get(), bad.get());
+        } else {
+            HIPCHK(c, hipMemcpyAsync(gt, host_calls, (uint64_t)D * TL, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * W, D, W, TL,
+                               c->locus_ids.get(), gt.get(), packed.get());
+        }
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_donor_tables, dim3(dn_grid(L * 16, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * 16,
                            c->s_alt.get(), c->s_ref.get(), dmask(), prm->err, prm->ambient, tab1.get(), tab2.get());
@@ -332,10 +593,34 @@ struct DonorRun {
         if (pair) DN_E(DP, true);                                                                                                      \
         else DN_E(DP, false);                                                                                                          \
         break;
-        switch (dpw) { DN_CASE(2) DN_CASE(4) DN_CASE(8) DN_CASE(16) DN_CASE(32) DN_CASE(64) }
+#define DN_GP_E(DP, PAIR)                                                                                                              \
+    hipLaunchKernelGGL((k_donor_gp_e<DP, PAIR>), dim3(grid), dim3(DN_THREADS), 0, c->stream, n, D, c->csr_ptr.get(), c->csr_ent.get(),   \
+                       w.get(), kind.get(), PAIR ? tab2.get() : tab1.get(), dmask(), lp.get(), tail, anchor_given, anchor.get(), s.get(), \
+                       best.get(), second.get(), cnt.get(), p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get())
+#define DN_GP_CASE(DP)                                                                                                                 \
+    case DP:                                                                                                                           \
+        if (pair) DN_GP_E(DP, true);                                                                                                   \
+        else DN_GP_E(DP, false);                                                                                                       \
+        break;
+        if (soft) switch (dpw) { DN_GP_CASE(2) DN_GP_CASE(4) DN_GP_CASE(8) DN_GP_CASE(16) DN_GP_CASE(32) DN_GP_CASE(64) }
+        else switch (dpw) { DN_CASE(2) DN_CASE(4) DN_CASE(8) DN_CASE(16) DN_CASE(32) DN_CASE(64) }
+#undef DN_GP_CASE
+#undef DN_GP_E
 #undef DN_CASE
 #undef DN_E
         HIPCHK(c, hipGetLastError());
+        return CELLECTOR_OK;
+    }
+
+    // a soft run: the weights as the device holds them, and the kernel's own count of rows the host's check should have refused
+    cellector_status fetch_weights(double *h_w, uint8_t *h_kind)
+    {
+        uint32_t h_bad = 0;
+        CHK(d2h(c, &h_bad, bad, 4));
+        if (h_w) CHK(d2h(c, h_w, w, L * D * 3 * 8));
+        if (h_kind) CHK(d2h(c, h_kind, kind, L * D));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_bad) return ctx_fail(c, CELLECTOR_EDEVICE, "donor weights: %u rows of gp are invalid on the device", h_bad);
         return CELLECTOR_OK;
     }
 
@@ -381,8 +666,23 @@ cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t 
     return st;
 }
 
+// cellector_donor_weights: validated arguments; host outputs, any may be null
+cellector_status donor_weights_run(cellector_ctx *c, const float *gp, uint32_t D, double *w, uint8_t *kind)
+{
+    DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
+    CHK(r.alloc(false, 0, true));
+    donors_invalidate(c);
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    cellector_status st = r.prepare(gp, nullptr, &prm);
+    if (st == CELLECTOR_OK) st = r.fetch_weights(w, kind);
+    (void)hipStreamSynchronize(c->stream);
+    return st;
+}
+
 // cellector_donor_posteriors: validated arguments (log_prior never null: the caller's or zeros); host outputs, any may be null
-cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
+// (gp: the soft calls, then gt is not read and packed stays null)
+cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, const float *gp, uint32_t D, const cellector_donor_params *prm, const double *log_prior,
                                       const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair, double *ll,
                                       double *pair_ll, double *posterior, double *pair_posterior, double *doublet_posterior, uint8_t *best,
                                       uint8_t *second, uint8_t *best_pair, uint32_t *n_entries, uint8_t *status, uint8_t *anchor_out,
@@ -391,14 +691,14 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint3
     LapTimer whole;
     DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
     const uint64_t n = r.n;
-    CHK(r.alloc(true, 0));
+    CHK(r.alloc(true, 0, gp != nullptr));
     std::vector<uint8_t> h_status(n), h_best(n);
     donors_invalidate(c);
     const DonorTail tail = {log_singlet, log_pair, prm->posterior_threshold, prm->min_loci};
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (r.timed)
         for (hipEvent_t &e : ev) (void)hipEventCreate(&e);
-    cellector_status st = r.prepare(gt, mask, prm);
+    cellector_status st = r.prepare(gp ? (const void *)gp : (const void *)gt, mask, prm);
     if (st == CELLECTOR_OK && hipMemcpyAsync(r.lp, log_prior, (uint64_t)D * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the priors failed");
     if (st == CELLECTOR_OK && anchor && n && hipMemcpyAsync(r.anchor, anchor, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
@@ -420,13 +720,14 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint3
     if (st == CELLECTOR_OK && n_entries) st = d2h(c, n_entries, r.cnt, n * 4);
     if (st == CELLECTOR_OK) st = d2h(c, h_status.data(), r.status, n);
     if (st == CELLECTOR_OK && anchor_out) st = d2h(c, anchor_out, r.anchor, n);
-    if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, packed);
+    if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, gp ? nullptr : packed);
+    if (st == CELLECTOR_OK && gp) st = r.fetch_weights(nullptr, nullptr);
     (void)hipStreamSynchronize(c->stream);
     if (r.timed && st == CELLECTOR_OK) {
         float ms1 = 0.f, ms2 = 0.f;
         if (ev[0] && ev[1] && ev[2] && hipEventElapsedTime(&ms1, ev[0], ev[1]) == hipSuccess &&
             hipEventElapsedTime(&ms2, ev[1], ev[2]) == hipSuccess)
-            fprintf(stderr, "[timing]   donors: D %u singlet pass %.3f ms, pair pass %.3f ms, whole call %.4f s\n", D, ms1, ms2, whole.lap());
+            fprintf(stderr, "[timing]   donors%s: D %u singlet pass %.3f ms, pair pass %.3f ms, whole call %.4f s\n", gp ? " (gp)" : "", D, ms1, ms2, whole.lap());
     }
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
@@ -447,29 +748,34 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, uint3
 }
 
 // cellector_match_donors: validated arguments; the tallies are cellector_class_tallies' own; host outputs, any may be null
-cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
+cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, const float *gp, uint32_t D,
                                  const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint8_t *best, double *margin,
                                  uint64_t *cells)
 {
     DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
     const uint64_t L = r.L;
-    CHK(r.alloc(false, K));
+    CHK(r.alloc(false, K, gp != nullptr));
     std::vector<uint64_t> h_alt((uint64_t)K * L), h_ref((uint64_t)K * L), h_cells(K);
     std::vector<double> h_ll((uint64_t)K * D, 0.0);
     CHK(classes_tallies_run(c, labels, K, nullptr, h_cells.data(), h_alt.data(), h_ref.data(), nullptr, nullptr));
     donors_invalidate(c);
-    cellector_status st = r.prepare(gt, mask, prm);
+    cellector_status st = r.prepare(gp ? (const void *)gp : (const void *)gt, mask, prm);
     if (st == CELLECTOR_OK && L) {
         if (hipMemcpyAsync(r.alt, h_alt.data(), (uint64_t)K * L * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(r.ref, h_ref.data(), (uint64_t)K * L * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
             st = ctx_fail(c, CELLECTOR_EDEVICE, "match_donors: the upload of the tallies failed");
     }
     if (st == CELLECTOR_OK) {
-        hipLaunchKernelGGL(k_donor_match, dim3(K), dim3(64), 0, c->stream, L, D, r.W, r.alt.get(), r.ref.get(), r.packed.get(),
-                           r.tab1.get(), r.dmask(), r.ll.get());
+        if (gp)
+            hipLaunchKernelGGL(k_donor_gp_match, dim3(K), dim3(64), 0, c->stream, L, D, r.alt.get(), r.ref.get(), r.w.get(), r.kind.get(),
+                               r.tab1.get(), r.dmask(), r.ll.get());
+        else
+            hipLaunchKernelGGL(k_donor_match, dim3(K), dim3(64), 0, c->stream, L, D, r.W, r.alt.get(), r.ref.get(), r.packed.get(),
+                               r.tab1.get(), r.dmask(), r.ll.get());
         if (hipGetLastError() != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "match_donors: launch failed");
     }
     if (st == CELLECTOR_OK) st = d2h(c, h_ll.data(), r.ll, (uint64_t)K * D * 8);
+    if (st == CELLECTOR_OK && gp) st = r.fetch_weights(nullptr, nullptr);
     (void)hipStreamSynchronize(c->stream);
     if (st != CELLECTOR_OK) return st;
     for (uint32_t k = 0; k < K; k++) {

@@ -10,8 +10,13 @@ The sums are the library's sums in the library's order (a cell's entries in by-c
 order, one rounded product and one rounded add at a time): fed the DEVICE's tables, singlet_sums, pair_sums and match_sums carry the
 device's bits.  log and exp are numpy's, not the device's: the tables made here and the posteriors agree with the device's to a few
 ulps.
+
+The same calls from genotype probabilities (cellector_donor_weights / cellector_donor_posteriors_gp / cellector_match_donors_gp):
+soft_weights, soft_singlet_sums, soft_pair_sums, soft_match_sums, posteriors_gp, match_gp, and read_donor_vcf_gp for the GP, GL or PL
+of a donor VCF.
 """
 import math
+import re
 
 import numpy as np
 
@@ -194,7 +199,10 @@ def match(alt, ref, cells, gt_used, alt_total, ref_total, mask=None, tab1=None, 
     g = np.asarray(gt_used, np.uint8).T
     if tab1 is None:
         tab1 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mask)[0]
-    ll = match_sums(alt, ref, tab1, g, mask)
+    return _match_calls(match_sums(alt, ref, tab1, g, mask), cells)
+
+
+def _match_calls(ll, cells):
     K, D = ll.shape
     best = np.argmax(ll, axis=1)
     if D > 1:
@@ -205,6 +213,160 @@ def match(alt, ref, cells, gt_used, alt_total, ref_total, mask=None, tab1=None, 
         margin = np.full(K, np.inf)
     live = np.asarray(cells) > 0
     return dict(ll=ll, best=np.where(live, best, NONE).astype(np.uint8), margin=np.where(live, margin, 0.0))
+
+
+# ---- genotype probabilities in place of hard calls ---------------------------------------------------------------------------------
+# The twin of cellector_donor_weights / cellector_donor_posteriors_gp / cellector_match_donors_gp.  A donor's row at a locus is three
+# weights; an entry's term is the mixture over the genotypes of positive weight, m + log(sum_g w_g exp(t_g - m)).  A one-hot row and a
+# no-call take the hard call's lookup, as the device does.  exp and log are passed in, as tables() takes log.
+SOFT = 4
+
+
+def one_hot(gt):
+    """gp [D, total_loci, 3] float32 from hard calls gt [D, total_loci]: weight 1 on the call, three NaN for a no-call"""
+    gt = np.asarray(gt, np.uint8)
+    gp = np.zeros(gt.shape + (3,), np.float32)
+    for g in range(3):
+        gp[..., g] = gt == g
+    gp[gt == NO_CALL] = np.nan
+    return gp
+
+
+def hard_codes(gp):
+    """gt [D, total_loci] uint8: the argmax of every row of gp, the smallest g on ties, 3 for a no-call (three NaN)"""
+    gp = np.asarray(gp, np.float32)
+    none = np.isnan(gp).all(axis=-1)
+    return np.where(none, NO_CALL, np.argmax(np.where(none[..., None], 0.0, gp), axis=-1)).astype(np.uint8)
+
+
+def soft_weights(gp, locus_ids):
+    """(w [L, D, 3] float64, kind [L, D] uint8) over the used loci from gp [D, total_loci, 3]: w_g = gp_g / ((gp_0 + gp_1) + gp_2) in
+    f64; kind 0, 1, 2 = a one-hot row of that genotype, 3 = a no-call (three NaN; w 0), 4 = a soft row.  Any other row is refused."""
+    gp = np.asarray(gp, np.float32)
+    x = gp[:, np.asarray(locus_ids, np.int64), :].astype(np.float64).transpose(1, 0, 2)
+    none = np.isnan(x).all(axis=2)
+    with np.errstate(invalid="ignore"):
+        fine = np.isfinite(x).all(axis=2) & (x >= 0).all(axis=2) & (x > 0).any(axis=2)
+    if not (none | fine).all():
+        l, d = np.argwhere(~(none | fine))[0]
+        raise ValueError(f"gp of donor {d} at locus {int(np.asarray(locus_ids)[l])} is {tuple(x[l, d])}: three NaN (no call), or three "
+                         "finite weights >= 0 that are not all zero")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(none[..., None], 0.0, x / ((x[..., 0] + x[..., 1]) + x[..., 2])[..., None])
+        pos = x > 0
+    kind = np.where(none, NO_CALL, np.where(pos.sum(axis=2) > 1, SOFT, np.argmax(pos, axis=2))).astype(np.uint8)
+    return w, kind
+
+
+def _mix(t, w, exp, log):
+    """m + log(z) over the last axis: m = the maximum of t where w > 0, z = the sum in ascending order from 0.0 of w exp(t - m) there.
+    A row without a positive weight gives nan: the callers select no such row."""
+    P = w > 0
+    m = np.where(P, t, -np.inf).max(axis=-1)
+    z = np.zeros(m.shape)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for g in range(t.shape[-1]):
+            e = exp(np.where(P[..., g], t[..., g] - m, 0.0))
+            z = np.where(P[..., g], z + (w[..., g] * e), z)
+        return m + log(z)
+
+
+def _soft_singlet_terms(a, r, t1, w, kind, exp, log):
+    """[m, D] terms from the counts a, r [m, 1], the loci's table rows t1 [m, 4, 2] and the donors' rows w [m, D, 3], kind [m, D]"""
+    m = len(t1)
+    hard = t1[np.arange(m)[:, None], np.minimum(kind, NO_CALL)]
+    term = (a * hard[:, :, 0]) + (r * hard[:, :, 1])
+    soft = kind == SOFT
+    if soft.any():
+        t = (a[:, :, None] * t1[:, None, :3, 0]) + (r[:, :, None] * t1[:, None, :3, 1])  # [m, 1, 3]
+        term = np.where(soft, _mix(np.broadcast_to(t, w.shape), w, exp, log), term)
+    return term
+
+
+def soft_singlet_sums(mat, tab1, w, kind, exp=np.exp, log=np.log):
+    """s [cells, D]: singlet_sums with the mixture term at the soft rows (w, kind: soft_weights' or the device's)"""
+    tab1, w, kind = np.asarray(tab1, np.float64), np.asarray(w, np.float64), np.asarray(kind, np.int64)
+    s = np.zeros((mat.N, kind.shape[1]))
+    for rows, ent in mat.rows.steps:
+        l = mat.r_lo[ent]
+        s[rows] = s[rows] + _soft_singlet_terms(mat.r_al[ent, None], mat.r_re[ent, None], tab1[l], w[l], kind[l], exp, log)
+    return s
+
+
+def _four(w, kind):
+    """[..., 4]: a row's weights over the four table rows; a one-hot row and a no-call are 1.0 on their own row"""
+    out = np.zeros(kind.shape + (4,))
+    out[..., :3] = np.where((kind == SOFT)[..., None], w, 0.0)
+    for g in range(4):
+        out[..., g] = np.where(kind == g, 1.0, out[..., g])
+    return out
+
+
+def soft_pair_sums(mat, tab2, w, kind, anchor, s, exp=np.exp, log=np.log):
+    """p [cells, D]: pair_sums with the mixture over the anchor row's and the donor row's genotypes (g ascending, then h) wherever
+    either is soft; column anchor_c is a copy of s[c, anchor_c]"""
+    tab2, w, kind = np.asarray(tab2, np.float64), np.asarray(w, np.float64), np.asarray(kind, np.int64)
+    anchor = np.asarray(anchor, np.int64)
+    D = kind.shape[1]
+    p = np.zeros((mat.N, D))
+    for rows, ent in mat.rows.steps:
+        l, a, r = mat.r_lo[ent], mat.r_al[ent, None], mat.r_re[ent, None]
+        ka, kd = kind[l, anchor[rows]], kind[l]
+        hard = tab2[l[:, None], 4 * np.minimum(ka, NO_CALL)[:, None] + np.minimum(kd, NO_CALL)]
+        term = (a * hard[:, :, 0]) + (r * hard[:, :, 1])
+        soft = (ka == SOFT)[:, None] | (kd == SOFT)
+        if soft.any():
+            wa, wd = _four(w[l, anchor[rows]], ka), _four(w[l], kd)
+            ww = (wa[:, None, :, None] * wd[:, :, None, :]).reshape(len(l), D, 16)
+            t2 = tab2[l]
+            t = (a[:, :, None] * t2[:, None, :, 0]) + (r[:, :, None] * t2[:, None, :, 1])  # [m, 1, 16]
+            term = np.where(soft, _mix(np.broadcast_to(t, ww.shape), ww, exp, log), term)
+        p[rows] = p[rows] + term
+    c = np.arange(mat.N)
+    p[c, anchor] = np.asarray(s)[c, anchor]
+    return p
+
+
+def soft_match_sums(alt, ref, tab1, w, kind, mask=None, exp=np.exp, log=np.log):
+    """ll [K, D]: match_sums with the mixture term at the soft rows"""
+    alt, ref = np.asarray(alt).astype(np.float64), np.asarray(ref).astype(np.float64)
+    tab1, w, kind = np.asarray(tab1, np.float64), np.asarray(w, np.float64), np.asarray(kind, np.int64)
+    K, L = alt.shape
+    D = kind.shape[1]
+    ll = np.zeros((K, D))
+    for l in range(L):
+        if mask is not None and not mask[l]:
+            continue
+        rep = lambda x: np.broadcast_to(x[None], (K,) + x.shape)
+        ll = ll + _soft_singlet_terms(alt[:, l, None], ref[:, l, None], rep(tab1[l]), rep(w[l]), rep(kind[l]), exp, log)
+    return ll
+
+
+def posteriors_gp(mat, w, kind, alt_total, ref_total, log_prior=None, anchor=None, tab1=None, tab2=None, exp=np.exp, log=np.log, **params):
+    """cellector_donor_posteriors_gp on host arrays: posteriors() with (w [L, D, 3], kind [L, D]) = soft_weights(gp, locus_ids) in
+    place of the hard calls.  tab1 / tab2: the device's tables, or None = numpy's."""
+    prm = _params(params)
+    if tab1 is None or tab2 is None:
+        tab1, tab2 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mat.mask, log=log)
+    s = soft_singlet_sums(mat, tab1, w, kind, exp, log)
+    best, _ = best_second(s, log_prior)
+    anchor = best if anchor is None else np.asarray(anchor, np.uint8)
+    p = soft_pair_sums(mat, tab2, w, kind, anchor, s, exp, log)
+    out = chain(s, p, anchor, mat.entries, log_prior, **prm)
+    st = out["status"]
+    out.update(ll=s, pair_ll=p, anchor=anchor, n_entries=mat.entries.astype(np.uint32), tab1=tab1, tab2=tab2,
+               summary=dict(n_singlet=int((st == SINGLET).sum()), n_doublet=int((st == DOUBLET).sum()),
+                            n_ambiguous=int((st == AMBIGUOUS).sum()), n_unassigned=int((st == UNASSIGNED).sum()),
+                            donor_cells=np.bincount(out["best"][st == SINGLET], minlength=kind.shape[1])))
+    return out
+
+
+def match_gp(alt, ref, cells, w, kind, alt_total, ref_total, mask=None, tab1=None, exp=np.exp, log=np.log, **params):
+    """cellector_match_donors_gp on host arrays: match() with (w, kind) in place of the hard calls"""
+    prm = _params(params)
+    if tab1 is None:
+        tab1 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mask, log=log)[0]
+    return _match_calls(soft_match_sums(alt, ref, tab1, w, kind, mask, exp, log), cells)
 
 
 # ---- the donors' genotypes from a VCF ----------------------------------------------------------------------------------------------
@@ -258,3 +420,63 @@ def read_donor_vcf(donor_vcf, variant_vcf):
             g = parse_gt(toks[9 + d], gi) if 9 + d < len(toks) else NO_CALL
             gt[d, at] = g if g == NO_CALL or not swap else 2 - g
     return names, gt
+
+
+# ---- the donors' genotype probabilities from a VCF ---------------------------------------------------------------------------------
+
+_NUMBER = re.compile(r"[+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?\Z")
+FIELDS = ("GP", "GL", "PL")
+
+
+def parse_weights(field, index, kind):
+    """the three weights (floats, in double) of a sample field's GP, GL or PL at position index, or None: the field absent, '.', not
+    three plain decimal numbers, a GP or PL below 0, a value that is not finite, or three zeros.  GP: as written.  GL: 10^(GL_g - max
+    GL).  PL: 10^(-(PL_g - min PL) / 10)."""
+    parts = field.split(":")
+    if index < 0 or index >= len(parts):
+        return None
+    toks = parts[index].split(",")
+    if len(toks) != 3 or not all(_NUMBER.match(t) for t in toks):
+        return None
+    v = [float(t) for t in toks]
+    if not all(math.isfinite(x) for x in v) or (kind != "GL" and min(v) < 0):
+        return None
+    if kind == "GL":
+        v = [10.0 ** (x - max(v)) for x in v]
+    elif kind == "PL":
+        v = [10.0 ** (-(x - min(v)) / 10.0) for x in v]
+    return v if max(v) > 0 else None
+
+
+def read_donor_vcf_gp(donor_vcf, variant_vcf, field="GP"):
+    """(names, gp): the donors' genotype weights gp [D, total_loci, 3] float32 from the GP, GL or PL of a donor VCF, matched to the
+    variant VCF as read_donor_vcf matches (a record whose ref and alt are swapped has its three values reversed).  A sample whose
+    field parse_weights refuses falls back to the one-hot row of its GT if that parses, else to a no-call (three NaN); so does a
+    variant without a donor record.  GL and PL are computed in double and stored as float."""
+    if field not in FIELDS:
+        raise ValueError(f"field: one of {FIELDS} expected, got {field!r}")
+    names = _sample_names(donor_vcf)
+    rows = {}
+    n = 0
+    for chrom, pos, toks in combine._vcf_records(variant_vcf, columns=True):
+        rows[(chrom, pos, toks[3], toks[4])] = n
+        n += 1
+    gp = np.full((len(names), n, 3), np.nan, np.float32)
+    for chrom, pos, toks in combine._vcf_records(donor_vcf, columns=True):
+        if len(toks) < 10:
+            continue
+        at, swap = rows.get((chrom, pos, toks[3], toks[4])), False
+        if at is None:
+            at, swap = rows.get((chrom, pos, toks[4], toks[3])), True
+        if at is None:
+            continue
+        fmt = toks[8].split(":")
+        gi = fmt.index("GT") if "GT" in fmt else -1
+        fi = fmt.index(field) if field in fmt else -1
+        for d in range(len(names)):
+            v = parse_weights(toks[9 + d], fi, field) if 9 + d < len(toks) else None
+            if v is None:
+                g = parse_gt(toks[9 + d], gi) if 9 + d < len(toks) else NO_CALL
+                v = [math.nan] * 3 if g == NO_CALL else [float(g == k) for k in range(3)]
+            gp[d, at] = v[::-1] if swap else v
+    return names, gp

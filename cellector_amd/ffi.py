@@ -92,6 +92,9 @@ SIGNATURES = {
     "cellector_donor_tables": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "cellector_donor_posteriors": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_match_donors": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
+    "cellector_donor_posteriors_gp": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
+    "cellector_donor_weights": (_i, [_vp, _vp, C.c_uint32, _vp, _vp]),
+    "cellector_match_donors_gp": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
     "cellector_ambient_default_params": (_i, [_vp]),
     "cellector_ambient_tables": (_i, [_vp, _vp, C.c_uint32, _d, _vp, _vp]),
     "cellector_ambient_profile": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _d, _u64, _vp] + [_vp] * 8),
@@ -870,6 +873,14 @@ class Cellector:
         self._ck(self._lib.cellector_donor_tables(self.h, _p(gt), D, C.byref(p), _p(mask), _p(tab1), _p(tab2), _p(packed)))
         return dict(tab1=tab1, tab2=tab2, packed=packed)
 
+    def _donor_gp_args(self, gp, mask, params):
+        gp = np.ascontiguousarray(gp, dtype=np.float32)
+        TL = self.dims().total_loci
+        if gp.ndim != 3 or gp.shape[2] != 3 or (self.dims().total_cells and gp.shape[1] != TL):
+            raise ValueError(f"gp: shape (D, {TL}, 3) expected, got {gp.shape}")
+        _, _, mask, p = self._donor_args(np.zeros((1, TL), np.uint8), mask, params)
+        return gp, gp.shape[0], mask, p
+
     def donor_posteriors(self, gt, log_prior=None, anchor=None, mask=None, tables=False, **params):
         """Every cell against D genotyped donors and the D - 1 doublets of its anchor donor with every other one
         (cellector_donor_posteriors).  anchor None = the best singlet.  params: err, ambient, doublet_rate, posterior_threshold,
@@ -877,6 +888,24 @@ class Cellector:
         best_pair, n_entries, status (0 singlet, 1 doublet, 2 ambiguous, 255 unassigned), anchor [cells], summary (DonorSummary) and,
         with tables, tab1 / tab2."""
         gt, D, mask, p = self._donor_args(gt, mask, params)
+        return self._donor_posteriors(self._lib.cellector_donor_posteriors, gt, D, mask, p, log_prior, anchor, tables)
+
+    def donor_posteriors_gp(self, gp, log_prior=None, anchor=None, mask=None, tables=False, **params):
+        """donor_posteriors from genotype probabilities gp [D, total_loci, 3] float32 (cellector_donor_posteriors_gp): a row of
+        three NaN is a no-call, any other row three weights >= 0 that need not sum to 1.  The same dict."""
+        gp, D, mask, p = self._donor_gp_args(gp, mask, params)
+        return self._donor_posteriors(self._lib.cellector_donor_posteriors_gp, gp, D, mask, p, log_prior, anchor, tables)
+
+    def donor_weights(self, gp):
+        """(w [L, D, 3] float64, kind [L, D] uint8) over the used loci as the device holds them (cellector_donor_weights): kind 0, 1,
+        2 = a one-hot row of that genotype, 3 = a no-call (w 0), 4 = a soft row."""
+        gp, D, _, _ = self._donor_gp_args(gp, None, {})
+        L, Da = self.dims().loci_used, min(max(D, 1), 64)
+        w, kind = np.zeros((L, Da, 3), np.float64), np.zeros((L, Da), np.uint8)
+        self._ck(self._lib.cellector_donor_weights(self.h, _p(gp), D, _p(w), _p(kind)))
+        return w, kind
+
+    def _donor_posteriors(self, call, gt, D, mask, p, log_prior, anchor, tables):
         Da = min(max(D, 1), 64)
         n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used  # (before a load the library refuses the call)
         log_prior = None if log_prior is None else np.ascontiguousarray(log_prior, np.float64)
@@ -894,7 +923,7 @@ class Cellector:
         if tables:
             out["tab1"], out["tab2"] = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64)
         s = DonorSummary()
-        self._ck(self._lib.cellector_donor_posteriors(
+        self._ck(call(
             self.h, _p(gt), D, C.byref(p), _p(log_prior), _p(anchor), _p(mask), _p(out["ll"]), _p(out["pair_ll"]), _p(out["posterior"]),
             _p(out["pair_posterior"]), _p(out["doublet_posterior"]), _p(out["best"]), _p(out["second"]), _p(out["best_pair"]),
             _p(out["n_entries"]), _p(out["status"]), _p(out["anchor"]), C.byref(s), _p(out.get("tab1")), _p(out.get("tab2"))))
@@ -910,6 +939,16 @@ class Cellector:
         ll, best, margin, cells = np.zeros((Ka, Da), np.float64), np.zeros(Ka, np.uint8), np.zeros(Ka, np.float64), np.zeros(Ka, np.uint64)
         self._ck(self._lib.cellector_match_donors(self.h, _p(labels), K, _p(gt), D, C.byref(p), _p(mask), _p(ll), _p(best), _p(margin),
                                                   _p(cells)))
+        return dict(ll=ll, best=best, margin=margin, cells=cells)
+
+    def match_donors_gp(self, labels, n_classes, gp, mask=None, **params):
+        """match_donors from genotype probabilities gp [D, total_loci, 3] (cellector_match_donors_gp): the same dict"""
+        labels, K, _, _, _ = self._class_args(labels, n_classes)
+        gp, D, mask, p = self._donor_gp_args(gp, mask, params)
+        Ka, Da = min(K, 16), min(max(D, 1), 64)
+        ll, best, margin, cells = np.zeros((Ka, Da), np.float64), np.zeros(Ka, np.uint8), np.zeros(Ka, np.float64), np.zeros(Ka, np.uint64)
+        self._ck(self._lib.cellector_match_donors_gp(self.h, _p(labels), K, _p(gp), D, C.byref(p), _p(mask), _p(ll), _p(best), _p(margin),
+                                                     _p(cells)))
         return dict(ll=ll, best=best, margin=margin, cells=cells)
 
     # ---- ambient fraction estimation: the cells of every source scored at G ambient fractions at once; gt [S, total_loci] coded as

@@ -204,6 +204,7 @@ struct Params {
     std::optional<std::string> donors;                 // the donors' genotypes, a VCF with one sample column per donor (needs --vcf)
     double donor_error = 0.01, donor_ambient = 0.03, donor_doublet_rate = 0.1;
     // extension: the pool's ambient fraction measured from the donor pass' singlets (cellector_estimate_ambient)
+    std::string donor_field = "GT";                    // GT: hard calls; GP, GL, PL: the donors' genotype weights (cellector_donor_posteriors_gp)
     int estimate_ambient = 0;                          // 0 = off, 1 = true: report it, 2 = apply: and score the donors again with it
 };
 
@@ -344,6 +345,16 @@ const char *USAGE =
     "        --donor_error <e>                                                  with --donors: allele fraction of a homozygous call (default 0.01)\n"
     "        --donor_ambient <a>                                                with --donors: share of ambient reads (default 0.03)\n"
     "        --donor_doublet_rate <r>                                           with --donors: prior mass of the doublets (default 0.1)\n"
+    "        --donor_field <GT|GP|GL|PL>                                        with --donors: what to read of a donor's sample (default GT, the\n"
+    "                                                                       hard call).  GP: three genotype probabilities; GL: log10\n"
+    "                                                                       likelihoods, 10^(GL - max GL); PL: phred-scaled ones,\n"
+    "                                                                       10^(-(PL - min PL) / 10).  A cell's term is then the mixture over\n"
+    "                                                                       the donor's three genotypes under those weights, and\n"
+    "                                                                       cellector_donors.tsv and cellector_cluster_donors.tsv carry the\n"
+    "                                                                       same columns.  A sample without a usable field falls back to its\n"
+    "                                                                       GT, then to no call.  --estimate_ambient keeps scoring hard calls,\n"
+    "                                                                       the most probable genotype of every row (the soft ambient profile\n"
+    "                                                                       is not implemented).  With GT no output changes\n"
     "        --estimate_ambient <true|apply>                                    with --donors: measure the pool's share of ambient reads from\n"
     "                                                                       the cells the donor pass calls singlets, each under its best\n"
     "                                                                       donor (a profile likelihood over a grid that zooms in).  Writes\n"
@@ -381,7 +392,7 @@ Params load_params(int argc, char **argv)
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
                                   "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask", "donors",
-                                  "donor_error", "donor_ambient", "donor_doublet_rate", "estimate_ambient"};
+                                  "donor_error", "donor_ambient", "donor_doublet_rate", "donor_field", "estimate_ambient"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -517,6 +528,12 @@ Params load_params(int argc, char **argv)
             if (!ok) die(1, "error: Invalid value '" + got[flag] + "' for '--" + f + "': expected a number in " + (f == "donor_error" ? "(0, 0.5)" : "[0, 1)"));
             (f == "donor_error" ? p.donor_error : f == "donor_ambient" ? p.donor_ambient : p.donor_doublet_rate) = v;
         }
+    if (got.count("donor_field")) {
+        if (!p.donors) die(1, "error: The argument '--donor_field <GT|GP|GL|PL>' requires '--donors <vcf>'");
+        p.donor_field = got["donor_field"];
+        if (p.donor_field != "GT" && p.donor_field != "GP" && p.donor_field != "GL" && p.donor_field != "PL")
+            die(1, "error: Invalid value '" + p.donor_field + "' for '--donor_field <GT|GP|GL|PL>': expected GT, GP, GL or PL");
+    }
     if (got.count("estimate_ambient")) {
         const std::string &v = got["estimate_ambient"];
         if (v != "true" && v != "apply" && v != "false")
@@ -1420,6 +1437,8 @@ int main(int argc, char **argv)
     // named by donor
     if (params.donors) {
         DonorGenotypes dg;
+        const bool soft = params.donor_field != "GT";
+        if (soft) dg.field = params.donor_field;
         {
             Lines vin(*params.vcf);
             std::string line;
@@ -1441,10 +1460,18 @@ int main(int argc, char **argv)
         std::vector<uint8_t> dbest(N), dsecond(N), dpair(N), dstatus(N);
         std::vector<uint32_t> dn(N);
         cellector_donor_summary ds;
+        // --donor_field GP / GL / PL: the soft calls score the weights; what needs a hard call takes every row's most probable genotype
+        const std::vector<uint8_t> hard_gt = soft ? donor_hard_codes(dg.gp) : std::vector<uint8_t>();
+        const uint8_t *const gt_codes = soft ? hard_gt.data() : dg.gt.data();
         auto donor_pass = [&]() {
-            g.ck(cellector_donor_posteriors(g.c, dg.gt.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(),
-                                            dppost.data(), ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(), dstatus.data(),
-                                            nullptr, &ds, nullptr, nullptr), "donor_posteriors");
+            if (soft)
+                g.ck(cellector_donor_posteriors_gp(g.c, dg.gp.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(),
+                                                   dppost.data(), ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(),
+                                                   dstatus.data(), nullptr, &ds, nullptr, nullptr), "donor_posteriors_gp");
+            else
+                g.ck(cellector_donor_posteriors(g.c, dg.gt.data(), D, &dp, nullptr, nullptr, nullptr, dll.data(), nullptr, dpost.data(),
+                                                dppost.data(), ddbl.data(), dbest.data(), dsecond.data(), dpair.data(), dn.data(), dstatus.data(),
+                                                nullptr, &ds, nullptr, nullptr), "donor_posteriors");
             fprintf(stderr, "donors: %u donors, singlet=%llu doublet=%llu ambiguous=%llu unassigned=%llu\n", D,
                     (unsigned long long)ds.n_singlet, (unsigned long long)ds.n_doublet, (unsigned long long)ds.n_ambiguous,
                     (unsigned long long)ds.n_unassigned);
@@ -1460,7 +1487,7 @@ int main(int argc, char **argv)
             cellector_ambient_summary as;
             std::vector<double> crho(N), cse(N);
             std::vector<uint32_t> cn(N);
-            g.ck(cellector_estimate_ambient(g.c, dg.gt.data(), D, assign.data(), &ap, nullptr, &as, crho.data(), cse.data(), cn.data()),
+            g.ck(cellector_estimate_ambient(g.c, gt_codes, D, assign.data(), &ap, nullptr, &as, crho.data(), cse.data(), cn.data()),
                  "estimate_ambient");
             {
                 std::string o = "ambient: rho=";
@@ -1526,8 +1553,12 @@ int main(int argc, char **argv)
             std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), mbest(K);
             std::vector<double> mll((uint64_t)K * D), margin(K);
             std::vector<uint64_t> mcells(K);
-            g.ck(cellector_match_donors(g.c, lab.data(), K, dg.gt.data(), D, &dp, nullptr, mll.data(), mbest.data(), margin.data(), mcells.data()),
-                 "match_donors");
+            if (soft)
+                g.ck(cellector_match_donors_gp(g.c, lab.data(), K, dg.gp.data(), D, &dp, nullptr, mll.data(), mbest.data(), margin.data(),
+                                               mcells.data()), "match_donors_gp");
+            else
+                g.ck(cellector_match_donors(g.c, lab.data(), K, dg.gt.data(), D, &dp, nullptr, mll.data(), mbest.data(), margin.data(), mcells.data()),
+                     "match_donors");
             FILE *fm = create(od + "/cellector_cluster_donors.tsv");
             std::string mh = "class\tcells\tdonor\tmargin";
             for (uint32_t d = 0; d < D; d++) mh += "\tlog_likelihood_" + dg.names[d];

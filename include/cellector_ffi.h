@@ -920,6 +920,56 @@ cellector_status cellector_match_donors(cellector_ctx *ctx, const uint8_t *label
                                         double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
                                         uint64_t *cells /*[K]*/); /* any output may be NULL */
 
+/* ---- donor calls from genotype probabilities: GP / GL / PL in place of a hard call --------------------------------
+ * An imputed array or a low-coverage genome gives a donor three weights per locus, and often the heaviest holds little more than
+ * half of the mass.  These calls are the donor calls above with a mixture over a donor's three genotypes in every entry's term.
+ * Everything not stated here is the donor model above, step for step.
+ *   gp [D][total_loci][3] f32, indexed as gt is: entry g = the weight of genotype g (0 = 0/0, 1 = 0/1, 2 = 1/1).  A row of three NaN
+ *   is a no-call.  Any other row must be finite, >= 0 and not all zero, else CELLECTOR_EINVAL (the message names the donor and the
+ *   locus).  Rows need not sum to 1: w_g = (double)gp_g / (((double)gp_0 + (double)gp_1) + (double)gp_2), and P = { g : w_g > 0 }
+ *   (w_g > 0 exactly where gp_g > 0: the quotient cannot underflow).  1 <= D <= 64.  mask, log_prior, anchor and the params are
+ *   those of cellector_donor_posteriors.
+ *   kind [L][D] u8 over the used loci: 0, 1, 2 = a one-hot row of that genotype (one positive weight: w_g = x / x = 1.0), 3 = a
+ *   no-call, 4 = a soft row.  cellector_donor_weights returns w [L][D][3] (0.0 in a no-call's row) and kind as the device holds
+ *   them.
+ *   tab1 / tab2 are cellector_donor_tables' own, bit for bit: the same kernel, the same theta; nothing of them depends on the donors.
+ *   Singlet term of donor d at an entry (alt a, ref r, locus l): t_g = ((double)a la_g) + ((double)r lb_g) from tab1[l][g], the bits
+ *   the hard path forms.  m = the maximum of t_g over P; z = the sum over g in P, ascending, from 0.0, of w_g exp(t_g - m), every
+ *   difference, product and sum rounded once, exp and log the device's; term = m + log(z).  Genotypes outside P take no part: no
+ *   0 exp(+big), and m is never the value of a genotype the row rules out.  A no-call's term is (a la_3) + (r lb_3).  A one-hot row
+ *   has z = 1.0 exp(0.0) = 1.0 and log(1.0) = 0.0: its term IS t_g, the hard call's bits, and the library takes the lookup for
+ *   kind < 4.  The terms are added strictly in row order from 0.0, as step 4.
+ *   Pair term of (anchor a_c, donor d): t_gh from tab2[l][4 g + h], g over the anchor row's P (a no-call: {3} at weight 1.0), h over
+ *   the donor row's likewise; m = the maximum over that product set; z = the sum over g ascending, then h ascending, of
+ *   (w_g w_h) exp(t_gh - m); term = m + log(z); the lookup tab2[l][4 g + h] when both rows have kind < 4.  Column d = a_c takes no
+ *   part in the chain, and pair_ll[c][a_c] is a copy of ll[c][a_c].
+ *   best, second, the anchor, the softmax chain over the 2 D - 1 hypotheses, status and the summary: steps 4 to 8, unchanged.
+ *   cellector_match_donors_gp: the singlet term with the class tallies ((double)a_kl, (double)r_kl) as counts, over ascending
+ *   unmasked loci; best / margin / cells as cellector_match_donors.
+ *   With gp the one-hot of a gt (and three NaN for its no-calls) every output equals the hard call's, byte for byte.
+ * Scope and errors as cellector_donor_posteriors: a single-device ctx that holds all cells, a loaded matrix, no iteration in flight,
+ * engines 1 and 2; CELLECTOR_EINVAL with a message and nothing written or launched (the rows of gp are checked on the host; the
+ * weights kernel counts any row it would refuse itself, and a count above 0 is CELLECTOR_EDEVICE).  All device scratch is allocated
+ * before anything is launched: 12 D bytes per locus of the matrix, 25 D + 321 B per used locus, 32 D + 17 B per cell (match: 16 K B
+ * per used locus more, nothing per cell); on CELLECTOR_ENOMEM the ctx is as it was.  The EM state is never touched; the caches
+ * cellector_cell_log_likelihoods invalidates are invalidated. */
+cellector_status cellector_donor_posteriors_gp(cellector_ctx *ctx, const float *gp /*[D][total_loci][3]*/, uint32_t n_donors,
+                                               const cellector_donor_params *p /*NULL = defaults*/, const double *log_prior /*[D] or NULL*/,
+                                               const uint8_t *anchor /*[cells] or NULL*/, const uint8_t *mask /*[L] or NULL*/,
+                                               double *ll /*[cells][D]*/, double *pair_ll /*[cells][D]*/, double *posterior /*[cells][D]*/,
+                                               double *pair_posterior /*[cells][D]*/, double *doublet_posterior /*[cells]*/,
+                                               uint8_t *best /*[cells]*/, uint8_t *second /*[cells]*/, uint8_t *best_pair /*[cells]*/,
+                                               uint32_t *n_entries /*[cells]*/, uint8_t *status /*[cells]*/, uint8_t *anchor_out /*[cells]*/,
+                                               cellector_donor_summary *out, double *tab1 /*[L][4][2]*/,
+                                               double *tab2 /*[L][16][2]*/); /* any output may be NULL */
+cellector_status cellector_donor_weights(cellector_ctx *ctx, const float *gp /*[D][total_loci][3]*/, uint32_t n_donors,
+                                         double *w /*[L][D][3]*/, uint8_t *kind /*[L][D]*/); /* any output may be NULL */
+cellector_status cellector_match_donors_gp(cellector_ctx *ctx, const uint8_t *labels /*[cells]*/, uint32_t n_classes,
+                                           const float *gp /*[D][total_loci][3]*/, uint32_t n_donors,
+                                           const cellector_donor_params *p /*NULL = defaults*/, const uint8_t *mask /*[L] or NULL*/,
+                                           double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
+                                           uint64_t *cells /*[K]*/); /* any output may be NULL */
+
 /* ---- ambient fraction estimation: a profile likelihood over a grid of rho ------------------------------------------
  * The donor calls above and cellector_class_genotypes take the ambient fraction (the share of a barcode's reads that come from the
  * pool and not from its own cell) as a number the caller supplies.  These calls measure it: every cell is scored under the
