@@ -419,6 +419,13 @@ inline void drop_built(cellector_ctx *c)
     static_cast<CtxBuilt &>(*c) = CtxBuilt();
 }
 
+// what cellector_cell_log_likelihoods invalidates, for the calls that run beside the EM state on scratch of their own
+inline void invalidate_cell_ll_state(cellector_ctx *c)
+{
+    c->tables_prebuilt = false;
+    c->work_zeroed = false;
+}
+
 #define SEL_T 6
 #define CELLECTOR_SUM_SEQ 31
 #define CELLECTOR_SEL_HIST_WORDS (4096 + SEL_T * 1024 + 64)

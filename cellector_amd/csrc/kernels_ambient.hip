@@ -5,29 +5,18 @@
 // The genotypes are packed as the donor calls pack them (k_donor_pack of kernels_donors.hip: 2 bits per source and locus), and a
 // locus has four table rows of G grid points each: tab [L][4][G] double2, 64 G bytes per locus.
 //   k_ambient_tables  one thread per (l, g, j): theta = ((1 - rho_j) e_g) + (rho_j soup), (log theta, log(1 - theta))
-//   k_ambient_e       rows = cells of the by-cell CSR, a group of GP lanes per cell, lane = grid point j (the shape of
-//                     k_donor_e<DP, false>: a lane owns one (cell, j) sum and walks the row's entries in order); the tail finds the
+//   k_ambient_e       rows = cells of the by-cell CSR, lane = grid point j, in the shape lane_rows.h states; the tail finds the
 //                     cell's own maximum over the grid and the vertex of the parabola through the three points around it
 //   k_ambient_fold    block s < S: the cells of source s, block S: every cell that takes part; G ordered sums of the cells' rows
 // All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
-#include "ctx.h"
+#include "lane_rows.h"
 
 #include <cmath>
 
-#define AM_THREADS 256
-#define AM_WAVES (AM_THREADS / 64)
-#define AM_AHEAD 4  // entries whose loads are issued before the first of their ordered adds (= DN_AHEAD of kernels_donors.hip)
 #define AM_NONE 255
+#define AM_MIN_GP 4  // the lane width of the smallest grid: the tail reads three points of it
 #define AM_MAX_G 32
 #define AM_FLAT 0x1p-40  // two steps of a profile that both stay within this share of its value are rounding, not signal (the header)
-
-static inline unsigned am_grid(uint64_t n, unsigned per_block, unsigned cap)
-{
-    uint64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
 
 // The vertex of the parabola through (x0, y0), (x1, y1), (x2, y2), the operations in the header's order.  curv = its second
 // derivative, 0 where neither step of y is resolved (|y1 - y0| and |y2 - y1| both <= AM_FLAT |y1|).  curv < 0: est = the vertex
@@ -62,11 +51,11 @@ __host__ __device__ static inline void am_vertex(double x0, double x1, double x2
 }
 
 // thread (l, g, j) of tab [L][4][G]: soup and e_g as k_donor_tables makes them; a masked locus carries (0, 0)
-__global__ __launch_bounds__(AM_THREADS) void k_ambient_tables(uint64_t n /*4 L G*/, uint32_t G, const double *__restrict__ s_alt,
-                                                               const double *__restrict__ s_ref, const uint8_t *__restrict__ mask /*or null*/,
-                                                               double err, const double *__restrict__ rho /*[G]*/, double2 *__restrict__ tab)
+__global__ __launch_bounds__(LANE_THREADS) void k_ambient_tables(uint64_t n /*4 L G*/, uint32_t G, const double *__restrict__ s_alt,
+                                                                 const double *__restrict__ s_ref, const uint8_t *__restrict__ mask /*or null*/,
+                                                                 double err, const double *__restrict__ rho /*[G]*/, double2 *__restrict__ tab)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * AM_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint32_t j = (uint32_t)(i % G);
     const uint64_t lg = i / G, l = lg >> 2;
@@ -88,38 +77,22 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_tables(uint64_t n /*4 L 
     tab[i] = out;
 }
 
-// (value, index) maximum over the group's GP lanes, the smallest index among equal values: every lane of the wave takes part
-template <int GP>
-__device__ __forceinline__ void am_argmax(double &v, int &idx)
-{
-#pragma unroll
-    for (int off = GP / 2; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(idx, off, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-}
-
 // The cell pass.  A group of GP lanes per cell, lane = grid point j.  acc = the ordered sum of (alt la + ref lb) over the row's
 // entries at unmasked loci, (la, lb) = tab[l][g][j], g = the genotype of the cell's source at l.  A cell whose assign is 255 walks
 // nothing.  The tail: j* = the smallest j of the largest sum, jj = min(max(j*, 1), G - 2), the vertex through jj - 1, jj, jj + 1.
 template <int GP>
-__global__ __launch_bounds__(AM_THREADS) void k_ambient_e(uint64_t n_rows, uint32_t G, uint32_t W, const uint64_t *__restrict__ row_ptr,
-                                                          const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
-                                                          const double2 *__restrict__ tab, const uint8_t *__restrict__ mask /*or null*/,
-                                                          const uint8_t *__restrict__ assign, const double *__restrict__ rho, uint64_t min_loci,
-                                                          double *__restrict__ ll /*[rows][G]*/, uint32_t *__restrict__ cnt_out /*or null*/,
-                                                          double *__restrict__ cell_rho /*or null*/, double *__restrict__ cell_se /*or null*/)
+__global__ __launch_bounds__(LANE_THREADS) void k_ambient_e(uint64_t n_rows, uint32_t G, uint32_t W, const uint64_t *__restrict__ row_ptr,
+                                                            const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
+                                                            const double2 *__restrict__ tab, const uint8_t *__restrict__ mask /*or null*/,
+                                                            const uint8_t *__restrict__ assign, const double *__restrict__ rho, uint64_t min_loci,
+                                                            double *__restrict__ ll /*[rows][G]*/, uint32_t *__restrict__ cnt_out /*or null*/,
+                                                            double *__restrict__ cell_rho /*or null*/, double *__restrict__ cell_se /*or null*/)
 {
-    constexpr int RPW = 64 / GP;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / GP, col = lane % GP;
-    const bool col_ok = (uint32_t)col < G;
-    const int base = sub * GP;
-    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * AM_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * AM_WAVES;
-    for (uint64_t grp = wave0; grp < n_groups; grp += n_waves) {
-        const uint64_t row = grp * RPW + sub;
+    const LaneGeom<GP> geo(n_rows, G);
+    const int col = geo.col, base = geo.base;
+    const bool col_ok = geo.ok;
+    for (uint64_t grp = geo.wave0; grp < geo.n_groups; grp += geo.n_waves) {
+        const uint64_t row = geo.row(grp);
         const bool have = row < n_rows;
         const uint32_t src = have ? assign[row] : AM_NONE;
         const bool part = src != AM_NONE && src < 32u * W;  // (the host checks that any other value is below S)
@@ -127,12 +100,13 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_e(uint64_t n_rows, uint3
         const uint32_t s_word = part ? src >> 5 : 0u, s_shift = 2u * (src & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        for (uint64_t i = beg; i < end; i += AM_AHEAD) {
-            uint64_t en[AM_AHEAD];
-            double2 t[AM_AHEAD];
-            bool use[AM_AHEAD];
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_donor_e and k_donor_match as well
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            double2 t[LANE_AHEAD];
+            bool use[LANE_AHEAD];
 #pragma unroll
-            for (int q = 0; q < AM_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 const bool in = i + q < end;
                 en[q] = in ? ent[i + q] : 0ull;
                 const uint64_t l = ENT_IDX(en[q]);
@@ -144,7 +118,7 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_e(uint64_t n_rows, uint3
                 }
             }
 #pragma unroll
-            for (int q = 0; q < AM_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 if (!use[q]) continue;
                 const uint32_t al = ENT_ALT(en[q]), re = ENT_REF(en[q]);
                 const double pa = (double)al * t[q].x, pb = (double)re * t[q].y;
@@ -153,10 +127,10 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_e(uint64_t n_rows, uint3
                 cnt++;
             }
         }
-        // the tail: every lane of the wave takes part in the shuffles, whatever its row and grid point
+        // the tail
         double v = col_ok ? acc : -INFINITY;
         int js = col_ok ? col : 0x7fff;
-        am_argmax<GP>(v, js);
+        lane_argmax<GP>(v, js);
         const int hi = (int)G - 2;
         int jj = js < 1 ? 1 : js;
         if (jj > hi) jj = hi;
@@ -181,18 +155,18 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_e(uint64_t n_rows, uint3
 // ... in ascending order, one sum per grid point; the 256 partial sums of a grid point are folded pairwise (h = 128 ... 1), as
 // k_cluster_objective folds.  cells[b] = how many cells the block summed.
 template <int GP>
-__global__ __launch_bounds__(AM_THREADS) void k_ambient_fold(uint64_t n, uint32_t G, uint32_t S, const double *__restrict__ ll /*[n][G]*/,
-                                                             const uint8_t *__restrict__ assign, double *__restrict__ tot /*[S + 1][G]*/,
-                                                             unsigned long long *__restrict__ cells /*[S + 1]*/)
+__global__ __launch_bounds__(LANE_THREADS) void k_ambient_fold(uint64_t n, uint32_t G, uint32_t S, const double *__restrict__ ll /*[n][G]*/,
+                                                               const uint8_t *__restrict__ assign, double *__restrict__ tot /*[S + 1][G]*/,
+                                                               unsigned long long *__restrict__ cells /*[S + 1]*/)
 {
-    __shared__ double sh[AM_THREADS];
-    __shared__ unsigned long long shn[AM_THREADS];
+    __shared__ double sh[LANE_THREADS];
+    __shared__ unsigned long long shn[LANE_THREADS];
     const uint32_t b = blockIdx.x;
     double a[GP];
 #pragma unroll
     for (int j = 0; j < GP; j++) a[j] = 0.0;
     unsigned long long m = 0;
-    for (uint64_t i = threadIdx.x; i < n; i += AM_THREADS) {
+    for (uint64_t i = threadIdx.x; i < n; i += LANE_THREADS) {
         const uint32_t src = assign[i];
         if (b < S ? src != b : src == AM_NONE) continue;
         const double *row = ll + i * G;
@@ -203,7 +177,7 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_fold(uint64_t n, uint32_
     }
     shn[threadIdx.x] = m;
     __syncthreads();
-    for (int h = AM_THREADS / 2; h > 0; h >>= 1) {
+    for (int h = LANE_THREADS / 2; h > 0; h >>= 1) {
         if ((int)threadIdx.x < h) shn[threadIdx.x] += shn[threadIdx.x + h];
         __syncthreads();
     }
@@ -213,7 +187,7 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_fold(uint64_t n, uint32_
         __syncthreads();
         sh[threadIdx.x] = a[j];
         __syncthreads();
-        for (int h = AM_THREADS / 2; h > 0; h >>= 1) {
+        for (int h = LANE_THREADS / 2; h > 0; h >>= 1) {
             if ((int)threadIdx.x < h) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
             __syncthreads();
         }
@@ -224,31 +198,24 @@ __global__ __launch_bounds__(AM_THREADS) void k_ambient_fold(uint64_t n, uint32_
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
 
-int am_gp(uint32_t G)
-{
-    int gp = 4;
-    while ((uint32_t)gp < G) gp <<= 1;
-    return gp;
-}
-
 // the scratch of one call; alloc() makes all of it before anything is launched
 struct AmbientRun {
     cellector_ctx *c;
     uint32_t S, W, G;
     uint64_t n, L, TL;
-    DevBuf<uint8_t> gt, mask, assign;  // [S][TL], [L], [n]
+    DevBuf<uint8_t> gt, assign;        // [S][TL], [n]
+    LociMask mask;                     // [L]
     DevBuf<uint64_t> packed;           // [L][W]
     DevBuf<double2> tab;               // [L][4][G]
     DevBuf<double> rho, ll, tot;       // [G], [n][G], [S + 1][G]
     DevBuf<double> cell_rho, cell_se;  // [n]
     DevBuf<uint32_t> cnt;              // [n]
     DevBuf<unsigned long long> cells;  // [S + 1]
-    bool have_mask = false;
-    const bool timed = getenv("CELLECTOR_TIMING") != nullptr;
+    EventMarks<2> ev;                  // around the cell pass and the folds of a profile
 
     cellector_status alloc(bool cell_pass)
     {
-        CHK(dev_alloc(c, &mask, L));
+        CHK(dev_alloc(c, &mask.buf, L));
         CHK(dev_alloc(c, &rho, G));
         CHK(dev_alloc(c, &tab, L * 4 * G));
         if (cell_pass) {
@@ -264,13 +231,10 @@ struct AmbientRun {
         return CELLECTOR_OK;
     }
 
-    const uint8_t *dmask() const { return have_mask ? mask.get() : nullptr; }
-
     // one upload of the mask, of gt and of assign, and the packing
     cellector_status prepare(const uint8_t *host_gt, const uint8_t *host_assign, const uint8_t *host_mask)
     {
-        have_mask = host_mask != nullptr;
-        if (have_mask && L) HIPCHK(c, hipMemcpyAsync(mask, host_mask, L, hipMemcpyHostToDevice, c->stream));
+        CHK(mask.set(c, host_mask, L));
         if (host_assign && n) HIPCHK(c, hipMemcpyAsync(assign, host_assign, n, hipMemcpyHostToDevice, c->stream));
         if (!host_gt || !L) return CELLECTOR_OK;
         HIPCHK(c, hipMemcpyAsync(gt, host_gt, (uint64_t)S * TL, hipMemcpyHostToDevice, c->stream));
@@ -283,8 +247,8 @@ struct AmbientRun {
         HIPCHK(c, hipMemcpyAsync(rho, host_rho, (uint64_t)G * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (!L) return CELLECTOR_OK;
-        hipLaunchKernelGGL(k_ambient_tables, dim3(am_grid(L * 4 * G, AM_THREADS, 0x7fffffffu)), dim3(AM_THREADS), 0, c->stream, L * 4 * G, G,
-                           c->s_alt.get(), c->s_ref.get(), dmask(), err, rho.get(), tab.get());
+        hipLaunchKernelGGL(k_ambient_tables, dim3(lane_grid(L * 4 * G, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream,
+                           L * 4 * G, G, c->s_alt.get(), c->s_ref.get(), mask.get(), err, rho.get(), tab.get());
         HIPCHK(c, hipGetLastError());
         return CELLECTOR_OK;
     }
@@ -292,36 +256,24 @@ struct AmbientRun {
     // the cell pass and the folds; cells == false: the per-cell outputs of an earlier pass stay
     cellector_status pass(uint64_t min_loci, bool cells_out)
     {
-        const int gp = am_gp(G);
+        const int gp = lane_width(G, AM_MIN_GP);
         if (n) {
-            const unsigned grid = am_grid((n + 64 / gp - 1) / (64 / gp), AM_WAVES, (unsigned)c->n_cu * 8);
-#define AM_CASE(GP)                                                                                                                    \
-    case GP:                                                                                                                           \
-        hipLaunchKernelGGL((k_ambient_e<GP>), dim3(grid), dim3(AM_THREADS), 0, c->stream, n, G, W, c->csr_ptr.get(), c->csr_ent.get(), \
-                           packed.get(), tab.get(), dmask(), assign.get(), rho.get(), min_loci, ll.get(),                              \
-                           cells_out ? cnt.get() : nullptr, cells_out ? cell_rho.get() : nullptr, cells_out ? cell_se.get() : nullptr); \
-        break;
-            switch (gp) { AM_CASE(4) AM_CASE(8) AM_CASE(16) AM_CASE(32) }
-#undef AM_CASE
+            lane_dispatch<AM_MIN_GP, AM_MAX_G>(gp, [&](auto GP) {
+                hipLaunchKernelGGL(k_ambient_e<GP>, dim3(lane_walk_grid(n, gp, c->n_cu)), dim3(LANE_THREADS), 0, c->stream, n, G, W,
+                                   c->csr_ptr.get(), c->csr_ent.get(), packed.get(), tab.get(), mask.get(), assign.get(), rho.get(), min_loci,
+                                   ll.get(), cells_out ? cnt.get() : nullptr, cells_out ? cell_rho.get() : nullptr,
+                                   cells_out ? cell_se.get() : nullptr);
+            });
             HIPCHK(c, hipGetLastError());
         }
-#define AM_CASE(GP)                                                                                                                    \
-    case GP:                                                                                                                           \
-        hipLaunchKernelGGL((k_ambient_fold<GP>), dim3(S + 1), dim3(AM_THREADS), 0, c->stream, n, G, S, ll.get(), assign.get(), tot.get(), \
-                           cells.get());                                                                                               \
-        break;
-        switch (gp) { AM_CASE(4) AM_CASE(8) AM_CASE(16) AM_CASE(32) }
-#undef AM_CASE
+        lane_dispatch<AM_MIN_GP, AM_MAX_G>(gp, [&](auto GP) {
+            hipLaunchKernelGGL(k_ambient_fold<GP>, dim3(S + 1), dim3(LANE_THREADS), 0, c->stream, n, G, S, ll.get(), assign.get(), tot.get(),
+                               cells.get());
+        });
         HIPCHK(c, hipGetLastError());
         return CELLECTOR_OK;
     }
 };
-
-void ambient_invalidate(cellector_ctx *c)
-{
-    c->tables_prebuilt = false;  // what cellector_cell_log_likelihoods invalidates (the calls themselves use scratch of their own)
-    c->work_zeroed = false;
-}
 
 // the vertex rule of the header's step 4 on G totals
 void am_host_vertex(const double *rho, const double *y, uint32_t G, uint32_t *j_star, double *est, double *se, double *curv)
@@ -342,7 +294,7 @@ cellector_status ambient_tables_run(cellector_ctx *c, const double *rho, uint32_
 {
     AmbientRun r{c, 0, 0, G, c->nloc, c->L, c->total_loci};
     CHK(r.alloc(false));
-    ambient_invalidate(c);
+    invalidate_cell_ll_state(c);
     cellector_status st = r.prepare(nullptr, nullptr, mask);
     if (st == CELLECTOR_OK) st = r.tables(rho, err);
     if (st == CELLECTOR_OK && tab) st = d2h(c, tab, r.tab, r.L * 4 * G * 16);
@@ -359,15 +311,12 @@ cellector_status ambient_profile_run(cellector_ctx *c, const uint8_t *gt, uint32
     AmbientRun r{c, S, (S + 31) / 32, G, c->nloc, c->L, c->total_loci};
     const uint64_t n = r.n;
     CHK(r.alloc(true));
-    ambient_invalidate(c);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (r.timed)
-        for (hipEvent_t &e : ev) (void)hipEventCreate(&e);
+    invalidate_cell_ll_state(c);
     cellector_status st = r.prepare(gt, assign, mask);
     if (st == CELLECTOR_OK) st = r.tables(rho, err);
-    if (ev[0]) (void)hipEventRecord(ev[0], c->stream);
+    r.ev.mark(0, c->stream);
     if (st == CELLECTOR_OK) st = r.pass(min_loci, true);
-    if (ev[1]) (void)hipEventRecord(ev[1], c->stream);
+    r.ev.mark(1, c->stream);
     std::vector<double> h_tot((uint64_t)(S + 1) * G);
     std::vector<unsigned long long> h_cells(S + 1);
     if (st == CELLECTOR_OK) st = d2h(c, h_tot.data(), r.tot, h_tot.size() * 8);
@@ -378,13 +327,9 @@ cellector_status ambient_profile_run(cellector_ctx *c, const uint8_t *gt, uint32
     if (st == CELLECTOR_OK && cell_se) st = d2h(c, cell_se, r.cell_se, n * 8);
     if (st == CELLECTOR_OK && tab) st = d2h(c, tab, r.tab, r.L * 4 * G * 16);
     (void)hipStreamSynchronize(c->stream);
-    if (r.timed && st == CELLECTOR_OK) {
-        float ms = 0.f;
-        if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            fprintf(stderr, "[timing]   ambient: S %u G %u cell pass and folds %.3f ms, whole call %.4f s\n", S, G, ms, whole.lap());
-    }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
+    float ms = 0.f;
+    if (st == CELLECTOR_OK && r.ev.ms(0, 1, &ms))
+        fprintf(stderr, "[timing]   ambient: S %u G %u cell pass and folds %.3f ms, whole call %.4f s\n", S, G, ms, whole.lap());
     if (st != CELLECTOR_OK) return st;
     if (total) memcpy(total, h_tot.data() + (uint64_t)S * G, (uint64_t)G * 8);
     if (source_total) memcpy(source_total, h_tot.data(), (uint64_t)S * G * 8);
@@ -402,7 +347,7 @@ cellector_status ambient_estimate_run(cellector_ctx *c, const uint8_t *gt, uint3
     AmbientRun r{c, S, (S + 31) / 32, G, c->nloc, c->L, c->total_loci};
     const uint64_t n = r.n;
     CHK(r.alloc(true));
-    ambient_invalidate(c);
+    invalidate_cell_ll_state(c);
     std::vector<double> h_tot((uint64_t)(S + 1) * G);
     std::vector<unsigned long long> h_cells(S + 1);
     double rho[AM_MAX_G];
@@ -437,7 +382,7 @@ cellector_status ambient_estimate_run(cellector_ctx *c, const uint8_t *gt, uint3
     }
     (void)hipStreamSynchronize(c->stream);
     if (st != CELLECTOR_OK) return st;
-    if (r.timed) fprintf(stderr, "[timing]   ambient: S %u G %u rounds %u, whole call %.4f s\n", S, G, p->rounds, whole.lap());
+    if (r.ev.on) fprintf(stderr, "[timing]   ambient: S %u G %u rounds %u, whole call %.4f s\n", S, G, p->rounds, whole.lap());
     if (!out) return CELLECTOR_OK;
     cellector_ambient_summary sum = {};
     const double *tot = h_tot.data() + (uint64_t)S * G;

@@ -4,37 +4,23 @@
 //
 // The restarts are COLUMNS: column j = r K + k is cluster k of restart r, J = K R <= 64 of them.  Every per-locus quantity is a
 // row of J values ([L][J] theta, [L][J][2] the two logs), every per-cell one a row of J ([cells][J] sums s and weights w).  Both
-// passes put the columns on the lanes: a lane owns one (row, column) sum and walks the row's entries in order, so every sum is
-// strictly sequential (the bits depend on the matrix alone) and every entry costs the wave one contiguous read of J values: the
-// restarts share the entry stream, the pointers and the launches (measured at cfg4, K = 3: sixteen restarts cost 7.4 E steps and
-// 5.0 M steps of one).  J is rounded up to a power of two J'; with J' <= 32 a wave carries 64 / J' rows.
+// passes put the columns on the lanes, in the shape lane_rows.h states: the restarts share the entry stream, the pointers and the
+// launches (measured at cfg4, K = 3: sixteen restarts cost 7.4 E steps and 5.0 M steps of one).
 //   E step  k_cluster_e  rows = cells of the by-cell CSR, per entry the double2 row of the table; tail: softmax per restart,
 //                        the cell's objective terms, its depth and its entry count
 //   M step  k_cluster_m  rows = loci of a by-locus list in ascending cell order, per entry a gather of the cell's w row
 // The by-locus list is a stable sort of the by-cell CSR by locus (the ingest's sorter): ascending cell, file order among the
 // repeats of a pair, whatever order the file had its cells in; engine 2 keeps no by-locus copy of the packed entries anyway.  It
 // lives in call-owned scratch.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
-#include "ctx.h"
+#include "lane_rows.h"
 #include "mix64.h"
 
 #include <cmath>
 
-#define CK_THREADS 256
-#define CK_WAVES (CK_THREADS / 64)
-#define CK_AHEAD 4  // entries whose loads are issued before the first of their ordered adds
-
-static inline unsigned ck_grid(uint64_t n, unsigned per_block, unsigned cap)
-{
-    uint64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 // theta[l][j] = floor + (1 - 2 floor) u(l, j), u = (mix64(sm + (l J + j + 1) GOLD) >> 11) 2^-53, sm = mix64(seed GOLD + GOLD)
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_start(uint64_t n /*L J*/, uint64_t sm, double floor, double *__restrict__ theta)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_start(uint64_t n /*L J*/, uint64_t sm, double floor, double *__restrict__ theta)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * CK_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const double u = (double)(mix64(sm + (i + 1) * GOLD) >> 11) * 0x1p-53;
     const double span = 1.0 - 2.0 * floor;
@@ -42,10 +28,10 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_start(uint64_t n /*L J*/
 }
 
 // tab[l][j] = (log theta, log(1 - theta)); a masked locus takes no part anywhere and carries (0, 0)
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_tables(uint64_t n /*L J*/, uint32_t J, const double *__restrict__ theta,
-                                                               const uint8_t *__restrict__ mask /*or null*/, double2 *__restrict__ tab)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_tables(uint64_t n /*L J*/, uint32_t J, const double *__restrict__ theta,
+                                                                 const uint8_t *__restrict__ mask /*or null*/, double2 *__restrict__ tab)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * CK_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const bool used = !mask || mask[i / J] != 0;
     const double t = theta[i];
@@ -56,34 +42,32 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_tables(uint64_t n /*L J*
 // loci; then per restart x_k = s_k / T, m = max, den = sum exp(x_k - m) in ascending k, w = exp(x - m) / den, o = m + log(den).
 // T = temp[cell], or max(1, depth / div) with the cell's own depth (div > 0), or 1.
 template <int JP>
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_e(uint64_t n_rows, uint32_t J, uint32_t K, const uint64_t *__restrict__ row_ptr,
-                                                          const uint64_t *__restrict__ ent, const double2 *__restrict__ tab,
-                                                          const uint8_t *__restrict__ mask /*or null*/,
-                                                          const double *__restrict__ temp /*or null*/, double div,
-                                                          double *__restrict__ s_out, double *__restrict__ w_out,
-                                                          double *__restrict__ o_out /*[rows][R]*/,
-                                                          unsigned long long *__restrict__ depth_out, uint32_t *__restrict__ cnt_out)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_e(uint64_t n_rows, uint32_t J, uint32_t K, const uint64_t *__restrict__ row_ptr,
+                                                            const uint64_t *__restrict__ ent, const double2 *__restrict__ tab,
+                                                            const uint8_t *__restrict__ mask /*or null*/,
+                                                            const double *__restrict__ temp /*or null*/, double div,
+                                                            double *__restrict__ s_out, double *__restrict__ w_out,
+                                                            double *__restrict__ o_out /*[rows][R]*/,
+                                                            unsigned long long *__restrict__ depth_out, uint32_t *__restrict__ cnt_out)
 {
-    constexpr int RPW = 64 / JP;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / JP, col = lane % JP;
-    const bool col_ok = (uint32_t)col < J;
+    const LaneGeom<JP> geo(n_rows, J);
+    const int col = geo.col;
+    const bool col_ok = geo.ok;
     const uint32_t R = J / K;
-    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * CK_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * CK_WAVES;
-    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
-        const uint64_t row = g * RPW + sub;
+    for (uint64_t g = geo.wave0; g < geo.n_groups; g += geo.n_waves) {
+        const uint64_t row = geo.row(g);
         const bool have = row < n_rows;
         const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
         double acc = 0.0;
         unsigned long long depth = 0;
         uint32_t cnt = 0;
-        for (uint64_t i = beg; i < end; i += CK_AHEAD) {
-            uint64_t en[CK_AHEAD];
-            double2 t[CK_AHEAD];
-            bool use[CK_AHEAD];
+        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_ambient_e and k_donor_match as well
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            double2 t[LANE_AHEAD];
+            bool use[LANE_AHEAD];
 #pragma unroll
-            for (int q = 0; q < CK_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 const bool in = i + q < end;
                 en[q] = in ? ent[i + q] : 0ull;
                 const uint64_t l = ENT_IDX(en[q]);
@@ -91,7 +75,7 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_e(uint64_t n_rows, uint3
                 t[q] = use[q] && col_ok ? tab[l * J + col] : make_double2(0.0, 0.0);
             }
 #pragma unroll
-            for (int q = 0; q < CK_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 if (!use[q]) continue;
                 const uint32_t a = ENT_ALT(en[q]), r = ENT_REF(en[q]);
                 const double pa = (double)a * t[q].x, pb = (double)r * t[q].y;
@@ -101,12 +85,12 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_e(uint64_t n_rows, uint3
                 cnt++;
             }
         }
-        // the tail: every lane of the wave takes part in the shuffles, whatever its row and column
+        // the tail (the restart's K lanes from base on)
         double T = 1.0;
         if (have) T = temp ? temp[row] : (div > 0.0 ? fmax(1.0, (double)depth / div) : 1.0);
         const double x = acc / T;
         const uint32_t r = col_ok ? (uint32_t)col / K : 0;
-        const int base = sub * JP + (int)(r * K);
+        const int base = geo.sub * JP + (int)(r * K);
         double m = -INFINITY;
         for (uint32_t k = 0; k < K; k++) m = fmax(m, __shfl(x, (base + (int)k) & 63, 64));
         double den = 0.0;
@@ -125,15 +109,15 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_e(uint64_t n_rows, uint3
 
 // obj[r] = sum over the cells of o[cell][r] in a fixed order: thread t of block r adds the cells t, t + 256, ... in ascending order,
 // the 256 partial sums are folded pairwise
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_objective(uint64_t n, uint32_t R, const double *__restrict__ o, double *__restrict__ obj)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_objective(uint64_t n, uint32_t R, const double *__restrict__ o, double *__restrict__ obj)
 {
-    __shared__ double sh[CK_THREADS];
+    __shared__ double sh[LANE_THREADS];
     const uint32_t r = blockIdx.x;
     double a = 0.0;
-    for (uint64_t i = threadIdx.x; i < n; i += CK_THREADS) a = a + o[i * R + r];
+    for (uint64_t i = threadIdx.x; i < n; i += LANE_THREADS) a = a + o[i * R + r];
     sh[threadIdx.x] = a;
     __syncthreads();
-    for (int h = CK_THREADS / 2; h > 0; h >>= 1) {
+    for (int h = LANE_THREADS / 2; h > 0; h >>= 1) {
         if ((int)threadIdx.x < h) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
         __syncthreads();
     }
@@ -144,37 +128,33 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_objective(uint64_t n, ui
 // in ascending cell order (a rounded product, then the add), theta = min(max((A + 1) / (T + 2), floor), 1 - floor).  A locus without
 // an entry gets 1 / 2 = 0.5 by the same formula; a masked locus is not walked: A = T = 0, theta = 0.5.
 template <int JP>
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_m(uint64_t L, uint32_t J, const uint64_t *__restrict__ col_ptr,
-                                                          const uint64_t *__restrict__ ent /*by locus, ascending cell*/,
-                                                          const double *__restrict__ w /*[cells][J]*/,
-                                                          const uint8_t *__restrict__ mask /*or null*/, double floor,
-                                                          double *__restrict__ A_out /*or null*/, double *__restrict__ T_out /*or null*/,
-                                                          double *__restrict__ theta)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_m(uint64_t L, uint32_t J, const uint64_t *__restrict__ col_ptr,
+                                                            const uint64_t *__restrict__ ent /*by locus, ascending cell*/,
+                                                            const double *__restrict__ w /*[cells][J]*/,
+                                                            const uint8_t *__restrict__ mask /*or null*/, double floor,
+                                                            double *__restrict__ A_out /*or null*/, double *__restrict__ T_out /*or null*/,
+                                                            double *__restrict__ theta)
 {
-    constexpr int RPW = 64 / JP;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / JP, col = lane % JP;
-    const bool col_ok = (uint32_t)col < J;
-    const uint64_t n_groups = (L + RPW - 1) / RPW;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * CK_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * CK_WAVES;
+    const LaneGeom<JP> geo(L, J);
+    const int col = geo.col;
     const double ceil_ = 1.0 - floor;
-    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
-        const uint64_t l = g * RPW + sub;
-        const bool have = l < L && col_ok;
+    for (uint64_t g = geo.wave0; g < geo.n_groups; g += geo.n_waves) {
+        const uint64_t l = geo.row(g);
+        const bool have = l < L && geo.ok;
         const bool used = have && (!mask || mask[l] != 0);
         const uint64_t beg = used ? col_ptr[l] : 0, end = used ? col_ptr[l + 1] : 0;
         double A = 0.0, T = 0.0;
-        for (uint64_t i = beg; i < end; i += CK_AHEAD) {
-            uint64_t en[CK_AHEAD];
-            double wv[CK_AHEAD];
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            double wv[LANE_AHEAD];
 #pragma unroll
-            for (int q = 0; q < CK_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 const bool in = i + q < end;
                 en[q] = in ? ent[i + q] : 0ull;
                 wv[q] = in ? w[(uint64_t)ENT_IDX(en[q]) * J + col] : 0.0;
             }
 #pragma unroll
-            for (int q = 0; q < CK_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 if (i + q >= end) continue;
                 const uint32_t a = ENT_ALT(en[q]), r = ENT_REF(en[q]);
                 const double pa = wv[q] * (double)a, pt = wv[q] * (double)(a + r);
@@ -191,12 +171,12 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_m(uint64_t L, uint32_t J
 }
 
 // the by-cell CSR as (locus key, cell | counts) pairs, one wave per row
-__global__ __launch_bounds__(CK_THREADS) void k_cluster_split(uint64_t n_rows, const uint64_t *__restrict__ row_ptr,
-                                                              const uint64_t *__restrict__ ent, uint32_t *__restrict__ key,
-                                                              uint64_t *__restrict__ val)
+__global__ __launch_bounds__(LANE_THREADS) void k_cluster_split(uint64_t n_rows, const uint64_t *__restrict__ row_ptr,
+                                                                const uint64_t *__restrict__ ent, uint32_t *__restrict__ key,
+                                                                uint64_t *__restrict__ val)
 {
     const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * CK_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * CK_WAVES;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * LANE_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * LANE_WAVES;
     for (uint64_t row = wave0; row < n_rows; row += n_waves) {
         const uint64_t beg = row_ptr[row], end = row_ptr[row + 1];
         for (uint64_t i = beg + lane; i < end; i += 64) {
@@ -209,13 +189,6 @@ __global__ __launch_bounds__(CK_THREADS) void k_cluster_split(uint64_t n_rows, c
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
-
-int ck_jp(uint32_t J)
-{
-    int jp = 2;
-    while ((uint32_t)jp < J) jp <<= 1;
-    return jp;
-}
 
 // the scratch of one call; alloc() makes all of it (and the by-locus list) before anything is launched
 struct ClusterRun {
@@ -230,38 +203,25 @@ struct ClusterRun {
     DevBuf<double> temp;        // [n] a caller's temperatures
     DevBuf<unsigned long long> depth;  // [n]
     DevBuf<uint32_t> cnt;       // [n]
-    DevBuf<uint8_t> mask;       // [L]
-    bool have_mask = false;
-    // CELLECTOR_TIMING=1: the GPU time of the E and M kernels of a cellector_cluster call (HIP events around every launch, read after
-    // the iteration's own synchronisation) and the wall time of the by-locus list, one stderr line per call
-    const bool timed = getenv("CELLECTOR_TIMING") != nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    LociMask mask;              // [L]
+    // CELLECTOR_TIMING=1: the GPU time of the E and M kernels of a cellector_cluster call (events 0, 1 around the E launches, 2, 3 around
+    // the M launch, read after the iteration's own synchronisation) and the wall time of the by-locus list, one stderr line per call
+    EventMarks<4> ev;
     double ms_e = 0.0, ms_m = 0.0, s_list = 0.0;
     unsigned n_e = 0, n_m = 0;
     bool open_e = false, open_m = false;
-    ~ClusterRun()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int i)
-    {
-        if (!timed) return;
-        if (!ev[i] && hipEventCreate(&ev[i]) != hipSuccess) return;
-        (void)hipEventRecord(ev[i], c->stream);
-    }
     void collect()  // (the stream is idle)
     {
         float ms = 0.f;
-        if (open_e && ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { ms_e += ms; n_e++; }
-        if (open_m && ev[2] && ev[3] && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) { ms_m += ms; n_m++; }
+        if (open_e && ev.ms(0, 1, &ms)) { ms_e += ms; n_e++; }
+        if (open_m && ev.ms(2, 3, &ms)) { ms_m += ms; n_m++; }
         open_e = open_m = false;
     }
 
     cellector_status alloc(bool e_side, bool m_side, bool at, bool temps)
     {
         const uint64_t LJ = L * J, nJ = n * J;
-        CHK(dev_alloc(c, &mask, L));
+        CHK(dev_alloc(c, &mask.buf, L));
         CHK(dev_alloc(c, &tab, LJ));
         CHK(dev_alloc(c, &w, nJ));
         if (m_side) {
@@ -290,7 +250,7 @@ struct ClusterRun {
         CHK(dev_alloc(c, &key, nnz)); CHK(dev_alloc(c, &key_o, nnz)); CHK(dev_alloc(c, &val, nnz));
         if (!nnz || !n) return CELLECTOR_OK;
         LapTimer t;
-        hipLaunchKernelGGL(k_cluster_split, dim3(ck_grid(n, CK_WAVES, 1u << 16)), dim3(CK_THREADS), 0, c->stream, n, c->csr_ptr.get(),
+        hipLaunchKernelGGL(k_cluster_split, dim3(lane_grid(n, LANE_WAVES, 1u << 16)), dim3(LANE_THREADS), 0, c->stream, n, c->csr_ptr.get(),
                            c->csr_ent.get(), key.get(), val.get());
         HIPCHK(c, hipGetLastError());
         int bits = 1;
@@ -300,58 +260,46 @@ struct ClusterRun {
         return CELLECTOR_OK;
     }
 
-    cellector_status set_mask(const uint8_t *host_mask)
-    {
-        have_mask = host_mask != nullptr;
-        if (have_mask && L) HIPCHK(c, hipMemcpyAsync(mask, host_mask, L, hipMemcpyHostToDevice, c->stream));
-        return CELLECTOR_OK;
-    }
-    const uint8_t *dmask() const { return have_mask ? mask.get() : nullptr; }
-
     cellector_status tables()
     {
         if (!(L * J)) return CELLECTOR_OK;
-        hipLaunchKernelGGL(k_cluster_tables, dim3(ck_grid(L * J, CK_THREADS, 0x7fffffffu)), dim3(CK_THREADS), 0, c->stream, L * J, J,
-                           theta.get(), dmask(), tab.get());
+        hipLaunchKernelGGL(k_cluster_tables, dim3(lane_grid(L * J, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * J, J,
+                           theta.get(), mask.get(), tab.get());
         HIPCHK(c, hipGetLastError());
         return CELLECTOR_OK;
     }
 
     cellector_status e_step(const double *d_temp, double div)
     {
-        const int jp = ck_jp(J);
-        const unsigned grid = ck_grid((n + 64 / jp - 1) / (64 / jp), CK_WAVES, (unsigned)c->n_cu * 8);
-#define CK_E(JP)                                                                                                                       \
-    case JP:                                                                                                                           \
-        hipLaunchKernelGGL(k_cluster_e<JP>, dim3(grid), dim3(CK_THREADS), 0, c->stream, n, J, K, c->csr_ptr.get(), c->csr_ent.get(),   \
-                           tab.get(), dmask(), d_temp, div, s.get(), w.get(), o.get(), depth.get(), cnt.get());                        \
-        break;
-        mark(0);
-        if (n) switch (jp) { CK_E(2) CK_E(4) CK_E(8) CK_E(16) CK_E(32) CK_E(64) }
-#undef CK_E
+        const int jp = lane_width(J, 2);
+        ev.mark(0, c->stream);
+        if (n)
+            lane_dispatch<2, 64>(jp, [&](auto JP) {
+                hipLaunchKernelGGL(k_cluster_e<JP>, dim3(lane_walk_grid(n, jp, c->n_cu)), dim3(LANE_THREADS), 0, c->stream, n, J, K,
+                                   c->csr_ptr.get(), c->csr_ent.get(), tab.get(), mask.get(), d_temp, div, s.get(), w.get(), o.get(),
+                                   depth.get(), cnt.get());
+            });
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_cluster_objective, dim3(R), dim3(CK_THREADS), 0, c->stream, n, R, o.get(), obj.get());
+        hipLaunchKernelGGL(k_cluster_objective, dim3(R), dim3(LANE_THREADS), 0, c->stream, n, R, o.get(), obj.get());
         HIPCHK(c, hipGetLastError());
-        mark(1);
-        open_e = timed;
+        ev.mark(1, c->stream);
+        open_e = ev.on;
         return CELLECTOR_OK;
     }
 
     cellector_status m_step(double floor, bool at)
     {
-        const int jp = ck_jp(J);
-        const unsigned grid = ck_grid((L + 64 / jp - 1) / (64 / jp), CK_WAVES, (unsigned)c->n_cu * 8);
-#define CK_M(JP)                                                                                                                       \
-    case JP:                                                                                                                           \
-        hipLaunchKernelGGL(k_cluster_m<JP>, dim3(grid), dim3(CK_THREADS), 0, c->stream, L, J, c->csc_ptr.get(), bl.get(), w.get(),     \
-                           dmask(), floor, at ? A.get() : (double *)nullptr, at ? T.get() : (double *)nullptr, theta.get());           \
-        break;
-        mark(2);
-        if (L) switch (jp) { CK_M(2) CK_M(4) CK_M(8) CK_M(16) CK_M(32) CK_M(64) }
-#undef CK_M
+        const int jp = lane_width(J, 2);
+        ev.mark(2, c->stream);
+        if (L)
+            lane_dispatch<2, 64>(jp, [&](auto JP) {
+                hipLaunchKernelGGL(k_cluster_m<JP>, dim3(lane_walk_grid(L, jp, c->n_cu)), dim3(LANE_THREADS), 0, c->stream, L, J,
+                                   c->csc_ptr.get(), bl.get(), w.get(), mask.get(), floor, at ? A.get() : (double *)nullptr,
+                                   at ? T.get() : (double *)nullptr, theta.get());
+            });
         HIPCHK(c, hipGetLastError());
-        mark(3);
-        open_m = timed;
+        ev.mark(3, c->stream);
+        open_m = ev.on;
         return CELLECTOR_OK;
     }
 };
@@ -368,12 +316,6 @@ cellector_status take_columns(cellector_ctx *c, const double *d, uint64_t rows, 
     return CELLECTOR_OK;
 }
 
-void invalidate_like_cell_ll(cellector_ctx *c)
-{
-    c->tables_prebuilt = false;  // what cellector_cell_log_likelihoods invalidates (the calls themselves use scratch of their own)
-    c->work_zeroed = false;
-}
-
 }  // namespace
 
 // one M step and the tables from its theta: w [cells][J] host; A, T, theta [J][L], tab [L][J][2] host, any may be null
@@ -382,8 +324,8 @@ cellector_status cluster_m_step_run(cellector_ctx *c, const double *w, uint32_t 
 {
     ClusterRun r{c, J, 1, J, c->nloc, c->L};
     CHK(r.alloc(false, true, A || T, false));
-    invalidate_like_cell_ll(c);
-    CHK(r.set_mask(mask));
+    invalidate_cell_ll_state(c);
+    CHK(r.mask.set(c, mask, r.L));
     if (r.n) HIPCHK(c, hipMemcpyAsync(r.w, w, r.n * J * 8, hipMemcpyHostToDevice, c->stream));
     cellector_status st = r.m_step(floor, A || T);
     if (st == CELLECTOR_OK) st = r.tables();
@@ -404,8 +346,8 @@ cellector_status cluster_e_step_run(cellector_ctx *c, const double *tab, uint32_
     const uint32_t J = K * R;
     ClusterRun r{c, K, R, J, c->nloc, c->L};
     CHK(r.alloc(true, false, false, temp != nullptr));
-    invalidate_like_cell_ll(c);
-    CHK(r.set_mask(mask));
+    invalidate_cell_ll_state(c);
+    CHK(r.mask.set(c, mask, r.L));
     if (r.L) HIPCHK(c, hipMemcpyAsync(r.tab, tab, r.L * J * 16, hipMemcpyHostToDevice, c->stream));
     if (temp && r.n) HIPCHK(c, hipMemcpyAsync(r.temp, temp, r.n * 8, hipMemcpyHostToDevice, c->stream));
     cellector_status st = r.e_step(temp ? r.temp.get() : nullptr, 0.0);
@@ -413,7 +355,7 @@ cellector_status cluster_e_step_run(cellector_ctx *c, const double *tab, uint32_
     if (st == CELLECTOR_OK && w) st = d2h(c, w, r.w, r.n * J * 8);
     if (st == CELLECTOR_OK && objective) st = d2h(c, objective, r.obj, (uint64_t)R * 8);
     (void)hipStreamSynchronize(c->stream);
-    if (r.timed && st == CELLECTOR_OK) {
+    if (r.ev.on && st == CELLECTOR_OK) {
         r.collect();
         fprintf(stderr, "[timing]   cluster_e_step: J %u E step %.3f ms\n", J, r.ms_e);
     }
@@ -430,13 +372,13 @@ cellector_status cluster_run(cellector_ctx *c, uint32_t K, uint32_t R, uint64_t 
     ClusterRun r{c, K, R, J, c->nloc, c->L};
     const uint64_t n = r.n, L = r.L;
     CHK(r.alloc(true, true, false, false));
-    invalidate_like_cell_ll(c);
-    CHK(r.set_mask(mask));
+    invalidate_cell_ll_state(c);
+    CHK(r.mask.set(c, mask, r.L));
     cellector_cluster_summary sum = {};
     std::vector<double> obj(R), prev(R);
     cellector_status st = CELLECTOR_OK;
     if (L * J) {
-        hipLaunchKernelGGL(k_cluster_start, dim3(ck_grid(L * J, CK_THREADS, 0x7fffffffu)), dim3(CK_THREADS), 0, c->stream, L * J,
+        hipLaunchKernelGGL(k_cluster_start, dim3(lane_grid(L * J, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * J,
                            mix64(seed * GOLD + GOLD), p->theta_floor, r.theta.get());
         if (hipGetLastError() != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "cluster: start launch failed");
     }
@@ -467,7 +409,7 @@ cellector_status cluster_run(cellector_ctx *c, uint32_t K, uint32_t R, uint64_t 
         return st;
     }
     r.collect();
-    if (r.timed)
+    if (r.ev.on)
         fprintf(stderr, "[timing]   cluster: K %u R %u by-locus list %.4f s, E step %.3f ms x %u, M step %.3f ms x %u, whole call %.4f s\n", K, R,
                 r.s_list, r.n_e ? r.ms_e / r.n_e : 0.0, r.n_e, r.n_m ? r.ms_m / r.n_m : 0.0, r.n_m, whole.lap());
     const double shift = (double)n * std::log((double)K);

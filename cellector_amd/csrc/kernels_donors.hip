@@ -7,35 +7,24 @@
 // and 256 B of pair table per locus, against the 16 D bytes of a table with a column per donor.
 //   k_donor_pack    gt [D][total_loci] u8 -> packed [L][W], over the used loci
 //   k_donor_tables  tab1 [L][4] and tab2 [L][16] double2 from the locus' alt / ref totals
-//   k_donor_e       rows = cells of the by-cell CSR, a group of DP lanes per cell, lane = donor (the shape of k_cluster_e: a lane
-//                   owns one (cell, donor) sum and walks the row's entries in order).  <DP, false>: the singlet sums, best, second and
-//                   the anchor; <DP, true>: the pair sums (anchor, d) and the posterior chain over the 2 D - 1 hypotheses
-//   k_donor_match   a lane per (class, donor): the class' tallies over ascending loci
+//   k_donor_e       rows = cells of the by-cell CSR, lane = donor, in the shape lane_rows.h states.  <DP, false>: the singlet sums,
+//                   best, second and the anchor; <DP, true>: the pair sums (anchor, d) and the posterior chain over the 2 D - 1
+//                   hypotheses
+//   k_donor_match   a lane per (class, donor): the class' tallies over ascending loci, the same terms in the same order
 // The same calls from genotype probabilities (three weights per donor and locus in place of a code) are the section behind
 // k_donor_match.  All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
-#include "ctx.h"
+#include "lane_rows.h"
 
 #include <cmath>
 
-#define DN_THREADS 256
-#define DN_WAVES (DN_THREADS / 64)
-#define DN_AHEAD 4  // entries whose loads are issued before the first of their ordered adds (= CK_AHEAD of kernels_cluster.hip)
 #define DN_NONE 255
 
-static inline unsigned dn_grid(uint64_t n, unsigned per_block, unsigned cap)
-{
-    uint64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 // packed[l][w]: donor d = 32 w + i at bits 2 i, from gt[d][locus_ids[l]]; the bits of donors >= D are 0
-__global__ __launch_bounds__(DN_THREADS) void k_donor_pack(uint64_t n /*L W*/, uint32_t D, uint32_t W, uint64_t TL,
-                                                           const uint64_t *__restrict__ locus_ids, const uint8_t *__restrict__ gt,
-                                                           uint64_t *__restrict__ packed)
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_pack(uint64_t n /*L W*/, uint32_t D, uint32_t W, uint64_t TL,
+                                                             const uint64_t *__restrict__ locus_ids, const uint8_t *__restrict__ gt,
+                                                             uint64_t *__restrict__ packed)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint64_t l = i / W, t = locus_ids[l];
     const uint32_t w = (uint32_t)(i % W);
@@ -48,11 +37,11 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_pack(uint64_t n /*L W*/, u
 // theta_g = (1 - ambient) e_g + ambient soup, e = {err, 0.5, 1 - err, soup}, soup = (A + 1) / ((A + R) + 2) from the locus' totals
 // (whole numbers below 2^53 held as doubles: their sum is exact).  Thread (l, 4 ga + gb): tab2 from 0.5 (theta_ga + theta_gb); the
 // diagonal is tab1 ((x + x) 0.5 == x).  A masked locus carries (0, 0).
-__global__ __launch_bounds__(DN_THREADS) void k_donor_tables(uint64_t n /*16 L*/, const double *__restrict__ s_alt, const double *__restrict__ s_ref,
-                                                             const uint8_t *__restrict__ mask /*or null*/, double err, double ambient,
-                                                             double2 *__restrict__ tab1, double2 *__restrict__ tab2)
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_tables(uint64_t n /*16 L*/, const double *__restrict__ s_alt, const double *__restrict__ s_ref,
+                                                               const uint8_t *__restrict__ mask /*or null*/, double err, double ambient,
+                                                               double2 *__restrict__ tab1, double2 *__restrict__ tab2)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint64_t l = i >> 4;
     const uint32_t ga = (uint32_t)(i >> 2) & 3u, gb = (uint32_t)i & 3u;
@@ -81,18 +70,6 @@ struct DonorTail {
     uint64_t min_loci;
 };
 
-// (value, index) maximum over the group's DP lanes, the smallest index among equal values: every lane of the wave takes part
-template <int DP>
-__device__ __forceinline__ void dn_argmax(double &v, int &idx)
-{
-#pragma unroll
-    for (int off = DP / 2; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(idx, off, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-}
-
 // The tail of a cell pass, shared by the hard and the soft kernels: acc = the lane's ordered sum, cnt = the row's entries.  Every lane of
 // the wave takes part in the shuffles, whatever its row and donor.
 // !PAIR: s = acc; u_d = s_d + lp_d; best = argmax u, second = argmax over d != best (smallest d on ties); the anchor, unless given
@@ -110,10 +87,10 @@ __device__ __forceinline__ void dn_tail(uint64_t row, bool have, int col, bool c
         double v = col_ok ? acc + prior : -INFINITY;
         int b = col_ok ? col : 0x7fff;
         const double u = v;
-        dn_argmax<DP>(v, b);
+        lane_argmax<DP>(v, b);
         double v2 = col_ok && col != b ? u : -INFINITY;
         int b2 = col_ok && col != b ? col : 0x7fff;
-        dn_argmax<DP>(v2, b2);
+        lane_argmax<DP>(v2, b2);
         if (have && col_ok) s[row * D + col] = acc;
         if (have && col == 0) {
             best[row] = (uint8_t)b;
@@ -131,7 +108,7 @@ __device__ __forceinline__ void dn_tail(uint64_t row, bool have, int col, bool c
         if (pair_ok) y = acc + tail.log_pair;
         double m = fmax(x, y);
         int dummy = 0;
-        dn_argmax<DP>(m, dummy);
+        lane_argmax<DP>(m, dummy);
         if (!have) m = 0.0;
         const double ex = exp(x - m), ey = exp(y - m);  // a lane that is no hypothesis: exp(-inf) = 0, and den + 0 is den
         double den = 0.0;
@@ -142,7 +119,7 @@ __device__ __forceinline__ void dn_tail(uint64_t row, bool have, int col, bool c
         for (uint32_t d = 0; d < D; d++) dp = dp + __shfl(wp, (base + (int)d) & 63, 64);
         double vy = y;
         int bp = pair_ok ? col : 0x7fff;
-        dn_argmax<DP>(vy, bp);
+        lane_argmax<DP>(vy, bp);
         const int b = have ? (int)best[row] : 0;
         const double wb = __shfl(w, (base + b) & 63, 64);
         if (have && col_ok) {
@@ -161,25 +138,21 @@ __device__ __forceinline__ void dn_tail(uint64_t row, bool have, int col, bool c
 // The cell pass.  A group of DP lanes per cell, lane = donor d.  acc = the ordered sum of (alt la + ref lb) over the row's entries at
 // unmasked loci, (la, lb) = the table row of the donor's genotype (PAIR: of the anchor's and the donor's); then dn_tail.
 template <int DP, bool PAIR>
-__global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_t D, uint32_t W, const uint64_t *__restrict__ row_ptr,
-                                                        const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
-                                                        const double2 *__restrict__ tab, const uint8_t *__restrict__ mask /*or null*/,
-                                                        const double *__restrict__ lp /*[D]*/, DonorTail tail, bool anchor_given,
-                                                        uint8_t *__restrict__ anchor, double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/,
-                                                        uint8_t *__restrict__ best, uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out,
-                                                        double *__restrict__ p_out, double *__restrict__ post, double *__restrict__ ppost,
-                                                        double *__restrict__ dp_out, uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_e(uint64_t n_rows, uint32_t D, uint32_t W, const uint64_t *__restrict__ row_ptr,
+                                                          const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
+                                                          const double2 *__restrict__ tab, const uint8_t *__restrict__ mask /*or null*/,
+                                                          const double *__restrict__ lp /*[D]*/, DonorTail tail, bool anchor_given,
+                                                          uint8_t *__restrict__ anchor, double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/,
+                                                          uint8_t *__restrict__ best, uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out,
+                                                          double *__restrict__ p_out, double *__restrict__ post, double *__restrict__ ppost,
+                                                          double *__restrict__ dp_out, uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
 {
-    constexpr int RPW = 64 / DP;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / DP, col = lane % DP;
-    const bool col_ok = (uint32_t)col < D;
-    const int base = sub * DP;
+    const LaneGeom<DP> geo(n_rows, D);
+    const int col = geo.col;
+    const bool col_ok = geo.ok;
     const uint32_t my_word = col_ok ? (uint32_t)col >> 5 : 0u, my_shift = 2u * ((uint32_t)col & 31u);
-    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * DN_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * DN_WAVES;
-    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
-        const uint64_t row = g * RPW + sub;
+    for (uint64_t g = geo.wave0; g < geo.n_groups; g += geo.n_waves) {
+        const uint64_t row = geo.row(g);
         const bool have = row < n_rows;
         const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
         uint32_t a = 0;
@@ -188,12 +161,13 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_
         const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        for (uint64_t i = beg; i < end; i += DN_AHEAD) {
-            uint64_t en[DN_AHEAD];
-            double2 t[DN_AHEAD];
-            bool use[DN_AHEAD];
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_ambient_e and k_donor_match as well
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            double2 t[LANE_AHEAD];
+            bool use[LANE_AHEAD];
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 const bool in = i + q < end;
                 en[q] = in ? ent[i + q] : 0ull;
                 const uint64_t l = ENT_IDX(en[q]);
@@ -210,7 +184,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_
                 }
             }
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 if (!use[q]) continue;
                 const uint32_t al = ENT_ALT(en[q]), re = ENT_REF(en[q]);
                 const double pa = (double)al * t[q].x, pb = (double)re * t[q].y;
@@ -219,8 +193,8 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_e(uint64_t n_rows, uint32_
                 cnt++;
             }
         }
-        dn_tail<DP, PAIR>(row, have, col, col_ok, base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out, p_out, post,
-                          ppost, dp_out, best_pair, status);
+        dn_tail<DP, PAIR>(row, have, col, col_ok, geo.base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out,
+                          p_out, post, ppost, dp_out, best_pair, status);
     }
 }
 
@@ -236,12 +210,13 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
     const uint32_t my_word = d >> 5, my_shift = 2u * (d & 31u);
     const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
     double acc = 0.0;
-    for (uint64_t l0 = 0; l0 < L; l0 += DN_AHEAD) {
-        double av[DN_AHEAD], rv[DN_AHEAD];
-        double2 t[DN_AHEAD];
-        bool use[DN_AHEAD];
+    // the entry loop of lane_rows.h over loci: a fix here belongs in k_cluster_e, k_donor_e and k_ambient_e as well
+    for (uint64_t l0 = 0; l0 < L; l0 += LANE_AHEAD) {
+        double av[LANE_AHEAD], rv[LANE_AHEAD];
+        double2 t[LANE_AHEAD];
+        bool use[LANE_AHEAD];
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++) {
+        for (int q = 0; q < LANE_AHEAD; q++) {
             const uint64_t l = l0 + q;
             use[q] = l < L && (!mask || mask[l] != 0);
             av[q] = rv[q] = 0.0;
@@ -253,7 +228,7 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
             }
         }
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++) {
+        for (int q = 0; q < LANE_AHEAD; q++) {
             if (!use[q]) continue;
             const double pa = av[q] * t[q].x, pb = rv[q] * t[q].y;
             const double term = pa + pb;
@@ -268,19 +243,19 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
 // its twin.
 //   k_donor_weights  gp [D][total_loci][3] f32 -> w [L][D][3] f64 and kind [L][D] u8 over the used loci: kind 0, 1, 2 = the one-hot row
 //                    of that genotype, 3 = no call, 4 = a soft row
-//   k_donor_gp_e     the shape of k_donor_e.  A lane's entry is a lookup (kind < 4: the hard call's bits) or the mixture over the
-//                    genotypes of positive weight, m + log(sum w exp(t - m)).  The terms of DN_AHEAD entries are formed first, the
-//                    lookups of all four in flight together, then exp / log and all where a row is soft: they depend on nothing of
-//                    the sum.  Then they are added in order.
+//   k_donor_gp_e     k_donor_e's geometry and tail around a loop in three phases.  A lane's entry is a lookup (kind < 4:
+//                    the hard call's bits) or the mixture over the genotypes of positive weight, m + log(sum w exp(t - m)).  The terms
+//                    of LANE_AHEAD entries are formed first, the lookups of all four in flight together, then exp / log and all where
+//                    a row is soft: they depend on nothing of the sum.  Then they are added in order.
 //   k_donor_gp_match a lane per (class, donor), the same term from the class' tallies
 #define DN_SOFT 4
 
 // thread (l, d).  The host has validated every row; a row it should have refused is counted in bad and held as a no-call.
-__global__ __launch_bounds__(DN_THREADS) void k_donor_weights(uint64_t n /*L D*/, uint32_t D, uint64_t TL, const uint64_t *__restrict__ locus_ids,
-                                                              const float *__restrict__ gp, double *__restrict__ w, uint8_t *__restrict__ kind,
-                                                              uint32_t *__restrict__ bad)
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_weights(uint64_t n /*L D*/, uint32_t D, uint64_t TL, const uint64_t *__restrict__ locus_ids,
+                                                                const float *__restrict__ gp, double *__restrict__ w, uint8_t *__restrict__ kind,
+                                                                uint32_t *__restrict__ bad)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint64_t l = i / D, t = locus_ids[l];
     const uint32_t d = (uint32_t)(i % D);
@@ -383,25 +358,21 @@ __device__ __forceinline__ double dn_gp_soft(uint64_t l, uint32_t D, uint32_t d,
 }
 
 template <int DP, bool PAIR>
-__global__ __launch_bounds__(DN_THREADS) void k_donor_gp_e(uint64_t n_rows, uint32_t D, const uint64_t *__restrict__ row_ptr,
-                                                           const uint64_t *__restrict__ ent, const double *__restrict__ w /*[L][D][3]*/,
-                                                           const uint8_t *__restrict__ kind /*[L][D]*/, const double2 *__restrict__ tab,
-                                                           const uint8_t *__restrict__ mask /*or null*/, const double *__restrict__ lp /*[D]*/,
-                                                           DonorTail tail, bool anchor_given, uint8_t *__restrict__ anchor,
-                                                           double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/, uint8_t *__restrict__ best,
-                                                           uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out, double *__restrict__ p_out,
-                                                           double *__restrict__ post, double *__restrict__ ppost, double *__restrict__ dp_out,
-                                                           uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_gp_e(uint64_t n_rows, uint32_t D, const uint64_t *__restrict__ row_ptr,
+                                                             const uint64_t *__restrict__ ent, const double *__restrict__ w /*[L][D][3]*/,
+                                                             const uint8_t *__restrict__ kind /*[L][D]*/, const double2 *__restrict__ tab,
+                                                             const uint8_t *__restrict__ mask /*or null*/, const double *__restrict__ lp /*[D]*/,
+                                                             DonorTail tail, bool anchor_given, uint8_t *__restrict__ anchor,
+                                                             double *__restrict__ s /*[rows][D]: !PAIR out, PAIR in*/, uint8_t *__restrict__ best,
+                                                             uint8_t *__restrict__ second, uint32_t *__restrict__ cnt_out, double *__restrict__ p_out,
+                                                             double *__restrict__ post, double *__restrict__ ppost, double *__restrict__ dp_out,
+                                                             uint8_t *__restrict__ best_pair, uint8_t *__restrict__ status)
 {
-    constexpr int RPW = 64 / DP;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / DP, col = lane % DP;
-    const bool col_ok = (uint32_t)col < D;
-    const int base = sub * DP;
-    const uint64_t n_groups = (n_rows + RPW - 1) / RPW;
-    const uint64_t wave0 = (uint64_t)blockIdx.x * DN_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * DN_WAVES;
-    for (uint64_t g = wave0; g < n_groups; g += n_waves) {
-        const uint64_t row = g * RPW + sub;
+    const LaneGeom<DP> geo(n_rows, D);
+    const int col = geo.col;
+    const bool col_ok = geo.ok;
+    for (uint64_t g = geo.wave0; g < geo.n_groups; g += geo.n_waves) {
+        const uint64_t row = geo.row(g);
         const bool have = row < n_rows;
         const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
         uint32_t a = 0;
@@ -410,14 +381,14 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_gp_e(uint64_t n_rows, uint
         const bool mine = PAIR && col_ok && (uint32_t)col == a;  // the anchor's own column: a copy of its singlet sum, no pair
         double acc = 0.0;
         uint32_t cnt = 0;
-        for (uint64_t i = beg; i < end; i += DN_AHEAD) {
-            uint64_t en[DN_AHEAD];
-            uint32_t ka[DN_AHEAD], kd[DN_AHEAD];
-            double term[DN_AHEAD];
-            bool use[DN_AHEAD], live[DN_AHEAD];
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            uint32_t ka[LANE_AHEAD], kd[LANE_AHEAD];
+            double term[LANE_AHEAD];
+            bool use[LANE_AHEAD], live[LANE_AHEAD];
             // the kinds, then the lookups of all four entries (k_donor_e's loads, in flight together), then the mixtures where a row is soft
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 const bool in = i + q < end;
                 en[q] = in ? ent[i + q] : 0ull;
                 const uint64_t l = ENT_IDX(en[q]);
@@ -427,26 +398,26 @@ __global__ __launch_bounds__(DN_THREADS) void k_donor_gp_e(uint64_t n_rows, uint
                 ka[q] = PAIR && live[q] ? kind[l * D + a] : 0u;
             }
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 double2 t = make_double2(0.0, 0.0);
                 if (live[q]) t = tab[dn_gp_row<PAIR>(ENT_IDX(en[q]), ka[q], kd[q])];
                 const double pa = (double)ENT_ALT(en[q]) * t.x, pb = (double)ENT_REF(en[q]) * t.y;
                 term[q] = pa + pb;
             }
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++)
+            for (int q = 0; q < LANE_AHEAD; q++)
                 if (live[q] && (kd[q] == DN_SOFT || ka[q] == DN_SOFT))
                     term[q] = dn_gp_soft<PAIR>(ENT_IDX(en[q]), D, (uint32_t)col, a, ka[q], kd[q], w, tab, (double)ENT_ALT(en[q]), (double)ENT_REF(en[q]));
 #pragma unroll
-            for (int q = 0; q < DN_AHEAD; q++) {
+            for (int q = 0; q < LANE_AHEAD; q++) {
                 if (!use[q]) continue;
                 acc = acc + term[q];
                 cnt++;
             }
         }
         if (mine && have) acc = s[row * D + col];
-        dn_tail<DP, PAIR>(row, have, col, col_ok, base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out, p_out, post,
-                          ppost, dp_out, best_pair, status);
+        dn_tail<DP, PAIR>(row, have, col, col_ok, geo.base, D, a, acc, cnt, lp, tail, anchor_given, anchor, s, best, second, cnt_out,
+                          p_out, post, ppost, dp_out, best_pair, status);
     }
 }
 
@@ -460,12 +431,12 @@ __global__ __launch_bounds__(64) void k_donor_gp_match(uint64_t L, uint32_t D, c
     if (d >= D) return;
     const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
     double acc = 0.0;
-    for (uint64_t l0 = 0; l0 < L; l0 += DN_AHEAD) {
-        double av[DN_AHEAD], rv[DN_AHEAD], term[DN_AHEAD];
-        uint32_t kd[DN_AHEAD];
-        bool use[DN_AHEAD];
+    for (uint64_t l0 = 0; l0 < L; l0 += LANE_AHEAD) {
+        double av[LANE_AHEAD], rv[LANE_AHEAD], term[LANE_AHEAD];
+        uint32_t kd[LANE_AHEAD];
+        bool use[LANE_AHEAD];
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++) {
+        for (int q = 0; q < LANE_AHEAD; q++) {
             const uint64_t l = l0 + q;
             use[q] = l < L && (!mask || mask[l] != 0);
             av[q] = use[q] ? (double)ak[l] : 0.0;
@@ -473,17 +444,17 @@ __global__ __launch_bounds__(64) void k_donor_gp_match(uint64_t L, uint32_t D, c
             kd[q] = use[q] ? kind[l * D + d] : 0u;
         }
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++) {
+        for (int q = 0; q < LANE_AHEAD; q++) {
             double2 t = make_double2(0.0, 0.0);
             if (use[q]) t = tab1[dn_gp_row<false>(l0 + q, 0u, kd[q])];
             const double pa = av[q] * t.x, pb = rv[q] * t.y;
             term[q] = pa + pb;
         }
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++)
+        for (int q = 0; q < LANE_AHEAD; q++)
             if (use[q] && kd[q] == DN_SOFT) term[q] = dn_gp_soft<false>(l0 + q, D, d, 0u, 0u, kd[q], w, tab1, av[q], rv[q]);
 #pragma unroll
-        for (int q = 0; q < DN_AHEAD; q++) {
+        for (int q = 0; q < LANE_AHEAD; q++) {
             if (!use[q]) continue;
             acc = acc + term[q];
         }
@@ -494,19 +465,13 @@ __global__ __launch_bounds__(64) void k_donor_gp_match(uint64_t L, uint32_t D, c
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
 
-int dn_dp(uint32_t D)
-{
-    int dp = 2;
-    while ((uint32_t)dp < D) dp <<= 1;
-    return dp;
-}
-
 // the scratch of one call; alloc() makes all of it before anything is launched
 struct DonorRun {
     cellector_ctx *c;
     uint32_t D, W;
     uint64_t n, L, TL;
-    DevBuf<uint8_t> gt, mask;       // [D][TL], [L]
+    DevBuf<uint8_t> gt;             // [D][TL]
+    LociMask mask;                  // [L]
     DevBuf<uint64_t> packed;        // [L][W]
     DevBuf<double2> tab1, tab2;     // [L][4], [L][16]
     DevBuf<double> lp;              // [D]
@@ -520,8 +485,8 @@ struct DonorRun {
     DevBuf<double> w;               // [L][D][3]
     DevBuf<uint8_t> kind;           // [L][D]
     DevBuf<uint32_t> bad;           // [1]
-    bool have_mask = false, soft = false;
-    const bool timed = getenv("CELLECTOR_TIMING") != nullptr;
+    bool soft = false;
+    EventMarks<3> ev;               // before the singlet pass, between the two passes, behind the pair pass
 
     cellector_status alloc(bool cells, uint32_t K, bool soft_calls = false)
     {
@@ -535,7 +500,7 @@ struct DonorRun {
             CHK(dev_alloc(c, &gt, (uint64_t)D * TL));
             CHK(dev_alloc(c, &packed, L * W));
         }
-        CHK(dev_alloc(c, &mask, L));
+        CHK(dev_alloc(c, &mask.buf, L));
         CHK(dev_alloc(c, &tab1, L * 4));
         CHK(dev_alloc(c, &tab2, L * 16));
         if (cells) {
@@ -554,27 +519,24 @@ struct DonorRun {
         return CELLECTOR_OK;
     }
 
-    const uint8_t *dmask() const { return have_mask ? mask.get() : nullptr; }
-
     // one upload of the calls (gt [D][TL] u8, or gp [D][TL][3] f32 of a soft run), the packing or the weights, and the tables
     cellector_status prepare(const void *host_calls, const uint8_t *host_mask, const cellector_donor_params *prm)
     {
-        have_mask = host_mask != nullptr;
-        if (have_mask && L) HIPCHK(c, hipMemcpyAsync(mask, host_mask, L, hipMemcpyHostToDevice, c->stream));
+        CHK(mask.set(c, host_mask, L));
         if (soft) HIPCHK(c, hipMemsetAsync(bad, 0, 4, c->stream));
         if (!L) return CELLECTOR_OK;
         if (soft) {
             HIPCHK(c, hipMemcpyAsync(gp, host_calls, (uint64_t)D * TL * 12, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_donor_weights, dim3(dn_grid(L * D, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * D, D, TL,
+            hipLaunchKernelGGL(k_donor_weights, dim3(lane_grid(L * D, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * D, D, TL,
                                c->locus_ids.get(), gp.get(), w.get(), kind.get(), bad.get());
         } else {
             HIPCHK(c, hipMemcpyAsync(gt, host_calls, (uint64_t)D * TL, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * W, D, W, TL,
+            hipLaunchKernelGGL(k_donor_pack, dim3(lane_grid(L * W, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * W, D, W, TL,
                                c->locus_ids.get(), gt.get(), packed.get());
         }
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_donor_tables, dim3(dn_grid(L * 16, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, L * 16,
-                           c->s_alt.get(), c->s_ref.get(), dmask(), prm->err, prm->ambient, tab1.get(), tab2.get());
+        hipLaunchKernelGGL(k_donor_tables, dim3(lane_grid(L * 16, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * 16,
+                           c->s_alt.get(), c->s_ref.get(), mask.get(), prm->err, prm->ambient, tab1.get(), tab2.get());
         HIPCHK(c, hipGetLastError());
         return CELLECTOR_OK;
     }
@@ -582,34 +544,30 @@ struct DonorRun {
     cellector_status pass(bool pair, bool anchor_given, const DonorTail &tail)
     {
         if (!n) return CELLECTOR_OK;
-        const int dpw = dn_dp(D);
-        const unsigned grid = dn_grid((n + 64 / dpw - 1) / (64 / dpw), DN_WAVES, (unsigned)c->n_cu * 8);
-#define DN_E(DP, PAIR)                                                                                                                 \
-    hipLaunchKernelGGL((k_donor_e<DP, PAIR>), dim3(grid), dim3(DN_THREADS), 0, c->stream, n, D, W, c->csr_ptr.get(), c->csr_ent.get(), \
-                       packed.get(), PAIR ? tab2.get() : tab1.get(), dmask(), lp.get(), tail, anchor_given, anchor.get(), s.get(),     \
-                       best.get(), second.get(), cnt.get(), p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get())
-#define DN_CASE(DP)                                                                                                                    \
-    case DP:                                                                                                                           \
-        if (pair) DN_E(DP, true);                                                                                                      \
-        else DN_E(DP, false);                                                                                                          \
-        break;
-#define DN_GP_E(DP, PAIR)                                                                                                              \
-    hipLaunchKernelGGL((k_donor_gp_e<DP, PAIR>), dim3(grid), dim3(DN_THREADS), 0, c->stream, n, D, c->csr_ptr.get(), c->csr_ent.get(),   \
-                       w.get(), kind.get(), PAIR ? tab2.get() : tab1.get(), dmask(), lp.get(), tail, anchor_given, anchor.get(), s.get(), \
-                       best.get(), second.get(), cnt.get(), p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get())
-#define DN_GP_CASE(DP)                                                                                                                 \
-    case DP:                                                                                                                           \
-        if (pair) DN_GP_E(DP, true);                                                                                                   \
-        else DN_GP_E(DP, false);                                                                                                       \
-        break;
-        if (soft) switch (dpw) { DN_GP_CASE(2) DN_GP_CASE(4) DN_GP_CASE(8) DN_GP_CASE(16) DN_GP_CASE(32) DN_GP_CASE(64) }
-        else switch (dpw) { DN_CASE(2) DN_CASE(4) DN_CASE(8) DN_CASE(16) DN_CASE(32) DN_CASE(64) }
-#undef DN_GP_CASE
-#undef DN_GP_E
-#undef DN_CASE
-#undef DN_E
+        if (pair) launch_pass(std::true_type(), anchor_given, tail);
+        else launch_pass(std::false_type(), anchor_given, tail);
         HIPCHK(c, hipGetLastError());
         return CELLECTOR_OK;
+    }
+
+    // the one launch of a pass: the hard or the soft kernel at the run's width
+    template <typename Pair>
+    void launch_pass(Pair, bool anchor_given, const DonorTail &tail)
+    {
+        constexpr bool PAIR = Pair::value;
+        const int dpw = lane_width(D, 2);
+        const dim3 grid(lane_walk_grid(n, dpw, c->n_cu)), block(LANE_THREADS);
+        const double2 *tab = PAIR ? tab2.get() : tab1.get();
+        lane_dispatch<2, 64>(dpw, [&](auto DP) {
+            if (soft)
+                hipLaunchKernelGGL((k_donor_gp_e<DP, PAIR>), grid, block, 0, c->stream, n, D, c->csr_ptr.get(), c->csr_ent.get(), w.get(),
+                                   kind.get(), tab, mask.get(), lp.get(), tail, anchor_given, anchor.get(), s.get(), best.get(), second.get(),
+                                   cnt.get(), p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get());
+            else
+                hipLaunchKernelGGL((k_donor_e<DP, PAIR>), grid, block, 0, c->stream, n, D, W, c->csr_ptr.get(), c->csr_ent.get(), packed.get(),
+                                   tab, mask.get(), lp.get(), tail, anchor_given, anchor.get(), s.get(), best.get(), second.get(), cnt.get(),
+                                   p.get(), post.get(), ppost.get(), dp.get(), best_pair.get(), status.get());
+        });
     }
 
     // a soft run: the weights as the device holds them, and the kernel's own count of rows the host's check should have refused
@@ -633,12 +591,6 @@ struct DonorRun {
     }
 };
 
-void donors_invalidate(cellector_ctx *c)
-{
-    c->tables_prebuilt = false;  // what cellector_cell_log_likelihoods invalidates (the calls themselves use scratch of their own)
-    c->work_zeroed = false;
-}
-
 }  // namespace
 
 // the packing alone, for the calls of other files that score cells against packed genotypes (kernels_ambient.hip): d_gt [D][TL] and
@@ -647,7 +599,7 @@ cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *
 {
     const uint32_t W = (D + 31) / 32;
     if (!c->L) return CELLECTOR_OK;
-    hipLaunchKernelGGL(k_donor_pack, dim3(dn_grid(c->L * W, DN_THREADS, 0x7fffffffu)), dim3(DN_THREADS), 0, c->stream, c->L * W, D, W,
+    hipLaunchKernelGGL(k_donor_pack, dim3(lane_grid(c->L * W, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, c->L * W, D, W,
                        c->total_loci, c->locus_ids.get(), d_gt, d_packed);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
@@ -659,7 +611,7 @@ cellector_status donor_tables_run(cellector_ctx *c, const uint8_t *gt, uint32_t 
 {
     DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
     CHK(r.alloc(false, 0));
-    donors_invalidate(c);
+    invalidate_cell_ll_state(c);
     cellector_status st = r.prepare(gt, mask, prm);
     if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, packed);
     (void)hipStreamSynchronize(c->stream);  // (nothing of the scratch may be in use when it goes)
@@ -671,7 +623,7 @@ cellector_status donor_weights_run(cellector_ctx *c, const float *gp, uint32_t D
 {
     DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
     CHK(r.alloc(false, 0, true));
-    donors_invalidate(c);
+    invalidate_cell_ll_state(c);
     cellector_donor_params prm;
     cellector_donor_default_params(&prm);
     cellector_status st = r.prepare(gp, nullptr, &prm);
@@ -693,21 +645,18 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, const
     const uint64_t n = r.n;
     CHK(r.alloc(true, 0, gp != nullptr));
     std::vector<uint8_t> h_status(n), h_best(n);
-    donors_invalidate(c);
+    invalidate_cell_ll_state(c);
     const DonorTail tail = {log_singlet, log_pair, prm->posterior_threshold, prm->min_loci};
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (r.timed)
-        for (hipEvent_t &e : ev) (void)hipEventCreate(&e);
     cellector_status st = r.prepare(gp ? (const void *)gp : (const void *)gt, mask, prm);
     if (st == CELLECTOR_OK && hipMemcpyAsync(r.lp, log_prior, (uint64_t)D * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the priors failed");
     if (st == CELLECTOR_OK && anchor && n && hipMemcpyAsync(r.anchor, anchor, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the anchors failed");
-    if (ev[0]) (void)hipEventRecord(ev[0], c->stream);
+    r.ev.mark(0, c->stream);
     if (st == CELLECTOR_OK) st = r.pass(false, anchor != nullptr, tail);
-    if (ev[1]) (void)hipEventRecord(ev[1], c->stream);
+    r.ev.mark(1, c->stream);
     if (st == CELLECTOR_OK) st = r.pass(true, anchor != nullptr, tail);
-    if (ev[2]) (void)hipEventRecord(ev[2], c->stream);
+    r.ev.mark(2, c->stream);
     const uint64_t nD = n * D;
     if (st == CELLECTOR_OK && ll) st = d2h(c, ll, r.s, nD * 8);
     if (st == CELLECTOR_OK && pair_ll) st = d2h(c, pair_ll, r.p, nD * 8);
@@ -723,14 +672,9 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, const
     if (st == CELLECTOR_OK) st = r.fetch_tables(tab1, tab2, gp ? nullptr : packed);
     if (st == CELLECTOR_OK && gp) st = r.fetch_weights(nullptr, nullptr);
     (void)hipStreamSynchronize(c->stream);
-    if (r.timed && st == CELLECTOR_OK) {
-        float ms1 = 0.f, ms2 = 0.f;
-        if (ev[0] && ev[1] && ev[2] && hipEventElapsedTime(&ms1, ev[0], ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&ms2, ev[1], ev[2]) == hipSuccess)
-            fprintf(stderr, "[timing]   donors%s: D %u singlet pass %.3f ms, pair pass %.3f ms, whole call %.4f s\n", gp ? " (gp)" : "", D, ms1, ms2, whole.lap());
-    }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
+    float ms1 = 0.f, ms2 = 0.f;
+    if (st == CELLECTOR_OK && r.ev.ms(0, 1, &ms1) && r.ev.ms(1, 2, &ms2))
+        fprintf(stderr, "[timing]   donors%s: D %u singlet pass %.3f ms, pair pass %.3f ms, whole call %.4f s\n", gp ? " (gp)" : "", D, ms1, ms2, whole.lap());
     if (st != CELLECTOR_OK) return st;
     cellector_donor_summary sum = {};
     for (uint64_t i = 0; i < n; i++) {
@@ -758,7 +702,7 @@ cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32
     std::vector<uint64_t> h_alt((uint64_t)K * L), h_ref((uint64_t)K * L), h_cells(K);
     std::vector<double> h_ll((uint64_t)K * D, 0.0);
     CHK(classes_tallies_run(c, labels, K, nullptr, h_cells.data(), h_alt.data(), h_ref.data(), nullptr, nullptr));
-    donors_invalidate(c);
+    invalidate_cell_ll_state(c);
     cellector_status st = r.prepare(gp ? (const void *)gp : (const void *)gt, mask, prm);
     if (st == CELLECTOR_OK && L) {
         if (hipMemcpyAsync(r.alt, h_alt.data(), (uint64_t)K * L * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -768,10 +712,10 @@ cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32
     if (st == CELLECTOR_OK) {
         if (gp)
             hipLaunchKernelGGL(k_donor_gp_match, dim3(K), dim3(64), 0, c->stream, L, D, r.alt.get(), r.ref.get(), r.w.get(), r.kind.get(),
-                               r.tab1.get(), r.dmask(), r.ll.get());
+                               r.tab1.get(), r.mask.get(), r.ll.get());
         else
             hipLaunchKernelGGL(k_donor_match, dim3(K), dim3(64), 0, c->stream, L, D, r.W, r.alt.get(), r.ref.get(), r.packed.get(),
-                               r.tab1.get(), r.dmask(), r.ll.get());
+                               r.tab1.get(), r.mask.get(), r.ll.get());
         if (hipGetLastError() != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "match_donors: launch failed");
     }
     if (st == CELLECTOR_OK) st = d2h(c, h_ll.data(), r.ll, (uint64_t)K * D * 8);

@@ -165,7 +165,7 @@ def compare_tab(theta, mask, got_tab):
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------------
-COLUMNS = ((2, 1), (3, 1), (16, 3), (4, 16))  # (K, R): J = 2, 3, 48, 64
+COLUMNS = ((2, 1), (3, 1), (5, 1), (4, 3), (8, 3), (16, 3), (4, 16))  # (K, R): J = 2, 3, 5, 12, 24, 48, 64: every lane width 2 ... 64
 _hand = {}
 
 

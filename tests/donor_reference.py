@@ -257,7 +257,7 @@ def match_reference(alt, ref, tab1, gt_used, mask=None):
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------------
-DONORS = (1, 2, 3, 5, 31, 32, 33, 64)
+DONORS = (1, 2, 3, 5, 9, 16, 31, 32, 33, 64)  # every lane width 2 ... 64
 CASE_L, CASE_N = 487, 677  # neither a multiple of 64; 677 is odd: no multiple of any rows-per-wave
 _case = {}
 

@@ -2,8 +2,8 @@
 csrc/kernels_donors.hip) on both engines, against the numpy twin cellector_amd/donors.py and tests/donor_reference.py.
 
 The matrix is donor_reference.case_matrix(): 677 cells x 487 loci, rows of 0, 1 ... 9 entries around the prefetch depth (a few up to
-18), repeated pairs, a cell count no rows-per-wave divides.  D = 1, 2, 3, 5, 31, 32, 33, 64: not powers of two, the edge of the
-packed word, the full wave; a donor and a locus without any call.
+18), repeated pairs, a cell count no rows-per-wave divides.  D = 1, 2, 3, 5, 9, 16, 31, 32, 33, 64: every lane width, counts that
+are no power of two, the edge of the packed word, the full wave; a donor and a locus without any call.
 
 Where the order of the operations is fixed the claim is exact: the packed words equal the definition's, the singlet, pair and match
 sums equal the twin's fed the device's tables bit for bit (tobytes), the (x + x) / 2 column is the singlet sum's bits.  What passes

@@ -2,7 +2,8 @@
 cellector_match_donors_gp; csrc/kernels_donors.hip) on both engines, against the hard calls, the numpy twin (cellector_amd/donors.py,
 soft_*) and tests/donor_gp_reference.py.
 
-The matrix is donor_reference.case_matrix() (677 cells x 487 loci) with D = 1, 2, 3, 5, 31, 32, 33, 64, as the hard calls' tests.
+The matrix is donor_reference.case_matrix() (677 cells x 487 loci) with D = 1, 2, 3, 5, 9, 16, 31, 32, 33, 64, as the hard calls'
+tests.
 
 What involves no exp or log is exact: the weights and kinds equal the twin's bit for bit; with the one-hot of a gt every output of the
 soft calls is the hard calls' bytes; under soft rows the columns of the donors that are one-hot or no-call throughout are the twin's
