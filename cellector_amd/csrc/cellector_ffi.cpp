@@ -1710,6 +1710,25 @@ cellector_status cellector_donor_tables(cellector_ctx *c, const uint8_t *gt, uin
     return donor_tables_run(c, gt, n_donors, &prm, mask, tab1, tab2, packed);
 }
 
+// the prior and the anchors of a cell call; lp [64]: the caller's prior, or zeros
+static cellector_status donor_prior_anchor_check(cellector_ctx *c, const char *what, uint32_t D, const double *log_prior, const uint8_t *anchor,
+                                                 double *lp)
+{
+    bool any = !log_prior;
+    for (uint32_t d = 0; log_prior && d < D; d++) {
+        if (std::isnan(log_prior[d]) || log_prior[d] == INFINITY)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior[%u] = %g is neither a finite value nor -inf", what, d, log_prior[d]);
+        any = any || log_prior[d] != -INFINITY;
+        lp[d] = log_prior[d];
+    }
+    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior is -inf for every donor", what);
+    for (uint64_t i = 0; anchor && i < c->nloc; i++)
+        if (anchor[i] >= D)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: anchor of cell %llu is %u, not below the %u donors", what, (unsigned long long)i,
+                            (unsigned)anchor[i], D);
+    return CELLECTOR_OK;
+}
+
 // cellector_donor_posteriors (gp null) and cellector_donor_posteriors_gp (gt null): the same checks, the same run
 static cellector_status donor_posteriors_call(cellector_ctx *c, const char *what, const uint8_t *gt, const float *gp, uint32_t n_donors,
                                               const cellector_donor_params *p, const double *log_prior, const uint8_t *anchor,
@@ -1726,18 +1745,7 @@ static cellector_status donor_posteriors_call(cellector_ctx *c, const char *what
     else CHK(donor_call_check(c, what, gt, n_donors, &prm));
     const uint32_t D = n_donors;
     double lp[64] = {};
-    bool any = !log_prior;
-    for (uint32_t d = 0; log_prior && d < D; d++) {
-        if (std::isnan(log_prior[d]) || log_prior[d] == INFINITY)
-            return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior[%u] = %g is neither a finite value nor -inf", what, d, log_prior[d]);
-        any = any || log_prior[d] != -INFINITY;
-        lp[d] = log_prior[d];
-    }
-    if (!any) return ctx_fail(c, CELLECTOR_EINVAL, "%s: log_prior is -inf for every donor", what);
-    for (uint64_t i = 0; anchor && i < c->nloc; i++)
-        if (anchor[i] >= D)
-            return ctx_fail(c, CELLECTOR_EINVAL, "%s: anchor of cell %llu is %u, not below the %u donors", what, (unsigned long long)i,
-                            (unsigned)anchor[i], D);
+    CHK(donor_prior_anchor_check(c, what, D, log_prior, anchor, lp));
     const double log_singlet = std::log(1.0 - prm.doublet_rate);
     const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
     SETDEV(c);
@@ -1767,6 +1775,55 @@ cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels,
     CHK(donor_args_check(c, "match_donors", gt, n_donors, &prm));
     SETDEV(c);
     return donor_match_run(c, labels, n_classes, gt, nullptr, n_donors, &prm, mask, ll, best, margin, cells);
+}
+
+// ---- the fit of the called hypothesis: k_donor_moments and k_donor_fit of kernels_donors.hip -------------------------------------
+cellector_status cellector_donor_fit_default_params(cellector_donor_fit_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->iqr_multiple = 3.0;
+    out->min_cells = 8;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_donor_moment_tables(cellector_ctx *c, const cellector_donor_params *p, const uint8_t *mask, double *mom1, double *mom2)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    CHK(locus_moments_scope(c, "donor_moment_tables"));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "donor_moment_tables: iteration in flight (finish it with cellector_em_finish)");
+    CHK(donor_params_check(c, "donor_moment_tables", &prm /*(the tables depend on no donor)*/, "gt", 1, &prm));
+    SETDEV(c);
+    return donor_moment_tables_run(c, &prm, mask, mom1, mom2);
+}
+
+cellector_status cellector_donor_fit(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *p,
+                                     const cellector_donor_fit_params *fit, const double *log_prior, const uint8_t *anchor, const uint8_t *mask,
+                                     double *fit_e, double *fit_v, double *pair_e, double *pair_v, double *z, double *pair_z, double *call_z,
+                                     uint8_t *hyp_a, uint8_t *hyp_b, uint8_t *status, uint8_t *unmatched, cellector_donor_fit_summary *out,
+                                     double *mom1, double *mom2)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (p) prm = *p;
+    cellector_donor_fit_params fp;
+    cellector_donor_fit_default_params(&fp);
+    if (fit) fp = *fit;
+    CHK(donor_call_check(c, "donor_fit", gt, n_donors, &prm));
+    if (!(fp.iqr_multiple >= 0.0)) return ctx_fail(c, CELLECTOR_EINVAL, "donor_fit: iqr_multiple = %g is not a value >= 0", fp.iqr_multiple);
+    if (fp.min_cells < 4) return ctx_fail(c, CELLECTOR_EINVAL, "donor_fit: min_cells must be at least 4");
+    const uint32_t D = n_donors;
+    double lp[64] = {};
+    CHK(donor_prior_anchor_check(c, "donor_fit", D, log_prior, anchor, lp));
+    const double log_singlet = std::log(1.0 - prm.doublet_rate);
+    const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
+    SETDEV(c);
+    return donor_fit_run(c, gt, D, &prm, &fp, lp, anchor, mask, log_singlet, log_pair, fit_e, fit_v, pair_e, pair_v, z, pair_z, call_z, hyp_a,
+                         hyp_b, status, unmatched, out, mom1, mom2);
 }
 
 // ---- the donor calls from genotype probabilities: the soft kernels of kernels_donors.hip ------------------------------------------

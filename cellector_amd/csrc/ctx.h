@@ -589,6 +589,14 @@ cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32
                                  uint64_t *cells);
 cellector_status donor_weights_run(cellector_ctx *c, const float *gp /*[D][total_loci][3]*/, uint32_t D, double *w, uint8_t *kind);
 cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *d_gt /*[D][total_loci]*/, uint64_t *d_packed /*[L][W]*/);
+// the fit of the called hypothesis: the moment tables alone; the donor call into scratch, then the fit pass, the keys' order statistics
+// (select_threshold) and the flags
+cellector_status donor_moment_tables_run(cellector_ctx *c, const cellector_donor_params *prm, const uint8_t *mask, double *mom1, double *mom2);
+cellector_status donor_fit_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const cellector_donor_fit_params *fp,
+                               const double *log_prior, const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair,
+                               double *fit_e, double *fit_v, double *pair_e, double *pair_v, double *z, double *pair_z, double *call_z,
+                               uint8_t *hyp_a, uint8_t *hyp_b, uint8_t *status, uint8_t *unmatched, cellector_donor_fit_summary *out,
+                               double *mom1, double *mom2);
 // ambient fraction estimation (kernels_ambient.hip) on one device holding all cells; validated arguments, host arrays, scratch of their
 // own, nothing of the ctx written: the tables of a grid alone, one profile over a grid, the zooming grid search
 cellector_status ambient_tables_run(cellector_ctx *c, const double *rho, uint32_t G, double err, const uint8_t *mask, double *tab);

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_ambient_e(uint64_t n_rows, uin
         const uint32_t s_word = part ? src >> 5 : 0u, s_shift = 2u * (src & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_donor_e and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t[LANE_AHEAD];

@@ -12,7 +12,8 @@
 //                   hypotheses
 //   k_donor_match   a lane per (class, donor): the class' tallies over ascending loci, the same terms in the same order
 // The same calls from genotype probabilities (three weights per donor and locus in place of a code) are the section behind
-// k_donor_match.  All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
+// k_donor_match; the fit of the called hypothesis (cellector_donor_fit: k_donor_moments, k_donor_fit) is the one behind that.  All
+// scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
 #include "lane_rows.h"
 
 #include <cmath>
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_donor_e(uint64_t n_rows, uint3
         const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_ambient_e and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_ambient_e, k_donor_fit and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t[LANE_AHEAD];
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
     const uint32_t my_word = d >> 5, my_shift = 2u * (d & 31u);
     const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
     double acc = 0.0;
-    // the entry loop of lane_rows.h over loci: a fix here belongs in k_cluster_e, k_donor_e and k_ambient_e as well
+    // the entry loop of lane_rows.h over loci: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit and k_ambient_e as well
     for (uint64_t l0 = 0; l0 < L; l0 += LANE_AHEAD) {
         double av[LANE_AHEAD], rv[LANE_AHEAD];
         double2 t[LANE_AHEAD];
@@ -462,6 +463,137 @@ __global__ __launch_bounds__(64) void k_donor_gp_match(uint64_t L, uint32_t D, c
     ll[(uint64_t)k * D + d] = acc;
 }
 
+// ---- the fit of the called hypothesis (cellector_donor_fit, cellector_donor_moment_tables) -----------------------------------------
+// The softmax of the donor call sums to 1 whoever the cell is: a cell of a donor nobody genotyped gets a confident call for something
+// else.  Under its called hypothesis an entry's term (a log theta + r log(1 - theta)) is n = a + r times a per-(locus, genotype)
+// constant in its mean and in its variance, so the expected sum and its variance are two more table rows and two more ordered sums
+// per lane.  include/cellector_ffi.h states the model; donors.py (moment_tables, fit_sums, fit) is its twin.
+//   k_donor_moments  mom1 [L][4] and mom2 [L][16] double2 = (h, v), thread (l, 4 ga + gb) as k_donor_tables
+//   k_donor_fit      one walk of the row, lane = donor: E, V from mom1, PE, PV from mom2 under the donor call's anchor; the tail forms
+//                    z, pz from the donor call's own s and p, the called hypothesis and its z
+
+// theta and rest by k_donor_tables' own operations; la = log(th), lb = log(rest); h = (th la) + (rest lb); d = la - lb;
+// v = (th rest) (d d).  The diagonal is mom1.  A masked locus carries (0, 0).
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_moments(uint64_t n /*16 L*/, const double *__restrict__ s_alt, const double *__restrict__ s_ref,
+                                                                const uint8_t *__restrict__ mask /*or null*/, double err, double ambient,
+                                                                double2 *__restrict__ mom1, double2 *__restrict__ mom2)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * LANE_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = i >> 4;
+    const uint32_t ga = (uint32_t)(i >> 2) & 3u, gb = (uint32_t)i & 3u;
+    double2 out = make_double2(0.0, 0.0);
+    if (!mask || mask[l] != 0) {
+        const double A = s_alt[l], R = s_ref[l];
+        const double num = A + 1.0, tot = A + R, den = tot + 2.0;
+        const double soup = num / den;
+        const double keep = 1.0 - ambient, amb = ambient * soup;
+        const double e2 = 1.0 - err;
+        const double ea = ga == 0 ? err : ga == 1 ? 0.5 : ga == 2 ? e2 : soup;
+        const double eb = gb == 0 ? err : gb == 1 ? 0.5 : gb == 2 ? e2 : soup;
+        const double pa = keep * ea, pb = keep * eb;
+        const double ta = pa + amb, tb = pb + amb;
+        const double sum = ta + tb;
+        const double th = 0.5 * sum;
+        const double rest = 1.0 - th;
+        const double la = log(th), lb = log(rest);
+        const double ha = th * la, hb = rest * lb;
+        const double h = ha + hb;
+        const double d = la - lb;
+        const double tr = th * rest, dd = d * d;
+        out = make_double2(h, tr * dd);
+    }
+    mom2[i] = out;
+    if (ga == gb) mom1[l * 4 + ga] = out;
+}
+
+// The fit pass.  k_donor_e's geometry: a group of DP lanes per cell, lane = donor d.  Four ordered sums per lane over the row's entries
+// at unmasked loci, n = (double)(alt + ref): E += n h, V += n v from mom1's row of the donor's genotype, PE, PV likewise from mom2's row
+// of (the anchor's, the donor's).  Tail: z = (s - E) / sqrt(V), pz = (p - PE) / sqrt(PV), 0.0 where the variance is 0.0; the called
+// hypothesis is (anchor, best_pair) under status 1 and (best, none) otherwise, its z is shuffled from the lane that holds it.
+template <int DP>
+__global__ __launch_bounds__(LANE_THREADS) void k_donor_fit(uint64_t n_rows, uint32_t D, uint32_t W, const uint64_t *__restrict__ row_ptr,
+                                                            const uint64_t *__restrict__ ent, const uint64_t *__restrict__ packed,
+                                                            const double2 *__restrict__ mom1, const double2 *__restrict__ mom2,
+                                                            const uint8_t *__restrict__ mask /*or null*/, const uint8_t *__restrict__ anchor,
+                                                            const double *__restrict__ s, const double *__restrict__ p,
+                                                            const uint8_t *__restrict__ best, const uint8_t *__restrict__ best_pair,
+                                                            const uint8_t *__restrict__ status, double *__restrict__ e_out,
+                                                            double *__restrict__ v_out, double *__restrict__ pe_out, double *__restrict__ pv_out,
+                                                            double *__restrict__ z_out, double *__restrict__ pz_out, double *__restrict__ call_z,
+                                                            uint8_t *__restrict__ hyp_a, uint8_t *__restrict__ hyp_b)
+{
+    const LaneGeom<DP> geo(n_rows, D);
+    const int col = geo.col;
+    const bool col_ok = geo.ok;
+    const uint32_t my_word = col_ok ? (uint32_t)col >> 5 : 0u, my_shift = 2u * ((uint32_t)col & 31u);
+    for (uint64_t g = geo.wave0; g < geo.n_groups; g += geo.n_waves) {
+        const uint64_t row = geo.row(g);
+        const bool have = row < n_rows;
+        const uint64_t beg = have ? row_ptr[row] : 0, end = have ? row_ptr[row + 1] : 0;
+        uint32_t a = have ? anchor[row] : 0u;
+        if (a >= D) a = 0;  // (never: the donor call checked a given anchor, or wrote a donor)
+        const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
+        double E = 0.0, V = 0.0, PE = 0.0, PV = 0.0;
+        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_cluster_e, k_ambient_e and k_donor_match as well
+        for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
+            uint64_t en[LANE_AHEAD];
+            double2 t1[LANE_AHEAD], t2[LANE_AHEAD];
+            bool use[LANE_AHEAD];
+#pragma unroll
+            for (int q = 0; q < LANE_AHEAD; q++) {
+                const bool in = i + q < end;
+                en[q] = in ? ent[i + q] : 0ull;
+                const uint64_t l = ENT_IDX(en[q]);
+                use[q] = in && (!mask || mask[l] != 0);
+                t1[q] = t2[q] = make_double2(0.0, 0.0);
+                if (use[q] && col_ok) {
+                    const uint32_t gd = (uint32_t)(packed[l * W + my_word] >> my_shift) & 3u;
+                    const uint32_t ga = (uint32_t)(packed[l * W + a_word] >> a_shift) & 3u;
+                    t1[q] = mom1[l * 4 + gd];
+                    t2[q] = mom2[l * 16 + 4 * ga + gd];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < LANE_AHEAD; q++) {
+                if (!use[q]) continue;
+                const double n = (double)(ENT_ALT(en[q]) + ENT_REF(en[q]));
+                const double eh = n * t1[q].x, ev = n * t1[q].y, ph = n * t2[q].x, pv = n * t2[q].y;
+                E = E + eh;
+                V = V + ev;
+                PE = PE + ph;
+                PV = PV + pv;
+            }
+        }
+        // the tail: every lane of the wave takes part in the shuffles; a lane without a row or a column carries 0.0
+        double z = 0.0, pz = 0.0;
+        if (have && col_ok) {
+            const uint64_t at = row * D + col;
+            if (V != 0.0) {
+                const double diff = s[at] - E, sd = sqrt(V);
+                z = diff / sd;
+            }
+            if (PV != 0.0) {
+                const double diff = p[at] - PE, sd = sqrt(PV);
+                pz = diff / sd;
+            }
+            e_out[at] = E; v_out[at] = V; pe_out[at] = PE; pv_out[at] = PV;
+            z_out[at] = z; pz_out[at] = pz;
+        }
+        const uint32_t st = have ? status[row] : (uint32_t)DN_NONE;
+        uint32_t b = have ? best[row] : 0u, bp = have ? best_pair[row] : 0u;
+        if (b >= D) b = 0;
+        if (bp >= D) bp = 0;  // (D = 1 has no pair and never status 1)
+        const double zb = __shfl(z, (geo.base + (int)b) & 63, 64), zp = __shfl(pz, (geo.base + (int)bp) & 63, 64);
+        if (have && col == 0) {
+            const bool pair = st == 1u;
+            call_z[row] = st == (uint32_t)DN_NONE ? 0.0 : pair ? zp : zb;
+            hyp_a[row] = pair ? (uint8_t)a : (uint8_t)b;
+            hyp_b[row] = pair ? (uint8_t)bp : (uint8_t)DN_NONE;
+        }
+    }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -570,6 +702,24 @@ struct DonorRun {
         });
     }
 
+    // the donor call on the device: the uploads, the tables and the two passes; everything stays in the run's buffers
+    cellector_status cells(const void *host_calls, const cellector_donor_params *prm, const double *log_prior, const uint8_t *host_anchor,
+                           const uint8_t *host_mask, double log_singlet, double log_pair)
+    {
+        const DonorTail tail = {log_singlet, log_pair, prm->posterior_threshold, prm->min_loci};
+        cellector_status st = prepare(host_calls, host_mask, prm);
+        if (st == CELLECTOR_OK && hipMemcpyAsync(lp, log_prior, (uint64_t)D * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the priors failed");
+        if (st == CELLECTOR_OK && host_anchor && n && hipMemcpyAsync(anchor, host_anchor, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the anchors failed");
+        ev.mark(0, c->stream);
+        if (st == CELLECTOR_OK) st = pass(false, host_anchor != nullptr, tail);
+        ev.mark(1, c->stream);
+        if (st == CELLECTOR_OK) st = pass(true, host_anchor != nullptr, tail);
+        ev.mark(2, c->stream);
+        return st;
+    }
+
     // a soft run: the weights as the device holds them, and the kernel's own count of rows the host's check should have refused
     cellector_status fetch_weights(double *h_w, uint8_t *h_kind)
     {
@@ -646,17 +796,7 @@ cellector_status donor_posteriors_run(cellector_ctx *c, const uint8_t *gt, const
     CHK(r.alloc(true, 0, gp != nullptr));
     std::vector<uint8_t> h_status(n), h_best(n);
     invalidate_cell_ll_state(c);
-    const DonorTail tail = {log_singlet, log_pair, prm->posterior_threshold, prm->min_loci};
-    cellector_status st = r.prepare(gp ? (const void *)gp : (const void *)gt, mask, prm);
-    if (st == CELLECTOR_OK && hipMemcpyAsync(r.lp, log_prior, (uint64_t)D * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the priors failed");
-    if (st == CELLECTOR_OK && anchor && n && hipMemcpyAsync(r.anchor, anchor, n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_posteriors: the upload of the anchors failed");
-    r.ev.mark(0, c->stream);
-    if (st == CELLECTOR_OK) st = r.pass(false, anchor != nullptr, tail);
-    r.ev.mark(1, c->stream);
-    if (st == CELLECTOR_OK) st = r.pass(true, anchor != nullptr, tail);
-    r.ev.mark(2, c->stream);
+    cellector_status st = r.cells(gp ? (const void *)gp : (const void *)gt, prm, log_prior, anchor, mask, log_singlet, log_pair);
     const uint64_t nD = n * D;
     if (st == CELLECTOR_OK && ll) st = d2h(c, ll, r.s, nD * 8);
     if (st == CELLECTOR_OK && pair_ll) st = d2h(c, pair_ll, r.p, nD * 8);
@@ -735,5 +875,148 @@ cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32
         if (cells) cells[k] = h_cells[k];
     }
     if (ll) memcpy(ll, h_ll.data(), h_ll.size() * 8);
+    return CELLECTOR_OK;
+}
+
+// ---- cellector_donor_fit, cellector_donor_moment_tables ----------------------------------------------------------------------------
+namespace {
+
+// the scratch of a fit beside the donor run's; alloc() makes all of it before anything is launched
+struct FitRun {
+    DevBuf<double2> mom1, mom2;         // [L][4], [L][16]
+    DevBuf<double> e, v, pe, pv, z, pz; // [n][D]
+    DevBuf<double> cz, keys;            // [n]
+    DevBuf<uint8_t> ha, hb;             // [n]
+
+    cellector_status alloc(cellector_ctx *c, uint64_t L, uint64_t n, uint32_t D, bool cells)
+    {
+        CHK(dev_alloc(c, &mom1, L * 4));
+        CHK(dev_alloc(c, &mom2, L * 16));
+        if (cells) {
+            const uint64_t nD = n * D;
+            CHK(dev_alloc(c, &e, nD)); CHK(dev_alloc(c, &v, nD)); CHK(dev_alloc(c, &pe, nD)); CHK(dev_alloc(c, &pv, nD));
+            CHK(dev_alloc(c, &z, nD)); CHK(dev_alloc(c, &pz, nD));
+            CHK(dev_alloc(c, &cz, n)); CHK(dev_alloc(c, &keys, n));
+            CHK(dev_alloc(c, &ha, n)); CHK(dev_alloc(c, &hb, n));
+            if (c->sel_list_cap < n) {  // (what select_threshold would grow behind the launches)
+                c->sel_list_cap = 0;
+                CHK(dev_alloc(c, &c->sel_list, n));
+                c->sel_list_cap = n;
+            }
+        }
+        return CELLECTOR_OK;
+    }
+
+    cellector_status moments(cellector_ctx *c, uint64_t L, const uint8_t *d_mask, const cellector_donor_params *prm)
+    {
+        if (!L) return CELLECTOR_OK;
+        hipLaunchKernelGGL(k_donor_moments, dim3(lane_grid(L * 16, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * 16,
+                           c->s_alt.get(), c->s_ref.get(), d_mask, prm->err, prm->ambient, mom1.get(), mom2.get());
+        HIPCHK(c, hipGetLastError());
+        return CELLECTOR_OK;
+    }
+};
+
+}  // namespace
+
+// cellector_donor_moment_tables: validated arguments; host outputs, any may be null
+cellector_status donor_moment_tables_run(cellector_ctx *c, const cellector_donor_params *prm, const uint8_t *mask, double *mom1, double *mom2)
+{
+    const uint64_t L = c->L;
+    LociMask m;
+    FitRun f;
+    CHK(dev_alloc(c, &m.buf, L));
+    CHK(f.alloc(c, L, 0, 0, false));
+    invalidate_cell_ll_state(c);
+    cellector_status st = m.set(c, mask, L);
+    if (st == CELLECTOR_OK) st = f.moments(c, L, m.get(), prm);
+    if (st == CELLECTOR_OK && mom1) st = d2h(c, mom1, f.mom1, L * 4 * 16);
+    if (st == CELLECTOR_OK && mom2) st = d2h(c, mom2, f.mom2, L * 16 * 16);
+    (void)hipStreamSynchronize(c->stream);  // (nothing of the scratch may be in use when it goes)
+    return st;
+}
+
+// cellector_donor_fit: validated arguments (log_prior never null); the donor call into the run's scratch, then the moment tables and
+// the fit pass over the same packed genotypes, anchors, sums and calls; the threshold and the flags on the host over the copied keys
+cellector_status donor_fit_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm, const cellector_donor_fit_params *fp,
+                               const double *log_prior, const uint8_t *anchor, const uint8_t *mask, double log_singlet, double log_pair,
+                               double *fit_e, double *fit_v, double *pair_e, double *pair_v, double *z, double *pair_z, double *call_z,
+                               uint8_t *hyp_a, uint8_t *hyp_b, uint8_t *status, uint8_t *unmatched, cellector_donor_fit_summary *out,
+                               double *mom1, double *mom2)
+{
+    LapTimer whole;
+    DonorRun r{c, D, (D + 31) / 32, c->nloc, c->L, c->total_loci};
+    FitRun f;
+    const uint64_t n = r.n, L = r.L, nD = n * D;
+    CHK(r.alloc(true, 0));
+    CHK(f.alloc(c, L, n, D, true));
+    std::vector<uint8_t> h_status(n), h_best(n), h_flag(n, 0);
+    std::vector<double> h_cz(n), h_keys;
+    h_keys.reserve(n);
+    invalidate_cell_ll_state(c);
+    cellector_status st = r.cells(gt, prm, log_prior, anchor, mask, log_singlet, log_pair);
+    if (st == CELLECTOR_OK) st = f.moments(c, L, r.mask.get(), prm);
+    EventMarks<2> ev;
+    ev.mark(0, c->stream);
+    if (st == CELLECTOR_OK && n) {
+        const int dpw = lane_width(D, 2);
+        const dim3 grid(lane_walk_grid(n, dpw, c->n_cu)), block(LANE_THREADS);
+        lane_dispatch<2, 64>(dpw, [&](auto DP) {
+            hipLaunchKernelGGL((k_donor_fit<DP>), grid, block, 0, c->stream, n, D, r.W, c->csr_ptr.get(), c->csr_ent.get(), r.packed.get(),
+                               f.mom1.get(), f.mom2.get(), r.mask.get(), r.anchor.get(), r.s.get(), r.p.get(), r.best.get(), r.best_pair.get(),
+                               r.status.get(), f.e.get(), f.v.get(), f.pe.get(), f.pv.get(), f.z.get(), f.pz.get(), f.cz.get(), f.ha.get(),
+                               f.hb.get());
+        });
+        if (hipGetLastError() != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_fit: launch failed");
+    }
+    ev.mark(1, c->stream);
+    if (st == CELLECTOR_OK && fit_e) st = d2h(c, fit_e, f.e, nD * 8);
+    if (st == CELLECTOR_OK && fit_v) st = d2h(c, fit_v, f.v, nD * 8);
+    if (st == CELLECTOR_OK && pair_e) st = d2h(c, pair_e, f.pe, nD * 8);
+    if (st == CELLECTOR_OK && pair_v) st = d2h(c, pair_v, f.pv, nD * 8);
+    if (st == CELLECTOR_OK && z) st = d2h(c, z, f.z, nD * 8);
+    if (st == CELLECTOR_OK && pair_z) st = d2h(c, pair_z, f.pz, nD * 8);
+    if (st == CELLECTOR_OK) st = d2h(c, h_cz.data(), f.cz, n * 8);
+    if (st == CELLECTOR_OK && hyp_a) st = d2h(c, hyp_a, f.ha, n);
+    if (st == CELLECTOR_OK && hyp_b) st = d2h(c, hyp_b, f.hb, n);
+    if (st == CELLECTOR_OK) st = d2h(c, h_status.data(), r.status, n);
+    if (st == CELLECTOR_OK) st = d2h(c, h_best.data(), r.best, n);
+    if (st == CELLECTOR_OK && mom1) st = d2h(c, mom1, f.mom1, L * 4 * 16);
+    if (st == CELLECTOR_OK && mom2) st = d2h(c, mom2, f.mom2, L * 16 * 16);
+    if (st == CELLECTOR_OK && hipStreamSynchronize(c->stream) != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_fit: the device failed");
+    // the keys: the called z of the status-0 cells in ascending cell order; the library's select gives the three statistics
+    cellector_donor_fit_summary sum = {};
+    sum.median = sum.iqr = NAN;
+    sum.threshold = -INFINITY;
+    if (st == CELLECTOR_OK) {
+        for (uint64_t i = 0; i < n; i++)
+            if (h_status[i] == 0) h_keys.push_back(h_cz[i]);
+        sum.n_keys = h_keys.size();
+        if (sum.n_keys >= fp->min_cells) {
+            double out3[3] = {};
+            if (hipMemcpyAsync(f.keys, h_keys.data(), sum.n_keys * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                st = ctx_fail(c, CELLECTOR_EDEVICE, "donor_fit: the upload of the keys failed");
+            if (st == CELLECTOR_OK) st = select_threshold(c, f.keys, sum.n_keys, fp->iqr_multiple);
+            if (st == CELLECTOR_OK) st = d2h(c, out3, c->sel_out + 8, sizeof out3);
+            sum.median = out3[0]; sum.iqr = out3[1]; sum.threshold = out3[2];
+        }
+    }
+    (void)hipStreamSynchronize(c->stream);  // (nothing of the scratch may be in use when it goes)
+    float ms = 0.f, ms1 = 0.f, ms2 = 0.f;
+    if (st == CELLECTOR_OK && ev.ms(0, 1, &ms) && r.ev.ms(0, 1, &ms1) && r.ev.ms(1, 2, &ms2))
+        fprintf(stderr, "[timing]   donor_fit: D %u singlet pass %.3f ms, pair pass %.3f ms, fit pass %.3f ms, whole call %.4f s\n", D, ms1, ms2,
+                ms, whole.lap());
+    if (st != CELLECTOR_OK) return st;
+    for (uint64_t i = 0; i < n; i++) {
+        if (h_status[i] == DN_NONE || !(h_cz[i] < sum.threshold)) continue;  // strict, main.rs:331
+        h_flag[i] = 1;
+        sum.n_unmatched++;
+        (h_status[i] == 0 ? sum.n_unmatched_singlet : h_status[i] == 1 ? sum.n_unmatched_doublet : sum.n_unmatched_ambiguous)++;
+        sum.donor_unmatched[h_best[i] < 64 ? h_best[i] : 0]++;
+    }
+    if (call_z && n) memcpy(call_z, h_cz.data(), n * 8);
+    if (status && n) memcpy(status, h_status.data(), n);
+    if (unmatched && n) memcpy(unmatched, h_flag.data(), n);
+    if (out) *out = sum;
     return CELLECTOR_OK;
 }

@@ -9,9 +9,9 @@
 // the sum; a masked locus adds nothing and is not counted.  Behind the walk comes a tail in which EVERY lane of the wave takes part in
 // the shuffles, whatever its row and column: a lane without a row or a column walks nothing and carries a neutral value.
 //
-// The entry loop itself stays in each kernel (k_cluster_e, k_donor_e, k_ambient_e, and over loci k_donor_match; each loop names
-// the others): one loop behind a callable for the table lookup was measured and did not hold the speed of the separate loops in
-// every pass.  What is shared is everything around it: the constants, the geometry, the argmax of the tails, and
+// The entry loop itself stays in each kernel (k_cluster_e, k_donor_e, k_donor_fit, k_ambient_e, and over loci k_donor_match; each
+// loop names the others): one loop behind a callable for the table lookup was measured and did not hold the speed of the separate
+// loops in every pass.  What is shared is everything around it: the constants, the geometry, the argmax of the tails, and
 // on the host the grid, the width, the width dispatch, the mask and the timing events.
 //
 // A block's waves take the groups g = wave0, wave0 + n_waves, ...; the grid is lane_grid(groups, LANE_WAVES, 8 per CU).

@@ -14,6 +14,10 @@ ulps.
 The same calls from genotype probabilities (cellector_donor_weights / cellector_donor_posteriors_gp / cellector_match_donors_gp):
 soft_weights, soft_singlet_sums, soft_pair_sums, soft_match_sums, posteriors_gp, match_gp, and read_donor_vcf_gp for the GP, GL or PL
 of a donor VCF.
+
+The fit of the called hypothesis (cellector_donor_moment_tables / cellector_donor_fit): moment_tables, fit_sums, fit_calls, fit.  The
+four moment sums carry the device's bits when fed the device's tables; z passes through a sqrt and a division and agrees to 2 ulp;
+the hypothesis, the keys, their statistics and the flags follow exactly from the numbers they are given.
 """
 import math
 import re
@@ -213,6 +217,103 @@ def _match_calls(ll, cells):
         margin = np.full(K, np.inf)
     live = np.asarray(cells) > 0
     return dict(ll=ll, best=np.where(live, best, NONE).astype(np.uint8), margin=np.where(live, margin, 0.0))
+
+
+# ---- the fit of the called hypothesis ----------------------------------------------------------------------------------------------
+# The twin of cellector_donor_moment_tables / cellector_donor_fit: how well the hypothesis the donor call chose explains the cell.  An
+# entry's term under Binomial(n, theta) has mean n h and variance n v, (h, v) a constant of (locus, genotype); the sums of both in the
+# library's order carry the device's bits when fed the device's tables.
+FIT_DEFAULTS = dict(iqr_multiple=3.0, min_cells=8)
+
+
+def moment_tables(alt_total, ref_total, err=0.01, ambient=0.03, mask=None, log=np.log):
+    """(mom1 [L, 4, 2], mom2 [L, 16, 2]) = (h, v): h = (th log th) + (rest log rest), v = (th rest) (d d), d = log th - log rest, rest =
+    1 - th, th the theta of tables(); a masked locus carries (0, 0)"""
+    th = thetas(alt_total, ref_total, err, ambient)
+    th2 = (0.5 * (th[:, :, None] + th[:, None, :])).reshape(len(th), 16)
+    out = []
+    for t in (th, th2):
+        rest = 1.0 - t
+        la, lb = log(t), log(rest)
+        d = la - lb
+        mom = np.stack([(t * la) + (rest * lb), (t * rest) * (d * d)], axis=-1)
+        if mask is not None:
+            mom[np.asarray(mask) == 0] = 0.0
+        out.append(mom)
+    return out[0], out[1]
+
+
+def fit_sums(mat, mom1, mom2, g, anchor):
+    """(E, V, PE, PV) [cells, D]: per (cell, donor) the sums over the cell's entries in row order of n h and n v, n = alt + ref, (h, v)
+    = mom1[l][g[l, d]], and of the same from mom2[l][4 g[l, anchor_c] + g[l, d]]"""
+    mom1, mom2, g = np.asarray(mom1, np.float64), np.asarray(mom2, np.float64), np.asarray(g, np.int64)
+    anchor = np.asarray(anchor, np.int64)
+    E, V, PE, PV = (np.zeros((mat.N, g.shape[1])) for _ in range(4))
+    for rows, ent in mat.rows.steps:
+        l = mat.r_lo[ent]
+        n = (mat.r_al[ent] + mat.r_re[ent])[:, None]  # (whole numbers: exact)
+        t1 = mom1[l[:, None], g[l]]
+        t2 = mom2[l[:, None], 4 * g[l, anchor[rows]][:, None] + g[l]]
+        E[rows] = E[rows] + (n * t1[:, :, 0])
+        V[rows] = V[rows] + (n * t1[:, :, 1])
+        PE[rows] = PE[rows] + (n * t2[:, :, 0])
+        PV[rows] = PV[rows] + (n * t2[:, :, 1])
+    return E, V, PE, PV
+
+
+def order_statistics(keys, iqr_multiple):
+    """(median, iqr, threshold) of the keys as cellector_order_statistics forms them (statrs' median and quartiles on exact order
+    statistics, threshold = q1 - iqr_multiple iqr); at least 4 keys"""
+    srt = np.sort(np.asarray(keys, np.float64))
+    n = len(srt)
+    k = n // 2
+    med = srt[k] if n % 2 else (srt[k - 1] + srt[k]) / 2.0
+    h1, h3 = (n + 1.0 / 3.0) * 0.25 + 1.0 / 3.0, (n + 1.0 / 3.0) * 0.75 + 1.0 / 3.0
+    q1 = srt[int(h1) - 1] + (h1 - int(h1)) * (srt[int(h1)] - srt[int(h1) - 1])
+    q3 = srt[int(h3) - 1] + (h3 - int(h3)) * (srt[int(h3)] - srt[int(h3) - 1])
+    iqr = q3 - q1
+    return float(med), float(iqr), float(q1 - iqr_multiple * iqr)
+
+
+def fit_calls(s, p, E, V, PE, PV, anchor, best, best_pair, status, iqr_multiple=3.0, min_cells=8):
+    """z, pair_z, the called hypothesis, its z, the keys' statistics and the flags from the sums and the donor call's decisions"""
+    n, D = s.shape
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = np.where(V != 0.0, (s - E) / np.sqrt(V), 0.0)
+        pz = np.where(PV != 0.0, (p - PE) / np.sqrt(PV), 0.0)
+    r = np.arange(n)
+    status, best, anchor = np.asarray(status), np.asarray(best, np.int64), np.asarray(anchor, np.int64)
+    pair = status == DOUBLET
+    bp = np.where(pair, np.asarray(best_pair, np.int64), 0)
+    call_z = np.where(status == UNASSIGNED, 0.0, np.where(pair, pz[r, bp], z[r, best]))
+    keys = call_z[status == SINGLET]
+    med, iqr, thr = (math.nan, math.nan, -math.inf) if len(keys) < int(min_cells) else order_statistics(keys, float(iqr_multiple))
+    unmatched = ((status != UNASSIGNED) & (call_z < thr)).astype(np.uint8)
+    flagged = unmatched != 0
+    return dict(z=z, pair_z=pz, call_z=call_z, hyp_a=np.where(pair, anchor, best).astype(np.uint8),
+                hyp_b=np.where(pair, bp, NONE).astype(np.uint8), status=status.astype(np.uint8), unmatched=unmatched,
+                summary=dict(n_keys=len(keys), median=med, iqr=iqr, threshold=thr, n_unmatched=int(flagged.sum()),
+                             n_unmatched_singlet=int((flagged & (status == SINGLET)).sum()),
+                             n_unmatched_doublet=int((flagged & pair).sum()),
+                             n_unmatched_ambiguous=int((flagged & (status == AMBIGUOUS)).sum()),
+                             donor_unmatched=np.bincount(best[flagged], minlength=D)))
+
+
+def fit(mat, gt_used, alt_total, ref_total, log_prior=None, anchor=None, tab1=None, tab2=None, mom1=None, mom2=None, call=None,
+        iqr_multiple=3.0, min_cells=8, **params):
+    """cellector_donor_fit on host arrays: posteriors() (or call, a donor call's dict with ll, pair_ll, anchor, best, best_pair and
+    status: the device's, for its bits) and the fit of the hypothesis it chose.  mom1 / mom2: the device's moment tables, or None =
+    numpy's.  Returns the dict of Cellector.donor_fit (summary: a dict) with the donor call under "call"."""
+    prm = _params(params)
+    if call is None:
+        call = posteriors(mat, gt_used, alt_total, ref_total, log_prior, anchor, tab1, tab2, **prm)
+    if mom1 is None or mom2 is None:
+        mom1, mom2 = moment_tables(alt_total, ref_total, prm["err"], prm["ambient"], mat.mask)
+    E, V, PE, PV = fit_sums(mat, mom1, mom2, np.asarray(gt_used, np.uint8).T, call["anchor"])
+    out = fit_calls(call["ll"], call["pair_ll"], E, V, PE, PV, call["anchor"], call["best"], call["best_pair"], call["status"],
+                    iqr_multiple, min_cells)
+    out.update(fit_e=E, fit_v=V, pair_e=PE, pair_v=PV, mom1=mom1, mom2=mom2, call=call)
+    return out
 
 
 # ---- genotype probabilities in place of hard calls ---------------------------------------------------------------------------------

@@ -92,6 +92,9 @@ SIGNATURES = {
     "cellector_donor_tables": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "cellector_donor_posteriors": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_match_donors": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
+    "cellector_donor_fit_default_params": (_i, [_vp]),
+    "cellector_donor_moment_tables": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "cellector_donor_fit": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_donor_posteriors_gp": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_donor_weights": (_i, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "cellector_match_donors_gp": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
@@ -160,6 +163,15 @@ class DonorParams(C.Structure):
 
 class DonorSummary(C.Structure):
     _fields_ = [("n_singlet", _u64), ("n_doublet", _u64), ("n_ambiguous", _u64), ("n_unassigned", _u64), ("donor_cells", _u64 * 64)]
+
+
+class DonorFitParams(C.Structure):
+    _fields_ = [("iqr_multiple", _d), ("min_cells", _u64)]
+
+
+class DonorFitSummary(C.Structure):
+    _fields_ = [("n_keys", _u64), ("median", _d), ("iqr", _d), ("threshold", _d), ("n_unmatched", _u64), ("n_unmatched_singlet", _u64),
+                ("n_unmatched_doublet", _u64), ("n_unmatched_ambiguous", _u64), ("donor_unmatched", _u64 * 64)]
 
 
 class AmbientParams(C.Structure):
@@ -927,6 +939,54 @@ class Cellector:
             self.h, _p(gt), D, C.byref(p), _p(log_prior), _p(anchor), _p(mask), _p(out["ll"]), _p(out["pair_ll"]), _p(out["posterior"]),
             _p(out["pair_posterior"]), _p(out["doublet_posterior"]), _p(out["best"]), _p(out["second"]), _p(out["best_pair"]),
             _p(out["n_entries"]), _p(out["status"]), _p(out["anchor"]), C.byref(s), _p(out.get("tab1")), _p(out.get("tab2"))))
+        out["summary"] = s
+        return out
+
+    # ---- the fit of the called hypothesis: cells no genotyped donor explains; donors.py (moment_tables, fit_sums, fit) is the twin
+    def donor_fit_default_params(self):
+        p = DonorFitParams()
+        self._ck(self._lib.cellector_donor_fit_default_params(C.byref(p)))
+        return p
+
+    def donor_moment_tables(self, mask=None, **params):
+        """The moment tables of the donor fit alone (cellector_donor_moment_tables): (mom1 [L, 4, 2], mom2 [L, 16, 2]) = (h, v), the
+        mean and the variance of an entry's term per read under the row's theta.  params: err, ambient (DonorParams)."""
+        TL = self.dims().total_loci
+        _, _, mask, p = self._donor_args(np.zeros((1, TL), np.uint8), mask, params)
+        L = self.dims().loci_used
+        mom1, mom2 = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64)
+        self._ck(self._lib.cellector_donor_moment_tables(self.h, C.byref(p), _p(mask), _p(mom1), _p(mom2)))
+        return mom1, mom2
+
+    def donor_fit(self, gt, log_prior=None, anchor=None, mask=None, tables=False, **params):
+        """How well the hypothesis the donor call chose explains every cell (cellector_donor_fit): z = (ll - expected) /
+        sqrt(variance) under it, and the cells whose z lies below q1 - iqr_multiple iqr of the singlets' flagged unmatched: cells of
+        a donor gt does not hold.  params: DonorParams' and iqr_multiple, min_cells (DonorFitParams).  Returns a dict: fit_e, fit_v,
+        pair_e, pair_v, z, pair_z [cells, D], call_z, hyp_a, hyp_b (255: a singlet hypothesis), status, unmatched [cells], summary
+        (DonorFitSummary) and, with tables, mom1 / mom2."""
+        fit = self.donor_fit_default_params()
+        for k in [k for k in params if k in dict(DonorFitParams._fields_)]:
+            setattr(fit, k, params.pop(k))
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        Da = min(max(D, 1), 64)
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used
+        log_prior = None if log_prior is None else np.ascontiguousarray(log_prior, np.float64)
+        if log_prior is not None and log_prior.shape != (D,):
+            raise ValueError(f"log_prior: {D} values expected, got shape {log_prior.shape}")
+        anchor = None if anchor is None else np.ascontiguousarray(anchor, np.uint8)
+        if anchor is not None and anchor.shape != (n,):
+            raise ValueError(f"anchor: {n} values expected, got shape {anchor.shape}")
+        out = {k: np.zeros((n, Da), np.float64) for k in ("fit_e", "fit_v", "pair_e", "pair_v", "z", "pair_z")}
+        out["call_z"] = np.zeros(n, np.float64)
+        for k in ("hyp_a", "hyp_b", "status", "unmatched"):
+            out[k] = np.zeros(n, np.uint8)
+        if tables:
+            out["mom1"], out["mom2"] = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64)
+        s = DonorFitSummary()
+        self._ck(self._lib.cellector_donor_fit(
+            self.h, _p(gt), D, C.byref(p), C.byref(fit), _p(log_prior), _p(anchor), _p(mask), _p(out["fit_e"]), _p(out["fit_v"]),
+            _p(out["pair_e"]), _p(out["pair_v"]), _p(out["z"]), _p(out["pair_z"]), _p(out["call_z"]), _p(out["hyp_a"]), _p(out["hyp_b"]),
+            _p(out["status"]), _p(out["unmatched"]), C.byref(s), _p(out.get("mom1")), _p(out.get("mom2"))))
         out["summary"] = s
         return out
 

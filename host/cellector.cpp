@@ -206,6 +206,9 @@ struct Params {
     // extension: the pool's ambient fraction measured from the donor pass' singlets (cellector_estimate_ambient)
     std::string donor_field = "GT";                    // GT: hard calls; GP, GL, PL: the donors' genotype weights (cellector_donor_posteriors_gp)
     int estimate_ambient = 0;                          // 0 = off, 1 = true: report it, 2 = apply: and score the donors again with it
+    // extension: the fit of every cell's called hypothesis, and the cells no genotyped donor explains (cellector_donor_fit)
+    bool donor_fit = false;
+    std::optional<double> donor_fit_iqr;               // the multiple of the iqr below the lower quartile (default: the library's, 3)
 };
 
 const char *USAGE =
@@ -363,7 +366,17 @@ const char *USAGE =
     "                                                                       rho, se; NA for a cell that took no part).  true: no other\n"
     "                                                                       output changes.  apply: the donor pass runs again with the\n"
     "                                                                       pooled estimate as its ambient share and those results are\n"
-    "                                                                       written; not with --donor_ambient (not in the reference)\n";
+    "                                                                       written; not with --donor_ambient (not in the reference)\n"
+    "        --donor_fit <true>                                                 with --donors: how well the hypothesis the donor pass chose\n"
+    "                                                                       explains every cell, z = (ll - expected) / sqrt(variance), and\n"
+    "                                                                       the cells whose z lies below the singlets' lower quartile by\n"
+    "                                                                       more than k interquartile ranges: cells of a donor the VCF does\n"
+    "                                                                       not hold.  Writes cellector_donor_fit.tsv (barcode, status,\n"
+    "                                                                       donor, second donor of a called pair, n_loci, ll, expected,\n"
+    "                                                                       variance, z, unmatched) and prints one line; no other output\n"
+    "                                                                       changes.  Under --donor_field GP|GL|PL it scores every row's\n"
+    "                                                                       most probable genotype (not in the reference)\n"
+    "        --donor_fit_iqr <k>                                                with --donor_fit: the multiple k (default 3)\n";
 
 uint64_t parse_usize(const std::string &name, const std::string &s)
 {
@@ -392,7 +405,8 @@ Params load_params(int argc, char **argv)
                                   "locus_expected", "cells", "downsample_rate", "seed", "mix_alt", "mix_ref", "mix_barcodes",
                                   "mix_cells", "doublets", "doublet_downsample_rate", "classes", "refine_classes",
                                   "class_doublets", "class_genotypes", "cluster", "cluster_restarts", "cluster_mask", "donors",
-                                  "donor_error", "donor_ambient", "donor_doublet_rate", "donor_field", "estimate_ambient"};
+                                  "donor_error", "donor_ambient", "donor_doublet_rate", "donor_field", "estimate_ambient", "donor_fit",
+                                  "donor_fit_iqr"};
     std::map<std::string, std::string> got;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], name, value;
@@ -542,6 +556,18 @@ Params load_params(int argc, char **argv)
         if (p.estimate_ambient && !p.donors) die(1, "error: The argument '--estimate_ambient <true|apply>' requires '--donors <vcf>'");
         if (p.estimate_ambient == 2 && got.count("donor_ambient"))
             die(1, "error: The argument '--estimate_ambient apply' cannot be used with '--donor_ambient <a>'");
+    }
+    if (got.count("donor_fit")) {
+        const std::string &v = got["donor_fit"];
+        if (v != "true" && v != "false") die(EXIT_PANIC, "invalid value '" + v + "' for --donor_fit: expected true or false");
+        p.donor_fit = v == "true";
+        if (p.donor_fit && !p.donors) die(1, "error: The argument '--donor_fit true' requires '--donors <vcf>'");
+    }
+    if (got.count("donor_fit_iqr")) {
+        if (!p.donor_fit) die(1, "error: The argument '--donor_fit_iqr <k>' requires '--donor_fit true'");
+        const double v = parse_f64("donor_fit_iqr", got["donor_fit_iqr"]);
+        if (!(v >= 0.0)) die(1, "error: Invalid value '" + got["donor_fit_iqr"] + "' for '--donor_fit_iqr <k>': expected a number >= 0");
+        p.donor_fit_iqr = v;
     }
     if (got.count("mix_alt")) p.mix_alt = got["mix_alt"];
     if (got.count("mix_ref")) p.mix_ref = got["mix_ref"];
@@ -1548,6 +1574,50 @@ int main(int argc, char **argv)
         });
         fclose(f);
         lap("cellector_donors.tsv");
+        // --donor_fit: the fit of the called hypothesis under the hard calls and the parameters the donor pass ended with
+        if (params.donor_fit) {
+            cellector_donor_fit_params fp;
+            cellector_donor_fit_default_params(&fp);
+            if (params.donor_fit_iqr) fp.iqr_multiple = *params.donor_fit_iqr;
+            std::vector<double> fe((uint64_t)N * D), fv((uint64_t)N * D), fpe((uint64_t)N * D), fpv((uint64_t)N * D), fll((uint64_t)N * D),
+                fpll((uint64_t)N * D), fz(N);
+            std::vector<uint8_t> ha(N), hb(N), fstatus(N), unmatched(N);
+            std::vector<uint32_t> fn(N);
+            cellector_donor_fit_summary fs;
+            g.ck(cellector_donor_fit(g.c, gt_codes, D, &dp, &fp, nullptr, nullptr, nullptr, fe.data(), fv.data(), fpe.data(), fpv.data(), nullptr,
+                                     nullptr, fz.data(), ha.data(), hb.data(), fstatus.data(), unmatched.data(), &fs, nullptr, nullptr),
+                 "donor_fit");
+            // the sums of the called hypothesis: the hard call's own ll and pair_ll (the bits the fit took its z from)
+            g.ck(cellector_donor_posteriors(g.c, gt_codes, D, &dp, nullptr, nullptr, nullptr, fll.data(), fpll.data(), nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, fn.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+                 "donor_posteriors");
+            {
+                std::string o = "donor_fit: keys=";
+                put(o, fs.n_keys); o += " median="; put(o, fs.median); o += " iqr="; put(o, fs.iqr); o += " threshold="; put(o, fs.threshold);
+                o += " unmatched="; put(o, fs.n_unmatched); o += '\n';
+                fputs(o.c_str(), stdout);
+            }
+            FILE *ff = create(od + "/cellector_donor_fit.tsv");
+            fputs("barcode\tstatus\tdonor\tsecond_donor\tn_loci\tll\texpected\tvariance\tz\tunmatched\n", ff);
+            write_rows(ff, N, [&](uint64_t c, std::string &o) {
+                static const char *const STATUS[3] = {"singlet", "doublet", "ambiguous"};
+                o += barcodes[c]; o += '\t'; o += fstatus[c] < 3 ? STATUS[fstatus[c]] : "unassigned"; o += '\t';
+                if (fstatus[c] == 255) {
+                    o += "NA\tNA\t"; put(o, (uint64_t)fn[c]); o += "\tNA\tNA\tNA\tNA\tNA\n";
+                    return;
+                }
+                const bool pair = hb[c] != 255;
+                const uint64_t at = c * D + (pair ? hb[c] : ha[c]);
+                o += dg.names[ha[c]]; o += '\t'; o += pair ? dg.names[hb[c]].c_str() : "NA"; o += '\t'; put(o, (uint64_t)fn[c]);
+                o += '\t'; put(o, pair ? fpll[at] : fll[at]);
+                o += '\t'; put(o, pair ? fpe[at] : fe[at]);
+                o += '\t'; put(o, pair ? fpv[at] : fv[at]);
+                o += '\t'; put(o, fz[c]);
+                o += unmatched[c] ? "\t1\n" : "\t0\n";
+            });
+            fclose(ff);
+            lap("cellector_donor_fit.tsv");
+        }
         if (params.classes || params.cluster) {
             const uint32_t K = (uint32_t)class_names.size();
             std::vector<uint8_t> lab(class_label.begin(), class_label.begin() + N), mbest(K);

@@ -970,6 +970,68 @@ cellector_status cellector_match_donors_gp(cellector_ctx *ctx, const uint8_t *la
                                            double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
                                            uint64_t *cells /*[K]*/); /* any output may be NULL */
 
+/* ---- the fit of the called hypothesis: cells no genotyped donor explains ----------------------------------------------
+ * The softmax of cellector_donor_posteriors sums to 1 over the 2 D - 1 hypotheses whoever the cell is: a cell of a donor missing from
+ * gt (a failed array, a sample swap, a pool member nobody genotyped) receives a confident call for something else, usually a doublet
+ * of two other donors.  These calls measure how well the CALLED hypothesis explains the cell: the statistic the reference's author
+ * left commented out at main.rs:317-318, (ll - expected) / sqrt(variance), for the donor model, and the loop's own robust rule
+ * (main.rs:324-331) over it.  Everything not stated here is the donor model above, step for step; all arithmetic is f64 without
+ * contraction, every product, quotient and sum rounds once.  cellector_amd/donors.py (moment_tables, fit_sums, fit) is the twin.
+ *   An entry's term is a log theta + r log(1 - theta) with no binomial coefficient.  Under Binomial(n = a + r, theta) its mean is
+ *   n (theta log theta + (1 - theta) log(1 - theta)) and its variance n theta (1 - theta) (log theta - log(1 - theta))^2: both are n
+ *   times a constant of (locus, genotype).
+ *   1 moment tables, with the device's log: mom1 [L][4][2] and mom2 [L][16][2] = (h, v).  th and rest = 1.0 - th are formed by exactly
+ *     the operations of steps 2 and 3 of the donor model for that (l, 4 g_a + g_b) (mom1: g_a = g_b); la = log(th), lb = log(rest);
+ *     h = (th la) + (rest lb); d = la - lb; v = (th rest) (d d).  mom2[l][5 g] carries the bits of mom1[l][g].  A masked locus' rows
+ *     are (0, 0).  tab1 / tab2 of the donor call are untouched by this: the same kernel makes them, the same bytes.
+ *   2 per-cell sums, over the cell's entries at used, unmasked loci in row order, strictly sequential from 0.0, n = (double)(alt +
+ *     ref): E_cd += n h, V_cd += n v with (h, v) = mom1[l][g_d(l)]; PE_cd, PV_cd likewise with mom2[l][4 g_{a_c}(l) + g_d(l)], a_c
+ *     the anchor the donor call used.  Column d = a_c of the pair sums is the bits of the singlet sums.
+ *   3 z_cd = (s_cd - E_cd) / sqrt(V_cd), pz_cd = (p_cd - PE_cd) / sqrt(PV_cd) with the device's sqrt; s and p are the donor call's
+ *     own ll and pair_ll (the call runs it internally: the same bits).  Where the variance is 0.0 (no entry, or only entries of
+ *     total 0) the z is 0.0.
+ *   4 the called hypothesis: status 1: (hyp_a, hyp_b) = (a_c, best_pair), call_z = pz[c][best_pair]; otherwise (best, 255) and
+ *     call_z = z[c][best].  A status-255 cell has call_z = 0.0 and is never judged.
+ *   5 keys = the call_z of the status-0 cells in ascending cell order; {median, iqr, threshold} are what
+ *     cellector_order_statistics(keys, n_keys, iqr_multiple) returns for them, bit for bit (the library's select).  With fewer than
+ *     min_cells keys the select is not run: median and iqr are NaN, threshold is -inf and nothing is flagged.
+ *   6 unmatched[c] = 1 when status != 255 and call_z < threshold (strict, main.rs:331).  The summary carries n_keys, the three
+ *     statistics, the unmatched cells in all and by status 0 / 1 / 2, and per best donor (the donor call's best) their number.
+ *   The z is not standard normal (theta is not the cell's true allele fraction at every locus): the threshold is the robust rule
+ *   over the pool's own singlets, not a fixed cut.  A doublet one of whose parents is missing can score inside the kept range.
+ *   Genotype probabilities (GP / GL / PL) are not in this model: a mixture's moments have no closed form.  A caller with soft calls
+ *   scores the most probable genotype of every row (donors.hard_codes), as --estimate_ambient does.
+ * Defaults (cellector_donor_fit_default_params): iqr_multiple 3.0, min_cells 8.
+ * Scope, errors and scratch as cellector_donor_posteriors (a single-device ctx that holds all cells, a loaded matrix, no iteration
+ * in flight, engines 1 and 2; CELLECTOR_EINVAL with a message, nothing written or launched), and CELLECTOR_EINVAL too for an
+ * iqr_multiple that is NaN or negative and for min_cells < 4.  All device scratch is allocated before anything is launched (the
+ * donor call's, and 320 B per used locus and 48 D + 18 B per cell more); on CELLECTOR_ENOMEM the ctx is as it was.  The EM state is
+ * never touched; the caches cellector_cell_log_likelihoods invalidates are invalidated, and the select's scratch is used as
+ * cellector_order_statistics uses it. */
+typedef struct {
+    double iqr_multiple;  /* 3.0: threshold = q1 - iqr_multiple * iqr over the status-0 cells' z */
+    uint64_t min_cells;   /* 8:   with fewer status-0 cells no threshold is formed (>= 4)       */
+} cellector_donor_fit_params;
+typedef struct {
+    uint64_t n_keys;                  /* status-0 cells                                          */
+    double median, iqr, threshold;    /* of their call_z; NaN, NaN, -inf below min_cells keys    */
+    uint64_t n_unmatched, n_unmatched_singlet, n_unmatched_doublet, n_unmatched_ambiguous; /* all; status 0, 1, 2 */
+    uint64_t donor_unmatched[64];     /* unmatched cells per best donor                          */
+} cellector_donor_fit_summary;
+cellector_status cellector_donor_fit_default_params(cellector_donor_fit_params *out);
+cellector_status cellector_donor_moment_tables(cellector_ctx *ctx, const cellector_donor_params *p /*NULL = defaults*/,
+                                               const uint8_t *mask /*[L] or NULL*/, double *mom1 /*[L][4][2]*/,
+                                               double *mom2 /*[L][16][2]*/); /* any output may be NULL */
+cellector_status cellector_donor_fit(cellector_ctx *ctx, const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                     const cellector_donor_params *p /*NULL = defaults*/,
+                                     const cellector_donor_fit_params *fit /*NULL = defaults*/, const double *log_prior /*[D] or NULL*/,
+                                     const uint8_t *anchor /*[cells] or NULL*/, const uint8_t *mask /*[L] or NULL*/,
+                                     double *fit_e /*[cells][D]*/, double *fit_v /*[cells][D]*/, double *pair_e /*[cells][D]*/,
+                                     double *pair_v /*[cells][D]*/, double *z /*[cells][D]*/, double *pair_z /*[cells][D]*/,
+                                     double *call_z /*[cells]*/, uint8_t *hyp_a /*[cells]*/, uint8_t *hyp_b /*[cells]*/,
+                                     uint8_t *status /*[cells]*/, uint8_t *unmatched /*[cells]*/, cellector_donor_fit_summary *out,
+                                     double *mom1 /*[L][4][2]*/, double *mom2 /*[L][16][2]*/); /* any output may be NULL */
+
 /* ---- ambient fraction estimation: a profile likelihood over a grid of rho ------------------------------------------
  * The donor calls above and cellector_class_genotypes take the ambient fraction (the share of a barcode's reads that come from the
  * pool and not from its own cell) as a number the caller supplies.  These calls measure it: every cell is scored under the
