@@ -34,43 +34,9 @@
 #include <unordered_set>
 #include <vector>
 
+#include "host_text.h"
+
 namespace {
-
-[[noreturn]] void die(int code, const std::string &msg)
-{
-    fprintf(stderr, "%s\n", msg.c_str());
-    exit(code);
-}
-constexpr int EXIT_PANIC = 101;  // what a Rust panic gives the caller
-
-// reader (main.rs:233-244): ".gz" by extension, multi-member; BufRead::lines() strips "\n" and a preceding "\r"
-struct Lines {
-    gzFile gz = nullptr;
-    explicit Lines(const std::string &path)
-    {
-        gz = gzopen(path.c_str(), "rb");
-        if (!gz) die(EXIT_PANIC, "couldn't open file " + path);
-        gzbuffer(gz, 1 << 20);
-    }
-    ~Lines() { if (gz) gzclose(gz); }
-    bool next(std::string &out)
-    {
-        out.clear();
-        char buf[1 << 16];
-        bool any = false;
-        while (gzgets(gz, buf, sizeof buf)) {
-            any = true;
-            size_t n = strlen(buf);
-            if (n && buf[n - 1] == '\n') {
-                out.append(buf, n - 1);
-                if (!out.empty() && out.back() == '\r') out.pop_back();
-                return true;
-            }
-            out.append(buf, n);
-        }
-        return any;
-    }
-};
 
 uint64_t parse_usize(const std::string &what, const std::string &s)
 {
@@ -288,13 +254,6 @@ void collect(const Params &p, const std::string &alt_path, const std::string &re
             if (rng.uniform() < p.downsample_rate) alt_count--;
         lines.emplace_back(out_locus, it->second, ref_count, alt_count);
     }
-}
-
-FILE *create(const std::string &path)
-{
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) die(EXIT_PANIC, "Unable to create file " + path);
-    return f;
 }
 
 }  // namespace

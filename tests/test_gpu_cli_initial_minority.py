@@ -6,16 +6,9 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "host", "cellector")
+from test_host_cli import host_bin  # noqa: F401
+
 L, N, D, SEED = 1500, 800, 0.1, 11
-
-
-@pytest.fixture(scope="module")
-def host_bin(hip_lib_path):
-    if not os.path.exists(BIN) or os.path.getmtime(BIN) < os.path.getmtime(os.path.join(ROOT, "host", "cellector.cpp")):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "host"), "-s"])
-    return BIN
 
 
 @pytest.fixture(scope="module")

@@ -17,8 +17,7 @@ BIN = os.path.join(ROOT, "host", "cellector")
 
 @pytest.fixture(scope="module")
 def host_bin(hip_lib_path):
-    if not os.path.exists(BIN) or os.path.getmtime(BIN) < os.path.getmtime(os.path.join(ROOT, "host", "cellector.cpp")):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "host"), "-s"])
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "host"), "-s"])  # (make knows the headers; a no-op costs milliseconds)
     return BIN
 
 
