@@ -672,6 +672,97 @@ cellector_status cellector_ingest_mtx(cellector_ctx *c, const char *alt_path, co
 
 }  // extern "C"
 
+// ---- the joined ingests: two count streams keyed by (locus, cell) (kernels_join.hip) ------------------------------------------------
+// why a ctx cannot take a joined ingest, or null: the scope of cellector_restage, before anything is staged
+static const char *join_scope(const cellector_ctx *c, uint64_t total_cells)
+{
+    if (c->multi) return "is a multi-device ctx: its staged entries are sharded";
+    if (comm_active(c->comm)) return "has a communicator: every rank stages its own cells";
+    if (c->req_cell_begin != 0 || c->req_cell_end < total_cells) return "holds a cellector_set_shard range, not all cells";
+    return nullptr;
+}
+static cellector_status join_mode_check(const cellector_ctx *c, int mode)
+{
+    if (mode != CELLECTOR_JOIN_REF && mode != CELLECTOR_JOIN_DEPTH)
+        return ctx_fail(c, CELLECTOR_EINVAL, "join: mode must be CELLECTOR_JOIN_REF (1) or CELLECTOR_JOIN_DEPTH (2)");
+    return CELLECTOR_OK;
+}
+// tokens -> staged COO -> PASS1; the ctx has been through begin_ingest
+static cellector_status join_finish_stage(cellector_ctx *c, JoinTokens *first, JoinTokens *second, uint32_t index_base, int mode,
+                                          cellector_join_summary *out, JoinPhases *ph)
+{
+    StagedCoo coo;
+    CHK(join_stage(c, first, second, index_base, mode, &coo, out, ph));
+    c->coo = std::move(coo);
+    CHK(ingest_pass1(c));
+    c->state = cellector_ctx::ST_STAGED;
+    if (getenv("CELLECTOR_TIMING"))
+        fprintf(stderr, "[timing]   join: tokens FIRST %.4f s, tokens SECOND %.4f s, checks %.4f s, sorts %.4f s, join %.4f s (its kernels %.3f ms)\n",
+                ph->tokens_first, ph->tokens_second, ph->checks, ph->sorts, ph->join, ph->join_kernels_ms);
+    return CELLECTOR_OK;
+}
+
+extern "C" {
+
+cellector_status cellector_ingest_mtx_joined(cellector_ctx *c, const char *first_path, const char *second_path, int mode,
+                                             cellector_join_summary *out)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "ingest_mtx_joined: ctx %s", join_scope(c, 0));
+    REQUIRE(c, first_path && second_path, "null path");
+    CHK(join_mode_check(c, mode));
+    MtxInput *in = nullptr;
+    uint64_t tl = 0, tc = 0, first_hint = 0;
+    CHK(ctx_mtx_open(c, first_path, second_path, &in, &tl, &tc));
+    struct Closer { MtxInput *in; ~Closer() { mtx_input_close(in); } } closer{in};
+    CHK(join_size_lines(c, in, &first_hint));
+    if (const char *why = join_scope(c, tc)) return ctx_fail(c, CELLECTOR_EINVAL, "ingest_mtx_joined: ctx %s", why);
+    // ---- validated: from here the ctx changes as in cellector_ingest_mtx
+    CHK(begin_ingest(c, tl, tc));
+    JoinTokens first, second;
+    JoinPhases ph;
+    CHK(join_parse_pair(c, in, first_hint, &first, &second, &ph));
+    return join_finish_stage(c, &first, &second, 1u, mode, out, &ph);
+}
+
+cellector_status cellector_ingest_coo_joined(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, uint64_t n_first,
+                                             const uint32_t *locus0_a, const uint32_t *cell0_a, const uint32_t *count_a, uint64_t n_second,
+                                             const uint32_t *locus0_b, const uint32_t *cell0_b, const uint32_t *count_b, int mode,
+                                             cellector_join_summary *out)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (const char *why = join_scope(c, total_cells)) return ctx_fail(c, CELLECTOR_EINVAL, "ingest_coo_joined: ctx %s", why);
+    REQUIRE(c, n_first == 0 || (locus0_a && cell0_a && count_a), "null COO array");
+    REQUIRE(c, n_second == 0 || (locus0_b && cell0_b && count_b), "null COO array");
+    CHK(join_mode_check(c, mode));
+    CHK(begin_ingest(c, total_loci, total_cells));
+    JoinTokens side[2];
+    JoinPhases ph;
+    LapTimer t;
+    const uint64_t n[2] = {n_first, n_second};
+    const uint32_t *src[2][3] = {{locus0_a, cell0_a, count_a}, {locus0_b, cell0_b, count_b}};
+    for (int s = 0; s < 2; s++) {
+        DevBuf<uint32_t> *dst[3] = {&side[s].locus, &side[s].cell, &side[s].count};
+        side[s].n = n[s];
+        for (int k = 0; k < 3; k++) {
+            CHK(dev_alloc(c, dst[k], n[s]));
+            if (n[s]) HIPCHK(c, hipMemcpyAsync(dst[k]->get(), src[s][k], n[s] * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (s ? ph.tokens_second : ph.tokens_first) = t.lap();
+    }
+    return join_finish_stage(c, &side[0], &side[1], 0u, mode, out, &ph);
+}
+
+cellector_status cellector_load_mtx_joined(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint64_t min_alt,
+                                           uint64_t min_ref, cellector_join_summary *out)
+{
+    CHK(cellector_ingest_mtx_joined(c, first_path, second_path, mode, out));
+    return cellector_ingest_finish(c, min_alt, min_ref);
+}
+
+}  // extern "C"
+
 // Multi-device text ingest, step 1: shard `c` tokenises the whole pair and stages the entries of ALL cells (global cell index).
 cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path, const char *ref_path, cellector_ctx *helper)
 {

@@ -661,6 +661,16 @@ cellector_status combine_cells(cellector_ctx *c, uint64_t n_ctx, uint64_t n_kept
 // ... a restage's source [n_keep]: old_source [tc] at the kept cells (rank as restage_cell_ranks made it)
 cellector_status combine_source_select(cellector_ctx *c, uint64_t tc, uint64_t n_keep, const uint32_t *rank, const uint8_t *old_source,
                                        DevBuf<uint8_t> *source);
+// the joined ingests (kernels_join.hip).  One stream's tokens on the device: (locus, cell, count) per entry, stream order
+struct JoinTokens {
+    DevBuf<uint32_t> locus, cell, count;
+    uint64_t n = 0;
+};
+struct JoinPhases { double tokens_first = 0, tokens_second = 0, checks = 0, sorts = 0, join = 0 /*wall s*/, join_kernels_ms = -1 /*events*/; };
+// ... two streams (indices index_base-based: 1 text, 0 COO) checked against the ctx's dims, put in key order and joined into `out`
+// (CELLECTOR_JOIN_REF / _DEPTH); the tokens are released on the way.  A refusal leaves its words in c->err, nothing in the ctx
+cellector_status join_stage(cellector_ctx *c, JoinTokens *first, JoinTokens *second, uint32_t index_base, int mode, StagedCoo *out,
+                            cellector_join_summary *sum /*may be null*/, JoinPhases *ph);
 // cellector_add_doublets (kernels_doublets.hip).  The doublet side: for every value 2 j + s of host_fan_val [n_fan] in the range
 // host_fan_ptr [tc + 1] gives cell c, every staged entry of c summed into (locus, tc + j), thinned per (entry, pair, side);
 // strictly ascending by (locus, cell).  *overflow: a sum exceeds CELLECTOR_MAX_COUNT; the first one in output order is named
@@ -701,3 +711,7 @@ void mtx_split_delete(MtxSplit *s);
 bool mtx_input_windowed(const MtxInput *in, int64_t parse_window_opt);
 cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit *s, int rank, uint64_t parse_window, StagedCoo *out);
 cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellector_ctx *helper = nullptr /*parses the ref file*/);
+// the joined text ingest: FIRST's size line against SECOND's (whose dims the MtxInput carries), then all three tokens of every line
+// of both files, each file windowed exactly when the aligned ingest would window it
+cellector_status join_size_lines(const cellector_ctx *c, const MtxInput *in, uint64_t *first_hint);
+cellector_status join_parse_pair(cellector_ctx *c, MtxInput *in, uint64_t first_hint, JoinTokens *first, JoinTokens *second, JoinPhases *ph);

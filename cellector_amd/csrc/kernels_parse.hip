@@ -821,6 +821,16 @@ static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size
     return CELLECTOR_OK;
 }
 
+// the window of a single-device ingest of the pair, and whether a file goes through the windows at all
+static uint64_t pair_window(const cellector_ctx *c, const MtxInput *in)
+{
+    return pw_window(in, 96, 32ull << 20, PW_WINDOW, "CELLECTOR_WINDOW_MB" /*the sweep*/, c->parse_window_opt > 0 ? (uint64_t)c->parse_window_opt : 0);
+}
+static bool file_windowed(const cellector_ctx *c, const FileBytes &f, size_t data_off)
+{
+    return c->parse_window_opt > 0 || !f.data || f.size - data_off >= PW_MIN;
+}
+
 cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellector_ctx *helper)
 {
     FileBytes &fa = in->fa, &fr = in->fr;
@@ -844,10 +854,8 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     // window: 1/96 of the bigger file, 32 MB .. PW_WINDOW.  (Pinning and releasing 3 x 256 MB of upload buffers is 0.1-0.15 s
     // of a 0.39 s ingest of 2 x 2.9 GB: 32 MB windows take 0.245 s there; at 2 x 31 GB the window size makes no difference,
     // 256 MB stays.  tools/window_sweep.sh)
-    const uint64_t win = pw_window(in, 96, 32ull << 20, PW_WINDOW, "CELLECTOR_WINDOW_MB" /*the sweep*/,
-                                   c->parse_window_opt > 0 ? (uint64_t)c->parse_window_opt : 0);
-    const bool win_a = c->parse_window_opt > 0 || !fa.data || fa.size - off_a >= PW_MIN;
-    const bool win_r = c->parse_window_opt > 0 || !fr.data || fr.size - off_r >= PW_MIN;
+    const uint64_t win = pair_window(c, in);
+    const bool win_a = file_windowed(c, fa, off_a), win_r = file_windowed(c, fr, off_r);
     if (helper) {  // the ref file on the helper's device, concurrently (its own ring of window buffers, its own stream)
         DevBuf<uint32_t> r_h;
         unsigned long long bad_r = ~0ull;
@@ -948,5 +956,49 @@ cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellect
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     lap("tokenise + zip + filter");
     if (e != hipSuccess) return ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
+    return CELLECTOR_OK;
+}
+
+// ---- the joined ingest's tokens (kernels_join.hip joins them) -------------------------------------------------------------------
+cellector_status join_size_lines(const cellector_ctx *c, const MtxInput *in, uint64_t *first_hint)
+{
+    std::string third;
+    uint64_t tl = 0, tc = 0;
+    const size_t off = skip_header(in->fa, &third);
+    if (!host_tok_u64(third, 0, &tl) || !host_tok_u64(third, 1, &tc))
+        return ctx_fail(c, CELLECTOR_EPARSE, "FIRST file: cannot parse the matrix market size line");
+    if (tl != in->total_loci || tc != in->total_cells)
+        return ctx_fail(c, CELLECTOR_EINVAL, "join: the size lines disagree: FIRST has %llu loci x %llu cells, SECOND %llu x %llu",
+                        (unsigned long long)tl, (unsigned long long)tc, (unsigned long long)in->total_loci, (unsigned long long)in->total_cells);
+    if (!host_tok_u64(third, 2, first_hint) || *first_hint > (in->fa.size - off) / 4) *first_hint = 0;  // (as mtx_input_open treats SECOND's)
+    return CELLECTOR_OK;
+}
+
+// (No pre-mapping thread here: the aligned ingest's is sized for token arrays that BECOME the staged COO; this route's COO is
+// allocated by the join, once the number of distinct keys is known, and the token arrays go back to the cache before the build.)
+cellector_status join_parse_pair(cellector_ctx *c, MtxInput *in, uint64_t first_hint, JoinTokens *first, JoinTokens *second, JoinPhases *ph)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    LapTimer t;
+    ParseStatus ps;
+    CHK(ps.init(c, false));
+    const uint64_t win = pair_window(c, in);
+    const bool win_a = file_windowed(c, in->fa, in->off_a), win_r = file_windowed(c, in->fr, in->off_r);
+    {
+        PwBuffers B;  // one ring of window buffers for both files
+        if (win_a || win_r) {
+            const uint64_t longest = std::max(win_a ? in->fa.size - in->off_a : 0, win_r ? in->fr.size - in->off_r : 0);
+            CHK(B.make(c, win, pw_ring(pw_windows(longest, win))));
+        }
+        CHK((parse_file<true>(c, in->fa, in->off_a, win_a, B, first_hint, &first->locus, &first->cell, &first->count, &first->n, ps.bad)));
+        ph->tokens_first = t.lap();
+        CHK((parse_file<true>(c, in->fr, in->off_r, win_r, B, in->nnz_hint, &second->locus, &second->cell, &second->count, &second->n, ps.bad + 1)));
+    }
+    CHK(ps.read(c, false));
+    ph->tokens_second = t.lap();
+    for (int s = 0; s < 2; s++)  // (every line of a file counts here: no file is cut at the other one's length)
+        if (ps.h_bad[s] != ~0ull)
+            return ctx_fail(c, CELLECTOR_EPARSE, "%s file: cannot parse mtx entry %llu (line %llu of the data section)", s ? "SECOND" : "FIRST",
+                            ps.h_bad[s], ps.h_bad[s] + 1);
     return CELLECTOR_OK;
 }

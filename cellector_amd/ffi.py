@@ -39,6 +39,9 @@ SIGNATURES = {
     "cellector_ingest_finish": (_i, [_vp, _u64, _u64]),
     "cellector_load_mtx": (_i, [_vp, _cp, _cp, _u64, _u64]),
     "cellector_load_coo": (_i, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _u64]),
+    "cellector_ingest_mtx_joined": (_i, [_vp, _cp, _cp, _i, _vp]),
+    "cellector_load_mtx_joined": (_i, [_vp, _cp, _cp, _i, _u64, _u64, _vp]),
+    "cellector_ingest_coo_joined": (_i, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _vp]),
     "cellector_dims": (_i, [_vp, _vp]),
     "cellector_locus_ids": (_i, [_vp, _vp]),
     "cellector_locus_counts": (_i, [_vp, _vp]),
@@ -184,6 +187,18 @@ class AmbientSummary(C.Structure):
                 ("source_rho", _d * 64), ("source_se", _d * 64), ("source_cells", _u64 * 64)]
 
 
+class JoinSummary(C.Structure):
+    _fields_ = [("n_first", _u64), ("n_second", _u64), ("n_both", _u64), ("n_first_only", _u64), ("n_second_only", _u64), ("n_out", _u64),
+                ("first_sorted", C.c_uint32), ("second_sorted", C.c_uint32), ("join_tile", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        """the fields join.join_coo returns as its summary"""
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+JOIN_MODES = {"join": 1, "ref": 1, "depth": 2, 1: 1, 2: 2}
+
+
 class CellectorError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {message}")
@@ -319,6 +334,31 @@ class Cellector:
     def load_coo(self, total_loci, total_cells, locus0, cell0, alt, ref, min_alt=4, min_ref=4):
         self.ingest_coo(total_loci, total_cells, locus0, cell0, alt, ref)
         self.ingest_finish(min_alt, min_ref)
+
+    # ---- joined ingest: two count matrices keyed by (locus, cell); mode "ref" / 1 (SECOND = ref counts) or "depth" / 2 (alt + ref)
+    def ingest_mtx_joined(self, first_path, second_path, mode="ref"):
+        """Stage the join of two .mtx files that need not list the same keys in the same order (cellector_ingest_mtx_joined;
+        join.join_coo is the bit-identical numpy twin).  Returns the JoinSummary."""
+        s = JoinSummary()
+        self._ck(self._lib.cellector_ingest_mtx_joined(self.h, str(first_path).encode(), str(second_path).encode(), int(JOIN_MODES.get(mode, mode)), C.byref(s)))
+        return s
+
+    def load_mtx_joined(self, first_path, second_path, mode="ref", min_alt=4, min_ref=4):
+        s = JoinSummary()
+        self._ck(self._lib.cellector_load_mtx_joined(self.h, str(first_path).encode(), str(second_path).encode(), int(JOIN_MODES.get(mode, mode)), min_alt,
+                                                     min_ref, C.byref(s)))
+        return s
+
+    def ingest_coo_joined(self, total_loci, total_cells, first, second, mode="ref"):
+        """first, second: (locus0, cell0, count) triples in any order, e.g. (m.row, m.col, m.data) of two scipy COO matrices"""
+        arrs = [[np.ascontiguousarray(a, dtype=np.uint32).ravel() for a in t] for t in (first, second)]
+        for t in arrs:
+            if len(t) != 3 or not (t[0].shape == t[1].shape == t[2].shape):
+                raise ValueError("ingest_coo_joined: a stream is three arrays of one length: (locus0, cell0, count)")
+        s = JoinSummary()
+        self._ck(self._lib.cellector_ingest_coo_joined(self.h, total_loci, total_cells, len(arrs[0][0]), *[_p(a) for a in arrs[0]],
+                                                       len(arrs[1][0]), *[_p(a) for a in arrs[1]], int(JOIN_MODES.get(mode, mode)), C.byref(s)))
+        return s
 
     def load_synthetic(self, total_loci, total_cells, density, seed=4, minority_fraction=0.05, doublet_fraction=0.0,
                        min_alt=4, min_ref=4):

@@ -421,6 +421,20 @@ void check_cell_in_matrix(const char *flag, std::string_view barcode, uint64_t c
                    " but the matrix has " + std::to_string(matrix_cells) + " cells");
 }
 
+// a pair's entries staged: zipped line by line, the reference's reading, or under --matrix_pair join | depth joined by (locus, cell)
+cellector_status ingest_pair(const Params &params, cellector_ctx *c, const std::string &first, const std::string &second)
+{
+    if (!params.matrix_pair) return cellector_ingest_mtx(c, first.c_str(), second.c_str());
+    cellector_join_summary s;
+    const cellector_status st = cellector_ingest_mtx_joined(c, first.c_str(), second.c_str(), params.matrix_pair, &s);
+    if (st == CELLECTOR_OK)
+        fprintf(stderr, "matrix_pair %s: %llu entries of %s, %llu of %s: %llu keys in both, %llu only in the first, %llu only in the second, %llu staged\n",
+                params.matrix_pair == CELLECTOR_JOIN_DEPTH ? "depth" : "join", (unsigned long long)s.n_first, first.c_str(),
+                (unsigned long long)s.n_second, second.c_str(), (unsigned long long)s.n_both, (unsigned long long)s.n_first_only,
+                (unsigned long long)s.n_second_only, (unsigned long long)s.n_out);
+    return st;
+}
+
 // --mix_*: the second dataset, staged in a ctx of its own on the same GPU, merged in, released
 void combine_second_dataset(const Run &run)
 {
@@ -429,7 +443,7 @@ void combine_second_dataset(const Run &run)
     const Ctx &g = run.g;
     Ctx second;
     if (cellector_create(&second.c, run.devices[0]) != CELLECTOR_OK) die(EXIT_PANIC, "cellector: no second context on the device");
-    second.ck(cellector_ingest_mtx(second.c, params.mix_alt->c_str(), params.mix_ref->c_str()), "load_cell_data (--mix_alt / --mix_ref)");
+    second.ck(ingest_pair(params, second.c, *params.mix_alt, *params.mix_ref), "load_cell_data (--mix_alt / --mix_ref)");
     cellector_dims_t ours, theirs;
     g.ck(cellector_dims(g.c, &ours), "dims");
     second.ck(cellector_dims(second.c, &theirs), "dims");
@@ -482,10 +496,13 @@ void load_matrix(Run &run)
     const Params &params = run.params;
     const RunInputs &in = run.in;
     const Ctx &g = run.g;
-    if (!params.restage() && !params.mix() && !params.doublets) {
+    if (!params.restage() && !params.mix() && !params.doublets && !params.matrix_pair) {
         g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
+    } else if (!params.restage() && !params.mix() && !params.doublets) {
+        g.ck(ingest_pair(params, g.c, params.alt_mtx, params.ref_mtx), "load_cell_data");
+        g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
     } else {  // --cells / --downsample_rate: the staged matrix is cut and thinned on the device before the locus filter sees it
-        g.ck(cellector_ingest_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str()), "load_cell_data");
+        g.ck(ingest_pair(params, g.c, params.alt_mtx, params.ref_mtx), "load_cell_data");
         cellector_dims_t staged;
         g.ck(cellector_dims(g.c, &staged), "dims");
         std::vector<uint8_t> keep;

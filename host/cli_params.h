@@ -58,6 +58,9 @@ struct Params {
     // extension: the fit of every cell's called hypothesis, and the cells no genotyped donor explains (cellector_donor_fit)
     bool donor_fit = false;
     std::optional<double> donor_fit_iqr;               // the multiple of the iqr below the lower quartile (default: the library's, 3)
+    // extension: how -a / -r (and --mix_alt / --mix_ref) belong together: 0 = zipped line by line (the reference's reading),
+    // CELLECTOR_JOIN_REF = joined by (locus, cell), CELLECTOR_JOIN_DEPTH = likewise, -r holding alt + ref (cellector_ingest_mtx_joined)
+    int matrix_pair = 0;
 };
 
 // ---- one row of the option table --------------------------------------------------------------------------------
@@ -322,6 +325,18 @@ inline const std::vector<Opt> &options()
         Opt("donor_fit_iqr", 0, Kind::F64, &P::donor_fit_iqr).as("--donor_fit_iqr <k>").within({0.0, INFINITY, false, false}, "expected a number >= 0")
             .requires_option("donor_fit").paragraph(
             "        --donor_fit_iqr <k>                                                with --donor_fit: the multiple k (default 3)\n"),
+        Opt("matrix_pair", 0, Kind::WORD_USAGE, &P::matrix_pair).as("--matrix_pair <aligned|join|depth>")
+            .one_of("aligned|join|depth", "expected aligned, join or depth").on_one_gpu("--matrix_pair %s").paragraph(
+            "        --matrix_pair <aligned|join|depth>                                 how the lines of -a and -r belong together.  aligned (default):\n"
+            "                                                                       line i of -r belongs to line i of -a, the reference's reading;\n"
+            "                                                                       the indices of -r are never looked at.  join: the two files are\n"
+            "                                                                       joined by (locus, cell) on the GPU; either may lack the other's\n"
+            "                                                                       keys (dropped zero lines) and be in any order, a missing count\n"
+            "                                                                       is 0.  depth: the same join, -r holding the total depth alt + ref\n"
+            "                                                                       (an AD / DP pair); a key whose depth is below its alt count is an\n"
+            "                                                                       error.  A key listed twice in one file is an error in both.  The\n"
+            "                                                                       --mix_alt / --mix_ref pair is read the same way.  One stderr line\n"
+            "                                                                       counts the keys; no output changes (not in the reference; one GPU)\n"),
     };
     return table;
 }
@@ -471,7 +486,7 @@ inline Params load_params(int argc, char **argv)
 
     if (!p.one_gpu())
         for (const Opt &o : options())
-            if (o.one_gpu && in_force(o)) {
+            if (o.one_gpu && in_force(o) && !(o.kind == Kind::WORD_USAGE && got[o.name] == split(o.words, '|')[0])) {  // (its default word asks for nothing)
                 std::string quoted = o.one_gpu;
                 if (const size_t at = quoted.find("%s"); at != std::string::npos) quoted.replace(at, 2, got[o.name]);
                 die(1, "error: The argument '" + quoted + "' works on one GPU and cannot be used with '--devices <a,b,...>'");

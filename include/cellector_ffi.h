@@ -208,6 +208,64 @@ cellector_status cellector_load_coo(cellector_ctx *ctx, uint64_t total_loci, uin
                                     const uint32_t *alt, const uint32_t *ref, uint64_t min_alt,
                                     uint64_t min_ref);
 
+/* ---- joined ingest: two count matrices keyed by (locus, cell) instead of zipped line by line -----------------
+ * cellector_ingest_mtx reads the pair like the reference's izip! (load_data.rs:190-197): line i of the ref file belongs to line i
+ * of the alt file and the ref file's indices are never read.  A pair whose files do not list the same keys in the same order —
+ * zero lines dropped, filtered or sorted by another tool — or an alt-depth / total-depth pair (AD / DP, each file listing its
+ * own non-zero keys) cannot be read that way.  The joined ingests take two streams of (locus, cell, count), FIRST and SECOND,
+ * each in ANY order, and stage their join.  Opt-in: the aligned ingests do not change.
+ *   Dims: both size lines must give the same total_loci and total_cells (CELLECTOR_EINVAL otherwise; the COO form takes them as
+ *   arguments).
+ *   mode CELLECTOR_JOIN_REF: SECOND holds ref counts.  One entry per distinct (locus, cell) that occurs in either stream;
+ *   alt = FIRST's count there or 0, ref = SECOND's count there or 0.
+ *   mode CELLECTOR_JOIN_DEPTH: SECOND holds alt + ref.  The same keys, the same alt; ref = depth - alt, an absent depth counting
+ *   as 0.  A key with depth < alt is refused.
+ *   Order: the staged COO ascends STRICTLY by (locus, cell), whatever order either stream had, and is locus-major.
+ *   Zeros: a line with an explicit count 0 is a key like any other, so a (0, 0) entry exists only if a stream lists it.
+ *   Equality with the aligned reader: the result is, array for array, what cellector_ingest_mtx stages from the COMPLETED pair:
+ *   both files rewritten over the union of their keys in ascending order, with explicit zeros (mode DEPTH: the second one
+ *   holding depth - alt).  cellector_amd/join.py is the bit-identical numpy twin.
+ *   Refusals, each naming the smallest offender of its kind, checked in this order:
+ *     1. a line that does not parse, in FIRST, then in SECOND (every line of a file counts: no file is cut at the other one's
+ *        length): CELLECTOR_EPARSE, the aligned reader's words behind "FIRST file: " / "SECOND file: ";
+ *     2. index 0 (text), a locus or cell out of range, a count above 65535, in FIRST, then in SECOND: CELLECTOR_EINVAL,
+ *        "join: FIRST entry <i>: <what>", i the 0-based position in the stream, the words those of cellector_ingest_mtx;
+ *     3. a key listed twice within one stream, FIRST, then SECOND: CELLECTOR_EINVAL, "join: SECOND lists (locus l, cell c)
+ *        twice", 1-based, the smallest such key.  (The aligned reader keeps repeated lines as separate entries; a join cannot
+ *        know which line of the other stream belongs to which.);
+ *     4. mode DEPTH: CELLECTOR_EINVAL, "join: depth below alt at (locus l, cell c)", 1-based, the smallest such key.
+ *   A refusal leaves the ctx as a failed cellector_ingest_mtx leaves it: the former matrix dropped, nothing staged.
+ *   Scope, as cellector_restage: a single-device ctx without a communicator of more than one rank and without a
+ *   cellector_set_shard range, engines 1 and 2; anything else is CELLECTOR_EINVAL with the ctx untouched, as are a mode other
+ *   than the two, size lines that disagree and a file that cannot be opened.  Option keep_coo is honoured as by any ingest,
+ *   option parse_window as by cellector_ingest_mtx (each file is windowed exactly when that call would window it).
+ *   Afterwards the ctx is STAGED; cellector_ingest_finish follows unchanged.
+ *   Memory: the tokens of both streams (12 B per entry; 20 B while a side's keys are formed) and 8 B + 4 B per entry of a side
+ *   that has to be sorted, beside the staged COO (12 B per distinct key); the tokens are released as soon as the COO is written.
+ *   The pre-mapping thread of the aligned text ingest is left out of this route: it is sized for token arrays that become the
+ *   COO, and here the COO's size is known only after the join's first pass.
+ *   CELLECTOR_TIMING=1 prints one line with the phases: tokens FIRST, tokens SECOND, checks, sorts, join (and the join
+ *   kernels' GPU time between two events). */
+#define CELLECTOR_JOIN_REF 1
+#define CELLECTOR_JOIN_DEPTH 2
+typedef struct {
+    uint64_t n_first, n_second;   /* entries read                                                             */
+    uint64_t n_both, n_first_only, n_second_only, n_out; /* keys in both / one stream; n_out = their sum       */
+    uint32_t first_sorted, second_sorted; /* 1: the stream arrived strictly ascending, no sort ran            */
+    uint32_t join_tile;           /* steps through the two streams one block of the join kernels walks; it    */
+                                  /* writes at most join_tile + 1 entries                                     */
+    uint32_t reserved;
+} cellector_join_summary;
+cellector_status cellector_ingest_mtx_joined(cellector_ctx *ctx, const char *first_path, const char *second_path, int mode,
+                                             cellector_join_summary *out /*may be NULL*/);
+cellector_status cellector_load_mtx_joined(cellector_ctx *ctx, const char *first_path, const char *second_path, int mode,
+                                           uint64_t min_alt, uint64_t min_ref, cellector_join_summary *out /*may be NULL*/);
+/* two caller COO streams, 0-based indices, any order (what a caller holding two sparse matrices has) */
+cellector_status cellector_ingest_coo_joined(cellector_ctx *ctx, uint64_t total_loci, uint64_t total_cells, uint64_t n_first,
+                                             const uint32_t *locus0_a, const uint32_t *cell0_a, const uint32_t *count_a,
+                                             uint64_t n_second, const uint32_t *locus0_b, const uint32_t *cell0_b,
+                                             const uint32_t *count_b, int mode, cellector_join_summary *out /*may be NULL*/);
+
 typedef struct {
     uint64_t total_cells, total_loci; /* header dims (consume_mtx_header, load_data.rs:206-223) */
     uint64_t loci_used;               /* L = loci passing the filter                            */
