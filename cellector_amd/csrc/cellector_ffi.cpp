@@ -2042,6 +2042,92 @@ cellector_status cellector_estimate_ambient(cellector_ctx *c, const uint8_t *gt,
     return ambient_estimate_run(c, gt, n_sources, assign, &prm, mask, summary, cell_rho, cell_se, n_entries);
 }
 
+// ---- donor pair fractions: kernels_pair_fraction.hip ----------------------------------------------------------------
+cellector_status cellector_pair_fraction_default_params(cellector_pair_fraction_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->min_fraction = 0.1;
+    out->min_loci = 1;
+    return CELLECTOR_OK;
+}
+
+// the grid of a pair fraction call: the caller's, checked, or the default j / 16.0; grid [32] receives it
+static cellector_status pair_fraction_grid_check(cellector_ctx *c, const char *what, const double *frac, uint32_t *G, double *grid)
+{
+    if (!frac) {
+        *G = 17;
+        for (uint32_t j = 0; j < 17; j++) grid[j] = (double)j / 16.0;
+        return CELLECTOR_OK;
+    }
+    if (*G < 4 || *G > 32) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u grid points, 4..32 are supported", what, *G);
+    for (uint32_t j = 0; j < *G; j++) {
+        if (!(frac[j] >= 0.0 && frac[j] <= 1.0)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: frac[%u] = %g is not within [0, 1]", what, j, frac[j]);
+        if (j && !(frac[j] > frac[j - 1]))
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: frac[%u] = %g is not above frac[%u] = %g: the grid ascends strictly", what, j, frac[j],
+                            j - 1, frac[j - 1]);
+        grid[j] = frac[j];
+    }
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_pair_fraction_tables(cellector_ctx *c, const cellector_donor_params *donor_params, const double *frac, uint32_t n_grid,
+                                                const uint8_t *mask, double *tab)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (donor_params) prm = *donor_params;
+    CHK(locus_moments_scope(c, "pair_fraction_tables"));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "pair_fraction_tables: iteration in flight (finish it with cellector_em_finish)");
+    CHK(donor_params_check(c, "pair_fraction_tables", &prm /*(the tables depend on no donor)*/, "gt", 1, &prm));
+    double grid[32];
+    uint32_t G = n_grid;
+    CHK(pair_fraction_grid_check(c, "pair_fraction_tables", frac, &G, grid));
+    SETDEV(c);
+    return pair_fraction_tables_run(c, &prm, grid, G, mask, tab);
+}
+
+cellector_status cellector_donor_pair_fractions(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, const cellector_donor_params *donor_params,
+                                                const cellector_pair_fraction_params *params, const uint8_t *pair_a, const uint8_t *pair_b,
+                                                const double *frac, uint32_t n_grid, const uint8_t *mask, double *ll, uint32_t *n_entries,
+                                                double *cell_frac, double *cell_se, uint8_t *j_star, uint8_t *kind,
+                                                cellector_pair_fraction_summary *summary, double *tab)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    const char *what = "donor_pair_fractions";
+    cellector_donor_params prm;
+    cellector_donor_default_params(&prm);
+    if (donor_params) prm = *donor_params;
+    cellector_pair_fraction_params fp;
+    cellector_pair_fraction_default_params(&fp);
+    if (params) fp = *params;
+    CHK(donor_call_check(c, what, gt, n_donors, &prm));
+    const uint32_t D = n_donors;
+    if (!pair_a) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null pair_a", what);
+    if (!pair_b) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null pair_b", what);
+    for (uint64_t i = 0; i < c->nloc; i++) {
+        if (pair_a[i] == 255) continue;
+        if (pair_a[i] >= D)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: pair_a of cell %llu is %u, neither 255 nor below the %u donors", what, (unsigned long long)i,
+                            (unsigned)pair_a[i], D);
+        if (pair_b[i] >= D)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: pair_b of cell %llu is %u, not below the %u donors", what, (unsigned long long)i,
+                            (unsigned)pair_b[i], D);
+        if (pair_b[i] == pair_a[i])
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: pair_b of cell %llu is %u, its pair_a: a pair is two donors", what, (unsigned long long)i,
+                            (unsigned)pair_b[i]);
+    }
+    double grid[32];
+    uint32_t G = n_grid;
+    CHK(pair_fraction_grid_check(c, what, frac, &G, grid));
+    if (!(fp.min_fraction >= 0.0 && fp.min_fraction <= 0.5))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: min_fraction = %g is not within [0, 0.5]", what, fp.min_fraction);
+    if (fp.min_loci < 1) return ctx_fail(c, CELLECTOR_EINVAL, "%s: min_loci must be at least 1", what);
+    SETDEV(c);
+    return pair_fractions_run(c, gt, D, &prm, &fp, pair_a, pair_b, grid, G, mask, ll, n_entries, cell_frac, cell_se, j_star, kind, summary, tab);
+}
+
 // ---- class genotypes: kernels_genotypes.hip and genotype_host.h ---------------------------------------------
 // load_mtx_final + the rule of output_final_vcf (main.rs:52-131) for the K classes of a labelling
 cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, double ambient, double gt_threshold,

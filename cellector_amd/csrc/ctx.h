@@ -606,6 +606,13 @@ cellector_status ambient_profile_run(cellector_ctx *c, const uint8_t *gt, uint32
 cellector_status ambient_estimate_run(cellector_ctx *c, const uint8_t *gt, uint32_t S, const uint8_t *assign, const cellector_ambient_params *p,
                                       const uint8_t *mask, cellector_ambient_summary *out, double *cell_rho, double *cell_se,
                                       uint32_t *n_entries);
+// donor pair fractions (kernels_pair_fraction.hip) on one device holding all cells; validated arguments, host arrays, scratch of their own
+cellector_status pair_fraction_tables_run(cellector_ctx *c, const cellector_donor_params *prm, const double *frac, uint32_t G,
+                                          const uint8_t *mask, double *tab);
+cellector_status pair_fractions_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, const cellector_donor_params *prm,
+                                    const cellector_pair_fraction_params *fp, const uint8_t *pair_a, const uint8_t *pair_b, const double *frac,
+                                    uint32_t G, const uint8_t *mask, double *ll, uint32_t *n_entries, double *cell_frac, double *cell_se,
+                                    uint8_t *j_star, uint8_t *kind, cellector_pair_fraction_summary *out, double *tab);
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
 cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);

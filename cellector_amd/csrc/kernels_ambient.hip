@@ -10,45 +10,14 @@
 //   k_ambient_fold    block s < S: the cells of source s, block S: every cell that takes part; G ordered sums of the cells' rows
 // All scratch belongs to the call.  Nothing of the ctx is written: the EM state, its tables and its outputs stay.
 #include "lane_rows.h"
+#include "vertex.h"
 
 #include <cmath>
 
 #define AM_NONE 255
 #define AM_MIN_GP 4  // the lane width of the smallest grid: the tail reads three points of it
 #define AM_MAX_G 32
-#define AM_FLAT 0x1p-40  // two steps of a profile that both stay within this share of its value are rounding, not signal (the header)
-
-// The vertex of the parabola through (x0, y0), (x1, y1), (x2, y2), the operations in the header's order.  curv = its second
-// derivative, 0 where neither step of y is resolved (|y1 - y0| and |y2 - y1| both <= AM_FLAT |y1|).  curv < 0: est = the vertex
-// clamped into [x0, x2], se = 1 / sqrt(-curv); otherwise (flat, convex, or not a number) est = flat, se = +inf.
-__host__ __device__ static inline void am_vertex(double x0, double x1, double x2, double y0, double y1, double y2, double flat, double *est,
-                                                 double *se, double *curv)
-{
-    const double h0 = x1 - x0, h1 = x2 - x1;
-    const double e0 = y1 - y0, e1 = y2 - y1;
-    const double d0 = e0 / h0, d1 = e1 / h1;
-    const double dd = d1 - d0, hs = h0 + h1;
-    const double two = 2.0 * dd;
-    const double lim = AM_FLAT * fabs(y1);
-    const bool resolved = fabs(e0) > lim || fabs(e1) > lim;
-    const double c = resolved ? two / hs : 0.0;
-    *curv = c;
-    if (c < 0.0) {
-        const double sx = x0 + x1;
-        const double mid = 0.5 * sx;
-        const double q = d0 / c;
-        double v = mid - q;
-        if (v < x0) v = x0;
-        if (v > x2) v = x2;
-        const double nc = -c;
-        const double r = sqrt(nc);
-        *est = v;
-        *se = 1.0 / r;
-    } else {
-        *est = flat;
-        *se = INFINITY;
-    }
-}
+// (AM_FLAT and am_vertex, the vertex rule of the tail and of the host folds: vertex.h, shared with kernels_pair_fraction.hip)
 
 // thread (l, g, j) of tab [L][4][G]: soup and e_g as k_donor_tables makes them; a masked locus carries (0, 0)
 __global__ __launch_bounds__(LANE_THREADS) void k_ambient_tables(uint64_t n /*4 L G*/, uint32_t G, const double *__restrict__ s_alt,
@@ -100,7 +69,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_ambient_e(uint64_t n_rows, uin
         const uint32_t s_word = part ? src >> 5 : 0u, s_shift = 2u * (src & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit, k_pair_fraction_e and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t[LANE_AHEAD];

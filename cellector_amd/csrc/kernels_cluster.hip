@@ -61,7 +61,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_cluster_e(uint64_t n_rows, uin
         double acc = 0.0;
         unsigned long long depth = 0;
         uint32_t cnt = 0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_donor_fit, k_ambient_e and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_donor_fit, k_ambient_e, k_pair_fraction_e and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t[LANE_AHEAD];

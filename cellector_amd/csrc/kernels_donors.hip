@@ -162,7 +162,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_donor_e(uint64_t n_rows, uint3
         const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
         double acc = 0.0;
         uint32_t cnt = 0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_ambient_e, k_donor_fit and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_cluster_e, k_ambient_e, k_donor_fit, k_pair_fraction_e and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t[LANE_AHEAD];
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(64) void k_donor_match(uint64_t L, uint32_t D, uint
     const uint32_t my_word = d >> 5, my_shift = 2u * (d & 31u);
     const unsigned long long *const ak = alt + (uint64_t)k * L, *const rk = ref + (uint64_t)k * L;
     double acc = 0.0;
-    // the entry loop of lane_rows.h over loci: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit and k_ambient_e as well
+    // the entry loop of lane_rows.h over loci: a fix here belongs in k_cluster_e, k_donor_e, k_donor_fit, k_ambient_e and k_pair_fraction_e as well
     for (uint64_t l0 = 0; l0 < L; l0 += LANE_AHEAD) {
         double av[LANE_AHEAD], rv[LANE_AHEAD];
         double2 t[LANE_AHEAD];
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_donor_fit(uint64_t n_rows, uin
         if (a >= D) a = 0;  // (never: the donor call checked a given anchor, or wrote a donor)
         const uint32_t a_word = a >> 5, a_shift = 2u * (a & 31u);
         double E = 0.0, V = 0.0, PE = 0.0, PV = 0.0;
-        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_cluster_e, k_ambient_e and k_donor_match as well
+        // the entry loop of lane_rows.h: a fix here belongs in k_donor_e, k_cluster_e, k_ambient_e, k_pair_fraction_e and k_donor_match as well
         for (uint64_t i = beg; i < end; i += LANE_AHEAD) {
             uint64_t en[LANE_AHEAD];
             double2 t1[LANE_AHEAD], t2[LANE_AHEAD];

@@ -1,6 +1,7 @@
 // The lane-per-column geometry of the cell passes that score every row of a CSR against a handful of columns: the restarts' clusters
-// (kernels_cluster.hip), the donors (kernels_donors.hip), the grid points of an ambient profile (kernels_ambient.hip).  The shape is
-// stated here once; those files say only what their columns and their table rows are.
+// (kernels_cluster.hip), the donors (kernels_donors.hip), the grid points of an ambient profile (kernels_ambient.hip) or of a donor
+// pair's mixing share (kernels_pair_fraction.hip).  The shape is stated here once; those files say only what their columns and their
+// table rows are.
 //
 // A group of P lanes (P = the power of two >= the columns, 64 / P rows per wave) owns one row, and a lane is one column: it owns the
 // (row, column) sum and walks the row's entries in order, so every sum is strictly sequential (the bits depend on the matrix alone)
@@ -9,8 +10,8 @@
 // the sum; a masked locus adds nothing and is not counted.  Behind the walk comes a tail in which EVERY lane of the wave takes part in
 // the shuffles, whatever its row and column: a lane without a row or a column walks nothing and carries a neutral value.
 //
-// The entry loop itself stays in each kernel (k_cluster_e, k_donor_e, k_donor_fit, k_ambient_e, and over loci k_donor_match; each
-// loop names the others): one loop behind a callable for the table lookup was measured and did not hold the speed of the separate
+// The entry loop itself stays in each kernel (k_cluster_e, k_donor_e, k_donor_fit, k_ambient_e, k_pair_fraction_e, and over loci
+// k_donor_match; each loop names the others): one loop behind a callable for the table lookup was measured and did not hold the speed of the separate
 // loops in every pass.  What is shared is everything around it: the constants, the geometry, the argmax of the tails, and
 // on the host the grid, the width, the width dispatch, the mask and the timing events.
 //

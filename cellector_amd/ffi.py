@@ -105,6 +105,9 @@ SIGNATURES = {
     "cellector_ambient_tables": (_i, [_vp, _vp, C.c_uint32, _d, _vp, _vp]),
     "cellector_ambient_profile": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _d, _u64, _vp] + [_vp] * 8),
     "cellector_estimate_ambient": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp] + [_vp] * 4),
+    "cellector_pair_fraction_default_params": (_i, [_vp]),
+    "cellector_pair_fraction_tables": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "cellector_donor_pair_fractions": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp] + [_vp] * 8),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -185,6 +188,15 @@ class AmbientSummary(C.Structure):
     _fields_ = [("rho", _d), ("se", _d), ("curvature", _d), ("log_likelihood", _d), ("lo", _d), ("hi", _d), ("j_star", C.c_uint32),
                 ("at_boundary", C.c_uint32), ("rounds", C.c_uint32), ("reserved", C.c_uint32), ("n_cells_used", _u64),
                 ("source_rho", _d * 64), ("source_se", _d * 64), ("source_cells", _u64 * 64)]
+
+
+class PairFractionParams(C.Structure):
+    _fields_ = [("min_fraction", _d), ("min_loci", _u64)]
+
+
+class PairFractionSummary(C.Structure):
+    _fields_ = [("n_balanced", _u64), ("n_toward_a", _u64), ("n_toward_b", _u64), ("n_flat", _u64), ("n_none", _u64),
+                ("donor_cells", _u64 * 64)]
 
 
 class JoinSummary(C.Structure):
@@ -1121,6 +1133,64 @@ class Cellector:
                                           "n_cells_used")}
         out.update(source_rho=np.array(s.source_rho[:Sa]), source_se=np.array(s.source_se[:Sa]),
                    source_cells=np.array(s.source_cells[:Sa], np.uint64), cell_rho=cell_rho, cell_se=cell_se, n_entries=cnt, summary=s)
+        return out
+
+    # ---- donor pair fractions: every cell under a pair of donors (pair_a, pair_b [cells] uint8, pair_a 255: the cell takes no part)
+    # at G shares f of donor a at once; pair_fraction.py is the numpy twin
+    def pair_fraction_default_params(self):
+        p = PairFractionParams()
+        self._ck(self._lib.cellector_pair_fraction_default_params(C.byref(p)))
+        return p
+
+    @staticmethod
+    def _pair_fraction_grid(frac):
+        if frac is None:
+            return None, 17
+        frac = np.ascontiguousarray(frac, np.float64)
+        if frac.ndim != 1:
+            raise ValueError(f"frac: one dimension expected, got shape {frac.shape}")
+        return frac, len(frac)
+
+    def pair_fraction_tables(self, frac=None, mask=None, donor_params=None):
+        """The per-locus tables of one grid of pair fractions alone (cellector_pair_fraction_tables): dict of tab [L, 16, G, 2] = (log
+        theta, log(1 - theta)) at index 4 g_a + g_b, theta = f_j theta_ga + (1 - f_j) theta_gb, and frac [G], the grid used (None:
+        j / 16).  donor_params: a dict of err, ambient (DonorParams)."""
+        TL = self.dims().total_loci
+        _, _, mask, p = self._donor_args(np.zeros((1, TL), np.uint8), mask, dict(donor_params or {}))
+        frac, G = self._pair_fraction_grid(frac)
+        tab = np.zeros((self.dims().loci_used, 16, min(max(G, 1), 32), 2), np.float64)
+        self._ck(self._lib.cellector_pair_fraction_tables(self.h, C.byref(p), _p(frac), G, _p(mask), _p(tab)))
+        return dict(tab=tab, frac=np.arange(17) / 16.0 if frac is None else frac)
+
+    def donor_pair_fractions(self, gt, pair_a, pair_b, frac=None, params=None, donor_params=None, mask=None, tables=False):
+        """The share of every cell's reads that come from donor pair_a[c] of its pair (pair_a[c], pair_b[c]), profiled over the grid
+        frac [G] (cellector_donor_pair_fractions; None: j / 16, j = 0 ... 16).  params: a dict of min_fraction, min_loci
+        (PairFractionParams); donor_params: a dict of err, ambient (DonorParams).  Returns a dict: ll [cells, G], n_entries,
+        cell_frac, cell_se (NaN for a cell that takes no part or has fewer than min_loci entries), j_star, kind (0 balanced, 1 toward
+        a, 2 toward b, 3 flat, 255 no part) [cells], frac [G], summary (PairFractionSummary) and, with tables, tab [L, 16, G, 2]."""
+        gt, D, mask, p = self._donor_args(gt, mask, dict(donor_params or {}))
+        fp = self.pair_fraction_default_params()
+        for k, v in dict(params or {}).items():
+            if k not in dict(PairFractionParams._fields_):
+                raise TypeError(f"pair fractions: unknown parameter {k!r}")
+            setattr(fp, k, v)
+        n = self.n_local if self.dims().total_cells else 0  # (before a load the library refuses the call)
+        pair_a, pair_b = np.ascontiguousarray(pair_a, np.uint8), np.ascontiguousarray(pair_b, np.uint8)
+        for name, v in (("pair_a", pair_a), ("pair_b", pair_b)):
+            if self.dims().total_cells and v.shape != (n,):
+                raise ValueError(f"{name}: {n} values expected, got shape {v.shape}")
+        frac, G = self._pair_fraction_grid(frac)
+        Ga = min(max(G, 1), 32)
+        out = dict(ll=np.zeros((n, Ga), np.float64), n_entries=np.zeros(n, np.uint32), cell_frac=np.zeros(n, np.float64),
+                   cell_se=np.zeros(n, np.float64), j_star=np.zeros(n, np.uint8), kind=np.zeros(n, np.uint8))
+        if tables:
+            out["tab"] = np.zeros((self.dims().loci_used, 16, Ga, 2), np.float64)
+        s = PairFractionSummary()
+        self._ck(self._lib.cellector_donor_pair_fractions(
+            self.h, _p(gt), D, C.byref(p), C.byref(fp), _p(pair_a), _p(pair_b), _p(frac), G, _p(mask), _p(out["ll"]), _p(out["n_entries"]),
+            _p(out["cell_frac"]), _p(out["cell_se"]), _p(out["j_star"]), _p(out["kind"]), C.byref(s), _p(out.get("tab"))))
+        out["frac"] = np.arange(17) / 16.0 if frac is None else frac
+        out["summary"] = s
         return out
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):

@@ -1269,6 +1269,49 @@ void write_donor_fit(const Run &run, const Donors &d)
     run.lap("cellector_donor_fit.tsv");
 }
 
+// --doublet_fraction: the mixing share of every called doublet under (the donor pass' anchor, its best pair), the hard calls and the
+// parameters the donor pass ended with
+void write_doublet_fractions(const Run &run, const Donors &d, const DonorCalls &calls)
+{
+    static const char *const KIND[4] = {"balanced", "toward_a", "toward_b", "flat"};
+    const uint64_t N = run.N, G = 17;
+    const CellNames &barcodes = run.in.cells;
+    std::vector<uint8_t> pa(N), pb(N);
+    for (uint64_t c = 0; c < N; c++) {
+        const bool dbl = calls.status[c] == 1 && calls.pair[c] != 255;
+        pa[c] = dbl ? calls.best[c] : (uint8_t)255;  // (no anchor was given: the pass anchored every cell at its best donor)
+        pb[c] = dbl ? calls.pair[c] : (uint8_t)255;
+    }
+    cellector_pair_fraction_params fp;
+    cellector_pair_fraction_default_params(&fp);
+    if (run.params.doublet_min_fraction) fp.min_fraction = *run.params.doublet_min_fraction;
+    fp.min_loci = d.dp.min_loci;
+    std::vector<double> ll(N * G), frac(N), se(N);
+    std::vector<uint32_t> cn(N);
+    std::vector<uint8_t> js(N), kind(N);
+    cellector_pair_fraction_summary fs;
+    run.g.ck(cellector_donor_pair_fractions(run.g.c, d.gt_codes(), d.D, &d.dp, &fp, pa.data(), pb.data(), nullptr, 0, nullptr, ll.data(),
+                                            cn.data(), frac.data(), se.data(), js.data(), kind.data(), &fs, nullptr),
+             "donor_pair_fractions");
+    {
+        std::string o = "doublet_fraction: balanced=";
+        put(o, fs.n_balanced); o += " toward_a="; put(o, fs.n_toward_a); o += " toward_b="; put(o, fs.n_toward_b);
+        o += " flat="; put(o, fs.n_flat); o += " none="; put(o, fs.n_none); o += '\n';
+        fputs(o.c_str(), stdout);
+    }
+    write_tsv(run.out("cellector_doublet_fractions.tsv"), "barcode\tdonor_a\tdonor_b\tn_loci\tfraction\tse\tll_half\tll_max\tkind\n", N,
+              [&](uint64_t c, std::string &o) {
+                  o += barcodes[c];
+                  if (pa[c] == 255) { o += "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n"; return; }
+                  o += '\t'; o += d.name(pa[c]); o += '\t'; o += d.name(pb[c]); o += '\t'; put(o, (uint64_t)cn[c]); o += '\t';
+                  if (kind[c] == 255) o += "NA\tNA";
+                  else { put(o, frac[c]); o += '\t'; put(o, se[c]); }
+                  o += '\t'; put(o, ll[c * G + G / 2]); o += '\t'; put(o, ll[c * G + js[c]]); o += '\t';
+                  o += kind[c] < 4 ? KIND[kind[c]] : "NA"; o += '\n';
+              });
+    run.lap("cellector_doublet_fractions.tsv");
+}
+
 // the classes in force named by donor
 void write_cluster_donors(const Run &run, const Donors &d, const ClassLabels &classes)
 {
@@ -1312,6 +1355,7 @@ void run_donors(const Run &run, const ClassLabels &classes)
     }
     write_donors_tsv(run, d, calls);
     if (params.donor_fit) write_donor_fit(run, d);
+    if (params.doublet_fraction) write_doublet_fractions(run, d, calls);
     if (params.classes || params.cluster) write_cluster_donors(run, d, classes);
 }
 

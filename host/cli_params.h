@@ -58,6 +58,9 @@ struct Params {
     // extension: the fit of every cell's called hypothesis, and the cells no genotyped donor explains (cellector_donor_fit)
     bool donor_fit = false;
     std::optional<double> donor_fit_iqr;               // the multiple of the iqr below the lower quartile (default: the library's, 3)
+    // extension: the mixing share of every called doublet's two donors (cellector_donor_pair_fractions)
+    bool doublet_fraction = false;
+    std::optional<double> doublet_min_fraction;        // a share within this of 1 or 0 leans to one donor (default: the library's, 0.1)
     // extension: how -a / -r (and --mix_alt / --mix_ref) belong together: 0 = zipped line by line (the reference's reading),
     // CELLECTOR_JOIN_REF = joined by (locus, cell), CELLECTOR_JOIN_DEPTH = likewise, -r holding alt + ref (cellector_ingest_mtx_joined)
     int matrix_pair = 0;
@@ -325,6 +328,23 @@ inline const std::vector<Opt> &options()
         Opt("donor_fit_iqr", 0, Kind::F64, &P::donor_fit_iqr).as("--donor_fit_iqr <k>").within({0.0, INFINITY, false, false}, "expected a number >= 0")
             .requires_option("donor_fit").paragraph(
             "        --donor_fit_iqr <k>                                                with --donor_fit: the multiple k (default 3)\n"),
+        Opt("doublet_fraction", 0, Kind::WORD, &P::doublet_fraction).as("--doublet_fraction true").one_of("false|true", "expected true or false")
+            .requires_option("donors").paragraph(
+            "        --doublet_fraction <true>                                          with --donors: the share of every called doublet's reads that\n"
+            "                                                                       come from its first donor, a profile likelihood over the grid\n"
+            "                                                                       0, 1/16 ... 1 under (the donor pass' anchor, its best pair),\n"
+            "                                                                       after the second donor pass of --estimate_ambient apply.\n"
+            "                                                                       Writes cellector_doublet_fractions.tsv (barcode, donor_a,\n"
+            "                                                                       donor_b, n_loci, fraction, se, ll_half, ll_max, kind: balanced,\n"
+            "                                                                       toward_a, toward_b or flat; NA for a cell that is no doublet)\n"
+            "                                                                       and prints one line; no other output changes.  A contaminated\n"
+            "                                                                       singlet leans to one donor, a doublet of two like cells is\n"
+            "                                                                       balanced.  Under --donor_field GP|GL|PL it scores every row's\n"
+            "                                                                       most probable genotype (not in the reference)\n"),
+        Opt("doublet_min_fraction", 0, Kind::F64, &P::doublet_min_fraction).as("--doublet_min_fraction <m>")
+            .within({0.0, 0.5, false, false}, "expected a number in [0, 0.5]").requires_option("doublet_fraction").paragraph(
+            "        --doublet_min_fraction <m>                                         with --doublet_fraction: a share above 1 - m leans toward_a, one\n"
+            "                                                                       below m toward_b (default 0.1)\n"),
         Opt("matrix_pair", 0, Kind::WORD_USAGE, &P::matrix_pair).as("--matrix_pair <aligned|join|depth>")
             .one_of("aligned|join|depth", "expected aligned, join or depth").on_one_gpu("--matrix_pair %s").paragraph(
             "        --matrix_pair <aligned|join|depth>                                 how the lines of -a and -r belong together.  aligned (default):\n"

@@ -1177,6 +1177,71 @@ cellector_status cellector_estimate_ambient(cellector_ctx *ctx, const uint8_t *g
                                             double *cell_rho /*[cells]*/, double *cell_se /*[cells]*/,
                                             uint32_t *n_entries /*[cells]*/); /* any output may be NULL */
 
+/* ---- donor pair fractions: a doublet's mixing share, profiled over a grid of f -----------------------------------------------
+ * Every doublet hypothesis of the donor calls mixes its two genotypes at equal weight (step 3 there: theta = 0.5 (theta_{g_a} +
+ * theta_{g_b})).  A droplet rarely obeys that: a large cell caught with a small one gives 80 / 20, a singlet carrying a clump of
+ * another donor's RNA 95 / 5, and the 0.5 hypothesis is the best the softmax has for both.  These calls measure the share: a cell is
+ * scored under a PAIR of donors (a, b) at G values of f, the share of its reads that come from donor a, at once; the maximum of that
+ * profile is the estimate.  The log-likelihood is a sum of logs of functions affine in f: it is concave, and the vertex rule of the
+ * ambient model (step 4 there) carries over unchanged.  Everything not stated here is the donor model above, step for step; all
+ * arithmetic is f64 without contraction: every product, quotient and sum below rounds once.  cellector_amd/pair_fraction.py is the
+ * twin; no parity with any other demultiplexer is claimed.
+ *   gt [D][total_loci] u8 is coded and packed exactly as for cellector_donor_posteriors (step 1 there), 1 <= D <= 64.  pair_a, pair_b
+ *   [cells] u8: the pair a cell is scored under; pair_a == 255 = the cell takes no part and its pair_b is ignored; otherwise both are
+ *   below D and differ.  frac [G], 4 <= G <= 32, every value finite and in [0, 1], strictly ascending; NULL = the default grid
+ *   j / 16.0, j = 0 ... 16 (n_grid is then ignored: G = 17), which holds 0, 0.5 and 1 exactly.  mask [L] or NULL = all loci.  The
+ *   cellector_donor_params are the donor call's; err and ambient are used.
+ *   1 tables: theta_g is step 2 of the donor model, ambient mix included.  theta_{g_a,g_b,j} = (f_j theta_{g_a}) + ((1.0 - f_j)
+ *     theta_{g_b}); tab [L][16][G][2] = (log theta, log(1.0 - theta)) at index 4 g_a + g_b with the device's log.  A masked locus'
+ *     rows are (0, 0) and no sum visits it.  256 G bytes per used locus; an entry reads one row of 16 G bytes.  Scaling by a power of
+ *     two is exact, so where f_j == 0.5 the column carries the bits of cellector_donor_tables' tab2[l][4 g_a + g_b] ((0.5 x) + (0.5 y)
+ *     is 0.5 (x + y)), where f_j == 1.0 it carries tab1[l][g_a] ((1.0 x) + (0.0 y) is x) and where f_j == 0.0 tab1[l][g_b].
+ *   2 cell sums: ll[c][j] = the sum over the cell's entries in row order of ((alt la) + (ref lb)), (la, lb) =
+ *     tab[l][4 g_{a_c}(l) + g_{b_c}(l)][j]: both products rounded, then their sum, then that added to the accumulator, strictly
+ *     sequential per (cell, j) from 0.0 (step 4 of the donor model).  n_entries[c] = the number of those entries.  A cell that takes
+ *     no part has a row of 0.0 and n_entries 0.  By step 1, ll[c][j] at f_j == 0.5, 1.0 and 0.0 is, bit for bit, pair_ll[c][b],
+ *     ll[c][a] and ll[c][b] of cellector_donor_posteriors run with anchor[c] = a.
+ *   3 the vertex rule: step 4 of the ambient model verbatim (the same function on the device), its "unresolved" rule included, on
+ *     (frac, ll[c]): j_star [cells] u8 = the smallest j that maximises ll[c][j] (0 for a cell that takes no part), cell_frac = the
+ *     vertex clamped into the three points' span, cell_se = 1 / sqrt(-curvature); a flat or convex profile gives frac[j_star] and
+ *     +inf.
+ *   4 kind [cells] u8: 255 = no part, or n_entries < min_loci: cell_frac and cell_se are NaN; else 3 = flat (cell_se == +inf, e.g. no
+ *     entry at a locus where the two genotypes differ); else 1 = toward a (cell_frac > 1.0 - min_fraction); else 2 = toward b
+ *     (cell_frac < min_fraction); else 0 = balanced.  The summary counts the five kinds, and per donor the kind-1 cells under their a
+ *     and the kind-2 cells under their b: the donor they lean to.
+ *   One grid per call and no zoom: each cell's maximum lies somewhere else, so a zoomed grid could not be shared across cells, and
+ *   one wide grid with one parabola is within the cell's own standard error at droplet depth.
+ * Defaults (cellector_pair_fraction_default_params): min_fraction 0.1, min_loci 1.
+ * Scope and errors as cellector_donor_posteriors: a single-device ctx that holds all cells, a loaded matrix, no iteration in flight,
+ * engines 1 and 2.  CELLECTOR_EINVAL with a message, nothing written or launched, for the donor call's own errors, NULL pair_a /
+ * pair_b, a pair_a that is neither 255 nor below D, a pair_b >= D or equal to pair_a where pair_a != 255 (the message names the first
+ * offending cell), G outside 4..32, a frac value that is NaN, outside [0, 1] or not above the one before it, min_fraction outside
+ * [0, 0.5], min_loci == 0.  All device scratch is allocated before anything is launched: D bytes per locus of the matrix, 256 G + 8 W
+ * + 1 B per used locus (W = ceil(D / 32)), 8 G + 24 B per cell and 8 G B beside them (cellector_pair_fraction_tables: 256 G + 1 B per
+ * used locus and 8 G B): on CELLECTOR_ENOMEM the ctx is as it was.  The EM state is never touched (an interrupted EM loop continues
+ * with the same bits) and nothing of the ctx is overwritten; the caches cellector_cell_log_likelihoods invalidates are invalidated. */
+typedef struct {
+    double min_fraction;  /* 0.1: a cell whose share lies within this of 1 or 0 leans to a or to b ([0, 0.5]) */
+    uint64_t min_loci;    /* 1:   a cell with fewer entries at used, unmasked loci gets kind 255              */
+} cellector_pair_fraction_params;
+typedef struct {
+    uint64_t n_balanced, n_toward_a, n_toward_b, n_flat, n_none;  /* kind 0, 1, 2, 3, 255                      */
+    uint64_t donor_cells[64];  /* the kind-1 cells per pair_a and the kind-2 cells per pair_b                   */
+} cellector_pair_fraction_summary;
+cellector_status cellector_pair_fraction_default_params(cellector_pair_fraction_params *out);
+cellector_status cellector_pair_fraction_tables(cellector_ctx *ctx, const cellector_donor_params *donor_params /*NULL = defaults*/,
+                                                const double *frac /*[G] or NULL*/, uint32_t n_grid, const uint8_t *mask /*[L] or NULL*/,
+                                                double *tab /*[L][16][G][2]*/);
+cellector_status cellector_donor_pair_fractions(cellector_ctx *ctx, const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                                const cellector_donor_params *donor_params /*NULL = defaults*/,
+                                                const cellector_pair_fraction_params *params /*NULL = defaults*/,
+                                                const uint8_t *pair_a /*[cells]*/, const uint8_t *pair_b /*[cells]*/,
+                                                const double *frac /*[G] or NULL*/, uint32_t n_grid, const uint8_t *mask /*[L] or NULL*/,
+                                                double *ll /*[cells][G]*/, uint32_t *n_entries /*[cells]*/, double *cell_frac /*[cells]*/,
+                                                double *cell_se /*[cells]*/, uint8_t *j_star /*[cells]*/, uint8_t *kind /*[cells]*/,
+                                                cellector_pair_fraction_summary *summary,
+                                                double *tab /*[L][16][G][2]*/); /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
