@@ -2184,6 +2184,51 @@ cellector_status cellector_class_genotypes(cellector_ctx *c, const uint8_t *labe
     return CELLECTOR_OK;
 }
 
+// ---- donor genotype refinement: kernels_donor_genotypes.hip ------------------------------------------------
+cellector_status cellector_donor_genotypes_default_params(cellector_donor_genotypes_params *out)
+{
+    if (!out) return CELLECTOR_EINVAL;
+    out->err = 0.01;
+    out->ambient = 0.03;
+    out->gt_threshold = 0.99;
+    out->prior_floor = 0.01;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_donor_genotypes(cellector_ctx *c, const uint8_t *assign, const float *prior, uint32_t n_donors,
+                                           const cellector_donor_genotypes_params *params, uint64_t *cells, uint64_t *alt, uint64_t *ref,
+                                           double *q, uint8_t *gt_out, uint8_t *kind, cellector_donor_genotypes_summary *summary, double *tab,
+                                           double *pass_ms)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    const char *what = "donor_genotypes";
+    cellector_donor_genotypes_params prm;
+    cellector_donor_genotypes_default_params(&prm);
+    if (params) prm = *params;
+    CHK(locus_moments_scope(c, what));
+    READY(c);
+    if (c->em_phase != 0) return ctx_fail(c, CELLECTOR_EINVAL, "%s: iteration in flight (finish it with cellector_em_finish)", what);
+    cellector_donor_params dp;  // (err and ambient are the donor call's, and so are their checks)
+    cellector_donor_default_params(&dp);
+    dp.err = prm.err;
+    dp.ambient = prm.ambient;
+    const uint32_t D = n_donors;
+    CHK(donor_params_check(c, what, &dp /*(a NULL prior is no error)*/, "prior", D, &dp));
+    if (!(prm.gt_threshold >= 0.0 && prm.gt_threshold <= 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: gt_threshold = %g is not within [0, 1]", what, prm.gt_threshold);
+    if (!(prm.prior_floor >= 0.0 && prm.prior_floor <= 1.0))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: prior_floor = %g is not within [0, 1]", what, prm.prior_floor);
+    if (!assign) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null assign", what);
+    for (uint64_t i = 0; i < c->nloc; i++)
+        if (assign[i] >= D && assign[i] != 255)
+            return ctx_fail(c, CELLECTOR_EINVAL, "%s: assign of cell %llu is %u, neither below the %u donors nor 255 (no part)", what,
+                            (unsigned long long)i, (unsigned)assign[i], D);
+    if (prior) CHK(donor_gp_check(c, what, prior, D, &dp));
+    REQUIRE(c, c->keep_coo && (c->coo.locus || !c->nnz), "donor_genotypes needs the staged COO (option keep_coo=1)");
+    SETDEV(c);
+    return donor_genotypes_run(c, assign, prior, D, &prm, cells, alt, ref, q, gt_out, kind, summary, tab, pass_ms);
+}
+
 // ---- posteriors ---------------------------------------------------------------------------------------
 // the minority fraction and the three log priors of calculate_posteriors, from the current exclusion set
 struct PosteriorPriors { double mf0, lp_min, lp_maj, lp_dbl; };

@@ -616,6 +616,10 @@ cellector_status pair_fractions_run(cellector_ctx *c, const uint8_t *gt, uint32_
 cellector_status launch_final_tallies(cellector_ctx *c, uint64_t *d_out /*[4*total_loci]*/);
 // the same over the K classes of a labelling (kernels_genotypes.hip): d_lab [nloc] on the device, slot K = the cells labelled 255
 cellector_status launch_genotype_tallies(cellector_ctx *c, const uint8_t *d_lab, uint32_t K, uint64_t *d_acc /*[K+1][2][total_loci]*/);
+// donor genotype refinement (kernels_donor_genotypes.hip): validated arguments, host arrays, scratch of its own
+cellector_status donor_genotypes_run(cellector_ctx *c, const uint8_t *assign, const float *prior, uint32_t D,
+                                     const cellector_donor_genotypes_params *p, uint64_t *cells, uint64_t *alt, uint64_t *ref, double *q,
+                                     uint8_t *gt_out, uint8_t *kind, cellector_donor_genotypes_summary *summary, double *tab, double *pass_ms);
 // placed state (kernels_state.hip): host_flags into c->flags, the set's minority tallies and member count into c->x_locus
 cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flags /*[nloc], 0 / 1*/);
 // order statistics: exact values at SEL_T 0-based ranks of n keys

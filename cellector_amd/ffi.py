@@ -108,6 +108,8 @@ SIGNATURES = {
     "cellector_pair_fraction_default_params": (_i, [_vp]),
     "cellector_pair_fraction_tables": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "cellector_donor_pair_fractions": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp] + [_vp] * 8),
+    "cellector_donor_genotypes_default_params": (_i, [_vp]),
+    "cellector_donor_genotypes": (_i, [_vp, _vp, _vp, C.c_uint32, _vp] + [_vp] * 9),
     "cellector_assign": (_i, [_vp, _d, _u64] + [_vp] * 7),
     "cellector_assign_resolution": (_i, [_vp, _vp]),
     "cellector_assign_resolved_cells": (_i, [_vp, _vp]),
@@ -197,6 +199,19 @@ class PairFractionParams(C.Structure):
 class PairFractionSummary(C.Structure):
     _fields_ = [("n_balanced", _u64), ("n_toward_a", _u64), ("n_toward_b", _u64), ("n_flat", _u64), ("n_none", _u64),
                 ("donor_cells", _u64 * 64)]
+
+
+class DonorGenotypesParams(C.Structure):
+    _fields_ = [("err", _d), ("ambient", _d), ("gt_threshold", _d), ("prior_floor", _d)]
+
+
+class DonorGenotypesSummary(C.Structure):
+    _fields_ = [("cells", _u64 * 64), ("loci_with_reads", _u64 * 64), ("confirmed", _u64 * 64), ("filled", _u64 * 64),
+                ("changed", _u64 * 64), ("withdrawn", _u64 * 64)]
+
+    def as_dict(self, n_donors):
+        """the fields donor_genotypes.summary returns, cut to the D donors"""
+        return {k: np.array(getattr(self, k)[:n_donors], np.uint64) for k, _ in self._fields_}
 
 
 class JoinSummary(C.Structure):
@@ -1192,6 +1207,78 @@ class Cellector:
         out["frac"] = np.arange(17) / 16.0 if frac is None else frac
         out["summary"] = s
         return out
+
+    # ---- donor genotype refinement: the donors' genotypes from the reads of the cells called for them; donor_genotypes.py is the
+    # numpy twin
+    def donor_genotypes_default_params(self):
+        p = DonorGenotypesParams()
+        self._ck(self._lib.cellector_donor_genotypes_default_params(C.byref(p)))
+        return p
+
+    def donor_genotypes(self, assign, prior=None, n_donors=None, posterior=True, timing=False, **params):
+        """The D donors' genotypes over all loci of the matrix from the reads of the cells assigned to them
+        (cellector_donor_genotypes).  assign [cells] uint8: a donor, or 255 = no part; prior [D, total_loci, 3] float32 (three NaN: a
+        no-call) or None = no calls at all, then n_donors names D.  params: err, ambient, gt_threshold, prior_floor
+        (DonorGenotypesParams).  Returns a dict: cells [D + 1], alt / ref [D + 1, total_loci] uint64 (slot D: the cells assigned 255)
+        and, with posterior, q [D, total_loci, 3], gt_out, kind [D, total_loci] uint8 (0 no reads, 1 confirmed, 2 filled, 3 changed,
+        4 withdrawn), tab [total_loci, 3, 2] and summary (a dict of [D] arrays); with timing, pass_ms [2]."""
+        TL = self.dims().total_loci
+        n = self.n_local if self.dims().total_cells else 0  # (before a load the library refuses the call)
+        assign = np.ascontiguousarray(assign, np.uint8)
+        if self.dims().total_cells and assign.shape != (n,):
+            raise ValueError(f"assign: {n} values expected, got shape {assign.shape}")
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, np.float32)
+            if prior.ndim != 3 or prior.shape[2] != 3 or (self.dims().total_cells and prior.shape[1] != TL):
+                raise ValueError(f"prior: shape (D, {TL}, 3) expected, got {prior.shape}")
+            if n_donors is not None and int(n_donors) != prior.shape[0]:
+                raise ValueError(f"n_donors = {n_donors}, but prior holds {prior.shape[0]} donors")
+            D = prior.shape[0]
+        elif n_donors is None:
+            raise ValueError("n_donors: needed when prior is None")
+        else:
+            D = int(n_donors)
+        p = self.donor_genotypes_default_params()
+        for k, v in params.items():
+            if k not in dict(DonorGenotypesParams._fields_):
+                raise TypeError(f"donor genotypes: unknown parameter {k!r}")
+            setattr(p, k, v)
+        Da = min(max(D, 1), 64)
+        out = dict(cells=np.zeros(Da + 1, np.uint64), alt=np.zeros((Da + 1, TL), np.uint64), ref=np.zeros((Da + 1, TL), np.uint64))
+        s = DonorGenotypesSummary()
+        if posterior:
+            out.update(q=np.zeros((Da, TL, 3), np.float64), gt_out=np.zeros((Da, TL), np.uint8), kind=np.zeros((Da, TL), np.uint8),
+                       tab=np.zeros((TL, 3, 2), np.float64))
+        if timing:
+            out["pass_ms"] = np.zeros(2, np.float64)
+        self._ck(self._lib.cellector_donor_genotypes(
+            self.h, _p(assign), _p(prior), max(D, 0), C.byref(p), _p(out["cells"]), _p(out["alt"]), _p(out["ref"]), _p(out.get("q")),
+            _p(out.get("gt_out")), _p(out.get("kind")), C.byref(s) if posterior else None, _p(out.get("tab")), _p(out.get("pass_ms"))))
+        if posterior:
+            out["summary"] = s.as_dict(Da)
+        return out
+
+    def refine_donors(self, prior, max_iter=10, log_prior=None, mask=None, donor_params=None, **params):
+        """Calls and genotypes in turn, a plain loop: donor_posteriors_gp under the current rows, donor_genotypes on the status-0 cells
+        under their best donor with the CALLER's prior, to_gp(q) as the next round's rows; it stops when no cell's (status, best)
+        changes, or after max_iter rounds.  donor_params: a dict for the donor call (DonorParams; err and ambient go to both calls
+        unless params names its own).  Returns (the last donor result, the last genotype result, the rounds run)."""
+        from . import donor_genotypes as dg
+        prior = np.ascontiguousarray(prior, np.float32)
+        dp = dict(donor_params or {})
+        gparams = {k: dp[k] for k in ("err", "ambient") if k in dp}
+        gparams.update(params)
+        gp, last, don, gen, rounds = prior, None, None, None, 0
+        for rounds in range(1, int(max_iter) + 1):
+            don = self.donor_posteriors_gp(gp, log_prior=log_prior, mask=mask, **dp)
+            key = (don["status"], don["best"])
+            if last is not None and np.array_equal(key[0], last[0]) and np.array_equal(key[1], last[1]):
+                break
+            last = key
+            assign = np.where(don["status"] == 0, don["best"], 255).astype(np.uint8)
+            gen = self.donor_genotypes(assign, prior, **gparams)
+            gp = dg.to_gp(gen["q"])
+        return don, gen, rounds
 
     def assign(self, posterior_threshold=0.999, min_loci_used=30):
         """calculate_posteriors + the labelling rule of output_final_assignments in one call (cellector_assign).  With option

@@ -1312,6 +1312,73 @@ void write_doublet_fractions(const Run &run, const Donors &d, const DonorCalls &
     run.lap("cellector_doublet_fractions.tsv");
 }
 
+// --donor_genotypes: the donors' genotypes from the reads of the status-0 cells, each under its best donor, with the donors' own
+// rows as the prior (--donor_field GT: the one-hot of the hard calls) and the parameters the donor pass ended with.  Returns q as
+// the float rows cellector_donor_posteriors_gp takes (apply scores the donors again with them).
+std::vector<float> write_donor_genotypes(const Run &run, const Donors &d, const DonorCalls &calls)
+{
+    const uint64_t N = run.N, TL = run.dims.total_loci;
+    const uint32_t D = d.D;
+    std::vector<uint8_t> assign(N);
+    for (uint64_t c = 0; c < N; c++) assign[c] = calls.status[c] == 0 ? calls.best[c] : (uint8_t)255;
+    std::vector<float> prior;
+    if (d.soft) {
+        prior = d.dg.gp;
+    } else {
+        prior.assign((uint64_t)D * TL * 3, 0.f);
+        for (uint64_t i = 0; i < (uint64_t)D * TL; i++) {
+            const uint8_t g = d.dg.gt[i];
+            if (g < 3) prior[3 * i + g] = 1.f;
+            else prior[3 * i] = prior[3 * i + 1] = prior[3 * i + 2] = std::numeric_limits<float>::quiet_NaN();
+        }
+    }
+    cellector_donor_genotypes_params gp;
+    cellector_donor_genotypes_default_params(&gp);
+    gp.err = d.dp.err; gp.ambient = d.dp.ambient;
+    std::vector<uint64_t> galt((uint64_t)(D + 1) * TL), gref((uint64_t)(D + 1) * TL);
+    std::vector<double> q((uint64_t)D * TL * 3);
+    std::vector<uint8_t> gt((uint64_t)D * TL);
+    cellector_donor_genotypes_summary gs;
+    run.g.ck(cellector_donor_genotypes(run.g.c, assign.data(), prior.data(), D, &gp, nullptr, galt.data(), gref.data(), q.data(), gt.data(), nullptr,
+                                       &gs, nullptr, nullptr), "donor_genotypes");
+    {
+        uint64_t tot[5] = {};
+        for (uint32_t k = 0; k < D; k++) {
+            tot[0] += gs.cells[k]; tot[1] += gs.confirmed[k]; tot[2] += gs.filled[k]; tot[3] += gs.changed[k]; tot[4] += gs.withdrawn[k];
+        }
+        std::string o = "donor_genotypes: donors=";
+        put(o, (uint64_t)D); o += " cells="; put(o, tot[0]); o += " confirmed="; put(o, tot[1]); o += " filled="; put(o, tot[2]);
+        o += " changed="; put(o, tot[3]); o += " withdrawn="; put(o, tot[4]); o += '\n';
+        fputs(o.c_str(), stdout);
+    }
+    static const char *const GT[4] = {"0/0", "0/1", "1/1", "./."};
+    write_sample_vcf(run, "cellector_donor_genotypes.vcf",
+                     [&](std::string &o) { for (uint32_t k = 0; k < D; k++) { o += '\t'; o += d.name((uint8_t)k); } },
+                     [&](uint64_t t, std::string &o) {
+                         for (uint32_t k = 0; k < D; k++) {
+                             const uint64_t i = (uint64_t)k * TL + t;
+                             o += '\t'; o += GT[gt[i] & 3]; o += ':';
+                             put(o, q[3 * i]); o += ','; put(o, q[3 * i + 1]); o += ','; put(o, q[3 * i + 2]); o += ':';
+                             put(o, galt[i]); o += ':'; put(o, gref[i]);
+                         }
+                     });
+    FILE *f = create(run.out("cellector_donor_genotypes.tsv"));
+    {
+        std::string o = "donor\tcells\tloci_with_reads\tconfirmed\tfilled\tchanged\twithdrawn\n";
+        for (uint32_t k = 0; k < D; k++) {
+            o += d.name((uint8_t)k);
+            for (const uint64_t v : {gs.cells[k], gs.loci_with_reads[k], gs.confirmed[k], gs.filled[k], gs.changed[k], gs.withdrawn[k]}) {
+                o += '\t'; put(o, v);
+            }
+            o += '\n';
+        }
+        fputs(o.c_str(), f);
+    }
+    fclose(f);
+    run.lap("cellector_donor_genotypes.vcf");
+    return std::vector<float>(q.begin(), q.end());
+}
+
 // the classes in force named by donor
 void write_cluster_donors(const Run &run, const Donors &d, const ClassLabels &classes)
 {
@@ -1350,6 +1417,15 @@ void run_donors(const Run &run, const ClassLabels &classes)
         const double rho = write_ambient(run, d, calls);
         if (params.estimate_ambient == 2) {  // apply: the donors again with it
             d.dp.ambient = rho;
+            calls = donor_pass(run, d);
+        }
+    }
+    if (params.donor_genotypes) {
+        std::vector<float> refined = write_donor_genotypes(run, d, calls);
+        if (params.donor_genotypes == 2) {  // apply: the donors again, under the refined rows as genotype weights
+            d.soft = true;
+            d.dg.gp = std::move(refined);
+            d.hard_gt = donor_hard_codes(d.dg.gp);
             calls = donor_pass(run, d);
         }
     }

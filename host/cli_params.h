@@ -61,6 +61,8 @@ struct Params {
     // extension: the mixing share of every called doublet's two donors (cellector_donor_pair_fractions)
     bool doublet_fraction = false;
     std::optional<double> doublet_min_fraction;        // a share within this of 1 or 0 leans to one donor (default: the library's, 0.1)
+    // extension: the donors' genotypes from the reads of the cells called for them (cellector_donor_genotypes)
+    int donor_genotypes = 0;                           // 0 = off, 1 = true: write them, 2 = apply: and score the donors again with them
     // extension: how -a / -r (and --mix_alt / --mix_ref) belong together: 0 = zipped line by line (the reference's reading),
     // CELLECTOR_JOIN_REF = joined by (locus, cell), CELLECTOR_JOIN_DEPTH = likewise, -r holding alt + ref (cellector_ingest_mtx_joined)
     int matrix_pair = 0;
@@ -345,6 +347,22 @@ inline const std::vector<Opt> &options()
             .within({0.0, 0.5, false, false}, "expected a number in [0, 0.5]").requires_option("doublet_fraction").paragraph(
             "        --doublet_min_fraction <m>                                         with --doublet_fraction: a share above 1 - m leans toward_a, one\n"
             "                                                                       below m toward_b (default 0.1)\n"),
+        Opt("donor_genotypes", 0, Kind::WORD, &P::donor_genotypes).as("--donor_genotypes <true|apply>")
+            .one_of("false|true|apply", "expected true, apply or false").requires_option("donors").paragraph(
+            "        --donor_genotypes <true|apply>                                     with --donors: the donors' genotypes from the reads of the cells\n"
+            "                                                                       the donor pass calls singlets, each under its best donor, after\n"
+            "                                                                       the second donor pass of --estimate_ambient apply and with the\n"
+            "                                                                       ambient share in force.  The donors' own rows are the prior (GP,\n"
+            "                                                                       GL, PL as read; GT as one-hot rows), floored at 0.01.  Writes\n"
+            "                                                                       cellector_donor_genotypes.vcf (the records of --vcf, one\n"
+            "                                                                       GT:GP:AO:RO column per donor, ./. below a posterior of 0.99)\n"
+            "                                                                       and cellector_donor_genotypes.tsv (donor, cells,\n"
+            "                                                                       loci_with_reads, confirmed, filled, changed, withdrawn) and\n"
+            "                                                                       prints one line.  true: no other output changes.  apply: the\n"
+            "                                                                       donor pass runs once more with the refined genotypes as\n"
+            "                                                                       weights, and cellector_donors.tsv, --donor_fit,\n"
+            "                                                                       --doublet_fraction and the class match are written from that\n"
+            "                                                                       pass (not in the reference)\n"),
         Opt("matrix_pair", 0, Kind::WORD_USAGE, &P::matrix_pair).as("--matrix_pair <aligned|join|depth>")
             .one_of("aligned|join|depth", "expected aligned, join or depth").on_one_gpu("--matrix_pair %s").paragraph(
             "        --matrix_pair <aligned|join|depth>                                 how the lines of -a and -r belong together.  aligned (default):\n"

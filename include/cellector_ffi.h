@@ -1242,6 +1242,68 @@ cellector_status cellector_donor_pair_fractions(cellector_ctx *ctx, const uint8_
                                                 cellector_pair_fraction_summary *summary,
                                                 double *tab /*[L][16][G][2]*/); /* any output may be NULL */
 
+/* ---- donor genotype refinement: fill and correct the donors' calls from the pool ----------------------------------------------
+ * The donor calls above carry genotypes to the cells; this call carries the cells' reads back to the genotypes.  A donor VCF from an
+ * array or a low-coverage genome has no call at many loci of the matrix, some wrong calls, and soft rows; the reads of the cells
+ * called for a donor say what that donor is at every covered locus, with far more depth than any single cell.  The model below is the
+ * specification (cellector_amd/donor_genotypes.py repeats it in numpy); it is the library's own, no parity with any other program is
+ * claimed.  All arithmetic is f64 without contraction: every product, quotient and sum below rounds once.
+ *   assign [cells] u8: the donor (< D) a cell's reads are counted for, or 255 = the cell takes no part (a caller passes best where
+ *   status == 0).  prior [D][total_loci][3] f32 or NULL, indexed by the matrix' own locus index: validated and normalised exactly as
+ *   the gp of cellector_donor_posteriors_gp (a row of three NaN is a no-call; any other row finite, >= 0, not all zero; w_g =
+ *   (double)p_g / (((double)p_0 + (double)p_1) + (double)p_2)); NULL = every row is a no-call.  1 <= D <= 64.  params: err and ambient
+ *   as in cellector_donor_params; gt_threshold (0.99, the reference's, main.rs:93-124) within [0, 1]; prior_floor (0.01) within
+ *   [0, 1]: the chance that a stated call is wrong, the meaning and the default of err.  At prior_floor 0 a one-hot row can never be
+ *   overturned.
+ *   1 tallies over ALL total_loci loci of the matrix, not only the used ones: alt[s][t], ref[s][t] u64 for s = 0 ... D = the sums of
+ *     the staged entries' counts at locus t over the cells of slot s; slot D holds the cells assigned 255.  Exact in any entry order;
+ *     a repeated (locus, cell) pair counts each time.  cells[s] = the number of cells in slot s.
+ *   2 per locus t: A, R = the sums over all D + 1 slots; soup = ((double)A + 1.0) / ((double)(A + R) + 2.0); e = {err, 0.5,
+ *     1.0 - err}; theta_g = ((1.0 - ambient) e_g) + (ambient soup); la_g = log(theta_g), lb_g = log(1.0 - theta_g) with the device's
+ *     log: tab [total_loci][3][2].  These are steps 2 and 3 of the donor model: at a used locus (la_g, lb_g) carries the bits of
+ *     cellector_donor_tables' tab1[l][g].
+ *   3 per (donor d, locus t) with tallies (a, r): lam_g = ((double)a la_g) + ((double)r lb_g); w_g = the normalised prior weight,
+ *     1.0 / 3.0 each in a no-call row; v_g = ((1.0 - prior_floor) w_g) + (prior_floor / 3.0); a g with v_g == 0 takes no part (its
+ *     q_g is 0); x_g = lam_g + log(v_g); m = the maximum of the x_g; den = the sum of exp(x_g - m) in ascending g from 0.0; q_g =
+ *     exp(x_g - m) / den, exp and log the device's.  Everything stays in log space: no depth underflows to NaN.  call = the argmax
+ *     of q, the smallest g on ties; gt_out = call if q_call > gt_threshold (strict), else 3.
+ *   4 kind [D][total_loci] u8, with prior_call = the argmax of w (the smallest g on ties), 3 for a no-call row: 0 = a + r == 0, so q
+ *     is the floored prior; else 4 = withdrawn: gt_out == 3 although there are reads; else 2 = filled: the prior is a no-call and
+ *     gt_out is a call; else 1 = confirmed: gt_out == prior_call; else 3 = changed: both are calls and they differ.
+ *   5 the summary: per donor its cells, the loci with reads (kind != 0) and the number of loci of each kind 1 ... 4.
+ * Limits.  The cells were called WITH the prior, so the tallies lean toward it: a wrong call that drew the wrong cells is confirmed
+ * by them.  A donor with few cells gets withdrawn, not a call.  Doublets must stay out of assign: their reads are another donor's.
+ * Defaults (cellector_donor_genotypes_default_params): err 0.01, ambient 0.03, gt_threshold 0.99, prior_floor 0.01.
+ * Scope as cellector_class_genotypes: the staged COO (option keep_coo), a loaded matrix, no iteration in flight, a single-device ctx
+ * that holds all cells and fewer than 2^32 used entries (the scope check all donor calls share; the planes themselves are u64).  The
+ * staged COO of a loaded matrix is locus-major whatever order it was ingested in, which is what the tally pass is fast on.  CELLECTOR_EINVAL with a message, nothing written or launched, for these and for D outside 1..64, NULL
+ * assign, an assign value that is neither below D nor 255 (the message names the cell), a refused row of prior (the message names
+ * the donor and the locus), err outside (0, 0.5), ambient outside [0, 1), gt_threshold or prior_floor outside [0, 1].  All device
+ * scratch is allocated before the first launch: 16 (D + 1) + 48 B per locus of the matrix, 2 D B more, 24 D B with q, 12 D B with a
+ * prior, and 1 B per cell; on CELLECTOR_ENOMEM the ctx is as it was.  With no output past ref asked for only the tallies run.  The EM
+ * state is never touched (an interrupted EM loop continues with the same bits) and nothing of the ctx is overwritten.  pass_ms [2],
+ * if given, receives the device time of the tally pass and of the table and posterior pass in milliseconds. */
+typedef struct {
+    double err;           /* 0.01: the allele fraction of a homozygous-reference donor                    */
+    double ambient;       /* 0.03: the share of a cell's reads that come from the pool                    */
+    double gt_threshold;  /* 0.99: a genotype is called when its posterior exceeds this                   */
+    double prior_floor;   /* 0.01: the chance that a stated call is wrong, spread over the three genotypes */
+} cellector_donor_genotypes_params;
+typedef struct {
+    uint64_t cells[64];            /* cells assigned to the donor                         */
+    uint64_t loci_with_reads[64];  /* kind != 0                                           */
+    uint64_t confirmed[64], filled[64], changed[64], withdrawn[64];  /* kind 1, 2, 3, 4 */
+} cellector_donor_genotypes_summary;
+cellector_status cellector_donor_genotypes_default_params(cellector_donor_genotypes_params *out);
+cellector_status cellector_donor_genotypes(cellector_ctx *ctx, const uint8_t *assign /*[cells]*/,
+                                           const float *prior /*[D][total_loci][3] or NULL*/, uint32_t n_donors,
+                                           const cellector_donor_genotypes_params *params /*NULL = defaults*/,
+                                           uint64_t *cells /*[D + 1]*/, uint64_t *alt /*[D + 1][total_loci]*/,
+                                           uint64_t *ref /*[D + 1][total_loci]*/, double *q /*[D][total_loci][3]*/,
+                                           uint8_t *gt_out /*[D][total_loci]*/, uint8_t *kind /*[D][total_loci]*/,
+                                           cellector_donor_genotypes_summary *summary, double *tab /*[total_loci][3][2]*/,
+                                           double *pass_ms /*[2]*/); /* any output may be NULL */
+
 /* ---- load_mtx_final (load_data.rs:109-132): per-locus allele tallies over ALL loci split by the
  * current exclusion set, for output_final_vcf (main.rs:52-131).  This shard's cells only; sum
  * across shards on the host. */
