@@ -265,7 +265,7 @@ struct CtxTiled {
     uint32_t t_nb = 0, t_nj = 0, t_groups = 0, t_cpg = 0;  // cell blocks, locus chunks, chunk groups, chunks/group
     uint64_t t_npad = 0;             // nb * T_BC
     DevBuf<uint64_t> tile_ptr;       // [nb*nj+1] offsets into tiles, in u16 elements (multiples of 128)
-    DevBuf<uint16_t> tiles;          // SELL-64-1024 slices: per tile 16 slices of 64 rows [cell, K entries code*384 + locus_in_chunk]
+    DevBuf<uint16_t> tiles;          // SELL-64-1024 slices: per tile 16 slices of 64 rows of K u16 entries and their cell ids (tiled.h: tile_entry)
     DevBuf<uint16_t> thdr;           // [nb*nj][T_HDR] tile headers: 16 x {first u16 of the slice, K}
     uint64_t t_elems = 0;            // entries (u16) in the stream, padding included
     double *tab_em = nullptr;        // table the last EM cell pass built, inside tab (the locus pass reads its log-pmfs)

@@ -12,7 +12,8 @@
 //               is odd and in a block of their own when K is even: tiled.h), so that all lanes of a wave run the
 //               SAME number of lookups — no divergence and ~9 % padding instead of the ~55 % idle lanes of a
 //               cell-per-lane walk in file order — and a lane fetches its row with one or two 16-byte loads.
-//               A u16 entry is n-1 << 14 | locus slot << 4 | code; padding points at an all-zero slot.
+//               A u16 entry carries where its two table values sit: the expected term's element << 4 | how many planes behind it
+//               the log-pmf lies (tiled.h, offset entries); padding points at an all-zero slot.
 //               A persistent 1024-thread workgroup takes columns of four cell blocks and a group of chunks: the chunk's
 //               table lives in LDS code-major (18 planes of 640 slots: the log-pmf and the expected term of an entry are two
 //               8-byte reads on the SAME bank pair, slot mod 32, whatever the code; tiled.h); a lane keeps its cell's entries of the tile in registers (prefetched two
@@ -289,16 +290,31 @@ __global__ __launch_bounds__(T_THREADS, 4) void k_tile_ll(uint32_t nb, uint32_t 
 #elif TILE_ABL == 4  /* ablation: lookups free of bank conflicts (a lane keeps to its own bank pair; wrong values) */
 #define TILE_LOOKUP(V, E16)                                                                                      \
     do {                                                                                                         \
+        if constexpr (G::OFFSET_ENTRIES) { /* the entry's own two elements, moved inside their planes onto the lane's bank pair */ \
+            static_assert(G::BL % 32u == 0, "a plane keeps the bank pair");                                      \
+            const uint32_t own__ = (tile_entry_exp<G>(E16) & ~31u) | (lane & 31u);                               \
+            if constexpr (EXPECTED) V = make_double2(s_tab[own__ + tile_entry_pmf<G>(E16) - tile_entry_exp<G>(E16)], s_tab[own__]); \
+            else V = s_tab[own__ + tile_entry_pmf<G>(E16) - tile_entry_exp<G>(E16)];                             \
+        } else {                                                                                                 \
         const uint32_t b__ = (((E16) >> 4) & 127u) * 32u + (lane & 31u), c__ = (((E16) >> 5) & 127u) * 32u + (lane & 31u); \
         if constexpr (EXPECTED) V = make_double2(s_tab[b__], s_tab[c__ + 4096u]);                                \
         else V = s_tab[b__];                                                                                     \
+        }                                                                                                        \
     } while (0)
 #else
+// the entry's log-pmf and, in the EM pass, its expected term: where they sit is the entry's business (tiled.h).  Offset entries:
+// the expected term's byte address is a shift and a mask of the row's dword, the log-pmf's one field extract and one multiply-add
+// on top of it (plane difference x plane bytes); slot << 4 | code: two instructions for slot x 8, then two for each value.
 #define TILE_LOOKUP(V, E16)                                                                                      \
     do {                                                                                                         \
-        const uint32_t s__ = ((E16) >> G::SHIFT) & G::SMASK;                                                     \
-        if constexpr (EXPECTED) V = make_double2(s_tab[tab_pmf<G>(s__, (E16) & G::CMASK)], s_tab[tab_exp<G>(s__, (E16) >> 14)]); \
-        else V = s_tab[tab_pmf<G>(s__, (E16) & G::CMASK)];                                                       \
+        if constexpr (G::OFFSET_ENTRIES) {                                                                       \
+            if constexpr (EXPECTED) V = make_double2(s_tab[tile_entry_pmf<G>(E16)], s_tab[tile_entry_exp<G>(E16)]); \
+            else V = s_tab[tile_entry_pmf<G>(E16)];                                                              \
+        } else { /* (the slot taken out once, as the tier-2 instances have always been compiled) */              \
+            const uint32_t s__ = tile_entry_slot<G>(E16);                                                        \
+            if constexpr (EXPECTED) V = make_double2(s_tab[tab_pmf<G>(s__, tile_entry_code<G>(E16))], s_tab[tab_exp<G>(s__, tile_entry_ne<G>(E16))]); \
+            else V = s_tab[tab_pmf<G>(s__, tile_entry_code<G>(E16))];                                            \
+        }                                                                                                        \
     } while (0)
 #endif
 #define TILE_RD(V, KK)                                                                                           \

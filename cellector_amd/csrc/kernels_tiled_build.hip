@@ -31,7 +31,7 @@ __device__ __forceinline__ uint16_t geo_encode(uint64_t e, uint32_t j)
 {
     const uint32_t r = ENT_REF(e), n = ENT_ALT(e) + r;
     const uint32_t code = G::NLO == 1 ? ent_code(e) : t2_code(n, r);
-    return (uint16_t)(((n - G::NLO) << 14) | ((ENT_IDX(e) - j * G::BLU) << G::SHIFT) | code);
+    return tile_entry<G>(ENT_IDX(e) - j * G::BLU, code);
 }
 template <bool FILL, class G = geo_reg>
 __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj, uint64_t tile0,
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj,
         const uint64_t e = csr_ent[i];
         if (geo_take<G>(e)) dst[k++] = geo_encode<G>(e, j);
     }
-    for (; k < K; k++) dst[k] = (uint16_t)(G::BLU << G::SHIFT);  // padding: the chunk's all-zero slot
+    for (; k < K; k++) dst[k] = tile_entry_null<G>();  // padding: the chunk's all-zero slot
 }
 
 // Bank-aware order of the entries inside the rows of one slice (option "bank_order"; a wave per slice, lane = row, the slice's rows
@@ -147,9 +147,8 @@ __global__ __launch_bounds__(T_BC) void k_tile_build(uint64_t nloc, uint32_t nj,
 __device__ __forceinline__ void tbo_banks(uint32_t e, uint32_t *a, uint32_t *b)
 {
     // (the tile kernel's own address function; code-major: both are the slot's bank pair, slot mod 32)
-    const uint32_t slot = (e >> geo_reg::SHIFT) & geo_reg::SMASK;
-    *a = tab_pmf<geo_reg>(slot, e & geo_reg::CMASK) & 31u;
-    *b = tab_exp<geo_reg>(slot, e >> 14) & 31u;
+    *a = tile_entry_pmf<geo_reg>(e) & 31u;
+    *b = tile_entry_exp<geo_reg>(e) & 31u;
 }
 // Which lane of its slice a row takes (any permutation of a slice's 64 rows is a valid layout).  The tile kernel adds a row's
 // sums to its cell's accumulator in LDS with one 16-byte read and one 16-byte write per lane: address = cell * 16, served in
@@ -258,7 +257,6 @@ __device__ void tile_bank_order(uint16_t *row /*this lane's K entries*/, uint32_
 //   * the slices are assembled in LDS and leave as whole 16-byte stores (rows written two bytes at a time straight to global
 //     memory cost 65x their bytes in partial-line traffic: 0.35 TB for 5.3 GB of tiles at 10^6 cells x 200k loci).
 // Same layout, bit for bit, as k_tile_build.
-__device__ __constant__ uint8_t T_NM1_OF[16] = {0, 0, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 3, 0, 0};  // alt+ref-1 of a code
 template <bool FILL, bool ORDER = false>
 __global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t nb, uint32_t nj, const uint64_t *__restrict__ csr_ptr,
                                                       const uint16_t *__restrict__ c4r, const uint32_t *__restrict__ toff /*[row][nj + 1]*/,
@@ -363,8 +361,7 @@ __global__ __launch_bounds__(T_BC, 8) void k_tile_build2(uint64_t nloc, uint32_t
                 do {                                                                                                   \
                     const uint32_t e__ = (E), code__ = e__ >> 12;                                                      \
                     if (code__ < (uint32_t)T_NCODE)                                                                    \
-                        dst[k++] = (uint16_t)(((uint32_t)T_NM1_OF[code__] << 14) |                                     \
-                                                  ((((e__ & (LR_LOCI - 1u)) - cbase) & (LR_LOCI - 1u)) << 4) | code__); \
+                        dst[k++] = tile_entry<geo_reg>(((e__ & (LR_LOCI - 1u)) - cbase) & (LR_LOCI - 1u), code__);     \
                 } while (0)
 #pragma unroll
                 for (uint32_t u = 0; u < TB_SEG; u++) TB_PUT(seg[u]);

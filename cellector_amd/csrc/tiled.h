@@ -26,9 +26,9 @@ static_assert(T_GROUPS_MAX == CELLECTOR_TILE_WORK_STRIDE, "k_alpha_beta resets t
 #define T_GROUPS 8      // chunk groups beyond this many are charged for their partial sums (tiled_build's cost model)
 #define T_ROW_U16 16    // u16 of a row held in registers (two 16-byte loads): 15 entries behind the cell id (K odd) or 16 (K even);
                         // longer rows: slow path
-// A u16 entry = n-1 << 14 | locus slot << 4 | code; where its log-pmf and its expected term sit in the chunk's table is the
-// geometry's business (tab_pmf / tab_exp below).
-#define T_NULL ((uint16_t)(T_BLU << 4))  // padding entry: code 0, n-1 = 0 of the zero slot
+// A u16 entry names a locus slot of the chunk and a code; its bits, and where its log-pmf and its expected term sit in the chunk's
+// table, are the geometry's business (tile_entry / tile_entry_pmf / tile_entry_exp and tab_pmf / tab_exp below).  T_NULL, the
+// padding entry (code 0 of the chunk's all-zero slot: both lookups read 0.0), is defined behind them.
 // A slice in `tiles` is 64 x (K + 1) u16, K = the entries of its longest row, at least 1 (every geometry: a slice without any
 // entry keeps one padding entry per row, 256 bytes, and the kernels need no form for an empty row; the tier-2 kernels skip it by
 // the header's flag).  Rows must start on a dword for the 16-byte loads, so the format follows from K's parity:
@@ -59,7 +59,8 @@ __device__ __forceinline__ uint32_t ent_code(uint64_t e)
 #define TB_PARTS 6  // waves of a k_build_tables workgroup: each takes its share of a locus' 18 values
 
 // Table / entry geometry of a tile set.  geo_reg: the regular entries (totals 1..T_K): 18 doubles per locus, u16 entry =
-// n-1 << 14 | slot << 4 | code.  geo_t2<NMAX>: the tier-2 tiles of a deep-coverage matrix (totals 5..NMAX, tiled_build):
+// E << 4 | c (offset entries, below; TILE_OE 0: n-1 << 14 | slot << 4 | code).  geo_t2<NMAX>: the tier-2 tiles of a deep-coverage
+// matrix (totals 5..NMAX, tiled_build):
 // NMAX = 8: 30 log-pmfs + 4 expected terms per locus, 338 loci per chunk, entry = n-5 << 14 | slot << 5 | pair;
 // NMAX = 6: 13 + 2 doubles per locus, 767 loci per chunk, entry = n-5 << 14 | slot << 4 | pair.
 // The image of a chunk's table (in global memory and, copied as it is, in LDS) is a property of the geometry:
@@ -72,10 +73,22 @@ __device__ __forceinline__ uint32_t ent_code(uint64_t e)
 #ifndef TILE_CM
 #define TILE_CM 1  // regular geometry: 1 = code-major table image, 0 = locus-major (the measurement's other arm)
 #endif
+// Offset entries (a code-major image whose expected-term planes fit 12 bits of element index): the entry carries where its two
+// values sit instead of naming slot, code and total, so that the tile kernel does not work that out again for every entry of every
+// pass —
+//   entry = E << 4 | c,   E = tab_exp(slot, n - NLO): the expected term's element (its plane is among the first LROW - NCODE),
+//                         c = the log-pmf's plane - the expected term's plane = LROW - NCODE + code - (n - NLO): 4..14,
+//   log-pmf element = E + c * BL (= tab_pmf(slot, code)); the total is E / BL + NLO, the slot E % BL, the code follows from c.
+// Two address instructions per value (shift + mask; field extract + multiply-add) where slot << 4 | code takes two for the slot and
+// two for each value.  The total's own field of the plain encoding is redundant with the code, which is where the bits come from.
+#ifndef TILE_OE
+#define TILE_OE 1  // regular geometry, code-major image: 1 = offset entries, 0 = n-1 << 14 | slot << 4 | code (the measurement's other arm)
+#endif
 struct geo_reg {
     static constexpr uint32_t LROW = T_LROW, BL = T_BL, NCODE = T_NCODE, SHIFT = 4, SMASK = 1023u, CMASK = 15u;
     static constexpr uint32_t BLU = BL - 1, NLO = 1, NHI = T_K;  // loci per chunk (the last slot is all zeros); totals covered
     static constexpr bool CODE_MAJOR = TILE_CM != 0;
+    static constexpr bool OFFSET_ENTRIES = CODE_MAJOR && TILE_OE != 0;
 };
 template <int NMAX>
 struct geo_t2 {
@@ -84,7 +97,7 @@ struct geo_t2 {
     static constexpr uint32_t BL = NMAX == 8 ? 339 : 768, SHIFT = NMAX == 8 ? 5 : 4, SMASK = NMAX == 8 ? 511u : 1023u,
                               CMASK = NMAX == 8 ? 31u : 15u;
     static constexpr uint32_t BLU = BL - 1, NLO = 5, NHI = NMAX;
-    static constexpr bool CODE_MAJOR = false;
+    static constexpr bool CODE_MAJOR = false, OFFSET_ENTRIES = false;  // (their fields do not fit 16 bits as offsets)
 };
 // THE index function of a chunk's table: element of the log-pmf of `code` resp. of the expected term number `ne` (= n - G::NLO)
 // of locus slot `slot`.  Everything that writes or reads a chunk table goes through these two.
@@ -98,6 +111,86 @@ __host__ __device__ __forceinline__ constexpr uint32_t tab_exp(uint32_t slot, ui
 {
     return G::CODE_MAJOR ? ne * G::BL + slot : slot * G::LROW + G::NCODE + ne;
 }
+// THE bit layout of a u16 tile entry: made from (slot, code), taken apart again, and turned into the elements of its two table
+// values.  The builders, the bank model and the tile kernel go through these and know no bits themselves.
+// total - NLO of a code (codes are numbered total by total, n + 1 of them for the total n: ent_code / t2_code)
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_code_ne(uint32_t code)
+{
+    uint32_t ne = 0;
+    for (uint32_t n = G::NLO, first = n + 1u; n < G::NHI && code >= first; n++, first += n + 1u) ne++;
+    return ne;
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint16_t tile_entry(uint32_t slot, uint32_t code)
+{
+    const uint32_t ne = tile_code_ne<G>(code);
+    if constexpr (G::OFFSET_ENTRIES) return (uint16_t)((tab_exp<G>(slot, ne) << 4) | (G::LROW - G::NCODE + code - ne));
+    else return (uint16_t)((ne << 14) | (slot << G::SHIFT) | code);
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_entry_ne(uint32_t e)  // total - NLO
+{
+    if constexpr (G::OFFSET_ENTRIES) return (e >> 4) / G::BL;
+    else return e >> 14;
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_entry_slot(uint32_t e)
+{
+    if constexpr (G::OFFSET_ENTRIES) return (e >> 4) % G::BL;
+    else return (e >> G::SHIFT) & G::SMASK;
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_entry_code(uint32_t e)
+{
+    if constexpr (G::OFFSET_ENTRIES) return (e & 15u) + tile_entry_ne<G>(e) - (G::LROW - G::NCODE);
+    else return e & G::CMASK;
+}
+// elements of the entry's log-pmf and of its expected term in the chunk's table (e: the 16 bits, zero-extended)
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_entry_pmf(uint32_t e)
+{
+    if constexpr (G::OFFSET_ENTRIES) return (e >> 4) + (e & 15u) * G::BL;
+    else return tab_pmf<G>(tile_entry_slot<G>(e), tile_entry_code<G>(e));
+}
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint32_t tile_entry_exp(uint32_t e)
+{
+    if constexpr (G::OFFSET_ENTRIES) return e >> 4;
+    else return tab_exp<G>(tile_entry_slot<G>(e), tile_entry_ne<G>(e));
+}
+// padding entry of a geometry: code 0 of the chunk's all-zero slot
+template <class G>
+__host__ __device__ __forceinline__ constexpr uint16_t tile_entry_null() { return tile_entry<G>(G::BLU, 0u); }
+#define T_NULL (tile_entry_null<geo_reg>())
+// Every (slot, code) of a geometry makes an entry that gives slot, code and total back and whose two elements are tab_pmf / tab_exp
+// of them, inside the chunk's image: a build that passes this cannot address outside the table.
+template <class G>
+constexpr bool tile_entries_round_trip()
+{
+    for (uint32_t slot = 0; slot < G::BL; slot++)
+        for (uint32_t code = 0; code < G::NCODE; code++) {
+            const uint32_t ne = tile_code_ne<G>(code), e = tile_entry<G>(slot, code);
+            const uint32_t pmf = tile_entry_pmf<G>(e), exp = tile_entry_exp<G>(e);
+            if (ne > G::NHI - G::NLO) return false;
+            if (tile_entry_slot<G>(e) != slot || tile_entry_code<G>(e) != code || tile_entry_ne<G>(e) != ne) return false;
+            if (pmf != tab_pmf<G>(slot, code) || exp != tab_exp<G>(slot, ne)) return false;
+            if (pmf >= G::LROW * G::BL || exp >= G::LROW * G::BL) return false;
+            if (G::OFFSET_ENTRIES && (G::LROW - G::NCODE + code - ne > 15u || exp >= 4096u)) return false;  // c: 4 bits, E: 12
+        }
+    return true;
+}
+static_assert(!geo_reg::OFFSET_ENTRIES || (geo_reg::LROW - geo_reg::NCODE) * geo_reg::BL <= 4096u,
+              "offset entries: the expected-term planes' elements take 12 bits");
+static_assert(tile_entries_round_trip<geo_reg>(), "regular tile entries");
+static_assert(tile_entries_round_trip<geo_t2<6>>(), "tier-2 tile entries, totals 5..6");
+static_assert(tile_entries_round_trip<geo_t2<8>>(), "tier-2 tile entries, totals 5..8");
+static_assert(tile_code_ne<geo_reg>(0) == 0 && tile_code_ne<geo_reg>(1) == 0 && tile_code_ne<geo_reg>(2) == 1 &&
+              tile_code_ne<geo_reg>(4) == 1 && tile_code_ne<geo_reg>(5) == 2 && tile_code_ne<geo_reg>(8) == 2 &&
+              tile_code_ne<geo_reg>(9) == 3 && tile_code_ne<geo_reg>(T_NCODE - 1) == 3, "codes of the totals 1..T_K (ent_code)");
+static_assert(tile_code_ne<geo_t2<8>>(5) == 0 && tile_code_ne<geo_t2<8>>(6) == 1 && tile_code_ne<geo_t2<8>>(13) == 2 &&
+              tile_code_ne<geo_t2<8>>(20) == 2 && tile_code_ne<geo_t2<8>>(21) == 3 && tile_code_ne<geo_t2<6>>(12) == 1,
+              "codes of the totals 5..8 (t2_code)");
 
 // overflow entries (alt+ref == 0 or > T_K)
 #define LF_LANES 16  // lanes that share a locus (k_locus_finalize) or a row (k_ovf_cell_wide)
