@@ -1,6 +1,7 @@
 // The re-staging calls of the C ABI: cellector_restage, cellector_combine and cellector_add_doublets replace the staged COO of a ctx
 // by one made from entries already on the device (kernels_restage.hip, kernels_combine.hip, kernels_doublets.hip) and take a READY
-// ctx back to STAGED; cellector_cell_origin, cellector_cell_source and cellector_staged_coo read the result.
+// ctx back to STAGED; cellector_cell_origin, cellector_cell_source and cellector_staged_coo read the result, and
+// cellector_write_mtx / cellector_format_mtx (kernels_mtx_write.hip) render it as mtx text.
 #include <vector>
 
 #include "ctx.h"
@@ -297,6 +298,48 @@ cellector_status cellector_add_doublets(cellector_ctx *c, const uint32_t *cell_a
     }
     // ---- validated: from here ctx changes
     return staged_append(c, lap, &dbl, dbl_origin, n_pairs, c->total_loci, false);
+}
+
+// ---- the staged matrix as mtx text -------------------------------------------------------------------------------------
+// what both calls check: the ctx (cellector_restage's scope), the mode, the flags
+static cellector_status write_scope(const cellector_ctx *c, const char *call, int mode, uint32_t flags)
+{
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "%s works on a single-device ctx: the staged entries of a multi-device ctx are sharded", call);
+    if (const char *why = restage_scope(c)) return ctx_fail(c, CELLECTOR_EINVAL, "%s: ctx %s", call, why);
+    if (mode != CELLECTOR_WRITE_ALIGNED && mode != CELLECTOR_WRITE_SPARSE && mode != CELLECTOR_WRITE_DEPTH)
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: mode %d is none of CELLECTOR_WRITE_ALIGNED, _SPARSE, _DEPTH", call, mode);
+    if (flags & ~(CELLECTOR_MTX_SPACE | CELLECTOR_MTX_HEADER_ZERO))
+        return ctx_fail(c, CELLECTOR_EINVAL, "%s: flags 0x%x hold a bit that is neither CELLECTOR_MTX_SPACE nor CELLECTOR_MTX_HEADER_ZERO", call, flags);
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_write_mtx(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint32_t flags,
+                                     cellector_write_summary *summary)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(write_scope(c, "write_mtx", mode, flags));
+    if (!first_path || !second_path) return ctx_fail(c, CELLECTOR_EINVAL, "write_mtx: %s is NULL", first_path ? "second_path" : "first_path");
+    if (!strcmp(first_path, second_path)) return ctx_fail(c, CELLECTOR_EINVAL, "write_mtx: both files are %s", first_path);
+    SETDEV(c);
+    return mtx_write_pair(c, first_path, second_path, mode, flags, summary);
+}
+
+cellector_status cellector_format_mtx(cellector_ctx *c, int which, int mode, uint32_t flags, uint64_t first_entry, uint64_t n_entries,
+                                      uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint64_t *n_lines)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(write_scope(c, "format_mtx", mode, flags));
+    if (which != 0 && which != 1) return ctx_fail(c, CELLECTOR_EINVAL, "format_mtx: which %d is neither 0 (first file) nor 1 (second)", which);
+    if (first_entry > c->coo.n || n_entries > c->coo.n - first_entry)
+        return ctx_fail(c, CELLECTOR_EINVAL, "format_mtx: entries [%llu, %llu + %llu) reach beyond the %llu staged", (unsigned long long)first_entry,
+                        (unsigned long long)first_entry, (unsigned long long)n_entries, (unsigned long long)c->coo.n);
+    SETDEV(c);
+    uint64_t bytes = 0, lines = 0;
+    const cellector_status st = mtx_format_range(c, which, mode, (flags & CELLECTOR_MTX_SPACE) ? ' ' : '\t', first_entry, n_entries, out, capacity,
+                                                 &bytes, &lines);
+    if (n_bytes) *n_bytes = bytes;  // (also when the capacity was too small)
+    if (n_lines) *n_lines = lines;
+    return st;
 }
 
 }  // extern "C"

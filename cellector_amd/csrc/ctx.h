@@ -129,6 +129,7 @@ struct CtxOptions {
     bool compute_expected = true;
     bool ref_arith = false;  // option ref_arith (engine 1): evaluate stats.rs:41-53 with ln_gamma differences, the reference's own rounding
     int64_t parse_window_opt = 0;  // option parse_window: 0 = whole file below 1 GB, 256 MB windows above; else the window in bytes
+    int64_t write_window_opt = 0;  // option write_window: entries per window of cellector_write_mtx / _format_mtx; 0 = 2^23
     bool fuse_filter = true;   // option "fuse_filter": an unsharded ctx applies the -80 locus filter inside k_locus_finalize (A/B)
     bool tally_delta = true;    // option "tally_delta": engine 2 keeps the exclusion set's per-(locus, code) counts across
                                 // iterations and updates them from the set's change (0: recounts every iteration; A/B)
@@ -691,6 +692,13 @@ cellector_status doublets_build(cellector_ctx *c, const CooView &in, uint64_t tc
 // ... origin [n_pairs] of the new cells: old_origin (device, null: identity) at host_cell_a
 cellector_status doublets_origin(cellector_ctx *c, const uint32_t *host_cell_a, uint64_t n_pairs, uint64_t tc, const uint32_t *old_origin,
                                  DevBuf<uint32_t> *origin);
+// cellector_write_mtx / cellector_format_mtx (kernels_mtx_write.hip) behind their checks: the staged entries as mtx text, window by
+// window (option write_window); only reads the ctx
+uint64_t mtx_write_window(const cellector_ctx *c);
+cellector_status mtx_write_pair(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint32_t flags,
+                                cellector_write_summary *sum);
+cellector_status mtx_format_range(cellector_ctx *c, int which, int mode, uint8_t sep, uint64_t first, uint64_t n, uint8_t *out,
+                                  uint64_t capacity, uint64_t *n_bytes, uint64_t *n_lines);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);

@@ -53,6 +53,8 @@ SIGNATURES = {
     "cellector_combine": (_i, [_vp, _vp, _vp, _vp, _u64, _d, _u64]),
     "cellector_cell_source": (_i, [_vp, _vp]),
     "cellector_add_doublets": (_i, [_vp, _vp, _vp, _u64, _d, _u64]),
+    "cellector_write_mtx": (_i, [_vp, _cp, _cp, _i, C.c_uint32, _vp]),
+    "cellector_format_mtx": (_i, [_vp, _i, _i, C.c_uint32, _u64, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -221,6 +223,25 @@ class JoinSummary(C.Structure):
     def as_dict(self):
         """the fields join.join_coo returns as its summary"""
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class WriteSummary(C.Structure):
+    _fields_ = [("n_entries", _u64), ("lines_first", _u64), ("lines_second", _u64), ("bytes_first", _u64), ("bytes_second", _u64),
+                ("n_dropped_keys", _u64), ("n_windows", _u64)]
+
+    def as_dict(self):
+        """the fields mtx_write.summary returns"""
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+WRITE_MODES = {"aligned": 0, "sparse": 1, "depth": 2, 0: 0, 1: 1, 2: 2}
+MTX_SPACE, MTX_HEADER_ZERO = 1, 2
+
+
+def _mtx_flags(sep, header_zero):
+    if sep not in ("\t", " ", b"\t", b" "):
+        raise ValueError("sep is a tab or a space")
+    return (MTX_SPACE if sep in (" ", b" ") else 0) | (MTX_HEADER_ZERO if header_zero else 0)
 
 
 JOIN_MODES = {"join": 1, "ref": 1, "depth": 2, 1: 1, 2: 2}
@@ -453,6 +474,32 @@ class Cellector:
         if n.value:
             self._ck(self._lib.cellector_staged_coo(self.h, C.byref(n), *[_p(a) for a in arrs], n.value))
         return tuple(arrs)
+
+    # ---- the staged matrix as mtx text, formatted on the GPU
+    def write_mtx(self, first, second, mode="aligned", sep="\t", header_zero=False):
+        """The staged matrix as a MatrixMarket text pair (cellector_write_mtx; mtx_write.write_pair is the byte-identical numpy
+        twin).  mode "aligned": alt / ref with explicit zeros, one line per entry, what load_mtx reads and the combiner writes (with
+        header_zero=True, its bytes); "sparse": the zero lines dropped, what load_mtx_joined(..., "ref") reads; "depth": alt and
+        alt + ref, what load_mtx_joined(..., "depth") reads.  Only reads the ctx.  Returns the WriteSummary."""
+        s = WriteSummary()
+        self._ck(self._lib.cellector_write_mtx(self.h, str(first).encode(), str(second).encode(), int(WRITE_MODES.get(mode, mode)),
+                                               _mtx_flags(sep, header_zero), C.byref(s)))
+        return s
+
+    def format_mtx(self, which, mode="aligned", first_entry=0, n_entries=None, sep="\t"):
+        """the body lines of the staged entries [first_entry, first_entry + n_entries) of file `which` (0 / 1) as bytes
+        (cellector_format_mtx); n_entries None: to the last entry"""
+        if n_entries is None:
+            n = C.c_uint64(0)
+            self._ck(self._lib.cellector_staged_coo(self.h, C.byref(n), None, None, None, None, 0))
+            n_entries = max(0, n.value - int(first_entry))
+        m, fl = int(WRITE_MODES.get(mode, mode)), _mtx_flags(sep, False)
+        nb, nl = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.cellector_format_mtx(self.h, int(which), m, fl, int(first_entry), int(n_entries), None, 0, C.byref(nb), C.byref(nl)))
+        out = np.empty(nb.value, np.uint8)
+        if nb.value:
+            self._ck(self._lib.cellector_format_mtx(self.h, int(which), m, fl, int(first_entry), int(n_entries), _p(out), nb.value, C.byref(nb), C.byref(nl)))
+        return out.tobytes()
 
     # ---- merging a second staged matrix in (the other half of the reference's combiner)
     def combine(self, src, keep=None, locus_map=None, total_loci=None, downsample_rate=0.0, seed=4):

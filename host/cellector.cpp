@@ -249,6 +249,49 @@ void write_run_barcodes_and_truth(const Params &params, RunInputs &in, size_t n_
     write_text("gt.tsv", gt_out);
 }
 
+// --write_matrices: the two names the matrix goes under (cellector_write_mtx, after the load)
+std::pair<const char *, const char *> written_matrix_names(const Params &params)
+{
+    return params.write_matrices - 1 == CELLECTOR_WRITE_DEPTH ? std::make_pair("ad.mtx", "dp.mtx") : std::make_pair("alt.mtx", "ref.mtx");
+}
+
+// --write_matrices, before a device is opened and before anything is written: an input of this run under one of the names the
+// flag writes in the output directory would be lost
+void refuse_to_overwrite_inputs_with_matrices(const Params &params)
+{
+    const auto [first, second] = written_matrix_names(params);
+    const bool own_barcodes = !params.mix() && !params.doublets;
+    std::vector<const char *> names{first, second};
+    if (own_barcodes) names.push_back("barcodes.tsv");
+    for (const char *name : names) {
+        const std::string path = params.output_directory + "/" + name;
+        struct stat mine, theirs;
+        if (stat(path.c_str(), &mine) != 0) continue;
+        for (const auto &[flag, file] : std::vector<std::pair<const char *, std::optional<std::string>>>{
+                 {"--alt", params.alt_mtx}, {"--ref", params.ref_mtx}, {"--mix_alt", params.mix_alt}, {"--mix_ref", params.mix_ref},
+                 {"--vcf", params.vcf}, {"--barcodes", params.barcodes}, {"--ground_truth", params.ground_truth},
+                 {"--mix_barcodes", params.mix_barcodes}, {"--mix_cells", params.mix_cells}, {"--cells", params.cells},
+                 {"--doublets", params.doublets}, {"--initial_minority", params.initial_minority}, {"--cell_detail", params.cell_detail},
+                 {"--classes", params.classes}, {"--donors", params.donors}})
+            if (file && stat(file->c_str(), &theirs) == 0 && mine.st_dev == theirs.st_dev && mine.st_ino == theirs.st_ino)
+                die(1, std::string("error: --write_matrices' ") + name + " would overwrite the " + flag + " file " + *file +
+                           ": choose another --output_directory");
+    }
+}
+
+// ... then barcodes.tsv of the cells in force, where --mix_* / --doublets have not written it already
+void write_barcodes_beside_matrices(const Params &params, const RunInputs &in)
+{
+    if (params.mix() || params.doublets) return;
+    std::string text;
+    for (size_t i = 0; i < in.cells.size(); i++) { text += in.cells[i]; text += '\n'; }
+    const std::string path = params.output_directory + "/barcodes.tsv";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) die(EXIT_PANIC, "Unable to create file " + path);
+    fwrite(text.data(), 1, text.size(), f);
+    fclose(f);
+}
+
 // a barcode list of an extension flag: one per line, first tab-separated column, blank lines ignored; file order, repeats kept
 std::vector<uint32_t> read_barcode_list(const Params &params, const CellNames &names, const char *flag, const std::string &path)
 {
@@ -320,7 +363,9 @@ RunInputs read_inputs(const Params &params)
             if (cell != SIZE_MAX && cell < in.ground_truth.size()) in.ground_truth[cell] = cols[1];
         }
     }
+    if (params.write_matrices) refuse_to_overwrite_inputs_with_matrices(params);
     if (params.mix() || params.doublets) write_run_barcodes_and_truth(params, in, n_first);
+    if (params.write_matrices) write_barcodes_beside_matrices(params, in);
 
     if (params.initial_minority) in.initial_minority = read_barcode_list(params, cells, "initial_minority", *params.initial_minority);
     if (params.cell_detail) in.detail_cells = read_barcode_list(params, cells, "cell_detail", *params.cell_detail);
@@ -490,16 +535,32 @@ void add_doublets(const Run &run)
     g.ck(st, "add_doublets");
 }
 
+// --write_matrices: the staged matrix as it is now, every flag that changes it applied, before the locus filter
+void write_matrices(const Run &run)
+{
+    const Params &params = run.params;
+    const auto [first, second] = written_matrix_names(params);
+    const int mode = params.write_matrices - 1;
+    cellector_write_summary s;
+    run.g.ck(cellector_write_mtx(run.g.c, run.out(first).c_str(), run.out(second).c_str(), mode, CELLECTOR_MTX_HEADER_ZERO, &s), "write_matrices");
+    fprintf(stderr, "write_matrices %s: %llu entries, %llu with alt = ref = 0%s: %llu lines, %llu bytes in %s; %llu lines, %llu bytes in %s; %llu windows\n",
+            mode == CELLECTOR_WRITE_DEPTH ? "depth" : mode == CELLECTOR_WRITE_SPARSE ? "sparse" : "aligned", (unsigned long long)s.n_entries,
+            (unsigned long long)s.n_dropped_keys, mode == CELLECTOR_WRITE_ALIGNED ? "" : " (in neither file)", (unsigned long long)s.lines_first,
+            (unsigned long long)s.bytes_first, first, (unsigned long long)s.lines_second, (unsigned long long)s.bytes_second, second,
+            (unsigned long long)s.n_windows);
+}
+
 // the matrix onto the device — the direct load, or ingest, restage, combine, add-doublets and finish — and its shape
 void load_matrix(Run &run)
 {
     const Params &params = run.params;
     const RunInputs &in = run.in;
     const Ctx &g = run.g;
-    if (!params.restage() && !params.mix() && !params.doublets && !params.matrix_pair) {
+    if (!params.restage() && !params.mix() && !params.doublets && !params.matrix_pair && !params.write_matrices) {
         g.ck(cellector_load_mtx(g.c, params.alt_mtx.c_str(), params.ref_mtx.c_str(), params.min_alt, params.min_ref), "load_cell_data");
     } else if (!params.restage() && !params.mix() && !params.doublets) {
         g.ck(ingest_pair(params, g.c, params.alt_mtx, params.ref_mtx), "load_cell_data");
+        if (params.write_matrices) write_matrices(run);
         g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
     } else {  // --cells / --downsample_rate: the staged matrix is cut and thinned on the device before the locus filter sees it
         g.ck(ingest_pair(params, g.c, params.alt_mtx, params.ref_mtx), "load_cell_data");
@@ -521,6 +582,7 @@ void load_matrix(Run &run)
         }
         if (params.mix()) combine_second_dataset(run);
         if (params.doublets) add_doublets(run);
+        if (params.write_matrices) write_matrices(run);
         g.ck(cellector_ingest_finish(g.c, params.min_alt, params.min_ref), "load_cell_data");
     }
     run.lap("load_mtx (text -> device)");

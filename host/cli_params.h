@@ -66,6 +66,9 @@ struct Params {
     // extension: how -a / -r (and --mix_alt / --mix_ref) belong together: 0 = zipped line by line (the reference's reading),
     // CELLECTOR_JOIN_REF = joined by (locus, cell), CELLECTOR_JOIN_DEPTH = likewise, -r holding alt + ref (cellector_ingest_mtx_joined)
     int matrix_pair = 0;
+    // extension: the staged matrix, after every flag that changes it, as an mtx text pair in the output directory
+    // (cellector_write_mtx): 0 = off, 1 + CELLECTOR_WRITE_ALIGNED / _SPARSE / _DEPTH
+    int write_matrices = 0;
 };
 
 // ---- one row of the option table --------------------------------------------------------------------------------
@@ -375,6 +378,21 @@ inline const std::vector<Opt> &options()
             "                                                                       error.  A key listed twice in one file is an error in both.  The\n"
             "                                                                       --mix_alt / --mix_ref pair is read the same way.  One stderr line\n"
             "                                                                       counts the keys; no output changes (not in the reference; one GPU)\n"),
+        Opt("write_matrices", 0, Kind::WORD_USAGE, &P::write_matrices).as("--write_matrices <aligned|sparse|depth>")
+            .one_of("off|aligned|sparse|depth", "expected aligned, sparse or depth").on_one_gpu("--write_matrices %s").paragraph(
+            "        --write_matrices <aligned|sparse|depth>                            write the matrix the run works on, after --matrix_pair, --cells,\n"
+            "                                                                       --downsample_rate, --mix_* and --doublets and before the locus\n"
+            "                                                                       filter, into the output directory as text formatted on the GPU,\n"
+            "                                                                       tab-separated with the combiner's header.  aligned: alt.mtx and\n"
+            "                                                                       ref.mtx, one line per entry, zeros explicit (the combiner's files;\n"
+            "                                                                       read back by default).  sparse: the same two names with the zero\n"
+            "                                                                       lines dropped (read back with --matrix_pair join).  depth: ad.mtx\n"
+            "                                                                       and dp.mtx, alt and alt + ref (read back with --matrix_pair depth).\n"
+            "                                                                       barcodes.tsv of the run's cells is written beside them where\n"
+            "                                                                       --mix_* or --doublets do not write it already.  An input of the\n"
+            "                                                                       run under one of these names in the output directory is refused.\n"
+            "                                                                       One stderr line gives the counts; no other output changes (not in\n"
+            "                                                                       the reference; one GPU)\n"),
     };
     return table;
 }

@@ -105,6 +105,8 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * per launch; 2 or 4 forces the width — tests; read per launch, same results to the bit; other values: CELLECTOR_EINVAL),
  * "parse_window" (default 0: a text file of 1 GB or more is uploaded and tokenised in 256 MB windows, a smaller
  * one whole; a positive value forces windows of that many bytes — tests; lines of a windowed file may be 1 MB long),
+ * "write_window" (default 0: cellector_write_mtx and cellector_format_mtx take the staged entries through windows of 2^23
+ * entries; a positive value forces windows of that many entries — tests; the bytes written do not depend on it),
  * "synth_continue_pct" (default 30: cellector_ingest_synthetic draws an entry's total as 1 + Geometric(0.7), vartrix-like
  * shallow coverage; a larger value gives deeper counts, e.g. 60 = 1 + Geometric(0.4) — benchmarks of the count distribution),
  * "norm_zero" (default 1: a shard clears the other shards' slices of CELLECTOR_XCHG_NORM before it writes
@@ -418,6 +420,61 @@ cellector_status cellector_cell_source(const cellector_ctx *ctx, uint8_t *out /*
  *   cellector_ingest_finish. */
 cellector_status cellector_add_doublets(cellector_ctx *ctx, const uint32_t *cell_a /*[n_pairs]*/, const uint32_t *cell_b /*[n_pairs]*/,
                                         uint64_t n_pairs, double downsample_rate, uint64_t seed);
+
+/* ---- the staged matrix as mtx text, made on the device: the way out for what the calls above make ------------------
+ * The reference's `combiner` is a program that writes files (combiner/src/main.rs:52-116: alt.mtx, ref.mtx, barcodes.tsv, gt.tsv).
+ * A matrix made on the device — a peel, a titration mixture, planted doublets, a downsampled copy, an AD / DP pair joined into
+ * alt / ref — leaves it through cellector_write_mtx as the text every tool of the field reads and the library's own three readers
+ * read back.  No format is invented here.  The lines are rendered by kernels (integers to decimal text, a byte-exact compaction
+ * into a stream); cellector_amd/mtx_write.py is the byte-identical numpy twin.
+ *   File layout: "%%MatrixMarket matrix coordinate real general\n% written by sprs\n", then `total_loci SEP total_cells SEP count\n`,
+ *   then one line `locus0+1 SEP cell0+1 SEP value\n` per entry that is written, entries in STAGED order.  Numbers are plain decimal
+ *   without sign, padding or exponent; the last byte of a file is '\n'.  SEP is '\t', or ' ' with CELLECTOR_MTX_SPACE (sprs /
+ *   vartrix); count is the number of body lines of the file, or 0 with CELLECTOR_MTX_HEADER_ZERO.  Tabs + HEADER_ZERO + mode ALIGNED
+ *   are the combiner's bytes (main.rs:67-69, :113-114).
+ *   mode CELLECTOR_WRITE_ALIGNED: both files hold one line per staged entry, zeros explicit: alt in the first, ref in the second
+ *   (read by cellector_ingest_mtx).  mode CELLECTOR_WRITE_SPARSE: the first file holds the entries with alt > 0, the second those
+ *   with ref > 0 (read by CELLECTOR_JOIN_REF).  mode CELLECTOR_WRITE_DEPTH: the first holds alt where alt > 0, the second alt + ref
+ *   where alt + ref > 0 (read by CELLECTOR_JOIN_DEPTH).
+ *   Index arithmetic: index + 1 is formed in 64 bits (index 2^32 - 1 is written 4294967296); alt + ref of DEPTH reaches 131070.
+ *   Dropped keys: n_dropped_keys counts the entries with alt = ref = 0 in every mode.  The combiner keeps them and ALIGNED writes
+ *   them; under SPARSE and DEPTH they are in neither file, so a read-back lacks exactly those keys.
+ *   Allowed where cellector_restage is: state STAGED, or a loaded matrix that kept its staged COO (option keep_coo 1) with no
+ *   iteration in flight; a single-device ctx that holds all cells.  The calls only read the ctx: the staged COO, the built matrix,
+ *   the EM state and every option are unchanged afterwards.
+ *   CELLECTOR_EINVAL with a message: a multi-device ctx, a communicator of more than one rank, a cellector_set_shard range, no
+ *   staged matrix, a loaded matrix without its COO, a call between cellector_em_begin and cellector_em_finish, an unknown mode or
+ *   flag bit, `which` outside 0 / 1, a range that reaches beyond the staged entries, a capacity below n_bytes (n_bytes and n_lines
+ *   are still returned), the two paths equal or NULL.
+ *   CELLECTOR_EIO when a file cannot be created, written or closed.  A failed call leaves what it has written and REMOVES NOTHING:
+ *   it never unlinks a path (a caller may pass a device node).  The first file is complete before the second is created.
+ *   Windows: the entries go through windows of option "write_window" entries (default 0 = 2^23; a positive value forces that many —
+ *   tests, like parse_window for the reader).  A window is formatted into one of two device buffers; while it is copied to pinned
+ *   host memory on a second stream and then written by a host thread, the next one is formatted into the other buffer.  The bytes
+ *   of a file depend neither on the window nor on the grid nor on the order the flags are or-ed in.  n_windows = the windows per
+ *   file, ceil(n_entries / window).  Under SPARSE / DEPTH without HEADER_ZERO the count of the size line needs a length pass over
+ *   all windows before the first byte is written.
+ *   Memory: per call two device and two pinned host buffers of 29 B (the longest line) per entry of a window, 8 B per 1024.
+ *   CELLECTOR_TIMING=1 prints one line: the host's time in formatting (and the two kernels' GPU time between events, summed over
+ *   the windows; the format kernel is then awaited), waiting for copies, waiting for writes.
+ * cellector_format_mtx: the body lines (no header) of the staged entries [first_entry, first_entry + n_entries) of file `which`
+ * (0 / 1) to host memory; out == NULL: n_bytes and n_lines only.  No byte of out outside [0, n_bytes) is written. */
+#define CELLECTOR_WRITE_ALIGNED 0
+#define CELLECTOR_WRITE_SPARSE 1
+#define CELLECTOR_WRITE_DEPTH 2
+#define CELLECTOR_MTX_SPACE 1u
+#define CELLECTOR_MTX_HEADER_ZERO 2u
+typedef struct {
+    uint64_t n_entries;                  /* staged entries                                                */
+    uint64_t lines_first, lines_second;  /* body lines of the two files                                   */
+    uint64_t bytes_first, bytes_second;  /* their sizes, header included                                  */
+    uint64_t n_dropped_keys;             /* entries with alt = ref = 0                                    */
+    uint64_t n_windows;                  /* windows per file                                              */
+} cellector_write_summary;
+cellector_status cellector_write_mtx(cellector_ctx *ctx, const char *first_path, const char *second_path, int mode, uint32_t flags,
+                                     cellector_write_summary *summary /*may be NULL*/);
+cellector_status cellector_format_mtx(cellector_ctx *ctx, int which, int mode, uint32_t flags, uint64_t first_entry, uint64_t n_entries,
+                                      uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint64_t *n_lines);
 
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
