@@ -342,4 +342,34 @@ cellector_status cellector_format_mtx(cellector_ctx *c, int which, int mode, uin
     return st;
 }
 
+// ---- ... and as .mtx.gz: BGZF made on the device (kernels_bgzf.hip) ------------------------------------------------------
+cellector_status cellector_write_mtx_bgzf(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint32_t flags,
+                                          cellector_write_bgzf_summary *summary)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    CHK(write_scope(c, "write_mtx_bgzf", mode, flags));
+    if (!first_path || !second_path)
+        return ctx_fail(c, CELLECTOR_EINVAL, "write_mtx_bgzf: %s is NULL", first_path ? "second_path" : "first_path");
+    if (!strcmp(first_path, second_path)) return ctx_fail(c, CELLECTOR_EINVAL, "write_mtx_bgzf: both files are %s", first_path);
+    SETDEV(c);
+    cellector_write_bgzf_summary gz = {};
+    CHK(mtx_write_pair(c, first_path, second_path, mode, flags, nullptr, &gz));
+    if (summary) *summary = gz;
+    return CELLECTOR_OK;
+}
+
+cellector_status cellector_bgzf_compress(cellector_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *n_out,
+                                         uint64_t *n_blocks)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "bgzf_compress works on a single-device ctx: a multi-device root ctx has no device of its own");
+    if (n && !in) return ctx_fail(c, CELLECTOR_EINVAL, "bgzf_compress: in is NULL for %llu bytes", (unsigned long long)n);
+    SETDEV(c);
+    uint64_t bytes = 0, blocks = 0;
+    const cellector_status st = bgzf_compress_host(c, in, n, out, capacity, &bytes, &blocks);
+    if (n_out) *n_out = bytes;  // (also when the capacity was too small)
+    if (n_blocks) *n_blocks = blocks;
+    return st;
+}
+
 }  // extern "C"

@@ -696,9 +696,33 @@ cellector_status doublets_origin(cellector_ctx *c, const uint32_t *host_cell_a, 
 // window (option write_window); only reads the ctx
 uint64_t mtx_write_window(const cellector_ctx *c);
 cellector_status mtx_write_pair(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint32_t flags,
-                                cellector_write_summary *sum);
+                                cellector_write_summary *sum, cellector_write_bgzf_summary *gz = nullptr /*non-null: BGZF files*/);
 cellector_status mtx_format_range(cellector_ctx *c, int which, int mode, uint8_t sep, uint64_t first, uint64_t n, uint8_t *out,
                                   uint64_t capacity, uint64_t *n_bytes, uint64_t *n_lines);
+// BGZF compression on the device (kernels_bgzf.hip; the format: bgzf_format.h).  bz_compress turns device text into members, one
+// launch per call; cellector_write_mtx_bgzf feeds it the writer's windows, cellector_bgzf_compress host bytes.
+struct BzScratch {
+    DevBuf<uint8_t> tables;               // BgzfTables
+    DevBuf<uint8_t> slots;                // [cap_blocks] members, one fixed slot each, before the compaction
+    DevBuf<uint64_t> sizes;               // [cap_blocks + 1] member sizes, then their offsets
+    DevBuf<unsigned long long> stored;    // [1] stored blocks of a launch
+    uint64_t cap_blocks = 0;
+    // CELLECTOR_TIMING=1: the two kernels' GPU time between events, summed over the calls (the compaction is then awaited)
+    bool timed = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms_block = 0, ms_compact = 0;
+    BzScratch() = default;
+    BzScratch(const BzScratch &) = delete;
+    BzScratch &operator=(const BzScratch &) = delete;
+    ~BzScratch();
+};
+uint64_t bz_blocks(uint64_t text_bytes);    // blocks of that many bytes of text
+uint64_t bz_out_capacity(uint64_t blocks);  // bytes a device buffer needs to take the members of that many blocks
+cellector_status bz_scratch(cellector_ctx *c, BzScratch *s, uint64_t cap_blocks);
+cellector_status bz_compress(cellector_ctx *c, BzScratch *s, const uint8_t *text, uint64_t n, uint8_t *out, uint64_t *bytes,
+                             uint64_t *blocks, uint64_t *stored);
+cellector_status bgzf_compress_host(cellector_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *n_out,
+                                    uint64_t *n_blocks);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);

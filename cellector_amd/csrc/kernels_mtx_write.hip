@@ -11,6 +11,9 @@
 // Lines are data-dependent in length (6 to 29 bytes) and a dropped entry (SPARSE / DEPTH) has none; nothing outside the window's
 // [0, bytes) is written.  The host side windows the entries, copies a window to pinned memory on a second stream while the next
 // one is formatted, and writes it from a thread of its own while the one after that is copied (mtx_write_file).
+// cellector_write_mtx_bgzf puts kernels_bgzf.hip between the format kernel and the copy: the window's text joins what the window before
+// left behind its last whole block (MwBgzf), the whole blocks of the FILE's text become BGZF members, and those are what is copied
+// and written; the rest is carried on.  The file's bytes do not depend on the window.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -18,6 +21,7 @@
 #include <future>
 
 #include "ctx.h"
+#include "bgzf_format.h"
 #include "mtx_format.h"
 
 #define MW_BLOCK 256
@@ -267,9 +271,8 @@ struct MwPipe {
     }
 };
 
-static cellector_status mw_pipe(cellector_ctx *c, MwPipe *p, uint64_t w_cap)
+static cellector_status mw_pipe(cellector_ctx *c, MwPipe *p, uint64_t cap /*bytes of a buffer*/)
 {
-    const uint64_t cap = w_cap * MTXF_MAX_LINE + 16;
     for (int b = 0; b < 2; b++) {
         CHK(dev_alloc(c, &p->dev[b], cap));
         if (hipHostMalloc((void **)&p->host[b], cap) != hipSuccess) {
@@ -283,10 +286,54 @@ static cellector_status mw_pipe(cellector_ctx *c, MwPipe *p, uint64_t w_cap)
     return CELLECTOR_OK;
 }
 
+// The text of one file on its way into BGZF blocks.  Blocks are cut at multiples of BGZF_PAYLOAD in the file's text: the header lines
+// go in front of the first window's text, and the ragged tail a window leaves (below BGZF_PAYLOAD bytes) is moved to the front of
+// the buffer for the next one by a device copy.
+#define MW_HEAD_MAX 160
+struct MwBgzf {
+    BzScratch scratch;
+    DevBuf<uint8_t> stage;  // a window's text as k_mw_format writes it (16-byte aligned)
+    DevBuf<uint8_t> text;   // what is carried | the window's text
+    uint64_t fill = 0;      // bytes in `text`
+    uint64_t file_bytes = 0, blocks = 0, stored = 0;  // of the file being written, so far
+};
+
+static uint64_t mwz_text_capacity(uint64_t w_cap) { return BGZF_PAYLOAD + MW_HEAD_MAX + w_cap * MTXF_MAX_LINE + 16; }
+
+static cellector_status mwz_init(cellector_ctx *c, MwBgzf *z, uint64_t w_cap)
+{
+    CHK(bz_scratch(c, &z->scratch, bz_blocks(mwz_text_capacity(w_cap))));
+    CHK(dev_alloc(c, &z->stage, w_cap * MTXF_MAX_LINE + 16));
+    return dev_alloc(c, &z->text, mwz_text_capacity(w_cap));
+}
+
+// m bytes from the host (the header lines) or from z->stage (a window) join the text; its whole blocks (all of it with `flush`) go to
+// `out` as members, the rest to the front.  Queued on c->stream behind the format kernel; the compaction is not awaited.
+static cellector_status mwz_push(cellector_ctx *c, MwBgzf *z, const void *host_src, uint64_t m, bool flush, uint8_t *out, uint64_t *out_bytes)
+{
+    *out_bytes = 0;
+    if (m) HIPCHK(c, hipMemcpyAsync(z->text + z->fill, host_src ? host_src : (const void *)z->stage.get(), m,
+                                    host_src ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    z->fill += m;
+    if (!out) return CELLECTOR_OK;
+    const uint64_t take = flush ? z->fill : z->fill / BGZF_PAYLOAD * BGZF_PAYLOAD, rest = z->fill - take;
+    uint64_t blocks = 0, stored = 0;
+    CHK(bz_compress(c, &z->scratch, z->text, take, out, out_bytes, &blocks, &stored));
+    // (take >= BGZF_PAYLOAD > rest: the two ranges do not overlap)
+    if (rest && take) HIPCHK(c, hipMemcpyAsync(z->text, z->text + take, rest, hipMemcpyDeviceToDevice, c->stream));
+    z->fill = rest;
+    z->file_bytes += *out_bytes;
+    z->blocks += blocks;
+    z->stored += stored;
+    return CELLECTOR_OK;
+}
+
 // One file: header, then the windows.  Window w is formatted into device buffer w & 1 while window w - 1 is copied to its pinned
 // buffer on the copy stream and window w - 2 is written by a thread of its own; a buffer is taken again only after its copy and
-// its write have ended.  `count` is the size line's third number.  Nothing is removed on a failure.
-static cellector_status mtx_write_file(cellector_ctx *c, MwScratch *s, MwPipe *p, const char *path, int which, int mode, uint8_t sep,
+// its write have ended.  `count` is the size line's third number.  Nothing is removed on a failure.  With z the file is the BGZF
+// stream of that text: a window's step compresses the text's whole blocks so far, one more step flushes the rest, and the EOF member
+// follows; file_bytes stays the size of the TEXT (z->file_bytes is the file's).
+static cellector_status mtx_write_file(cellector_ctx *c, MwScratch *s, MwPipe *p, MwBgzf *z, const char *path, int which, int mode, uint8_t sep,
                                        uint64_t count, uint64_t *file_bytes, uint64_t *file_lines, uint64_t *zeros, uint64_t *n_windows,
                                        double *phase_s /*[3]: format, wait for copies, wait for writes; may be null*/)
 {
@@ -296,9 +343,16 @@ static cellector_status mtx_write_file(cellector_ctx *c, MwScratch *s, MwPipe *p
     const int hn = snprintf(head, sizeof head, "%%%%MatrixMarket matrix coordinate real general\n%% written by sprs\n%llu%c%llu%c%llu\n",
                             (unsigned long long)c->total_loci, (char)sep, (unsigned long long)c->total_cells, (char)sep, (unsigned long long)count);
     cellector_status st = CELLECTOR_OK;
-    int io_err = write_all(fd, (const uint8_t *)head, (uint64_t)hn);
-    const uint64_t n = c->coo.n, W = mtx_write_window(c);
-    uint64_t bytes_of[2] = {0, 0}, total = (uint64_t)hn, lines = 0, zz = 0, nw = 0;
+    int io_err = 0;
+    uint64_t none = 0;
+    if (z) {
+        z->fill = z->file_bytes = z->blocks = z->stored = 0;
+        st = mwz_push(c, z, head, (uint64_t)hn, false, nullptr, &none);
+    } else {
+        io_err = write_all(fd, (const uint8_t *)head, (uint64_t)hn);
+    }
+    const uint64_t n = c->coo.n, W = mtx_write_window(c), n_win = (n + W - 1) / W, n_steps = n_win + (z ? 1 : 0);
+    uint64_t bytes_of[2] = {0, 0}, total = (uint64_t)hn, lines = 0, zz = 0, nw = 0;  // nw: steps taken
     std::future<int> writing;  // the write of the window before the last one copied
     LapTimer lt;
     auto lap = [&](int k) { const double d = lt.lap(); if (phase_s) phase_s[k] += d; };
@@ -315,13 +369,18 @@ static cellector_status mtx_write_file(cellector_ctx *c, MwScratch *s, MwPipe *p
         const uint64_t m = bytes_of[b];
         writing = std::async(std::launch::async, [fd, src, m]() { return write_all(fd, src, m); });
     };
-    for (uint64_t at = 0; at < n && st == CELLECTOR_OK && !io_err; at += W, nw++) {
+    for (; nw < n_steps && st == CELLECTOR_OK && !io_err; nw++) {
         const int b = (int)(nw & 1);
-        uint64_t l, z;
-        st = mw_window(c, s, mw_slice(c, at, n - at < W ? n - at : W), which, mode, sep, p->dev[b], &bytes_of[b], &l, &z);
+        const uint64_t at = nw * W;
+        uint64_t text = 0, l = 0, zeros_here = 0;
+        if (nw < n_win)
+            st = mw_window(c, s, mw_slice(c, at, n - at < W ? n - at : W), which, mode, sep, z ? z->stage.get() : p->dev[b].get(), &text, &l,
+                           &zeros_here);
+        bytes_of[b] = text;
+        if (z && st == CELLECTOR_OK) st = mwz_push(c, z, nullptr, text, nw == n_win, p->dev[b], &bytes_of[b]);
         lap(0);
         if (st != CELLECTOR_OK) break;
-        total += bytes_of[b]; lines += l; zz += z;
+        total += text; lines += l; zz += zeros_here;
         join_write();  // (window nw - 2 has left pinned buffer b)
         lap(2);
         hipError_t e = hipEventRecord(p->formatted[b], c->stream);
@@ -341,25 +400,32 @@ static cellector_status mtx_write_file(cellector_ctx *c, MwScratch *s, MwPipe *p
     // (nothing of this call may still be in flight when its buffers go)
     (void)hipStreamSynchronize(p->copy);
     (void)hipStreamSynchronize(c->stream);
+    if (z && st == CELLECTOR_OK && !io_err) {
+        io_err = write_all(fd, BGZF_EOF, BGZF_EOF_BYTES);
+        z->file_bytes += BGZF_EOF_BYTES;
+    }
     if (close(fd) != 0 && !io_err) io_err = errno ? errno : EIO;
     if (st == CELLECTOR_OK && io_err) st = ctx_fail(c, CELLECTOR_EIO, "write_mtx: cannot write %s: %s", path, strerror(io_err));
     *file_bytes = total;
     *file_lines = lines;
     *zeros = zz;
-    *n_windows = nw;
+    *n_windows = nw < n_win ? nw : n_win;
     return st;
 }
 
-// cellector_write_mtx behind its checks
+// cellector_write_mtx (gz null) / cellector_write_mtx_bgzf behind their checks
 cellector_status mtx_write_pair(cellector_ctx *c, const char *first_path, const char *second_path, int mode, uint32_t flags,
-                                cellector_write_summary *sum)
+                                cellector_write_summary *sum, cellector_write_bgzf_summary *gz)
 {
     const uint8_t sep = (flags & CELLECTOR_MTX_SPACE) ? ' ' : '\t';
     const uint64_t n = c->coo.n, W = mtx_write_window(c), w_cap = n < W ? n : W;
     MwScratch s;
     MwPipe p;
+    MwBgzf z;
     CHK(mw_scratch(c, &s, w_cap));
-    CHK(mw_pipe(c, &p, w_cap));
+    if (gz) CHK(mwz_init(c, &z, w_cap));
+    CHK(mw_pipe(c, &p, gz ? bz_out_capacity(z.scratch.cap_blocks) : w_cap * MTXF_MAX_LINE + 16));
+    cellector_write_bgzf_summary zout = {};
     const bool timing = getenv("CELLECTOR_TIMING") != nullptr;
     double phase[3] = {0, 0, 0};
     cellector_write_summary out = {};
@@ -380,17 +446,30 @@ cellector_status mtx_write_pair(cellector_ctx *c, const char *first_path, const 
             }
         }
         uint64_t zeros = 0, nw = 0;
-        const cellector_status st = mtx_write_file(c, &s, &p, which ? second_path : first_path, which, mode, sep, count,
+        const cellector_status st = mtx_write_file(c, &s, &p, gz ? &z : nullptr, which ? second_path : first_path, which, mode, sep, count,
                                                    which ? &out.bytes_second : &out.bytes_first, which ? &out.lines_second : &out.lines_first,
                                                    &zeros, &nw, timing ? phase : nullptr);
         out.n_windows = nw;
         out.n_dropped_keys = zeros;  // (the entries with alt = ref = 0, whichever file counted them; ALIGNED writes them)
+        (which ? zout.file_bytes_second : zout.file_bytes_first) = z.file_bytes;
+        (which ? zout.blocks_second : zout.blocks_first) = z.blocks;
+        zout.stored_blocks += z.stored;
         if (st != CELLECTOR_OK) return st;
     }
     if (timing)
         fprintf(stderr, "[timing]   write_mtx: %llu entries, %llu windows per file: format %.4f s (length kernels %.3f ms, format kernels %.3f ms), "
                         "waiting for copies %.4f s, for writes %.4f s\n",
                 (unsigned long long)n, (unsigned long long)out.n_windows, phase[0], s.ms_length, s.ms_format, phase[1], phase[2]);
+    if (timing && gz)
+        fprintf(stderr, "[timing]   write_mtx_bgzf: %llu + %llu bytes of text in %llu + %llu blocks (%llu stored) -> %llu + %llu bytes: "
+                        "block kernels %.3f ms, compaction kernels %.3f ms\n",
+                (unsigned long long)out.bytes_first, (unsigned long long)out.bytes_second, (unsigned long long)zout.blocks_first,
+                (unsigned long long)zout.blocks_second, (unsigned long long)zout.stored_blocks, (unsigned long long)zout.file_bytes_first,
+                (unsigned long long)zout.file_bytes_second, z.scratch.ms_block, z.scratch.ms_compact);
     if (sum) *sum = out;
+    if (gz) {
+        zout.text = out;
+        *gz = zout;
+    }
     return CELLECTOR_OK;
 }

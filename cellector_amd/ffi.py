@@ -55,6 +55,8 @@ SIGNATURES = {
     "cellector_add_doublets": (_i, [_vp, _vp, _vp, _u64, _d, _u64]),
     "cellector_write_mtx": (_i, [_vp, _cp, _cp, _i, C.c_uint32, _vp]),
     "cellector_format_mtx": (_i, [_vp, _i, _i, C.c_uint32, _u64, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "cellector_bgzf_compress": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "cellector_write_mtx_bgzf": (_i, [_vp, _cp, _cp, _i, C.c_uint32, _vp]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -232,6 +234,17 @@ class WriteSummary(C.Structure):
     def as_dict(self):
         """the fields mtx_write.summary returns"""
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class WriteBgzfSummary(C.Structure):
+    _fields_ = [("text", WriteSummary), ("file_bytes_first", _u64), ("file_bytes_second", _u64), ("blocks_first", _u64),
+                ("blocks_second", _u64), ("stored_blocks", _u64)]
+
+    def as_dict(self):
+        """text: the fields mtx_write.summary returns; the rest: the files as they are"""
+        out = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "text"}
+        out["text"] = self.text.as_dict()
+        return out
 
 
 WRITE_MODES = {"aligned": 0, "sparse": 1, "depth": 2, 0: 0, 1: 1, 2: 2}
@@ -499,6 +512,27 @@ class Cellector:
         out = np.empty(nb.value, np.uint8)
         if nb.value:
             self._ck(self._lib.cellector_format_mtx(self.h, int(which), m, fl, int(first_entry), int(n_entries), _p(out), nb.value, C.byref(nb), C.byref(nl)))
+        return out.tobytes()
+
+    # ---- ... and as .mtx.gz: BGZF made on the GPU
+    def write_mtx_bgzf(self, first, second, mode="aligned", sep="\t", header_zero=False):
+        """write_mtx's pair as BGZF files (cellector_write_mtx_bgzf): each file is bgzf.compress of the file write_mtx writes with
+        the same arguments, whatever option write_window says; load_mtx and load_mtx_joined read the paths as they are.  Returns
+        the WriteBgzfSummary (its .text is write_mtx's summary)."""
+        s = WriteBgzfSummary()
+        self._ck(self._lib.cellector_write_mtx_bgzf(self.h, str(first).encode(), str(second).encode(), int(WRITE_MODES.get(mode, mode)),
+                                                    _mtx_flags(sep, header_zero), C.byref(s)))
+        return s
+
+    def bgzf_compress(self, data):
+        """`data` (bytes) as a BGZF stream, compressed on this ctx's GPU (cellector_bgzf_compress; bgzf.compress is the
+        byte-identical numpy twin).  Works in any state of the ctx and leaves it as it is."""
+        src = np.frombuffer(bytes(data), np.uint8)
+        n_out, n_blocks = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.cellector_bgzf_compress(self.h, _p(src) if len(src) else None, len(src), None, 0, C.byref(n_out), C.byref(n_blocks)))
+        out = np.empty(n_out.value, np.uint8)
+        self._ck(self._lib.cellector_bgzf_compress(self.h, _p(src) if len(src) else None, len(src), _p(out), n_out.value, C.byref(n_out),
+                                                   C.byref(n_blocks)))
         return out.tobytes()
 
     # ---- merging a second staged matrix in (the other half of the reference's combiner)

@@ -249,9 +249,12 @@ void write_run_barcodes_and_truth(const Params &params, RunInputs &in, size_t n_
     write_text("gt.tsv", gt_out);
 }
 
-// --write_matrices: the two names the matrix goes under (cellector_write_mtx, after the load)
+// --write_matrices: the two names the matrix goes under (cellector_write_mtx or, with --write_matrices_gz, cellector_write_mtx_bgzf,
+// after the load)
 std::pair<const char *, const char *> written_matrix_names(const Params &params)
 {
+    if (params.write_matrices_gz)
+        return params.write_matrices - 1 == CELLECTOR_WRITE_DEPTH ? std::make_pair("ad.mtx.gz", "dp.mtx.gz") : std::make_pair("alt.mtx.gz", "ref.mtx.gz");
     return params.write_matrices - 1 == CELLECTOR_WRITE_DEPTH ? std::make_pair("ad.mtx", "dp.mtx") : std::make_pair("alt.mtx", "ref.mtx");
 }
 
@@ -542,12 +545,24 @@ void write_matrices(const Run &run)
     const auto [first, second] = written_matrix_names(params);
     const int mode = params.write_matrices - 1;
     cellector_write_summary s;
-    run.g.ck(cellector_write_mtx(run.g.c, run.out(first).c_str(), run.out(second).c_str(), mode, CELLECTOR_MTX_HEADER_ZERO, &s), "write_matrices");
-    fprintf(stderr, "write_matrices %s: %llu entries, %llu with alt = ref = 0%s: %llu lines, %llu bytes in %s; %llu lines, %llu bytes in %s; %llu windows\n",
+    cellector_write_bgzf_summary gz = {};
+    if (params.write_matrices_gz) {
+        run.g.ck(cellector_write_mtx_bgzf(run.g.c, run.out(first).c_str(), run.out(second).c_str(), mode, CELLECTOR_MTX_HEADER_ZERO, &gz),
+                 "write_matrices");
+        s = gz.text;
+    } else {
+        run.g.ck(cellector_write_mtx(run.g.c, run.out(first).c_str(), run.out(second).c_str(), mode, CELLECTOR_MTX_HEADER_ZERO, &s), "write_matrices");
+    }
+    fprintf(stderr, "write_matrices %s: %llu entries, %llu with alt = ref = 0%s: %llu lines, %llu bytes in %s; %llu lines, %llu bytes in %s; %llu windows",
             mode == CELLECTOR_WRITE_DEPTH ? "depth" : mode == CELLECTOR_WRITE_SPARSE ? "sparse" : "aligned", (unsigned long long)s.n_entries,
             (unsigned long long)s.n_dropped_keys, mode == CELLECTOR_WRITE_ALIGNED ? "" : " (in neither file)", (unsigned long long)s.lines_first,
             (unsigned long long)s.bytes_first, first, (unsigned long long)s.lines_second, (unsigned long long)s.bytes_second, second,
             (unsigned long long)s.n_windows);
+    if (params.write_matrices_gz)  // (the bytes above are the text's)
+        fprintf(stderr, "; compressed to %llu and %llu bytes in %llu and %llu blocks (%llu stored)", (unsigned long long)gz.file_bytes_first,
+                (unsigned long long)gz.file_bytes_second, (unsigned long long)gz.blocks_first, (unsigned long long)gz.blocks_second,
+                (unsigned long long)gz.stored_blocks);
+    fputc('\n', stderr);
 }
 
 // the matrix onto the device — the direct load, or ingest, restage, combine, add-doublets and finish — and its shape

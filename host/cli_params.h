@@ -69,6 +69,7 @@ struct Params {
     // extension: the staged matrix, after every flag that changes it, as an mtx text pair in the output directory
     // (cellector_write_mtx): 0 = off, 1 + CELLECTOR_WRITE_ALIGNED / _SPARSE / _DEPTH
     int write_matrices = 0;
+    bool write_matrices_gz = false;                    // ... as .mtx.gz: BGZF compressed on the GPU (cellector_write_mtx_bgzf)
 };
 
 // ---- one row of the option table --------------------------------------------------------------------------------
@@ -393,6 +394,13 @@ inline const std::vector<Opt> &options()
             "                                                                       run under one of these names in the output directory is refused.\n"
             "                                                                       One stderr line gives the counts; no other output changes (not in\n"
             "                                                                       the reference; one GPU)\n"),
+        Opt("write_matrices_gz", 0, Kind::WORD, &P::write_matrices_gz).as("--write_matrices_gz true").one_of("false|true", "expected true or false")
+            .requires_option("write_matrices").paragraph(
+            "        --write_matrices_gz <true>                                         with --write_matrices: the same two files as alt.mtx.gz and\n"
+            "                                                                       ref.mtx.gz (ad.mtx.gz and dp.mtx.gz), block-compressed gzip (BGZF,\n"
+            "                                                                       what bgzip writes) made on the GPU: zcat, gzip -t and -a / -r of\n"
+            "                                                                       this program read them.  The stderr line gains the compressed\n"
+            "                                                                       sizes (not in the reference)\n"),
     };
     return table;
 }
@@ -525,6 +533,8 @@ inline Params load_params(int argc, char **argv)
     if (p.zscore && p.resolve_assignments)
         die(1, "error: The argument '--normalization zscore' cannot be used with '--resolve_assignments " + got["resolve_assignments"] +
                    "': the reference has no arithmetic of that score to resolve to");
+    if (p.write_matrices_gz && !p.write_matrices)
+        die(1, "error: The argument '--write_matrices_gz true' requires '--write_matrices <aligned|sparse|depth>'");
     if (p.cluster && p.classes) die(1, "error: The argument '--cluster <K>' cannot be used with '--classes <file>'");
     if (got.count("cluster_restarts") && (p.cluster_restarts < 1 || p.cluster_restarts * p.cluster > 64))
         die(1, "error: Invalid value '" + got["cluster_restarts"] + "' for '--cluster_restarts <R>': expected 1..64 / K");

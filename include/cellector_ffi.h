@@ -476,6 +476,42 @@ cellector_status cellector_write_mtx(cellector_ctx *ctx, const char *first_path,
 cellector_status cellector_format_mtx(cellector_ctx *ctx, int which, int mode, uint32_t flags, uint64_t first_entry, uint64_t n_entries,
                                       uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint64_t *n_lines);
 
+/* ---- the same text as .mtx.gz, compressed block-wise on the device -------------------------------------------------
+ * The field ships matrices as .mtx.gz, and cellector_write_mtx is bound by write(2), not by its kernels.  cellector_write_mtx_bgzf
+ * writes the SAME text as BGZF (block-compressed gzip, what `bgzip` writes): independent gzip members of at most 64 KB, each with
+ * its own CRC-32 and size field, then the 28-byte EOF member.  zcat, gzip -t, Python's gzip, htslib, the reference's
+ * MultiGzDecoder (load_data.rs:246) and this library's own block-parallel reader (cellector_ingest_mtx and the joins take the
+ * paths as they are) read it.  No format is invented.
+ *   The stream: the text is cut at multiples of 32640 bytes; every piece is one member (18-byte BGZF header, one deflate block with
+ *   BFINAL = 1, CRC-32, ISIZE).  The deflate block uses a PRESET Huffman table sent in the block (BTYPE = 10, the same bits in every
+ *   block), and its only matches are against the same column of the line before: (length, distance = the length of that line), in
+ *   pieces of at most 258 bytes; everything is defined inside a block.  A block the preset does not make smaller than len + 5 bytes
+ *   is a stored block (BTYPE = 00).  cellector_amd/bgzf.py states the format and is the byte-identical numpy twin;
+ *   cellector_amd/csrc/bgzf_format.h is its C form.  The bytes depend neither on the grid nor on any option.
+ * cellector_bgzf_compress: n host bytes as their BGZF stream in host memory, compressed on the ctx's device; any ctx with a device
+ *   of its own will do (state EMPTY included; a multi-device root ctx is refused).  n_out receives the stream's size (EOF member
+ *   included), n_blocks its data blocks; out == NULL: those only.  CELLECTOR_EINVAL when capacity < n_out: the sizes are still
+ *   returned and not a byte of out is written.  No byte of out outside [0, n_out) is written.  The ctx is only used for its device
+ *   and stream: nothing of its state changes.
+ * cellector_write_mtx_bgzf: the arguments, modes, flags, scope and refusals of cellector_write_mtx; each file equals the BGZF
+ *   stream (cellector_bgzf_compress, bgzf.compress) of the file cellector_write_mtx would have written, the three header lines
+ *   included.  Blocks are cut in the FILE's text, not in a window's: what a window leaves behind its last whole block is carried
+ *   to the next on the device, so the files do not depend on "write_window".  summary->text is what cellector_write_mtx reports
+ *   (sizes of the TEXT); file_bytes_* are the sizes of the files, blocks_* their data blocks, stored_blocks those of both files
+ *   that are stored.  Memory: the text buffers of cellector_write_mtx once more on the device (one aligned, one with the carry), the
+ *   members' slots, and pinned buffers of the compressed worst case.  CELLECTOR_TIMING=1 prints cellector_write_mtx's line and
+ *   one more: blocks, bytes in and out, the two compress kernels' GPU time. */
+typedef struct {
+    cellector_write_summary text;                  /* what cellector_write_mtx reports for the same arguments */
+    uint64_t file_bytes_first, file_bytes_second;  /* sizes of the two files, EOF member included              */
+    uint64_t blocks_first, blocks_second;          /* their data blocks                                       */
+    uint64_t stored_blocks;                        /* blocks of both files that are stored                    */
+} cellector_write_bgzf_summary;
+cellector_status cellector_bgzf_compress(cellector_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity,
+                                         uint64_t *n_out, uint64_t *n_blocks);
+cellector_status cellector_write_mtx_bgzf(cellector_ctx *ctx, const char *first_path, const char *second_path, int mode, uint32_t flags,
+                                          cellector_write_bgzf_summary *summary /*may be NULL*/);
+
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
     CELLECTOR_XCHG_PASS1 = 0, /* [5*total_loci]: cells_ref | cells_alt | sum_ref | sum_alt | n_entries */
