@@ -254,7 +254,8 @@ cellector_status cellector_create(cellector_ctx **out, int device_id)
               hipHostMalloc((void **)&c->h_sel, 32 * sizeof(double)) == hipSuccess &&
               (memset(c->h_sel, 0, 32 * sizeof(double)), true) &&
               hipHostGetDevicePointer((void **)&c->h_sum_dev, c->h_sel, 0) == hipSuccess &&
-              dev_alloc(c, &c->t2_ctr, 3) == CELLECTOR_OK &&
+              dev_alloc(c, &c->t2_ctr, T2_CTR_N) == CELLECTOR_OK &&
+              hipMemset(c->t2_ctr, 0, T2_CTR_N * sizeof(uint32_t)) == hipSuccess &&  // (the caching passes' counters start clear)
               create_side_stream(&c->side) &&
               create_side_stream(&c->side2) &&
               hipEventCreateWithFlags(&c->ev_t2tab, hipEventDisableTiming) == hipSuccess &&
@@ -488,6 +489,14 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
     else if (!strcmp(key, "t2_helper")) {
         if (v < -1 || v > 64) return ctx_fail(c, CELLECTOR_EINVAL, "t2_helper must be -1 (automatic), 0 (off) or 1..64 blocks per free CU (forced)");
         c->t2_helper = (int)v;
+    }
+    else if (!strcmp(key, "t2_cache")) {
+        if (v < -1 || v > 1) return ctx_fail(c, CELLECTOR_EINVAL, "t2_cache must be -1 (automatic), 0 (off) or 1 (on)");
+        c->t2_cache = (int)v;
+    }
+    else if (!strcmp(key, "t2_fill")) {
+        if (v < -1 || v > 1) return ctx_fail(c, CELLECTOR_EINVAL, "t2_fill must be -1 (decided on the device), 0 (bypass) or 1 (fill)");
+        c->t2_fill = (int)v;
     }
     else if (!strcmp(key, "t2")) {
         if (v < -1 || v > 1) return ctx_fail(c, CELLECTOR_EINVAL, "t2 must be -1 (automatic), 0 or 1");

@@ -168,7 +168,11 @@ struct CtxOptions {
                                      // (512, or 256 beside a helper grid)
     int t2_helper = -1;              // option "t2_helper": blocks of k_t2_cell's helper grid per CU the tile grid leaves free; -1 = automatic
                                      // (EM pass only), 0 = none, n = forced, on one CU's worth when none is free (tests)
-    int t2_tiles_opt = -1;           // option "t2_tiles": -1 = automatic (8 on an ovf_deep matrix), 0 = off, 6 / 8 = totals 5..6 / 5..8
+    int t2_cache = -1;               // option "t2_cache": the EM pass' tier-2 lookups keep their values per entry (t2_val) and gather
+                                     // again only at loci whose (alpha, beta) bits moved; 0 = off, 1 = on, -1 = automatic (t2_cache_on)
+    int t2_fill = -1;                // option "t2_fill": what a caching pass does with dirty loci: 1 = gather and store (fill), 0 = gather
+                                     // without storing (bypass), -1 = decided on the device from the loci that moved since the last pass
+    int t2_tiles_opt = -1;           // option "t2_tiles":-1 = automatic (8 on an ovf_deep matrix), 0 = off, 6 / 8 = totals 5..6 / 5..8
     int c4_bits_opt = 0;             // option "compact_bits": 0 = automatic, 32 = force the 32-bit entries
     int locus_mode = 0;              // option "locus_mode": 0 = chosen on the device per iteration, 1 = stream the compact CSC,
                                      // 2 = minority-driven tally over the by-cell CSR
@@ -294,6 +298,13 @@ struct CtxTiled {
     DevBuf<uint32_t> t2_pmask;       // [L] bit c2: the pair occurs at the locus (static)
     DevBuf<uint32_t> cnt2;           // [L][32] ... of the cells of the exclusion set (k_t2_minority; kept across iterations, see tally_valid)
     DevBuf<double> tab2;             // [L][48] per pass: log-pmfs of the pairs that occur + expected terms, six 64-byte sectors per locus
+    // the EM pass' lookup values kept per entry (option t2_cache; k_t2_cell<.., CACHE>): made with the ELLPACK copy, gone with it
+    uint64_t ovf_ell_slots = 0;      // slots of ovf_ell
+    DevBuf<double2> t2_val;          // [ovf_ell_slots] (log-pmf, expected term) per slot of ovf_ell, same layout; 0 where no tier-2 entry
+    DevBuf<double2> ab_t2;           // [L] the (alpha, beta) bits a locus' kept values were written under (all-ones: none yet)
+    DevBuf<double2> ab_last;         // [L] the (alpha, beta) bits of the last caching pass (the fill rule counts what moved since)
+    DevBuf<uint32_t> t2_dirty;       // [(L + 63) / 64 * 2] bit l: ab differs from ab_t2 in this pass (k_t2_tables writes every word)
+    bool t2_val_exp = false;         // every kept value has its expected term (a pass without the column stores none)
     // tier-2 TILES (deep coverage; tiled.h, geo_t2): the cell side of the totals 5..t2_tiles walks a second tile set with
     // its own chunk tables in LDS instead of evaluating those entries one by one (k_ovf_cell_wide keeps the other totals)
     int t2_tiles = 0;                // 0, 6 or 8: in use (tiled_build)
@@ -383,7 +394,10 @@ struct cellector_ctx : CtxOptions, CtxStaged, CtxBuilt, CtxTiled, CtxCarry {
 
     DevBuf<double> lf;            // [LF_TABLE_N] ln factorial table
     DevBuf<uint32_t> d_counters;  // [8] device scratch counters
-    DevBuf<uint32_t> t2_ctr;      // [3] next 64-row group of the tier-2 lookups, per table set (reset by k_t2_tables)
+    DevBuf<uint32_t> t2_ctr;      // [T2_CTR_N] [0..2] next 64-row group of the tier-2 lookups, per table set (reset by k_t2_tables);
+                                  // [4 + 2p], [5 + 2p] dirty loci / loci moved since the last pass, of the caching passes of parity p
+                                  // (a pass' k_t2_tables adds to its own pair and clears the other)
+    uint32_t t2_pass = 0;         // caching passes launched so far
     // cellector_assign's host arrays, kept between calls: a device-to-host copy into memory the process has not touched
     // before costs milliseconds, into a buffer used before microseconds
     struct AssignHost {
@@ -428,6 +442,7 @@ inline void invalidate_cell_ll_state(cellector_ctx *c)
 }
 
 #define SEL_T 6
+#define T2_CTR_N 8
 #define CELLECTOR_SUM_SEQ 31
 #define CELLECTOR_SEL_HIST_WORDS (4096 + SEL_T * 1024 + 64)
 
@@ -741,6 +756,11 @@ cellector_status tiled_masked_recount(cellector_ctx *c, uint8_t *ones);
 // ... under the mask of one call, into the caller's scratch cnt [nloc] (host_mask [L] or null = all used); the ctx's own stay
 cellector_status tiled_call_masked_count(cellector_ctx *c, const uint8_t *host_mask, uint32_t *cnt);
 cellector_status tiled_prebuild_tables(cellector_ctx *c);
+// the store of option t2_cache for the ELLPACK copy the ctx holds, empty (kernels_tiled_build.hip; no-op where k_t2_cell does not run)
+cellector_status t2_cache_alloc(cellector_ctx *c);
+// option t2_cache resolved for the shard the ctx holds.  Automatic: on a big shard, whose lookups miss the L2 (a 77 MB table at
+// 200k loci) and whose tile kernel streams through their traffic; a small shard's lookups hit it and gain nothing
+inline bool t2_cache_on(const cellector_ctx *c) { return c->t2_cache > 0 || (c->t2_cache < 0 && c->nloc >= (1ull << 19)); }
 cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, double lp_maj, double lp_dbl, double *sdbl);
 // device-side mtx text parse (kernels_parse.hip); the pair's bytes and header: mtx_bytes.h
 struct MtxInput;

@@ -758,14 +758,61 @@ __global__ __launch_bounds__(256) void k_ovf_cell_wide(uint64_t n_rows, const ui
 // the long expected-term loop — took 0.41 ms beside the tile kernel at 200k loci, 0.30 ms on a 125k-cell shard.)
 // Slots of pairs that do not occur are never written and never read.  A masked locus (alpha < 0) gets zeros: its
 // entries add nothing.
+//
+// A caching pass (option t2_cache, k_t2_cell<.., CACHE>) has this kernel say which loci it must gather again: blocks [g0, ...)
+// take 1024 loci each, a thread per locus and turn, and compare the pass' (alpha, beta) BITS with those the locus' kept values were written under (ab_t2;
+// the masked encoding alpha = -1 like any other value) and with the last caching pass' (ab_last, brought up to date here: one
+// thread per locus).  A wave writes its 64 loci's dirty bits as two whole words — every word of the mask, every pass, nothing
+// to clear — and adds its counts to the pass' pair of counters; the other pair, the previous pass', is cleared for the next.
+// Validity is this comparison and nothing else: whatever moved alpha / beta (the exclusion set, the loci mask, a reset, an
+// engine switch, a posterior phase in between) shows here, and no call site has anything to invalidate.
+struct t2_dirty_t {
+    uint32_t *bits;         // null: not a caching pass.  [ceil(L / 64)][2] bit l % 64 of word pair l / 64: locus l is dirty
+    uint32_t g0, L;         // first block of the per-locus part; loci
+    const double2 *ab_t2;   // [L]
+    double2 *ab_last;       // [L]
+    uint32_t *cnt, *other;  // [2] dirty loci, loci that moved since the last caching pass: this pass' / the one to clear
+};
+__device__ __forceinline__ bool ab_differ(double2 a, double2 b)
+{
+    return __double_as_longlong(a.x) != __double_as_longlong(b.x) || __double_as_longlong(a.y) != __double_as_longlong(b.y);
+}
 template <bool EXPECTED>
 __global__ __launch_bounds__(256) void k_t2_tables(uint32_t n_pairs, const uint32_t *__restrict__ plist /*locus << 5 | pair*/,
                                                    uint32_t n_sec, const uint32_t *__restrict__ slist /*locus << 3 | sector*/,
                                                    uint32_t gp, const double2 *__restrict__ ab, const double *__restrict__ lf,
-                                                   double *__restrict__ tab2, uint32_t *__restrict__ grp_ctr /*null: none*/)
+                                                   double *__restrict__ tab2, uint32_t *__restrict__ grp_ctr /*null: none*/,
+                                                   t2_dirty_t dz)
 {
     // (the lookups that follow on this stream deal their row groups from this counter: reset here, no memset of its own)
     if (grp_ctr && blockIdx.x == 0 && threadIdx.x == 0) *grp_ctr = 0u;
+    if (dz.bits && blockIdx.x == 0 && threadIdx.x == 0) dz.other[0] = dz.other[1] = 0u;
+    if (dz.bits && blockIdx.x >= dz.g0) {
+        // (a wave takes 256 loci, 64 at a time, and adds its counts once: the lookups wait for this kernel, and thousands of
+        //  atomics on one address in front of them are time the side chain does not have beside an all-dirty pass)
+        const uint32_t lane = threadIdx.x & 63u, l0 = ((blockIdx.x - dz.g0) * 4u + (threadIdx.x >> 6)) * 256u;
+        uint32_t nd = 0, nm = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t l = l0 + k * 64u + lane;
+            bool dirty = false, moved = false;
+            if (l < dz.L) {
+                const double2 p = ab[l];
+                dirty = ab_differ(p, dz.ab_t2[l]);
+                moved = ab_differ(p, dz.ab_last[l]);
+                if (moved) dz.ab_last[l] = p;
+            }
+            const uint64_t bd = __ballot(dirty), bm = __ballot(moved);
+            if (lane == 0u && l < dz.L) {  // (l: the first of the 64 loci, a multiple of 64)
+                dz.bits[(l >> 6) * 2] = (uint32_t)bd;
+                dz.bits[(l >> 6) * 2 + 1] = (uint32_t)(bd >> 32);
+            }
+            nd += (uint32_t)__popcll(bd);
+            nm += (uint32_t)__popcll(bm);
+        }
+        if (lane == 0u && nd) atomicAdd(&dz.cnt[0], nd);
+        if (lane == 0u && nm) atomicAdd(&dz.cnt[1], nm);
+        return;
+    }
     if (blockIdx.x < gp) {
         const uint32_t i = blockIdx.x * 256 + threadIdx.x;
         if (i >= n_pairs) return;
@@ -872,14 +919,54 @@ __global__ __launch_bounds__(256) void k_t2_tile_add(uint64_t n_rows, uint32_t g
 constexpr unsigned T2_HELP_LDS = 8192;  // dynamic LDS a helper block asks for and does not use: no room beside a tile workgroup
 constexpr unsigned T2_HELP_BLOCKS = 4;  // helper blocks (four waves each) per free CU
 constexpr int T2_HELP_U = 8;            // lookups in flight per lane of a helper block (registers are not scarce on a free CU)
-template <bool EXPECTED, int WAVES, int U, bool DEAL>
+constexpr unsigned T2_FILL_WAVES = 512;  // co-resident waves of a caching pass that fills (the others: t2_waves' automatic value)
+constexpr unsigned T2_FILL_PCT = 25;    // a caching pass fills while at most this share of the loci moved since the last
+//
+// CACHE (option t2_cache; the EM pass' table set only): an entry's two values are a pure function of its locus' (alpha, beta)
+// bits, and those move only at loci touched by a cell that changed sides or whose mask changed — every locus early in a run, a
+// few per cent late, none once the exclusion set stands still.  The instance keeps them in `val`, a double2 per slot of the
+// ELLPACK copy in the copy's layout (coalesced), and the pass' k_t2_tables says which loci are dirty (t2_dirty_t).  Per pass,
+// the same for every wave (the counters are final when the tables kernel ends):
+//   clean   no locus is dirty: the row's sums are a sequential stream over `val`, 16 bytes per slot; the entries are not read
+//           (slots of padding and of entries outside tier 2 hold the 0.0 the other forms add);
+//   fill    every slot's kept values are loaded beside the entries (the two do not depend on each other); entries of dirty loci
+//           then gather as ever and STORE what they found in their place; the wave that takes group g
+//           also copies the g-th share of the loci's (alpha, beta) to ab_t2 — every group is taken in a pass, so when the pass
+//           ends all entries of every locus are written under the bits ab_t2 then holds;
+//   bypass  the form without CACHE, bit for bit: nothing stored, ab_t2 untouched, so what was dirty stays dirty.
+// fill or bypass (cz.fill; -1: by rule): a pass in which nearly every locus moved would store 16 bytes per slot that the next
+// pass, as volatile, never reads.  The rule fills while at most cz.fill_max loci MOVED since the last caching pass — not "are
+// dirty": a store that was never filled is all dirty and would never get filled.  The sums add the same values in the same
+// order in all three: the output does not depend on the state of the store.
+struct t2_cache_t {
+    double2 *val;           // [slots of ell]
+    const uint32_t *bits;   // the pass' dirty mask (t2_dirty_t)
+    const uint32_t *cnt;    // [2] dirty loci, loci that moved
+    int fill;               // 1 = fill, 0 = bypass, -1 = fill while cnt[1] <= fill_max
+    uint32_t fill_max, L;
+    uint32_t calm;          // blocks of the launch that take part in a pass that does not fill (the others end at once)
+    const double2 *ab;      // [L] the pass'
+    double2 *ab_t2;         // [L]
+};
+template <bool EXPECTED, int WAVES, int U, bool DEAL, bool CACHE = false>
 __global__ __launch_bounds__(64 * WAVES) void k_t2_cell(uint64_t n_rows, const uint64_t *__restrict__ ell_ptr,
                                                         const uint64_t *__restrict__ ell, const double *__restrict__ tab2,
                                                         double *__restrict__ o_ll, double *__restrict__ o_ell,
-                                                        uint32_t *__restrict__ grp_ctr)
+                                                        uint32_t *__restrict__ grp_ctr, t2_cache_t cz)
 {
   const uint64_t n_grp = (n_rows + 63) >> 6;
   const uint32_t lane = threadIdx.x & 63u;
+  bool clean = false, fill = false;  // (wave-uniform, and the same in every wave of the pass)
+  uint32_t n_blk = gridDim.x;        // blocks that take part
+  if constexpr (CACHE) {
+      clean = cz.cnt[0] == 0u;
+      fill = !clean && (cz.fill >= 0 ? cz.fill != 0 : cz.cnt[1] <= cz.fill_max);
+      // How many waves suit a pass depends on what it does, which only the device knows: a filling pass waits on three loads
+      // in a row (entry, dirty bit, gather) and moves few bytes, so it takes the whole grid; a bypassing pass is the burst of
+      // gathers the small grid was sized for, and the clean stream disturbs the tile kernel least from few waves too.
+      if (!fill) n_blk = min(n_blk, cz.calm);
+      if (blockIdx.x >= n_blk) return;
+  }
   for (uint64_t turn = 0;; turn++) {  // (bounded: every turn takes a group; nothing waits for another wave)
     uint64_t grp;
     if constexpr (DEAL) {
@@ -887,13 +974,61 @@ __global__ __launch_bounds__(64 * WAVES) void k_t2_cell(uint64_t n_rows, const u
         if (lane == 0) take = atomicAdd(grp_ctr, 1u);
         grp = (uint32_t)__builtin_amdgcn_readfirstlane((int)take);
     } else {
-        grp = blockIdx.x + turn * gridDim.x;  // (one-wave blocks)
+        grp = blockIdx.x + turn * n_blk;  // (one-wave blocks)
     }
     if (grp >= n_grp) break;
+    if (CACHE && fill) {  // this group's share of the loci
+        const uint64_t per = (cz.L + n_grp - 1) / n_grp, l1 = min((grp + 1) * per, (uint64_t)cz.L);
+        for (uint64_t l = grp * per + lane; l < l1; l += 64) cz.ab_t2[l] = cz.ab[l];
+    }
     const uint64_t row = grp * 64 + lane;
     if (row < n_rows) {
     double s = 0.0, e = 0.0;
     const uint64_t base = ell_ptr[grp] + lane, end = ell_ptr[grp + 1];
+    if (CACHE && clean) {
+        for (uint64_t i = base; i < end; i += (uint64_t)U * 64) {
+            double2 v[U];
+#pragma unroll
+            for (int u = 0; u < U; u++)  // (wave-uniform bound)
+                v[u] = i + (uint64_t)u * 64 < end ? cz.val[i + (uint64_t)u * 64] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                s += v[u].x;
+                if (EXPECTED) e += v[u].y;
+            }
+        }
+    } else if (CACHE && fill) {
+        for (uint64_t i = base; i < end; i += (uint64_t)U * 64) {
+            uint64_t en[U];
+            uint32_t dw[U];
+            double2 v[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {  // the entries and, beside them, not behind them, what is kept for their slots
+                const bool in = i + (uint64_t)u * 64 < end;
+                en[u] = in ? ell[i + (uint64_t)u * 64] : OVF_PAD;
+                v[u] = in ? cz.val[i + (uint64_t)u * 64] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {  // the entry's locus' dirty bit (a 25 KB mask at 200k loci: cache hits)
+                const bool ok = en[u] != OVF_PAD && t2_total(ENT_ALT(en[u]) + ENT_REF(en[u]));
+                dw[u] = ok ? (cz.bits[ENT_IDX(en[u]) >> 5] >> (ENT_IDX(en[u]) & 31u)) & 1u : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++)
+                if (dw[u]) {
+                    const uint32_t r = ENT_REF(en[u]), n = ENT_ALT(en[u]) + r;
+                    const uint64_t at = (uint64_t)ENT_IDX(en[u]) * T2_ROW + t2_pos(n, r);
+                    v[u].x = tab2[at];
+                    v[u].y = EXPECTED ? tab2[at & ~7ull] : 0.0;
+                }
+#pragma unroll
+            for (int u = 0; u < U; u++) {  // (the stores behind all the loads: U lookups stay in flight)
+                if (dw[u]) cz.val[i + (uint64_t)u * 64] = v[u];
+                s += v[u].x;
+                if (EXPECTED) e += v[u].y;
+            }
+        }
+    } else
     for (uint64_t i = base; i < end; i += (uint64_t)U * 64) {
         uint64_t en[U];
         double lp[U], ev[U];
@@ -1752,7 +1887,8 @@ static cellector_status t2_tiles_add(cellector_ctx *c, int set, bool expected)
 // Overflow side of one pass: tables -> per-entry values (locus-major) -> per-cell sums.  Launched on the side stream so
 // that these small, latency-bound kernels run next to the tile kernel instead of in front of it.
 // cell side of the overflow entries of one pass, on stream `st`
-static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2 *ab, int set, bool expected, bool em_pass = false)
+static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2 *ab, int set, bool expected, bool em_pass = false,
+                                 bool cache = false /*the EM pass of a ctx with the store of option t2_cache*/)
 {
     double *o_ll = c->ovf_sum + (uint64_t)set * 2 * c->nloc, *o_ell = o_ll + c->nloc;
     const unsigned g = gcap(c->nloc, 256, 0x7fffffffu), eg = gcap(c->L * 16, 256, 0x7fffffffu);
@@ -1784,29 +1920,50 @@ static void launch_overflow_cell(cellector_ctx *c, hipStream_t st, const double2
             // waves of the co-resident grid: all groups at once when it has the machine to itself; beside the tile kernel option
             // t2_waves, 0 = 512, or 256 where a helper grid takes part of the groups
             const unsigned side_waves = c->t2_waves > 0 ? (unsigned)c->t2_waves : hg ? 256u : 512u;
-            const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)side_waves : 0x7fffffffull);
+            // (a caching pass launches the waves a filling pass wants; in the other passes the device sends the surplus home)
+            const unsigned launch_waves = cache && c->t2_waves <= 0 ? std::max(side_waves, T2_FILL_WAVES) : side_waves;
+            const unsigned cg = (unsigned)std::min<uint64_t>(n_grp ? n_grp : 1, st == c->side ? (uint64_t)launch_waves : 0x7fffffffull);
             uint32_t *ctr = c->t2_ctr + set;  // a counter per table set (the EM pass uses set 0, the posterior passes 0..2)
+            // A caching pass (option t2_cache, see k_t2_cell): the tables kernel also forms the dirty mask and the two counts, into
+            // the pair of counters of the pass' parity; the lookup grids read them.  Kept values of a pass without the expected
+            // column have none: the next pass with it starts from an empty store (ab_t2 back to all-ones).
+            t2_dirty_t dz = {};
+            t2_cache_t cz = {};
+            unsigned gd = 0;
+            if (cache) {
+                uint32_t *cnt = c->t2_ctr + 4 + 2 * (c->t2_pass & 1u), *other = c->t2_ctr + 4 + 2 * (~c->t2_pass & 1u);
+                c->t2_pass++;
+                if (EXP && !c->t2_val_exp) (void)hipMemsetAsync(c->ab_t2, 0xff, c->L * sizeof(double2), st);
+                c->t2_val_exp = EXP;
+                gd = gcap(c->L, 1024, 0x7fffffffu);  // (a wave per 256 loci)
+                dz = t2_dirty_t{c->t2_dirty, gp + gs, (uint32_t)c->L, c->ab_t2, c->ab_last, cnt, other};
+                cz = t2_cache_t{c->t2_val, c->t2_dirty, cnt, c->t2_fill, (uint32_t)(c->L * T2_FILL_PCT / 100), (uint32_t)c->L,
+                                st == c->side ? side_waves : 0x7fffffffu, ab, c->ab_t2};
+            }
             if (hg)  // the helper starts behind the tables: an event that rides on their dispatch (no barrier packet)
-                hipExtLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, nullptr, c->ev_t2tab, 0, (uint32_t)c->t2_np,
+                hipExtLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs + gd), dim3(256), 0, st, nullptr, c->ev_t2tab, 0, (uint32_t)c->t2_np,
                                       (const uint32_t *)c->t2_plist, (uint32_t)c->t2_ns, (const uint32_t *)c->t2_slist, (uint32_t)gp, ab,
-                                      (const double *)c->lf, (double *)c->tab2, ctr);
+                                      (const double *)c->lf, (double *)c->tab2, ctr, dz);
             else
-                hipLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp, ab,
-                                   c->lf, c->tab2, ctr);
+                hipLaunchKernelGGL(k_t2_tables<EXP>, dim3(gp + gs + gd), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns, c->t2_slist, gp,
+                                   ab, c->lf, c->tab2, ctr, dz);
             // (without a helper the grid strides over the groups as it always did: 15 000 one-wave blocks alone on the machine
             //  cost 0.18 ms of an overlap-0 iteration in atomics on the one counter)
-            if (hg)
-                hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, true>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2,
-                                   o_ll, o_ell, ctr);
-            else
-                hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, false>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr, c->ovf_ell, c->tab2,
-                                   o_ll, o_ell, ctr);
-            if (hg) {
-                (void)hipStreamWaitEvent(c->side2, c->ev_t2tab, 0);
-                hipLaunchKernelGGL((k_t2_cell<EXP, 4, T2_HELP_U, true>), dim3(hg), dim3(256), T2_HELP_LDS, c->side2, c->nloc, c->ovf_ell_ptr,
-                                   c->ovf_ell, c->tab2, o_ll, o_ell, ctr);
-                (void)hipEventRecord(c->ev_help, c->side2);
-            }
+            with_bool(cache, [&](auto CA) {
+                if (hg)
+                    hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, true, CA.value>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr,
+                                       c->ovf_ell, c->tab2, o_ll, o_ell, ctr, cz);
+                else
+                    hipLaunchKernelGGL((k_t2_cell<EXP, 1, 4, false, CA.value>), dim3(cg), dim3(64), lds_req, st, c->nloc, c->ovf_ell_ptr,
+                                       c->ovf_ell, c->tab2, o_ll, o_ell, ctr, cz);
+                if (hg) {
+                    cz.calm = hg;  // (the helper grid is the same in every pass)
+                    (void)hipStreamWaitEvent(c->side2, c->ev_t2tab, 0);
+                    hipLaunchKernelGGL((k_t2_cell<EXP, 4, T2_HELP_U, true, CA.value>), dim3(hg), dim3(256), T2_HELP_LDS, c->side2, c->nloc,
+                                       c->ovf_ell_ptr, c->ovf_ell, c->tab2, o_ll, o_ell, ctr, cz);
+                    (void)hipEventRecord(c->ev_help, c->side2);
+                }
+            });
             if (EXP && n0) tables_e();  // E(9..17) of the tier-0 entries
             // the kernels below add to the sums the lookups store, and the next pass' tables overwrite what they read
             if (hg) (void)hipStreamWaitEvent(st, c->ev_help, 0);
@@ -1852,7 +2009,7 @@ static void launch_overflow_locus_values(cellector_ctx *c, hipStream_t st, const
     }
     if (c->t2)  // deep: the pairs' log-pmfs for the locus finalize's counts (the cell side does not use the table)
         hipLaunchKernelGGL(k_t2_tables<false>, dim3(gcap(c->t2_np, 256, 0x7fffffffu)), dim3(256), 0, st, c->t2_np, c->t2_plist, c->t2_ns,
-                           c->t2_slist, gcap(c->t2_np, 256, 0x7fffffffu), ab, c->lf, c->tab2, (uint32_t *)nullptr);
+                           c->t2_slist, gcap(c->t2_np, 256, 0x7fffffffu), ab, c->lf, c->tab2, (uint32_t *)nullptr, t2_dirty_t{});
     hipLaunchKernelGGL(k_ovf_tables, dim3(gcap(c->L * 3, 256, 0x7fffffffu)), dim3(256), 0, st, c->L, ab, c->ovf_nmask, c->ovf_tab);
     if (!c->ovf_deep)  // shallow coverage: the values are stored here, beside the tile kernel, and the finalize reads them
         hipLaunchKernelGGL(k_ovf_values, dim3(gcap(c->ovf_n, 256, 0x7fffffffu)), dim3(256), 0, st, c->ovf_n, c->ovc_locus, c->ovc_ent, ab,
@@ -1946,13 +2103,16 @@ static cellector_status cell_pass_launch(cellector_ctx *c, const double2 *ab, bo
     // (deep coverage, ovf_deep: the same arrangement with the unthrottled 16-lanes-per-row kernel — it fills the tile kernel's
     //  idle issue slots while that runs and has the machine to itself afterwards: 7.8 ms per iteration at 1M x 200k deep
     //  against 8.3 with the two one after the other)
+    // the EM pass' tier-2 lookups keep their values (option t2_cache); a ctx built with the option off gets its store here
+    const bool cache = for_em && ovf && c->t2 && !c->ovf_deep && t2_cache_on(c);
+    if (cache && !c->t2_val) CHK(t2_cache_alloc(c));
     if (ovf && c->overlap) {
         // the tile kernel is launched FIRST: with the tables built ahead the queue is empty when the host gets here, and
         // every launch ahead of it (five on the side stream) would be ~10 us of idle GPU
         CHK(side_fork(c));
         CHK(run_tile_pass(c, 0, c->compute_expected));
         CHK(t2_tiles_pass(c, ab, 0, c->compute_expected));
-        launch_overflow_cell(c, c->side, ab, 0, c->compute_expected, for_em);
+        launch_overflow_cell(c, c->side, ab, 0, c->compute_expected, for_em, cache);
         HIPCHK(c, hipEventRecord(c->ev_join, c->side));
         if (for_em && c->overlap == 1) {  // the locus side's values right behind the cell side, beside the tile kernel
             launch_overflow_locus_values(c, c->side, ab);  // (they may end after it: only the locus finalize waits for them)
@@ -1969,7 +2129,7 @@ static cellector_status cell_pass_launch(cellector_ctx *c, const double2 *ab, bo
         c->cell_join_pending = true;
     } else {
         if (ovf) {
-            launch_overflow_cell(c, c->stream, ab, 0, c->compute_expected);
+            launch_overflow_cell(c, c->stream, ab, 0, c->compute_expected, for_em, cache);
             if (for_em) launch_overflow_locus_values(c, c->stream, ab);
         }
         CHK(run_tile_pass(c, 0, c->compute_expected));

@@ -660,6 +660,26 @@ static void launch_tile_build(cellector_ctx *c, uint64_t nt, uint32_t nj, const 
                            tile_ptr, tiles, thdr, (const uint32_t *)nullptr);
 }
 
+// ---- the kept values of the EM pass' tier-2 lookups (option t2_cache; kernels_tiled.hip, k_t2_cell<.., CACHE>) ----
+// One (log-pmf, expected term) per slot of ovf_ell, zero until a pass stores it (padding slots and entries outside tier 2 stay
+// zero: they add 0.0), and the (alpha, beta) bits every locus' values were written under: all-ones, which no live locus
+// (finite, positive) and no masked one (alpha = -1) has, so every locus starts dirty.  Only where k_t2_cell runs.
+cellector_status t2_cache_alloc(cellector_ctx *c)
+{
+    if (!c->t2 || c->ovf_deep || !c->L || !c->nloc) return CELLECTOR_OK;
+    const uint64_t L = c->L, words = (L + 63) / 64 * 2;
+    CHK(dev_alloc(c, &c->t2_val, c->ovf_ell_slots));
+    CHK(dev_alloc(c, &c->ab_t2, L));
+    CHK(dev_alloc(c, &c->ab_last, L));
+    CHK(dev_alloc(c, &c->t2_dirty, words));
+    HIPCHK(c, hipMemsetAsync(c->t2_val, 0, c->ovf_ell_slots * sizeof(double2), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ab_t2, 0xff, L * sizeof(double2), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ab_last, 0xff, L * sizeof(double2), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->t2_dirty, 0xff, words * sizeof(uint32_t), c->stream));
+    c->t2_val_exp = true;  // (nothing kept yet)
+    return CELLECTOR_OK;
+}
+
 // ---- tier-2 tiles (deep coverage): a second tile set over the overflow CSR's entries with totals 5..G::NHI ----
 // Built with the per-tile builder (the overflow rows are short); the rows keep
 // their file order.  A tile holds all 1024 rows of its block, most of them with one padding entry: 4 bytes per row (K = 1).
@@ -865,6 +885,11 @@ cellector_status tiled_build(cellector_ctx *c)
                 hipLaunchKernelGGL(k_ovf_ell_build<FILL.value>, dim3(gcap(n_grp * 64, 256, 0x7fffffffu)), dim3(256), 0, c->stream, nloc,
                                    c->ovf_ptr, c->ovf_ent, c->ovf_ell_ptr, c->ovf_ell);
         }, [&] { return dev_alloc(c, &c->ovf_ell, slots); }));
+        c->ovf_ell_slots = slots;
+        // (a rebuild dropped the kept lookup values with the copy they follow; a ctx that has them switched off gets them with
+        //  its first caching pass, should the option change)
+        c->t2_val.reset(); c->ab_t2.reset(); c->ab_last.reset(); c->t2_dirty.reset();
+        if (t2_cache_on(c)) CHK(t2_cache_alloc(c));
     }
     // the tier lists of the entries the fast cell-side kernel leaves out
     c->ovf_n_tier[0] = c->ovf_n_tier[1] = 0;

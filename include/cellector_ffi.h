@@ -120,6 +120,11 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * the entries with totals 5..8 through per-(locus, pair) tables, default on unless the matrix has deep coverage),
  * "t2_helper" (engine 2: blocks of the tier-2 lookup kernel's helper grid per compute unit the tile grid leaves free;
  * -1 = automatic, 0 = none, n = forced; placement only, the results do not depend on it),
+ * "t2_cache" (engine 2, default -1: the EM pass keeps every tier-2 entry's looked-up values and gathers again only at loci whose
+ * (alpha, beta) bits differ from those the kept values were written under — nothing once the exclusion set stands still;
+ * 1 = on, 0 = off, -1 = automatic; 16 bytes per overflow slot of device memory; same bits either way),
+ * "t2_fill" (with t2_cache: what a pass does at the loci that moved, 1 = gather and keep, 0 = gather without keeping,
+ * default -1 = the device decides per pass from how many loci moved since the pass before; same bits either way — A/B, tests),
  * "bank_order" (engine 2, default 1: the tile builder orders every row's entries and the rows of a slice against LDS bank
  * conflicts; 0 keeps file order, the layout whose per-cell sums do not depend on which cells share a shard),
  * "t2_tiles" (engine 2, deep coverage: the cell side of the totals 5..8 (8, the default of a matrix with more than 3 % of
