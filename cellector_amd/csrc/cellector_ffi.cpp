@@ -514,6 +514,10 @@ cellector_status cellector_set_option(cellector_ctx *c, const char *key, int64_t
     else if (!strcmp(key, "sharded_select")) c->sharded_select = v < 0 ? -1 : (v != 0);
     else if (!strcmp(key, "parse_window")) c->parse_window_opt = v < 0 ? 0 : v;
     else if (!strcmp(key, "write_window")) c->write_window_opt = v < 0 ? 0 : v;
+    else if (!strcmp(key, "gz_device")) {
+        if (v != 0 && v != 1) return ctx_fail(c, CELLECTOR_EINVAL, "gz_device must be 0 (a .gz is inflated on the host) or 1 (a BGZF .gz on the device)");
+        c->gz_device = v != 0;
+    }
     else if (!strcmp(key, "tile_groups")) {
         if (v < 0 || v > 64) return ctx_fail(c, CELLECTOR_EINVAL, "tile_groups must be 0 (automatic) or 1..64");
         c->tile_groups_opt = (int)v;
@@ -668,7 +672,7 @@ cellector_status cellector_ingest_mtx(cellector_ctx *c, const char *alt_path, co
     LapTimer t;
     MtxInput *in = nullptr;
     uint64_t tl = 0, tc = 0;
-    CHK(ctx_mtx_open(c, alt_path, ref_path, &in, &tl, &tc));
+    CHK(ctx_mtx_open(c, alt_path, ref_path, &in, &tl, &tc, true));
     if (timing) fprintf(stderr, "[timing]   open / inflate          %8.3f s\n", t.lap());
     cellector_status s = begin_ingest(c, tl, tc);
     if (s == CELLECTOR_OK) s = ingest_stage_mtx_device(c, in);  // tokenised and converted on the GPU
@@ -723,7 +727,7 @@ cellector_status cellector_ingest_mtx_joined(cellector_ctx *c, const char *first
     CHK(join_mode_check(c, mode));
     MtxInput *in = nullptr;
     uint64_t tl = 0, tc = 0, first_hint = 0;
-    CHK(ctx_mtx_open(c, first_path, second_path, &in, &tl, &tc));
+    CHK(ctx_mtx_open(c, first_path, second_path, &in, &tl, &tc, true));
     struct Closer { MtxInput *in; ~Closer() { mtx_input_close(in); } } closer{in};
     CHK(join_size_lines(c, in, &first_hint));
     if (const char *why = join_scope(c, tc)) return ctx_fail(c, CELLECTOR_EINVAL, "ingest_mtx_joined: ctx %s", why);

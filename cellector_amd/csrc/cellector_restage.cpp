@@ -372,4 +372,18 @@ cellector_status cellector_bgzf_compress(cellector_ctx *c, const uint8_t *in, ui
     return st;
 }
 
+cellector_status cellector_bgzf_decompress(cellector_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *n_out,
+                                           uint64_t *n_blocks)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    if (c->multi) return ctx_fail(c, CELLECTOR_EINVAL, "bgzf_decompress works on a single-device ctx: a multi-device root ctx has no device of its own");
+    if (n && !in) return ctx_fail(c, CELLECTOR_EINVAL, "bgzf_decompress: in is NULL for %llu bytes", (unsigned long long)n);
+    SETDEV(c);
+    uint64_t bytes = 0, blocks = 0;
+    const cellector_status st = bgzf_decompress_host(c, in, n, out, capacity, &bytes, &blocks);
+    if (n_out) *n_out = bytes;  // (also when the capacity was too small)
+    if (n_blocks) *n_blocks = blocks;
+    return st;
+}
+
 }  // extern "C"

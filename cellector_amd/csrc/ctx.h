@@ -128,6 +128,7 @@ struct CtxOptions {
     int overlap = 1;  // option "overlap": 1 = the overflow kernels run on the side stream next to the tile kernel, 0 = in front
     bool compute_expected = true;
     bool ref_arith = false;  // option ref_arith (engine 1): evaluate stats.rs:41-53 with ln_gamma differences, the reference's own rounding
+    bool gz_device = false;        // option gz_device: a BGZF .gz input stays compressed on the host and is inflated on the device
     int64_t parse_window_opt = 0;  // option parse_window: 0 = whole file below 1 GB, 256 MB windows above; else the window in bytes
     int64_t write_window_opt = 0;  // option write_window: entries per window of cellector_write_mtx / _format_mtx; 0 = 2^23
     bool fuse_filter = true;   // option "fuse_filter": an unsharded ctx applies the -80 locus filter inside k_locus_finalize (A/B)
@@ -738,6 +739,39 @@ cellector_status bz_compress(cellector_ctx *c, BzScratch *s, const uint8_t *text
                              uint64_t *blocks, uint64_t *stored);
 cellector_status bgzf_compress_host(cellector_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *n_out,
                                     uint64_t *n_blocks);
+// BGZF inflation on the device (kernels_inflate.hip; the format: inflate_format.h).  inf_launch queues one launch over a run of
+// members; cellector_bgzf_decompress feeds it host bytes, the mtx ingest (option gz_device) the windows of a file.
+struct InfMember {       // one member for k_bgzf_inflate: its deflate body in the launch's input, its text in the launch's output
+    uint64_t in_off;
+    uint64_t out_off;
+    uint32_t in_len, isize, crc, pad;
+};
+struct BgzfBlock;
+struct InfScratch {
+    DevBuf<uint8_t> tables;            // InfCrcTables
+    DevBuf<InfMember> members;         // [cap_members]
+    DevBuf<unsigned long long> status;       // [1] the status word
+    unsigned long long *h_status = nullptr;  // pinned: where the status word arrives behind every launch
+    uint64_t cap_members = 0;
+    uint64_t n_members = 0, bytes_in = 0, bytes_out = 0;  // summed over the launches
+    // CELLECTOR_TIMING=1: the kernel's GPU time between events, summed by inf_launch_timed
+    bool timed = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms_kernel = 0;
+    InfScratch() = default;
+    InfScratch(const InfScratch &) = delete;
+    InfScratch &operator=(const InfScratch &) = delete;
+    ~InfScratch();
+};
+uint64_t inf_chunk_members();  // members per launch (CELLECTOR_INFLATE_CHUNK: fewer, for tests)
+cellector_status inf_scratch(cellector_ctx *c, InfScratch *s, uint64_t cap_members);
+cellector_status inf_launch(cellector_ctx *c, InfScratch *s, hipStream_t st, const std::vector<BgzfBlock> &blocks, uint64_t k0, uint64_t k1,
+                            InfMember *host, const uint8_t *file, const uint8_t *dev_in, uint64_t in_first, uint64_t n_in, uint8_t *dev_out,
+                            uint64_t out_first, uint64_t out_cap, bool reset);
+void inf_launch_timed(InfScratch *s);
+cellector_status inf_refused(const cellector_ctx *c, const char *what, unsigned long long status);
+cellector_status bgzf_decompress_host(cellector_ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *n_out,
+                                      uint64_t *n_blocks);
 cellector_status synth_generate(cellector_ctx *c, double density, uint64_t seed, double minority_fraction,
                                 double doublet_fraction);
 cellector_status synth_write_mtx(cellector_ctx *c, const char *alt_path, const char *ref_path);
@@ -765,7 +799,7 @@ cellector_status tiled_posteriors(cellector_ctx *c, double mf0, double lp_min, d
 // device-side mtx text parse (kernels_parse.hip); the pair's bytes and header: mtx_bytes.h
 struct MtxInput;
 cellector_status ctx_mtx_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out,
-                              uint64_t *total_loci, uint64_t *total_cells);  // mtx_input_open, its failure into c->err
+                              uint64_t *total_loci, uint64_t *total_cells, bool single_device = false /*option gz_device applies*/);  // mtx_input_open, its failure into c->err
 void mtx_input_close(MtxInput *in);
 // split ingest of a multi-device ctx (kernels_parse.hip): every shard tokenises a range of windows of both files
 struct MtxSplit;

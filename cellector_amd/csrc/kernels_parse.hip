@@ -225,6 +225,8 @@ namespace {
 
 struct DevText {
     DevBuf<uint8_t> text;
+    uint64_t lead = 0;  // the data section starts this far into `text` (a multiple of 16; not 0 only for a file inflated on the device)
+    uint8_t *at() const { return text.get() + lead; }
     uint64_t n = 0, n_lines = 0;
     DevBuf<uint64_t> seg_off;  // newlines before each NL_SEG-byte segment (exclusive scan of k_nl_count)
     uint64_t n_seg = 0;
@@ -238,6 +240,58 @@ inline unsigned pgrid(uint64_t n) { return (unsigned)((n + PB - 1) / PB ? (n + P
 #define UP_PIECE (256ull << 20)
 #define UP_THREADS 8
 #define UP_MIN (4ull << 30)
+// one timing line of a file inflated on the device (CELLECTOR_TIMING=1)
+void inf_report(const InfScratch &s, const FileBytes &fb)
+{
+    if (s.timed)
+        fprintf(stderr, "[timing]     inflate on the device: %s: %llu members, %llu -> %llu bytes, inflate kernel %.3f ms\n", fb.path.c_str(),
+                (unsigned long long)s.n_members, (unsigned long long)s.bytes_in, (unsigned long long)s.bytes_out, s.ms_kernel);
+}
+
+// ... of a BGZF file left compressed (option gz_device): the compressed bytes from the first member that holds data-section text to
+// the end go up in pieces of inf_chunk_members() members, and k_bgzf_inflate writes their text straight into dt->text, at the offset
+// that puts the data section's first byte at dt->at()[0] (the header's tail in that first member lands in the `lead` bytes before).
+// *refused: a member the device does not accept (the caller hands the file to the host reader).
+cellector_status upload_text_gz(cellector_ctx *c, const FileBytes &fb, size_t data_off, DevText *dt, bool *refused)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    dt->n = fb.size - data_off;
+    const uint64_t nb = fb.blocks.size(), k_first = dt->n ? fb.member_at(data_off) : nb;
+    const uint64_t before = dt->n ? data_off - fb.blocks[k_first].out : 0;  // text of that member in front of the data section
+    dt->lead = (before + 15) & ~15ull;
+    CHK(dev_alloc(c, &dt->text, dt->lead + dt->n + 16));
+    HIPCHK(c, hipMemsetAsync(dt->at() + dt->n, '\n', 16, c->stream));
+    if (!dt->n) return CELLECTOR_OK;
+    const uint64_t chunk = inf_chunk_members(), out_first = fb.blocks[k_first].out;
+    uint64_t max_in = 0;
+    for (uint64_t k0 = k_first; k0 < nb; k0 += chunk) {
+        const uint64_t k1 = std::min(nb, k0 + chunk);
+        max_in = std::max<uint64_t>(max_in, fb.blocks[k1 - 1].off + fb.blocks[k1 - 1].clen - fb.blocks[k0].off);
+    }
+    InfScratch s;
+    DevBuf<uint8_t> d_in;
+    CHK(inf_scratch(c, &s, std::min(chunk, nb - k_first)));
+    CHK(dev_alloc(c, &d_in, max_in));
+    std::vector<InfMember> table(s.cap_members);
+    for (uint64_t k0 = k_first; k0 < nb; k0 += chunk) {
+        const uint64_t k1 = std::min(nb, k0 + chunk);
+        const uint64_t in_first = fb.blocks[k0].off, n_in = fb.blocks[k1 - 1].off + fb.blocks[k1 - 1].clen - in_first;
+        HIPCHK(c, hipMemcpyAsync(d_in, fb.gz + in_first, n_in, hipMemcpyHostToDevice, c->stream));
+        // (every member's place is relative to the first member's text; the kernel checks it against the bytes behind that)
+        CHK(inf_launch(c, &s, c->stream, fb.blocks, k0, k1, table.data(), fb.gz, d_in, in_first, n_in, dt->at() - before, out_first,
+                       fb.size - out_first, false));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        inf_launch_timed(&s);
+        if (*s.h_status != ~0ull) {
+            *refused = true;
+            return inf_refused(c, fb.path.c_str(), *s.h_status);
+        }
+    }
+    s.bytes_out = fb.size - out_first;
+    inf_report(s, fb);
+    return CELLECTOR_OK;
+}
+
 cellector_status upload_text(cellector_ctx *c, const FileBytes &fb, size_t data_off, DevText *dt)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -291,14 +345,26 @@ cellector_status upload_text(cellector_ctx *c, const FileBytes &fb, size_t data_
     return CELLECTOR_OK;
 }
 
-cellector_status split_lines(cellector_ctx *c, const FileBytes &fb, DevText *dt)
+// the file's last byte; of a file left compressed through the host decoder, whose refusal of that member counts like the device's
+cellector_status read_last_byte(cellector_ctx *c, const FileBytes &fb, uint8_t *byte, bool *refused)
 {
-    const bool unterminated = dt->n > 0 && fb.data[fb.size - 1] != '\n';
+    if (fb.read(fb.size - 1, 1, byte)) return CELLECTOR_OK;
+    if (!fb.gz) return ctx_fail(c, CELLECTOR_EIO, "cannot read the input file");
+    *refused = true;
+    return ctx_fail(c, CELLECTOR_EIO, "%s: member %llu is refused: the host decoder does not accept it", fb.path.c_str(),
+                    (unsigned long long)fb.member_at(fb.size - 1));
+}
+
+cellector_status split_lines(cellector_ctx *c, const FileBytes &fb, DevText *dt, bool *refused)
+{
+    uint8_t last_byte = '\n';
+    if (dt->n > 0) CHK(read_last_byte(c, fb, &last_byte, refused));
+    const bool unterminated = last_byte != '\n';
     const uint64_t n_scan = dt->n + (unterminated ? 1 : 0);  // include one padding '\n' as the terminator
     const uint64_t nthreads = (n_scan + NL_SEG - 1) / NL_SEG;
     CHK(dev_alloc(c, &dt->seg_off, nthreads + 1));
     HIPCHK(c, hipMemsetAsync(dt->seg_off, 0, (nthreads + 1) * 8, c->stream));
-    if (nthreads) hipLaunchKernelGGL(k_nl_count, dim3(pgrid(nthreads)), dim3(PB), 0, c->stream, dt->text, n_scan, dt->seg_off);
+    if (nthreads) hipLaunchKernelGGL(k_nl_count, dim3(pgrid(nthreads)), dim3(PB), 0, c->stream, dt->at(), n_scan, dt->seg_off);
     HIPCHK(c, hipGetLastError());
     uint64_t n_nl = 0;
     CHK(dev_exclusive_scan_u64(c, dt->seg_off, nthreads + 1, &n_nl));
@@ -397,6 +463,46 @@ struct PwBuffers {
     }
 };
 
+// what the windowed parser needs beside PwBuffers for a file left compressed (option gz_device): per ring slot a pinned buffer
+// for a window's compressed bytes and one for its member table; one device buffer for the compressed bytes and one for the
+// inflated members (the upload stream orders their reuse).  Sized from the member index: the largest window of this call.
+struct GzWindows {
+    InfScratch s;
+    uint8_t *pin_in[PW_NB] = {};
+    InfMember *pin_members[PW_NB] = {};
+    DevBuf<uint8_t> d_in, d_text;
+    uint64_t cap_in = 0, cap_text = 0;
+    uint64_t have_a = 1, have_b = 0;  // the members d_text holds (none yet): a window they cover needs no launch
+    cellector_status make(cellector_ctx *c, const FileBytes &fb, size_t data_off, uint64_t window, uint64_t nb, uint64_t w_begin, uint64_t w_end,
+                          int n_ring, hipStream_t up)
+    {
+        uint64_t cap_members = 0;
+        for (uint64_t w = w_begin; w < w_end; w++) {
+            const uint64_t o = w * window, len = std::min<uint64_t>(window + PW_LOOK, nb - o);
+            const uint64_t ka = fb.member_at(data_off + o), kb = fb.member_at(data_off + o + len - 1);
+            cap_in = std::max<uint64_t>(cap_in, fb.blocks[kb].off + fb.blocks[kb].clen - fb.blocks[ka].off);
+            cap_text = std::max<uint64_t>(cap_text, fb.blocks[kb].out + fb.blocks[kb].isize - fb.blocks[ka].out);
+            cap_members = std::max(cap_members, kb + 1 - ka);
+        }
+        CHK(inf_scratch(c, &s, cap_members));
+        CHK(dev_alloc(c, &d_in, cap_in));
+        CHK(dev_alloc(c, &d_text, cap_text));
+        for (int b = 0; b < n_ring; b++) {
+            HIPCHK(c, hipHostMalloc((void **)&pin_in[b], cap_in ? cap_in : 1));
+            HIPCHK(c, hipHostMalloc((void **)&pin_members[b], cap_members * sizeof(InfMember)));
+        }
+        HIPCHK(c, hipMemsetAsync(s.status, 0xff, sizeof(unsigned long long), up));  // (one status word for the file's launches)
+        return CELLECTOR_OK;
+    }
+    ~GzWindows()
+    {
+        for (int b = 0; b < PW_NB; b++) {
+            if (pin_in[b]) (void)hipHostFree(pin_in[b]);
+            if (pin_members[b]) (void)hipHostFree(pin_members[b]);
+        }
+    }
+};
+
 template <typename T>
 cellector_status grow_tokens(cellector_ctx *c, DevBuf<T> *arr, uint64_t used, uint64_t new_cap)
 {
@@ -415,7 +521,7 @@ cellector_status grow_tokens(cellector_ctx *c, DevBuf<T> *arr, uint64_t used, ui
 template <bool ALT>
 cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t data_off, PwBuffers &B, uint64_t cap_hint,
                                 DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1, DevBuf<uint32_t> *o2, uint64_t *n_lines,
-                                unsigned long long *bad, uint64_t w_begin = 0, uint64_t w_end = ~0ull)
+                                unsigned long long *bad, bool *refused, uint64_t w_begin = 0, uint64_t w_end = ~0ull)
 {
     // [w_begin, w_end): the windows this call takes (a multi-device ingest gives every GPU a range of them).  Line indices
     // are then LOCAL: the number of newlines before the line inside the range; the line that starts right behind the range's
@@ -434,11 +540,13 @@ cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t da
     CHK(dev_alloc(c, o2, cap));
     if (nb == 0) return CELLECTOR_OK;
     uint8_t last_byte = '\n';
-    if (!fb.read(data_off + nb - 1, 1, &last_byte)) return ctx_fail(c, CELLECTOR_EIO, "cannot read the input file");
+    CHK(read_last_byte(c, fb, &last_byte, refused));
     const bool unterminated = last_byte != '\n';
     const uint64_t n_win = (nb + window - 1) / window;
     if (w_end > n_win) w_end = n_win;
     if (w_begin >= w_end) return CELLECTOR_OK;
+    GzWindows G;  // (a file left compressed: the producer inflates every window on the device)
+    if (fb.gz) CHK(G.make(c, fb, data_off, window, nb, w_begin, w_end, (int)n_ring, up));
     hipError_t e = hipSuccess;
     std::mutex mu;
     std::condition_variable cv;
@@ -462,6 +570,50 @@ cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t da
                 }
                 const uint64_t o = w * window;
                 const size_t len = (size_t)std::min<uint64_t>(window + PW_LOOK, nb - o);
+                if (fb.gz) {
+                    // the members that cover the window's text: their compressed bytes through the slot's pinned buffer to the
+                    // device, inflated there into a scratch whose origin is the first member's text, the window's slice of that
+                    // into dev[b], the padding newlines behind it; ev_up[b] last.  (Consecutive windows inflate the look-ahead's
+                    // members twice: at most PW_LOOK of text a window, not worth a carry.)
+                    const uint64_t t0 = data_off + o, ka = fb.member_at(t0), kb = fb.member_at(t0 + len - 1);
+                    const uint64_t in_first = fb.blocks[ka].off, n_in = fb.blocks[kb].off + fb.blocks[kb].clen - in_first;
+                    const uint64_t out_first = fb.blocks[ka].out, n_text = fb.blocks[kb].out + fb.blocks[kb].isize - out_first;
+                    if (n_in > G.cap_in || n_text > G.cap_text || kb + 1 - ka > G.s.cap_members) { pe = hipErrorInvalidValue; break; }
+                    // (the scratch still holds the members of the last launch; a window they cover — every one after the first of
+                    //  a file shorter than the look-ahead — is only sliced out of it: the stream orders the copies)
+                    const bool launch = !(ka >= G.have_a && kb <= G.have_b);
+                    if (launch) {
+                        G.have_a = ka;
+                        G.have_b = kb;
+                        std::thread th[PW_THREADS];
+                        const size_t slice = ((size_t)n_in + PW_THREADS - 1) / PW_THREADS;
+                        for (int t = 0; t < PW_THREADS; t++)
+                            th[t] = std::thread([&, t] {
+                                const size_t b0 = std::min((size_t)n_in, (size_t)t * slice), b1 = std::min((size_t)n_in, b0 + slice);
+                                if (b1 > b0) memcpy(G.pin_in[b] + b0, fb.gz + in_first + b0, b1 - b0);
+                            });
+                        for (int t = 0; t < PW_THREADS; t++) th[t].join();
+                        pe = hipMemcpyAsync(G.d_in, G.pin_in[b], n_in, hipMemcpyHostToDevice, up);
+                        if (pe == hipSuccess && inf_launch(c, &G.s, up, fb.blocks, ka, kb + 1, G.pin_members[b], fb.gz, G.d_in, in_first, n_in,
+                                                           G.d_text, out_first, n_text, false) != CELLECTOR_OK)
+                            pe = hipErrorLaunchFailure;
+                    }
+                    if (pe == hipSuccess)
+                        pe = hipMemcpyAsync(dev[b], G.d_text + (t0 - fb.blocks[G.have_a].out), len, hipMemcpyDeviceToDevice, up);
+                    if (pe == hipSuccess) pe = hipMemsetAsync(dev[b] + len, '\n', 32, up);
+                    if (pe == hipSuccess) pe = hipEventRecord(ev_up[b], up);
+                    if (pe == hipSuccess && launch && G.s.timed) {  // (the kernel's time is read before its events are recorded again)
+                        pe = hipStreamSynchronize(up);
+                        inf_launch_timed(&G.s);
+                    }
+                    if (pe != hipSuccess) break;
+                    {
+                        std::lock_guard<std::mutex> lk(mu);
+                        produced = wi + 1;
+                    }
+                    cv.notify_all();
+                    continue;
+                }
                 std::thread th[PW_THREADS];
                 bool got[PW_THREADS];
                 const size_t slice = (len + PW_THREADS - 1) / PW_THREADS;
@@ -545,6 +697,14 @@ cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t da
         if (st == CELLECTOR_OK) *n_lines = line_base;
     }
     if (up) (void)hipStreamSynchronize(up);  // (the buffers go on to the pair's other file)
+    if (fb.gz) {  // the status word of the file's launches arrived behind the last one; a refusal goes before whatever else failed
+        if (*G.s.h_status != ~0ull) {
+            *refused = true;
+            *n_lines = 0;
+            return inf_refused(c, fb.path.c_str(), *G.s.h_status);
+        }
+        if (st == CELLECTOR_OK) inf_report(G.s, fb);
+    }
     return st;
 }
 
@@ -553,16 +713,16 @@ cellector_status parse_windowed(cellector_ctx *c, const FileBytes &fb, size_t da
 // a file small enough to sit on the device whole: one upload, one scan of its newlines, one tokeniser launch
 template <bool ALT>
 static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_t data_off, DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1,
-                                    DevBuf<uint32_t> *o2, uint64_t *n_lines, unsigned long long *bad)
+                                    DevBuf<uint32_t> *o2, uint64_t *n_lines, unsigned long long *bad, bool *refused)
 {
     DevText t;
-    cellector_status st = upload_text(c, fb, data_off, &t);
-    if (st == CELLECTOR_OK) st = split_lines(c, fb, &t);
+    cellector_status st = fb.gz ? upload_text_gz(c, fb, data_off, &t, refused) : upload_text(c, fb, data_off, &t);
+    if (st == CELLECTOR_OK) st = split_lines(c, fb, &t, refused);
     const uint64_t n = t.n_lines;
     if (st == CELLECTOR_OK && ALT) { st = dev_alloc(c, o0, n); if (st == CELLECTOR_OK) st = dev_alloc(c, o1, n); }
     if (st == CELLECTOR_OK) st = dev_alloc(c, o2, n);
     if (st == CELLECTOR_OK && n) {
-        hipLaunchKernelGGL(k_parse_lines<ALT>, dim3(pgrid(t.n_seg)), dim3(PB), 0, c->stream, t.text, t.n, t.n, n, 0ull, true, false,
+        hipLaunchKernelGGL(k_parse_lines<ALT>, dim3(pgrid(t.n_seg)), dim3(PB), 0, c->stream, t.at(), t.n, t.n, n, 0ull, true, false,
                            t.seg_off, ALT ? *o0 : (uint32_t *)nullptr, ALT ? *o1 : (uint32_t *)nullptr, *o2, bad);
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) st = ctx_fail(c, CELLECTOR_EDEVICE, "parse: %s", hipGetErrorString(e));
@@ -573,12 +733,26 @@ static cellector_status parse_whole(cellector_ctx *c, const FileBytes &fb, size_
 
 // one file's tokens, through B's windows (made by the caller; [w_begin, w_end): see parse_windowed) or whole
 template <bool ALT>
-static cellector_status parse_file(cellector_ctx *c, const FileBytes &fb, size_t data_off, bool windowed, PwBuffers &B, uint64_t cap_hint,
+static cellector_status parse_file(cellector_ctx *c, FileBytes &fb, size_t data_off, bool windowed, PwBuffers &B, uint64_t cap_hint,
                                    DevBuf<uint32_t> *o0, DevBuf<uint32_t> *o1, DevBuf<uint32_t> *o2, uint64_t *n_lines,
                                    unsigned long long *bad, uint64_t w_begin = 0, uint64_t w_end = ~0ull)
 {
-    return windowed ? parse_windowed<ALT>(c, fb, data_off, B, cap_hint, o0, o1, o2, n_lines, bad, w_begin, w_end)
-                    : parse_whole<ALT>(c, fb, data_off, o0, o1, o2, n_lines, bad);
+    for (int attempt = 0;; attempt++) {
+        bool refused = false;
+        const cellector_status st = windowed ? parse_windowed<ALT>(c, fb, data_off, B, cap_hint, o0, o1, o2, n_lines, bad, &refused, w_begin, w_end)
+                                             : parse_whole<ALT>(c, fb, data_off, o0, o1, o2, n_lines, bad, &refused);
+        if (!refused || attempt) return st;
+        // The device refused a member of a file left compressed (option gz_device).  The host reader decides what the file is, as
+        // it does for a damaged block without the option: the outcome is then the one of gz_device 0.  What the tokeniser made of
+        // the member's bytes meanwhile is forgotten.
+        // Neither case is silent: the failure keeps the device's words (file, member, why), and a file the host accepts where
+        // the device did not is reported on stderr — the decoder then disagrees with zlib's reader, and the load paid for both.
+        const std::string why = c->err;
+        if (!file_bytes_to_host(&fb)) return ctx_fail(c, CELLECTOR_EIO, "couldn't open file %s (%s)", fb.path.c_str(), why.c_str());
+        fprintf(stderr, "cellector: gz_device: %s; the host reader accepts the file: it is read on the host\n", why.c_str());
+        HIPCHK(c, hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
 }
 
 // ---- split ingest of a multi-device ctx -------------------------------------------------------------------------------------
@@ -616,10 +790,10 @@ MtxSplit *mtx_split_new(int n, LocalGroup *bar, bool balance)
 }
 void mtx_split_delete(MtxSplit *S) { delete S; }
 cellector_status ctx_mtx_open(const cellector_ctx *c, const char *alt_path, const char *ref_path, MtxInput **out, uint64_t *total_loci,
-                              uint64_t *total_cells)
+                              uint64_t *total_cells, bool single_device)
 {
     std::string msg;
-    const cellector_status st = mtx_input_open(alt_path, ref_path, out, &msg);
+    const cellector_status st = mtx_input_open(alt_path, ref_path, out, &msg, single_device && c->gz_device);
     if (st != CELLECTOR_OK) return ctx_fail(c, st, "%s", msg.c_str());
     *total_loci = (*out)->total_loci;
     *total_cells = (*out)->total_cells;
@@ -805,7 +979,7 @@ cellector_status ingest_stage_mtx_split(cellector_ctx *c, MtxInput *in, MtxSplit
 // The ref file's count tokens parsed on ANOTHER ctx's device and stream (multi-device ingest: the two files are independent
 // byte streams until they are zipped, so a second GPU takes the second file over its own PCIe link while the first one
 // tokenises the alt file; two files together also read faster from the page cache than one: 76 vs 43 GB/s measured).
-static cellector_status parse_ref_on(cellector_ctx *h, const FileBytes &fr, size_t off_r, uint64_t win, bool windowed, uint64_t nnz_hint,
+static cellector_status parse_ref_on(cellector_ctx *h, FileBytes &fr, size_t off_r, uint64_t win, bool windowed, uint64_t nnz_hint,
                                      DevBuf<uint32_t> *r_out, uint64_t *n_r, unsigned long long *bad_host)
 {
     HIPCHK(h, hipSetDevice(h->device));
@@ -828,7 +1002,7 @@ static uint64_t pair_window(const cellector_ctx *c, const MtxInput *in)
 }
 static bool file_windowed(const cellector_ctx *c, const FileBytes &f, size_t data_off)
 {
-    return c->parse_window_opt > 0 || !f.data || f.size - data_off >= PW_MIN;
+    return c->parse_window_opt > 0 || (!f.data && !f.gz) || f.size - data_off >= PW_MIN;  // (a compressed file is not an unmapped one)
 }
 
 cellector_status ingest_stage_mtx_device(cellector_ctx *c, MtxInput *in, cellector_ctx *helper)

@@ -1,6 +1,11 @@
 // See mtx_bytes.h.
 #include "mtx_bytes.h"
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // (the library builds this file as HIP: the format headers' host/device qualifiers)
+#endif
+#include "inflate_format.h"
+
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -76,10 +81,55 @@ bool bgzf_inflate(const uint8_t *f, const std::vector<BgzfBlock> &blocks, uint8_
     return ok;
 }
 
+// ---- the compressed kind ------------------------------------------------------------------------------------------------------------
+size_t FileBytes::member_at(size_t text_off) const
+{
+    size_t lo = 0, hi = blocks.size();  // the last member with out <= text_off: the empty ones before it share its `out` and come first
+    while (hi - lo > 1) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (blocks[mid].out <= text_off) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// text [off, off + len) through the serial decoder of inflate_format.h, member by member (CRC-32 and length checked like the device does)
+bool FileBytes::read_gz(size_t off, size_t len, uint8_t *dst) const
+{
+    if (off > size || len > size - off) return false;
+    if (!len) return true;
+    std::vector<uint8_t> text(INF_MAX_OUT);
+    for (size_t k = member_at(off); len; k++) {
+        if (k >= blocks.size()) return false;
+        const BgzfBlock &b = blocks[k];
+        const uint8_t *body = gz + b.off + 12 + b.xlen, *tr = gz + b.off + b.clen - 8;
+        const uint32_t crc = tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
+        int err = INF_OK;
+        inflate_member_host(body, (uint32_t)(b.clen - 12 - b.xlen - 8), text.data(), b.isize, &err);
+        if (err != INF_OK || (uint32_t)crc32(crc32(0L, Z_NULL, 0), text.data(), b.isize) != crc) return false;
+        const size_t from = off - b.out, take = std::min<size_t>(len, b.isize - from);  // (off >= b.out; an empty member gives nothing)
+        memcpy(dst, text.data() + from, take);
+        dst += take; off += take; len -= take;
+    }
+    return true;
+}
+static void file_bytes_drop_gz(FileBytes *fb)
+{
+    if (fb->map) munmap(fb->map, fb->map_len);
+    if (fb->fd >= 0) close(fb->fd);
+    fb->map = nullptr; fb->map_len = 0; fb->fd = -1;
+    fb->gz = nullptr; fb->gz_len = 0; fb->blocks.clear(); fb->owned.clear(); fb->head_len = 0; fb->size = 0;
+}
+bool file_bytes_to_host(FileBytes *fb)
+{
+    const std::string path = fb->path;
+    file_bytes_drop_gz(fb);
+    return load_bytes(path.c_str(), fb, false);
+}
+
 // reader (load_data.rs:240-251): ".gz" by extension (multi-member), plain otherwise
-bool load_bytes(const char *path, FileBytes *fb)
+bool load_bytes(const char *path, FileBytes *fb, bool gz_device)
 {
     const size_t n = strlen(path);
+    fb->path = path;
     if (n >= 3 && strcmp(path + n - 3, ".gz") == 0) {
         {   // block-compressed (bgzip)?  then in parallel
             const int fd = open(path, O_RDONLY);
@@ -91,6 +141,21 @@ bool load_bytes(const char *path, FileBytes *fb)
                     size_t total = 0;
                     bool done = false;
                     try {
+                        if (gz_device && bgzf_index((const uint8_t *)m, (size_t)st.st_size, &blocks, &total)) {
+                            // left compressed: the device inflates it (option gz_device); only the head's members here
+                            fb->map = m; fb->map_len = (size_t)st.st_size; fb->fd = fd;
+                            fb->gz = (const uint8_t *)m; fb->gz_len = (size_t)st.st_size;
+                            fb->blocks = std::move(blocks);
+                            fb->size = total;
+                            fb->head_len = std::min<size_t>(total, FB_HEAD);
+                            fb->owned.resize(fb->head_len ? fb->head_len : 1);
+                            if (fb->read_gz(0, fb->head_len, fb->owned.data())) return true;
+                            // (a damaged member among the first: the host reader below decides, as it does without the option)
+                            fb->map = nullptr; fb->map_len = 0; fb->fd = -1;
+                            fb->gz = nullptr; fb->gz_len = 0; fb->blocks.clear(); fb->owned.clear(); fb->head_len = 0; fb->size = 0;
+                            blocks.clear();
+                            total = 0;
+                        }
                         if (bgzf_index((const uint8_t *)m, (size_t)st.st_size, &blocks, &total)) {
                             fb->owned.resize(total ? total : 1);
                             done = bgzf_inflate((const uint8_t *)m, blocks, fb->owned.data());
@@ -185,7 +250,7 @@ bool host_tok_u64(const std::string &s, int idx, uint64_t *out)
     }
 }
 
-cellector_status mtx_input_open(const char *alt_path, const char *ref_path, MtxInput **out, std::string *msg)
+cellector_status mtx_input_open(const char *alt_path, const char *ref_path, MtxInput **out, std::string *msg, bool gz_device)
 {
     MtxInput *in = new (std::nothrow) MtxInput();
     if (!in) { *msg = "out of host memory"; return CELLECTOR_ENOMEM; }
@@ -193,8 +258,8 @@ cellector_status mtx_input_open(const char *alt_path, const char *ref_path, MtxI
     std::string third;
     bool ok_a = false, ok_r = false;
     {   // the two files are independent byte streams: inflate / map them concurrently
-        std::thread ta([&] { ok_a = load_bytes(alt_path, &in->fa); });
-        ok_r = load_bytes(ref_path, &in->fr);
+        std::thread ta([&] { ok_a = load_bytes(alt_path, &in->fa, gz_device); });
+        ok_r = load_bytes(ref_path, &in->fr, gz_device);
         ta.join();
     }
     if (!ok_a || !ok_r) {

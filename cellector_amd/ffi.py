@@ -57,6 +57,7 @@ SIGNATURES = {
     "cellector_format_mtx": (_i, [_vp, _i, _i, C.c_uint32, _u64, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "cellector_bgzf_compress": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "cellector_write_mtx_bgzf": (_i, [_vp, _cp, _cp, _i, C.c_uint32, _vp]),
+    "cellector_bgzf_decompress": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "cellector_exchange_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u64)]),
     "cellector_bind_exchange_buffer": (_i, [_vp, _i, _vp, _u64]),
     "cellector_em_begin": (_i, [_vp]),
@@ -533,6 +534,17 @@ class Cellector:
         out = np.empty(n_out.value, np.uint8)
         self._ck(self._lib.cellector_bgzf_compress(self.h, _p(src) if len(src) else None, len(src), _p(out), n_out.value, C.byref(n_out),
                                                    C.byref(n_blocks)))
+        return out.tobytes()
+
+    def bgzf_decompress(self, data):
+        """The text of a BGZF stream `data` (bytes), inflated on this ctx's GPU (cellector_bgzf_decompress): what gzip.decompress
+        returns, for bgzip's streams and this library's alike.  Works in any state of the ctx and leaves it as it is."""
+        src = np.frombuffer(bytes(data), np.uint8)
+        n_out, n_blocks = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.cellector_bgzf_decompress(self.h, _p(src) if len(src) else None, len(src), None, 0, C.byref(n_out), C.byref(n_blocks)))
+        out = np.empty(n_out.value, np.uint8)
+        self._ck(self._lib.cellector_bgzf_decompress(self.h, _p(src) if len(src) else None, len(src), _p(out) if n_out.value else _p(np.empty(1, np.uint8)),
+                                                     n_out.value, C.byref(n_out), C.byref(n_blocks)))
         return out.tobytes()
 
     # ---- merging a second staged matrix in (the other half of the reference's combiner)

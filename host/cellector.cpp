@@ -458,6 +458,7 @@ Ctx open_device(const Params &params, std::vector<int> &devices)
     }
     if (params.zscore) g.ck(cellector_set_option(g.c, "normalization", 1), "normalization");
     if (params.locus_expected) g.ck(cellector_set_option(g.c, "locus_moments", 1), "locus_expected");
+    if (params.gz_device) g.ck(cellector_set_option(g.c, "gz_device", 1), "gz_device");
     return g;
 }
 
@@ -491,6 +492,7 @@ void combine_second_dataset(const Run &run)
     const Ctx &g = run.g;
     Ctx second;
     if (cellector_create(&second.c, run.devices[0]) != CELLECTOR_OK) die(EXIT_PANIC, "cellector: no second context on the device");
+    if (params.gz_device) second.ck(cellector_set_option(second.c, "gz_device", 1), "gz_device");
     second.ck(ingest_pair(params, second.c, *params.mix_alt, *params.mix_ref), "load_cell_data (--mix_alt / --mix_ref)");
     cellector_dims_t ours, theirs;
     g.ck(cellector_dims(g.c, &ours), "dims");

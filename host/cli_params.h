@@ -70,6 +70,8 @@ struct Params {
     // (cellector_write_mtx): 0 = off, 1 + CELLECTOR_WRITE_ALIGNED / _SPARSE / _DEPTH
     int write_matrices = 0;
     bool write_matrices_gz = false;                    // ... as .mtx.gz: BGZF compressed on the GPU (cellector_write_mtx_bgzf)
+    // extension: a block-compressed (BGZF) -a / -r / --mix_alt / --mix_ref is inflated on the GPU, not on the host (option gz_device)
+    bool gz_device = false;
 };
 
 // ---- one row of the option table --------------------------------------------------------------------------------
@@ -401,6 +403,13 @@ inline const std::vector<Opt> &options()
             "                                                                       what bgzip writes) made on the GPU: zcat, gzip -t and -a / -r of\n"
             "                                                                       this program read them.  The stderr line gains the compressed\n"
             "                                                                       sizes (not in the reference)\n"),
+        Opt("gz_device", 0, Kind::WORD, &P::gz_device).as("--gz_device true").one_of("false|true", "expected true or false").paragraph(
+            "        --gz_device <true|false>                                           a block-compressed .gz (BGZF: bgzip's, --write_matrices_gz's)\n"
+            "                                                                       given as -a / -r or --mix_alt / --mix_ref goes to the GPU\n"
+            "                                                                       compressed and is inflated there, under every --matrix_pair; a\n"
+            "                                                                       plain file or a plain gzip is read as ever, and so is every file\n"
+            "                                                                       of a run on several GPUs.  No output changes (not in the\n"
+            "                                                                       reference; default false)\n"),
     };
     return table;
 }

@@ -105,6 +105,15 @@ cellector_status cellector_set_stream(cellector_ctx *ctx, void *hip_stream);
  * per launch; 2 or 4 forces the width — tests; read per launch, same results to the bit; other values: CELLECTOR_EINVAL),
  * "parse_window" (default 0: a text file of 1 GB or more is uploaded and tokenised in 256 MB windows, a smaller
  * one whole; a positive value forces windows of that many bytes — tests; lines of a windowed file may be 1 MB long),
+ * "gz_device" (default 0: a ".gz" input is inflated on the host before the ingest; 1: cellector_ingest_mtx / cellector_load_mtx
+ * and cellector_ingest_mtx_joined / cellector_load_mtx_joined on a single-device ctx leave a BGZF ".gz" compressed, upload the
+ * compressed bytes and inflate them on the device — cellector_amd/csrc/kernels_inflate.hip, whole or window by window as
+ * "parse_window" says.  Each file of the pair decides for itself: a plain file, a plain-gzip ".gz" and a file that
+ * CELLECTOR_NO_BGZF covers go the way they go with 0.  Every call stages exactly what it stages with 0; a member the device
+ * refuses hands the file back to the host reader, so a pair that fails with 0 fails with 1 with the same status (the error then
+ * names the file, the member and the reason; a file the host reader accepts after all is announced on stderr).  The split
+ * ingest of a multi-device ctx ignores the option.  Other values: CELLECTOR_EINVAL.  CELLECTOR_TIMING=1 prints one more line
+ * per file: members, bytes in and out, the inflate kernel's GPU time),
  * "write_window" (default 0: cellector_write_mtx and cellector_format_mtx take the staged entries through windows of 2^23
  * entries; a positive value forces windows of that many entries — tests; the bytes written do not depend on it),
  * "synth_continue_pct" (default 30: cellector_ingest_synthetic draws an entry's total as 1 + Geometric(0.7), vartrix-like
@@ -505,7 +514,20 @@ cellector_status cellector_format_mtx(cellector_ctx *ctx, int which, int mode, u
  *   (sizes of the TEXT); file_bytes_* are the sizes of the files, blocks_* their data blocks, stored_blocks those of both files
  *   that are stored.  Memory: the text buffers of cellector_write_mtx once more on the device (one aligned, one with the carry), the
  *   members' slots, and pinned buffers of the compressed worst case.  CELLECTOR_TIMING=1 prints cellector_write_mtx's line and
- *   one more: blocks, bytes in and out, the two compress kernels' GPU time. */
+ *   one more: blocks, bytes in and out, the two compress kernels' GPU time.
+ * cellector_bgzf_decompress: the mirror of cellector_bgzf_compress, with its scope and its two-call sizing: the n host bytes of a BGZF
+ *   stream as their text in host memory, inflated on the ctx's device (cellector_amd/csrc/inflate_format.h, kernels_inflate.hip: one
+ *   wave per member).  Any BGZF stream will do, bgzip's and this library's alike: gzip members that carry the 'BC' size field, whole,
+ *   of at most 64 KB of text each, stored, fixed and dynamic blocks, any number per member.  n_out receives the size of the text,
+ *   n_blocks the members (EOF member and other empty ones included); out == NULL: those only.  CELLECTOR_EINVAL when
+ *   capacity < n_out: the sizes are still returned and not a byte of out is written.  No byte of out outside [0, n_out) is ever
+ *   written.  CELLECTOR_EPARSE when `in` is no such stream (plain gzip, a member cut short, ISIZE above 65536).  A member is refused
+ *   exactly when zlib's inflate of its body fails or leaves input unused, or its length is not ISIZE, or its CRC-32 not the
+ *   trailer's: CELLECTOR_EIO, and cellector_last_error names the smallest refused member of the launch by its index in the stream
+ *   and says why; out may then hold the text of members before it.  The members go through the device in launches of 2048
+ *   (CELLECTOR_INFLATE_CHUNK in the environment: fewer, for tests), so device memory does not grow with n.  The ctx is only used
+ *   for its device and stream: nothing of its state changes.  CELLECTOR_TIMING=1 prints members, bytes in and out and the
+ *   kernel's GPU time. */
 typedef struct {
     cellector_write_summary text;                  /* what cellector_write_mtx reports for the same arguments */
     uint64_t file_bytes_first, file_bytes_second;  /* sizes of the two files, EOF member included              */
@@ -516,6 +538,8 @@ cellector_status cellector_bgzf_compress(cellector_ctx *ctx, const uint8_t *in, 
                                          uint64_t *n_out, uint64_t *n_blocks);
 cellector_status cellector_write_mtx_bgzf(cellector_ctx *ctx, const char *first_path, const char *second_path, int mode, uint32_t flags,
                                           cellector_write_bgzf_summary *summary /*may be NULL*/);
+cellector_status cellector_bgzf_decompress(cellector_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t capacity,
+                                           uint64_t *n_out, uint64_t *n_blocks);
 
 /* ---- exchange buffers (device memory, f64) --------------------------------------------------- */
 typedef enum {
