@@ -2,7 +2,7 @@
 // host, with the C library: the reference (Rust f64::exp / ln / log10) and the CPU oracle call these very functions, so the
 // cells option resolve_posteriors evaluates get their posterior, label and qual from here and not from the device's exp / log.
 //
-// No HIP in this file: cellector_ffi.cpp includes it, and tests/test_ref_log_posterior.py builds it as plain C++.  Scalar code
+// No HIP in this file: api_posteriors.cpp includes it, and tests/test_ref_log_posterior.py builds it as plain C++.  Scalar code
 // and explicit expression order only; compile without contraction (-ffp-contract=off; clang also gets the pragma).
 #pragma once
 #include <cmath>

@@ -7,7 +7,7 @@
 #include "ctx.h"
 
 // why a ctx cannot take part in a re-staging call, or null.  They work where one device holds every cell (the conditions of
-// locus_moments_scope, without its entry limit), between iterations, on a staged COO that is still there
+// whole_matrix_scope of api_checks.h, without its entry limit), between iterations, on a staged COO that is still there
 static const char *restage_scope(const cellector_ctx *c)
 {
     if (c->multi) return "is a multi-device ctx: its staged entries are sharded";

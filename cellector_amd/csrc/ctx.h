@@ -1,5 +1,5 @@
 // Internal state of a cellector_ctx (one shard on one GPU) and the launch wrappers that the
-// C-ABI layer (cellector_ffi.cpp, cellector_restage.cpp) calls.  Not part of the public ABI.
+// C-ABI layer (ctx_core.cpp, api_*.cpp, cellector_restage.cpp) calls.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/cellector_ffi.h"
-// Device memory goes through a small caching layer (cellector_ffi.cpp): mapping fresh VRAM costs ~30-50 ms per GB on
+// Device memory goes through a small caching layer (dev_cache.cpp): mapping fresh VRAM costs ~30-50 ms per GB on
 // this platform once the footprint is large, and the ingest allocates and frees tens of GB of temporaries several times
 // over (measured at 2e9 entries: 3.1 s of hipMalloc for 64 GB in the CSR build alone).  Freed blocks of >= 64 MB are kept
 // and handed out again to requests of at least half their size; dev_cache_trim() returns them to the driver.
@@ -435,6 +435,13 @@ inline void drop_built(cellector_ctx *c)
     static_cast<CtxBuilt &>(*c) = CtxBuilt();
 }
 
+// A reload (and cellector_destroy) drops what was built and what was staged, each group as a whole.
+static inline void drop_matrix(cellector_ctx *c)
+{
+    drop_built(c);
+    static_cast<CtxStaged &>(*c) = CtxStaged();
+}
+
 // what cellector_cell_log_likelihoods invalidates, for the calls that run beside the EM state on scratch of their own
 inline void invalidate_cell_ll_state(cellector_ctx *c)
 {
@@ -642,7 +649,7 @@ cellector_status launch_state_tallies(cellector_ctx *c, const uint8_t *host_flag
 // order statistics: exact values at SEL_T 0-based ranks of n keys
 cellector_status select_threshold(cellector_ctx *c, const double *keys, uint64_t n, double iqr_multiple);
 cellector_status ffi_order_statistics(cellector_ctx *c, const double *keys, uint64_t n_local, uint64_t n_total, double iqr_multiple,
-                                      double *out3);  // (cellector_ffi.cpp; a shard's slice of cellector_order_statistics)
+                                      double *out3);  // (api_em.cpp; a shard's slice of cellector_order_statistics)
 // ... over the keys of all shards of a sharded run (this shard holds n_local of the n_total), exchanged as digit histograms
 cellector_status select_threshold_sharded(cellector_ctx *c, const double *keys, uint64_t n_local, uint64_t n_total, double iqr_multiple);
 // option resolve_ties (kernels_resolve.hip): after select_threshold, before launch_flag
@@ -661,7 +668,9 @@ cellector_status ingest_pass1(cellector_ctx *c);
 // index made local, order kept; `keep` is caller scratch of all.n + 1 words
 cellector_status ingest_split_coo(cellector_ctx *c, const CooView &all, uint64_t cb, uint64_t ce, uint64_t *keep, StagedCoo *out);
 cellector_status ingest_cell_histogram(cellector_ctx *c, const uint32_t *d_cell, uint64_t n, uint64_t total_cells, std::vector<uint32_t> *out);
-// multi-device text ingest (cellector_ffi.cpp): stage the whole pair on one shard / hand a shard its routed entries
+// multi-device text ingest (api_ingest.cpp): stage the whole pair on one shard / hand a shard its routed entries
+// the EM state a load leaves, queued on the stream (api_em.cpp): cellector_ingest_finish and cellector_em_reset
+__attribute__((visibility("hidden"))) cellector_status em_state_clear(cellector_ctx *c);
 cellector_status ffi_stage_mtx_all_cells(cellector_ctx *c, const char *alt_path, const char *ref_path, cellector_ctx *helper);
 cellector_status ffi_adopt_staged(cellector_ctx *c, uint64_t total_loci, uint64_t total_cells, StagedCoo &&coo);
 cellector_status ingest_build(cellector_ctx *c, uint64_t min_alt, uint64_t min_ref);

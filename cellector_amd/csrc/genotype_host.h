@@ -3,7 +3,7 @@
 // (orc_vcf_genotype) call the C library's exp and log, so does this file: with ambient = 0.03 and threshold = 0.99 the result for
 // (a, r, A, R) is bit for bit the oracle's minority output for orc_vcf_genotype(a, r, A - a, R - r).
 //
-// No HIP in this file: cellector_ffi.cpp (cellector_class_genotypes) and host/cellector.cpp (the two VCF writers) include it, and
+// No HIP in this file: api_classes.cpp (cellector_class_genotypes) and host/cellector.cpp (the two VCF writers) include it, and
 // tests/test_genotype_reference.py builds it as plain C++.  Scalar code and explicit expression order only; compile without
 // contraction (-ffp-contract=off; clang also gets the pragma).
 //

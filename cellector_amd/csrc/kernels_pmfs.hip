@@ -97,7 +97,7 @@ static inline unsigned pm_grid(uint64_t n)
     return (unsigned)g;
 }
 
-// The call behind cellector_cell_pmfs on one device; the ids are validated (cellector_ffi.cpp).
+// The call behind cellector_cell_pmfs on one device; the ids are validated (api_em.cpp).
 cellector_status pmfs_run(cellector_ctx *c, const double *alpha, const double *beta, const uint8_t *mask, const uint32_t *cells,
                           uint64_t n_cells, uint64_t *rec_ptr, uint64_t capacity, uint32_t *locus_index, uint32_t *alt, uint32_t *ref,
                           double *log_pmf, double *expected_log_pmf, double *expected_log_variance)

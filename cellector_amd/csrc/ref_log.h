@@ -14,7 +14,7 @@
 //   log x = k ln2_hi + log c_i + r  +  (k ln2_lo + rounding terms)  +  r^2 (A0 + r A1 + r^2 A2 + r^3 A3 + r^4 A4).
 //
 // Origin: the algorithm and its constants are glibc's log (sysdeps/ieee754/dbl-64/e_log.c, e_log_data.c, LGPL-2.1+), which
-// glibc took from Arm's optimized-routines (math/log.c, log_data.c; MIT OR Apache-2.0 WITH LLVM-exception).  cellector_ffi.cpp
+// glibc took from Arm's optimized-routines (math/log.c, log_data.c; MIT OR Apache-2.0 WITH LLVM-exception).  api_options.cpp
 // compares ref_log with the host's log on a few arguments before it accepts option resolve_ties (ref_log_matches_host).
 //
 // Positive finite normal arguments only (the Lanczos sums and arguments of ln_gamma at alpha, beta >= 1 are).  Explicit fma

@@ -63,7 +63,7 @@ OUTPUTS = ("ll_minority", "ll_majority", "posterior", "doublet_posterior")
 
 # ---- alpha / beta and the priors -----------------------------------------------------------------------------------------------
 def priors(n_excluded, n_cells):
-    """(mf0, lp_min, lp_maj, lp_dbl) of main.rs:240-265 as the host computes them (cellector_ffi.cpp posterior_priors)"""
+    """(mf0, lp_min, lp_maj, lp_dbl) of main.rs:240-265 as the host computes them (api_posteriors.cpp posterior_priors)"""
     mf0 = (n_excluded + 1.0) / (n_cells + 1.0)
     mf = max(mf0, 0.01)
     with np.errstate(divide="ignore"):  # every cell excluded: log(1 - 1) = -inf

@@ -1,5 +1,5 @@
 """GPU: the posterior phase (calculate_posteriors; csrc/kernels_tiled.hip tiled_posteriors / k_posterior_finalize, csrc/kernels_em.hip
-k_ab_posterior / k_posterior, cellector_ffi.cpp posterior_priors) held to an exact reference, the doublet set included.
+k_ab_posterior / k_posterior, api_posteriors.cpp posterior_priors) held to an exact reference, the doublet set included.
 
 Every other test of posterior and doublet_posterior compares with the oracle at 1e-6 absolute, which a value wrong by a factor of
 e^5 passes in most cells (p ~ 1 or ~ 1e-30), and none looks at the doublet set's per-cell sum, which the ABI does not return.

@@ -104,7 +104,7 @@ def test_term_bound_upper_is_an_upper_bound():
 
 def test_ln_choose_bound_holds_for_the_planted_mid_totals():
     """ln C(n, a) = lf[n] - lf[a] - lf[n - a] with the table's values (ln of the factorial in double, host arithmetic as on the
-    device: csrc/cellector_ffi.cpp uploads the host libm's logs) against mpmath, for the planted pairs of totals 65..170"""
+    device: csrc/ctx_core.cpp uploads the host libm's logs) against mpmath, for the planted pairs of totals 65..170"""
     mp = tr._mp()
     for a, r in PLANTED_MID:
         n = a + r

@@ -27,7 +27,7 @@ static double g_lf[171];
 static bool g_lf_ready = false;
 static void lf_init()
 {
-    // the library's ln-factorial table: statrs' FCACHE running product, the host's log (cellector_ffi.cpp)
+    // the library's ln-factorial table: statrs' FCACHE running product, the host's log (ctx_core.cpp)
     if (g_lf_ready) return;
     double f = 1.0;
     g_lf[0] = std::log(1.0);

@@ -16,7 +16,7 @@ def _read(*parts):
 
 def _branch(key):
     """the branch of cellector_set_option's table that takes `key`"""
-    table = _read(CSRC, "cellector_ffi.cpp")
+    table = _read(CSRC, "api_options.cpp")
     m = re.search(r'else if \(!strcmp\(key, "' + key + r'"\)\) \{(.*?)\n    \}', table, flags=re.S)
     assert m, f'option "{key}" is not in the table'
     return m.group(1)
