@@ -1,7 +1,9 @@
 // The genotype models of the C ABI: donor calls from hard calls and from genotype probabilities and the donor fit
-// (kernels_donors.hip), ambient fractions (kernels_ambient.hip), donor pair fractions (kernels_pair_fraction.hip) and donor genotype
+// (kernels_donors.hip), donor panels (kernels_donor_panel.hip), ambient fractions (kernels_ambient.hip), donor pair fractions (kernels_pair_fraction.hip) and donor genotype
 // refinement (kernels_donor_genotypes.hip).  Every call opens with model_call_scope (api_checks.h), then its argument checks.
 #include "api_checks.h"
+
+#include <vector>
 
 // ---- donor demultiplexing: kernels_donors.hip -------------------------------------------------------------------
 cellector_status cellector_donor_default_params(cellector_donor_params *out)
@@ -63,8 +65,9 @@ cellector_status cellector_donor_tables(cellector_ctx *c, const uint8_t *gt, uin
     return donor_tables_run(c, gt, n_donors, &prm, mask, tab1, tab2, packed);
 }
 
-// the prior and the anchors of a cell call; lp [64]: the caller's prior, or zeros
-static cellector_status donor_prior_anchor_check(cellector_ctx *c, const char *what, uint32_t D, const double *log_prior, const uint8_t *anchor,
+// the prior and the anchors of a cell call (u8 anchors, or the panel's u16); lp [D]: the caller's prior, or zeros
+template <class Anchor>
+static cellector_status donor_prior_anchor_check(cellector_ctx *c, const char *what, uint32_t D, const double *log_prior, const Anchor *anchor,
                                                  double *lp)
 {
     bool any = !log_prior;
@@ -124,6 +127,52 @@ cellector_status cellector_match_donors(cellector_ctx *c, const uint8_t *labels,
     CHK(donor_args_check(c, "match_donors", gt, n_donors, &prm));
     SETDEV(c);
     return donor_match_run(c, labels, n_classes, gt, nullptr, n_donors, &prm, mask, ll, best, margin, cells);
+}
+
+// ---- donor panels: kernels_donor_panel.hip --------------------------------------------------------------------------
+// how many donors a panel holds, is gt there, are the parameters and the calls in range
+static cellector_status panel_args_check(cellector_ctx *c, const char *what, const uint8_t *gt, uint32_t D, const cellector_donor_params *p)
+{
+    if (D < 1 || D > 4096) return ctx_fail(c, CELLECTOR_EINVAL, "%s: %u donors, 1..4096 are supported", what, D);
+    if (!gt) return ctx_fail(c, CELLECTOR_EINVAL, "%s: null gt", what);
+    CHK(donor_params_check(c, what, p));
+    return gt_values_check(c, what, "donor", gt, D);
+}
+
+cellector_status cellector_donor_panel(cellector_ctx *c, const uint8_t *gt, uint32_t n_donors, uint32_t shortlist, const cellector_donor_params *p,
+                                       const double *log_prior, const uint16_t *anchor, const uint8_t *mask, uint16_t *cand, double *cand_ll,
+                                       double *cand_pair_ll, double *cand_posterior, double *cand_pair_posterior, double *doublet_posterior,
+                                       double *best_posterior, uint16_t *best, uint16_t *second, uint16_t *best_pair, uint16_t *anchor_out,
+                                       uint32_t *n_entries, uint8_t *status, uint64_t *donor_cells, cellector_donor_panel_summary *out,
+                                       double *ll, uint64_t *packed, double *tab1, double *tab2)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    const char *what = "donor_panel";
+    cellector_donor_params prm = params_or_default(cellector_donor_default_params, p);
+    CHK(model_call_scope(c, what));
+    CHK(panel_args_check(c, what, gt, n_donors, &prm));
+    const uint32_t D = n_donors;
+    if (shortlist < 1 || shortlist > 64) return ctx_fail(c, CELLECTOR_EINVAL, "%s: a shortlist of %u, 1..64 are supported", what, shortlist);
+    std::vector<double> lp(D, 0.0);
+    CHK(donor_prior_anchor_check(c, what, D, log_prior, anchor, lp.data()));
+    const double log_singlet = std::log(1.0 - prm.doublet_rate);
+    const double log_pair = D > 1 ? std::log(prm.doublet_rate / (double)(D - 1)) : 0.0;
+    SETDEV(c);
+    return donor_panel_run(c, gt, D, shortlist < D ? shortlist : D, &prm, lp.data(), anchor, mask, log_singlet, log_pair, cand, cand_ll,
+                           cand_pair_ll, cand_posterior, cand_pair_posterior, doublet_posterior, best_posterior, best, second, best_pair,
+                           anchor_out, n_entries, status, donor_cells, out, ll, packed, tab1, tab2);
+}
+
+cellector_status cellector_match_donors_panel(cellector_ctx *c, const uint8_t *labels, uint32_t n_classes, const uint8_t *gt, uint32_t n_donors,
+                                              const cellector_donor_params *p, const uint8_t *mask, double *ll, uint16_t *best, double *margin,
+                                              uint64_t *cells)
+{
+    if (!c) return CELLECTOR_EINVAL;
+    cellector_donor_params prm = params_or_default(cellector_donor_default_params, p);
+    CHK(class_call_check(c, "match_donors_panel", labels, n_classes, nullptr, nullptr));
+    CHK(panel_args_check(c, "match_donors_panel", gt, n_donors, &prm));
+    SETDEV(c);
+    return donor_panel_match_run(c, labels, n_classes, gt, n_donors, &prm, mask, ll, best, margin, cells);
 }
 
 // ---- the fit of the called hypothesis: k_donor_moments and k_donor_fit of kernels_donors.hip -------------------------------------

@@ -613,6 +613,18 @@ cellector_status donor_match_run(cellector_ctx *c, const uint8_t *labels, uint32
                                  uint64_t *cells);
 cellector_status donor_weights_run(cellector_ctx *c, const float *gp /*[D][total_loci][3]*/, uint32_t D, double *w, uint8_t *kind);
 cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *d_gt /*[D][total_loci]*/, uint64_t *d_packed /*[L][W]*/);
+cellector_status donor_tables_launch(cellector_ctx *c, const uint8_t *d_mask /*[L] or null*/, const cellector_donor_params *prm,
+                                     double2 *d_tab1 /*[L][4]*/, double2 *d_tab2 /*[L][16]*/);
+// donor panels (kernels_donor_panel.hip): the same calls for up to 4096 donors, a shortlist of M pairs per cell; indices are u16
+cellector_status donor_panel_run(cellector_ctx *c, const uint8_t *gt, uint32_t D, uint32_t M, const cellector_donor_params *prm,
+                                 const double *log_prior, const uint16_t *anchor, const uint8_t *mask, double log_singlet, double log_pair,
+                                 uint16_t *cand, double *cand_ll, double *cand_pair_ll, double *cand_posterior, double *cand_pair_posterior,
+                                 double *doublet_posterior, double *best_posterior, uint16_t *best, uint16_t *second, uint16_t *best_pair,
+                                 uint16_t *anchor_out, uint32_t *n_entries, uint8_t *status, uint64_t *donor_cells,
+                                 cellector_donor_panel_summary *out, double *ll, uint64_t *packed, double *tab1, double *tab2);
+cellector_status donor_panel_match_run(cellector_ctx *c, const uint8_t *labels, uint32_t K, const uint8_t *gt, uint32_t D,
+                                       const cellector_donor_params *prm, const uint8_t *mask, double *ll, uint16_t *best, double *margin,
+                                       uint64_t *cells);
 // the fit of the called hypothesis: the moment tables alone; the donor call into scratch, then the fit pass, the keys' order statistics
 // (select_threshold) and the flags
 cellector_status donor_moment_tables_run(cellector_ctx *c, const cellector_donor_params *prm, const uint8_t *mask, double *mom1, double *mom2);

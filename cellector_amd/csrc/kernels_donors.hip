@@ -667,10 +667,7 @@ struct DonorRun {
                                c->locus_ids.get(), gt.get(), packed.get());
         }
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_donor_tables, dim3(lane_grid(L * 16, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, L * 16,
-                           c->s_alt.get(), c->s_ref.get(), mask.get(), prm->err, prm->ambient, tab1.get(), tab2.get());
-        HIPCHK(c, hipGetLastError());
-        return CELLECTOR_OK;
+        return donor_tables_launch(c, mask.get(), prm, tab1.get(), tab2.get());
     }
 
     cellector_status pass(bool pair, bool anchor_given, const DonorTail &tail)
@@ -751,6 +748,16 @@ cellector_status donor_pack_launch(cellector_ctx *c, uint32_t D, const uint8_t *
     if (!c->L) return CELLECTOR_OK;
     hipLaunchKernelGGL(k_donor_pack, dim3(lane_grid(c->L * W, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, c->L * W, D, W,
                        c->total_loci, c->locus_ids.get(), d_gt, d_packed);
+    HIPCHK(c, hipGetLastError());
+    return CELLECTOR_OK;
+}
+
+// the tables alone, for the donor panel (kernels_donor_panel.hip): d_mask [L] or null, d_tab1 [L][4] and d_tab2 [L][16] on the device
+cellector_status donor_tables_launch(cellector_ctx *c, const uint8_t *d_mask, const cellector_donor_params *prm, double2 *d_tab1, double2 *d_tab2)
+{
+    if (!c->L) return CELLECTOR_OK;
+    hipLaunchKernelGGL(k_donor_tables, dim3(lane_grid(c->L * 16, LANE_THREADS, 0x7fffffffu)), dim3(LANE_THREADS), 0, c->stream, c->L * 16,
+                       c->s_alt.get(), c->s_ref.get(), d_mask, prm->err, prm->ambient, d_tab1, d_tab2);
     HIPCHK(c, hipGetLastError());
     return CELLECTOR_OK;
 }

@@ -15,6 +15,10 @@ The same calls from genotype probabilities (cellector_donor_weights / cellector_
 soft_weights, soft_singlet_sums, soft_pair_sums, soft_match_sums, posteriors_gp, match_gp, and read_donor_vcf_gp for the GP, GL or PL
 of a donor VCF.
 
+Donor panels (cellector_donor_panel / cellector_match_donors_panel; csrc/kernels_donor_panel.hip), up to 4096 donors with the pairs
+of a cell's anchor and a shortlist of its best singlets: panel_shortlist, panel_posteriors, panel_present, panel_match.  The shortlist,
+best, second and the sums are the device's exactly when fed the device's tables.
+
 The fit of the called hypothesis (cellector_donor_moment_tables / cellector_donor_fit): moment_tables, fit_sums, fit_calls, fit.  The
 four moment sums carry the device's bits when fed the device's tables; z passes through a sqrt and a division and agrees to 2 ulp;
 the hypothesis, the keys, their statistics and the flags follow exactly from the numbers they are given.
@@ -217,6 +221,106 @@ def _match_calls(ll, cells):
         margin = np.full(K, np.inf)
     live = np.asarray(cells) > 0
     return dict(ll=ll, best=np.where(live, best, NONE).astype(np.uint8), margin=np.where(live, margin, 0.0))
+
+
+# ---- donor panels ------------------------------------------------------------------------------------------------------------------
+# The twin of cellector_donor_panel / cellector_match_donors_panel (csrc/kernels_donor_panel.hip): up to 4096 donors, one softmax over
+# the D singlets and the pairs of the anchor with a shortlist of the cell's M best singlets.  Donor indices are uint16, 65535 = none.
+PANEL_NONE = 65535
+PANEL_MAX_DONORS = 4096
+
+
+def panel_shortlist(u, M):
+    """cand [cells, M] uint16: per cell the first M donors in (u descending, d ascending), listed in ascending d; a function of the
+    bits of u alone (a stable sort: equal values, -inf among them, keep their index order)"""
+    u = np.asarray(u, np.float64)
+    M = min(int(M), u.shape[1])
+    first = np.argsort(-u, axis=1, kind="stable")[:, :M]
+    return np.sort(first, axis=1).astype(np.uint16)
+
+
+def _panel_pair_sums(mat, tab2, g, anchor, cand):
+    """p [cells, M]: pair_sums' sum for the donors cand [cells, M] of each cell alone"""
+    tab2, g, anchor, cand = np.asarray(tab2, np.float64), np.asarray(g, np.int64), np.asarray(anchor, np.int64), np.asarray(cand, np.int64)
+    p = np.zeros((mat.N, cand.shape[1]))
+    for rows, ent in mat.rows.steps:
+        l = mat.r_lo[ent]
+        t = tab2[l[:, None], 4 * g[l, anchor[rows]][:, None] + g[l[:, None], cand[rows]]]
+        p[rows] = p[rows] + ((mat.r_al[ent, None] * t[:, :, 0]) + (mat.r_re[ent, None] * t[:, :, 1]))
+    return p
+
+
+def panel_posteriors(mat, gt_used, alt_total, ref_total, shortlist=8, log_prior=None, anchor=None, tab1=None, tab2=None, s=None, **params):
+    """cellector_donor_panel on host arrays.  mat: a cluster.Matrix over the used loci, built with the call's mask; gt_used [D, L] the
+    donors' genotypes at the used loci; tab1 / tab2: the device's tables, for the device's bits in ll, cand_ll and cand_pair_ll; None =
+    numpy's.  s: singlet_sums(mat, tab1, gt_used.T) where the caller has them already (they depend on neither the shortlist nor the
+    anchor).  Returns the dict of Cellector.donor_panel with ll (summary: a dict).  The chain adds its D + M terms one at a time, in
+    the model's order."""
+    prm = _params(params)
+    g = np.asarray(gt_used, np.uint8).T
+    n, D = mat.N, g.shape[1]
+    if not 1 <= D <= PANEL_MAX_DONORS:
+        raise ValueError(f"{D} donors, 1..{PANEL_MAX_DONORS} are supported")
+    if not 1 <= int(shortlist) <= 64:
+        raise ValueError(f"a shortlist of {shortlist}, 1..64 are supported")
+    M = min(int(shortlist), D)
+    if tab1 is None or tab2 is None:
+        tab1, tab2 = tables(alt_total, ref_total, prm["err"], prm["ambient"], mat.mask)
+    lp = np.zeros(D) if log_prior is None else np.asarray(log_prior, np.float64)
+    r = np.arange(n)
+    s = singlet_sums(mat, tab1, g) if s is None else np.asarray(s, np.float64)
+    u = s + lp[None, :]
+    best = _argmax_first(u)
+    second = _argmax_first(u, best).astype(np.uint16) if D > 1 else np.full(n, PANEL_NONE, np.uint16)
+    cand = panel_shortlist(u, M)
+    ci = cand.astype(np.int64)
+    a = best.astype(np.int64) if anchor is None else np.asarray(anchor, np.int64)
+    p = _panel_pair_sums(mat, tab2, g, a, ci)
+    rate = float(prm["doublet_rate"])
+    with np.errstate(divide="ignore"):
+        log_singlet = math.log(1.0 - rate)
+        log_pair = (math.log(rate / float(D - 1)) if rate > 0 else -math.inf) if D > 1 else 0.0
+    x = u + log_singlet
+    pair_ok = ci != a[:, None]
+    y = np.where(pair_ok, p + log_pair, -np.inf)
+    m = np.maximum(x.max(axis=1), y.max(axis=1))
+    ex, ey = np.exp(x - m[:, None]), np.exp(y - m[:, None])
+    den = np.zeros(n)
+    for d in range(D):
+        den = den + ex[:, d]
+    for j in range(M):
+        den = den + ey[:, j]
+    post, ppost = ex[r[:, None], ci] / den[:, None], ey / den[:, None]
+    dp = np.zeros(n)
+    for j in range(M):
+        dp = dp + ppost[:, j]
+    top = np.where(pair_ok, y, -np.inf).max(axis=1)
+    j_pair = np.argmax(pair_ok & (y == top[:, None]), axis=1)
+    best_pair = np.where(pair_ok.any(axis=1), ci[r, j_pair], PANEL_NONE).astype(np.uint16)
+    pb = ex[r, best] / den
+    entries = np.asarray(mat.entries)
+    status = np.where(entries < int(prm["min_loci"]), UNASSIGNED,
+                      np.where(dp > 0.5, DOUBLET, np.where(pb >= float(prm["posterior_threshold"]), SINGLET, AMBIGUOUS))).astype(np.uint8)
+    cells = np.bincount(best[status == SINGLET], minlength=D).astype(np.uint64)
+    return dict(cand=cand, cand_ll=s[r[:, None], ci], cand_pair_ll=p, cand_posterior=post, cand_pair_posterior=ppost, doublet_posterior=dp,
+                best_posterior=pb, best=best.astype(np.uint16), second=second, best_pair=best_pair, anchor=a.astype(np.uint16),
+                n_entries=entries.astype(np.uint32), status=status, donor_cells=cells, ll=s, tab1=tab1, tab2=tab2, x=x, y=y,
+                summary=dict(n_singlet=int((status == SINGLET).sum()), n_doublet=int((status == DOUBLET).sum()),
+                             n_ambiguous=int((status == AMBIGUOUS).sum()), n_unassigned=int((status == UNASSIGNED).sum()),
+                             n_present=int((cells > 0).sum())))
+
+
+def panel_present(result, min_cells=1):
+    """the ascending indices of the donors with at least min_cells status-0 cells in the dict of donor_panel / panel_posteriors: the
+    donors the 64-donor calls (donor_fit, estimate_ambient, ...) are then run on, as gt[panel_present(result)]"""
+    return np.flatnonzero(np.asarray(result["donor_cells"]) >= max(int(min_cells), 1))
+
+
+def panel_match(alt, ref, cells, gt_used, alt_total, ref_total, mask=None, tab1=None, **params):
+    """cellector_match_donors_panel on host arrays: match() with best as uint16, 65535 for a class without a cell"""
+    out = match(alt, ref, cells, gt_used, alt_total, ref_total, mask, tab1, **params)
+    out["best"] = np.where(np.asarray(cells) > 0, np.argmax(out["ll"], axis=1), PANEL_NONE).astype(np.uint16)
+    return out
 
 
 # ---- the fit of the called hypothesis ----------------------------------------------------------------------------------------------

@@ -100,6 +100,8 @@ SIGNATURES = {
     "cellector_donor_tables": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "cellector_donor_posteriors": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 14),
     "cellector_match_donors": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
+    "cellector_donor_panel": (_i, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp] + [_vp] * 19),
+    "cellector_match_donors_panel": (_i, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp] + [_vp] * 4),
     "cellector_donor_fit_default_params": (_i, [_vp]),
     "cellector_donor_moment_tables": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cellector_donor_fit": (_i, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp] + [_vp] * 14),
@@ -176,6 +178,10 @@ class DonorParams(C.Structure):
 
 class DonorSummary(C.Structure):
     _fields_ = [("n_singlet", _u64), ("n_doublet", _u64), ("n_ambiguous", _u64), ("n_unassigned", _u64), ("donor_cells", _u64 * 64)]
+
+
+class DonorPanelSummary(C.Structure):
+    _fields_ = [("n_singlet", _u64), ("n_doublet", _u64), ("n_ambiguous", _u64), ("n_unassigned", _u64), ("n_present", _u64)]
 
 
 class DonorFitParams(C.Structure):
@@ -1101,6 +1107,57 @@ class Cellector:
             _p(out["n_entries"]), _p(out["status"]), _p(out["anchor"]), C.byref(s), _p(out.get("tab1")), _p(out.get("tab2"))))
         out["summary"] = s
         return out
+
+    # ---- donor panels: up to 4096 donors, pairs of the anchor with a shortlist; donors.py (panel_posteriors) is the twin
+    def donor_panel(self, gt, shortlist=8, log_prior=None, anchor=None, mask=None, ll=False, tables=False, **params):
+        """Every cell against a panel of D <= 4096 genotyped donors and the doublets of its anchor donor with the M = min(shortlist, D)
+        best singlets of the cell (cellector_donor_panel).  Returns a dict: cand [cells, M] uint16 (the shortlist in ascending donor
+        index), cand_ll, cand_pair_ll, cand_posterior, cand_pair_posterior [cells, M], doublet_posterior, best_posterior, best, second,
+        best_pair (uint16, 65535 = none), anchor, n_entries, status [cells], donor_cells [D] (status-0 cells per best donor), summary
+        (DonorPanelSummary) and, with ll, ll [cells, D]; with tables, packed [L, W], tab1 and tab2."""
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        shortlist = int(shortlist)
+        Da, M = min(max(D, 1), 4096), min(max(shortlist, 1), 64, max(D, 1))
+        n, L = (self.n_local if self.dims().total_cells else 0), self.dims().loci_used
+        log_prior = None if log_prior is None else np.ascontiguousarray(log_prior, np.float64)
+        if log_prior is not None and log_prior.shape != (D,):
+            raise ValueError(f"log_prior: {D} values expected, got shape {log_prior.shape}")
+        anchor = None if anchor is None else np.ascontiguousarray(anchor, np.uint16)
+        if anchor is not None and anchor.shape != (n,):
+            raise ValueError(f"anchor: {n} values expected, got shape {anchor.shape}")
+        out = dict(cand=np.zeros((n, M), np.uint16))
+        for k in ("cand_ll", "cand_pair_ll", "cand_posterior", "cand_pair_posterior"):
+            out[k] = np.zeros((n, M), np.float64)
+        out["doublet_posterior"], out["best_posterior"] = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        for k in ("best", "second", "best_pair", "anchor"):
+            out[k] = np.zeros(n, np.uint16)
+        out["n_entries"], out["status"] = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        out["donor_cells"] = np.zeros(Da, np.uint64)
+        if ll:
+            out["ll"] = np.zeros((n, Da), np.float64)
+        if tables:
+            out["packed"] = np.zeros((L, (Da + 31) // 32), np.uint64)
+            out["tab1"], out["tab2"] = np.zeros((L, 4, 2), np.float64), np.zeros((L, 16, 2), np.float64)
+        s = DonorPanelSummary()
+        self._ck(self._lib.cellector_donor_panel(
+            self.h, _p(gt), D, max(shortlist, 0), C.byref(p), _p(log_prior), _p(anchor), _p(mask), _p(out["cand"]), _p(out["cand_ll"]),
+            _p(out["cand_pair_ll"]), _p(out["cand_posterior"]), _p(out["cand_pair_posterior"]), _p(out["doublet_posterior"]),
+            _p(out["best_posterior"]), _p(out["best"]), _p(out["second"]), _p(out["best_pair"]), _p(out["anchor"]), _p(out["n_entries"]),
+            _p(out["status"]), _p(out["donor_cells"]), C.byref(s), _p(out.get("ll")), _p(out.get("packed")), _p(out.get("tab1")),
+            _p(out.get("tab2"))))
+        out["summary"] = s
+        return out
+
+    def match_donors_panel(self, labels, n_classes, gt, mask=None, **params):
+        """match_donors for a panel of D <= 4096 donors (cellector_match_donors_panel): the same dict, best uint16 (65535: a class
+        without a cell)"""
+        labels, K, _, _, _ = self._class_args(labels, n_classes)
+        gt, D, mask, p = self._donor_args(gt, mask, params)
+        Ka, Da = min(K, 16), min(max(D, 1), 4096)
+        ll, best, margin, cells = np.zeros((Ka, Da), np.float64), np.zeros(Ka, np.uint16), np.zeros(Ka, np.float64), np.zeros(Ka, np.uint64)
+        self._ck(self._lib.cellector_match_donors_panel(self.h, _p(labels), K, _p(gt), D, C.byref(p), _p(mask), _p(ll), _p(best), _p(margin),
+                                                        _p(cells)))
+        return dict(ll=ll, best=best, margin=margin, cells=cells)
 
     # ---- the fit of the called hypothesis: cells no genotyped donor explains; donors.py (moment_tables, fit_sums, fit) is the twin
     def donor_fit_default_params(self):

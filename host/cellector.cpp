@@ -1172,7 +1172,7 @@ struct Donors {
     uint32_t D = 0;
     cellector_donor_params dp;
     const uint8_t *gt_codes() const { return soft ? hard_gt.data() : dg.gt.data(); }
-    const std::string &name(uint8_t d) const { return dg.names[d]; }
+    const std::string &name(uint32_t d) const { return dg.names[d]; }
 };
 // --donor_field: call(entry point, the donors' calls as that entry takes them, its name) with the hard pair or the soft one
 template <class Hard, class Soft, class F>
@@ -1196,7 +1196,10 @@ Donors read_donors(const Run &run)
         while (din.next(line)) d.dg.add_donor_line(line);
     }
     d.D = (uint32_t)d.dg.names.size();
-    if (d.D < 1 || d.D > 64) die(1, "error: --donors " + *params.donors + ": " + std::to_string(d.dg.names.size()) + " sample columns, 1..64 donors are supported");
+    if (params.donor_panel && (d.D < 1 || d.D > 4096))
+        die(1, "error: --donors " + *params.donors + ": " + std::to_string(d.dg.names.size()) + " sample columns, --donor_panel takes 1..4096 donors");
+    if (!params.donor_panel && (d.D < 1 || d.D > 64))
+        die(1, "error: --donors " + *params.donors + ": " + std::to_string(d.dg.names.size()) + " sample columns, 1..64 donors are supported");
     if (d.dg.total_loci != run.dims.total_loci)
         die(1, "error: --donors: --vcf " + *params.vcf + " has " + std::to_string(d.dg.total_loci) + " records but the matrix has " +
                    std::to_string(run.dims.total_loci) + " loci");
@@ -1485,12 +1488,116 @@ void write_cluster_donors(const Run &run, const Donors &d, const ClassLabels &cl
     run.lap("cellector_cluster_donors.tsv");
 }
 
+// --donor_panel: every cell against the whole panel (cellector_donor_panel), the panel's two files and, with classes in force, the
+// classes named by panel donor.  The donors with --donor_panel_min_cells status-0 cells replace the panel in d, in panel order; false
+// where the donor pass cannot follow (none or more than 64 present).
+bool run_donor_panel(const Run &run, Donors &d, const ClassLabels &classes)
+{
+    const Params &params = run.params;
+    const uint64_t N = run.N, TL = run.dims.total_loci;
+    const uint32_t D = d.D, asked = (uint32_t)params.donor_panel, M = std::min(asked, D);
+    const CellNames &barcodes = run.in.cells;
+    std::vector<uint16_t> cand(N * M), best(N), second(N), pair(N), anchor(N);
+    std::vector<double> cll(N * M), cpost(N * M), cppost(N * M), dbl(N), bpost(N);
+    std::vector<uint32_t> n(N);
+    std::vector<uint8_t> status(N);
+    std::vector<uint64_t> cells(D), dcells(D, 0);
+    cellector_donor_panel_summary ps;
+    run.g.ck(cellector_donor_panel(run.g.c, d.dg.gt.data(), D, asked, &d.dp, nullptr, nullptr, nullptr, cand.data(), cll.data(), nullptr,
+                                   cpost.data(), cppost.data(), dbl.data(), bpost.data(), best.data(), second.data(), pair.data(),
+                                   anchor.data(), n.data(), status.data(), cells.data(), &ps, nullptr, nullptr, nullptr, nullptr),
+             "donor_panel");
+    uint64_t n_present = 0;
+    for (uint32_t k = 0; k < D; k++) n_present += cells[k] >= params.donor_panel_min_cells;
+    fprintf(stderr, "donor_panel: %u donors, shortlist %u, singlet=%llu doublet=%llu ambiguous=%llu unassigned=%llu present=%llu\n", D, asked,
+            (unsigned long long)ps.n_singlet, (unsigned long long)ps.n_doublet, (unsigned long long)ps.n_ambiguous,
+            (unsigned long long)ps.n_unassigned, (unsigned long long)n_present);
+    std::string head = "barcode\tstatus\tdonor\tsecond_donor\tbest_pair\tposterior\tpair_posterior\tdoublet_posterior\tn_loci";
+    for (uint32_t j = 0; j < asked; j++) {
+        const std::string t = std::to_string(j);
+        head += "\tcandidate_" + t + "\tlog_likelihood_" + t + "\tposterior_" + t;
+    }
+    head += '\n';
+    write_tsv(run.out("cellector_donor_panel.tsv"), head, N, [&](uint64_t c, std::string &o) {
+        o += barcodes[c]; o += '\t'; o += donor_status(status[c]); o += '\t';
+        o += d.name(best[c]); o += '\t';
+        o += second[c] == 65535 ? "NA" : d.name(second[c]).c_str(); o += '\t';
+        double pp = 0.0;
+        if (pair[c] == 65535) o += "NA";
+        else {
+            o += d.name(anchor[c]); o += '+'; o += d.name(pair[c]);
+            for (uint32_t j = 0; j < M; j++)
+                if (cand[c * M + j] == pair[c]) pp = cppost[c * M + j];
+        }
+        o += '\t'; put(o, bpost[c]);
+        o += '\t'; put(o, pp);
+        o += '\t'; put(o, dbl[c]);
+        o += '\t'; put(o, (uint64_t)n[c]);
+        for (uint32_t j = 0; j < asked; j++) {
+            if (j >= M) { o += "\tNA\tNA\tNA"; continue; }
+            o += '\t'; o += d.name(cand[c * M + j]); o += '\t'; put(o, cll[c * M + j]); o += '\t'; put(o, cpost[c * M + j]);
+        }
+        o += '\n';
+    });
+    for (uint64_t c = 0; c < N; c++)
+        if (status[c] == 1 && pair[c] != 65535) { dcells[anchor[c]]++; dcells[pair[c]]++; }
+    {
+        FILE *f = create(run.out("cellector_donor_panel_donors.tsv"));
+        std::string o = "donor\tsinglet_cells\tdoublet_cells\tpresent\n";
+        for (uint32_t k = 0; k < D; k++) {
+            o += d.name(k); o += '\t'; put(o, cells[k]); o += '\t'; put(o, dcells[k]);
+            o += cells[k] >= params.donor_panel_min_cells ? "\t1\n" : "\t0\n";
+        }
+        fputs(o.c_str(), f);
+        fclose(f);
+    }
+    run.lap("cellector_donor_panel.tsv");
+    if (params.classes || params.cluster) {
+        const uint32_t K = (uint32_t)classes.names.size();
+        std::vector<uint8_t> lab(classes.label.begin(), classes.label.begin() + N);
+        std::vector<uint16_t> mbest(K);
+        std::vector<double> margin(K);
+        std::vector<uint64_t> mcells(K);
+        run.g.ck(cellector_match_donors_panel(run.g.c, lab.data(), K, d.dg.gt.data(), D, &d.dp, nullptr, nullptr, mbest.data(), margin.data(),
+                                              mcells.data()), "match_donors_panel");
+        FILE *fm = create(run.out("cellector_cluster_panel_donors.tsv"));
+        std::string o = "class\tcells\tdonor\tmargin\n";
+        for (uint32_t k = 0; k < K; k++) {
+            o += classes.names[k]; o += '\t'; put(o, mcells[k]); o += '\t'; o += mbest[k] == 65535 ? "NA" : d.name(mbest[k]).c_str();
+            o += '\t'; put(o, margin[k]); o += '\n';
+        }
+        fputs(o.c_str(), fm);
+        fclose(fm);
+        run.lap("cellector_cluster_panel_donors.tsv");
+    }
+    if (n_present < 1 || n_present > 64) {
+        fprintf(stderr, "donor_panel: %llu donors are present, the donor pass takes 1..64: skipped\n", (unsigned long long)n_present);
+        if (params.estimate_ambient || params.donor_fit || params.doublet_fraction || params.donor_genotypes)
+            die(1, "error: --donor_panel found " + std::to_string(n_present) + " donors present; --estimate_ambient, --donor_fit, "
+                   "--doublet_fraction and --donor_genotypes need the donor pass over 1..64 of them");
+        return false;
+    }
+    // the present donors, in panel order, as if the VCF held only their columns
+    std::vector<std::string> names;
+    std::vector<uint8_t> gt;
+    for (uint32_t k = 0; k < D; k++) {
+        if (cells[k] < params.donor_panel_min_cells) continue;
+        names.push_back(d.dg.names[k]);
+        gt.insert(gt.end(), d.dg.gt.begin() + (uint64_t)k * TL, d.dg.gt.begin() + (uint64_t)(k + 1) * TL);
+    }
+    d.dg.names = std::move(names);
+    d.dg.gt = std::move(gt);
+    d.D = (uint32_t)n_present;
+    return true;
+}
+
 // --donors: every cell against the genotyped donors of the pool, and the classes in force (--classes / --cluster, refined if asked)
 // named by donor
 void run_donors(const Run &run, const ClassLabels &classes)
 {
     const Params &params = run.params;
     Donors d = read_donors(run);
+    if (params.donor_panel && !run_donor_panel(run, d, classes)) return;
     DonorCalls calls = donor_pass(run, d);
     if (params.estimate_ambient) {
         const double rho = write_ambient(run, d, calls);

@@ -52,6 +52,10 @@ struct Params {
     // extension: donor demultiplexing after the ordinary run (cellector_donor_posteriors / cellector_match_donors; one GPU)
     std::optional<std::string> donors;                 // the donors' genotypes, a VCF with one sample column per donor (needs --vcf)
     double donor_error = 0.01, donor_ambient = 0.03, donor_doublet_rate = 0.1;
+    // extension: a panel of up to 4096 genotyped donors in front of the donor pass (cellector_donor_panel); the donors it finds
+    // present are the donors of the pass
+    uint64_t donor_panel = 0;                          // 0 = off; else the shortlist: the pairs of a cell are its anchor with its M best singlets
+    uint64_t donor_panel_min_cells = 1;                // a donor is present with this many status-0 cells
     // extension: the pool's ambient fraction measured from the donor pass' singlets (cellector_estimate_ambient)
     std::string donor_field = "GT";                    // GT: hard calls; GP, GL, PL: the donors' genotype weights (cellector_donor_posteriors_gp)
     int estimate_ambient = 0;                          // 0 = off, 1 = true: report it, 2 = apply: and score the donors again with it
@@ -311,6 +315,25 @@ inline const std::vector<Opt> &options()
             "                                                                       GT, then to no call.  --estimate_ambient keeps scoring hard calls,\n"
             "                                                                       the most probable genotype of every row (the soft ambient profile\n"
             "                                                                       is not implemented).  With GT no output changes\n"),
+        Opt("donor_panel", 0, Kind::USIZE, &P::donor_panel).as("--donor_panel <M>").within({1.0, 64.0, false, false}, "expected a number in 1..64")
+            .requires_option("donors").paragraph(
+            "        --donor_panel <M>                                                  with --donors: the VCF is a PANEL of 1..4096 genotyped donors\n"
+            "                                                                       (hard calls: not with --donor_field GP|GL|PL).  Every cell is\n"
+            "                                                                       scored against all of them and the doublets of its best donor\n"
+            "                                                                       with its M best ones (1..64) in one softmax.  Writes\n"
+            "                                                                       cellector_donor_panel.tsv (barcode, status, donor, second_donor,\n"
+            "                                                                       best_pair, the three posteriors, n_loci and per shortlist slot\n"
+            "                                                                       candidate_j, log_likelihood_j, posterior_j) and\n"
+            "                                                                       cellector_donor_panel_donors.tsv (donor, singlet_cells,\n"
+            "                                                                       doublet_cells, present), with --classes or --cluster also\n"
+            "                                                                       cellector_cluster_panel_donors.tsv.  The donors that are present\n"
+            "                                                                       then are the donors of the ordinary donor pass, as if the VCF\n"
+            "                                                                       held only their columns; with none or more than 64 present\n"
+            "                                                                       that pass is skipped (not in the reference)\n"),
+        Opt("donor_panel_min_cells", 0, Kind::USIZE, &P::donor_panel_min_cells).as("--donor_panel_min_cells <n>")
+            .within({1.0, 1e18, false, false}, "expected a number >= 1").requires_option("donor_panel").paragraph(
+            "        --donor_panel_min_cells <n>                                        with --donor_panel: a donor is present with at least n cells\n"
+            "                                                                       called singlets of it (default 1)\n"),
         Opt("estimate_ambient", 0, Kind::WORD, &P::estimate_ambient).as("--estimate_ambient <true|apply>")
             .one_of("false|true|apply", "expected true, apply or false").requires_option("donors").paragraph(
             "        --estimate_ambient <true|apply>                                    with --donors: measure the pool's share of ambient reads from\n"
@@ -551,6 +574,8 @@ inline Params load_params(int argc, char **argv)
     for (const char *flag : {"class_doublets", "class_genotypes", "refine_classes"})
         if (in_force(*find_option(flag)) && !p.classes && !p.cluster)
             die(1, std::string("error: The argument '") + find_option(flag)->shown + "' requires '--classes <file>'");
+    if (p.donor_panel && p.donor_field != "GT")
+        die(1, "error: The argument '--donor_panel <M>' cannot be used with '--donor_field " + p.donor_field + "': a panel is scored from hard calls");
     if (p.estimate_ambient == 2 && got.count("donor_ambient"))
         die(1, "error: The argument '--estimate_ambient apply' cannot be used with '--donor_ambient <a>'");
     if (p.mix_alt || p.mix_ref || p.mix_barcodes || p.mix_cells)

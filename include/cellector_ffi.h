@@ -1100,6 +1100,65 @@ cellector_status cellector_match_donors(cellector_ctx *ctx, const uint8_t *label
                                         double *ll /*[K][D]*/, uint8_t *best /*[K]*/, double *margin /*[K]*/,
                                         uint64_t *cells /*[K]*/); /* any output may be NULL */
 
+/* ---- donor panels: cells and classes against up to 4096 genotyped donors ---------------------------------------------
+ * The donor calls above stop at 64 donors.  A cell village of 100+ lines holds more, and so does the question "which of the 500
+ * genotyped individuals of this facility are in this pool".  These calls score every cell against all D donors of a panel in one pass
+ * and one softmax; the pairs are those of the anchor with a SHORTLIST of the cell's M best singlets.  Everything not stated here is
+ * the donor model above, steps 1 - 8, operation for operation, f64 without contraction.
+ *   D donors, 1 <= D <= 4096; gt [D][total_loci] u8 coded as there.  shortlist, 1 <= shortlist <= 64; M = min(shortlist, D).  Donor
+ *   indices are uint16_t; 65535 means "none" where the 64-donor calls say 255.
+ *   1 - 3 packing, theta, tab1, tab2: unchanged; the tables are cellector_donor_tables' bits; packed [L][W] has W = ceil(D / 32) up to
+ *     128.  The u8 genotypes are uploaded and packed in slabs of 256 donors: they never sit on the device whole.
+ *   4 singlets: s_cd for all D donors, the same strictly sequential sum; u_d = s_cd + log_prior[d] (NULL: + 0.0); best and second by the
+ *     same rule (second 65535 with D = 1).  The bits of s_cd depend on donor d's genotypes alone: column d of ll equals column j of
+ *     cellector_donor_posteriors' ll on any subset S of <= 64 donors with S[j] = d, and the ll of cellector_match_donors_panel equals
+ *     cellector_match_donors' likewise.
+ *   4b the shortlist: the donors ordered by (u_d descending, d ascending); the first M; cand[c][0..M) lists them in ascending d.  The
+ *     selection is a function of the bits of u alone.  cand_ll[c][j] = s_{c, cand[c][j]}.
+ *   5 anchor: a_c = anchor[c] if given (< D), else best.  A given anchor need not be in the shortlist.
+ *   6 pairs: p_cd as there, for d in cand[c] only: cand_pair_ll[c][j].  The slot where cand == a_c carries the bits of s_{c, a_c} and
+ *     takes no part in the chain.
+ *   7 chain: one softmax over D + (the shortlisted donors other than a_c) hypotheses: the D singlets x_d = u_d + log_singlet in
+ *     ascending d, then the pairs (a_c, d), d over cand[c] ascending, d != a_c, y_d = p_cd + log_pair.  log_singlet = log(1.0 -
+ *     doublet_rate), log_pair = log(doublet_rate / (double)(D - 1)) with the host's log (D = 1: no pairs): the prior of a pair does not
+ *     depend on M.  PAIRS OUTSIDE THE SHORTLIST ARE NOT EVALUATED AND ARE NOT IN den: the posteriors are those of the model that holds
+ *     only the listed hypotheses.  m = the maximum of all terms; den = sum exp(t - m) in that order from 0.0; cand_posterior[c][j] =
+ *     exp(x_d - m) / den and cand_pair_posterior[c][j] = exp(y_d - m) / den at d = cand[c][j], 0 at d = a_c; best_posterior =
+ *     exp(x_best - m) / den; doublet_posterior = the sum of the pair posteriors in ascending d from 0.0; best_pair = the d of the
+ *     largest y_d, the smallest on ties, 65535 when the chain has no pair term (D = 1, or M = 1 and the one shortlisted donor is a_c).
+ *   8 status: unchanged, from doublet_posterior and best_posterior.  The summary counts the four; donor_cells[d] = the status-0 cells
+ *     whose best is d; n_present = the donors with at least one.
+ *   With D <= 64 and shortlist >= D, cand[c] is 0 ... D - 1 and every common output equals cellector_donor_posteriors' bit for bit
+ *   (indices widened, 255 <-> 65535).
+ *   cellector_match_donors_panel: cellector_match_donors for D <= 4096; best is uint16_t, 65535 for a class without a cell.
+ * Scope and refusals as cellector_donor_posteriors, with D outside 1..4096, shortlist outside 1..64 and an anchor >= D refused with
+ * CELLECTOR_EINVAL and a message, nothing written or launched.  The soft calls (GP / GL / PL), cellector_donor_fit, the ambient, pair
+ * fraction and genotype refinement calls stay at D <= 64: a panel call names the donors that are present (donor_cells), and those calls
+ * take that subset.  All device scratch is allocated before anything is launched (min(D, 256) bytes per locus of the matrix, 8 W + 321
+ * B per used locus, 8 D B, 34 M + 31 B per cell, and 8 D B per cell more only where ll is asked for; match: 16 K B per used locus and
+ * 8 K D B): on CELLECTOR_ENOMEM the ctx is as it was.  The calls never touch the EM state and overwrite nothing of the ctx; they
+ * invalidate the caches cellector_cell_log_likelihoods invalidates. */
+typedef struct {
+    uint64_t n_singlet, n_doublet, n_ambiguous, n_unassigned;  /* status 0, 1, 2, 255                            */
+    uint64_t n_present;          /* donors with at least one status-0 cell                                      */
+} cellector_donor_panel_summary;
+cellector_status cellector_donor_panel(cellector_ctx *ctx, const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors, uint32_t shortlist,
+                                       const cellector_donor_params *p /*NULL = defaults*/, const double *log_prior /*[D] or NULL*/,
+                                       const uint16_t *anchor /*[cells] or NULL*/, const uint8_t *mask /*[L] or NULL*/,
+                                       uint16_t *cand /*[cells][M]*/, double *cand_ll /*[cells][M]*/, double *cand_pair_ll /*[cells][M]*/,
+                                       double *cand_posterior /*[cells][M]*/, double *cand_pair_posterior /*[cells][M]*/,
+                                       double *doublet_posterior /*[cells]*/, double *best_posterior /*[cells]*/, uint16_t *best /*[cells]*/,
+                                       uint16_t *second /*[cells]*/, uint16_t *best_pair /*[cells]*/, uint16_t *anchor_out /*[cells]*/,
+                                       uint32_t *n_entries /*[cells]*/, uint8_t *status /*[cells]*/,
+                                       uint64_t *donor_cells /*[D]: status-0 cells per best donor*/, cellector_donor_panel_summary *out,
+                                       double *ll /*[cells][D] or NULL*/, uint64_t *packed /*[L][W] or NULL*/, double *tab1 /*[L][4][2]*/,
+                                       double *tab2 /*[L][16][2]*/); /* any output may be NULL */
+cellector_status cellector_match_donors_panel(cellector_ctx *ctx, const uint8_t *labels /*[cells]*/, uint32_t n_classes,
+                                              const uint8_t *gt /*[D][total_loci]*/, uint32_t n_donors,
+                                              const cellector_donor_params *p /*NULL = defaults*/, const uint8_t *mask /*[L] or NULL*/,
+                                              double *ll /*[K][D]*/, uint16_t *best /*[K]*/, double *margin /*[K]*/,
+                                              uint64_t *cells /*[K]*/); /* any output may be NULL */
+
 /* ---- donor calls from genotype probabilities: GP / GL / PL in place of a hard call --------------------------------
  * An imputed array or a low-coverage genome gives a donor three weights per locus, and often the heaviest holds little more than
  * half of the mass.  These calls are the donor calls above with a mixture over a donor's three genotypes in every entry's term.
